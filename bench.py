@@ -2,6 +2,7 @@
 """bench.py -- collocation-points/sec of the PINN hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|f64] [--nf-total M | --nf-per-gpu M]
+                    [--full] [--dump-outputs DIR]
 
 A *step* is one optimiser iteration = one full-batch pass of the hot path (Taylor-mode forward over every
 collocation point, PDE residual, loss reduction, flat gradient, all-reduce when N > 1, optimiser update).
@@ -10,15 +11,23 @@ inference, 8x20 tanh MLP, N_u = 100, N_f = 10000 IN TOTAL (at N > 1 the 10000 po
 strong scaling, honest for a 40-microsecond step), Adam then L-BFGS in the reference's 1:2 proportion (100:200
 default epochs, 1d-burgers/inf_cont_burgers.py:35-41), canonical glorot init, inputs resident in HBM.
 
-Timing: W untimed warm-up steps; then blocks of EXACTLY K steps, each bracketed by barrier + stream sync on both sides
-(barrier + sync before, sync + MAX-over-ranks reduction after) ; blocks are repeated (same initial state each time, reset outside the bracket) until
->= 3 s have been timed per leg (PINN_BENCH_MIN_TIMED_MS), and the MEDIAN block is reported -- a single 20-step block
-is 1 ms, below the noise of a fresh box, and 50 ms per leg (rounds 1-2) was too short for the driver's 5-second
-GPU-busy sampler to corroborate.  `value` = N_f_total x K / median block.  The kernel duration behind `roofline` is measured live in a
-separate pass of the same steps with HIP events attached to the launches themselves (>= 32 samples).
+Timing of the headline: W untimed warm-up steps, then ONE block of exactly K steps (K // 3 Adam + the rest L-BFGS),
+bracketed by barrier + stream sync on both sides (barrier + sync before, sync + MAX-over-ranks reduction after).
+`ms_per_step` = block / K, `value` = N_f_total x K / block: --steps sets the number of timed steps, so a caller that
+wants a longer window asks for more steps.
+
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR), one JSON line.
+--dump-outputs DIR writes what the timed steps computed, after the last one: weights.npy (the trained flat float64
+weight vector), lbfgs_losses.npy (the loss log L-BFGS returned), loss.npy / loss_terms.npy / grad.npy (loss+gradient
+at those weights) -- same arguments, same seeded inputs, so two builds can be compared output for output.
+
+--full adds everything else, as before: the kernel duration behind `roofline` (a separate pass of the same steps
+with HIP events attached to the launches themselves, >= 32 samples), and the legs below.  Each of those legs is
+timed in blocks of exactly K steps, repeated (same initial state each time, reset outside the bracket) until >= 3 s
+have been timed per leg (PINN_BENCH_MIN_TIMED_MS), and reports the MEDIAN block.
 
 One JSON line on rank 0.  The headline is float64 -- the reference's arithmetic (utils/neuralnetwork.py:24-26) and
-the product's default (hp["dtype"]); --dtype f32 swaps the roles.  Beside it the line carries
+the product's default (hp["dtype"]); --dtype f32 swaps the roles.  Beside it the line carries, under --full,
   float32_leg   the same K steps on the float32 kernels (the FP32 mode north_star sanctions), with its own roofline
                 (float64_leg under --dtype f32)
   cfg5_leg      BASELINE configs[4]: N_f = 10^6 in total, sharded over the N ranks (125k per GPU at N = 8); at N = 1
@@ -137,8 +146,9 @@ def reset(eng, w0, adam=BURGERS_ADAM):
     eng.adam_init(*adam)
 
 
-def run_steps(eng, k_adam, k_lbfgs, lbfgs=BURGERS_LBFGS):
-    """exactly k_adam + k_lbfgs optimiser iterations = as many loss+grad evaluations; -> L-BFGS done code"""
+def run_steps(eng, k_adam, k_lbfgs, lbfgs=BURGERS_LBFGS, log=None):
+    """exactly k_adam + k_lbfgs optimiser iterations = as many loss+grad evaluations; -> L-BFGS done code.
+    log: a list that receives the loss arrays lbfgs_run returns (what a caller of these steps gets back)"""
     done = 1
     if k_adam:
         eng.adam_run(k_adam, want_losses=False)
@@ -146,20 +156,25 @@ def run_steps(eng, k_adam, k_lbfgs, lbfgs=BURGERS_LBFGS):
         eng.lbfgs_begin(k_lbfgs, lbfgs[0], lbfgs[1], float(np.finfo(float).eps))      # the initial evaluation
         done = 0
         while not done:
-            _, _, done = eng.lbfgs_run(k_lbfgs)
+            _, losses, done = eng.lbfgs_run(k_lbfgs)
+            if log is not None:
+                log.append(losses)
     return int(done)
 
 
 def time_blocks(eng, wd, w0, k_adam, k_lbfgs, min_ms=MIN_TIMED_MS, max_blocks=MAX_BLOCKS, adam=BURGERS_ADAM,
-                lbfgs=BURGERS_LBFGS):
-    """blocks of exactly K steps, barrier + sync on both sides, MAX over ranks; repeated until >= min_ms are timed.
-    Every rank sees the same (max-reduced) block times, so every rank runs the same number of blocks."""
+                lbfgs=BURGERS_LBFGS, log=None):
+    """blocks of exactly K steps, barrier + sync on both sides, MAX over ranks; repeated until >= min_ms are timed
+    (min_ms = 0: exactly one block).  Every rank sees the same (max-reduced) block times, so every rank runs the same
+    number of blocks.  log (a list) ends up holding the L-BFGS loss arrays of the last block."""
     times, done = [], 1
     while (sum(times) * 1e3 < min_ms and len(times) < max_blocks) or not times:
         reset(eng, w0, adam)
+        if log is not None:
+            del log[:]
         wd.barrier(eng)                                    # everybody starts together ...
         t0 = time.perf_counter()
-        done = run_steps(eng, k_adam, k_lbfgs, lbfgs)
+        done = run_steps(eng, k_adam, k_lbfgs, lbfgs, log)
         eng.sync()                                         # ... this rank's K steps are complete on its GPU ...
         dt = time.perf_counter() - t0
         times.append(wd.max(dt))                           # ... and the block lasts as long as the slowest rank
@@ -222,9 +237,27 @@ def roofline(eng, tim, dtype, n_f_local, n_u_local, traffic=None, flops=None, n_
     }
 
 
+def step_outputs(eng, log):
+    """what the timed steps handed back, read after the last one: the trained weights, the L-BFGS loss log, and the
+    loss + gradient at those weights (one more evaluation, outside the timing; collective at N > 1, so every rank calls it)"""
+    loss, grad, terms = eng.loss_grad()
+    losses = [np.asarray(l, dtype=np.float64).ravel() for l in log]
+    return {"weights": np.asarray(eng.get_weights(), dtype=np.float64),
+            "lbfgs_losses": np.concatenate(losses) if losses else np.zeros(0),
+            "loss": np.array([loss], dtype=np.float64), "loss_terms": np.asarray(terms, dtype=np.float64),
+            "grad": np.asarray(grad, dtype=np.float64)}
+
+
+def write_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def leg(name, dtype, device, data, w0, wd, k_adam, k_lbfgs, warmup, kernel_path=-1, traffic=None, spin=True,
-        init_comm=None, min_ms=None):
-    """one timed leg on one workload (a dict as burgers_workload makes it, or the Burgers data tuple); -> (result dict, engine)"""
+        init_comm=None, min_ms=None, detail=True, outputs=None):
+    """one timed leg on one workload (a dict as burgers_workload makes it, or the Burgers data tuple); -> (result dict, engine)
+    detail=False: no kernel-timing pass, no roofline.  outputs (a dict): receives step_outputs() of the last timed block."""
     wl = data if isinstance(data, dict) else burgers_workload(data)
     sets, adam, lbfgs = wl["sets"], wl["adam"], wl["lbfgs"] or BURGERS_LBFGS
     if not wl["lbfgs"]:                                    # an Adam-only schedule (the reference's Schrodinger script)
@@ -248,9 +281,12 @@ def leg(name, dtype, device, data, w0, wd, k_adam, k_lbfgs, warmup, kernel_path=
             w_lbfgs = max(warmup - w_adam, 2)
             eng.lbfgs_begin(max(k_lbfgs, w_lbfgs), lbfgs[0], lbfgs[1], float(np.finfo(float).eps))
             eng.lbfgs_run(w_lbfgs)
+    log = [] if outputs is not None else None
     times, done = time_blocks(eng, wd, w0, k_adam, k_lbfgs, min_ms=MIN_TIMED_MS if min_ms is None else min_ms, adam=adam,
-                              lbfgs=lbfgs)
-    tim = kernel_samples(eng, w0, k_adam, k_lbfgs, adam=adam, lbfgs=lbfgs)
+                              lbfgs=lbfgs, log=log)
+    if outputs is not None:
+        outputs.update(step_outputs(eng, log))
+    tim = kernel_samples(eng, w0, k_adam, k_lbfgs, adam=adam, lbfgs=lbfgs) if detail else None
     from pinn_native.parallel import shard_bounds
 
     def local(key):
@@ -270,7 +306,7 @@ def leg(name, dtype, device, data, w0, wd, k_adam, k_lbfgs, warmup, kernel_path=
         "allreduce": comm_mode, "allreduce_probe_us": getattr(eng, "comm_probe_us", None),
         "allreduce_fallback": getattr(eng, "comm_fallback", None),       # "rccl failed: ..." when the mailboxes took over
         "roofline": roofline(eng, tim, dtype, n_local["f"], n_local["u"], traffic, flops=wl["flops"](n_local),
-                             n_b_local=n_local["b"]),
+                             n_b_local=n_local["b"]) if detail else None,
     }
     return out, eng
 
@@ -591,6 +627,13 @@ def main():
     ap.add_argument("--nf-per-gpu", type=int, default=0,
                     help="weak scaling instead: this many collocation points per GPU (overrides --nf-total)")
     ap.add_argument("--kernel-path", type=int, default=-1, help="-1 engine default; see pinn_set_kernel_path")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline steps: the roofline (its own kernel-timing pass), the leg in the other "
+                         "arithmetic, the cfg 3 / 4 / 5 legs, the final errors, cpu_baseline and script_leg; the --no-* "
+                         "options below trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (weights, L-BFGS loss log, loss and gradient at the final "
+                         "weights) as DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-final-error", action="store_true")
     ap.add_argument("--no-script-leg", action="store_true", help="skip the script-level leg (fit() of the drop-in script, logging on)")
@@ -651,12 +694,16 @@ def main():
         from pinn_native.parallel import init_engine_comm
         return init_engine_comm(eng, dist, world, rank, probe=True)   # "rccl" unless PINN_COMM=auto and the mailboxes win
 
-    # ---- headline leg ---------------------------------------------------------------------------------------
+    # ---- headline leg: one block of exactly --steps steps ------------------------------------------------------
+    outputs = {} if args.dump_outputs else None
     main_leg, eng = leg("headline", args.dtype, device, data, w0, wd, k_adam, k_lbfgs, args.warmup, args.kernel_path,
-                        init_comm=init_comm)
-    with_traffic(main_leg, world)
+                        init_comm=init_comm, min_ms=0.0, detail=args.full, outputs=outputs)
+    if outputs is not None and rank == 0:
+        write_outputs(args.dump_outputs, outputs)
     replicas_identical = None
-    if dist is not None:
+    if args.full:
+        with_traffic(main_leg, world)
+    if args.full and dist is not None:
         import hashlib
         digests = [None] * world
         dist.all_gather_object(digests, hashlib.sha256(eng.get_weights().tobytes()).hexdigest())
@@ -665,7 +712,7 @@ def main():
     # ---- accuracy legs (untimed): the reference's default schedule on the reference's own N_f = 10000 set ------
     errs = {}
     ref_data = data if n_f_total == 10000 else None
-    if not args.no_final_error:
+    if args.full and not args.no_final_error:
         if ref_data is None:
             _, _, ref_data = dataset(10000)
             from pinn_native.parallel import attach_shards
@@ -677,7 +724,7 @@ def main():
     # headline is the reference's float64; float64 when the headline was asked for in float32) -----------------------
     other = "f32" if args.dtype == "f64" else "f64"
     other_leg = None
-    if not args.no_f64_leg:
+    if args.full and not args.no_f64_leg:
         other_leg, e2 = leg("float32" if other == "f32" else "float64", other, device, data, w0, wd, k_adam, k_lbfgs,
                             min(args.warmup, 9), spin=False, init_comm=init_comm)
         with_traffic(other_leg, world)
@@ -690,7 +737,7 @@ def main():
 
     # ---- cfg 5: N_f = 10^6 in total, sharded over the ranks (BASELINE configs[4]) ---------------------------------
     cfg5 = None
-    if not args.no_cfg5_leg and not weak:
+    if args.full and not args.no_cfg5_leg and not weak:
         _, _, data5 = dataset(1000000)
         cfg5, e5 = leg("cfg5", args.dtype, device, data5, w0, wd, k_adam, k_lbfgs, min(args.warmup, 6),
                        args.kernel_path, spin=False, init_comm=init_comm)
@@ -714,7 +761,7 @@ def main():
 
     # ---- cfg 3 / cfg 4: the other two single-GPU configurations of BASELINE.json, in the headline's arithmetic -------------
     cfg3 = cfg4 = None
-    if not args.no_cfg34_legs and not weak:
+    if args.full and not args.no_cfg34_legs and not weak:
         for tag, make in (("cfg3", identification_workload), ("cfg4", schrodinger_workload)):
             wl = make()
             ka = max(1, int(round(args.steps * wl.get("adam_share", 1.0 / 3.0)))) if wl["lbfgs"] else args.steps
@@ -744,11 +791,6 @@ def main():
     if dist is not None:
         dist.barrier()
     if rank == 0:
-        ens = reference_ensemble("f64")
-        ens_of = {"f64": ens, "f32": reference_ensemble("f32")}      # each arithmetic against the ensemble the tests use for it
-
-        def delta(v):
-            return abs(v - ens["reference"]) if (v is not None and ens) else None
         out = {
             "metric": "collocation-points/sec",
             "value": main_leg["value"], "unit": "collocation-points/s",
@@ -766,12 +808,9 @@ def main():
                        "parallelism": "dp%d" % world, "allreduce": main_leg["allreduce"],
                        "allreduce_probe_us": main_leg["allreduce_probe_us"], "replicas_identical": replicas_identical,
                        "kernel_path": main_leg["kernel_path"], "lbfgs_done_code": main_leg["lbfgs_done_code"],
-                       "timing": "median of %d blocks of exactly %d steps (barrier+sync around each, MAX over ranks), "
-                                 "%.1f ms timed in total" % (main_leg["blocks_timed"], args.steps, main_leg["timed_ms_total"]),
-                       "ms_per_step_first_block": main_leg["ms_per_step_first_block"],
-                       "ms_per_step_min_block": main_leg["ms_per_step_min_block"]},
+                       "timing": "one block of exactly %d steps (barrier+sync around it, MAX over ranks), "
+                                 "%.1f ms timed" % (args.steps, main_leg["timed_ms_total"])},
             "valid": main_leg["valid"],
-            "roofline": main_leg["roofline"],
             # which HIP runtime / RCCL build this process bound (pinn_native._bind_runtime: /opt/rocm in a plain process,
             # torch's bundled set in a rank that needs torch.distributed) and how the ranks were started
             "runtime": runtime_record(),
@@ -783,37 +822,46 @@ def main():
                                "same_runtime_as_multi_rank_runs": (runtime_record().get("bound") == "torch")},
             "launch": ("single process" if world == 1 else "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ
                        else "bench.py --gpus %d (self-launched ranks)" % world),
-            ("float32_leg" if other == "f32" else "float64_leg"): other_leg,
-            "cfg5_leg": cfg5, "cfg3_leg": cfg3, "cfg4_leg": cfg4,
-            "final_l2_error": errs.get(args.dtype), "final_l2_error_f64": errs.get("f64"),
-            "final_l2_error_f32": errs.get("f32"),
-            "final_l2_error_reference": ens, "final_l2_error_reference_f32": ens_of["f32"],
-            # north_star's literal criterion, per arithmetic: |final error - the reference's k = 0 run| (<= 1e-3 asked;
-            # the reference's own runs differ by more than that between two hosts)
-            "final_l2_error_abs_delta": delta(errs.get(args.dtype)), "final_l2_error_abs_delta_f64": delta(errs.get("f64")),
-            "final_l2_error_abs_delta_f32": delta(errs.get("f32")),
-            "final_l2_error_within_1e-3": {k: (delta(v) is not None and delta(v) <= 1e-3) for k, v in errs.items()},
-            "final_l2_error_inside_reference_ensemble": {k: (ens_of[k] is not None and
-                                                             ens_of[k]["ensemble_min"] <= v <= ens_of[k]["ensemble_max"])
-                                                         for k, v in errs.items()},
-            "final_l2_error_schedule": "100 Adam (lr .03) + 200 L-BFGS (lr .8, m=50), reference defaults, on the "
-                                       "reference set N_f=10000 (sharded over the ranks)",
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline_port(ref_data[0] if ref_data else data[0][:10000], data[1], data[2],
-                                                    data[3], data[4], w0, X_star, u_star)
-        else:
-            out["cpu_baseline"] = None
-        if not args.no_script_leg and world == 1:
-            try:
-                sl = script_leg(args.dtype, device)
-                sl["ratio_to_engine_level_step"] = sl["ms_per_step"] / main_leg["ms_per_step"]
-                if out["cpu_baseline"] and out["cpu_baseline"].get("value"):
-                    # like for like: fit() with its logging on both sides
-                    sl["gpu_over_cpu_baseline"] = sl["value"] / out["cpu_baseline"]["value"]
-                out["script_leg"] = sl
-            except Exception as e:                                  # never lose the line over a secondary leg
-                out["script_leg"] = {"error": str(e)[-300:]}
+        if args.full:
+            ens = reference_ensemble("f64")
+            ens_of = {"f64": ens, "f32": reference_ensemble("f32")}      # each arithmetic against the ensemble the tests use for it
+
+            def delta(v):
+                return abs(v - ens["reference"]) if (v is not None and ens) else None
+            out.update({
+                "roofline": main_leg["roofline"],
+                ("float32_leg" if other == "f32" else "float64_leg"): other_leg,
+                "cfg5_leg": cfg5, "cfg3_leg": cfg3, "cfg4_leg": cfg4,
+                "final_l2_error": errs.get(args.dtype), "final_l2_error_f64": errs.get("f64"),
+                "final_l2_error_f32": errs.get("f32"),
+                "final_l2_error_reference": ens, "final_l2_error_reference_f32": ens_of["f32"],
+                # north_star's literal criterion, per arithmetic: |final error - the reference's k = 0 run| (<= 1e-3 asked;
+                # the reference's own runs differ by more than that between two hosts)
+                "final_l2_error_abs_delta": delta(errs.get(args.dtype)), "final_l2_error_abs_delta_f64": delta(errs.get("f64")),
+                "final_l2_error_abs_delta_f32": delta(errs.get("f32")),
+                "final_l2_error_within_1e-3": {k: (delta(v) is not None and delta(v) <= 1e-3) for k, v in errs.items()},
+                "final_l2_error_inside_reference_ensemble": {k: (ens_of[k] is not None and
+                                                                 ens_of[k]["ensemble_min"] <= v <= ens_of[k]["ensemble_max"])
+                                                             for k, v in errs.items()},
+                "final_l2_error_schedule": "100 Adam (lr .03) + 200 L-BFGS (lr .8, m=50), reference defaults, on the "
+                                           "reference set N_f=10000 (sharded over the ranks)",
+            })
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline_port(ref_data[0] if ref_data else data[0][:10000], data[1], data[2],
+                                                        data[3], data[4], w0, X_star, u_star)
+            else:
+                out["cpu_baseline"] = None
+            if not args.no_script_leg and world == 1:
+                try:
+                    sl = script_leg(args.dtype, device)
+                    sl["ratio_to_engine_level_step"] = sl["ms_per_step"] / main_leg["ms_per_step"]
+                    if out["cpu_baseline"] and out["cpu_baseline"].get("value"):
+                        # like for like: fit() with its logging on both sides
+                        sl["gpu_over_cpu_baseline"] = sl["value"] / out["cpu_baseline"]["value"]
+                    out["script_leg"] = sl
+                except Exception as e:                                  # never lose the line over a secondary leg
+                    out["script_leg"] = {"error": str(e)[-300:]}
         flush_c()
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of library variants on the headline leg (and cfg 5 with CFG5=1): bench.py's kernel time by HIP events
 #   bash profiles/r06_ab_variants.sh <variant> [<variant> ...]     variant = a name under pinn_native/abl/ or "tree" (the in-tree library)
-B="--gpus 1 --steps 20 --warmup 5 --no-cfg34-legs --no-f64-leg --no-cpu-baseline --no-script-leg --no-final-error"
+B="--gpus 1 --steps 20 --warmup 5 --full --no-cfg34-legs --no-f64-leg --no-cpu-baseline --no-script-leg --no-final-error"
 [ -z "$CFG5" ] && B="$B --no-cfg5-leg"
 for i in 1 2; do
 for v in "$@"; do

@@ -35,6 +35,7 @@ What each fixture pins, and from which reference code:
                          adapters (see gen_burgers_disc): the Butcher table file of the absent PINNs
                          submodule, np.asscalar (removed from numpy), Logger(frequency=...) (older
                          Logger signature than utils/logger.py in the same tree)
+  reference_py_sha256.json    sha256 of each of the reference's Python sources (digests only, no text)
 """
 import contextlib
 import hashlib
@@ -642,6 +643,21 @@ def gen_disc_runs():
     print("disc ide run: l1 %.6e l2 %.6e" % (rec["lambda_1"], rec["lambda_2"]))
 
 
+def gen_reference_digests():
+    """sha256 of every Python source of the reference: what tests/test_host_api.py looks for in the tree (no source is
+    stored, only the digests)"""
+    digests = set()
+    for dp, dn, fn in os.walk(REF):
+        dn[:] = [d for d in dn if d != ".git"]
+        for f in fn:
+            if f.endswith(".py"):
+                with open(os.path.join(dp, f), "rb") as fh:
+                    digests.add(hashlib.sha256(fh.read()).hexdigest())
+    with open(os.path.join(HERE, "reference_py_sha256.json"), "w") as f:
+        json.dump({"what": "sha256 of each Python source file of the reference", "sha256": sorted(digests)}, f, indent=1)
+    print("reference digests: %d files" % len(digests))
+
+
 def main():
     os.chdir(REF)
     sys.path.insert(0, SHIMS)
@@ -678,6 +694,8 @@ def main():
         gen_burgers_disc()
     if "disc_runs" in which or not sys.argv[1:]:
         gen_disc_runs()
+    if "digests" in which or not sys.argv[1:]:
+        gen_reference_digests()
 
 
 if __name__ == "__main__":

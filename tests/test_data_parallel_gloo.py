@@ -240,7 +240,7 @@ def _bench_main_worker(rank, world, port, out_dir):
     import bench
     pinn_native.Engine = _StubEngine
     pinn_native.device_info = lambda d=0: {"name": "stub", "compute_units": 256, "hbm_bytes": 0}
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "6", "--warmup", "3"]
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "6", "--warmup", "3", "--full"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
@@ -314,7 +314,7 @@ def test_bench_self_launch_two_ranks_prints_one_contract_line():
     """the driver's N-GPU command may be plain `python3 bench.py --gpus N`; the launcher spawns the
     ranks with the environment torch.distributed.run would give them and forwards rank 0's single JSON line"""
     import json
-    rc, out, err = _self_launch(2, ["--gpus", "2", "--steps", "6", "--warmup", "3", "--no-cfg34-legs"],
+    rc, out, err = _self_launch(2, ["--gpus", "2", "--steps", "6", "--warmup", "3", "--full", "--no-cfg34-legs"],
                                 device_count=lambda: 2)
     assert rc == 0, err
     lines = [l for l in out.splitlines() if l.strip()]
@@ -327,6 +327,36 @@ def test_bench_self_launch_two_ranks_prints_one_contract_line():
     assert j["runtime"]["bound"] == "torch" and j["runtime"]["single_runtime"] is True
     assert j["runtime"]["hip_runtime"] > 0 and j["runtime"]["rccl_version"].count(".") == 2
     assert j["roofline"]["traffic_provenance"]["measured_in_run"] is False
+
+
+def test_bench_plain_run_times_the_steps_only_and_dumps_their_outputs(tmp_path):
+    """a plain run (no --full) times exactly --steps steps in one block and prints the headline alone; --dump-outputs
+    writes what those steps computed, the same files from run to run"""
+    import json
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("out%d" % run))
+        rc, out, err = _self_launch(1, ["--gpus", "1", "--steps", "6", "--warmup", "3", "--dump-outputs", d],
+                                    device_count=lambda: 1)
+        assert rc == 0, err
+        lines = [l for l in out.splitlines() if l.strip()]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["steps"] == 6 and j["warmup"] == 3 and j["valid"] is True and j["dtype"] == "f64"
+        assert j["metric"] == "collocation-points/sec" and j["unit"] == "collocation-points/s" and j["higher_is_better"] is True
+        assert j["config"]["timing"].startswith("one block of exactly 6 steps")
+        assert abs(j["value"] - 10000 * 6 / (j["ms_per_step"] * 6e-3)) < 1e-6 * j["value"]
+        for key in ("roofline", "float32_leg", "cfg3_leg", "cfg4_leg", "cfg5_leg", "final_l2_error", "cpu_baseline",
+                    "script_leg"):
+            assert key not in j, key
+        assert sorted(os.listdir(d)) == ["grad.npy", "lbfgs_losses.npy", "loss.npy", "loss_terms.npy", "weights.npy"]
+        dumps.append({f: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    import bench
+    # the stub's 'training': +1e-3 per Adam step (2 of 6), -1e-4 per L-BFGS iteration (4 of 6), from the canonical weights
+    assert np.allclose(dumps[0]["weights.npy"], bench.canonical_weights() + 2e-3 - 4e-4, rtol=0, atol=1e-15)
+    assert dumps[0]["weights.npy"].dtype == np.float64 and dumps[0]["grad.npy"].shape == (3021,)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def test_bench_self_launch_refuses_more_ranks_than_devices():
@@ -565,7 +595,7 @@ def test_bench_self_launch_eight_ranks_prints_one_contract_line():
     """the driver's 8-GPU command, with the engine scripted: one JSON line, the metric's 10000 points and cfg 5's 10^6 split
     eight ways, every leg on an 8-rank communicator"""
     import json
-    rc, out, err = _self_launch(8, ["--gpus", "8", "--steps", "6", "--warmup", "3"], device_count=lambda: 8)
+    rc, out, err = _self_launch(8, ["--gpus", "8", "--steps", "6", "--warmup", "3", "--full"], device_count=lambda: 8)
     assert rc == 0, err
     lines = [l for l in out.splitlines() if l.strip()]
     assert len(lines) == 1 and "exited with code" not in err

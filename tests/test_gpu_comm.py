@@ -204,7 +204,7 @@ def test_bench_two_ranks_on_one_device_end_to_end(tmp_path, launcher):
                PINN_BENCH_MIN_TIMED_MS="60")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    args = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3"]
+    args = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--full"]
     if launcher == "torchrun":
         port = 29300 + os.getpid() % 90
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
@@ -232,3 +232,39 @@ def test_bench_two_ranks_on_one_device_end_to_end(tmp_path, launcher):
         # the sharded default schedule still trains in the default arithmetic (float32 under this L-BFGS may diverge for an
         # unlucky rounding, tests/test_gpu_end_to_end.py: only its finiteness is checked)
         assert 0.1 < j["final_l2_error"] < 0.6 and np.isfinite(j["final_l2_error_f32"])
+
+
+def test_bench_plain_run_dumps_the_outputs_of_its_timed_steps(tmp_path, burgers_sets):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` with the real engine: one block of exactly K steps, the
+    headline alone, and the dumped arrays are what those steps produced -- identical in two runs, the loss and gradient
+    at the dumped weights those of the oracle on the same seeded set"""
+    import json
+    import os
+    import subprocess
+    import sys
+    from oracle import pde
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "PINN_BENCH_DEVICE"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("out%d" % run))
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "6",
+               "--dump-outputs", d]
+        res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert res.returncode == 0 and len(lines) == 1, res.stdout[-3000:] + res.stderr[-3000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 30 and j["valid"] is True and j["value"] > 0 and j["config"]["lbfgs_done_code"] == 1
+        assert j["config"]["timing"].startswith("one block of exactly 30 steps") and "roofline" not in j
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    assert sorted(dumps[0]) == ["grad", "lbfgs_losses", "loss", "loss_terms", "weights"]
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name        # float64 kernels: bit-reproducible
+    r = burgers_sets(100, 10000)
+    w = dumps[0]["weights"]
+    lo, go, _ = pde.burgers_loss_grad(w, [2] + [20] * 8 + [1], r[11], r[10], r[9], r[7], r[8], NU)
+    assert abs(dumps[0]["loss"][0] - lo) <= 1e-11 * lo
+    assert np.max(np.abs(dumps[0]["grad"] - go)) <= 1e-11 * np.max(np.abs(go))
+    assert dumps[0]["lbfgs_losses"].size > 0 and np.all(np.isfinite(dumps[0]["lbfgs_losses"]))

@@ -238,6 +238,49 @@ int pinn_debug_t16f_stamps(long long* out512);
  * every tile and every row is dealt exactly once for every width. */
 int pinn_debug_t16_deal(int W, int* out49);
 
+/* Ensembles: K = n_members (1..64) copies of one float64 Burgers net (kernel path 7: pde 0 or 1, 2-20-...-20-1 with 4, 6
+ * or 8 hidden layers) trained side by side on ONE point set with one set of PDE parameters -- seeds, learning-rate
+ * sweeps, repeated identification runs.  Each member has its own weights (lambda_1, lambda_2 included), Adam moments,
+ * L-BFGS state, history and log, and non-finite status; member k ends bit-identical to a pinn_ctx trained alone from the
+ * same weights with the same calls.  One evaluation of all members = one loss+gradient launch with a member grid dimension
+ * + one member-batched reduction.  Per-member arrays are member-major: weights [K][P], gradients [K][P], terms [K][3].
+ * Device memory per member, N_f = 10^4, 8 x 20: ~3.8 MB of gradient rows + ~2.5 MB of L-BFGS rings (n_corr = 50) + the
+ * member's small per-context buffers (~6.5 MB); the point sets are held once.  Calls are synchronous.
+ * pinn_ens_create refuses float32, Schrodinger, discrete-time models and other shapes with PINN_EUNSUPPORTED and
+ * K outside 1..64 with PINN_EINVAL, before touching a device; an ensemble has no communicator.  (Additive: the ABI
+ * version stays 6; callers detect the feature by the presence of the symbols.) */
+typedef struct pinn_ens pinn_ens;
+int pinn_ens_create(pinn_ens** out, const int* layers, int n_layers, const double* lb, const double* ub, int pde_kind,
+                    int dtype, int device, int n_members);
+int pinn_ens_destroy(pinn_ens* e);
+int pinn_ens_size(pinn_ens* e, int* n_members, int64_t* n_params);
+/* the point sets and PDE parameters, shared by all members: pinn_set_collocation / _data / _pde_params */
+int pinn_ens_set_collocation(pinn_ens* e, const double* X_f, int64_t n, int64_t n_total);
+int pinn_ens_set_data(pinn_ens* e, const double* X_u, const double* u, int64_t n, int64_t n_total);
+int pinn_ens_set_pde_params(pinn_ens* e, const double* p, int n);
+/* w [K][P], n = K * P */
+int pinn_ens_set_weights(pinn_ens* e, const double* w, int64_t n);
+int pinn_ens_get_weights(pinn_ens* e, double* w, int64_t n);
+/* losses [K]; grads [K][P] and terms [K][3] may be NULL */
+int pinn_ens_loss_grad(pinn_ens* e, double* losses, double* grads, double* terms);
+/* pinn_adam_init per member; lr_k [K] (may be NULL: lr for all) */
+int pinn_ens_adam_init(pinn_ens* e, double lr, double beta1, double beta2, double eps, const double* lr_k);
+/* n_steps Adam steps of every member; losses [n_steps][K] (may be NULL) = each member's loss before update i */
+int pinn_ens_adam_run(pinn_ens* e, int n_steps, double* losses);
+/* pinn_lbfgs_begin per member: n_corr, tol_fun, tol_x, max_eval shared; lr_k [K] / max_iter_k [K] may be NULL (lr /
+ * max_iter for all) */
+int pinn_ens_lbfgs_begin(pinn_ens* e, int n_corr, double tol_fun, double tol_x, double max_eval, double lr,
+                         const double* lr_k, int max_iter, const int* max_iter_k);
+/* up to n_iters iterations of every member that has not issued its max_iter yet (as pinn_lbfgs_run does per member; a
+ * member whose run ended on the device stops moving while the others go on).  iters / losses [K][n_iters + 1] (may be
+ * NULL): member k's log entries in row k, n_logged [K] of them; done [K] as pinn_lbfgs_run's done. */
+int pinn_ens_lbfgs_run(pinn_ens* e, int n_iters, int* iters, double* losses, int* n_logged, int* done);
+/* out [K][n] (one output); err [K] = pinn_error_l2 kind 0 per member */
+int pinn_ens_predict(pinn_ens* e, const double* X, int64_t n, double* out);
+int pinn_ens_error_l2(pinn_ens* e, const double* X, const double* ref, int64_t n, double* err);
+/* pinn_get_status per member: n_evals [K], first_nonfinite_eval [K] (either may be NULL) */
+int pinn_ens_get_status(pinn_ens* e, int64_t* n_evals, int64_t* first_nonfinite_eval);
+
 #ifdef __cplusplus
 }
 #endif

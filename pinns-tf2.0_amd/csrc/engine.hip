@@ -106,6 +106,7 @@ static constexpr int LOSS_SLOTS = 4;         // residual, data, boundary, pad
 struct pinn_ctx {
   int device = 0, dtype = PINN_F32, pde = PINN_PDE_BURGERS, path = 0;
   hipStream_t stream = nullptr;
+  bool own_stream = true;            // false: an ensemble member, on its ensemble's stream (pinn_ens_create)
   NetDesc nd{};
   int layers[MAX_DENSE + 1]{};
   int n_layers = 0;
@@ -1271,7 +1272,7 @@ int pinn_destroy(pinn_ctx* c) {
   }
   if (c->h_err) (void)hipHostFree(c->h_err);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-  (void)hipStreamDestroy(c->stream);
+  if (c->own_stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return 0;
 }
@@ -1571,8 +1572,10 @@ int pinn_adam_run_terms(pinn_ctx* c, int n_steps, double* terms3) {
   return rc;
 }
 
-int pinn_lbfgs_begin(pinn_ctx* c, int max_iter, double lr, int n_corr, double tol_fun,
-                     double tol_x, double max_eval) {
+// pinn_lbfgs_begin up to the initial evaluation; *eval = 0: nothing follows (max_iter == 0)
+static int lbfgs_begin_setup(pinn_ctx* c, int max_iter, double lr, int n_corr, double tol_fun, double tol_x,
+                             double max_eval, bool* eval) {
+  *eval = false;
   REQUIRE(c && max_iter >= 0 && n_corr >= 1 && lr > 0, "bad L-BFGS arguments");
   HIPCHK(hipSetDevice(c->device));
   const size_t n = c->nd.n_theta;
@@ -1628,10 +1631,15 @@ int pinn_lbfgs_begin(pinn_ctx* c, int max_iter, double lr, int n_corr, double to
     c->lb_cap_log = max_iter + 1;
   }
   HIPCHK(hipMemcpyAsync(c->lb_x, c->theta, n * 8, hipMemcpyDeviceToDevice, c->stream));
-  int rc = eval_loss_grad(c);                                      // :65
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_lbfgs_post, dim3(1), dim3(LB_THREADS), 0, c->stream, (int)n, (int)n,
-                     max_iter, c->lb_max_eval, tol_fun, tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_d,
+  *eval = true;
+  return 0;
+}
+
+// pinn_lbfgs_begin behind the initial evaluation
+static int lbfgs_begin_post(pinn_ctx* c) {
+  const int n = c->nd.n_theta;
+  hipLaunchKernelGGL(k_lbfgs_post, dim3(1), dim3(LB_THREADS), 0, c->stream, n, n,
+                     c->lb_max_iter, c->lb_max_eval, c->lb_tol_fun, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_d,
                      c->lb_log_iter, c->lb_log_loss, 1);
   HIPCHK(hipGetLastError());
   if (c->xg.on) {                                 // a lost mailbox peer in the first evaluation surfaces here
@@ -1642,13 +1650,27 @@ int pinn_lbfgs_begin(pinn_ctx* c, int max_iter, double lr, int n_corr, double to
   return 0;
 }
 
+int pinn_lbfgs_begin(pinn_ctx* c, int max_iter, double lr, int n_corr, double tol_fun,
+                     double tol_x, double max_eval) {
+  bool eval = false;
+  if (int rc = lbfgs_begin_setup(c, max_iter, lr, n_corr, tol_fun, tol_x, max_eval, &eval)) return rc;
+  if (!eval) return 0;
+  if (int rc = eval_loss_grad(c)) return rc;                       // :65
+  return lbfgs_begin_post(c);
+}
+
 // up to n_iters iterations into the stream, then the state and the window of log entries they can have added on their way
 // to the chunk's pinned buffers
-static int lbfgs_issue(pinn_ctx* c, int n_iters, int* ticket) {
+//   lbfgs_open     the chunk's pending slot (*pp = nullptr: max_iter == 0, the ticket is issued already)
+//   lbfgs_iter     one iteration's step kernels; *eval: an evaluation follows (not behind the last iteration)
+//   lbfgs_behind   what follows that evaluation
+//   lbfgs_close    the state and log window to the chunk's pinned buffers, the ticket
+// (pieces, so that pinn_ens_lbfgs_run can put one evaluation of all its members between them)
+static int lbfgs_open(pinn_ctx* c, int n_iters, int* ticket, pinn_ctx::Pending** pp, int* window_out) {
+  *pp = nullptr;
   REQUIRE(c && n_iters >= 0, "bad arguments");
   REQUIRE(c->lb_ready, "pinn_lbfgs_begin has not been called");
   HIPCHK(hipSetDevice(c->device));
-  const Range rg("pinn_lbfgs_run");
   pinn_ctx::Pending* p = nullptr;
   // one log entry per evaluation settled since the host last looked: the iterations issued since then, this chunk's, + 1
   int window = (c->lb_iters_issued - c->lb_issued_at_read) + n_iters + 1;
@@ -1662,8 +1684,14 @@ static int lbfgs_issue(pinn_ctx* c, int n_iters, int* ticket) {
     c->tickets_issued += 1;
     return 0;
   }
+  *pp = p;
+  *window_out = window;
+  return 0;
+}
+
+static int lbfgs_iter(pinn_ctx* c, bool* eval) {
   const int n = c->nd.n_theta;
-  for (int s = 0; s < n_iters && c->lb_iters_issued < c->lb_max_iter; ++s) {
+  {
     c->lb_iters_issued += 1;
     if (c->lb_mode_active) {
       const int M1 = c->lb_M1;
@@ -1703,13 +1731,21 @@ static int lbfgs_issue(pinn_ctx* c, int n_iters, int* ticket) {
       hipLaunchKernelGGL((k_lbfgs_step<double>), dim3(1), dim3(LB_THREADS), 0, c->stream, n, c->lb_max_iter, c->lb_ncorr, c->lb_lr, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_x, c->theta, (double*)c->theta_r, c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al, c->lb_q, c->nd, c->img);
     else
       hipLaunchKernelGGL((k_lbfgs_step<float>), dim3(1), dim3(LB_THREADS), 0, c->stream, n, c->lb_max_iter, c->lb_ncorr, c->lb_lr, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_x, c->theta, (float*)c->theta_r, c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al, c->lb_q, c->nd, c->img);
-    if (c->lb_iters_issued == c->lb_max_iter) break;              // last iteration: no re-evaluation
-    if (int rc = eval_loss_grad(c)) return rc;
-    if (c->lb_mode_active) { c->lb_post_pending = true; continue; }   // folded into the next k_lbc_coef
-    hipLaunchKernelGGL(k_lbfgs_post, dim3(1), dim3(LB_THREADS), 0, c->stream, n, n, c->lb_max_iter,
-                       c->lb_max_eval, c->lb_tol_fun, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_d,
-                       c->lb_log_iter, c->lb_log_loss, 0);
+    *eval = c->lb_iters_issued != c->lb_max_iter;                  // last iteration: no re-evaluation
   }
+  return 0;
+}
+
+static void lbfgs_behind(pinn_ctx* c) {
+  const int n = c->nd.n_theta;
+  if (c->lb_mode_active) { c->lb_post_pending = true; return; }   // folded into the next k_lbc_coef
+  hipLaunchKernelGGL(k_lbfgs_post, dim3(1), dim3(LB_THREADS), 0, c->stream, n, n, c->lb_max_iter,
+                     c->lb_max_eval, c->lb_tol_fun, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_d,
+                     c->lb_log_iter, c->lb_log_loss, 0);
+}
+
+static int lbfgs_close(pinn_ctx* c, pinn_ctx::Pending* p, int window, int* ticket) {
+  const int n = c->nd.n_theta;
   if (c->lb_post_pending) {                       // the host is about to read the state: settle it
     hipLaunchKernelGGL(k_lbfgs_post, dim3(1), dim3(LB_THREADS), 0, c->stream, n, n, c->lb_max_iter,
                        c->lb_max_eval, c->lb_tol_fun, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_d,
@@ -1727,6 +1763,22 @@ static int lbfgs_issue(pinn_ctx* c, int n_iters, int* ticket) {
   if (ticket) *ticket = (int)(c->tickets_issued & 0x7fffffff);
   c->tickets_issued += 1;
   return 0;
+}
+
+static int lbfgs_issue(pinn_ctx* c, int n_iters, int* ticket) {
+  const Range rg("pinn_lbfgs_run");
+  pinn_ctx::Pending* p = nullptr;
+  int window = 0;
+  if (int rc = lbfgs_open(c, n_iters, ticket, &p, &window)) return rc;
+  if (!p) return 0;
+  for (int s = 0; s < n_iters && c->lb_iters_issued < c->lb_max_iter; ++s) {
+    bool eval = false;
+    if (int rc = lbfgs_iter(c, &eval)) return rc;
+    if (!eval) break;
+    if (int rc = eval_loss_grad(c)) return rc;
+    lbfgs_behind(c);
+  }
+  return lbfgs_close(c, p, window, ticket);
 }
 
 static int lbfgs_collect(pinn_ctx* c, int ticket, int cap, int* iters, double* losses, int* n_logged, int* done) {
@@ -2203,6 +2255,321 @@ int pinn_debug_t16f_stamps(long long* out512) {
 int pinn_get_kernel_path(pinn_ctx* c, int* path) {
   REQUIRE(c && path, "null");
   *path = c->path;
+  return 0;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// ensembles: K members of one float64 Burgers net (kernel path 7) trained side by side on one point set
+// ------------------------------------------------------------------------------------------
+// A base context holds the point sets, the PDE parameters, the launch plan and the stream; every member is a context of
+// its own (Adam moments, L-BFGS state, rings and log, status) whose weight, mirror, gradient, moment and status buffers are
+// slices of the ensemble's blocks below and whose stream is the base's.  One evaluation = ONE k_fused20d<.., ENS> launch
+// for all members (grid (n_wg, K)) + ONE member-batched reduction (k_reduce_rows_ens / k_reduce_adam_ens); the L-BFGS
+// step kernels run per member between them, exactly as pinn_lbfgs_run issues them.  Member k is bit-identical to a solo
+// context trained from the same weights: same launch plan, same row order, same per-column arithmetic.
+struct pinn_ens {
+  pinn_ctx* base = nullptr;
+  int K = 0, P = 0, sw = 0;                    // members, parameters, weight-mirror stride (fused20d_weight_doubles(P))
+  std::vector<pinn_ctx*> mem;
+  double *theta = nullptr, *theta_r = nullptr, *gl = nullptr, *m = nullptr, *v = nullptr;   // [K][P] / [K][sw] / [K][R]
+  unsigned long long* nonfinite = nullptr;     // [K]
+  double* part = nullptr;                      // [K][n_wg][R]
+  size_t cap_part = 0;
+  double* loss_hist = nullptr;                 // Adam: [steps][K][3]
+  size_t cap_loss = 0;
+};
+
+static void ens_free(pinn_ens* e) {
+  for (pinn_ctx* c : e->mem) {
+    if (!c) continue;
+    c->theta = nullptr; c->theta_r = nullptr; c->gl = nullptr; c->adam_m = nullptr; c->adam_v = nullptr;
+    c->d_nonfinite = nullptr;                  // slices of the blocks below
+    (void)pinn_destroy(c);
+  }
+  if (e->base) { (void)hipSetDevice(e->base->device); (void)hipStreamSynchronize(e->base->stream); }
+  void* ptrs[] = {e->theta, e->theta_r, e->gl, e->m, e->v, e->nonfinite, e->part, e->loss_hist};
+  for (void* p : ptrs) if (p) (void)hipFree(p);
+  if (e->base) (void)pinn_destroy(e->base);
+  delete e;
+}
+
+// one evaluation of every member at its current weights.  active[k] = false: member k's rows are computed but not reduced
+// (its gradient, status and evaluation count stay as they are).  alpha != nullptr: the Adam step behind the reduction,
+// loss3 <- [K][3] loss parts.
+static int ens_eval(pinn_ens* e, const bool* active, const double* alpha, double* loss3) {
+  pinn_ctx* b = e->base;
+  if (int rc = ensure_sets(b)) return rc;
+  const size_t need = (size_t)e->K * b->n_wg * b->R;
+  if (need > e->cap_part) { if (dev_alloc(&e->part, need * 8)) return PINN_EHIP; e->cap_part = need; }
+  const double sx = 2.0 / (b->ub[0] - b->lb[0]), st = 2.0 / (b->ub[1] - b->lb[1]);
+  const int rc = fused20d_ens_launch_any(b->pde, b->nd, b->sd, e->theta_r, (const double*)b->xs, (const double*)b->ts,
+                                         (const double*)b->tgt, b->lb[0], b->lb[1], sx, st, b->nu, e->part, b->R,
+                                         b->n_wg, e->K, b->row_index, b->stream);
+  if (rc) return fail(PINN_EHIP, "ensemble fused20d launch failed: %s", hipGetErrorString((hipError_t)rc));
+  EnsStep es{};
+  for (int k = 0; k < e->K; ++k) {
+    if (!active[k]) continue;
+    pinn_ctx* c = e->mem[k];
+    c->n_evals += 1;
+    es.eval_no[k] = c->n_evals;
+    if (alpha) es.alpha[k] = alpha[k];
+  }
+  const dim3 grid((b->R + RED_COLS - 1) / RED_COLS, e->K);
+  pinn_ctx* c0 = e->mem[0];
+  if (alpha)
+    hipLaunchKernelGGL(k_reduce_adam_ens, grid, dim3(RED_THREADS), 0, b->stream, (const double*)e->part, b->n_wg, b->R,
+                       e->gl, e->P, e->sw, e->theta, e->theta_r, e->m, e->v, c0->b1, c0->b2, c0->eps, loss3, e->nonfinite,
+                       es);
+  else
+    hipLaunchKernelGGL(k_reduce_rows_ens, grid, dim3(RED_THREADS), 0, b->stream, (const double*)e->part, b->n_wg, b->R,
+                       e->gl, e->P, e->nonfinite, es);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int pinn_ens_create(pinn_ens** out, const int* layers, int n_layers, const double* lb, const double* ub, int pde_kind,
+                    int dtype, int device, int n_members) {
+  // every refusal comes before any device work
+  REQUIRE(out && layers && lb && ub, "null argument");
+  REQUIRE(n_members >= 1 && n_members <= ENS_MAX, "ensemble size %d outside 1..%d", n_members, ENS_MAX);
+  if (dtype != PINN_F64)
+    return fail(PINN_EUNSUPPORTED, "ensembles are float64 only (kernel path 7); float32 is not supported");
+  if (pde_kind != PINN_PDE_BURGERS && pde_kind != PINN_PDE_BURGERS_IDE)
+    return fail(PINN_EUNSUPPORTED, "ensembles support Burgers inference and identification (pde 0, 1) only; "
+                                   "Schrodinger and discrete-time models are not supported");
+  const int H = n_layers - 2;
+  bool shape_ok = n_layers >= 3 && fused20d_depth_ok(H) && layers[0] == 2 && layers[n_layers - 1] == 1;
+  for (int i = 1; shape_ok && i <= H; ++i) shape_ok = layers[i] == FW;
+  if (!shape_ok)
+    return fail(PINN_EUNSUPPORTED, "ensembles need the 2-%d-1 net with 4, 6 or 8 hidden layers of width %d", FW, FW);
+  *out = nullptr;
+  pinn_ens* e = new pinn_ens();
+  e->K = n_members;
+  if (int rc = pinn_create(&e->base, layers, n_layers, lb, ub, pde_kind, dtype, device)) { delete e; return rc; }
+  pinn_ctx* b = e->base;
+  if (b->path != 7) { ens_free(e); return fail(PINN_EUNSUPPORTED, "ensembles need kernel path 7 (got %d)", b->path); }
+  e->P = b->nd.n_theta;
+  e->sw = (int)fused20d_weight_doubles(e->P);
+  const size_t K = e->K, P = e->P;
+  if (dev_alloc(&e->theta, K * P * 8) || dev_alloc(&e->m, K * P * 8) || dev_alloc(&e->v, K * P * 8) ||
+      dev_alloc(&e->theta_r, K * e->sw * 8 + 1024) || dev_alloc(&e->gl, K * b->R * 8) ||
+      dev_alloc(&e->nonfinite, K * 8)) { ens_free(e); return PINN_EHIP; }
+  HIPCHK(hipMemsetAsync(e->theta, 0, K * P * 8, b->stream));
+  HIPCHK(hipMemsetAsync(e->theta_r, 0, K * e->sw * 8 + 1024, b->stream));
+  HIPCHK(hipMemsetAsync(e->gl, 0, K * b->R * 8, b->stream));
+  HIPCHK(hipMemsetAsync(e->nonfinite, 0, K * 8, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  e->mem.assign(K, nullptr);
+  for (size_t k = 0; k < K; ++k) {
+    pinn_ctx* c = nullptr;
+    if (int rc = pinn_create(&c, layers, n_layers, lb, ub, pde_kind, dtype, device)) { ens_free(e); return rc; }
+    e->mem[k] = c;
+    void* own[] = {c->theta, c->theta_r, c->gl, c->adam_m, c->adam_v, c->d_nonfinite};
+    for (void* p : own) (void)hipFree(p);
+    c->theta = e->theta + k * P; c->adam_m = e->m + k * P; c->adam_v = e->v + k * P;
+    c->theta_r = e->theta_r + k * e->sw; c->gl = e->gl + k * b->R; c->d_nonfinite = e->nonfinite + k;
+    (void)hipStreamDestroy(c->stream);
+    c->stream = b->stream;
+    c->own_stream = false;
+  }
+  *out = e;
+  return 0;
+}
+
+int pinn_ens_destroy(pinn_ens* e) {
+  if (e) ens_free(e);
+  return 0;
+}
+
+int pinn_ens_size(pinn_ens* e, int* n_members, int64_t* n_params) {
+  REQUIRE(e, "null");
+  if (n_members) *n_members = e->K;
+  if (n_params) *n_params = e->P;
+  return 0;
+}
+
+int pinn_ens_set_collocation(pinn_ens* e, const double* X_f, int64_t n, int64_t n_total) {
+  REQUIRE(e, "null");
+  return pinn_set_collocation(e->base, X_f, n, n_total);
+}
+
+int pinn_ens_set_data(pinn_ens* e, const double* X_u, const double* u, int64_t n, int64_t n_total) {
+  REQUIRE(e, "null");
+  return pinn_set_data(e->base, X_u, u, n, n_total);
+}
+
+int pinn_ens_set_pde_params(pinn_ens* e, const double* p, int n) {
+  REQUIRE(e, "null");
+  return pinn_set_pde_params(e->base, p, n);
+}
+
+int pinn_ens_set_weights(pinn_ens* e, const double* w, int64_t n) {
+  REQUIRE(e && w, "null");
+  REQUIRE(n == (int64_t)e->K * e->P, "weight array has %lld entries, expected K x P = %d x %d", (long long)n, e->K, e->P);
+  pinn_ctx* b = e->base;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipMemcpyAsync(e->theta, w, (size_t)n * 8, hipMemcpyHostToDevice, b->stream));
+  for (pinn_ctx* c : e->mem) if (int rc = cast_weights(c)) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+int pinn_ens_get_weights(pinn_ens* e, double* w, int64_t n) {
+  REQUIRE(e && w, "null");
+  REQUIRE(n == (int64_t)e->K * e->P, "weight array has %lld entries, expected K x P = %d x %d", (long long)n, e->K, e->P);
+  pinn_ctx* b = e->base;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipMemcpyAsync(w, e->theta, (size_t)n * 8, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+int pinn_ens_loss_grad(pinn_ens* e, double* losses, double* grads, double* terms) {
+  REQUIRE(e, "null");
+  pinn_ctx* b = e->base;
+  HIPCHK(hipSetDevice(b->device));
+  std::vector<char> all((size_t)e->K, 1);
+  if (int rc = ens_eval(e, (const bool*)all.data(), nullptr, nullptr)) return rc;
+  const int R = b->R, P = e->P;
+  std::vector<double> h((size_t)e->K * R);
+  HIPCHK(hipMemcpyAsync(h.data(), e->gl, h.size() * 8, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  for (int k = 0; k < e->K; ++k) {
+    const double* g = h.data() + (size_t)k * R;
+    if (losses) losses[k] = g[P] + g[P + 1] + g[P + 2];
+    if (terms) { terms[3 * k] = g[P]; terms[3 * k + 1] = g[P + 1]; terms[3 * k + 2] = g[P + 2]; }
+    if (grads) memcpy(grads + (size_t)k * P, g, (size_t)P * 8);
+  }
+  return 0;
+}
+
+int pinn_ens_adam_init(pinn_ens* e, double lr, double beta1, double beta2, double eps, const double* lr_k) {
+  REQUIRE(e, "null");
+  for (int k = 0; k < e->K; ++k)
+    if (int rc = pinn_adam_init(e->mem[k], lr_k ? lr_k[k] : lr, beta1, beta2, eps)) return rc;
+  return 0;
+}
+
+int pinn_ens_adam_run(pinn_ens* e, int n_steps, double* losses) {
+  REQUIRE(e && n_steps >= 0, "bad arguments");
+  for (pinn_ctx* c : e->mem) REQUIRE(c->adam_ready, "pinn_ens_adam_init has not been called");
+  pinn_ctx* b = e->base;
+  HIPCHK(hipSetDevice(b->device));
+  if (n_steps == 0) return 0;
+  const size_t K = e->K;
+  if ((size_t)n_steps * K * 3 > e->cap_loss) {
+    if (dev_alloc(&e->loss_hist, (size_t)n_steps * K * 3 * 8)) return PINN_EHIP;
+    e->cap_loss = (size_t)n_steps * K * 3;
+  }
+  std::vector<char> all(K, 1);
+  std::vector<double> alpha(K);
+  for (int s = 0; s < n_steps; ++s) {
+    for (size_t k = 0; k < K; ++k) {             // the step size exactly as adam_issue forms it
+      pinn_ctx* c = e->mem[k];
+      c->adam_t += 1;
+      const double t = (double)c->adam_t;
+      alpha[k] = c->lr * std::sqrt(1.0 - std::pow(c->b2, t)) / (1.0 - std::pow(c->b1, t));
+    }
+    if (int rc = ens_eval(e, (const bool*)all.data(), alpha.data(), e->loss_hist + (size_t)s * K * 3)) return rc;
+  }
+  std::vector<double> h((size_t)n_steps * K * 3);
+  HIPCHK(hipMemcpyAsync(h.data(), e->loss_hist, h.size() * 8, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (losses)
+    for (size_t i = 0; i < (size_t)n_steps * K; ++i) losses[i] = h[3 * i] + h[3 * i + 1] + h[3 * i + 2];
+  return 0;
+}
+
+int pinn_ens_lbfgs_begin(pinn_ens* e, int n_corr, double tol_fun, double tol_x, double max_eval, double lr,
+                         const double* lr_k, int max_iter, const int* max_iter_k) {
+  REQUIRE(e, "null");
+  REQUIRE(n_corr >= 1, "bad L-BFGS arguments");
+  for (int k = 0; k < e->K; ++k) {
+    REQUIRE((lr_k ? lr_k[k] : lr) > 0 && (max_iter_k ? max_iter_k[k] : max_iter) >= 0,
+            "bad L-BFGS arguments for member %d", k);
+  }
+  HIPCHK(hipSetDevice(e->base->device));
+  std::vector<char> ev((size_t)e->K, 0);
+  bool any = false;
+  for (int k = 0; k < e->K; ++k) {
+    bool eval = false;
+    if (int rc = lbfgs_begin_setup(e->mem[k], max_iter_k ? max_iter_k[k] : max_iter, lr_k ? lr_k[k] : lr, n_corr,
+                                   tol_fun, tol_x, max_eval, &eval)) return rc;
+    ev[k] = eval;
+    any = any || eval;
+  }
+  if (!any) return 0;
+  if (int rc = ens_eval(e, (const bool*)ev.data(), nullptr, nullptr)) return rc;     // custom_lbfgs.py:65
+  for (int k = 0; k < e->K; ++k)
+    if (ev[k]) { if (int rc = lbfgs_begin_post(e->mem[k])) return rc; }
+  return 0;
+}
+
+int pinn_ens_lbfgs_run(pinn_ens* e, int n_iters, int* iters, double* losses, int* n_logged, int* done) {
+  REQUIRE(e && n_iters >= 0, "bad arguments");
+  for (pinn_ctx* c : e->mem) {
+    REQUIRE(c->lb_ready, "pinn_ens_lbfgs_begin has not been called");
+    REQUIRE(pend_outstanding(c) == 0, "chunks in flight");
+  }
+  HIPCHK(hipSetDevice(e->base->device));
+  const Range rg("pinn_ens_lbfgs_run");
+  const int K = e->K;
+  std::vector<pinn_ctx::Pending*> pend(K, nullptr);
+  std::vector<int> window(K, 0), ticket(K, 0);
+  for (int k = 0; k < K; ++k)
+    if (int rc = lbfgs_open(e->mem[k], n_iters, &ticket[k], &pend[k], &window[k])) return rc;
+  std::vector<char> act(K, 0);
+  for (int s = 0; s < n_iters; ++s) {          // pinn_lbfgs_run's loop, member by member, one evaluation for all
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+      pinn_ctx* c = e->mem[k];
+      act[k] = 0;
+      if (!pend[k] || c->lb_iters_issued >= c->lb_max_iter) continue;
+      bool eval = false;
+      if (int rc = lbfgs_iter(c, &eval)) return rc;
+      act[k] = eval;
+      any = any || eval;
+    }
+    if (!any) break;
+    if (int rc = ens_eval(e, (const bool*)act.data(), nullptr, nullptr)) return rc;
+    for (int k = 0; k < K; ++k) if (act[k]) lbfgs_behind(e->mem[k]);
+  }
+  const int cap = n_iters + 1;
+  for (int k = 0; k < K; ++k) {
+    pinn_ctx* c = e->mem[k];
+    if (pend[k]) { if (int rc = lbfgs_close(c, pend[k], window[k], &ticket[k])) return rc; }
+    int nl = 0, dn = 0;
+    if (int rc = lbfgs_collect(c, ticket[k], cap, iters ? iters + (size_t)k * cap : nullptr,
+                               losses ? losses + (size_t)k * cap : nullptr, &nl, &dn)) return rc;
+    if (n_logged) n_logged[k] = nl;
+    if (done) done[k] = dn;
+  }
+  return 0;
+}
+
+int pinn_ens_predict(pinn_ens* e, const double* X, int64_t n, double* out) {
+  REQUIRE(e && X && out && n >= 0, "bad arguments");
+  for (int k = 0; k < e->K; ++k)
+    if (int rc = pinn_predict(e->mem[k], X, n, out + (size_t)k * n)) return rc;
+  return 0;
+}
+
+int pinn_ens_error_l2(pinn_ens* e, const double* X, const double* ref, int64_t n, double* err) {
+  REQUIRE(e && X && ref && err && n > 0, "bad arguments");
+  for (int k = 0; k < e->K; ++k)
+    if (int rc = pinn_error_l2(e->mem[k], X, ref, n, 0, err + k)) return rc;
+  return 0;
+}
+
+int pinn_ens_get_status(pinn_ens* e, int64_t* n_evals, int64_t* first_nonfinite_eval) {
+  REQUIRE(e, "null");
+  for (int k = 0; k < e->K; ++k) {
+    int64_t a = 0, b = 0;
+    if (int rc = pinn_get_status(e->mem[k], &a, &b)) return rc;
+    if (n_evals) n_evals[k] = a;
+    if (first_nonfinite_eval) first_nonfinite_eval[k] = b;
+  }
   return 0;
 }
 

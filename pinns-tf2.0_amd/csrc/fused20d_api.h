@@ -34,4 +34,10 @@ int fused20d_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const dou
                         double* part, int R, int n_wg, const int* row_index, hipStream_t stream,
                         long long* stamps, hipEvent_t ev_start, hipEvent_t ev_stop);
 
+// the same for n_members weight vectors fused20d_weight_doubles(n_theta) apart (an ensemble sharing the point set): member
+// m's n_wg gradient rows at part + m * n_wg * R, each bit-identical to a solo launch's
+int fused20d_ens_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
+                            const double* ts, const double* tgt, double lbx, double lbt, double sx, double st, double nu,
+                            double* part, int R, int n_wg, int n_members, const int* row_index, hipStream_t stream);
+
 }  // namespace pinn

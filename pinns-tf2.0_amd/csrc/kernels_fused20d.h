@@ -187,7 +187,11 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
 
 // ONE_TILE: the launch has at least as many workgroups as tiles: every gradient block is produced exactly once, so
 // it is stored, not accumulated (no LDS read-modify-write), and there is no loop-carried coordinate prefetch.
-template <int PDE, int H, bool ONE_TILE>
+// ENS: ensemble launch, grid (n_wg, members) over a shared point set: member m = blockIdx.y reads its weights at
+// th + m * fused20d_weight_doubles(n_theta) and writes its gradient rows at part + m * gridDim.x * R; everything else is the
+// solo kernel's, so a member's rows are bit-identical to those of a solo launch with the same n_wg.  (A template flag, not a
+// wrapper around a shared body: the wrapper changed the schedule of the solo instantiations.)
+template <int PDE, int H, bool ONE_TILE, bool ENS = false>
 __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th, const double* __restrict__ xs,
                                                   const double* __restrict__ ts, const double* __restrict__ tgt,
                                                   double* __restrict__ part, const int* __restrict__ row_index, int R,
@@ -204,6 +208,10 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   double* const wl = reinterpret_cast<double*>(lds_raw);
   const int nwp = (nd.n_theta + 127) / 128 * 128;
+  if constexpr (ENS) {
+    th += (size_t)blockIdx.y * nwp;
+    part += (size_t)blockIdx.y * gridDim.x * R;
+  }
   double* const gacc_all = wl + nwp;                  // tile loop: 4 x NBLK x 16 accumulators; one tile: 2 staging buffers
   double* const lacc_all = gacc_all + (ONE_TILE ? 2 * FUSED20D_STAGE_BUF : 4 * NBLK * 16);
 
@@ -791,6 +799,30 @@ inline int fused20d_launch(const NetDesc& nd, const SetDesc& sd, const double* t
   else
     hipLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles, lbx,
                        lbt, sx, st, nu, sd, stamps, w20_desc(H, PDE == 1));
+  return (int)hipGetLastError();
+}
+
+// one evaluation of n_members weight vectors on the shared point set: the solo launch plan (n_wg, one-tile or tile loop)
+// per member, grid (n_wg, n_members); returns a hipError_t
+template <int PDE, int H>
+inline int fused20d_ens_launch(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
+                               const double* tgt, double lbx, double lbt, double sx, double st, double nu, double* part,
+                               int R, int n_wg, int n_members, const int* row_index, hipStream_t stream) {
+  if (!w20_layout_ok(nd, H, PDE == 1)) return (int)hipErrorInvalidValue;
+  const size_t lds = fused20d_lds_bytes(H, nd.n_theta);
+  static unsigned long long attr_set = 0;
+  if (first_call_on_device(attr_set)) {
+    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, false, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  const int n_tiles = sd.n_pad / 64;
+  auto* const kern = n_wg >= n_tiles ? k_fused20d<PDE, H, true, true> : k_fused20d<PDE, H, false, true>;
+  hipLaunchKernelGGL(kern, dim3(n_wg, n_members), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles,
+                     lbx, lbt, sx, st, nu, sd, (long long*)nullptr, w20_desc(H, PDE == 1));
   return (int)hipGetLastError();
 }
 

@@ -224,6 +224,65 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce_adam(const real* __restr
   finish(c, g);
 }
 
+// ---- ensembles: K members sharing the point set, float64, kernel path 7 (grid.y = member) ------------------------------
+// The member kernels below are k_reduce_rows / k_reduce_adam with per-member bases and the same per-column arithmetic, so a
+// member's gradient, moments and weights are bit-identical to a solo engine's.  Layouts: part [K][n_rows][R], gl [K][R],
+// theta / m / v [K][n], theta_r [K][sw] (sw = fused20d_weight_doubles(n): the LDS-DMA pieces of k_fused20d_ens),
+// loss3 [K][3] (per step), nonfinite [K].
+constexpr int ENS_MAX = 64;
+struct EnsStep {
+  double alpha[ENS_MAX];                  // Adam: the member's step size, formed on the host exactly as adam_issue forms it
+  unsigned long long eval_no[ENS_MAX];    // the member's evaluation number; 0: the member is not reduced by this launch
+};
+
+__global__ __launch_bounds__(RED_THREADS) void k_reduce_rows_ens(const double* __restrict__ part, int n_rows, int R,
+                                                                 double* __restrict__ gl, int n_theta,
+                                                                 unsigned long long* __restrict__ nonfinite, EnsStep es) {
+  __shared__ double sh[RED_SLICES][RED_COLS];
+  const int mem = blockIdx.y;
+  const unsigned long long eval_no = es.eval_no[mem];
+  if (eval_no == 0) return;
+  part += (size_t)mem * n_rows * R;
+  gl += (size_t)mem * R;
+  const int q = threadIdx.x >> 6, c = blockIdx.x * RED_COLS + (threadIdx.x & 63);
+  const double g = reduce_column(part, n_rows, R, c, q, sh);
+  if (q == 0 && c < R) { gl[c] = g; note_nonfinite(g, c, n_theta, eval_no, nonfinite + mem); }
+}
+
+__global__ __launch_bounds__(RED_THREADS) void k_reduce_adam_ens(const double* __restrict__ part, int n_rows, int R,
+                                                                 double* __restrict__ gl, int n, int sw,
+                                                                 double* __restrict__ theta, double* __restrict__ theta_r,
+                                                                 double* __restrict__ m, double* __restrict__ v,
+                                                                 double b1, double b2, double eps,
+                                                                 double* __restrict__ loss3,
+                                                                 unsigned long long* __restrict__ nonfinite, EnsStep es) {
+  __shared__ double sh[RED_SLICES][RED_COLS];
+  const int mem = blockIdx.y;
+  const unsigned long long eval_no = es.eval_no[mem];
+  if (eval_no == 0) return;
+  const double alpha = es.alpha[mem];
+  part += (size_t)mem * n_rows * R;
+  gl += (size_t)mem * R;
+  theta += (size_t)mem * n; m += (size_t)mem * n; v += (size_t)mem * n;
+  theta_r += (size_t)mem * sw;
+  const int q = threadIdx.x >> 6, c = blockIdx.x * RED_COLS + (threadIdx.x & 63);
+  const double g = reduce_column(part, n_rows, R, c, q, sh);
+  if (q != 0 || c >= R) return;
+  gl[c] = g;
+  note_nonfinite(g, c, n, eval_no, nonfinite + mem);
+  if (c < n) {
+    const double mi = m[c] + (1.0 - b1) * (g - m[c]);
+    const double vi = v[c] + (1.0 - b2) * (g * g - v[c]);
+    m[c] = mi;
+    v[c] = vi;
+    const double t = theta[c] - alpha * mi / (sqrt(vi) + eps);
+    theta[c] = t;
+    theta_r[c] = t;
+  } else if (loss3 && c < n + 3) {
+    loss3[(size_t)mem * 3 + c - n] = g;
+  }
+}
+
 // TF-2.0 ResourceApplyAdam (reference call site
 // utils/neuralnetwork.py:114): m += (1-b1)(g-m); v += (1-b2)(g^2-v);
 // theta -= alpha*m/(sqrt(v)+eps), alpha = lr*sqrt(1-b2^t)/(1-b1^t) computed by the host.

@@ -219,6 +219,27 @@ _SIGNATURES = {
     "pinn_debug_t16_deal": (ctypes.c_int, [ctypes.c_int, _c_int_p]),
     "pinn_debug_stamps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong),
                                          ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    # ensembles (include/pinn_hip.h: pinn_ens_*)
+    "pinn_ens_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _c_int_p, ctypes.c_int, _c_double_p,
+                                       _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "pinn_ens_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "pinn_ens_size": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, ctypes.POINTER(ctypes.c_int64)]),
+    "pinn_ens_set_collocation": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, ctypes.c_int64]),
+    "pinn_ens_set_data": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int64]),
+    "pinn_ens_set_pde_params": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int]),
+    "pinn_ens_set_weights": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
+    "pinn_ens_get_weights": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
+    "pinn_ens_loss_grad": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p]),
+    "pinn_ens_adam_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, _c_double_p]),
+    "pinn_ens_adam_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_double_p]),
+    "pinn_ens_lbfgs_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_double, _c_double_p, ctypes.c_int, _c_int_p]),
+    "pinn_ens_lbfgs_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_int_p, _c_double_p, _c_int_p, _c_int_p]),
+    "pinn_ens_predict": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, _c_double_p]),
+    "pinn_ens_error_l2": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p]),
+    "pinn_ens_get_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                           ctypes.POINTER(ctypes.c_int64)]),
 }
 
 
@@ -683,3 +704,132 @@ class Engine(object):
         p = ctypes.c_int(0)
         self._check(self._lib.pinn_get_kernel_path(self._h, ctypes.byref(p)))
         return p.value
+
+
+class Ensemble(object):
+    """K members of one float64 Burgers net (kernel path 7) trained side by side on one point set (include/pinn_hip.h:
+    pinn_ens_*).  Everything per member carries a leading K axis; member k ends bit-identical to an Engine trained alone
+    from the same weights with the same calls."""
+
+    MAX_MEMBERS = 64
+
+    def __init__(self, layers, lb, ub, n_members, pde="burgers", dtype="f64", device=0):
+        self._lib = load()
+        self._h = ctypes.c_void_p()
+        if pde not in PDE_KINDS:
+            raise ValueError("pde must be one of %s" % sorted(PDE_KINDS))
+        if dtype not in DTYPES:
+            raise ValueError("dtype must be one of %s" % sorted(DTYPES))
+        self.layers = [int(v) for v in layers]
+        self.pde = pde
+        arr = (ctypes.c_int * len(self.layers))(*self.layers)
+        lb, ub = _f64(lb, (2,)), _f64(ub, (2,))
+        self._check(self._lib.pinn_ens_create(ctypes.byref(self._h), arr, len(self.layers), _dp(lb), _dp(ub),
+                                              PDE_KINDS[pde], DTYPES[dtype], int(device), int(n_members)))
+        k, n = ctypes.c_int(0), ctypes.c_int64(0)
+        self._check(self._lib.pinn_ens_size(self._h, ctypes.byref(k), ctypes.byref(n)))
+        self.n_members, self.n_params = k.value, n.value
+
+    def _check(self, rc):
+        if rc != 0:
+            raise PinnNativeError("libpinn_hip: %s (code %d)" % (
+                self._lib.pinn_last_error().decode(errors="replace"), rc))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.pinn_ens_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- shared point sets and PDE parameters ------------------------------------------------
+    def set_collocation(self, X_f, n_total=None):
+        X_f = _f64(X_f).reshape(-1, 2)
+        self._check(self._lib.pinn_ens_set_collocation(self._h, _dp(X_f), X_f.shape[0],
+                                                       X_f.shape[0] if n_total is None else int(n_total)))
+
+    def set_data(self, X_u, u, n_total=None):
+        X_u = _f64(X_u).reshape(-1, 2)
+        u = _f64(u).reshape(X_u.shape[0], 1)
+        self._check(self._lib.pinn_ens_set_data(self._h, _dp(X_u), _dp(u), X_u.shape[0],
+                                                X_u.shape[0] if n_total is None else int(n_total)))
+
+    def set_pde_params(self, *p):
+        p = _f64(p)
+        self._check(self._lib.pinn_ens_set_pde_params(self._h, _dp(p), p.size))
+
+    # ---- per-member weights --------------------------------------------------------------------
+    def set_weights(self, W):
+        W = _f64(W).reshape(self.n_members, self.n_params)
+        self._check(self._lib.pinn_ens_set_weights(self._h, _dp(W), W.size))
+
+    def get_weights(self):
+        W = np.empty((self.n_members, self.n_params), dtype=np.float64)
+        self._check(self._lib.pinn_ens_get_weights(self._h, _dp(W), W.size))
+        return W
+
+    def loss_grad(self, want_grad=True):
+        """-> losses [K], grads [K, P] (or None), terms [K, 3]"""
+        losses = np.empty(self.n_members, dtype=np.float64)
+        terms = np.empty((self.n_members, 3), dtype=np.float64)
+        grads = np.empty((self.n_members, self.n_params), dtype=np.float64) if want_grad else None
+        self._check(self._lib.pinn_ens_loss_grad(self._h, _dp(losses), _dp(grads) if want_grad else None, _dp(terms)))
+        return losses, grads, terms
+
+    # ---- optimisers ------------------------------------------------------------------------------
+    def adam_init(self, lr, beta1=0.9, beta2=0.999, eps=1e-7):
+        """lr: a number, or one per member"""
+        lr_k = np.broadcast_to(_f64(lr), (self.n_members,)).copy()
+        self._check(self._lib.pinn_ens_adam_init(self._h, float(lr_k[0]), beta1, beta2, eps, _dp(lr_k)))
+
+    def adam_run(self, n_steps):
+        """-> losses [n_steps, K], each member's loss before update i"""
+        losses = np.empty((max(int(n_steps), 1), self.n_members), dtype=np.float64)
+        self._check(self._lib.pinn_ens_adam_run(self._h, int(n_steps), _dp(losses)))
+        return losses[:n_steps]
+
+    def lbfgs_begin(self, max_iter, lr, n_corr, tol_fun, tol_x=1e-19, max_eval=0.0):
+        """max_iter, lr: a number, or one per member; n_corr, tol_fun, tol_x, max_eval are shared"""
+        it_k = np.ascontiguousarray(np.broadcast_to(np.asarray(max_iter, dtype=np.int32), (self.n_members,)))
+        lr_k = np.broadcast_to(_f64(lr), (self.n_members,)).copy()
+        self._check(self._lib.pinn_ens_lbfgs_begin(self._h, int(n_corr), tol_fun, tol_x, max_eval, float(lr_k[0]),
+                                                   _dp(lr_k), int(it_k[0]), it_k.ctypes.data_as(_c_int_p)))
+
+    def lbfgs_run(self, n_iters):
+        """-> (iters, losses, done): lists of K arrays of the log entries each member produced, done [K]"""
+        K, cap = self.n_members, int(n_iters) + 1
+        iters = np.zeros((K, cap), dtype=np.int32)
+        losses = np.zeros((K, cap), dtype=np.float64)
+        n_logged, done = np.zeros(K, dtype=np.int32), np.zeros(K, dtype=np.int32)
+        self._check(self._lib.pinn_ens_lbfgs_run(self._h, int(n_iters), iters.ctypes.data_as(_c_int_p), _dp(losses),
+                                                 n_logged.ctypes.data_as(_c_int_p), done.ctypes.data_as(_c_int_p)))
+        return ([iters[k, :n_logged[k]].copy() for k in range(K)], [losses[k, :n_logged[k]].copy() for k in range(K)],
+                done)
+
+    # ---- evaluation ------------------------------------------------------------------------------
+    def predict(self, X):
+        """-> [K, n, 1]"""
+        X = _f64(X).reshape(-1, 2)
+        out = np.empty((self.n_members, X.shape[0], 1), dtype=np.float64)
+        self._check(self._lib.pinn_ens_predict(self._h, _dp(X), X.shape[0], _dp(out)))
+        return out
+
+    def error_l2(self, X, ref):
+        """-> [K] relative L2 errors of each member's prediction at X against ref"""
+        X = _f64(X).reshape(-1, 2)
+        ref = _f64(ref).reshape(X.shape[0], 1)
+        err = np.empty(self.n_members, dtype=np.float64)
+        self._check(self._lib.pinn_ens_error_l2(self._h, _dp(X), _dp(ref), X.shape[0], _dp(err)))
+        return err
+
+    def status(self):
+        """-> (evaluations [K], first non-finite evaluation [K], 0 = none)"""
+        n = np.zeros(self.n_members, dtype=np.int64)
+        bad = np.zeros(self.n_members, dtype=np.int64)
+        self._check(self._lib.pinn_ens_get_status(self._h, n.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                  bad.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return n, bad

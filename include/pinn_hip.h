@@ -245,7 +245,8 @@ int pinn_debug_t16_deal(int W, int* out49);
  * same weights with the same calls.  One evaluation of all members = one loss+gradient launch with a member grid dimension
  * + one member-batched reduction.  Per-member arrays are member-major: weights [K][P], gradients [K][P], terms [K][3].
  * Device memory per member, N_f = 10^4, 8 x 20: ~3.8 MB of gradient rows + ~2.5 MB of L-BFGS rings (n_corr = 50) + the
- * member's small per-context buffers (~6.5 MB); the point sets are held once.  Calls are synchronous.
+ * member's small per-context buffers (~6.5 MB); the point sets are held once (shared mode; per-member sets, below, add
+ * K x n_pad x 24 B: 15 MB at K = 64, N_f = 10^4).  Calls are synchronous.
  * pinn_ens_create refuses float32, Schrodinger, discrete-time models and other shapes with PINN_EUNSUPPORTED and
  * K outside 1..64 with PINN_EINVAL, before touching a device; an ensemble has no communicator.  (Additive: the ABI
  * version stays 6; callers detect the feature by the presence of the symbols.) */
@@ -280,6 +281,23 @@ int pinn_ens_predict(pinn_ens* e, const double* X, int64_t n, double* out);
 int pinn_ens_error_l2(pinn_ens* e, const double* X, const double* ref, int64_t n, double* err);
 /* pinn_get_status per member: n_evals [K], first_nonfinite_eval [K] (either may be NULL) */
 int pinn_ens_get_status(pinn_ens* e, int64_t* n_evals, int64_t* first_nonfinite_eval);
+
+/* Per-member point sets and viscosities (parameter sweeps, bagged ensembles, per-epoch resampling).  An ensemble starts
+ * in shared mode; the first call below switches it to per-member mode, where member k has its own data, collocation set
+ * and nu, held member-major ([K][n_pad] per coordinate), and the shared setters above broadcast (the same set or nu in
+ * every member's slots).  Every member has the same counts n and totals n_total, so all share one launch plan; a call
+ * whose counts differ from the sets in place rebuilds them as a pinn_ctx does.  Member k stays bit-identical to a
+ * pinn_ctx given member k's points, data, nu and seeds with the same calls.  Arrays are member-major: X_f [K][n][2],
+ * X_u [K][n][2], u [K][n], nu [K], seeds [K].  Refusals (PINN_EINVAL, nothing changed): null arrays, n_members != K,
+ * n, count or n_design out of range, collocation points or a Latin hypercube for identification (pde 1, which has no
+ * collocation set; its nu is accepted and unused, as by pinn_set_pde_params).  (Named pinn_ensk_: additive, detected
+ * by the presence of the symbols.) */
+int pinn_ensk_set_collocation(pinn_ens* e, const double* X_f, int64_t n, int64_t n_total);
+int pinn_ensk_set_data(pinn_ens* e, const double* X_u, const double* u, int64_t n, int64_t n_total);
+int pinn_ensk_set_pde_params(pinn_ens* e, const double* nu, int n_members);
+/* pinn_lhs_collocation for every member in one launch: points [first, first + count) of the n_design-point design with
+ * seed seeds[k] become member k's collocation set */
+int pinn_ensk_lhs_collocation(pinn_ens* e, int64_t n_design, int64_t first, int64_t count, const uint64_t* seeds);
 
 #ifdef __cplusplus
 }

@@ -2278,6 +2278,15 @@ struct pinn_ens {
   size_t cap_part = 0;
   double* loss_hist = nullptr;                 // Adam: [steps][K][3]
   size_t cap_loss = 0;
+  // per-member point sets and viscosities (pinn_ensk_*).  Off (shared mode) until the first per-member call; then the
+  // members' sets live here, member-major, while the base keeps member 0's, so that ensure_sets(base) still gives the
+  // SetDesc and the launch plan (every member has the same counts).  The shared setters broadcast in this mode.
+  bool k_mode = false, k_dirty = true, k_nu_dirty = true;
+  std::vector<double> kXf, kXu, kU;            // [K][n_f][2], [K][n_u][2], [K][n_u], as handed over
+  std::vector<uint64_t> k_seeds;               // [K] device LHS seeds (the design geometry is the base's lhs)
+  std::vector<double> k_nu;                    // [K]
+  double *k_xs = nullptr, *k_ts = nullptr, *k_tgt = nullptr, *k_nud = nullptr;   // [K][n_pad] x 3, [K]
+  size_t k_cap = 0;
 };
 
 static void ens_free(pinn_ens* e) {
@@ -2288,10 +2297,86 @@ static void ens_free(pinn_ens* e) {
     (void)pinn_destroy(c);
   }
   if (e->base) { (void)hipSetDevice(e->base->device); (void)hipStreamSynchronize(e->base->stream); }
-  void* ptrs[] = {e->theta, e->theta_r, e->gl, e->m, e->v, e->nonfinite, e->part, e->loss_hist};
+  void* ptrs[] = {e->theta, e->theta_r, e->gl, e->m, e->v, e->nonfinite, e->part, e->loss_hist, e->k_xs, e->k_ts,
+                  e->k_tgt, e->k_nud};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (e->base) (void)pinn_destroy(e->base);
   delete e;
+}
+
+// shared -> per-member mode: every member starts from the shared sets and viscosity
+static void ens_to_k(pinn_ens* e) {
+  if (e->k_mode) return;
+  pinn_ctx* b = e->base;
+  const size_t K = e->K;
+  e->kXf.clear(); e->kXu.clear(); e->kU.clear();
+  for (size_t k = 0; k < K; ++k) {
+    e->kXf.insert(e->kXf.end(), b->Xf.begin(), b->Xf.end());
+    e->kXu.insert(e->kXu.end(), b->Xu.begin(), b->Xu.end());
+    e->kU.insert(e->kU.end(), b->U.begin(), b->U.end());
+  }
+  e->k_seeds.assign(K, b->lhs.seed);
+  e->k_nu.assign(K, b->nu);
+  e->k_mode = true; e->k_dirty = true; e->k_nu_dirty = true;
+}
+
+// the device LHS of every member in one launch: member k's collocation slots <- points [first, first + count) of the
+// design with seed k_seeds[k], each bit-identical to lhs_fill of a solo context with that seed
+static int ens_lhs_fill(pinn_ens* e) {
+  pinn_ctx* b = e->base;
+  const int64_t cnt = b->lhs.count;
+  if (cnt <= 0) return 0;
+  const size_t off = (size_t)(2 * b->sd.n_b + b->sd.n_u);      // off + cnt <= n_pad: inside member k's slice
+  const uint64_t n = (uint64_t)b->lhs.n_design;
+  LhsSeeds sd{};
+  for (int k = 0; k < e->K; ++k) { sd.lo[k] = (uint32_t)e->k_seeds[k]; sd.hi[k] = (uint32_t)(e->k_seeds[k] >> 32); }
+  const dim3 grid((unsigned)((cnt + 255) / 256), (unsigned)e->K), block(256);
+  hipLaunchKernelGGL(k_lhs_fill_ens, grid, block, 0, b->stream, e->k_xs + off, e->k_ts + off, (int64_t)b->sd.n_pad, cnt,
+                     (uint64_t)b->lhs.first, n, lhs_half_bits(n), sd, b->lb[0], b->lb[1], b->ub[0] - b->lb[0],
+                     b->ub[1] - b->lb[1]);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ensure_sets for the ensemble: the base's SetDesc and plan, then (per-member mode) the [K][n_pad] sets, assembled as
+// ensure_sets assembles one: [data | collocation | pad]
+static int ens_ensure_sets(pinn_ens* e) {
+  pinn_ctx* b = e->base;
+  if (b->sets_dirty) e->k_dirty = true;
+  if (int rc = ensure_sets(b)) return rc;
+  if (!e->k_mode) return 0;
+  const size_t K = e->K;
+  if (!e->k_nud) {
+    if (dev_alloc(&e->k_nud, K * 8)) return PINN_EHIP;
+    e->k_nu_dirty = true;
+  }
+  if (e->k_nu_dirty) {
+    if (upload_real(b, e->k_nud, e->k_nu.data(), K)) return PINN_EHIP;
+    e->k_nu_dirty = false;
+  }
+  if (!e->k_dirty) return 0;
+  const SetDesc& sd = b->sd;
+  const size_t n_pad = sd.n_pad, n_u = sd.n_u, n_f = sd.n_f;
+  std::vector<double> hx(K * n_pad), ht(K * n_pad), htg(K * n_pad, 0.0);
+  for (size_t k = 0; k < K; ++k) {
+    double *x = hx.data() + k * n_pad, *t = ht.data() + k * n_pad, *tg = htg.data() + k * n_pad;
+    const double *xu = e->kXu.data() + k * 2 * n_u, *u = e->kU.data() + k * n_u, *xf = e->kXf.data() + k * 2 * n_f;
+    size_t g = 0;
+    for (size_t i = 0; i < n_u; ++i, ++g) { x[g] = xu[2 * i]; t[g] = xu[2 * i + 1]; tg[g] = u[i]; }
+    if (!b->lhs.on)
+      for (size_t i = 0; i < n_f; ++i, ++g) { x[g] = xf[2 * i]; t[g] = xf[2 * i + 1]; }
+    for (; g < n_pad; ++g) { x[g] = b->lb[0]; t[g] = b->lb[1]; }  // inert padding; LHS slots filled below
+  }
+  if (K * n_pad > e->k_cap) {
+    if (dev_alloc(&e->k_xs, K * n_pad * 8) || dev_alloc(&e->k_ts, K * n_pad * 8) || dev_alloc(&e->k_tgt, K * n_pad * 8))
+      return PINN_EHIP;
+    e->k_cap = K * n_pad;
+  }
+  if (upload_real(b, e->k_xs, hx.data(), K * n_pad) || upload_real(b, e->k_ts, ht.data(), K * n_pad) ||
+      upload_real(b, e->k_tgt, htg.data(), K * n_pad)) return PINN_EHIP;
+  if (b->lhs.on) { if (int rc = ens_lhs_fill(e)) return rc; }
+  e->k_dirty = false;
+  return 0;
 }
 
 // one evaluation of every member at its current weights.  active[k] = false: member k's rows are computed but not reduced
@@ -2299,13 +2384,17 @@ static void ens_free(pinn_ens* e) {
 // loss3 <- [K][3] loss parts.
 static int ens_eval(pinn_ens* e, const bool* active, const double* alpha, double* loss3) {
   pinn_ctx* b = e->base;
-  if (int rc = ensure_sets(b)) return rc;
+  if (int rc = ens_ensure_sets(e)) return rc;
   const size_t need = (size_t)e->K * b->n_wg * b->R;
   if (need > e->cap_part) { if (dev_alloc(&e->part, need * 8)) return PINN_EHIP; e->cap_part = need; }
   const double sx = 2.0 / (b->ub[0] - b->lb[0]), st = 2.0 / (b->ub[1] - b->lb[1]);
-  const int rc = fused20d_ens_launch_any(b->pde, b->nd, b->sd, e->theta_r, (const double*)b->xs, (const double*)b->ts,
-                                         (const double*)b->tgt, b->lb[0], b->lb[1], sx, st, b->nu, e->part, b->R,
-                                         b->n_wg, e->K, b->row_index, b->stream);
+  const int rc =
+      e->k_mode ? fused20d_ens_sets_launch_any(b->pde, b->nd, b->sd, e->theta_r, e->k_xs, e->k_ts, e->k_tgt, b->lb[0],
+                                               b->lb[1], sx, st, e->k_nud, e->part, b->R, b->n_wg, e->K, b->row_index,
+                                               b->stream)
+                : fused20d_ens_launch_any(b->pde, b->nd, b->sd, e->theta_r, (const double*)b->xs, (const double*)b->ts,
+                                          (const double*)b->tgt, b->lb[0], b->lb[1], sx, st, b->nu, e->part, b->R,
+                                          b->n_wg, e->K, b->row_index, b->stream);
   if (rc) return fail(PINN_EHIP, "ensemble fused20d launch failed: %s", hipGetErrorString((hipError_t)rc));
   EnsStep es{};
   for (int k = 0; k < e->K; ++k) {
@@ -2389,19 +2478,91 @@ int pinn_ens_size(pinn_ens* e, int* n_members, int64_t* n_params) {
   return 0;
 }
 
+// (per-member mode: the shared setters broadcast -- the same set or viscosity in every member's slots)
 int pinn_ens_set_collocation(pinn_ens* e, const double* X_f, int64_t n, int64_t n_total) {
   REQUIRE(e, "null");
-  return pinn_set_collocation(e->base, X_f, n, n_total);
+  if (int rc = pinn_set_collocation(e->base, X_f, n, n_total)) return rc;
+  if (e->k_mode) {
+    e->kXf.clear();
+    for (int k = 0; k < e->K; ++k) e->kXf.insert(e->kXf.end(), X_f, X_f + 2 * n);
+    e->k_dirty = true;
+  }
+  return 0;
 }
 
 int pinn_ens_set_data(pinn_ens* e, const double* X_u, const double* u, int64_t n, int64_t n_total) {
   REQUIRE(e, "null");
-  return pinn_set_data(e->base, X_u, u, n, n_total);
+  if (int rc = pinn_set_data(e->base, X_u, u, n, n_total)) return rc;
+  if (e->k_mode) {
+    e->kXu.clear(); e->kU.clear();
+    for (int k = 0; k < e->K; ++k) { e->kXu.insert(e->kXu.end(), X_u, X_u + 2 * n); e->kU.insert(e->kU.end(), u, u + n); }
+    e->k_dirty = true;
+  }
+  return 0;
 }
 
 int pinn_ens_set_pde_params(pinn_ens* e, const double* p, int n) {
   REQUIRE(e, "null");
-  return pinn_set_pde_params(e->base, p, n);
+  if (int rc = pinn_set_pde_params(e->base, p, n)) return rc;
+  if (e->k_mode) { e->k_nu.assign((size_t)e->K, p[0]); e->k_nu_dirty = true; }
+  return 0;
+}
+
+// per-member sets (every refusal before anything changes)
+static constexpr int64_t ENSK_MAX_POINTS = (int64_t)1 << 30;
+
+int pinn_ensk_set_collocation(pinn_ens* e, const double* X_f, int64_t n, int64_t n_total) {
+  REQUIRE(e && X_f, "null argument");
+  REQUIRE(n >= 0 && n <= ENSK_MAX_POINTS && n_total >= n, "bad collocation arguments (n %lld, n_total %lld)",
+          (long long)n, (long long)n_total);
+  REQUIRE(e->base->pde != PINN_PDE_BURGERS_IDE || n == 0,
+          "identification evaluates the residual at the data points; no collocation set");
+  ens_to_k(e);
+  if (int rc = pinn_set_collocation(e->base, X_f, n, n_total)) return rc;     // member 0's: the SetDesc and the plan
+  e->kXf.assign(X_f, X_f + (size_t)e->K * 2 * n);
+  e->k_dirty = true;
+  return 0;
+}
+
+int pinn_ensk_set_data(pinn_ens* e, const double* X_u, const double* u, int64_t n, int64_t n_total) {
+  REQUIRE(e && X_u && u, "null argument");
+  REQUIRE(n >= 0 && n <= ENSK_MAX_POINTS && n_total >= n, "bad data arguments (n %lld, n_total %lld)", (long long)n,
+          (long long)n_total);
+  ens_to_k(e);
+  if (int rc = pinn_set_data(e->base, X_u, u, n, n_total)) return rc;
+  e->kXu.assign(X_u, X_u + (size_t)e->K * 2 * n);
+  e->kU.assign(u, u + (size_t)e->K * n);
+  e->k_dirty = true;
+  return 0;
+}
+
+int pinn_ensk_set_pde_params(pinn_ens* e, const double* nu, int n_members) {
+  REQUIRE(e && nu, "null argument");
+  REQUIRE(n_members == e->K, "%d viscosities for %d members", n_members, e->K);
+  ens_to_k(e);
+  if (int rc = pinn_set_pde_params(e->base, nu, 1)) return rc;      // (identification: accepted and unused, as solo)
+  e->k_nu.assign(nu, nu + e->K);
+  e->k_nu_dirty = true;
+  return 0;
+}
+
+int pinn_ensk_lhs_collocation(pinn_ens* e, int64_t n_design, int64_t first, int64_t count, const uint64_t* seeds) {
+  REQUIRE(e && seeds, "null argument");
+  pinn_ctx* b = e->base;
+  REQUIRE(b->pde != PINN_PDE_BURGERS_IDE, "pinn_ensk_lhs_collocation: this model has no collocation set");
+  REQUIRE(n_design >= 1 && first >= 0 && count >= 0 && first + count <= n_design && count <= (1 << 30),
+          "bad design geometry (n_design %lld, first %lld, count %lld)", (long long)n_design, (long long)first,
+          (long long)count);
+  HIPCHK(hipSetDevice(b->device));
+  // re-draw in place (one launch, nothing rebuilt) when only the seeds change, as pinn_lhs_collocation does
+  const bool in_place = e->k_mode && !e->k_dirty && !b->sets_dirty && b->lhs.on && b->lhs.count == count;
+  ens_to_k(e);
+  if (int rc = pinn_lhs_collocation(b, n_design, first, count, seeds[0])) return rc;
+  e->k_seeds.assign(seeds, seeds + e->K);
+  e->kXf.clear();
+  if (in_place && !b->sets_dirty) return ens_lhs_fill(e);
+  e->k_dirty = true;
+  return 0;
 }
 
 int pinn_ens_set_weights(pinn_ens* e, const double* w, int64_t n) {

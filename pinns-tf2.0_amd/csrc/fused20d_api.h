@@ -40,4 +40,11 @@ int fused20d_ens_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const
                             const double* ts, const double* tgt, double lbx, double lbt, double sx, double st, double nu,
                             double* part, int R, int n_wg, int n_members, const int* row_index, hipStream_t stream);
 
+// the same with a point set per member -- xs, ts, tgt [n_members][sd.n_pad], all of one SetDesc -- and nu_k [n_members]
+// in device memory: member m's rows bit-identical to a solo launch on member m's set with viscosity nu_k[m]
+int fused20d_ens_sets_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
+                                 const double* ts, const double* tgt, double lbx, double lbt, double sx, double st,
+                                 const double* nu_k, double* part, int R, int n_wg, int n_members, const int* row_index,
+                                 hipStream_t stream);
+
 }  // namespace pinn

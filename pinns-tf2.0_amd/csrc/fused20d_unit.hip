@@ -52,4 +52,18 @@ int fused20d_ens_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const
 #undef ARGS
 }
 
+int fused20d_ens_sets_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
+                                 const double* ts, const double* tgt, double lbx, double lbt, double sx, double st,
+                                 const double* nu_k, double* part, int R, int n_wg, int n_members, const int* row_index,
+                                 hipStream_t stream) {
+#define ARGS nd, sd, th, xs, ts, tgt, lbx, lbt, sx, st, nu_k, part, R, n_wg, n_members, row_index, stream
+  switch (nd.n_hidden) {
+    case 4: return pde == 1 ? fused20d_ens_launch<1, 4, true>(ARGS) : fused20d_ens_launch<0, 4, true>(ARGS);
+    case 6: return pde == 1 ? fused20d_ens_launch<1, 6, true>(ARGS) : fused20d_ens_launch<0, 6, true>(ARGS);
+    case 8: return pde == 1 ? fused20d_ens_launch<1, 8, true>(ARGS) : fused20d_ens_launch<0, 8, true>(ARGS);
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef ARGS
+}
+
 }  // namespace pinn

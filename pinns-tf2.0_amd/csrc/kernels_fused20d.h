@@ -40,6 +40,7 @@
 // tape of utils/neuralnetwork.py:55-59; identification (PDE == 1): 1d-burgers/ide_cont_burgers.py:56-91.
 #pragma once
 #include <hip/hip_ext.h>
+#include <type_traits>
 #include "kernels_fused20.h"
 #include "fused20d_api.h"
 
@@ -191,12 +192,21 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
 // th + m * fused20d_weight_doubles(n_theta) and writes its gradient rows at part + m * gridDim.x * R; everything else is the
 // solo kernel's, so a member's rows are bit-identical to those of a solo launch with the same n_wg.  (A template flag, not a
 // wrapper around a shared body: the wrapper changed the schedule of the solo instantiations.)
-template <int PDE, int H, bool ONE_TILE, bool ENS = false>
+// SETS (with ENS): every member has its own point set of the common SetDesc -- member m reads xs, ts and tgt at
+// m * sd.n_pad -- and its own viscosity, nu[m] of a device array [members] passed in the slot of the scalar (a pointer
+// has the size and alignment of a double, so the argument layout of every instantiation is the same).
+template <bool SETS> using f20d_nu_t = typename std::conditional<SETS, const double*, double>::type;
+__device__ __forceinline__ double f20d_nu(double nu) { return nu; }
+__device__ __forceinline__ double f20d_nu(const double* nu) { return nu[blockIdx.y]; }   // wave-uniform
+
+template <int PDE, int H, bool ONE_TILE, bool ENS = false, bool SETS = false>
 __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th, const double* __restrict__ xs,
                                                   const double* __restrict__ ts, const double* __restrict__ tgt,
                                                   double* __restrict__ part, const int* __restrict__ row_index, int R,
-                                                  int n_tiles, double lbx, double lbt, double sx, double st, double nu,
-                                                  SetDesc sd, long long* __restrict__ stamps, W20Desc nd_arg) {
+                                                  int n_tiles, double lbx, double lbt, double sx, double st,
+                                                  f20d_nu_t<SETS> nu, SetDesc sd, long long* __restrict__ stamps,
+                                                  W20Desc nd_arg) {
+  static_assert(ENS || !SETS, "per-member point sets are an ensemble launch");
   // weight offsets: compile-time constants in the one-tile variant (immediate operands; Adam step 41.9 -> 40.8 us with
   // the preloaded pointers); the tile-loop variant keeps them in SGPRs -- with immediates its schedule came out 9 %
   // slower (N_f = 10^6: 2104 vs 1930 us per step, same box)
@@ -211,6 +221,10 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
   if constexpr (ENS) {
     th += (size_t)blockIdx.y * nwp;
     part += (size_t)blockIdx.y * gridDim.x * R;
+    if constexpr (SETS) {                             // before the first tile's coordinate prefetch below
+      const size_t po = (size_t)blockIdx.y * sd.n_pad;
+      xs += po; ts += po; tgt += po;
+    }
   }
   double* const gacc_all = wl + nwp;                  // tile loop: 4 x NBLK x 16 accumulators; one tile: 2 staging buffers
   double* const lacc_all = gacc_all + (ONE_TILE ? 2 * FUSED20D_STAGE_BUF : 4 * NBLK * 16);
@@ -265,7 +279,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  double c1 = 1.0, c2 = nu;
+  double c1 = 1.0, c2 = f20d_nu(nu);
   if (PDE == 1) { c1 = wl[nd.n_net]; c2 = exp(wl[nd.n_net + 1]); }
   const double inv_nf = sd.inv_nf, inv_nu = sd.inv_nu;
   // per-lane partial sums of the loss parts and of the two lambda gradients (slot-0 lanes only) live in LDS, four
@@ -802,25 +816,26 @@ inline int fused20d_launch(const NetDesc& nd, const SetDesc& sd, const double* t
   return (int)hipGetLastError();
 }
 
-// one evaluation of n_members weight vectors on the shared point set: the solo launch plan (n_wg, one-tile or tile loop)
-// per member, grid (n_wg, n_members); returns a hipError_t
-template <int PDE, int H>
+// one evaluation of n_members weight vectors on the shared point set (SETS: on [n_members][sd.n_pad] point sets, with
+// nu [n_members] on the device): the solo launch plan (n_wg, one-tile or tile loop) per member, grid (n_wg, n_members);
+// returns a hipError_t
+template <int PDE, int H, bool SETS = false>
 inline int fused20d_ens_launch(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
-                               const double* tgt, double lbx, double lbt, double sx, double st, double nu, double* part,
-                               int R, int n_wg, int n_members, const int* row_index, hipStream_t stream) {
+                               const double* tgt, double lbx, double lbt, double sx, double st, f20d_nu_t<SETS> nu,
+                               double* part, int R, int n_wg, int n_members, const int* row_index, hipStream_t stream) {
   if (!w20_layout_ok(nd, H, PDE == 1)) return (int)hipErrorInvalidValue;
   const size_t lds = fused20d_lds_bytes(H, nd.n_theta);
   static unsigned long long attr_set = 0;
   if (first_call_on_device(attr_set)) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, false, true>,
+    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, false, true, SETS>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
+      e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, true, true, SETS>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
   const int n_tiles = sd.n_pad / 64;
-  auto* const kern = n_wg >= n_tiles ? k_fused20d<PDE, H, true, true> : k_fused20d<PDE, H, false, true>;
+  auto* const kern = n_wg >= n_tiles ? k_fused20d<PDE, H, true, true, SETS> : k_fused20d<PDE, H, false, true, SETS>;
   hipLaunchKernelGGL(kern, dim3(n_wg, n_members), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles,
                      lbx, lbt, sx, st, nu, sd, (long long*)nullptr, w20_desc(H, PDE == 1));
   return (int)hipGetLastError();

@@ -80,4 +80,35 @@ __global__ __launch_bounds__(256) void k_lhs_fill(real* __restrict__ xs, real* _
   ts[t] = (real)tt;
 }
 
+// one seed per ensemble member (kernel argument)
+constexpr int LHS_MEMBERS_MAX = 64;
+struct LhsSeeds {
+  uint32_t lo[LHS_MEMBERS_MAX], hi[LHS_MEMBERS_MAX];
+};
+
+// k_lhs_fill for members m = blockIdx.y with seeds (s.lo[m], s.hi[m]): member m's points at xs/ts + m * stride (float64).
+// The per-point arithmetic is k_lhs_fill's, restated rather than shared: with a common helper hipcc allocated the solo
+// kernel's registers differently.
+__global__ __launch_bounds__(256) void k_lhs_fill_ens(double* __restrict__ xs, double* __restrict__ ts, int64_t stride,
+                                                      int64_t count, uint64_t first, uint64_t n, int half_bits,
+                                                      LhsSeeds s, double lbx, double lbt, double rx, double rt) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= count) return;
+  const int m = blockIdx.y;
+  const uint32_t seed_lo = s.lo[m], seed_hi = s.hi[m];
+  const uint64_t i = first + (uint64_t)t;
+  uint32_t ctr[4] = {(uint32_t)i, (uint32_t)(i >> 32), 0u, 0x4C485321u};
+  philox4x32_10(ctr, seed_lo, seed_hi);
+  const double inv = 1.0 / 9007199254740992.0;             // 2^-53
+  const double u0 = (double)((((uint64_t)ctr[0] << 32) | ctr[1]) >> 11) * inv;
+  const double u1 = (double)((((uint64_t)ctr[2] << 32) | ctr[3]) >> 11) * inv;
+  const uint64_t p0 = lhs_permute(i, n, half_bits, seed_lo ^ 0x243F6A88u, seed_hi ^ 0x85A308D3u);
+  const uint64_t p1 = lhs_permute(i, n, half_bits, seed_lo ^ 0x13198A2Eu, seed_hi ^ 0x03707344u);
+  const double dn = (double)n;
+  const double x = __dadd_rn(lbx, __dmul_rn(rx, __ddiv_rn(__dadd_rn((double)p0, u0), dn)));
+  const double tt = __dadd_rn(lbt, __dmul_rn(rt, __ddiv_rn(__dadd_rn((double)p1, u1), dn)));
+  xs[(size_t)m * stride + t] = x;
+  ts[(size_t)m * stride + t] = tt;
+}
+
 }  // namespace pinn

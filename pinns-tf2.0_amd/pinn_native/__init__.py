@@ -240,6 +240,12 @@ _SIGNATURES = {
     "pinn_ens_error_l2": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p]),
     "pinn_ens_get_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
                                            ctypes.POINTER(ctypes.c_int64)]),
+    # per-member point sets of an ensemble (include/pinn_hip.h: pinn_ensk_*)
+    "pinn_ensk_set_collocation": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, ctypes.c_int64]),
+    "pinn_ensk_set_data": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int64]),
+    "pinn_ensk_set_pde_params": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int]),
+    "pinn_ensk_lhs_collocation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                 ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 
@@ -707,9 +713,10 @@ class Engine(object):
 
 
 class Ensemble(object):
-    """K members of one float64 Burgers net (kernel path 7) trained side by side on one point set (include/pinn_hip.h:
-    pinn_ens_*).  Everything per member carries a leading K axis; member k ends bit-identical to an Engine trained alone
-    from the same weights with the same calls."""
+    """K members of one float64 Burgers net (kernel path 7) trained side by side (include/pinn_hip.h: pinn_ens_*), on one
+    shared point set or, once a per-member set, viscosity or hypercube is given, on one set per member (pinn_ensk_*).
+    Everything per member carries a leading K axis; member k ends bit-identical to an Engine trained alone from the same
+    weights, points and viscosity with the same calls."""
 
     MAX_MEMBERS = 64
 
@@ -746,21 +753,62 @@ class Ensemble(object):
         except Exception:
             pass
 
-    # ---- shared point sets and PDE parameters ------------------------------------------------
+    # ---- point sets and PDE parameters: shared, or one per member ----------------------------------
+    def _per_member(self, a, what, cols):
+        """a [n, cols] (shared) -> (a, False); a [K, n, cols] (one per member) -> (a, True); anything else: ValueError"""
+        a = _f64(a)
+        if a.ndim == 3:
+            if a.shape[0] != self.n_members or a.shape[2] != cols:
+                raise ValueError("%s: per-member array must be [K=%d, n, %d], got %s" % (what, self.n_members, cols,
+                                                                                       a.shape))
+            return a, True
+        if a.size % cols:
+            raise ValueError("%s: array must be [n, %d] (shared) or [K=%d, n, %d] (per member), got %s" % (
+                what, cols, self.n_members, cols, a.shape))
+        return a.reshape(-1, cols), False
+
     def set_collocation(self, X_f, n_total=None):
-        X_f = _f64(X_f).reshape(-1, 2)
-        self._check(self._lib.pinn_ens_set_collocation(self._h, _dp(X_f), X_f.shape[0],
-                                                       X_f.shape[0] if n_total is None else int(n_total)))
+        """X_f [n, 2] for every member, or [K, n, 2]: member k's own set"""
+        X_f, per = self._per_member(X_f, "X_f", 2)
+        n = X_f.shape[-2]
+        nt = n if n_total is None else int(n_total)
+        fn = self._lib.pinn_ensk_set_collocation if per else self._lib.pinn_ens_set_collocation
+        self._check(fn(self._h, _dp(X_f), n, nt))
 
     def set_data(self, X_u, u, n_total=None):
-        X_u = _f64(X_u).reshape(-1, 2)
-        u = _f64(u).reshape(X_u.shape[0], 1)
-        self._check(self._lib.pinn_ens_set_data(self._h, _dp(X_u), _dp(u), X_u.shape[0],
-                                                X_u.shape[0] if n_total is None else int(n_total)))
+        """X_u [n, 2], u [n, 1] for every member, or [K, n, 2], [K, n, 1]: member k's own data"""
+        X_u, per = self._per_member(X_u, "X_u", 2)
+        n = X_u.shape[-2]
+        u = _f64(u)
+        want = (self.n_members, n, 1) if per else (n, 1)
+        if u.size != n * (self.n_members if per else 1) or (per and u.shape[:2] != want[:2]):
+            raise ValueError("u: expected %s to go with X_u %s, got %s" % (want, X_u.shape, u.shape))
+        u = u.reshape(want)
+        nt = n if n_total is None else int(n_total)
+        fn = self._lib.pinn_ensk_set_data if per else self._lib.pinn_ens_set_data
+        self._check(fn(self._h, _dp(X_u), _dp(u), n, nt))
 
     def set_pde_params(self, *p):
+        """nu for every member, or nu [K]: member k's own (identification: accepted and unused)"""
+        if len(p) == 1 and np.ndim(p[0]) == 1:
+            nu = _f64(p[0])
+            if nu.shape != (self.n_members,):
+                raise ValueError("nu: per-member array must be [K=%d], got %s" % (self.n_members, nu.shape))
+            self._check(self._lib.pinn_ensk_set_pde_params(self._h, _dp(nu), nu.size))
+            return
         p = _f64(p)
         self._check(self._lib.pinn_ens_set_pde_params(self._h, _dp(p), p.size))
+
+    def lhs_collocation(self, n_design, seeds, first=0, count=None):
+        """Engine.lhs_collocation for every member in one launch: member k draws points [first, first+count) of the
+        n_design-point Latin hypercube with seed seeds[k]"""
+        seeds = np.asarray(seeds)
+        if seeds.shape != (self.n_members,) or not np.issubdtype(seeds.dtype, np.integer):
+            raise ValueError("seeds: expected [K=%d] integers, got %s %s" % (self.n_members, seeds.shape, seeds.dtype))
+        seeds = np.ascontiguousarray(seeds.astype(np.uint64))
+        count = int(n_design) - int(first) if count is None else int(count)
+        self._check(self._lib.pinn_ensk_lhs_collocation(self._h, int(n_design), int(first), count,
+                                                        seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
 
     # ---- per-member weights --------------------------------------------------------------------
     def set_weights(self, W):

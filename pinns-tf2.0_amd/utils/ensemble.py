@@ -1,14 +1,20 @@
-"""NeuralNetworkEnsemble: K Burgers PINNs trained side by side on one point set (several seeds, a learning-rate sweep,
-repeated identification runs) by one engine ensemble (pinn_native.Ensemble, include/pinn_hip.h pinn_ens_*).
+"""NeuralNetworkEnsemble: K Burgers PINNs trained side by side (several seeds, a learning-rate or viscosity sweep, bagged
+point sets, repeated identification runs) by one engine ensemble (pinn_native.Ensemble, include/pinn_hip.h pinn_ens_* /
+pinn_ensk_*).
 
 Scope: float64, kernel path 7 -- Burgers inference (pde "burgers") and identification ("burgers_ide"), 2-20-...-20-1 nets
-with 4, 6 or 8 hidden layers, one GPU.  The members share the point sets, the PDE parameters and every hyperparameter
-except the per-member overrides in `members`:
+with 4, 6 or 8 hidden layers, one GPU.  The members share every hyperparameter except the per-member overrides in
+`members`:
     seed, init_scale          the initial weights (member k's vector is exactly NeuralNetwork._initial_weights of hp
                               updated with member k's overrides)
     tf_lr, nt_lr, nt_epochs   Adam learning rate, L-BFGS learningRate and maxIter
-fit() follows NeuralNetwork.fit's float64 schedule (Adam tf_epochs, then L-BFGS with the same lbfgs_begin arguments) with no
-restart guard and no resampling; member k ends bit-identical to a NeuralNetwork of its own hp trained alone.
+    nu                        the viscosity (overrides set_pde_params for that member; identification: unused)
+    resample_seed             the member's collocation redraws (hp["resample_every"]): seed resample_seed + epoch
+The point sets are shared, or one per member: set_collocation(X_f) and fit(X_u, u) take [n, 2] / [n, 1] arrays for
+all members or [K, n, 2] / [K, n, 1] arrays, member k's at index k (every member with the same n).
+fit() follows NeuralNetwork.fit's float64 schedule (Adam tf_epochs with NeuralNetwork.tf_optimization's chunks and
+redraws, then L-BFGS with the same lbfgs_begin arguments) with no restart guard; member k ends bit-identical to a
+NeuralNetwork of its own hp trained alone on its own points.
 """
 import os
 import sys
@@ -19,7 +25,7 @@ sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from neuralnetwork import NeuralNetwork  # noqa: E402
 from pinn_native import Ensemble  # noqa: E402
 
-MEMBER_KEYS = ("seed", "init_scale", "tf_lr", "nt_lr", "nt_epochs")
+MEMBER_KEYS = ("seed", "init_scale", "tf_lr", "nt_lr", "nt_epochs", "nu", "resample_seed")
 _LINE = "{tag} = {epoch:6d}  elapsed = {total}  loss min = {lo:.4e}  median = {med:.4e}  max = {hi:.4e}  {custom}"
 
 
@@ -40,17 +46,24 @@ class NeuralNetworkEnsemble(object):
         self.ub = np.asarray(ub, dtype=np.float64)
         self.lb = np.asarray(lb, dtype=np.float64)
         self.logger = logger
+        self.members = [dict(m) for m in members]
         self.member_hp = [dict(hp, **m) for m in members]
         self.n_members = len(members)
         self.tf_epochs = int(hp["tf_epochs"])
         self.tf_b1, self.tf_eps = hp["tf_b1"], 1e-7 if hp["tf_eps"] is None else hp["tf_eps"]   # (Keras default)
         self.nt_ncorr = hp["nt_ncorr"]
         self.tol_fun = 1.0 * np.finfo(float).eps                       # NeuralNetwork.nt_config.tolFun
+        # device-side redraws of the collocation set (NeuralNetwork.tf_optimization): member k's seeds resample_seed_k + epoch
+        self.resample_every = int(hp.get("resample_every", 0))
+        self.resample_seeds = np.array([int(h.get("resample_seed", 1234)) for h in self.member_hp], dtype=np.int64)
+        self._n_design = 0
         device = hp.get("device", os.environ.get("PINN_DEVICE", 0))
         self._engine = self.engine_class(self.layers, self.lb, self.ub, self.n_members, pde=pde, dtype="f64",
                                          device=int(device))
         self.initial_weights = self._member_weights()
         self._engine.set_weights(self.initial_weights)
+        if any("nu" in m for m in members):      # per-member viscosities (a later set_pde_params keeps them)
+            self.set_pde_params(float(hp.get("nu", 0.0)))
         self.adam_losses = np.zeros((0, self.n_members))
         self.nt_log = [([], []) for _ in range(self.n_members)]       # per member: L-BFGS (iterations, losses)
         self.nt_done = np.zeros(self.n_members, dtype=np.int32)
@@ -78,10 +91,22 @@ class NeuralNetworkEnsemble(object):
 
     # ---- point sets -----------------------------------------------------------------------------------
     def set_collocation(self, X_f):
-        self._engine.set_collocation(np.asarray(X_f, dtype=np.float64).reshape(-1, 2))
+        """X_f [n, 2] for every member, or [K, n, 2]: member k's own set"""
+        X_f = np.asarray(X_f, dtype=np.float64)
+        X_f = X_f if X_f.ndim == 3 else X_f.reshape(-1, 2)
+        self._engine.set_collocation(X_f)
+        self._n_design = X_f.shape[-2]
 
     def set_pde_params(self, nu):
-        self._engine.set_pde_params(nu)
+        """nu for every member (a member's "nu" override wins), or nu [K]"""
+        nu_k = np.broadcast_to(np.asarray(nu, dtype=np.float64), (self.n_members,)).copy()
+        for k, m in enumerate(self.members):
+            if "nu" in m:
+                nu_k[k] = m["nu"]
+        if np.ndim(nu) == 0 and not any("nu" in m for m in self.members):
+            self._engine.set_pde_params(float(nu))
+        else:
+            self._engine.set_pde_params(nu_k)
 
     # ---- training ---------------------------------------------------------------------------------------
     def _line(self, tag, epoch, losses, custom=""):
@@ -95,12 +120,21 @@ class NeuralNetworkEnsemble(object):
     def fit(self, X_u, u):
         eng, K = self._engine, self.n_members
         freq = max(int(self.logger.frequency if self.logger is not None else 10), 1)
-        eng.set_data(np.asarray(X_u, dtype=np.float64).reshape(-1, 2), np.asarray(u, dtype=np.float64).reshape(-1, 1))
-        # Adam (NeuralNetwork.tf_optimization)
+        X_u, u = np.asarray(X_u, dtype=np.float64), np.asarray(u, dtype=np.float64)
+        if X_u.ndim == 3:                                              # one data set per member
+            eng.set_data(X_u, u.reshape(K, X_u.shape[1], 1))
+        else:
+            eng.set_data(X_u.reshape(-1, 2), u.reshape(-1, 1))
+        # Adam (NeuralNetwork.tf_optimization): the same chunks and redraws, all members' redraws in one launch
         eng.adam_init(np.array([h["tf_lr"] for h in self.member_hp], dtype=np.float64), self.tf_b1, 0.999, self.tf_eps)
         chunks, epoch = [], 0
+        every = self.resample_every if self._n_design > 0 else 0
         while epoch < self.tf_epochs:
+            if every and epoch > 0 and epoch % every == 0:
+                eng.lhs_collocation(self._n_design, self.resample_seeds + epoch)
             stop = min(self.tf_epochs, (epoch + freq - 1) // freq * freq + 1)
+            if every:
+                stop = min(stop, (epoch // every + 1) * every)
             losses = eng.adam_run(stop - epoch)
             chunks.append(losses)
             for i, row in enumerate(losses):

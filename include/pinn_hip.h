@@ -81,6 +81,18 @@ int pinn_set_data(pinn_ctx* c, const double* X_u, const double* u, int64_t n, in
  * back, [n][2] float64 (also valid after pinn_set_collocation). */
 int pinn_lhs_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t count, uint64_t seed);
 int pinn_get_collocation(pinn_ctx* c, double* X, int64_t n);
+/* Residual-based adaptive collocation (RAD, Wu et al. 2023: p(x) ~ |f(x)|^k / mean|f|^k + c_add), drawn on the device
+ * (csrc/kernels_rad.h).  The pool is the n_pool-point design pinn_lhs_collocation(n_pool, seed) would draw, its residuals
+ * are what pinn_residual_at returns at the current weights (stream order), and slots [first, first + count) of an
+ * n_design-sample set are drawn from it WITH replacement (a set may hold a pool point more than once).  The weights are
+ * quantised to integers, so every rank of a data-parallel job builds the same CDF and draws its own slice of one set
+ * without communication.  pde 0 and 2, float32 and float64; PINN_EUNSUPPORTED for identification and discrete-time
+ * models, PINN_EINVAL for bad geometry, n_pool outside 1..2^24, k outside 1..4 or c_add outside [0, 64] -- both before
+ * any device work, the set unchanged.  With the set assembled and count unchanged the call only enqueues work.  The mean()
+ * denominator becomes n_design; the points survive pinn_set_data / pinn_set_boundary and are replaced by
+ * pinn_set_collocation, pinn_lhs_collocation or the next adaptive draw.  (Additive: the ABI version stays 6.) */
+int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t count, int64_t n_pool, uint64_t seed,
+                         int k, double c_add);
 int pinn_set_boundary(pinn_ctx* c, const double* X_lb, const double* X_ub, int64_t n,
                       int64_t n_total);
 /* Discrete-time models (pde_kind 3, 4; layers[0] == 1, lb/ub hold one value each).  A stage set contributes

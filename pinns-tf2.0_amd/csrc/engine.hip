@@ -26,6 +26,7 @@
 #include "kernels_optim.h"
 #include "kernels_disc.h"
 #include "kernels_sampling.h"
+#include "kernels_rad.h"
 #include "kernels_tile16.h"
 #include "kernels_tile16f.h"
 #include "kernels_xgmi.h"
@@ -205,6 +206,20 @@ struct pinn_ctx {
 
   // collocation set generated on the device (pinn_lhs_collocation) instead of handed over
   struct { bool on = false; int64_t n_design = 0, first = 0, count = 0; uint64_t seed = 0; } lhs;
+  // collocation set drawn by residual-based adaptive sampling (pinn_rad_collocation, kernels_rad.h): the drawn points as a
+  // float64 device copy (cx, ct: ensure_sets re-places them after a re-assembly) and the call's own buffers -- pool points,
+  // their Taylor outputs and residuals, integer weights, block sums, totals -- so that no evaluation cache is disturbed
+  struct {
+    bool on = false, filled = false;
+    int64_t n_design = 0, first = 0, count = 0;
+    double *cx = nullptr, *ct = nullptr;
+    size_t cap = 0;
+    void *px = nullptr, *pt = nullptr, *O = nullptr;
+    double* f = nullptr;
+    unsigned long long *w = nullptr, *bsum = nullptr;
+    RadTotals* tot = nullptr;
+    size_t cap_pool = 0;
+  } rad;
 
   // discrete-time models (pde 3, 4): stage sets as handed over, device copies, scratch
   struct DiscSet { std::vector<double> x, t, M; int q = 0; bool has_M = false; };
@@ -364,7 +379,7 @@ static int lhs_fill(pinn_ctx* c) {
 static int ensure_sets(pinn_ctx* c) {
   if (!c->sets_dirty) return 0;
   const int n_b = (int)(c->Xlo.size() / 2), n_u = (int)(c->Xu.size() / 2),
-            n_f = c->lhs.on ? (int)c->lhs.count : (int)(c->Xf.size() / 2);
+            n_f = c->lhs.on ? (int)c->lhs.count : c->rad.on ? (int)c->rad.count : (int)(c->Xf.size() / 2);
   const int NO = c->nd.n_out;
   if (c->pde == PINN_PDE_BURGERS_IDE)
     REQUIRE(n_f == 0, "identification evaluates the residual at the data points; no collocation set");
@@ -388,9 +403,15 @@ static int ensure_sets(pinn_ctx* c) {
     hx[g] = c->Xu[2 * i]; ht[g] = c->Xu[2 * i + 1];
     for (int o = 0; o < NO; ++o) htg[(size_t)o * n_pad + g] = c->U[(size_t)i * NO + o];
   }
-  if (!c->lhs.on)
+  if (!c->lhs.on && !c->rad.on)
     for (int i = 0; i < n_f; ++i, ++g) { hx[g] = c->Xf[2 * i]; ht[g] = c->Xf[2 * i + 1]; }
   for (; g < n_pad; ++g) { hx[g] = c->lb[0]; ht[g] = c->lb[1]; }   // inert padding (zero seeds); LHS slots filled below
+  if (c->rad.on && c->rad.filled && n_f > 0) {                     // the last adaptive draw, kept through re-assemblies
+    const size_t off = (size_t)(2 * n_b + n_u);
+    HIPCHK(hipMemcpyAsync(hx.data() + off, c->rad.cx, (size_t)n_f * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ht.data() + off, c->rad.ct, (size_t)n_f * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
 
   const size_t rs = real_size(c);
   if ((size_t)n_pad > c->cap_pts) {
@@ -1111,6 +1132,81 @@ static int predict_values(pinn_ctx* c, int64_t n, int n_pad) {
 }
 
 // ------------------------------------------------------------------------------------------
+// residual-based adaptive collocation (kernels_rad.h)
+// ------------------------------------------------------------------------------------------
+// the buffers of pinn_rad_collocation: grown only (a grow synchronises; a repeat at the same sizes only enqueues)
+static int rad_alloc(pinn_ctx* c, int64_t count, int64_t M) {
+  if ((size_t)count > c->rad.cap) {
+    if (dev_alloc(&c->rad.cx, (size_t)count * 8) || dev_alloc(&c->rad.ct, (size_t)count * 8)) return PINN_EHIP;
+    c->rad.cap = (size_t)count;
+  }
+  if (!c->rad.tot && dev_alloc(&c->rad.tot, sizeof(RadTotals))) return PINN_EHIP;
+  const size_t n_pad = (size_t)((M + 63) / 64 * 64), rs = real_size(c), NO = (size_t)c->nd.n_out;
+  if (n_pad > c->rad.cap_pool) {
+    const size_t nb = (n_pad + RAD_BLOCK - 1) / RAD_BLOCK;
+    if (dev_alloc(&c->rad.px, n_pad * rs) || dev_alloc(&c->rad.pt, n_pad * rs) ||
+        dev_alloc(&c->rad.O, NO * n_pad * 4 * rs) || dev_alloc(&c->rad.f, NO * n_pad * 8) ||
+        dev_alloc(&c->rad.w, n_pad * 8) || dev_alloc(&c->rad.bsum, nb * 8)) return PINN_EHIP;
+    // pad points of the pool: finite, inert, never drawn
+    HIPCHK(hipMemsetAsync(c->rad.px, 0, n_pad * rs, c->stream));
+    HIPCHK(hipMemsetAsync(c->rad.pt, 0, n_pad * rs, c->stream));
+    c->rad.cap_pool = n_pad;
+  }
+  return 0;
+}
+
+// pool -> residuals -> integer weights -> CDF -> the rad.count samples from rad.first, into the collocation slots and the
+// float64 copy.  Enqueues only.
+static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) {
+  const int64_t cnt = c->rad.count;
+  if (cnt <= 0) return 0;
+  const int NO = c->nd.n_out;
+  const int n_pad = (int)((M + 63) / 64 * 64);
+  const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+  const uint64_t n = (uint64_t)M;
+  const dim3 grid_m((unsigned)((M + RAD_BLOCK - 1) / RAD_BLOCK)), block(RAD_BLOCK);
+  const bool f64 = c->dtype == PINN_F64;
+  // 1. the pool: points [0, M) of the M-point design, in the compute dtype (k_lhs_fill, as pinn_lhs_collocation draws it)
+  if (f64)
+    hipLaunchKernelGGL((k_lhs_fill<double>), grid_m, block, 0, c->stream, (double*)c->rad.px, (double*)c->rad.pt, M,
+                       (uint64_t)0, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
+                       c->ub[1] - c->lb[1]);
+  else
+    hipLaunchKernelGGL((k_lhs_fill<float>), grid_m, block, 0, c->stream, (float*)c->rad.px, (float*)c->rad.pt, M,
+                       (uint64_t)0, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
+                       c->ub[1] - c->lb[1]);
+  HIPCHK(hipGetLastError());
+  // 2. residuals at the current weights: pinn_residual_at's forward sweep and k_residual
+  if (int rc = forward_taylor(c, c->rad.px, c->rad.pt, n_pad, n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS, c->rad.O)) return rc;
+#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid_m, block, 0, c->stream, 0, (int)M, n_pad, (const vec4<REAL>*)c->rad.O, (const REAL*)c->theta_r, c->nd.n_net, (REAL)c->nu, c->rad.f, NO)
+  if (f64) { if (c->pde == PINN_PDE_SCHRODINGER) RES(double, 2); else RES(double, 0); }
+  else { if (c->pde == PINN_PDE_SCHRODINGER) RES(float, 2); else RES(float, 0); }
+#undef RES
+  HIPCHK(hipGetLastError());
+  // 3.-4. weights and their CDF
+  HIPCHK(hipMemsetAsync(c->rad.tot, 0, sizeof(RadTotals), c->stream));
+  hipLaunchKernelGGL(k_rad_mag, grid_m, block, 0, c->stream, (const double*)c->rad.f, NO, M, k, c->rad.w, c->rad.tot);
+  hipLaunchKernelGGL(k_rad_q, grid_m, block, 0, c->stream, c->rad.w, M, (const RadTotals*)c->rad.tot, c->rad.bsum);
+  hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(RAD_SCAN), 0, c->stream, c->rad.bsum, (int)grid_m.x, M, c_add, c->rad.tot);
+  HIPCHK(hipGetLastError());
+  // 5. the draw
+  const size_t off = (size_t)(2 * c->sd.n_b + c->sd.n_u);
+  const dim3 grid_s((unsigned)((cnt + 255) / 256)), block_s(256);
+  if (f64)
+    hipLaunchKernelGGL((k_rad_select<double>), grid_s, block_s, 0, c->stream, (const double*)c->rad.px,
+                       (const double*)c->rad.pt, (const unsigned long long*)c->rad.w,
+                       (const unsigned long long*)c->rad.bsum, (const RadTotals*)c->rad.tot, M, (uint64_t)c->rad.first,
+                       cnt, lo, hi, (double*)c->xs + off, (double*)c->ts + off, c->rad.cx, c->rad.ct);
+  else
+    hipLaunchKernelGGL((k_rad_select<float>), grid_s, block_s, 0, c->stream, (const float*)c->rad.px,
+                       (const float*)c->rad.pt, (const unsigned long long*)c->rad.w,
+                       (const unsigned long long*)c->rad.bsum, (const RadTotals*)c->rad.tot, M, (uint64_t)c->rad.first,
+                       cnt, lo, hi, (float*)c->xs + off, (float*)c->ts + off, c->rad.cx, c->rad.ct);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
 extern "C" {
@@ -1262,7 +1358,8 @@ int pinn_destroy(pinn_ctx* c) {
                   c->lb_q, c->lb_log_loss, c->lb_log_iter, c->lb_SY, c->lb_YY, c->lb_dots, c->lb_cs,
                   c->lb_cy, c->lb_ex, c->img, c->row_index, c->d_ginfo, c->d_M[0], c->d_M[1], c->d_MT[0], c->d_MT[1],
                   c->d_Ast, c->d_A3, c->d_U3, c->d_Nn, c->d_R, c->d_dAp, c->d_lossp, c->d_lamp,
-                  c->pred, c->d_ref, c->err_partial, c->err_res, c->d_nonfinite, c->t16_bsync, c->t16_gscr};
+                  c->pred, c->d_ref, c->err_partial, c->err_res, c->d_nonfinite, c->t16_bsync, c->t16_gscr,
+                  c->rad.cx, c->rad.ct, c->rad.px, c->rad.pt, c->rad.O, c->rad.f, c->rad.w, c->rad.bsum, c->rad.tot};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& p : c->pend) {
     if (p.h_state) (void)hipHostFree(p.h_state);
@@ -1289,6 +1386,7 @@ int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_to
   c->Xf.assign(X_f, X_f + 2 * n);
   c->nf_total = n_total;
   c->lhs.on = false;
+  c->rad.on = false;
   c->sets_dirty = true;
   return 0;
 }
@@ -1302,11 +1400,42 @@ int pinn_lhs_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   HIPCHK(hipSetDevice(c->device));
   const bool same_shape = c->lhs.on && !c->sets_dirty && c->lhs.count == count;
   c->lhs.on = true; c->lhs.n_design = n_design; c->lhs.first = first; c->lhs.count = count; c->lhs.seed = seed;
+  c->rad.on = false;
   c->Xf.clear();
   c->nf_total = n_design;
   c->sd.inv_nf = 1.0 / (double)n_design;
   if (same_shape) return lhs_fill(c);            // re-draw in place: one launch, nothing reallocated
   c->sets_dirty = true;
+  return 0;
+}
+
+int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t count, int64_t n_pool, uint64_t seed,
+                         int k, double c_add) {
+  REQUIRE(c, "null");
+  if (is_disc(c) || c->pde == PINN_PDE_BURGERS_IDE)
+    return fail(PINN_EUNSUPPORTED, "pinn_rad_collocation: this model has no collocation set");
+  REQUIRE(n_design >= 1 && first >= 0 && count >= 0 && first + count <= n_design && count <= (1 << 30),
+          "bad design geometry (n_design %lld, first %lld, count %lld)", (long long)n_design, (long long)first,
+          (long long)count);
+  REQUIRE(n_pool >= 1 && n_pool <= RAD_POOL_MAX, "pinn_rad_collocation: n_pool %lld is outside 1..2^24", (long long)n_pool);
+  REQUIRE(k >= 1 && k <= 4, "pinn_rad_collocation: k %d is outside 1..4", k);
+  REQUIRE(std::isfinite(c_add) && c_add >= 0.0 && c_add <= 64.0, "pinn_rad_collocation: c %g is outside [0, 64]", c_add);
+  HIPCHK(hipSetDevice(c->device));
+  // the slots stay where they are (same count, set assembled): the draw only enqueues, as an in-place LHS redraw does
+  const bool in_place = !c->sets_dirty && c->sd.n_f == count;
+  if (int rc = rad_alloc(c, count, n_pool)) return rc;
+  c->lhs.on = false;
+  c->rad.on = true; c->rad.n_design = n_design; c->rad.first = first; c->rad.count = count;
+  c->Xf.clear();
+  c->nf_total = n_design;
+  c->sd.inv_nf = 1.0 / (double)n_design;
+  if (!in_place) {
+    c->rad.filled = false;
+    c->sets_dirty = true;
+    if (int rc = ensure_sets(c)) return rc;
+  }
+  if (int rc = rad_draw(c, n_pool, seed, k, c_add)) return rc;
+  c->rad.filled = true;
   return 0;
 }
 

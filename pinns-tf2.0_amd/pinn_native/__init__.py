@@ -17,7 +17,7 @@ _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _REPO = os.path.dirname(os.path.dirname(_HERE))
 LIB_PATH = os.environ.get("PINN_HIP_LIB") or os.path.join(_HERE, "libpinn_hip.so")
 SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_wide.h", "kernels_predict20.h",
-           "kernels_disc.h", "kernels_sampling.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h"]
+           "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h"]
 HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
 PDE_KINDS = {"burgers": 0, "burgers_ide": 1, "schrodinger": 2, "burgers_disc": 3, "burgers_disc_ide": 4}
@@ -202,6 +202,8 @@ _SIGNATURES = {
     "pinn_lhs_collocation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_uint64]),
     "pinn_get_collocation": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
+    "pinn_rad_collocation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_uint64, ctypes.c_int, ctypes.c_double]),
     "pinn_disc_set_stage": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_double_p, _c_double_p,
                                            ctypes.c_int64, _c_double_p, ctypes.c_int]),
     "pinn_disc_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_double_p, ctypes.c_int64,
@@ -439,6 +441,15 @@ class Engine(object):
         """Draw collocation points [first, first+count) of an n_design-point Latin hypercube on the device."""
         count = int(n_design) - int(first) if count is None else int(count)
         self._check(self._lib.pinn_lhs_collocation(self._h, int(n_design), int(first), count, int(seed)))
+        self.n_f = count
+
+    def rad_collocation(self, n_design, seed, n_pool, k=1, c=1.0, first=0, count=None):
+        """Draw collocation points [first, first+count) of an n_design-sample set by residual-based adaptive sampling
+        (include/pinn_hip.h pinn_rad_collocation): from the n_pool-point LHS design with this seed, with probability
+        ~ |f|^k / mean|f|^k + c at the current weights, with replacement."""
+        count = int(n_design) - int(first) if count is None else int(count)
+        self._check(self._lib.pinn_rad_collocation(self._h, int(n_design), int(first), count, int(n_pool), int(seed),
+                                                   int(k), float(c)))
         self.n_f = count
 
     def get_collocation(self):

@@ -41,6 +41,9 @@ class NeuralNetworkEnsemble(object):
                 raise ValueError("per-member overrides are %s; got %s" % (", ".join(MEMBER_KEYS), sorted(bad)))
         if hp.get("dtype", "f64") not in ("f64", "float64"):
             raise ValueError("ensembles are float64 only")
+        if hp.get("resample", "lhs") != "lhs":
+            raise ValueError('hp["resample"]: ensembles redraw uniform Latin hypercubes only ("lhs"); per-member adaptive '
+                             'sampling ("rad") is not supported')
         self.pde = pde
         self.layers = [int(v) for v in hp["layers"]]
         self.ub = np.asarray(ub, dtype=np.float64)

@@ -13,7 +13,8 @@ It names one of the engine's residual kinds instead (`pde="burgers" | "burgers_i
 "schrodinger" | "burgers_disc" | "burgers_disc_ide"`) and the engine evaluates forward, u_t/u_x/u_xx, residual, loss and the flat
 gradient on the GPU (csrc/).  Extra, optional hp keys: "dtype" ("f64" default = the reference's
 arithmetic, neuralnetwork.py:24-26 | "f32" = the throughput mode north_star sanctions) for the
-kernel arithmetic, "device" (HIP ordinal), "nt_guard" (see nt_optimization).  Host interchange stays float64.
+kernel arithmetic, "device" (HIP ordinal), "nt_guard" (see nt_optimization), "resample_every" / "resample" / "rad_*"
+(device-side redraws of the collocation set, see _resample_options).  Host interchange stays float64.
 
 Data parallel (north_star; the reference has no distributed code): launched as
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 1d-burgers/inf_cont_burgers.py [hp.json]
@@ -54,6 +55,32 @@ def _init_stream():
     if _INIT_STREAM["rs"] is None:
         set_seed(_INIT_STREAM["seed"])
     return _INIT_STREAM["rs"]
+
+
+RAD_POOL_MAX = 1 << 24
+
+
+def _resample_options(hp, pde):
+    """hp["resample"] = "lhs" (default: every hp["resample_every"] Adam epochs a new Latin hypercube) | "rad" (residual-based
+    adaptive sampling, Engine.rad_collocation: the new set is drawn from a pool of hp["rad_pool"] LHS points, default
+    10 N_f, with density ~ |f|^rad_k / mean|f|^rad_k + rad_c at the current weights; rad_k in 1..4, default 1; rad_c in
+    [0, 64], default 1.0).  Refused here, before any device work, with the offending key named."""
+    mode = hp.get("resample", "lhs")
+    if mode not in ("lhs", "rad"):
+        raise ValueError('hp["resample"] must be "lhs" or "rad" (got %r)' % (mode,))
+    k, c, pool = hp.get("rad_k", 1), hp.get("rad_c", 1.0), hp.get("rad_pool")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 4:
+        raise ValueError('hp["rad_k"] must be an integer in 1..4 (got %r)' % (k,))
+    if isinstance(c, bool) or not isinstance(c, (int, float, np.integer, np.floating)) or not (np.isfinite(c) and 0.0 <= c <= 64.0):
+        raise ValueError('hp["rad_c"] must be a finite number in [0, 64] (got %r)' % (c,))
+    if pool is not None and (isinstance(pool, bool) or not isinstance(pool, (int, np.integer)) or not 1 <= pool <= RAD_POOL_MAX):
+        raise ValueError('hp["rad_pool"] must be an integer in 1..2^24 (got %r)' % (pool,))
+    if mode == "rad":
+        if int(hp.get("resample_every", 0)) <= 0:
+            raise ValueError('hp["resample"] = "rad" redraws every hp["resample_every"] epochs; resample_every must be > 0')
+        if pde not in ("burgers", "schrodinger"):
+            raise ValueError('hp["resample"] = "rad" needs a collocation set; the %s model has none' % pde)
+    return mode, int(k), float(c), None if pool is None else int(pool)
 
 
 class _AdamConfig(object):
@@ -114,6 +141,7 @@ class NeuralNetwork(object):
         layers = hp["layers"]
         if pde is not None:
             self.pde = pde
+        self._resample, self._rad_k, self._rad_c, self._rad_pool = _resample_options(hp, self.pde)
 
         # L-BFGS configuration, same fields as the reference (neuralnetwork.py:13-17)
         self.nt_config = Struct()
@@ -331,7 +359,13 @@ class NeuralNetwork(object):
             if every and epoch > 0 and epoch % every == 0:
                 # one design for the whole job; a rank draws its own block of it (counter-based: no communication)
                 lo, hi = self._dp.shard(n_design) if self._dp else (0, n_design)
-                self._engine.lhs_collocation(n_design, self._resample_seed + epoch, first=lo, count=hi - lo)
+                if getattr(self, "_resample", "lhs") == "rad":
+                    # the pool, its residuals and the CDF are the same on every rank (replicated weights)
+                    pool = self._rad_pool or min(10 * n_design, RAD_POOL_MAX)
+                    self._engine.rad_collocation(n_design, self._resample_seed + epoch, pool, k=self._rad_k,
+                                                 c=self._rad_c, first=lo, count=hi - lo)
+                else:
+                    self._engine.lhs_collocation(n_design, self._resample_seed + epoch, first=lo, count=hi - lo)
                 self._X_f = None
             # run up to and including the next epoch that is logged, then sync once
             stop = min(self.tf_epochs, (epoch + freq - 1) // freq * freq + 1)

@@ -311,6 +311,31 @@ int pinn_ensk_set_pde_params(pinn_ens* e, const double* nu, int n_members);
  * seed seeds[k] become member k's collocation set */
 int pinn_ensk_lhs_collocation(pinn_ens* e, int64_t n_design, int64_t first, int64_t count, const uint64_t* seeds);
 
+/* Self-adaptive point weights (SA-PINN, McClenny & Braga-Neto, arXiv:2009.04544) for Burgers inference (pde 0) in float64 on
+ * kernel path 7.  Every data point j and collocation point i gets a trainable weight, and the loss becomes
+ *     L = (1/N_f) sum_i lam_f,i^2 f_i^2 + (1/N_u) sum_j lam_u,j^2 (u_j - u*_j)^2
+ * with the same global denominators as before.  Each Adam step (pinn_adam_run and its enqueue forms) descends in the network
+ * weights and ASCENDS in the lam, both from one evaluation at (theta_t, lam_t): lam += alpha_t m^ / (sqrt(v^) + eps) with
+ * dL/dlam = 2 lam r^2 / N, alpha_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), and the step counter, beta1, beta2 and eps of
+ * pinn_adam_init; every lam has its own moments.  The ascent runs inside the loss+gradient kernel (no extra launch).
+ * pinn_loss_grad, the L-BFGS evaluations, pinn_residual*, pinn_predict and pinn_error_l2 read the weights and never move
+ * them: L-BFGS minimises the weighted loss with lam frozen at their values after Adam, the paper's Adam -> L-BFGS schedule.
+ *   pinn_sa_set_weights  enables the weighted loss; lam_u [n_u] in the order of pinn_set_data's rows, lam_f [n_f] in the
+ *                        order of the collocation set (for a device-drawn set: what pinn_get_collocation returns); the counts
+ *                        must equal the current local set sizes.  Zeroes the moments.
+ *   pinn_sa_get_weights  reads them back (same shapes); PINN_EINVAL while the weights are off
+ *   pinn_sa_adam_init    the ascent's rate lr (default 0: the weights are held fixed, their moments do not move)
+ *   pinn_sa_disable      back to the plain kernel: results bit-identical to a context that never enabled the weights
+ * pinn_set_collocation, pinn_lhs_collocation and pinn_rad_collocation reset the collocation weights to 1 and their moments to
+ * 0, pinn_set_data the data weights.  Refusals, before any device work, the context unchanged: PINN_EUNSUPPORTED for pde != 0,
+ * float32, a kernel path other than 7 or a communicator (pinn_comm_init, pinn_comm_xgmi_export and pinn_set_kernel_path to
+ * another path are refused the same way while the weights are on); PINN_EINVAL for null arrays, counts that differ from the
+ * set sizes, non-finite weights, a negative or non-finite lr.  (Additive: the ABI version stays 6.) */
+int pinn_sa_set_weights(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam_f, int64_t n_f);
+int pinn_sa_get_weights(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, int64_t n_f);
+int pinn_sa_adam_init(pinn_ctx* c, double lr);
+int pinn_sa_disable(pinn_ctx* c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,10 @@ def run(hp):
     pinn = BurgersInformedNN(hp, logger, X_f, ub, lb, nu=0.01 / np.pi)
     logger.set_error_fn(lambda: pinn.error_l2(X_star, u_star))     # = relative_l2(u_star, model(X_star)), on the device
     pinn.fit(X_u_train, u_train)
+    if hp.get("sa_weights") and pinn.is_root:      # self-adaptive point weights (hp["sa_weights"]): where they ended
+        lam_u, lam_f = pinn.get_sa_weights()
+        print("SA weights: data min %.4e median %.4e max %.4e | collocation min %.4e median %.4e max %.4e" % (
+            lam_u.min(), np.median(lam_u), lam_u.max(), lam_f.min(), np.median(lam_f), lam_f.max()))
 
     u_pred = pinn.predict(X_star)[0]
     if not os.environ.get("PINN_NO_PLOT") and pinn.is_root:

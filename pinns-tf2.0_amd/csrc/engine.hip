@@ -221,6 +221,18 @@ struct pinn_ctx {
     size_t cap_pool = 0;
   } rad;
 
+  // self-adaptive point weights (pinn_sa_*, k_fused20d's SAW variants): the device array of fused20d_api.h (SA_CONST
+  // constants, then (lambda, m, v) per point of the assembled set), laid out for n_u data and n_f collocation points with the
+  // ascent constants k; reset_u / reset_f: that class's set was replaced since (sa_prepare puts its weights back to 1)
+  struct {
+    bool on = false, reset_u = false, reset_f = false;
+    double lr = 0.0;
+    double* buf = nullptr;
+    size_t cap = 0;
+    int n_u = 0, n_f = 0;
+    double k[3] = {0.0, 0.0, 0.0};
+  } sa;
+
   // discrete-time models (pde 3, 4): stage sets as handed over, device copies, scratch
   struct DiscSet { std::vector<double> x, t, M; int q = 0; bool has_M = false; };
   DiscSet dset[2];
@@ -455,7 +467,41 @@ static int ensure_sets(pinn_ctx* c) {
 struct AdamFuse {          // single-GPU Adam step applied by the reduction kernel itself
   double alpha;
   double* loss3;
+  double alpha_sa = 0.0;   // self-adaptive weights: the ascent's step size, applied by the evaluation kernel (0: none)
 };
+
+// self-adaptive weights: (re)build the device array for the assembled set when a class's set was replaced (its weights
+// back to 1, its moments to 0; the other class keeps its values) or the ascent constants changed.  Synchronous, and only
+// then: the common case returns at once.
+static int sa_prepare(pinn_ctx* c) {
+  const SetDesc& sd = c->sd;
+  const bool keep_u = c->sa.buf && !c->sa.reset_u && c->sa.n_u == sd.n_u;
+  const bool keep_f = c->sa.buf && !c->sa.reset_f && c->sa.n_f == sd.n_f;
+  const bool k_same = c->sa.k[0] == c->b1 && c->sa.k[1] == c->b2 && c->sa.k[2] == c->eps;
+  if (keep_u && keep_f && k_same) return 0;
+  std::vector<double> old;
+  if (keep_u || keep_f) {
+    old.resize(sa_doubles(c->sa.n_u + c->sa.n_f));
+    HIPCHK(hipMemcpyAsync(old.data(), c->sa.buf, old.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  std::vector<double> h(sa_doubles(sd.n_u + sd.n_f), 0.0);
+  h[0] = c->b1; h[1] = c->b2; h[2] = c->eps;
+  for (int j = 0; j < sd.n_u; ++j)
+    for (int e = 0; e < 3; ++e) h[SA_CONST + 3 * j + e] = keep_u ? old[SA_CONST + 3 * j + e] : (e == 0 ? 1.0 : 0.0);
+  for (int i = 0; i < sd.n_f; ++i)
+    for (int e = 0; e < 3; ++e)
+      h[SA_CONST + 3 * (sd.n_u + i) + e] = keep_f ? old[SA_CONST + 3 * (c->sa.n_u + i) + e] : (e == 0 ? 1.0 : 0.0);
+  if (h.size() * 8 > c->sa.cap) {
+    if (dev_alloc(&c->sa.buf, h.size() * 8)) return PINN_EHIP;
+    c->sa.cap = h.size() * 8;
+  }
+  HIPCHK(hipMemcpyAsync(c->sa.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->sa.n_u = sd.n_u; c->sa.n_f = sd.n_f; c->sa.reset_u = c->sa.reset_f = false;
+  c->sa.k[0] = c->b1; c->sa.k[1] = c->b2; c->sa.k[2] = c->eps;
+  return 0;
+}
 
 // k_t16_fused (path 8) leaves the hidden-layer weight gradients in its tile-major scratch: the reductions read them there
 static TileScratch tile_scratch(const pinn_ctx* c) {
@@ -605,8 +651,21 @@ static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   if (ev4 && c->path != 2 && c->path != 1 && c->path != 7) HIPCHK(hipEventRecord(ev4[0], c->stream));
   if (c->path == 7) {
     int rc = hipErrorInvalidValue;
+    bool weighted = false;
+    if constexpr (sizeof(real) == 8 && PDE == 0) {
+      if (c->sa.on) {                               // the weighted variant; an Adam step moves the weights too
+        if (int e = sa_prepare(c)) return e;
+        const SaArgs sa{(double)c->nu, c->sa.buf, af ? af->alpha_sa : 0.0};
+        rc = fused20d_sa_launch_any(c->nd, sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
+                                    (const double*)c->tgt, (double)lbx, (double)lbt, (double)sx, (double)st, sa,
+                                    (double*)c->part, c->R, c->n_wg, c->row_index, c->stream, ev4 ? ev4[0] : nullptr,
+                                    ev4 ? ev4[1] : nullptr);
+        weighted = true;
+      }
+    }
+    (void)weighted;
     if constexpr (sizeof(real) == 8 && PDE != 2)
-      rc = fused20d_launch_any(PDE, c->nd, sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
+      if (!weighted) rc = fused20d_launch_any(PDE, c->nd, sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
                                (const double*)c->tgt, (double)lbx, (double)lbt, (double)sx, (double)st,
                                (double)c->nu, (double*)c->part, c->R, c->n_wg, c->row_index,
                                c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr);
@@ -1356,7 +1415,7 @@ int pinn_destroy(pinn_ctx* c) {
                   c->O, c->ZA, c->ZB, c->part, c->xe, c->te, c->Oe, c->f_out, c->loss_hist, c->snap,
                   c->lb_state, c->lb_x, c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al,
                   c->lb_q, c->lb_log_loss, c->lb_log_iter, c->lb_SY, c->lb_YY, c->lb_dots, c->lb_cs,
-                  c->lb_cy, c->lb_ex, c->img, c->row_index, c->d_ginfo, c->d_M[0], c->d_M[1], c->d_MT[0], c->d_MT[1],
+                  c->lb_cy, c->lb_ex, c->img, c->row_index, c->sa.buf, c->d_ginfo, c->d_M[0], c->d_M[1], c->d_MT[0], c->d_MT[1],
                   c->d_Ast, c->d_A3, c->d_U3, c->d_Nn, c->d_R, c->d_dAp, c->d_lossp, c->d_lamp,
                   c->pred, c->d_ref, c->err_partial, c->err_res, c->d_nonfinite, c->t16_bsync, c->t16_gscr,
                   c->rad.cx, c->rad.ct, c->rad.px, c->rad.pt, c->rad.O, c->rad.f, c->rad.w, c->rad.bsum, c->rad.tot};
@@ -1387,6 +1446,7 @@ int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_to
   c->nf_total = n_total;
   c->lhs.on = false;
   c->rad.on = false;
+  c->sa.reset_f = true;
   c->sets_dirty = true;
   return 0;
 }
@@ -1401,6 +1461,7 @@ int pinn_lhs_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   const bool same_shape = c->lhs.on && !c->sets_dirty && c->lhs.count == count;
   c->lhs.on = true; c->lhs.n_design = n_design; c->lhs.first = first; c->lhs.count = count; c->lhs.seed = seed;
   c->rad.on = false;
+  c->sa.reset_f = true;
   c->Xf.clear();
   c->nf_total = n_design;
   c->sd.inv_nf = 1.0 / (double)n_design;
@@ -1426,6 +1487,7 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   if (int rc = rad_alloc(c, count, n_pool)) return rc;
   c->lhs.on = false;
   c->rad.on = true; c->rad.n_design = n_design; c->rad.first = first; c->rad.count = count;
+  c->sa.reset_f = true;
   c->Xf.clear();
   c->nf_total = n_design;
   c->sd.inv_nf = 1.0 / (double)n_design;
@@ -1465,6 +1527,7 @@ int pinn_set_data(pinn_ctx* c, const double* X_u, const double* u, int64_t n, in
   c->Xu.assign(X_u, X_u + 2 * n);
   c->U.assign(u, u + (size_t)c->nd.n_out * n);
   c->nu_total = n_total;
+  c->sa.reset_u = true;
   c->sets_dirty = true;
   return 0;
 }
@@ -1627,7 +1690,9 @@ static int adam_issue(pinn_ctx* c, int n_steps, bool record, int* ticket) {
     const double alpha = c->lr * std::sqrt(1.0 - std::pow(c->b2, t)) / (1.0 - std::pow(c->b1, t));
     double* slot = region ? region + (size_t)3 * s : nullptr;
     if (!c->comm || c->xg.on) {                   // reduction (+ mailbox all-reduce) + update in one kernel
-      const AdamFuse af{alpha, slot};
+      AdamFuse af{alpha, slot};
+      if (c->sa.on && c->sa.lr > 0.0)             // self-adaptive weights: the ascent, same counter, same form
+        af.alpha_sa = c->sa.lr * std::sqrt(1.0 - std::pow(c->b2, t)) / (1.0 - std::pow(c->b1, t));
       int rc = eval_loss_grad(c, &af);
       if (rc) return rc;
       continue;
@@ -2121,6 +2186,7 @@ int pinn_comm_unique_id(char* id128) {
 
 int pinn_comm_init(pinn_ctx* c, const char* id128, int n_ranks, int rank) {
   REQUIRE(c && id128 && n_ranks >= 1 && rank >= 0 && rank < n_ranks, "bad communicator arguments");
+  if (c->sa.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: self-adaptive weights are single-device (pinn_sa_disable first)");
   HIPCHK(hipSetDevice(c->device));
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
   xg_release(c);
@@ -2135,6 +2201,8 @@ int pinn_comm_init(pinn_ctx* c, const char* id128, int n_ranks, int rank) {
 int pinn_comm_xgmi_export(pinn_ctx* c, int n_ranks, int rank, char* handle64) {
   REQUIRE(c && handle64 && n_ranks >= 1 && n_ranks <= XG_MAX_RANKS && rank >= 0 && rank < n_ranks,
           "bad arguments (at most %d ranks)", XG_MAX_RANKS);
+  if (c->sa.on)
+    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: self-adaptive weights are single-device (pinn_sa_disable first)");
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is expected to be 64 bytes");
   HIPCHK(hipSetDevice(c->device));
   xg_release(c);
@@ -2307,6 +2375,8 @@ int pinn_set_kernel_path(pinn_ctx* c, int path) {
   REQUIRE(c && path >= 0 && path <= 8, "path must be 0 (generic), 1 (fused width-20), 2 (fused width-20, register stash), "
           "3 (wide MFMA sweeps), 4 (shape-generic MFMA sweeps), 5 / 6 (4's forward / reverse half with the generic other half), "
           "7 (fused width-20 float64, register stash), 8 (fused float64 MFMA sweep, widths 65..128, 2-4 hidden layers)");
+  if (c->sa.on && path != 7)
+    return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: self-adaptive weights run on kernel path 7 only (pinn_sa_disable first)");
   if (path == 8) REQUIRE(t16_fused_ok(c), "the fused float64 sweep needs float64, hidden width 65..128 and 2, 3 or 4 hidden layers");
   if (path >= 4 && path <= 6) REQUIRE(tile16_ok(c), "the shape-generic MFMA sweeps need hidden width <= 128");
   if (path == 7)
@@ -2384,6 +2454,88 @@ int pinn_debug_t16f_stamps(long long* out512) {
 int pinn_get_kernel_path(pinn_ctx* c, int* path) {
   REQUIRE(c && path, "null");
   *path = c->path;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// self-adaptive point weights (include/pinn_hip.h pinn_sa_*; the SAW variants of k_fused20d, fused20d_api.h)
+// ------------------------------------------------------------------------------------------
+// what the weighted kernel serves: Burgers inference in float64 on kernel path 7, one device; checked before any device work
+static int sa_supported(const pinn_ctx* c, const char* who) {
+  if (c->pde != PINN_PDE_BURGERS)
+    return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights are for Burgers inference (pde 0) only", who);
+  if (c->dtype != PINN_F64) return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights need float64", who);
+  if (c->path != 7)
+    return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights need kernel path 7 (this context runs path %d)", who, c->path);
+  if (c->comm || c->xg.box)
+    return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights are single-device; this context has a communicator", who);
+  return 0;
+}
+
+// the local set sizes as ensure_sets will assemble them
+static void sa_counts(const pinn_ctx* c, int64_t* n_u, int64_t* n_f) {
+  *n_u = (int64_t)(c->Xu.size() / 2);
+  *n_f = c->lhs.on ? c->lhs.count : c->rad.on ? c->rad.count : (int64_t)(c->Xf.size() / 2);
+}
+
+int pinn_sa_set_weights(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam_f, int64_t n_f) {
+  REQUIRE(c, "null");
+  if (int rc = sa_supported(c, "pinn_sa_set_weights")) return rc;
+  int64_t cu, cf;
+  sa_counts(c, &cu, &cf);
+  REQUIRE((lam_u || n_u == 0) && (lam_f || n_f == 0), "pinn_sa_set_weights: null weight array");
+  REQUIRE(n_u == cu && n_f == cf, "pinn_sa_set_weights: %lld / %lld weights for %lld data and %lld collocation points",
+          (long long)n_u, (long long)n_f, (long long)cu, (long long)cf);
+  for (int64_t j = 0; j < n_u; ++j) REQUIRE(std::isfinite(lam_u[j]), "pinn_sa_set_weights: lam_u[%lld] is not finite", (long long)j);
+  for (int64_t i = 0; i < n_f; ++i) REQUIRE(std::isfinite(lam_f[i]), "pinn_sa_set_weights: lam_f[%lld] is not finite", (long long)i);
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = ensure_sets(c)) return rc;
+  std::vector<double> h(sa_doubles(c->sd.n_u + c->sd.n_f), 0.0);
+  h[0] = c->b1; h[1] = c->b2; h[2] = c->eps;
+  for (int64_t j = 0; j < n_u; ++j) h[SA_CONST + 3 * j] = lam_u[j];
+  for (int64_t i = 0; i < n_f; ++i) h[SA_CONST + 3 * (n_u + i)] = lam_f[i];
+  if (h.size() * 8 > c->sa.cap) {
+    if (dev_alloc(&c->sa.buf, h.size() * 8)) return PINN_EHIP;
+    c->sa.cap = h.size() * 8;
+  }
+  HIPCHK(hipMemcpyAsync(c->sa.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->sa.n_u = c->sd.n_u; c->sa.n_f = c->sd.n_f; c->sa.reset_u = c->sa.reset_f = false;
+  c->sa.k[0] = c->b1; c->sa.k[1] = c->b2; c->sa.k[2] = c->eps;
+  c->sa.on = true;
+  return 0;
+}
+
+int pinn_sa_get_weights(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, int64_t n_f) {
+  REQUIRE(c, "null");
+  REQUIRE(c->sa.on, "pinn_sa_get_weights: self-adaptive weights are off (pinn_sa_set_weights)");
+  int64_t cu, cf;
+  sa_counts(c, &cu, &cf);
+  REQUIRE((lam_u || n_u == 0) && (lam_f || n_f == 0), "pinn_sa_get_weights: null weight array");
+  REQUIRE(n_u == cu && n_f == cf, "pinn_sa_get_weights: %lld / %lld weights for %lld data and %lld collocation points",
+          (long long)n_u, (long long)n_f, (long long)cu, (long long)cf);
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = ensure_sets(c)) return rc;
+  if (int rc = sa_prepare(c)) return rc;            // a replaced set reads back as ones
+  std::vector<double> h(sa_doubles(c->sd.n_u + c->sd.n_f));
+  HIPCHK(hipMemcpyAsync(h.data(), c->sa.buf, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int64_t j = 0; j < n_u; ++j) lam_u[j] = h[SA_CONST + 3 * j];
+  for (int64_t i = 0; i < n_f; ++i) lam_f[i] = h[SA_CONST + 3 * (n_u + i)];
+  return 0;
+}
+
+int pinn_sa_adam_init(pinn_ctx* c, double lr) {
+  REQUIRE(c, "null");
+  if (int rc = sa_supported(c, "pinn_sa_adam_init")) return rc;
+  REQUIRE(std::isfinite(lr) && lr >= 0.0, "pinn_sa_adam_init: lr %g must be finite and >= 0", lr);
+  c->sa.lr = lr;
+  return 0;
+}
+
+int pinn_sa_disable(pinn_ctx* c) {
+  REQUIRE(c, "null");
+  c->sa.on = false;
   return 0;
 }
 

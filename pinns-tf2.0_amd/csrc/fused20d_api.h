@@ -40,6 +40,26 @@ int fused20d_ens_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const
                             const double* ts, const double* tgt, double lbx, double lbt, double sx, double st, double nu,
                             double* part, int R, int n_wg, int n_members, const int* row_index, hipStream_t stream);
 
+// Self-adaptive point weights (k_fused20d<0, H, ., false, false, true>).  lam holds SA_CONST doubles (beta1, beta2, eps of
+// the ascent), then (lambda, m, v) of every point of the assembled set, [n_all][3]: the data points, then the collocation
+// points, each in the order they were handed over.  alpha = lr_lambda sqrt(1 - b2^t) / (1 - b1^t) as the host forms
+// Adam's step size; 0 = the weights are only read (loss_grad, L-BFGS, lr_lambda = 0), otherwise one ascent step is
+// written back.  (Three values and one interleaved array: with eight arguments, or per-class arrays, the tile-loop
+// variants spilled SGPRs.)
+constexpr int SA_CONST = 4;
+inline size_t sa_doubles(int n_all) { return (size_t)3 * n_all + SA_CONST; }
+struct SaArgs {
+  double nu;
+  double* lam;
+  double alpha;
+};
+
+// one weighted loss+gradient evaluation of pde 0 (4, 6 or 8 hidden layers); returns a hipError_t
+int fused20d_sa_launch_any(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
+                           const double* tgt, double lbx, double lbt, double sx, double st, const SaArgs& sa,
+                           double* part, int R, int n_wg, const int* row_index, hipStream_t stream, hipEvent_t ev_start,
+                           hipEvent_t ev_stop);
+
 // the same with a point set per member -- xs, ts, tgt [n_members][sd.n_pad], all of one SetDesc -- and nu_k [n_members]
 // in device memory: member m's rows bit-identical to a solo launch on member m's set with viscosity nu_k[m]
 int fused20d_ens_sets_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,

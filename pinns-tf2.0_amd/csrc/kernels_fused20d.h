@@ -195,18 +195,26 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
 // SETS (with ENS): every member has its own point set of the common SetDesc -- member m reads xs, ts and tgt at
 // m * sd.n_pad -- and its own viscosity, nu[m] of a device array [members] passed in the slot of the scalar (a pointer
 // has the size and alignment of a double, so the argument layout of every instantiation is the same).
-template <bool SETS> using f20d_nu_t = typename std::conditional<SETS, const double*, double>::type;
+// SAW: self-adaptive point weights (McClenny & Braga-Neto, arXiv:2009.04544), pde 0, solo launch: data point j and collocation
+// point i count with m(lambda) = lambda^2, i.e. inv_nu * lambda_u,j^2 and inv_nf * lambda_f,i^2 stand where inv_nu and inv_nf
+// stand in the plain kernel.  The SaArgs travel in the slot of the scalar nu (as SETS's pointer does), so the argument
+// layout of every other instantiation stays as it was.  With `update` set (an Adam step) the slot-0 lane of a point writes
+// back lambda, m and v after one ascent step on dL/dlambda = 2 lambda r^2 inv_n -- its own residual only, no reduction.
+template <bool SETS, bool SAW = false>
+using f20d_nu_t = typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type;
 __device__ __forceinline__ double f20d_nu(double nu) { return nu; }
 __device__ __forceinline__ double f20d_nu(const double* nu) { return nu[blockIdx.y]; }   // wave-uniform
+__device__ __forceinline__ double f20d_nu(const SaArgs& a) { return a.nu; }
 
-template <int PDE, int H, bool ONE_TILE, bool ENS = false, bool SETS = false>
+template <int PDE, int H, bool ONE_TILE, bool ENS = false, bool SETS = false, bool SAW = false>
 __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th, const double* __restrict__ xs,
                                                   const double* __restrict__ ts, const double* __restrict__ tgt,
                                                   double* __restrict__ part, const int* __restrict__ row_index, int R,
                                                   int n_tiles, double lbx, double lbt, double sx, double st,
-                                                  f20d_nu_t<SETS> nu, SetDesc sd, long long* __restrict__ stamps,
+                                                  f20d_nu_t<SETS, SAW> nu, SetDesc sd, long long* __restrict__ stamps,
                                                   W20Desc nd_arg) {
   static_assert(ENS || !SETS, "per-member point sets are an ensemble launch");
+  static_assert(!SAW || (PDE == 0 && !ENS), "self-adaptive weights: Burgers inference, solo launch");
   // weight offsets: compile-time constants in the one-tile variant (immediate operands; Adam step 41.9 -> 40.8 us with
   // the preloaded pointers); the tile-loop variant keeps them in SGPRs -- with immediates its schedule came out 9 %
   // slower (N_f = 10^6: 2104 vs 1930 us per step, same box)
@@ -281,6 +289,14 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
 
   double c1 = 1.0, c2 = f20d_nu(nu);
   if (PDE == 1) { c1 = wl[nd.n_net]; c2 = exp(wl[nd.n_net + 1]); }
+  // SAW, tile loop: the weight array and the ascent step size are held in vector registers (an opaque move): the tile-loop
+  // variants use 96 of the 106 scalar registers already, and with these four more they spilled 2-4 of them
+  double* sa_lam_p = nullptr;
+  double sa_alpha = 0.0;
+  if constexpr (SAW) {
+    sa_lam_p = nu.lam; sa_alpha = nu.alpha;
+    if constexpr (!ONE_TILE) asm volatile("" : "+v"(sa_lam_p), "+v"(sa_alpha));
+  }
   const double inv_nf = sd.inv_nf, inv_nu = sd.inv_nu;
   // per-lane partial sums of the loss parts and of the two lambda gradients (slot-0 lanes only) live in LDS, four
   // slots per lane behind the gradient accumulators: one read-modify-write per tile instead of eight registers held
@@ -425,6 +441,14 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
       return j != 0 ? -1 : m < 5 ? nd.off_w[H] + 4 * m + i : (i == 0 ? nd.off_b[H] : -1);
     };
     const int pt = tile * 64 + wave * 16 + q;
+    // SAW: this point's weight (and, in an Adam step, its moments), requested here so that the forward sweep hides the
+    // round trip
+    double sa_lam = 1.0, sa_m = 0.0, sa_v = 0.0;
+    double* sa_row = nullptr;
+    if constexpr (SAW) {      // (padding lanes read point 0's entry, unused: no branch, no saved execution mask)
+      sa_row = sa_lam_p + SA_CONST + 3 * (pt < sd.n_all ? pt : 0);
+      sa_lam = sa_row[0]; sa_m = sa_row[1]; sa_v = sa_row[2];
+    }
     const double hx = __builtin_fma(sx, x - lbx, -1.0), ht = __builtin_fma(st, t - lbt, -1.0);
     {
       const int nt = tile + gridDim.x;
@@ -513,10 +537,19 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
     // ------------------------------------------------------------------ seeds + loss parts
     double sb[4] = {0.0, 0.0, 0.0, 0.0};
     {
-      const int cls = point_class(sd, pt);
+      // (SAW: pde 0 has no boundary pairs; classing without n_b saves the tile-loop variants a scalar register)
+      const int cls = SAW ? (pt < sd.n_u ? CLS_DATA : pt < sd.n_all ? CLS_COL : CLS_PAD) : point_class(sd, pt);
       const bool res = (PDE == 0) ? (cls == CLS_COL) : (cls == CLS_DATA);
+      // SAW: inv_n * lambda^2 as a product of its own (never contracted into a neighbour), so lambda = 1 gives inv_n itself
+      // and every bit downstream is the plain kernel's
+      double wf = inv_nf, wu = inv_nu, r2 = 0.0;
+      if constexpr (SAW) {
+#pragma clang fp contract(off)
+        const double l2 = sa_lam * sa_lam;
+        wf = inv_nf * l2; wu = inv_nu * l2;
+      }
       if (res) {
-        const double wgt = (PDE == 0) ? inv_nf : inv_nu;
+        const double wgt = (PDE == 0) ? wf : inv_nu;
         const double f = o[2] + c1 * o[0] * o[1] - c2 * o[3];
         const double fbar = 2.0 * f * wgt;
         if (s == 0) {
@@ -524,11 +557,25 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
           if (PDE == 1) { lacc[128] += fbar * o[0] * o[1]; lacc[192] -= fbar * c2 * o[3]; }
         }
         sb[0] = fbar * c1 * o[1]; sb[1] = fbar * c1 * o[0]; sb[2] = fbar; sb[3] = -c2 * fbar;
+        if constexpr (SAW) r2 = f * f;
       }
       if (cls == CLS_DATA) {
         const double dd = o[0] - tgt[pt];
-        if (s == 0) lacc[64] += dd * dd * inv_nu;
-        sb[0] += 2.0 * dd * inv_nu;
+        if (s == 0) lacc[64] += dd * dd * wu;
+        sb[0] += 2.0 * dd * wu;
+        if constexpr (SAW) r2 = dd * dd;
+      }
+      if constexpr (SAW) {
+        // one Adam ascent step on lambda from this evaluation (TF form, as k_reduce_adam steps theta), slot-0 lane only
+        if (sa_alpha != 0.0 && s == 0 && pt < sd.n_all) {
+          const double* const k = sa_lam_p;                        // beta1, beta2, eps
+          const double g = 2.0 * sa_lam * r2 * (cls == CLS_DATA ? inv_nu : inv_nf);
+          const double mi = sa_m + (1.0 - k[0]) * (g - sa_m);
+          const double vi = sa_v + (1.0 - k[1]) * (g * g - sa_v);
+          sa_row[0] = sa_lam + sa_alpha * mi / (sqrt(vi) + k[2]);
+          sa_row[1] = mi;
+          sa_row[2] = vi;
+        }
       }
     }
 
@@ -813,6 +860,34 @@ inline int fused20d_launch(const NetDesc& nd, const SetDesc& sd, const double* t
   else
     hipLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles, lbx,
                        lbt, sx, st, nu, sd, stamps, w20_desc(H, PDE == 1));
+  return (int)hipGetLastError();
+}
+
+// the weighted evaluation of pde 0 (self-adaptive weights, SaArgs): the solo launch plan; returns a hipError_t
+template <int H>
+inline int fused20d_sa_launch(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
+                              const double* tgt, double lbx, double lbt, double sx, double st, const SaArgs& sa,
+                              double* part, int R, int n_wg, const int* row_index, hipStream_t stream,
+                              hipEvent_t ev_start, hipEvent_t ev_stop) {
+  if (!w20_layout_ok(nd, H, false)) return (int)hipErrorInvalidValue;
+  const size_t lds = fused20d_lds_bytes(H, nd.n_theta);
+  static unsigned long long attr_set = 0;
+  if (first_call_on_device(attr_set)) {
+    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<0, H, false, false, false, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)k_fused20d<0, H, true, false, false, true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  const int n_tiles = sd.n_pad / 64;
+  auto* const kern = n_wg >= n_tiles ? k_fused20d<0, H, true, false, false, true> : k_fused20d<0, H, false, false, false, true>;
+  if (ev_start && ev_stop)
+    hipExtLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, ev_start, ev_stop, 0, th, xs, ts, tgt, part,
+                          row_index, R, n_tiles, lbx, lbt, sx, st, sa, sd, (long long*)nullptr, w20_desc(H, false));
+  else
+    hipLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles, lbx,
+                       lbt, sx, st, sa, sd, (long long*)nullptr, w20_desc(H, false));
   return (int)hipGetLastError();
 }
 

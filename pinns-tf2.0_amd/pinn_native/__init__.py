@@ -248,6 +248,11 @@ _SIGNATURES = {
     "pinn_ensk_set_pde_params": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int]),
     "pinn_ensk_lhs_collocation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                  ctypes.POINTER(ctypes.c_uint64)]),
+    # self-adaptive point weights (include/pinn_hip.h: pinn_sa_*)
+    "pinn_sa_set_weights": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, _c_double_p, ctypes.c_int64]),
+    "pinn_sa_get_weights": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, _c_double_p, ctypes.c_int64]),
+    "pinn_sa_adam_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
+    "pinn_sa_disable": (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 
@@ -451,6 +456,26 @@ class Engine(object):
         self._check(self._lib.pinn_rad_collocation(self._h, int(n_design), int(first), count, int(n_pool), int(seed),
                                                    int(k), float(c)))
         self.n_f = count
+
+    # ---- self-adaptive point weights (include/pinn_hip.h pinn_sa_*) ------------------------------------------------------
+    def sa_set_weights(self, lam_u, lam_f):
+        """Enable the weighted loss with one weight per data point (rows of set_data) and per collocation point (rows of
+        get_collocation); resets the weights' Adam moments."""
+        lam_u, lam_f = _f64(lam_u).ravel(), _f64(lam_f).ravel()
+        self._check(self._lib.pinn_sa_set_weights(self._h, _dp(lam_u), lam_u.size, _dp(lam_f), lam_f.size))
+
+    def sa_get_weights(self):
+        """-> (lam_u [n_u], lam_f [n_f])"""
+        lam_u, lam_f = np.empty(self.n_u, dtype=np.float64), np.empty(self.n_f, dtype=np.float64)
+        self._check(self._lib.pinn_sa_get_weights(self._h, _dp(lam_u), lam_u.size, _dp(lam_f), lam_f.size))
+        return lam_u, lam_f
+
+    def sa_adam_init(self, lr):
+        """ascent rate of the weights in every Adam step (0: held fixed)"""
+        self._check(self._lib.pinn_sa_adam_init(self._h, float(lr)))
+
+    def sa_disable(self):
+        self._check(self._lib.pinn_sa_disable(self._h))
 
     def get_collocation(self):
         X = np.empty((self.n_f, 2), dtype=np.float64)

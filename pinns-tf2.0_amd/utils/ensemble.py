@@ -44,6 +44,9 @@ class NeuralNetworkEnsemble(object):
         if hp.get("resample", "lhs") != "lhs":
             raise ValueError('hp["resample"]: ensembles redraw uniform Latin hypercubes only ("lhs"); per-member adaptive '
                              'sampling ("rad") is not supported')
+        if hp.get("sa_weights", False):
+            raise ValueError('hp["sa_weights"]: self-adaptive point weights are for single models (NeuralNetwork), not '
+                             'ensembles')
         self.pde = pde
         self.layers = [int(v) for v in hp["layers"]]
         self.ub = np.asarray(ub, dtype=np.float64)

@@ -14,7 +14,8 @@ It names one of the engine's residual kinds instead (`pde="burgers" | "burgers_i
 gradient on the GPU (csrc/).  Extra, optional hp keys: "dtype" ("f64" default = the reference's
 arithmetic, neuralnetwork.py:24-26 | "f32" = the throughput mode north_star sanctions) for the
 kernel arithmetic, "device" (HIP ordinal), "nt_guard" (see nt_optimization), "resample_every" / "resample" / "rad_*"
-(device-side redraws of the collocation set, see _resample_options).  Host interchange stays float64.
+(device-side redraws of the collocation set, see _resample_options), "sa_weights" / "sa_lr" / "sa_init" (self-adaptive
+point weights, see _sa_options).  Host interchange stays float64.
 
 Data parallel (north_star; the reference has no distributed code): launched as
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 1d-burgers/inf_cont_burgers.py [hp.json]
@@ -83,6 +84,38 @@ def _resample_options(hp, pde):
     return mode, int(k), float(c), None if pool is None else int(pool)
 
 
+def _sa_options(hp, pde):
+    """hp["sa_weights"] = true: self-adaptive point weights (McClenny & Braga-Neto, arXiv:2009.04544; Engine.sa_set_weights):
+    every data and collocation point gets a trainable weight lambda, the loss counts it with lambda^2, and every Adam step
+    ascends in the lambdas at rate hp["sa_lr"] (default tf_lr) while it descends in the network weights; L-BFGS then
+    minimises the weighted loss with the lambdas frozen.  hp["sa_init"] = [data, collocation] start values (default
+    [1.0, 1.0]).  Float64 Burgers inference on one device, without redraws: anything else is refused here, before any
+    engine is made, with the offending key named.  -> None (off) or (lr, init_u, init_f)."""
+    if not hp.get("sa_weights", False):
+        return None
+    if hp.get("dtype", "f64") not in ("f64", "float64"):
+        raise ValueError('hp["sa_weights"]: self-adaptive weights need hp["dtype"] = "f64" (got %r)' % (hp.get("dtype"),))
+    if pde != "burgers":
+        raise ValueError('hp["sa_weights"]: self-adaptive weights are for Burgers inference ("burgers"); the %s model is '
+                         'not supported' % pde)
+    if int(hp.get("resample_every", 0)) > 0:
+        raise ValueError('hp["sa_weights"]: self-adaptive weights keep their points; hp["resample_every"] must be 0')
+    if parallel.env_world()[0] > 1 and bool(hp.get("data_parallel", True)):
+        raise ValueError('hp["sa_weights"]: self-adaptive weights run on one device; a data-parallel world > 1 is not '
+                         'supported')
+    lr = hp.get("sa_lr", hp["tf_lr"])
+    if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not (np.isfinite(lr) and lr >= 0):
+        raise ValueError('hp["sa_lr"] must be a finite number >= 0 (got %r)' % (lr,))
+    init = hp.get("sa_init", [1.0, 1.0])
+    try:
+        init_u, init_f = (float(v) for v in init)
+    except (TypeError, ValueError):
+        raise ValueError('hp["sa_init"] must be [data, collocation] start values (got %r)' % (init,))
+    if not (np.isfinite(init_u) and np.isfinite(init_f)):
+        raise ValueError('hp["sa_init"] must be finite (got %r)' % (init,))
+    return float(lr), init_u, init_f
+
+
 class _AdamConfig(object):
     """Holds what tf.keras.optimizers.Adam held (neuralnetwork.py:19-22)."""
 
@@ -142,6 +175,7 @@ class NeuralNetwork(object):
         if pde is not None:
             self.pde = pde
         self._resample, self._rad_k, self._rad_c, self._rad_pool = _resample_options(hp, self.pde)
+        self._sa = _sa_options(hp, self.pde)
 
         # L-BFGS configuration, same fields as the reference (neuralnetwork.py:13-17)
         self.nt_config = Struct()
@@ -187,6 +221,8 @@ class NeuralNetwork(object):
             self.load_weights(hp["init_weights"])
         self._engine.adam_init(self.tf_optimizer.learning_rate, self.tf_optimizer.beta_1,
                                self.tf_optimizer.beta_2, self.tf_optimizer.epsilon)
+        if self._sa:
+            self._engine.sa_adam_init(self._sa[0])
         self._bound = None
         self.logger = logger
         # optional: re-draw the collocation set on the device every k Adam epochs (not in the reference, which
@@ -548,6 +584,12 @@ class NeuralNetwork(object):
         self.logger.log_train_start(self)
         X_u = self.tensor(X_u)
         u = self.tensor(u)
+        if self._sa:
+            # the start values, once per fit, on the data it trains (tf_optimization / nt_optimization bind the same set:
+            # no reset); the ascent itself runs inside every Adam step on the device
+            self._bind(X_u, u)
+            eng = self._engine
+            eng.sa_set_weights(np.full(eng.n_u, self._sa[1]), np.full(eng.n_f, self._sa[2]))
         self.tf_optimization(X_u, u)
         self.nt_optimization(X_u, u)
         self.logger.log_train_end(self.tf_epochs + self.nt_config.maxIter)
@@ -560,6 +602,13 @@ class NeuralNetwork(object):
 
     def predict(self, X_star):
         return self._engine.predict(_as_points(X_star, self))
+
+    def get_sa_weights(self):
+        """(lambda_u [N_u], lambda_f [N_f]): the self-adaptive point weights (hp["sa_weights"]) in the order of the data rows
+        and of the collocation set"""
+        if not self._sa:
+            raise ValueError('self-adaptive weights are off (hp["sa_weights"])')
+        return self._engine.sa_get_weights()
 
     def error_l2(self, X_star, reference, modulus=False):
         """The scripts' error metric ||reference - model(X_star)||_2 / ||reference||_2

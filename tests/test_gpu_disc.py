@@ -3,11 +3,16 @@ oracle (oracle/disc.py, itself pinned to the reference scripts run over the shim
 Tolerances: f64 1e-11 (relative to the largest gradient entry), f32 2e-4 gradient / 2e-5 loss -- the losses are
 sums over up to 250 x 501 squared residuals of magnitude 1e4..1e5, so f32 is looser than on the continuous models."""
 import json
+import os
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import golden
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import disc_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -143,6 +148,95 @@ def test_wide_hidden_layers_f32():
     assert abs(loss - lo) <= 2e-5 * abs(lo) and rel(grad, go) <= 2e-4
     with pytest.raises(pinn_native.PinnNativeError, match="hidden width"):
         pinn_native.Engine(layers, [-1.0], [1.0], pde="burgers_disc", dtype="f64")
+
+
+_SWEEP = disc_cases.fixed_cases() + disc_cases.random_cases()
+
+
+def test_sweep_cases_are_all_accepted_shapes():
+    """the sweep holds only shapes the engine admits (a refused one would be a failure, never a skip), and reaches
+    every edge it is meant to: H = 1 and 6, 1..5 output chunks, a narrow table, empty and one-point sets"""
+    assert all(disc_cases.accepted(*c[:6]) for c in _SWEEP)
+    chunks = {(c[2][-1] + 63) // 64 for c in _SWEEP}
+    assert chunks >= {1, 2, 3, 4, 5}
+    assert {len(c[2]) - 2 for c in _SWEEP} >= {1, 6}
+    assert any(c[2][-1] > c[3] + 1 for c in _SWEEP)
+    assert any(c[0] == "burgers_disc_ide" and (c[2][-1] + 63) // 64 >= 3 for c in _SWEEP)
+    assert any(c[0] == "burgers_disc_ide" and 1 in (c[4], c[5]) for c in _SWEEP)
+
+
+@pytest.mark.parametrize("case", _SWEEP, ids=[disc_cases.case_id(c) for c in _SWEEP])
+def test_shape_sweep_against_oracle(case, record):
+    """kernels_disc.h at the edges of its grid (H = 1, output-chunk counts 1..5, narrow tables, tile-edge widths,
+    empty / one-point / many-group sets): loss_grad, predict on every column, disc_predict of both sets, repeat bits and
+    a re-sized set 0 against oracle/disc.py.  n == 0 removes a set with its table (include/pinn_hip.h), so the
+    reference of an empty set's disc_predict is U.  Bounds: TOL for loss / gradient / terms, the lambda bound of
+    test_identification_loss_grad_vs_golden_and_oracle, network values f64 1e-12 / f32 5e-6 and stage predictions
+    f64 1e-10 / f32 1e-3, both relative to max(1, max|ref|)."""
+    import pinn_native
+    from oracle import disc, mlp
+    model, dtype, layers, q, n0, n1, seed = case
+    assert disc_cases.accepted(model, dtype, layers, q, n0, n1)
+    identify = model == "burgers_disc_ide"
+    sets, w, nu = disc_cases.build(model, layers, q, n0, n1, seed)
+    tl, tg = TOL[dtype]
+    lb, ub = np.array([-1.0]), np.array([1.0])
+    eng = pinn_native.Engine(layers, lb, ub, pde=model, dtype=dtype)
+    try:
+        assert eng.n_params == w.size
+        for s, (x, t, M) in enumerate(sets):
+            eng.disc_set_stage(s, x, t, M)
+        if not identify:
+            eng.set_pde_params(nu)
+        eng.set_weights(w)
+
+        def check_loss_grad(sets, tag):
+            loss, grad, terms = eng.loss_grad()
+            lo, go, ex = disc.disc_loss_grad(w, layers, lb, ub, sets, nu=nu, identify=identify)
+            d_loss, d_grad = abs(loss - lo) / abs(lo), rel(grad, go)
+            d_terms = max(abs(terms[0] - ex["sse"][0]), abs(terms[1] - ex["sse"][1])) / abs(lo)
+            d_lam = (np.max(np.abs(grad[-2:] - go[-2:])) / np.max(np.abs(go[-2:]))) if identify else 0.0
+            record(case=disc_cases.case_id(case), step=tag, dtype=dtype, loss=d_loss, grad=d_grad, terms=d_terms,
+                   lam=d_lam)
+            assert d_loss <= tl and d_grad <= tg and d_terms <= tl, (tag, d_loss, d_grad, d_terms)
+            if identify:
+                assert d_lam <= (1e-9 if dtype == "f64" else 5e-3), (tag, d_lam)
+            return loss, grad
+
+        loss, grad = check_loss_grad(sets, "first")
+        loss2, grad2 = eng.loss_grad()[:2]
+        assert loss2 == loss and np.array_equal(grad2, grad)
+
+        # network outputs on every column, at ragged counts
+        params = mlp.unpack(w[:-2] if identify else w, layers)
+        c1, c2 = (w[-2], np.exp(w[-1])) if identify else (1.0, nu)
+        rs = np.random.RandomState(seed + 1)
+        for n in (37, 1001):
+            xs = np.sort(rs.uniform(-1, 1, n))[:, None]
+            U = eng.predict(xs)
+            ref = mlp.forward_value(params, xs, lb, ub)
+            d_val = np.max(np.abs(U - ref)) / max(1.0, np.max(np.abs(ref)))
+            record(case=disc_cases.case_id(case), step="predict%d" % n, dtype=dtype, value=d_val)
+            assert U.shape == ref.shape and d_val <= (1e-12 if dtype == "f64" else 5e-6), (n, d_val)
+        # U + N(U) M^T with the table of each set (an empty set has none left)
+        xs = rs.uniform(-1, 1, 53)
+        for s, (x, _, M) in enumerate(sets):
+            P = eng.disc_predict(s, xs)
+            pred = disc.stage_prediction(params, xs[:, None], lb, ub, M if len(x) else None, c1, c2)[0]
+            d_st = np.max(np.abs(P - pred)) / max(1.0, np.max(np.abs(pred)))
+            record(case=disc_cases.case_id(case), step="stage%d" % s, dtype=dtype, stage=d_st)
+            assert d_st <= (1e-10 if dtype == "f64" else 1e-3), (s, d_st)
+
+        # set 0 replaced with another point count: new groups, new scratch sizes, same table
+        x0, t0, M0 = sets[0]
+        m = 21 if len(x0) != 21 else 5
+        xn = rs.uniform(-1, 1, (m, 1))
+        tn = -np.sin(np.pi * xn) + 0.1 * rs.standard_normal((m, 1))
+        sets = [(xn, tn, M0), sets[1]]
+        eng.disc_set_stage(0, xn, tn, M0)
+        check_loss_grad(sets, "resized")
+    finally:
+        eng.close()
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])

@@ -123,6 +123,183 @@ def test_error_l2_modulus_kind_schrodinger(schrodinger_sets, dtype):
     eng.close()
 
 
+# ---- forward-only evaluation over shapes: pinn_predict, pinn_residual_at, pinn_residual, pinn_error_l2 ----------------
+# (pde, dtype, W, H, n, seed); the comment names the forward kernel (engine.hip forward_chunk).  Width 20 with one output
+# (k_fwd20d / k_fwd20f) is test_width20_forward_sweeps_any_depth above.
+_FWD = [
+    # k_forward<real, JT> (one lane per point; JT = 10 float64, 20 float32): widths below 24 other than Burgers 20
+    *[("burgers", dt, W, 1 + i % 3, (65, 777, 1000, 63, 2049, 3001, 1)[i], 10 + i)
+      for i, W in enumerate((1, 7, 10, 11, 19, 21, 23)) for dt in ("f64", "f32")],
+    ("schrodinger", "f64", 20, 3, 1000, 20),          # k_forward: two outputs, so not k_fwd20d
+    ("schrodinger", "f32", 20, 2, 777, 21),           # k_forward
+    ("schrodinger", "f64", 23, 2, 513, 22),           # k_forward
+    ("schrodinger", "f32", 23, 3, 1000, 23),          # k_forward
+    ("burgers_ide", "f64", 13, 3, 800, 24),           # k_forward, lambdas from the weight image
+    ("burgers_ide", "f32", 13, 2, 999, 25),           # k_forward
+    # k_t16_fwd, NT = 4
+    ("burgers", "f64", 24, 3, 1000, 30),              # k_t16_fwd NT 4, weights from L2
+    ("burgers_ide", "f64", 40, 2, 1500, 31),          # k_t16_fwd NT 4
+    ("schrodinger", "f64", 64, 2, 777, 32),           # k_t16_fwd NT 4
+    ("burgers", "f32", 40, 2, 40000, 33),             # k_t16_fwd NT 4: 32768-point chunk with LDS weights, 7232 without
+    ("schrodinger", "f32", 64, 3, 600, 34),           # k_t16_fwd NT 4, few groups: weights from L2
+    # k_t16_fwd, NT = 8 (float64 and float32: eight waves, weights from L2)
+    ("burgers", "f64", 65, 2, 1000, 40),              # k_t16_fwd NT 8
+    ("burgers", "f32", 65, 3, 1000, 41),              # k_t16_fwd NT 8
+    ("schrodinger", "f64", 100, 2, 1200, 42),         # k_t16_fwd NT 8
+    ("schrodinger", "f32", 100, 4, 1000, 43),         # k_t16_fwd NT 8
+    ("burgers_ide", "f64", 128, 2, 800, 44),          # k_t16_fwd NT 8
+    ("burgers_ide", "f32", 128, 3, 800, 45),          # k_t16_fwd NT 8
+    # several 32768-point chunks per call
+    ("burgers", "f64", 24, 2, 32769, 50),             # k_t16_fwd NT 4, chunks of 32768 + 64
+    ("burgers", "f32", 24, 2, 70001, 51),             # k_t16_fwd NT 4, 2 LDS-weight chunks + one of 4480 points without
+    ("schrodinger", "f64", 100, 2, 70001, 52),        # k_t16_fwd NT 8, three chunks
+    ("burgers", "f32", 100, 2, 32769, 53),            # k_t16_fwd NT 8, two chunks
+]
+_BOX = {"burgers": (LB, UB), "burgers_ide": (LB, UB),
+        "schrodinger": (np.array([-5.0, 0.0]), np.array([5.0, np.pi / 2]))}
+
+
+def _fwd_net(pde_kind, W, H, rs):
+    layers = [2] + [W] * H + [2 if pde_kind == "schrodinger" else 1]
+    w = 0.9 / np.sqrt(W) * rs.standard_normal(sum(a * b + b for a, b in zip(layers[:-1], layers[1:])))
+    if pde_kind == "burgers_ide":
+        w = np.concatenate([w, [rs.uniform(0.5, 1.5), rs.uniform(-7.0, -4.0)]])
+    return layers, w
+
+
+def _fwd_oracle(pde_kind, layers, w, X, lb, ub, nu):
+    """(values [n, n_out], residual [n, n_out]) of oracle/pde.py"""
+    from oracle import mlp, pde
+    if pde_kind == "schrodinger":
+        f_u, f_v, (h, _, _, _), _ = pde.schrodinger_residual(mlp.unpack(w, layers), X, lb, ub)
+        return h, np.concatenate([f_u, f_v], axis=1)
+    if pde_kind == "burgers_ide":
+        f, (u, _, _, _), _ = pde.burgers_residual(mlp.unpack(w[:-2], layers), X, lb, ub, w[-2], np.exp(w[-1]))
+    else:
+        f, (u, _, _, _), _ = pde.burgers_residual(mlp.unpack(w, layers), X, lb, ub, 1.0, nu)
+    return u, f
+
+
+def _points(rs, n, lb, ub):
+    return np.column_stack([rs.uniform(lb[0], ub[0], n), rs.uniform(lb[1], ub[1], n)])
+
+
+@pytest.mark.parametrize("pde_kind,dtype,W,H,n,seed", _FWD,
+                         ids=["%s-%s-W%d-H%d-n%d" % c[:5] for c in _FWD])
+def test_forward_only_evaluation_sweep(pde_kind, dtype, W, H, n, seed, record):
+    """predict / residual_at / residual / error_l2 and the evaluation-point cache against oracle/pde.py and numpy, on
+    every forward kernel the caller-sized dispatch can pick.  Bounds: values f64 1e-12, f32 5e-6; residuals f64 1e-10,
+    f32 2e-4, both relative to max(1, max|ref|) (test_gpu_parity.py); error_l2 1e-14 relative against numpy on the
+    device's own prediction (test_error_l2_on_the_device_equals_numpy), 1e-13 for the modulus kind
+    (test_error_l2_modulus_kind_schrodinger)."""
+    import pinn_native
+    from oracle import mlp
+    rs = np.random.RandomState(seed)
+    lb, ub = _BOX[pde_kind]
+    layers, w = _fwd_net(pde_kind, W, H, rs)
+    nu = rs.uniform(0.001, 0.1)                       # not the default: a viscosity left in place would show
+    tol_u, tol_f = (1e-12, 1e-10) if dtype == "f64" else (5e-6, 2e-4)
+    tag = "%s-%s-W%d-H%d-n%d" % (pde_kind, dtype, W, H, n)
+
+    def dev(a, ref):
+        return np.max(np.abs(a - ref)) / max(1.0, np.max(np.abs(ref)))
+
+    eng = pinn_native.Engine(layers, lb, ub, pde=pde_kind, dtype=dtype)
+    try:
+        if pde_kind == "burgers":
+            eng.set_pde_params(nu)
+        eng.set_weights(w)
+        X = _points(rs, n, lb, ub)
+        u_ref, f_ref = _fwd_oracle(pde_kind, layers, w, X, lb, ub, nu)
+        # 1. values, 2. residuals at the caller's points
+        u = eng.predict(X)
+        f = eng.residual_at(X)
+        d_u, d_f = dev(u, u_ref), dev(f, f_ref)
+        # 3. the same points as the stored set, behind a data set (and boundary pairs): the residual starts at an offset
+        if pde_kind == "burgers_ide":
+            eng.set_data(X, rs.standard_normal((n, 1)))
+        else:
+            if pde_kind == "schrodinger":
+                tb = rs.uniform(lb[1], ub[1], (5, 1))
+                eng.set_boundary(np.hstack([0 * tb + lb[0], tb]), np.hstack([0 * tb + ub[0], tb]))
+            no = layers[-1]
+            eng.set_data(_points(rs, 9, lb, ub), rs.standard_normal((9, no)))
+            eng.set_collocation(X)
+        d_fs = dev(eng.residual(), f_ref)
+        record(case=tag, value=d_u, residual=d_f, residual_stored=d_fs)
+        assert u.shape == u_ref.shape and f.shape == f_ref.shape
+        assert d_u <= tol_u and d_f <= tol_f and d_fs <= tol_f, (d_u, d_f, d_fs)
+        # 4. error_l2: element-wise against numpy on the device's own prediction, and against the oracle's prediction
+        #    within the triangle inequality; the modulus kind on one- and two-output nets
+        ref = u_ref + 0.1 * rs.standard_normal(u_ref.shape)
+        e = eng.error_l2(X, ref)
+        e_np = np.linalg.norm(ref - u) / np.linalg.norm(ref)
+        e_or = np.linalg.norm(ref - u_ref) / np.linalg.norm(ref)
+        slack = np.linalg.norm(u - u_ref) / np.linalg.norm(ref)
+        href = np.sqrt(np.sum(u_ref ** 2, axis=1)) + 0.1 * np.abs(rs.standard_normal(n))
+        em = eng.error_l2(X, href, modulus=True)
+        em_np = np.linalg.norm(href - np.sqrt(np.sum(u ** 2, axis=1))) / np.linalg.norm(href)
+        record(case=tag, err_l2=abs(e - e_np) / e_np, err_l2_oracle=abs(e - e_or), err_l2_slack=slack,
+               err_l2_modulus=abs(em - em_np) / em_np)
+        assert abs(e - e_np) <= 1e-14 * e_np, (e, e_np)
+        assert abs(e - e_or) <= slack + 1e-14 * e_or, (e, e_or, slack)
+        assert abs(em - em_np) <= 1e-13 * em_np, (em, em_np)
+        # 5. the evaluation-point cache: same points after new weights, same count with new contents, fewer points
+        w2 = w * (1.0 + 0.05 * rs.standard_normal(w.size))
+        eng.set_weights(w2)
+        p2 = mlp.unpack(w2[:-2] if pde_kind == "burgers_ide" else w2, layers)
+        u2 = eng.predict(X)
+        d_c1 = dev(u2, mlp.forward_value(p2, X, lb, ub))
+        e2 = eng.error_l2(X, ref)
+        e2_np = np.linalg.norm(ref - u2) / np.linalg.norm(ref)
+        X2 = _points(rs, n, lb, ub)
+        d_c2 = dev(eng.predict(X2), mlp.forward_value(p2, X2, lb, ub))
+        X3 = X2[:max(1, n // 3)]
+        u3_ref, f3_ref = _fwd_oracle(pde_kind, layers, w2, X3, lb, ub, nu)
+        d_c3, d_c3f = dev(eng.predict(X3), u3_ref), dev(eng.residual_at(X3), f3_ref)
+        record(case=tag, value_new_weights=d_c1, value_new_points=d_c2, value_fewer_points=d_c3,
+               residual_fewer_points=d_c3f)
+        assert d_c1 <= tol_u and not np.array_equal(u2, u), d_c1
+        assert abs(e2 - e2_np) <= 1e-14 * e2_np and e2 != e, (e2, e2_np)
+        assert d_c2 <= tol_u and d_c3 <= tol_u and d_c3f <= tol_f, (d_c2, d_c3, d_c3f)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("pde_kind,dtype,W,H,sizes", [
+    ("burgers", "f64", 24, 2, (2047, 2048, 2049, 4096, 100003)),        # k_t16_fwd, one output
+    ("burgers", "f32", 7, 2, (2047, 2048, 2049, 4096, 100003)),         # k_forward, one output
+    ("schrodinger", "f64", 23, 2, (1023, 1024, 1025, 2047, 2048, 2049, 50003)),   # k_forward, two outputs
+    ("schrodinger", "f32", 100, 2, (1023, 1024, 1025, 2047, 2048, 2049, 50003)),  # k_t16_fwd NT 8, two outputs
+])
+def test_error_l2_at_reduction_block_edges(pde_kind, dtype, W, H, sizes, record):
+    """k_err_partial sums blocks of 2048 elements: counts that end just before, on and just past a block, two blocks,
+    and over 100 000 elements.  The element-wise kind reduces n n_out elements, the modulus kind n.  A two-output net
+    has no odd element-wise count, so it takes 2046 / 2048 / 2050 (n = 1023..1025) there and n = 2047..2049 for the
+    modulus kind.  Bounds as in test_forward_only_evaluation_sweep."""
+    import pinn_native
+    rs = np.random.RandomState(W + len(sizes))
+    lb, ub = _BOX[pde_kind]
+    layers, w = _fwd_net(pde_kind, W, H, rs)
+    eng = pinn_native.Engine(layers, lb, ub, pde=pde_kind, dtype=dtype)
+    try:
+        eng.set_weights(w)
+        for n in sizes:
+            X = _points(rs, n, lb, ub)
+            u = eng.predict(X)
+            ref = u + 0.1 * rs.standard_normal(u.shape)
+            e, e_np = eng.error_l2(X, ref), np.linalg.norm(ref - u) / np.linalg.norm(ref)
+            href = np.sqrt(np.sum(u ** 2, axis=1)) + 0.1 * rs.standard_normal(n)
+            em = eng.error_l2(X, href, modulus=True)
+            em_np = np.linalg.norm(href - np.sqrt(np.sum(u ** 2, axis=1))) / np.linalg.norm(href)
+            record(case="%s-%s-W%d" % (pde_kind, dtype, W), n=n, err_l2=abs(e - e_np) / e_np,
+                   err_l2_modulus=abs(em - em_np) / em_np)
+            assert abs(e - e_np) <= 1e-14 * e_np, (n, e, e_np)
+            assert abs(em - em_np) <= 1e-13 * em_np, (n, em, em_np)
+    finally:
+        eng.close()
+
+
 def test_status_records_the_first_nonfinite_evaluation(burgers_sets):
     """SURVEY 5 failure detection: the reference lets a NaN loss propagate (custom_lbfgs.py:154); the engine does the
     same and additionally records WHEN it happened"""

@@ -329,6 +329,36 @@ def test_disc_identification_eval(tag):
     assert np.max(np.abs(w - g["w_after_10"])) < 1e-12
 
 
+@pytest.mark.parametrize("model,layers,q", [("burgers_disc", [1, 7, 9], 8),               # H = 1
+                                             ("burgers_disc", [1, 6, 6, 65], 10),          # narrow table
+                                             ("burgers_disc_ide", [1, 6, 6, 6], 6)])       # lambda directions
+def test_disc_gradient_matches_finite_differences(model, layers, q):
+    """oracle.disc.disc_loss_grad at shapes no golden pins (the discrete-time shape sweep of test_gpu_disc.py relies on
+    them): central differences along unit directions, h = 1e-6.  The losses are sums (here ~1e2..1e3), so the bound
+    is 1e-7 |g.v| + 1e-8 |loss|: the second term is ~45 x the rounding floor eps |loss| / h of a central difference,
+    which a lambda_2 direction (derivative ~ exp(lambda_2) <= e^-4) can otherwise fall below."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+    import disc_cases
+    from oracle import disc
+    identify = model == "burgers_disc_ide"
+    assert disc_cases.accepted(model, "f64", layers, q, 23, 17)
+    sets, w, nu = disc_cases.build(model, layers, q, 23, 17, 7)
+    loss, g, _ = disc.disc_loss_grad(w, layers, [-1.0], [1.0], sets, nu=nu, identify=identify)
+    dirs = []
+    for seed in range(3):
+        v = np.random.RandomState(seed).standard_normal(w.size)
+        dirs.append(v / np.linalg.norm(v))
+    if identify:
+        dirs += [np.eye(w.size)[-2], np.eye(w.size)[-1]]
+    h = 1e-6
+    for v in dirs:
+        fp = disc.disc_loss_grad(w + h * v, layers, [-1.0], [1.0], sets, nu=nu, identify=identify)[0]
+        fm = disc.disc_loss_grad(w - h * v, layers, [-1.0], [1.0], sets, nu=nu, identify=identify)[0]
+        assert abs((fp - fm) / (2 * h) - g @ v) <= 1e-7 * abs(g @ v) + 1e-8 * abs(loss), ((fp - fm) / (2 * h), g @ v)
+
+
 @pytest.mark.parametrize("q", [1, 2, 3, 8, 81, 500])
 def test_gauss_legendre_butcher_conditions(q):
     """The Butcher files of the un-vendored PINNs submodule are restated, not copied: check the construction

@@ -36,7 +36,15 @@ enum {
   PINN_PDE_SCHRODINGER = 2, /* 1dcomplex-schrodinger/inf_cont_schrodinger.py:79-129                        */
   /* discrete-time (implicit Runge-Kutta) models: 1 input (x), q or q+1 outputs, see pinn_disc_set_stage */
   PINN_PDE_BURGERS_DISC = 3,     /* 1d-burgers/inf_disc_burgers.py:57-95   N = U U_x - nu U_xx             */
-  PINN_PDE_BURGERS_DISC_IDE = 4  /* 1d-burgers/ide_disc_burgers.py:81-115  N = l1 U U_x - exp(l2) U_xx     */
+  PINN_PDE_BURGERS_DISC_IDE = 4, /* 1d-burgers/ide_disc_burgers.py:81-115  N = l1 U U_x - exp(l2) U_xx     */
+  /* advection-diffusion-reaction, one output u(x, t), six fixed coefficients p = [a0, a1, nu, r1, r2, r3]
+   * (pinn_set_pde_params):  f = u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3.
+   * Burgers [0, 1, nu, 0, 0, 0], Allen-Cahn [0, 0, 1e-4, -5, 0, 5], Fisher-KPP [0, 0, D, -rho, rho, 0].
+   * loss = mean_f f^2 + mean_u (u - u*)^2 + mean_b [(u(lo) - u(hi))^2 + (u_x(lo) - u_x(hi))^2]; any set but the
+   * collocation set may be empty.  Kernel paths 0 (any shape, float32 / float64) and 7 (float64, width 20, 4 / 6 / 8
+   * hidden layers: the default there); PINN_EUNSUPPORTED for the other paths, self-adaptive weights and ensembles.
+   * (Additive: one enum value, no new entry point; the ABI version stays 6.) */
+  PINN_PDE_ADR = 5
 };
 enum { PINN_F32 = 0, PINN_F64 = 1 };
 enum {
@@ -70,7 +78,8 @@ int pinn_num_params(pinn_ctx* c, int64_t* n);       /* incl. lambda_1, lambda_2 
  *   data:        fit(X_u, u) arguments   (utils/neuralnetwork.py:138-143); targets [n, n_out];
  *                for PINN_PDE_BURGERS_IDE these points also carry the residual
  *                (ide_cont_burgers.py:88-91) and no collocation set is used.
- *   boundary:    X_lb, X_ub              (inf_cont_schrodinger.py:50-53), Schrodinger only. */
+ *   boundary:    X_lb, X_ub              (inf_cont_schrodinger.py:50-53): periodic pairs, row i of X_lb with row i of
+ *                X_ub; PINN_PDE_SCHRODINGER (h and h_x of both outputs) and PINN_PDE_ADR (u and u_x). */
 int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_total);
 int pinn_set_data(pinn_ctx* c, const double* X_u, const double* u, int64_t n, int64_t n_total);
 /* Collocation points drawn on the device instead of handed over: points [first, first + count) of an
@@ -86,7 +95,7 @@ int pinn_get_collocation(pinn_ctx* c, double* X, int64_t n);
  * are what pinn_residual_at returns at the current weights (stream order), and slots [first, first + count) of an
  * n_design-sample set are drawn from it WITH replacement (a set may hold a pool point more than once).  The weights are
  * quantised to integers, so every rank of a data-parallel job builds the same CDF and draws its own slice of one set
- * without communication.  pde 0 and 2, float32 and float64; PINN_EUNSUPPORTED for identification and discrete-time
+ * without communication.  pde 0, 2 and 5, float32 and float64; PINN_EUNSUPPORTED for identification and discrete-time
  * models, PINN_EINVAL for bad geometry, n_pool outside 1..2^24, k outside 1..4 or c_add outside [0, 64] -- both before
  * any device work, the set unchanged.  With the set assembled and count unchanged the call only enqueues work.  The mean()
  * denominator becomes n_design; the points survive pinn_set_data / pinn_set_boundary and are replaced by
@@ -108,7 +117,9 @@ int pinn_disc_set_stage(pinn_ctx* c, int set, const double* x, const double* tar
  * out [n][n_out] = U + N(U) M^T.  pinn_predict returns the plain network outputs U [n][n_out]. */
 int pinn_disc_predict(pinn_ctx* c, int set, const double* x, int64_t n, double* out);
 
-/* get_params (inf_cont_burgers.py:92): p[0] = nu for PINN_PDE_BURGERS and PINN_PDE_BURGERS_DISC */
+/* get_params (inf_cont_burgers.py:92): p[0] = nu for PINN_PDE_BURGERS and PINN_PDE_BURGERS_DISC.
+ * PINN_PDE_ADR: n must be 6, p = [a0, a1, nu, r1, r2, r3], all finite; otherwise PINN_EINVAL and the context keeps the
+ * coefficients it had (a new context holds Burgers', [0, 1, 0.01 / pi, 0, 0, 0]). */
 int pinn_set_pde_params(pinn_ctx* c, const double* p, int n);
 
 /* get_weights / set_weights (utils/neuralnetwork.py:68-89) */

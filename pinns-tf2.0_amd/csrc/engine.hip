@@ -112,6 +112,7 @@ struct pinn_ctx {
   int layers[MAX_DENSE + 1]{};
   int n_layers = 0;
   double lb[2]{}, ub[2]{}, nu = 0.0;
+  double adr[6]{};                   // PINN_PDE_ADR: a0, a1, nu, r1, r2, r3 (pinn_set_pde_params)
 
   // host copies of the point sets (float64, as handed over)
   std::vector<double> Xf, Xu, U, Xlo, Xhi;
@@ -271,10 +272,21 @@ struct pinn_ctx {
 static size_t real_size(const pinn_ctx* c) { return c->dtype == PINN_F64 ? 8 : 4; }
 static bool is_disc(const pinn_ctx* c) { return c->pde == PINN_PDE_BURGERS_DISC || c->pde == PINN_PDE_BURGERS_DISC_IDE; }
 static bool has_lambdas(int pde) { return pde == PINN_PDE_BURGERS_IDE || pde == PINN_PDE_BURGERS_DISC_IDE; }
+// advection-diffusion-reaction with run-time coefficients: template value PDE_ADR of the continuous kernels
+// (kernels_generic.h); it runs on the generic path 0 and, float64 width 20, on k_fused20d (path 7)
+static bool is_adr(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR; }
+// what a kernel of kind PDE takes in the place of the scalar nu
+template <typename real, int PDE>
+static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
+  if constexpr (PDE == PDE_ADR)
+    return AdrCoef<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5]};
+  else
+    return (real)c->nu;
+}
 
 // the fused kernel serves width-20 Burgers nets whose staged weights fit the 160 KiB LDS
 static bool fused_ok(const pinn_ctx* c) {
-  if (!fused20_supported(c->nd) || c->pde == PINN_PDE_SCHRODINGER || is_disc(c)) return false;
+  if (!fused20_supported(c->nd) || c->pde == PINN_PDE_SCHRODINGER || is_disc(c) || is_adr(c)) return false;
   const size_t lds = c->dtype == PINN_F64 ? fused20_lds_bytes<double>(c->nd.n_hidden)
                                           : fused20_lds_bytes<float>(c->nd.n_hidden);
   return lds <= 160 * 1024;
@@ -282,7 +294,7 @@ static bool fused_ok(const pinn_ctx* c) {
 
 // the register-stash kernel: float32, width 20, instantiated depths, weights + tiles within LDS
 static bool fused_regs_ok(const pinn_ctx* c) {
-  return c->dtype == PINN_F32 && fused20_supported(c->nd) && c->pde != PINN_PDE_SCHRODINGER && !is_disc(c) &&
+  return c->dtype == PINN_F32 && fused20_supported(c->nd) && c->pde != PINN_PDE_SCHRODINGER && !is_disc(c) && !is_adr(c) &&
          fused20m_depth_ok(c->nd.n_hidden) && fused20m_lds_bytes(c->nd.n_hidden) <= 160 * 1024;
 }
 
@@ -395,7 +407,7 @@ static int ensure_sets(pinn_ctx* c) {
   const int NO = c->nd.n_out;
   if (c->pde == PINN_PDE_BURGERS_IDE)
     REQUIRE(n_f == 0, "identification evaluates the residual at the data points; no collocation set");
-  if (c->pde != PINN_PDE_SCHRODINGER) REQUIRE(n_b == 0, "boundary pairs are Schrodinger-only");
+  if (c->pde != PINN_PDE_SCHRODINGER && !is_adr(c)) REQUIRE(n_b == 0, "boundary pairs are Schrodinger-only");
   const int n_all = 2 * n_b + n_u + n_f;
   REQUIRE(n_all > 0, "no training points set");
   const int n_pad = (n_all + 63) / 64 * 64;
@@ -409,8 +421,15 @@ static int ensure_sets(pinn_ctx* c) {
 
   std::vector<double> hx(n_pad), ht(n_pad), htg((size_t)NO * n_pad, 0.0);
   int g = 0;
-  for (int i = 0; i < n_b; ++i, ++g) { hx[g] = c->Xlo[2 * i]; ht[g] = c->Xlo[2 * i + 1]; }
-  for (int i = 0; i < n_b; ++i, ++g) { hx[g] = c->Xhi[2 * i]; ht[g] = c->Xhi[2 * i + 1]; }
+  if (is_adr(c)) {      // pair-interleaved [lo_0, hi_0, lo_1, hi_1, ...] on every kernel path: the partner of point g is g ^ 1
+    for (int i = 0; i < n_b; ++i, g += 2) {
+      hx[g] = c->Xlo[2 * i]; ht[g] = c->Xlo[2 * i + 1];
+      hx[g + 1] = c->Xhi[2 * i]; ht[g + 1] = c->Xhi[2 * i + 1];
+    }
+  } else {
+    for (int i = 0; i < n_b; ++i, ++g) { hx[g] = c->Xlo[2 * i]; ht[g] = c->Xlo[2 * i + 1]; }
+    for (int i = 0; i < n_b; ++i, ++g) { hx[g] = c->Xhi[2 * i]; ht[g] = c->Xhi[2 * i + 1]; }
+  }
   for (int i = 0; i < n_u; ++i, ++g) {
     hx[g] = c->Xu[2 * i]; ht[g] = c->Xu[2 * i + 1];
     for (int o = 0; o < NO; ++o) htg[(size_t)o * n_pad + g] = c->U[(size_t)i * NO + o];
@@ -664,7 +683,12 @@ static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
       }
     }
     (void)weighted;
-    if constexpr (sizeof(real) == 8 && PDE != 2)
+    if constexpr (sizeof(real) == 8 && PDE == PDE_ADR)
+      rc = fused20d_adr_launch_any(c->nd, sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
+                                   (const double*)c->tgt, (double)lbx, (double)lbt, (double)sx, (double)st,
+                                   pde_coef<double, PDE_ADR>(c), (double*)c->part, c->R, c->n_wg, c->row_index, c->stream,
+                                   ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr);
+    if constexpr (sizeof(real) == 8 && PDE != 2 && PDE != PDE_ADR)
       if (!weighted) rc = fused20d_launch_any(PDE, c->nd, sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
                                (const double*)c->tgt, (double)lbx, (double)lbt, (double)sx, (double)st,
                                (double)c->nu, (double*)c->part, c->R, c->n_wg, c->row_index,
@@ -672,7 +696,7 @@ static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
     if (rc) return fail(PINN_EHIP, "fused20d launch failed: %s", hipGetErrorString((hipError_t)rc));
   } else if (c->path == 2) {
     int rc = hipErrorInvalidValue;
-    if constexpr (sizeof(real) == 4 && PDE != 2) {
+    if constexpr (sizeof(real) == 4 && PDE != 2 && PDE != PDE_ADR) {
       if (c->nd.n_hidden == 8)
         rc = fused20m_launch<PDE, 8>(c->nd, sd, (const float*)c->theta_r, c->img, (const float*)c->xs,
                                      (const float*)c->ts, (const float*)c->tgt, (float)lbx, (float)lbt,
@@ -686,17 +710,19 @@ static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
     }
     if (rc) return fail(PINN_EHIP, "fused20m launch failed: %s", hipGetErrorString((hipError_t)rc));
   } else if (c->path == 1) {
-    const int rc = fused20_launch<real, PDE>(c->nd, sd, (const real*)c->theta_r, (const real*)c->xs,
-                                             (const real*)c->ts, (const real*)c->tgt, lbx, lbt, sx,
-                                             st, (real)c->nu, (vec4<real>*)c->S, (real*)c->part, c->R,
-                                             c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr);
+    int rc = hipErrorInvalidValue;
+    if constexpr (PDE != PDE_ADR)
+      rc = fused20_launch<real, PDE>(c->nd, sd, (const real*)c->theta_r, (const real*)c->xs,
+                                     (const real*)c->ts, (const real*)c->tgt, lbx, lbt, sx,
+                                     st, (real)c->nu, (vec4<real>*)c->S, (real*)c->part, c->R,
+                                     c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr);
     if (rc) return fail(PINN_EHIP, "fused20 launch failed: %s", hipGetErrorString((hipError_t)rc));
   } else {
     for (int base = 0, ci = 0; base < sd.n_pad; base += c->chunk, ++ci) {
       const int pts = (sd.n_pad - base < c->chunk) ? sd.n_pad - base : c->chunk;
       const dim3 grid(pts / 64), block(64);
       bool fwd_done = false;
-      if constexpr (sizeof(real) == 8) {
+      if constexpr (sizeof(real) == 8 && PDE != PDE_ADR) {
         if (c->path == 8) {
           const int rows_cap = t16_wgs(c, c->chunk);
           const int wgs = t16_wgs(c, pts) < rows_cap ? t16_wgs(c, pts) : rows_cap;
@@ -765,9 +791,11 @@ static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
                          (vec4<real>*)c->O);
       if (ev4 && ci == 0) HIPCHK(hipEventRecord(ev4[1], c->stream));
       bool bwd_done = false;
-      if (t16_bwd_on(c)) {
-        if (int rc = t16_bwd<real, PDE>(c, base, pts, lbx, lbt, sx, st, ci > 0 ? 1 : 0)) return rc;
-        bwd_done = true;
+      if constexpr (PDE != PDE_ADR) {
+        if (t16_bwd_on(c)) {
+          if (int rc = t16_bwd<real, PDE>(c, base, pts, lbx, lbt, sx, st, ci > 0 ? 1 : 0)) return rc;
+          bwd_done = true;
+        }
       }
       if constexpr (sizeof(real) == 4 && PDE == 2) {
         if (c->path == 3) {
@@ -790,7 +818,7 @@ static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
       hipLaunchKernelGGL((k_backward<real, PDE, KT>), grid, block, 0, c->stream, c->nd, sd,
                          (const real*)c->theta_r, (const real*)c->xs, (const real*)c->ts,
                          (const real*)c->tgt, base, sd.n_pad, c->chunk, lbx, lbt, sx, st,
-                         (real)c->nu, (const vec4<real>*)c->S, (const vec4<real>*)c->O,
+                         pde_coef<real, PDE>(c), (const vec4<real>*)c->S, (const vec4<real>*)c->O,
                          (vec4<real>*)c->ZA, (vec4<real>*)c->ZB, (real*)c->part, c->R,
                          ci > 0 ? 1 : 0);
     }
@@ -947,6 +975,7 @@ static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
   switch (c->pde) {                                                          \
     case PINN_PDE_BURGERS: rc = launch_sweeps<REAL, 0>(c, ev4, af); break;       \
     case PINN_PDE_BURGERS_IDE: rc = launch_sweeps<REAL, 1>(c, ev4, af); break;   \
+    case PINN_PDE_ADR: rc = launch_sweeps<REAL, PDE_ADR>(c, ev4, af); break;     \
     default: rc = launch_sweeps<REAL, 2>(c, ev4, af); break;                     \
   }
   if (is_disc(c)) rc = disc_eval_any(c, ev4, af);
@@ -1237,9 +1266,9 @@ static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) 
   HIPCHK(hipGetLastError());
   // 2. residuals at the current weights: pinn_residual_at's forward sweep and k_residual
   if (int rc = forward_taylor(c, c->rad.px, c->rad.pt, n_pad, n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS, c->rad.O)) return rc;
-#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid_m, block, 0, c->stream, 0, (int)M, n_pad, (const vec4<REAL>*)c->rad.O, (const REAL*)c->theta_r, c->nd.n_net, (REAL)c->nu, c->rad.f, NO)
-  if (f64) { if (c->pde == PINN_PDE_SCHRODINGER) RES(double, 2); else RES(double, 0); }
-  else { if (c->pde == PINN_PDE_SCHRODINGER) RES(float, 2); else RES(float, 0); }
+#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid_m, block, 0, c->stream, 0, (int)M, n_pad, (const vec4<REAL>*)c->rad.O, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->rad.f, NO)
+  if (f64) { if (c->pde == PINN_PDE_SCHRODINGER) RES(double, 2); else if (is_adr(c)) RES(double, PDE_ADR); else RES(double, 0); }
+  else { if (c->pde == PINN_PDE_SCHRODINGER) RES(float, 2); else if (is_adr(c)) RES(float, PDE_ADR); else RES(float, 0); }
 #undef RES
   HIPCHK(hipGetLastError());
   // 3.-4. weights and their CDF
@@ -1305,7 +1334,7 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   REQUIRE(out && layers && lb && ub, "null argument");
   REQUIRE(n_layers >= 3 && n_layers <= MAX_DENSE + 1, "need 3..%d layer sizes, got %d", MAX_DENSE + 1, n_layers);
   REQUIRE(dtype == PINN_F32 || dtype == PINN_F64, "dtype must be PINN_F32 or PINN_F64");
-  REQUIRE(pde_kind >= 0 && pde_kind <= 4, "unknown pde kind %d", pde_kind);
+  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADR, "unknown pde kind %d", pde_kind);
   const bool disc = pde_kind == PINN_PDE_BURGERS_DISC || pde_kind == PINN_PDE_BURGERS_DISC_IDE;
   if (disc) REQUIRE(layers[0] == 1, "discrete-time models take one input (x), got %d", layers[0]);
   else REQUIRE(layers[0] == 2, "input dimension must be 2 (x, t), got %d", layers[0]);
@@ -1332,6 +1361,7 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   c->lb[0] = lb[0]; c->ub[0] = ub[0];
   if (disc) { c->lb[1] = 0.0; c->ub[1] = 1.0; } else { c->lb[1] = lb[1]; c->ub[1] = ub[1]; }
   c->nu = 0.01 / M_PI;
+  c->adr[1] = 1.0; c->adr[2] = c->nu;              // PINN_PDE_ADR starts as Burgers: [0, 1, nu, 0, 0, 0]
   NetDesc& nd = c->nd;
   nd.n_hidden = n_layers - 2; nd.width = W; nd.n_out = NO;
   int off = 0;
@@ -1401,6 +1431,7 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   // default kernel family: 2 width-20 f32 (MFMA GEMVs, register stash), 7 its float64 counterpart (4x4x4 MFMA GEMVs,
   // no exchange), 1 width-20 HBM-stash, 3 wide MFMA sweeps (width 100, 2 outputs), 4 shape-generic MFMA sweeps, 0 generic
   c->path = fused_regs_ok(c) ? 2 : fused_f64_ok(c) ? 7 : fused_ok(c) ? 1 : wide_ok(c) ? 3 : t16_fused_ok(c) ? 8 : tile16_ok(c) ? 4 : 0;
+  if (is_adr(c)) c->path = fused_f64_ok(c) ? 7 : 0;   // the kind's two implementations (pinn_set_kernel_path refuses the others)
   *out = c;
   return 0;
 }
@@ -1535,7 +1566,7 @@ int pinn_set_data(pinn_ctx* c, const double* X_u, const double* u, int64_t n, in
 int pinn_set_boundary(pinn_ctx* c, const double* X_lb, const double* X_ub, int64_t n, int64_t n_total) {
   if (c && is_disc(c)) return fail(PINN_EINVAL, "pinn_set_boundary: discrete-time models take stage sets (pinn_disc_set_stage)");
   REQUIRE(c && ((X_lb && X_ub) || n == 0) && n >= 0 && n_total >= n, "bad boundary arguments");
-  REQUIRE(c->pde == PINN_PDE_SCHRODINGER || n == 0, "boundary pairs are Schrodinger-only");
+  REQUIRE(c->pde == PINN_PDE_SCHRODINGER || is_adr(c) || n == 0, "boundary pairs are Schrodinger-only");
   c->Xlo.assign(X_lb, X_lb + 2 * n);
   c->Xhi.assign(X_ub, X_ub + 2 * n);
   c->nb_total = n_total;
@@ -1545,6 +1576,13 @@ int pinn_set_boundary(pinn_ctx* c, const double* X_lb, const double* X_ub, int64
 
 int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
   REQUIRE(c && p && n >= 1, "bad pde params");
+  if (is_adr(c)) {      // a0, a1, nu, r1, r2, r3; nothing changes on a refusal
+    REQUIRE(n == 6, "pinn_set_pde_params: the adr kind takes 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
+    for (int i = 0; i < 6; ++i) REQUIRE(std::isfinite(p[i]), "pinn_set_pde_params: coefficient %d is not finite", i);
+    for (int i = 0; i < 6; ++i) c->adr[i] = p[i];
+    c->nu = p[2];
+    return 0;
+  }
   c->nu = p[0];
   return 0;
 }
@@ -2144,9 +2182,9 @@ int pinn_residual(pinn_ctx* c, double* f, int64_t n) {
   if ((size_t)cnt * NO > c->cap_f) { if (dev_alloc(&c->f_out, (size_t)cnt * NO * 8)) return PINN_EHIP; c->cap_f = (size_t)cnt * NO; }
   if (int rc2 = forward_taylor(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O)) return rc2;
   const dim3 grid((cnt + 255) / 256), block(256);
-#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, first, cnt, sd.n_pad, (const vec4<REAL>*)c->O, (const REAL*)c->theta_r, c->nd.n_net, (REAL)c->nu, c->f_out, NO)
-  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else RES(double, 2); }
-  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else RES(float, 2); }
+#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, first, cnt, sd.n_pad, (const vec4<REAL>*)c->O, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->f_out, NO)
+  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) RES(double, PDE_ADR); else RES(double, 2); }
+  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) RES(float, PDE_ADR); else RES(float, 2); }
 #undef RES
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)cnt * NO * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2165,9 +2203,9 @@ int pinn_residual_at(pinn_ctx* c, const double* X, int64_t n, double* f) {
   if (int rc = forward_taylor(c, c->xe, c->te, n_pad, n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS, c->Oe)) return rc;
   if ((size_t)n * NO > c->cap_f) { if (dev_alloc(&c->f_out, (size_t)n * NO * 8)) return PINN_EHIP; c->cap_f = (size_t)n * NO; }
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, 0, (int)n, n_pad, (const vec4<REAL>*)c->Oe, (const REAL*)c->theta_r, c->nd.n_net, (REAL)c->nu, c->f_out, NO)
-  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else RES(double, 2); }
-  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else RES(float, 2); }
+#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, 0, (int)n, n_pad, (const vec4<REAL>*)c->Oe, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->f_out, NO)
+  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) RES(double, PDE_ADR); else RES(double, 2); }
+  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) RES(float, PDE_ADR); else RES(float, 2); }
 #undef RES
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)n * NO * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2377,6 +2415,10 @@ int pinn_set_kernel_path(pinn_ctx* c, int path) {
           "7 (fused width-20 float64, register stash), 8 (fused float64 MFMA sweep, widths 65..128, 2-4 hidden layers)");
   if (c->sa.on && path != 7)
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: self-adaptive weights run on kernel path 7 only (pinn_sa_disable first)");
+  if (is_adr(c) && path != 0 && path != 7)
+    return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: the adr kind (pde 5) runs on kernel paths 0 and 7 only; path %d "
+                "(%s) has no variant for it", path, path == 1 ? "fused width-20" : path == 2 ? "float32 register stash" :
+                path == 3 ? "wide MFMA sweeps" : path == 8 ? "fused float64 MFMA sweep" : "shape-generic MFMA sweeps");
   if (path == 8) REQUIRE(t16_fused_ok(c), "the fused float64 sweep needs float64, hidden width 65..128 and 2, 3 or 4 hidden layers");
   if (path >= 4 && path <= 6) REQUIRE(tile16_ok(c), "the shape-generic MFMA sweeps need hidden width <= 128");
   if (path == 7)

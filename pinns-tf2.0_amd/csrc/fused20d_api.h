@@ -60,6 +60,13 @@ int fused20d_sa_launch_any(const NetDesc& nd, const SetDesc& sd, const double* t
                            double* part, int R, int n_wg, const int* row_index, hipStream_t stream, hipEvent_t ev_start,
                            hipEvent_t ev_stop);
 
+// one evaluation of the advection-diffusion-reaction kind (k_fused20d<PDE_ADR, H, .>; 4, 6 or 8 hidden layers): six
+// run-time coefficients, boundary block pair-interleaved; returns a hipError_t
+int fused20d_adr_launch_any(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
+                            const double* tgt, double lbx, double lbt, double sx, double st, const AdrCoef<double>& k,
+                            double* part, int R, int n_wg, const int* row_index, hipStream_t stream, hipEvent_t ev_start,
+                            hipEvent_t ev_stop);
+
 // the same with a point set per member -- xs, ts, tgt [n_members][sd.n_pad], all of one SetDesc -- and nu_k [n_members]
 // in device memory: member m's rows bit-identical to a solo launch on member m's set with viscosity nu_k[m]
 int fused20d_ens_sets_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,

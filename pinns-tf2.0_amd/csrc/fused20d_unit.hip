@@ -53,6 +53,20 @@ int fused20d_sa_launch_any(const NetDesc& nd, const SetDesc& sd, const double* t
 #undef ARGS
 }
 
+int fused20d_adr_launch_any(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
+                            const double* tgt, double lbx, double lbt, double sx, double st, const AdrCoef<double>& k,
+                            double* part, int R, int n_wg, const int* row_index, hipStream_t stream, hipEvent_t ev_start,
+                            hipEvent_t ev_stop) {
+#define ARGS nd, sd, th, xs, ts, tgt, lbx, lbt, sx, st, k, part, R, n_wg, row_index, stream, ev_start, ev_stop
+  switch (nd.n_hidden) {
+    case 4: return fused20d_adr_launch<4>(ARGS);
+    case 6: return fused20d_adr_launch<6>(ARGS);
+    case 8: return fused20d_adr_launch<8>(ARGS);
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef ARGS
+}
+
 int fused20d_ens_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
                             const double* ts, const double* tgt, double lbx, double lbt, double sx, double st, double nu,
                             double* part, int R, int n_wg, int n_members, const int* row_index, hipStream_t stream) {

@@ -200,9 +200,15 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
 // stand in the plain kernel.  The SaArgs travel in the slot of the scalar nu (as SETS's pointer does), so the argument
 // layout of every other instantiation stays as it was.  With `update` set (an Adam step) the slot-0 lane of a point writes
 // back lambda, m and v after one ascent step on dL/dlambda = 2 lambda r^2 inv_n -- its own residual only, no reduction.
-template <bool SETS, bool SAW = false>
-using f20d_nu_t = typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type;
+// PDE == PDE_ADR (advection-diffusion-reaction with run-time coefficients, kernels_generic.h), solo launch: the six
+// coefficients travel in the same slot (AdrCoef<double>, wave-uniform), and the set's periodic boundary pairs are stored
+// pair-interleaved, so the partner of point pt is pt ^ 1 = the neighbouring lane of the same slot: its (u, u_x) come by one
+// DPP quad permutation per 32-bit half -- no second launch, no LDS hand-over, no barrier.  The boundary part of the loss is
+// summed in the third per-wave slot (lacc[128], free when PDE != 1) and lands in the row at n_theta + 2.
+template <bool SETS, bool SAW = false, bool ADR = false>
+using f20d_nu_t = typename std::conditional<ADR, AdrCoef<double>, typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type>::type;
 __device__ __forceinline__ double f20d_nu(double nu) { return nu; }
+__device__ __forceinline__ double f20d_nu(const AdrCoef<double>& k) { return k.nu; }
 __device__ __forceinline__ double f20d_nu(const double* nu) { return nu[blockIdx.y]; }   // wave-uniform
 __device__ __forceinline__ double f20d_nu(const SaArgs& a) { return a.nu; }
 
@@ -211,9 +217,10 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
                                                   const double* __restrict__ ts, const double* __restrict__ tgt,
                                                   double* __restrict__ part, const int* __restrict__ row_index, int R,
                                                   int n_tiles, double lbx, double lbt, double sx, double st,
-                                                  f20d_nu_t<SETS, SAW> nu, SetDesc sd, long long* __restrict__ stamps,
-                                                  W20Desc nd_arg) {
+                                                  f20d_nu_t<SETS, SAW, PDE == PDE_ADR> nu, SetDesc sd,
+                                                  long long* __restrict__ stamps, W20Desc nd_arg) {
   static_assert(ENS || !SETS, "per-member point sets are an ensemble launch");
+  static_assert(PDE != PDE_ADR || (!ENS && !SETS && !SAW), "advection-diffusion-reaction: solo launch, plain loss");
   static_assert(!SAW || (PDE == 0 && !ENS), "self-adaptive weights: Burgers inference, solo launch");
   // weight offsets: compile-time constants in the one-tile variant (immediate operands; Adam step 41.9 -> 40.8 us with
   // the preloaded pointers); the tile-loop variant keeps them in SGPRs -- with immediates its schedule came out 9 %
@@ -298,6 +305,19 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
     if constexpr (!ONE_TILE) asm volatile("" : "+v"(sa_lam_p), "+v"(sa_alpha));
   }
   const double inv_nf = sd.inv_nf, inv_nu = sd.inv_nu;
+  // PDE_ADR, tile loop: the six coefficients and 1 / n_b would take 14 more scalar registers than the 96 of 106 these
+  // variants use already (6 of them spilled): every wave parks its own copy in the fourth quarter of its loss-part slots
+  // (lacc[192..], used when PDE == 1 only) and reads it back per tile through an opaque address, wave-uniform.  One tile
+  // per workgroup: they stay in scalar registers.
+  double* adr_park = nullptr;
+  if constexpr (PDE == PDE_ADR && !ONE_TILE) {
+    adr_park = lacc_all + wave * 256 + 192;
+    if ((tid & 63) == 0) {
+      adr_park[0] = nu.a0; adr_park[1] = nu.a1; adr_park[2] = nu.nu; adr_park[3] = nu.r1; adr_park[4] = nu.r2;
+      adr_park[5] = nu.r3; adr_park[6] = sd.inv_nb;
+    }
+  }
+  (void)adr_park;
   // per-lane partial sums of the loss parts and of the two lambda gradients (slot-0 lanes only) live in LDS, four
   // slots per lane behind the gradient accumulators: one read-modify-write per tile instead of eight registers held
   // across the whole kernel (which cost the identification variant 20 B of scratch per lane)
@@ -536,7 +556,37 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
 
     // ------------------------------------------------------------------ seeds + loss parts
     double sb[4] = {0.0, 0.0, 0.0, 0.0};
-    {
+    if constexpr (PDE == PDE_ADR) {
+      // partner of a boundary pair: pt ^ 1 is lane ^ 1 (pt = tile * 64 + wave * 16 + q), same slot.  The moves are
+      // unconditional (no divergent branch around a cross-lane move); their results count in the boundary class only.
+      const double pu = dpp_mov<DPP_QUAD_XOR1>(o[0]), pp = dpp_mov<DPP_QUAD_XOR1>(o[1]);
+      AdrCoef<double> kc;
+      double inv_nb;
+      if constexpr (ONE_TILE) { kc = nu; inv_nb = sd.inv_nb; }
+      else {
+        const double* kp = adr_park;
+        asm volatile("" : "+v"(kp));
+        kc = AdrCoef<double>{kp[0], kp[1], kp[2], kp[3], kp[4], kp[5]};
+        inv_nb = kp[6];
+      }
+      const int cls = point_class_adr(sd, pt);
+      if (cls == CLS_COL) {
+        const double u = o[0], adv = kc.a0 + kc.a1 * u;
+        const double f = o[2] + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
+        const double fbar = 2.0 * f * inv_nf;
+        if (s == 0) lacc[0] += f * f * inv_nf;
+        sb[0] = fbar * (kc.a1 * o[1] + kc.r1 + u * (2.0 * kc.r2 + 3.0 * kc.r3 * u));
+        sb[1] = fbar * adv; sb[2] = fbar; sb[3] = -kc.nu * fbar;
+      } else if (cls == CLS_DATA) {
+        const double dd = o[0] - tgt[pt];
+        if (s == 0) lacc[64] += dd * dd * inv_nu;
+        sb[0] = 2.0 * dd * inv_nu;
+      } else if (cls != CLS_PAD) {       // own minus partner: +2 (lo - hi) / n_b at lo, -2 (lo - hi) / n_b at hi
+        const double du = o[0] - pu, dp = o[1] - pp;
+        if (s == 0 && cls == CLS_BLO) lacc[128] += (du * du + dp * dp) * inv_nb;
+        sb[0] = 2.0 * du * inv_nb; sb[1] = 2.0 * dp * inv_nb;
+      }
+    } else {
       // (SAW: pde 0 has no boundary pairs; classing without n_b saves the tile-loop variants a scalar register)
       const int cls = SAW ? (pt < sd.n_u ? CLS_DATA : pt < sd.n_all ? CLS_COL : CLS_PAD) : point_class(sd, pt);
       const bool res = (PDE == 0) ? (cls == CLS_COL) : (cls == CLS_DATA);
@@ -805,7 +855,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
       idx[it] = (!ONE_TILE && e < NE) ? row_index[e] : -1;
     }
     const double t0 = wave_sum(lacc[0]), t1 = wave_sum(lacc[64]);
-    const double t2 = PDE == 1 ? wave_sum(lacc[128]) : 0.0, t3 = PDE == 1 ? wave_sum(lacc[192]) : 0.0;
+    const double t2 = (PDE == 1 || PDE == PDE_ADR) ? wave_sum(lacc[128]) : 0.0, t3 = PDE == 1 ? wave_sum(lacc[192]) : 0.0;
     __syncthreads();                                   // every wave's accumulators are final
     double* const scal = wl;                           // the weight copy is dead: 4 x 4 loss / lambda partials
     if (lane == 0) { scal[wave * 4 + 0] = t0; scal[wave * 4 + 1] = t1; scal[wave * 4 + 2] = t2; scal[wave * 4 + 3] = t3; }
@@ -827,8 +877,9 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
     }
     if (tid < 4) {
       const double v = ((scal[tid] + scal[4 + tid]) + scal[8 + tid]) + scal[12 + tid];
-      if (tid == 0) { row[nd.n_theta + 0] = v; row[nd.n_theta + 2] = 0.0; }
+      if (tid == 0) { row[nd.n_theta + 0] = v; if (PDE != PDE_ADR) row[nd.n_theta + 2] = 0.0; }
       if (tid == 1) row[nd.n_theta + 1] = v;
+      if (PDE == PDE_ADR && tid == 2) row[nd.n_theta + 2] = v;     // the periodic pairs' part
       if (PDE == 1 && tid == 2) row[nd.n_net] = v;
       if (PDE == 1 && tid == 3) row[nd.n_net + 1] = v;
     }
@@ -888,6 +939,35 @@ inline int fused20d_sa_launch(const NetDesc& nd, const SetDesc& sd, const double
   else
     hipLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles, lbx,
                        lbt, sx, st, sa, sd, (long long*)nullptr, w20_desc(H, false));
+  return (int)hipGetLastError();
+}
+
+// one evaluation of the advection-diffusion-reaction kind (coefficients k, pair-interleaved boundary block): the solo
+// launch plan; returns a hipError_t
+template <int H>
+inline int fused20d_adr_launch(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
+                               const double* tgt, double lbx, double lbt, double sx, double st, const AdrCoef<double>& k,
+                               double* part, int R, int n_wg, const int* row_index, hipStream_t stream,
+                               hipEvent_t ev_start, hipEvent_t ev_stop) {
+  if (!w20_layout_ok(nd, H, false)) return (int)hipErrorInvalidValue;
+  const size_t lds = fused20d_lds_bytes(H, nd.n_theta);
+  static unsigned long long attr_set = 0;
+  if (first_call_on_device(attr_set)) {
+    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<PDE_ADR, H, false>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)k_fused20d<PDE_ADR, H, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  const int n_tiles = sd.n_pad / 64;
+  auto* const kern = n_wg >= n_tiles ? k_fused20d<PDE_ADR, H, true> : k_fused20d<PDE_ADR, H, false>;
+  if (ev_start && ev_stop)
+    hipExtLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, ev_start, ev_stop, 0, th, xs, ts, tgt, part,
+                          row_index, R, n_tiles, lbx, lbt, sx, st, k, sd, (long long*)nullptr, w20_desc(H, false));
+  else
+    hipLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles, lbx,
+                       lbt, sx, st, k, sd, (long long*)nullptr, w20_desc(H, false));
   return (int)hipGetLastError();
 }
 

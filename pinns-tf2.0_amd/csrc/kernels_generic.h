@@ -8,6 +8,7 @@
 // is what the reference's nested GradientTapes compute
 // (1d-burgers/inf_cont_burgers.py:65-90, utils/neuralnetwork.py:55-59).
 #pragma once
+#include <type_traits>
 #include "wave.h"
 
 namespace pinn {
@@ -34,6 +35,27 @@ struct SetDesc {
   int n_pad;                 // rounded up to a multiple of 64
   double inv_nb, inv_nu, inv_nf;   // 1 / GLOBAL set sizes (mean() denominators)
 };
+
+// Template number of the advection-diffusion-reaction kind (PINN_PDE_ADR = 5 of the C interface; the enum's 3 and 4 are the
+// discrete-time models of kernels_disc.h, which are no template values of the continuous kernels):
+//   f = u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3
+// Its six run-time coefficients travel where the other kinds pass the scalar nu (pde_coef_t), so the argument list of
+// every other instantiation is what it was.  Boundary pairs of this kind are stored pair-interleaved,
+// [lo_0, hi_0, lo_1, hi_1, ...]: the partner of point g is g ^ 1.
+constexpr int PDE_ADR = 3;
+template <typename real> struct AdrCoef { real a0, a1, nu, r1, r2, r3; };
+template <typename real, int PDE>
+using pde_coef_t = typename std::conditional<PDE == PDE_ADR, AdrCoef<real>, real>::type;
+template <typename real> __device__ __forceinline__ real coef_nu(real nu) { return nu; }
+template <typename real> __device__ __forceinline__ real coef_nu(const AdrCoef<real>& k) { return k.nu; }
+template <typename real> __device__ __forceinline__ AdrCoef<real> coef_adr(real) { return AdrCoef<real>{0, 0, 0, 0, 0, 0}; }
+template <typename real> __device__ __forceinline__ AdrCoef<real> coef_adr(const AdrCoef<real>& k) { return k; }
+// residual of the new kind from the four Taylor channels of a point
+template <typename real>
+__device__ __forceinline__ real adr_residual(const AdrCoef<real>& k, const vec4<real>& o) {
+  const real u = o.x;
+  return o.z + (k.a0 + k.a1 * u) * o.y - k.nu * o.w + u * (k.r1 + u * (k.r2 + k.r3 * u));
+}
 
 template <typename real> __device__ __forceinline__ real tanh_r(real z);
 template <> __device__ __forceinline__ float tanh_r<float>(float z) { return tanhf(z); }
@@ -129,6 +151,14 @@ __device__ __forceinline__ int point_class(const SetDesc& sd, int g) {
   return CLS_PAD;
 }
 
+// the same for the pair-interleaved boundary block of PDE_ADR: lo points at even, hi points at odd indices below 2 n_b
+__device__ __forceinline__ int point_class_adr(const SetDesc& sd, int g) {
+  if (g < 2 * sd.n_b) return (g & 1) ? CLS_BHI : CLS_BLO;
+  if (g < 2 * sd.n_b + sd.n_u) return CLS_DATA;
+  if (g < sd.n_all) return CLS_COL;
+  return CLS_PAD;
+}
+
 // Per-point loss contributions and output adjoints.
 //   sb[o] <- (h_bar, p_bar, q_bar, r_bar) of output o;  lt[0..2] <- (f, data, boundary) loss parts
 //   dl[0..1] <- d/d lambda_1, d/d lambda_2 contributions (identification only)
@@ -138,27 +168,48 @@ template <typename real, int PDE>
 __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_pad, const vec4<real>& ou,
                                                 const vec4<real>& ov, const vec4<real>* __restrict__ O,
                                                 const real* __restrict__ tgt, real c1, real c2,
-                                                vec4<real> sb[2], real lt[3], real dl[2]);
+                                                vec4<real> sb[2], real lt[3], real dl[2],
+                                                const AdrCoef<real>& k = AdrCoef<real>{0, 0, 0, 0, 0, 0});
 template <typename real, int PDE>
 __device__ __forceinline__ void point_seeds(const SetDesc& sd, int g, int n_pad,
                                             const vec4<real>* __restrict__ O,
                                             const real* __restrict__ tgt, real c1, real c2,
-                                            vec4<real> sb[2], real lt[3], real dl[2]) {
+                                            vec4<real> sb[2], real lt[3], real dl[2],
+                                            const AdrCoef<real>& k = AdrCoef<real>{0, 0, 0, 0, 0, 0}) {
   const vec4<real> ou = O[g], ov = PDE == 2 ? O[(size_t)n_pad + g] : vec4<real>{0, 0, 0, 0};
-  point_seeds_own<real, PDE>(sd, g, n_pad, ou, ov, O, tgt, c1, c2, sb, lt, dl);
+  point_seeds_own<real, PDE>(sd, g, n_pad, ou, ov, O, tgt, c1, c2, sb, lt, dl, k);
 }
 template <typename real, int PDE>
 __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_pad, const vec4<real>& ou,
                                                 const vec4<real>& ov, const vec4<real>* __restrict__ O,
                                                 const real* __restrict__ tgt, real c1, real c2,
-                                                vec4<real> sb[2], real lt[3], real dl[2]) {
-  const int cls = point_class(sd, g);
+                                                vec4<real> sb[2], real lt[3], real dl[2], const AdrCoef<real>& k) {
+  const int cls = PDE == PDE_ADR ? point_class_adr(sd, g) : point_class(sd, g);
   sb[0] = sb[1] = vec4<real>{0, 0, 0, 0};
   lt[0] = lt[1] = lt[2] = real(0);
   dl[0] = dl[1] = real(0);
   if (cls == CLS_PAD) return;
   const real inv_nf = (real)sd.inv_nf, inv_nu = (real)sd.inv_nu, inv_nb = (real)sd.inv_nb;
-  if (PDE == 0 || PDE == 1) {   // Burgers (inference / identification)
+  if constexpr (PDE == PDE_ADR) {   // advection-diffusion-reaction, run-time coefficients, periodic pairs (g, g ^ 1)
+    const vec4<real> o = ou;
+    if (cls == CLS_COL) {
+      const real u = o.x, adv = k.a0 + k.a1 * u;
+      const real f = adr_residual(k, o);
+      const real fb = real(2) * f * inv_nf;
+      lt[0] = f * f * inv_nf;
+      sb[0].x = fb * (k.a1 * o.y + k.r1 + u * (real(2) * k.r2 + real(3) * k.r3 * u));
+      sb[0].y = fb * adv; sb[0].z = fb; sb[0].w = -k.nu * fb;
+    } else if (cls == CLS_DATA) {
+      const real dd = o.x - tgt[g];
+      lt[1] = dd * dd * inv_nu;
+      sb[0].x = real(2) * dd * inv_nu;
+    } else {                        // own minus partner: +2 (lo - hi) / n_b at lo, -2 (lo - hi) / n_b at hi
+      const vec4<real> pr = O[g ^ 1];
+      const real du = o.x - pr.x, dp = o.y - pr.y;
+      if (cls == CLS_BLO) lt[2] = (du * du + dp * dp) * inv_nb;
+      sb[0].x = real(2) * du * inv_nb; sb[0].y = real(2) * dp * inv_nb;
+    }
+  } else if (PDE == 0 || PDE == 1) {   // Burgers (inference / identification)
     const vec4<real> o = ou;
     const bool res = (PDE == 0) ? (cls == CLS_COL) : (cls == CLS_DATA);
     if (res) {
@@ -241,7 +292,7 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
                                                  const real* __restrict__ ts,
                                                  const real* __restrict__ tgt, int base, int n_pad,
                                                  int s_pad, real lbx, real lbt, real sx, real st,
-                                                 real nu, const vec4<real>* __restrict__ S,
+                                                 pde_coef_t<real, PDE> nu, const vec4<real>* __restrict__ S,
                                                  const vec4<real>* __restrict__ O,
                                                  vec4<real>* __restrict__ ZA,
                                                  vec4<real>* __restrict__ ZB,
@@ -252,12 +303,13 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
   const int W = nd.width, H = nd.n_hidden, NO = nd.n_out;
   real* __restrict__ row = part + (size_t)blockIdx.x * R;
 
-  real c1 = real(1), c2 = nu;
+  real c1 = real(1), c2 = coef_nu<real>(nu);
   if (PDE == 1) { c1 = th[nd.n_net]; c2 = exp(th[nd.n_net + 1]); }
 
   vec4<real> sb[2];
   real lt[3], dl[2];
-  point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl);
+  if constexpr (PDE == PDE_ADR) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr<real>(nu));
+  else point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl);
 
   auto put = [&](int idx, real v) {   // lane-uniform idx; executed by one lane
     row[idx] = accumulate ? row[idx] + v : v;
@@ -374,18 +426,20 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
 // PDE residual at stored points from the forward outputs (f_model()).
 template <typename real, int PDE>
 __global__ void k_residual(int first, int n, int n_pad, const vec4<real>* __restrict__ O,
-                           const real* __restrict__ th, int n_net, real nu,
+                           const real* __restrict__ th, int n_net, pde_coef_t<real, PDE> nu,
                            double* __restrict__ f, int n_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int g = first + i;
-  if (PDE == 2) {
+  if constexpr (PDE == PDE_ADR) {
+    f[i] = (double)adr_residual(nu, O[g]);
+  } else if (PDE == 2) {
     const vec4<real> ou = O[g], ov = O[(size_t)n_pad + g];
     const real u = ou.x, v = ov.x, h2 = u * u + v * v;
     f[(size_t)i * 2 + 0] = (double)(ou.z + real(0.5) * ov.w + h2 * v);
     f[(size_t)i * 2 + 1] = (double)(ov.z - real(0.5) * ou.w - h2 * u);
   } else {
-    real c1 = real(1), c2 = nu;
+    real c1 = real(1), c2 = coef_nu<real>(nu);
     if (PDE == 1) { c1 = th[n_net]; c2 = exp(th[n_net + 1]); }
     const vec4<real> o = O[g];
     f[i] = (double)(o.z + c1 * o.x * o.y - c2 * o.w);

@@ -10,7 +10,8 @@ return shapes (numpy arrays where the reference returns eager tensors).
 
 What changes: there is no TensorFlow, so a subclass cannot spell its PDE with GradientTapes.
 It names one of the engine's residual kinds instead (`pde="burgers" | "burgers_ide" |
-"schrodinger" | "burgers_disc" | "burgers_disc_ide"`) and the engine evaluates forward, u_t/u_x/u_xx, residual, loss and the flat
+"schrodinger" | "burgers_disc" | "burgers_disc_ide" | "adr"`; the last is u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 = 0
+with fixed coefficients the subclass hands to `self._engine.set_pde_params(a0, a1, nu, r1, r2, r3)`) and the engine evaluates forward, u_t/u_x/u_xx, residual, loss and the flat
 gradient on the GPU (csrc/).  Extra, optional hp keys: "dtype" ("f64" default = the reference's
 arithmetic, neuralnetwork.py:24-26 | "f32" = the throughput mode north_star sanctions) for the
 kernel arithmetic, "device" (HIP ordinal), "nt_guard" (see nt_optimization), "resample_every" / "resample" / "rad_*"
@@ -79,7 +80,7 @@ def _resample_options(hp, pde):
     if mode == "rad":
         if int(hp.get("resample_every", 0)) <= 0:
             raise ValueError('hp["resample"] = "rad" redraws every hp["resample_every"] epochs; resample_every must be > 0')
-        if pde not in ("burgers", "schrodinger"):
+        if pde not in ("burgers", "schrodinger", "adr"):
             raise ValueError('hp["resample"] = "rad" needs a collocation set; the %s model has none' % pde)
     return mode, int(k), float(c), None if pool is None else int(pool)
 
@@ -195,6 +196,9 @@ class NeuralNetwork(object):
 
         # one rank of a torchrun launch = one shard of the point sets on GPU LOCAL_RANK (module docstring); the
         # discrete-time models hold <= 256 points and stay replicated
+        if self.pde == "adr" and parallel.env_world()[0] > 1 and bool(hp.get("data_parallel", True)):
+            raise ValueError('pde "adr": a data-parallel launch (world > 1) is not supported for this kind; run one process, '
+                             'or set hp["data_parallel"] = false for independent replicas')
         self._dp = None if self.pde.startswith("burgers_disc") else parallel.from_env(bool(hp.get("data_parallel", True)))
         self.is_root = parallel.is_root()
         world, _, local_rank = parallel.env_world()

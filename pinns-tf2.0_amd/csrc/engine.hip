@@ -104,8 +104,24 @@ struct Range {
 static constexpr int CHUNK_POINTS = 32768;   // points per forward/backward launch pair
 static constexpr int LOSS_SLOTS = 4;         // residual, data, boundary, pad
 
+// The kernel families that serve a loss+gradient evaluation.  The values are the numbers of the ABI (pinn_set_kernel_path,
+// include/pinn_hip.h); what the engine knows about each path stands in PATHS and path_rows below, nowhere else.
+enum KernelPath : int {
+  KP_GENERIC = 0,    // one lane per point, chunked
+  KP_FUSED20 = 1,    // width 20, one kernel, whole-set stash in HBM (kernels_fused20.h)
+  KP_FUSED20M = 2,   // width 20 float32, one kernel, register stash (kernels_fused20m.h)
+  KP_WIDE = 3,       // width 100, two outputs, float32: wide MFMA sweeps per chunk (kernels_wide.h)
+  KP_T16 = 4,        // shape-generic MFMA sweeps per chunk (kernels_tile16.h)
+  KP_T16_FWD = 5,    // 4's forward half with the generic reverse half (tests)
+  KP_T16_BWD = 6,    // the generic forward half with 4's reverse half (tests)
+  KP_FUSED20D = 7,   // width 20 float64, one kernel, register stash (kernels_fused20d.h)
+  KP_T16_FUSED = 8,  // float64 widths 65..128: forward + reverse of a group in one kernel per chunk (kernels_tile16f.h)
+  KP_COUNT
+};
+
 struct pinn_ctx {
-  int device = 0, dtype = PINN_F32, pde = PINN_PDE_BURGERS, path = 0;
+  int device = 0, dtype = PINN_F32, pde = PINN_PDE_BURGERS;
+  KernelPath path = KP_GENERIC;
   hipStream_t stream = nullptr;
   bool own_stream = true;            // false: an ensemble member, on its ensemble's stream (pinn_ens_create)
   NetDesc nd{};
@@ -316,8 +332,44 @@ static bool tile16_ok(const pinn_ctx* c) { return !is_disc(c) && c->nd.width <= 
 static bool t16_fused_ok(const pinn_ctx* c) {
   return tile16_ok(c) && c->dtype == PINN_F64 && c->nd.width > 64 && c->nd.n_hidden >= 2 && c->nd.n_hidden <= 4;
 }
-static bool t16_fwd_on(const pinn_ctx* c) { return c->path == 4 || c->path == 5; }
-static bool t16_bwd_on(const pinn_ctx* c) { return c->path == 4 || c->path == 6 || c->path == 8; }   // (one partial row per workgroup, t16_wgs)
+static bool any_net_ok(const pinn_ctx*) { return true; }
+
+// what the host code has to know about a kernel path; PATHS is indexed by KernelPath, its rows in the order 0..8
+enum Stash { STASH_NONE, STASH_CHUNK, STASH_SET };   // the forward sweep's stash in HBM: none, one chunk's, the whole set's
+struct PathInfo {
+  const char* name;
+  Stash stash;
+  bool one_launch;                  // one kernel per evaluation, the timing events attached to the launch itself
+  bool (*ok)(const pinn_ctx*);      // eligibility, and what pinn_set_kernel_path answers where it fails
+  const char* needs;
+};
+static const PathInfo PATHS[KP_COUNT] = {
+    {"generic", STASH_CHUNK, false, any_net_ok, ""},
+    {"fused width-20", STASH_SET, true, fused_ok,
+     "the fused path needs hidden width 20, a Burgers problem and weights that fit LDS"},
+    {"float32 register stash", STASH_NONE, true, fused_regs_ok,
+     "the register-stash path needs float32, hidden width 20, 4, 6, 8 or 10 hidden layers and a Burgers problem"},
+    {"wide MFMA sweeps", STASH_CHUNK, false, wide_ok, "the wide path needs float32, hidden width 100 and two outputs"},
+    // KP_T16 and its two halves
+    {"shape-generic MFMA sweeps", STASH_CHUNK, false, tile16_ok, "the shape-generic MFMA sweeps need hidden width <= 128"},
+    {"shape-generic MFMA sweeps", STASH_CHUNK, false, tile16_ok, "the shape-generic MFMA sweeps need hidden width <= 128"},
+    {"shape-generic MFMA sweeps", STASH_CHUNK, false, tile16_ok, "the shape-generic MFMA sweeps need hidden width <= 128"},
+    {"float64 register stash", STASH_NONE, true, fused_f64_ok,
+     "the float64 register-stash path needs float64, hidden width 20, 4, 6 or 8 hidden layers and a Burgers problem"},
+    // KP_T16_FUSED (no stash: 257 MB at cfg 4 that nothing would touch)
+    {"fused float64 MFMA sweep", STASH_NONE, false, t16_fused_ok,
+     "the fused float64 sweep needs float64, hidden width 65..128 and 2, 3 or 4 hidden layers"},
+};
+// default kernel family, fastest first: width-20 f32 (MFMA GEMVs, register stash), its float64 counterpart (4x4x4 MFMA
+// GEMVs, no exchange), width-20 HBM-stash, wide MFMA sweeps (width 100, 2 outputs), the fused float64 sweep, the
+// shape-generic MFMA sweeps, generic
+static const KernelPath PATH_PREFERENCE[] = {KP_FUSED20M, KP_FUSED20D, KP_FUSED20, KP_WIDE, KP_T16_FUSED, KP_T16, KP_GENERIC};
+// the adr kind's two implementations
+static bool adr_has_path(KernelPath p) { return p == KP_GENERIC || p == KP_FUSED20D; }
+static bool path_ok(const pinn_ctx* c, KernelPath p) { return PATHS[p].ok(c) && (!is_adr(c) || adr_has_path(p)); }
+
+static bool t16_fwd_on(const pinn_ctx* c) { return c->path == KP_T16 || c->path == KP_T16_FWD; }
+static bool t16_bwd_on(const pinn_ctx* c) { return c->path == KP_T16 || c->path == KP_T16_BWD || c->path == KP_T16_FUSED; }
 // Launch plan of the shape-generic sweeps for a chunk of `pts` points (measured, profiles/r01_t16_plan.txt):
 //   widths <= 64, float32: few groups (<= 3 per CU: every group resident at once) -> weights straight from L2, three
 //     workgroups per CU; many groups -> weights staged in LDS, two workgroups per CU;
@@ -354,6 +406,20 @@ static int t16_wgs(const pinn_ctx* c, int pts) {
   if (per_cu > fit) per_cu = fit;
   const int cap = per_cu * c->n_cu;
   return g < cap ? g : cap;
+}
+// persistent workgroups of the wide sweeps for a chunk of `pts` points
+static int wide_wgs(const pinn_ctx* c, int pts) { return pts / 16 < c->n_cu ? pts / 16 : c->n_cu; }
+
+// partial gradient rows the path leaves in c->part for the assembled set (c->sd, c->chunk, c->n_rows and c->n_wg as
+// ensure_sets set them): what `part` is sized for and what the reduction sums
+static int path_rows(const pinn_ctx* c) {
+  if (t16_bwd_on(c)) return t16_wgs(c, c->chunk);              // one row per workgroup of a full chunk
+  switch (c->path) {
+    case KP_WIDE: return wide_wgs(c, c->chunk);
+    case KP_FUSED20M: case KP_FUSED20D: return c->n_wg;        // persistent workgroups
+    case KP_FUSED20: return fused20_rows(c->sd);
+    default: return c->n_rows;                                 // one row per 64 points of a chunk
+  }
 }
 
 template <typename T>
@@ -460,15 +526,13 @@ static int ensure_sets(pinn_ctx* c) {
   c->chunk = n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS;
   c->n_rows = c->chunk / 64;
   const size_t W = c->nd.width, H = c->nd.n_hidden;
+  c->n_wg = (n_pad / 64 < c->n_cu) ? n_pad / 64 : c->n_cu;   // persistent workgroups (KP_FUSED20M, KP_FUSED20D)
   // the fused kernel keeps the whole set's stash (one launch); the generic path works in chunks
-  const size_t stash_pts = c->path == 1 ? (size_t)n_pad : (size_t)c->chunk;
-  c->n_wg = (n_pad / 64 < c->n_cu) ? n_pad / 64 : c->n_cu;   // persistent workgroups (paths 2 and 7)
-  const int wide_wg = (c->chunk / 16 < c->n_cu) ? c->chunk / 16 : c->n_cu;     // persistent workgroups (path 3)
-  const size_t rows = t16_bwd_on(c) ? (size_t)t16_wgs(c, c->chunk) : c->path == 3 ? (size_t)wide_wg : (c->path == 2 || c->path == 7) ? (size_t)c->n_wg : c->path == 1 ? (size_t)n_pad / 64 : (size_t)c->n_rows;
-  const bool no_stash = c->path == 2 || c->path == 7 || c->path == 8;   // (path 8: 257 MB at cfg 4 that nothing would touch)
-  const size_t need_S = no_stash ? 16 : H * W * stash_pts * 4 * rs;
-  const size_t need_Z = no_stash ? 16 : W * (size_t)c->chunk * 4 * rs;
-  const size_t need_part = rows * c->R * rs;
+  const Stash stash = PATHS[c->path].stash;
+  const size_t stash_pts = stash == STASH_SET ? (size_t)n_pad : (size_t)c->chunk;
+  const size_t need_S = stash == STASH_NONE ? 16 : H * W * stash_pts * 4 * rs;
+  const size_t need_Z = stash == STASH_NONE ? 16 : W * (size_t)c->chunk * 4 * rs;
+  const size_t need_part = (size_t)path_rows(c) * c->R * rs;
   if (need_S > c->cap_S) { if (dev_alloc(&c->S, need_S)) return PINN_EHIP; c->cap_S = need_S; }
   if (need_Z > c->cap_Z) {
     if (dev_alloc(&c->ZA, need_Z)) return PINN_EHIP;
@@ -522,10 +586,10 @@ static int sa_prepare(pinn_ctx* c) {
   return 0;
 }
 
-// k_t16_fused (path 8) leaves the hidden-layer weight gradients in its tile-major scratch: the reductions read them there
+// k_t16_fused (KP_T16_FUSED) leaves the hidden-layer weight gradients in its tile-major scratch: the reductions read them there
 static TileScratch tile_scratch(const pinn_ctx* c) {
   TileScratch ts{};
-  if (c->path != 8 || c->dtype != PINN_F64 || !c->t16_gscr) return ts;
+  if (c->path != KP_T16_FUSED || c->dtype != PINN_F64 || !c->t16_gscr) return ts;
   const int W = c->nd.width, ntl = (W + 15) / 16;
   ts.gscr = c->t16_gscr;
   ts.n_tiles = ntl * ntl; ts.ntl = ntl; ts.W = W;
@@ -660,174 +724,206 @@ static int t16_fused_launch(pinn_ctx* c, const SetDesc& sd, int base, int pts, i
   return 0;
 }
 
+// the affine map of the inputs to [-1, 1] in the compute type
+template <typename real>
+struct InMap {
+  real lbx, lbt, sx, st;
+  explicit InMap(const pinn_ctx* c)
+      : lbx((real)c->lb[0]), lbt((real)c->lb[1]), sx((real)(2.0 / (c->ub[0] - c->lb[0]))), st((real)(2.0 / (c->ub[1] - c->lb[1]))) {}
+};
+
+// what every k_fused20d launch of context c takes (fused20d_api.h): the solo plan on c's set and weights.  An ensemble
+// overrides the weights, the rows, the member count and, with per-member sets, the points.
+static F20dLaunch fused20d_args(const pinn_ctx* c, hipEvent_t* ev4) {
+  const InMap<double> m(c);
+  return F20dLaunch{c->nd, c->sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
+                    (const double*)c->tgt, m.lbx, m.lbt, m.sx, m.st, (double*)c->part, c->R, c->n_wg, 1, c->row_index,
+                    c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr};
+}
+
+// KP_FUSED20D: the plain, the weighted (self-adaptive) or the adr evaluation, one launch
 template <typename real, int PDE>
-static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
-  constexpr int JT = sizeof(real) == 4 ? 20 : 10;
-  constexpr int KT = sizeof(real) == 4 ? 10 : 5;
-  const SetDesc sd = c->sd;
-  const real lbx = (real)c->lb[0], lbt = (real)c->lb[1];
-  const real sx = (real)(2.0 / (c->ub[0] - c->lb[0])), st = (real)(2.0 / (c->ub[1] - c->lb[1]));
-  if (ev4 && c->path != 2 && c->path != 1 && c->path != 7) HIPCHK(hipEventRecord(ev4[0], c->stream));
-  if (c->path == 7) {
-    int rc = hipErrorInvalidValue;
-    bool weighted = false;
-    if constexpr (sizeof(real) == 8 && PDE == 0) {
-      if (c->sa.on) {                               // the weighted variant; an Adam step moves the weights too
-        if (int e = sa_prepare(c)) return e;
-        const SaArgs sa{(double)c->nu, c->sa.buf, af ? af->alpha_sa : 0.0};
-        rc = fused20d_sa_launch_any(c->nd, sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
-                                    (const double*)c->tgt, (double)lbx, (double)lbt, (double)sx, (double)st, sa,
-                                    (double*)c->part, c->R, c->n_wg, c->row_index, c->stream, ev4 ? ev4[0] : nullptr,
-                                    ev4 ? ev4[1] : nullptr);
-        weighted = true;
+static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
+  int rc = hipErrorInvalidValue;
+  if constexpr (sizeof(real) == 8 && PDE != 2) {
+    const bool weighted = PDE == 0 && c->sa.on;     // an Adam step moves the weights too
+    if (weighted) { if (int e = sa_prepare(c)) return e; }
+    const F20dLaunch a = fused20d_args(c, ev4);
+    if constexpr (PDE == PDE_ADR) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR>(c));
+    else if (weighted) rc = fused20d_launch_any(a, SaArgs{(double)c->nu, c->sa.buf, af ? af->alpha_sa : 0.0});
+    else rc = fused20d_launch_any(PDE, a, (double)c->nu);
+  }
+  if (rc) return fail(PINN_EHIP, "fused20d launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// KP_FUSED20M: one launch; depth 8 is instantiated here, depths 4, 6 and 10 in fused20m_unit.hip
+template <typename real, int PDE>
+static int launch_fused20m(pinn_ctx* c, hipEvent_t* ev4) {
+  int rc = hipErrorInvalidValue;
+  if constexpr (sizeof(real) == 4 && PDE != 2 && PDE != PDE_ADR) {
+    const InMap<float> m(c);
+    hipEvent_t const e0 = ev4 ? ev4[0] : nullptr, e1 = ev4 ? ev4[1] : nullptr;
+    if (c->nd.n_hidden == 8)
+      rc = fused20m_launch<PDE, 8>(c->nd, c->sd, (const float*)c->theta_r, c->img, (const float*)c->xs,
+                                   (const float*)c->ts, (const float*)c->tgt, m.lbx, m.lbt, m.sx, m.st, (float)c->nu,
+                                   (float*)c->part, c->R, c->n_wg, c->stream, c->stamps, e0, e1);
+    else
+      rc = fused20m_launch_depth(PDE, c->nd, c->sd, (const float*)c->theta_r, c->img, (const float*)c->xs,
+                                 (const float*)c->ts, (const float*)c->tgt, m.lbx, m.lbt, m.sx, m.st, (float)c->nu,
+                                 (float*)c->part, c->R, c->n_wg, c->stream, c->stamps, e0, e1);
+  }
+  if (rc) return fail(PINN_EHIP, "fused20m launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// KP_FUSED20: one launch, the whole set's stash in HBM
+template <typename real, int PDE>
+static int launch_fused20(pinn_ctx* c, hipEvent_t* ev4) {
+  int rc = hipErrorInvalidValue;
+  if constexpr (PDE != PDE_ADR) {
+    const InMap<real> m(c);
+    rc = fused20_launch<real, PDE>(c->nd, c->sd, (const real*)c->theta_r, (const real*)c->xs, (const real*)c->ts,
+                                   (const real*)c->tgt, m.lbx, m.lbt, m.sx, m.st, (real)c->nu, (vec4<real>*)c->S,
+                                   (real*)c->part, c->R, c->stream, c->stamps, ev4 ? ev4[0] : nullptr,
+                                   ev4 ? ev4[1] : nullptr);
+  }
+  if (rc) return fail(PINN_EHIP, "fused20 launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// KP_T16_FUSED, chunk ci = points [base, base + pts): forward + reverse in one kernel.  ev1 (first chunk, timing on) is
+// recorded in front of the kernel, behind a pre-pass.
+template <typename real, int PDE>
+static int chunk_t16_fused(pinn_ctx* c, const InMap<real>& m, hipEvent_t ev1, int base, int pts, int ci) {
+  if constexpr (sizeof(real) == 8 && PDE != PDE_ADR) {
+    const SetDesc& sd = c->sd;
+    const int rows_cap = t16_wgs(c, c->chunk);
+    const int wgs = t16_wgs(c, pts) < rows_cap ? t16_wgs(c, pts) : rows_cap;
+    // periodic-boundary seeds read the outputs of a partner point another workgroup may own.  The boundary points
+    // fill the first groups of the set: when each of them is the first group of its workgroup the kernel hands
+    // the outputs over itself (kernels_tile16f.h); otherwise a forward sweep over those groups runs first
+    int n_bg = (PDE == 2 && base == 0 && sd.n_b > 0) ? (2 * sd.n_b + 15) / 16 : 0;
+    // the kernel's direct-store mode writes every entry of a fresh partial row exactly once, from the workgroup
+    // that owns the row: every launched workgroup must own a group, and chunk 0 must fill all rows_cap rows
+    REQUIRE(wgs >= 1 && wgs <= pts / 16 && (ci > 0 || wgs == rows_cap),
+            "k_t16_fused launch plan: %d workgroups for %d groups (rows %d, chunk %d)", wgs, pts / 16, rows_cap, ci);
+    if (n_bg > wgs || (n_bg > 0 && c->t16_prepass)) {
+      const size_t need_S = (size_t)c->nd.n_hidden * c->nd.width * (size_t)c->chunk * 4 * sizeof(double);   // (k_t16_fwd stashes)
+      if (need_S > c->cap_S) { if (dev_alloc(&c->S, need_S)) return PINN_EHIP; c->cap_S = need_S; }
+      if (int rc = t16_fwd<real>(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O, 0, 16 * n_bg < pts ? 16 * n_bg : pts, m.lbx, m.lbt, m.sx, m.st)) return rc;
+      n_bg = 0;
+    }
+    if (!c->t16_bsync) {
+      if (dev_alloc(&c->t16_bsync, 64)) return PINN_EHIP;
+      HIPCHK(hipMemsetAsync(c->t16_bsync, 0, 64, c->stream));
+      c->t16_bcount = 0;
+    }
+    c->t16_bcount += (unsigned int)n_bg;
+    {  // tile-major scratch of the hidden-layer weight gradients: one block per workgroup (kernels_tile16f.h)
+      const size_t ntl = ((size_t)c->nd.width + 15) / 16;
+      const size_t need = (size_t)rows_cap * (c->nd.n_hidden - 1) * ntl * ntl * 256 * sizeof(double);
+      if (need > c->t16_gscr_bytes) {
+        if (dev_alloc(&c->t16_gscr, need)) return PINN_EHIP;
+        c->t16_gscr_bytes = need;
       }
     }
-    (void)weighted;
-    if constexpr (sizeof(real) == 8 && PDE == PDE_ADR)
-      rc = fused20d_adr_launch_any(c->nd, sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
-                                   (const double*)c->tgt, (double)lbx, (double)lbt, (double)sx, (double)st,
-                                   pde_coef<double, PDE_ADR>(c), (double*)c->part, c->R, c->n_wg, c->row_index, c->stream,
-                                   ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr);
-    if constexpr (sizeof(real) == 8 && PDE != 2 && PDE != PDE_ADR)
-      if (!weighted) rc = fused20d_launch_any(PDE, c->nd, sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
-                               (const double*)c->tgt, (double)lbx, (double)lbt, (double)sx, (double)st,
-                               (double)c->nu, (double*)c->part, c->R, c->n_wg, c->row_index,
-                               c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr);
-    if (rc) return fail(PINN_EHIP, "fused20d launch failed: %s", hipGetErrorString((hipError_t)rc));
-  } else if (c->path == 2) {
-    int rc = hipErrorInvalidValue;
-    if constexpr (sizeof(real) == 4 && PDE != 2 && PDE != PDE_ADR) {
-      if (c->nd.n_hidden == 8)
-        rc = fused20m_launch<PDE, 8>(c->nd, sd, (const float*)c->theta_r, c->img, (const float*)c->xs,
-                                     (const float*)c->ts, (const float*)c->tgt, (float)lbx, (float)lbt,
-                                     (float)sx, (float)st, (float)c->nu, (float*)c->part, c->R, c->n_wg,
-                                     c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr);
-      else        // depths 4, 6, 10: fused20m_unit.hip
-        rc = fused20m_launch_depth(PDE, c->nd, sd, (const float*)c->theta_r, c->img, (const float*)c->xs,
-                                   (const float*)c->ts, (const float*)c->tgt, (float)lbx, (float)lbt,
-                                   (float)sx, (float)st, (float)c->nu, (float*)c->part, c->R, c->n_wg,
-                                   c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr);
-    }
-    if (rc) return fail(PINN_EHIP, "fused20m launch failed: %s", hipGetErrorString((hipError_t)rc));
-  } else if (c->path == 1) {
-    int rc = hipErrorInvalidValue;
-    if constexpr (PDE != PDE_ADR)
-      rc = fused20_launch<real, PDE>(c->nd, sd, (const real*)c->theta_r, (const real*)c->xs,
-                                     (const real*)c->ts, (const real*)c->tgt, lbx, lbt, sx,
-                                     st, (real)c->nu, (vec4<real>*)c->S, (real*)c->part, c->R,
-                                     c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr);
-    if (rc) return fail(PINN_EHIP, "fused20 launch failed: %s", hipGetErrorString((hipError_t)rc));
-  } else {
-    for (int base = 0, ci = 0; base < sd.n_pad; base += c->chunk, ++ci) {
-      const int pts = (sd.n_pad - base < c->chunk) ? sd.n_pad - base : c->chunk;
-      const dim3 grid(pts / 64), block(64);
-      bool fwd_done = false;
-      if constexpr (sizeof(real) == 8 && PDE != PDE_ADR) {
-        if (c->path == 8) {
-          const int rows_cap = t16_wgs(c, c->chunk);
-          const int wgs = t16_wgs(c, pts) < rows_cap ? t16_wgs(c, pts) : rows_cap;
-          // periodic-boundary seeds read the outputs of a partner point another workgroup may own.  The boundary points
-          // fill the first groups of the set: when each of them is the first group of its workgroup the kernel hands
-          // the outputs over itself (kernels_tile16f.h); otherwise a forward sweep over those groups runs first
-          int n_bg = (PDE == 2 && base == 0 && sd.n_b > 0) ? (2 * sd.n_b + 15) / 16 : 0;
-          // the kernel's direct-store mode writes every entry of a fresh partial row exactly once, from the workgroup
-          // that owns the row: every launched workgroup must own a group, and chunk 0 must fill all rows_cap rows
-          REQUIRE(wgs >= 1 && wgs <= pts / 16 && (ci > 0 || wgs == rows_cap),
-                  "k_t16_fused launch plan: %d workgroups for %d groups (rows %d, chunk %d)", wgs, pts / 16, rows_cap, ci);
-          if (n_bg > wgs || (n_bg > 0 && c->t16_prepass)) {
-            const size_t need_S = (size_t)c->nd.n_hidden * c->nd.width * (size_t)c->chunk * 4 * sizeof(double);   // (k_t16_fwd stashes)
-            if (need_S > c->cap_S) { if (dev_alloc(&c->S, need_S)) return PINN_EHIP; c->cap_S = need_S; }
-            if (int rc = t16_fwd<real>(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O, 0, 16 * n_bg < pts ? 16 * n_bg : pts, lbx, lbt, sx, st)) return rc;
-            n_bg = 0;
-          }
-          if (!c->t16_bsync) {
-            if (dev_alloc(&c->t16_bsync, 64)) return PINN_EHIP;
-            HIPCHK(hipMemsetAsync(c->t16_bsync, 0, 64, c->stream));
-            c->t16_bcount = 0;
-          }
-          c->t16_bcount += (unsigned int)n_bg;
-          {  // tile-major scratch of the hidden-layer weight gradients: one block per workgroup (kernels_tile16f.h)
-            const size_t ntl = ((size_t)c->nd.width + 15) / 16;
-            const size_t need = (size_t)rows_cap * (c->nd.n_hidden - 1) * ntl * ntl * 256 * sizeof(double);
-            if (need > c->t16_gscr_bytes) {
-              if (dev_alloc(&c->t16_gscr, need)) return PINN_EHIP;
-              c->t16_gscr_bytes = need;
-            }
-          }
-          if (ev4 && ci == 0) HIPCHK(hipEventRecord(ev4[1], c->stream));
-          int rc = PINN_EINVAL;
-          switch (c->nd.n_hidden) {            // the stash is a register array: the depth is a template parameter
-            case 2: rc = t16_fused_launch<PDE, 2>(c, sd, base, pts, ci, wgs, n_bg, lbx, lbt, sx, st); break;
-            case 3: rc = t16_fused_launch<PDE, 3>(c, sd, base, pts, ci, wgs, n_bg, lbx, lbt, sx, st); break;
-            case 4: rc = t16_fused_launch<PDE, 4>(c, sd, base, pts, ci, wgs, n_bg, lbx, lbt, sx, st); break;
-          }
-          if (rc) return rc;
-          continue;
-        }
-      }
-      if (t16_fwd_on(c)) {
-        if (int rc = t16_fwd<real>(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O, base, pts, lbx, lbt, sx, st)) return rc;
-        fwd_done = true;
-      }
-      if constexpr (sizeof(real) == 4) {
-        if (c->path == 3) {
-          static unsigned long long attr = 0;
-          if (first_call_on_device(attr))
-            HIPCHK(hipFuncSetAttribute((const void*)k_wide_fwd<100, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)wide_lds_bytes<100>()));
-          const int n_groups = pts / 16;
-          const int wg = n_groups < c->n_cu ? n_groups : c->n_cu;
-          hipLaunchKernelGGL((k_wide_fwd<100, 2>), dim3(wg), dim3(256), wide_lds_bytes<100>(), c->stream, c->nd,
-                             (const float*)c->theta_r, c->img, (const float*)c->xs, (const float*)c->ts, base,
-                             sd.n_pad, c->chunk, n_groups, (float)lbx, (float)lbt, (float)sx, (float)st,
-                             (vec4<float>*)c->S, (vec4<float>*)c->O);
-          fwd_done = true;
-        }
-      }
-      if (!fwd_done)
-      hipLaunchKernelGGL((k_forward<real, JT>), grid, block, 0, c->stream, c->nd,
-                         (const real*)c->theta_r, (const real*)c->xs, (const real*)c->ts, base,
-                         sd.n_pad, c->chunk, lbx, lbt, sx, st, (vec4<real>*)c->S,
-                         (vec4<real>*)c->O);
-      if (ev4 && ci == 0) HIPCHK(hipEventRecord(ev4[1], c->stream));
-      bool bwd_done = false;
-      if constexpr (PDE != PDE_ADR) {
-        if (t16_bwd_on(c)) {
-          if (int rc = t16_bwd<real, PDE>(c, base, pts, lbx, lbt, sx, st, ci > 0 ? 1 : 0)) return rc;
-          bwd_done = true;
-        }
-      }
-      if constexpr (sizeof(real) == 4 && PDE == 2) {
-        if (c->path == 3) {
-          static unsigned long long attr = 0;
-          if (first_call_on_device(attr))
-            HIPCHK(hipFuncSetAttribute((const void*)k_wide_bwd<100, 2, 2, 4>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_lds_bytes<100>()));
-          const int n_groups = pts / 16;
-          const int wg = n_groups < c->n_cu ? n_groups : c->n_cu;
-          hipLaunchKernelGGL((k_wide_bwd<100, 2, 2, 4>), dim3(wg), dim3(256), wide_lds_bytes<100>(), c->stream,
-                             c->nd, sd, (const float*)c->theta_r, c->img, (const float*)c->xs,
-                             (const float*)c->ts, (const float*)c->tgt, base, sd.n_pad, c->chunk, n_groups,
-                             (float)lbx, (float)lbt, (float)sx, (float)st, (float)c->nu,
-                             (const vec4<float>*)c->S, (const vec4<float>*)c->O, (float*)c->part, c->R,
-                             ci > 0 ? 1 : 0);
-          bwd_done = true;
-        }
-      }
-      if (!bwd_done)
-      hipLaunchKernelGGL((k_backward<real, PDE, KT>), grid, block, 0, c->stream, c->nd, sd,
-                         (const real*)c->theta_r, (const real*)c->xs, (const real*)c->ts,
-                         (const real*)c->tgt, base, sd.n_pad, c->chunk, lbx, lbt, sx, st,
-                         pde_coef<real, PDE>(c), (const vec4<real>*)c->S, (const vec4<real>*)c->O,
-                         (vec4<real>*)c->ZA, (vec4<real>*)c->ZB, (real*)c->part, c->R,
-                         ci > 0 ? 1 : 0);
+    if (ev1) HIPCHK(hipEventRecord(ev1, c->stream));
+    switch (c->nd.n_hidden) {            // the stash is a register array: the depth is a template parameter
+      case 2: return t16_fused_launch<PDE, 2>(c, sd, base, pts, ci, wgs, n_bg, m.lbx, m.lbt, m.sx, m.st);
+      case 3: return t16_fused_launch<PDE, 3>(c, sd, base, pts, ci, wgs, n_bg, m.lbx, m.lbt, m.sx, m.st);
+      case 4: return t16_fused_launch<PDE, 4>(c, sd, base, pts, ci, wgs, n_bg, m.lbx, m.lbt, m.sx, m.st);
     }
   }
+  return PINN_EINVAL;
+}
+
+// forward half of a chunk -> stash c->S, outputs c->O: the shape-generic MFMA sweep, the wide one or one lane per point
+template <typename real>
+static int chunk_fwd(pinn_ctx* c, const InMap<real>& m, int base, int pts) {
+  const int n_pad = c->sd.n_pad;
+  if (t16_fwd_on(c)) return t16_fwd<real>(c, c->xs, c->ts, n_pad, c->chunk, c->O, base, pts, m.lbx, m.lbt, m.sx, m.st);
+  if constexpr (sizeof(real) == 4) {
+    if (c->path == KP_WIDE) {
+      static unsigned long long attr = 0;
+      if (first_call_on_device(attr))
+        HIPCHK(hipFuncSetAttribute((const void*)k_wide_fwd<100, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)wide_lds_bytes<100>()));
+      hipLaunchKernelGGL((k_wide_fwd<100, 2>), dim3(wide_wgs(c, pts)), dim3(256), wide_lds_bytes<100>(), c->stream, c->nd,
+                         (const float*)c->theta_r, c->img, (const float*)c->xs, (const float*)c->ts, base, n_pad,
+                         c->chunk, pts / 16, m.lbx, m.lbt, m.sx, m.st, (vec4<float>*)c->S, (vec4<float>*)c->O);
+      return 0;
+    }
+  }
+  constexpr int JT = sizeof(real) == 4 ? 20 : 10;
+  hipLaunchKernelGGL((k_forward<real, JT>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, (const real*)c->theta_r,
+                     (const real*)c->xs, (const real*)c->ts, base, n_pad, c->chunk, m.lbx, m.lbt, m.sx, m.st,
+                     (vec4<real>*)c->S, (vec4<real>*)c->O);
+  return 0;
+}
+
+// reverse half of a chunk: its partial gradient rows written to (accumulate = 0) or added to c->part
+template <typename real, int PDE>
+static int chunk_bwd(pinn_ctx* c, const InMap<real>& m, int base, int pts, int accumulate) {
+  const SetDesc& sd = c->sd;
+  if constexpr (PDE != PDE_ADR) {
+    if (t16_bwd_on(c)) return t16_bwd<real, PDE>(c, base, pts, m.lbx, m.lbt, m.sx, m.st, accumulate);
+  }
+  if constexpr (sizeof(real) == 4 && PDE == 2) {
+    if (c->path == KP_WIDE) {
+      static unsigned long long attr = 0;
+      if (first_call_on_device(attr))
+        HIPCHK(hipFuncSetAttribute((const void*)k_wide_bwd<100, 2, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)wide_lds_bytes<100>()));
+      hipLaunchKernelGGL((k_wide_bwd<100, 2, 2, 4>), dim3(wide_wgs(c, pts)), dim3(256), wide_lds_bytes<100>(), c->stream,
+                         c->nd, sd, (const float*)c->theta_r, c->img, (const float*)c->xs, (const float*)c->ts,
+                         (const float*)c->tgt, base, sd.n_pad, c->chunk, pts / 16, m.lbx, m.lbt, m.sx, m.st, (float)c->nu,
+                         (const vec4<float>*)c->S, (const vec4<float>*)c->O, (float*)c->part, c->R, accumulate);
+      return 0;
+    }
+  }
+  constexpr int KT = sizeof(real) == 4 ? 10 : 5;
+  hipLaunchKernelGGL((k_backward<real, PDE, KT>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, sd,
+                     (const real*)c->theta_r, (const real*)c->xs, (const real*)c->ts, (const real*)c->tgt, base, sd.n_pad,
+                     c->chunk, m.lbx, m.lbt, m.sx, m.st, pde_coef<real, PDE>(c), (const vec4<real>*)c->S,
+                     (const vec4<real>*)c->O, (vec4<real>*)c->ZA, (vec4<real>*)c->ZB, (real*)c->part, c->R, accumulate);
+  return 0;
+}
+
+// the chunked paths: chunk after chunk on the stream, the first chunk's rows written, the later ones' added
+template <typename real, int PDE>
+static int launch_chunks(pinn_ctx* c, hipEvent_t* ev4) {
+  const InMap<real> m(c);
+  const int n_pad = c->sd.n_pad;
+  for (int base = 0, ci = 0; base < n_pad; base += c->chunk, ++ci) {
+    const int pts = (n_pad - base < c->chunk) ? n_pad - base : c->chunk;
+    hipEvent_t const ev1 = (ev4 && ci == 0) ? ev4[1] : nullptr;       // between the halves of the first chunk
+    if (c->path == KP_T16_FUSED) {
+      if (int rc = chunk_t16_fused<real, PDE>(c, m, ev1, base, pts, ci)) return rc;
+    } else {
+      if (int rc = chunk_fwd<real>(c, m, base, pts)) return rc;
+      if (ev1) HIPCHK(hipEventRecord(ev1, c->stream));
+      if (int rc = chunk_bwd<real, PDE>(c, m, base, pts, ci > 0 ? 1 : 0)) return rc;
+    }
+  }
+  return 0;
+}
+
+// events of a sampled evaluation: [0] start, [1] forward done, [2] sweeps done; the one-launch paths attach [0] and [1] to
+// their kernel (its own begin and end)
+template <typename real, int PDE>
+static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
+  if (ev4 && !PATHS[c->path].one_launch) HIPCHK(hipEventRecord(ev4[0], c->stream));
+  int rc;
+  switch (c->path) {
+    case KP_FUSED20D: rc = launch_fused20d<real, PDE>(c, ev4, af); break;
+    case KP_FUSED20M: rc = launch_fused20m<real, PDE>(c, ev4); break;
+    case KP_FUSED20: rc = launch_fused20<real, PDE>(c, ev4); break;
+    default: rc = launch_chunks<real, PDE>(c, ev4); break;
+  }
+  if (rc) return rc;
   if (ev4) HIPCHK(hipEventRecord(ev4[2], c->stream));
-  const int n_rows = t16_bwd_on(c) ? t16_wgs(c, c->chunk)
-                   : c->path == 3 ? ((c->chunk / 16 < c->n_cu) ? c->chunk / 16 : c->n_cu)
-                   : (c->path == 2 || c->path == 7) ? c->n_wg : c->path == 1 ? fused20_rows(sd) : c->n_rows;
-  return launch_reduce<real>(c, n_rows, af);
+  return launch_reduce<real>(c, path_rows(c), af);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1428,10 +1524,8 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
     HIPCHK(hipStreamSynchronize(c->stream));
     nd.img_kind = 2;
   }
-  // default kernel family: 2 width-20 f32 (MFMA GEMVs, register stash), 7 its float64 counterpart (4x4x4 MFMA GEMVs,
-  // no exchange), 1 width-20 HBM-stash, 3 wide MFMA sweeps (width 100, 2 outputs), 4 shape-generic MFMA sweeps, 0 generic
-  c->path = fused_regs_ok(c) ? 2 : fused_f64_ok(c) ? 7 : fused_ok(c) ? 1 : wide_ok(c) ? 3 : t16_fused_ok(c) ? 8 : tile16_ok(c) ? 4 : 0;
-  if (is_adr(c)) c->path = fused_f64_ok(c) ? 7 : 0;   // the kind's two implementations (pinn_set_kernel_path refuses the others)
+  for (KernelPath p : PATH_PREFERENCE)      // (KP_GENERIC, the last, takes every net)
+    if (path_ok(c, p)) { c->path = p; break; }
   *out = c;
   return 0;
 }
@@ -2397,7 +2491,7 @@ int pinn_timing_read(pinn_ctx* c, double* avg_ms, int* n) {
   *n = c->ev_used;
   const double k = c->ev_used ? 1.0 / c->ev_used : 0.0;
   avg_ms[0] = a * k; avg_ms[1] = b * k; avg_ms[2] = t * k; avg_ms[3] = c->ev_overhead_ms;
-  avg_ms[4] = (c->path == 2 || c->path == 1 || c->path == 7) ? 1.0 : 0.0;
+  avg_ms[4] = PATHS[c->path].one_launch ? 1.0 : 0.0;
   c->ev_used = 0;
   return 0;
 }
@@ -2410,25 +2504,17 @@ int pinn_sync(pinn_ctx* c) {
 }
 
 int pinn_set_kernel_path(pinn_ctx* c, int path) {
-  REQUIRE(c && path >= 0 && path <= 8, "path must be 0 (generic), 1 (fused width-20), 2 (fused width-20, register stash), "
+  REQUIRE(c && (unsigned)path < (unsigned)KP_COUNT, "path must be 0 (generic), 1 (fused width-20), 2 (fused width-20, register stash), "
           "3 (wide MFMA sweeps), 4 (shape-generic MFMA sweeps), 5 / 6 (4's forward / reverse half with the generic other half), "
           "7 (fused width-20 float64, register stash), 8 (fused float64 MFMA sweep, widths 65..128, 2-4 hidden layers)");
-  if (c->sa.on && path != 7)
+  const KernelPath p = (KernelPath)path;
+  if (c->sa.on && p != KP_FUSED20D)
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: self-adaptive weights run on kernel path 7 only (pinn_sa_disable first)");
-  if (is_adr(c) && path != 0 && path != 7)
+  if (is_adr(c) && !adr_has_path(p))
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: the adr kind (pde 5) runs on kernel paths 0 and 7 only; path %d "
-                "(%s) has no variant for it", path, path == 1 ? "fused width-20" : path == 2 ? "float32 register stash" :
-                path == 3 ? "wide MFMA sweeps" : path == 8 ? "fused float64 MFMA sweep" : "shape-generic MFMA sweeps");
-  if (path == 8) REQUIRE(t16_fused_ok(c), "the fused float64 sweep needs float64, hidden width 65..128 and 2, 3 or 4 hidden layers");
-  if (path >= 4 && path <= 6) REQUIRE(tile16_ok(c), "the shape-generic MFMA sweeps need hidden width <= 128");
-  if (path == 7)
-    REQUIRE(fused_f64_ok(c), "the float64 register-stash path needs float64, hidden width 20, 4, 6 or 8 hidden layers and a Burgers problem");
-  if (path == 3) REQUIRE(wide_ok(c), "the wide path needs float32, hidden width 100 and two outputs");
-  if (path == 1)
-    REQUIRE(fused_ok(c), "the fused path needs hidden width 20, a Burgers problem and weights that fit LDS");
-  if (path == 2)
-    REQUIRE(fused_regs_ok(c), "the register-stash path needs float32, hidden width 20, 4, 6, 8 or 10 hidden layers and a Burgers problem");
-  c->path = path;
+                "(%s) has no variant for it", path, PATHS[p].name);
+  REQUIRE(PATHS[p].ok(c), "%s", PATHS[p].needs);
+  c->path = p;
   c->sets_dirty = true;
   return 0;
 }
@@ -2436,11 +2522,11 @@ int pinn_set_kernel_path(pinn_ctx* c, int path) {
 int pinn_debug_stamps(pinn_ctx* c, long long* out, int64_t cap, int64_t* n_waves) {
 #ifdef PINN_STAMPS
   REQUIRE(c && out && n_waves, "null");
-  REQUIRE(c->path >= 1, "stamps exist for the fused kernels only");
+  REQUIRE(c->path != KP_GENERIC, "stamps exist for the fused kernels only");
   HIPCHK(hipSetDevice(c->device));
   int rc = ensure_sets(c);
   if (rc) return rc;
-  const size_t n = (size_t)((c->path == 2 || c->path == 7) ? c->n_wg : c->sd.n_pad / 64) * 4 * 32;
+  const size_t n = (size_t)path_rows(c) * 4 * 32;
   REQUIRE((size_t)cap >= n, "stamp buffer too small: need %zu", n);
   if (dev_alloc(&c->stamps, n * 8)) return PINN_EHIP;
   HIPCHK(hipMemsetAsync(c->stamps, 0, n * 8, c->stream));
@@ -2507,8 +2593,8 @@ static int sa_supported(const pinn_ctx* c, const char* who) {
   if (c->pde != PINN_PDE_BURGERS)
     return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights are for Burgers inference (pde 0) only", who);
   if (c->dtype != PINN_F64) return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights need float64", who);
-  if (c->path != 7)
-    return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights need kernel path 7 (this context runs path %d)", who, c->path);
+  if (c->path != KP_FUSED20D)
+    return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights need kernel path 7 (this context runs path %d)", who, (int)c->path);
   if (c->comm || c->xg.box)
     return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights are single-device; this context has a communicator", who);
   return 0;
@@ -2708,16 +2794,13 @@ static int ens_ensure_sets(pinn_ens* e) {
 static int ens_eval(pinn_ens* e, const bool* active, const double* alpha, double* loss3) {
   pinn_ctx* b = e->base;
   if (int rc = ens_ensure_sets(e)) return rc;
-  const size_t need = (size_t)e->K * b->n_wg * b->R;
+  const int n_rows = path_rows(b);
+  const size_t need = (size_t)e->K * n_rows * b->R;
   if (need > e->cap_part) { if (dev_alloc(&e->part, need * 8)) return PINN_EHIP; e->cap_part = need; }
-  const double sx = 2.0 / (b->ub[0] - b->lb[0]), st = 2.0 / (b->ub[1] - b->lb[1]);
-  const int rc =
-      e->k_mode ? fused20d_ens_sets_launch_any(b->pde, b->nd, b->sd, e->theta_r, e->k_xs, e->k_ts, e->k_tgt, b->lb[0],
-                                               b->lb[1], sx, st, e->k_nud, e->part, b->R, b->n_wg, e->K, b->row_index,
-                                               b->stream)
-                : fused20d_ens_launch_any(b->pde, b->nd, b->sd, e->theta_r, (const double*)b->xs, (const double*)b->ts,
-                                          (const double*)b->tgt, b->lb[0], b->lb[1], sx, st, b->nu, e->part, b->R,
-                                          b->n_wg, e->K, b->row_index, b->stream);
+  F20dLaunch a = fused20d_args(b, nullptr);
+  a.th = e->theta_r; a.part = e->part; a.n_members = e->K;
+  if (e->k_mode) { a.xs = e->k_xs; a.ts = e->k_ts; a.tgt = e->k_tgt; }
+  const int rc = e->k_mode ? fused20d_ens_launch_any(b->pde, a, (const double*)e->k_nud) : fused20d_ens_launch_any(b->pde, a, b->nu);
   if (rc) return fail(PINN_EHIP, "ensemble fused20d launch failed: %s", hipGetErrorString((hipError_t)rc));
   EnsStep es{};
   for (int k = 0; k < e->K; ++k) {
@@ -2730,11 +2813,11 @@ static int ens_eval(pinn_ens* e, const bool* active, const double* alpha, double
   const dim3 grid((b->R + RED_COLS - 1) / RED_COLS, e->K);
   pinn_ctx* c0 = e->mem[0];
   if (alpha)
-    hipLaunchKernelGGL(k_reduce_adam_ens, grid, dim3(RED_THREADS), 0, b->stream, (const double*)e->part, b->n_wg, b->R,
+    hipLaunchKernelGGL(k_reduce_adam_ens, grid, dim3(RED_THREADS), 0, b->stream, (const double*)e->part, n_rows, b->R,
                        e->gl, e->P, e->sw, e->theta, e->theta_r, e->m, e->v, c0->b1, c0->b2, c0->eps, loss3, e->nonfinite,
                        es);
   else
-    hipLaunchKernelGGL(k_reduce_rows_ens, grid, dim3(RED_THREADS), 0, b->stream, (const double*)e->part, b->n_wg, b->R,
+    hipLaunchKernelGGL(k_reduce_rows_ens, grid, dim3(RED_THREADS), 0, b->stream, (const double*)e->part, n_rows, b->R,
                        e->gl, e->P, e->nonfinite, es);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2760,7 +2843,7 @@ int pinn_ens_create(pinn_ens** out, const int* layers, int n_layers, const doubl
   e->K = n_members;
   if (int rc = pinn_create(&e->base, layers, n_layers, lb, ub, pde_kind, dtype, device)) { delete e; return rc; }
   pinn_ctx* b = e->base;
-  if (b->path != 7) { ens_free(e); return fail(PINN_EUNSUPPORTED, "ensembles need kernel path 7 (got %d)", b->path); }
+  if (b->path != KP_FUSED20D) { ens_free(e); return fail(PINN_EUNSUPPORTED, "ensembles need kernel path 7 (got %d)", (int)b->path); }
   e->P = b->nd.n_theta;
   e->sw = (int)fused20d_weight_doubles(e->P);
   const size_t K = e->K, P = e->P;

@@ -28,17 +28,33 @@ void fused20d_row_index(const NetDesc& nd, int H, int* out);
 
 inline bool fused20d_depth_ok(int n_hidden) { return n_hidden == 4 || n_hidden == 6 || n_hidden == 8; }
 // Launch plan of path 7: 64-point tiles, persistent over n_wg = min(tiles, CUs) workgroups = partial gradient rows.
-// one loss+gradient evaluation (pde 0: Burgers inference, 1: identification; 4, 6 or 8 hidden layers); returns a hipError_t
-int fused20d_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
-                        const double* ts, const double* tgt, double lbx, double lbt, double sx, double st, double nu,
-                        double* part, int R, int n_wg, const int* row_index, hipStream_t stream,
-                        long long* stamps, hipEvent_t ev_start, hipEvent_t ev_stop);
 
-// the same for n_members weight vectors fused20d_weight_doubles(n_theta) apart (an ensemble sharing the point set): member
-// m's n_wg gradient rows at part + m * n_wg * R, each bit-identical to a solo launch's
-int fused20d_ens_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
-                            const double* ts, const double* tgt, double lbx, double lbt, double sx, double st, double nu,
-                            double* part, int R, int n_wg, int n_members, const int* row_index, hipStream_t stream);
+// what every launch of k_fused20d takes besides its coefficient argument
+struct F20dLaunch {
+  const NetDesc& nd;
+  const SetDesc& sd;
+  const double* th;              // n_members weight vectors, fused20d_weight_doubles(n_theta) apart
+  const double *xs, *ts, *tgt;   // the point set ([n_members][sd.n_pad] where every member has its own)
+  double lbx, lbt, sx, st;       // the affine map of the inputs to [-1, 1]
+  double* part;                  // member m's n_wg gradient rows of R doubles at part + m * n_wg * R
+  int R, n_wg, n_members;        // n_members: 1 = solo
+  const int* row_index;          // fused20d_row_index
+  hipStream_t stream;
+  long long* stamps;             // -DPINN_STAMPS builds: the waves' clock stamps (nullptr: none)
+  hipEvent_t ev_start, ev_stop;  // both set: attached to the launch itself
+};
+
+// one loss+gradient evaluation, 4, 6 or 8 hidden layers; every entry point returns a hipError_t
+// pde 0: Burgers inference, 1: identification
+int fused20d_launch_any(int pde, const F20dLaunch& a, double nu);
+
+// the same for n_members weight vectors (an ensemble sharing the point set): each member's rows bit-identical to a solo
+// launch's
+int fused20d_ens_launch_any(int pde, const F20dLaunch& a, double nu);
+
+// the same with a point set per member, all of one SetDesc, and nu_k [n_members] in device memory: member m's rows
+// bit-identical to a solo launch on member m's set with viscosity nu_k[m]
+int fused20d_ens_launch_any(int pde, const F20dLaunch& a, const double* nu_k);
 
 // Self-adaptive point weights (k_fused20d<0, H, ., false, false, true>).  lam holds SA_CONST doubles (beta1, beta2, eps of
 // the ascent), then (lambda, m, v) of every point of the assembled set, [n_all][3]: the data points, then the collocation
@@ -54,24 +70,11 @@ struct SaArgs {
   double alpha;
 };
 
-// one weighted loss+gradient evaluation of pde 0 (4, 6 or 8 hidden layers); returns a hipError_t
-int fused20d_sa_launch_any(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
-                           const double* tgt, double lbx, double lbt, double sx, double st, const SaArgs& sa,
-                           double* part, int R, int n_wg, const int* row_index, hipStream_t stream, hipEvent_t ev_start,
-                           hipEvent_t ev_stop);
+// one weighted evaluation of pde 0
+int fused20d_launch_any(const F20dLaunch& a, const SaArgs& sa);
 
-// one evaluation of the advection-diffusion-reaction kind (k_fused20d<PDE_ADR, H, .>; 4, 6 or 8 hidden layers): six
-// run-time coefficients, boundary block pair-interleaved; returns a hipError_t
-int fused20d_adr_launch_any(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
-                            const double* tgt, double lbx, double lbt, double sx, double st, const AdrCoef<double>& k,
-                            double* part, int R, int n_wg, const int* row_index, hipStream_t stream, hipEvent_t ev_start,
-                            hipEvent_t ev_stop);
-
-// the same with a point set per member -- xs, ts, tgt [n_members][sd.n_pad], all of one SetDesc -- and nu_k [n_members]
-// in device memory: member m's rows bit-identical to a solo launch on member m's set with viscosity nu_k[m]
-int fused20d_ens_sets_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
-                                 const double* ts, const double* tgt, double lbx, double lbt, double sx, double st,
-                                 const double* nu_k, double* part, int R, int n_wg, int n_members, const int* row_index,
-                                 hipStream_t stream);
+// one evaluation of the advection-diffusion-reaction kind (k_fused20d<PDE_ADR, H, .>): six run-time coefficients, boundary
+// block pair-interleaved
+int fused20d_launch_any(const F20dLaunch& a, const AdrCoef<double>& k);
 
 }  // namespace pinn

@@ -25,73 +25,27 @@ void fused20d_row_index(const NetDesc& nd, int H, int* out) {
   }
 }
 
-int fused20d_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
-                        const double* ts, const double* tgt, double lbx, double lbt, double sx, double st, double nu,
-                        double* part, int R, int n_wg, const int* row_index, hipStream_t stream,
-                        long long* stamps, hipEvent_t ev_start, hipEvent_t ev_stop) {
-#define ARGS nd, sd, th, xs, ts, tgt, lbx, lbt, sx, st, nu, part, R, n_wg, row_index, stream, stamps, ev_start, ev_stop
-  switch (nd.n_hidden) {     // the AGPR stash holds (H - 2) x 40 registers: depths up to 8 fit the 256 of a wave
-    case 4: return pde == 1 ? fused20d_launch<1, 4>(ARGS) : fused20d_launch<0, 4>(ARGS);
-    case 6: return pde == 1 ? fused20d_launch<1, 6>(ARGS) : fused20d_launch<0, 6>(ARGS);
-    case 8: return pde == 1 ? fused20d_launch<1, 8>(ARGS) : fused20d_launch<0, 8>(ARGS);
+// variant (ENS, SETS, SAW, ADR) at the depth of the net: PDE_ADR, pde 0 (the weighted loss) or pde 0 / 1
+template <int H, bool ENS, bool SETS, bool SAW, bool ADR>
+static int launch_h(int pde, const F20dLaunch& a, const f20d_nu_t<SETS, SAW, ADR>& nu) {
+  if constexpr (ADR) return fused20d_launch<PDE_ADR, H, ENS, SETS, SAW>(a, nu);
+  else if constexpr (SAW) return fused20d_launch<0, H, ENS, SETS, SAW>(a, nu);
+  else return pde == 1 ? fused20d_launch<1, H, ENS, SETS, SAW>(a, nu) : fused20d_launch<0, H, ENS, SETS, SAW>(a, nu);
+}
+template <bool ENS, bool SETS, bool SAW, bool ADR>
+static int launch_depth(int pde, const F20dLaunch& a, const f20d_nu_t<SETS, SAW, ADR>& nu) {
+  switch (a.nd.n_hidden) {     // the AGPR stash holds (H - 2) x 40 registers: depths up to 8 fit the 256 of a wave
+    case 4: return launch_h<4, ENS, SETS, SAW, ADR>(pde, a, nu);
+    case 6: return launch_h<6, ENS, SETS, SAW, ADR>(pde, a, nu);
+    case 8: return launch_h<8, ENS, SETS, SAW, ADR>(pde, a, nu);
     default: return (int)hipErrorInvalidValue;
   }
-#undef ARGS
 }
 
-int fused20d_sa_launch_any(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
-                           const double* tgt, double lbx, double lbt, double sx, double st, const SaArgs& sa,
-                           double* part, int R, int n_wg, const int* row_index, hipStream_t stream, hipEvent_t ev_start,
-                           hipEvent_t ev_stop) {
-#define ARGS nd, sd, th, xs, ts, tgt, lbx, lbt, sx, st, sa, part, R, n_wg, row_index, stream, ev_start, ev_stop
-  switch (nd.n_hidden) {
-    case 4: return fused20d_sa_launch<4>(ARGS);
-    case 6: return fused20d_sa_launch<6>(ARGS);
-    case 8: return fused20d_sa_launch<8>(ARGS);
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef ARGS
-}
-
-int fused20d_adr_launch_any(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
-                            const double* tgt, double lbx, double lbt, double sx, double st, const AdrCoef<double>& k,
-                            double* part, int R, int n_wg, const int* row_index, hipStream_t stream, hipEvent_t ev_start,
-                            hipEvent_t ev_stop) {
-#define ARGS nd, sd, th, xs, ts, tgt, lbx, lbt, sx, st, k, part, R, n_wg, row_index, stream, ev_start, ev_stop
-  switch (nd.n_hidden) {
-    case 4: return fused20d_adr_launch<4>(ARGS);
-    case 6: return fused20d_adr_launch<6>(ARGS);
-    case 8: return fused20d_adr_launch<8>(ARGS);
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef ARGS
-}
-
-int fused20d_ens_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
-                            const double* ts, const double* tgt, double lbx, double lbt, double sx, double st, double nu,
-                            double* part, int R, int n_wg, int n_members, const int* row_index, hipStream_t stream) {
-#define ARGS nd, sd, th, xs, ts, tgt, lbx, lbt, sx, st, nu, part, R, n_wg, n_members, row_index, stream
-  switch (nd.n_hidden) {
-    case 4: return pde == 1 ? fused20d_ens_launch<1, 4>(ARGS) : fused20d_ens_launch<0, 4>(ARGS);
-    case 6: return pde == 1 ? fused20d_ens_launch<1, 6>(ARGS) : fused20d_ens_launch<0, 6>(ARGS);
-    case 8: return pde == 1 ? fused20d_ens_launch<1, 8>(ARGS) : fused20d_ens_launch<0, 8>(ARGS);
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef ARGS
-}
-
-int fused20d_ens_sets_launch_any(int pde, const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs,
-                                 const double* ts, const double* tgt, double lbx, double lbt, double sx, double st,
-                                 const double* nu_k, double* part, int R, int n_wg, int n_members, const int* row_index,
-                                 hipStream_t stream) {
-#define ARGS nd, sd, th, xs, ts, tgt, lbx, lbt, sx, st, nu_k, part, R, n_wg, n_members, row_index, stream
-  switch (nd.n_hidden) {
-    case 4: return pde == 1 ? fused20d_ens_launch<1, 4, true>(ARGS) : fused20d_ens_launch<0, 4, true>(ARGS);
-    case 6: return pde == 1 ? fused20d_ens_launch<1, 6, true>(ARGS) : fused20d_ens_launch<0, 6, true>(ARGS);
-    case 8: return pde == 1 ? fused20d_ens_launch<1, 8, true>(ARGS) : fused20d_ens_launch<0, 8, true>(ARGS);
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef ARGS
-}
+int fused20d_launch_any(int pde, const F20dLaunch& a, double nu) { return launch_depth<false, false, false, false>(pde, a, nu); }
+int fused20d_ens_launch_any(int pde, const F20dLaunch& a, double nu) { return launch_depth<true, false, false, false>(pde, a, nu); }
+int fused20d_ens_launch_any(int pde, const F20dLaunch& a, const double* nu_k) { return launch_depth<true, true, false, false>(pde, a, nu_k); }
+int fused20d_launch_any(const F20dLaunch& a, const SaArgs& sa) { return launch_depth<false, false, true, false>(0, a, sa); }
+int fused20d_launch_any(const F20dLaunch& a, const AdrCoef<double>& k) { return launch_depth<false, false, false, true>(0, a, k); }
 
 }  // namespace pinn

@@ -887,112 +887,32 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
   STAMP(2 * H + 2);
 }
 
-// returns a hipError_t (0 = ok)
-template <int PDE, int H>
-inline int fused20d_launch(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
-                           const double* tgt, double lbx, double lbt, double sx, double st, double nu, double* part,
-                           int R, int n_wg, const int* row_index, hipStream_t stream, long long* stamps = nullptr,
-                           hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
-  if (!w20_layout_ok(nd, H, PDE == 1)) return (int)hipErrorInvalidValue;
-  const size_t lds = fused20d_lds_bytes(H, nd.n_theta);
+// One loss+gradient evaluation by k_fused20d<PDE, H, ., ENS, SETS, SAW> (F20dLaunch, fused20d_api.h; nu: the variant's
+// coefficient argument).  Every member runs the solo launch plan: the one-tile instantiation when each tile has a workgroup
+// of its own, the tile loop otherwise, on a grid of (n_wg, n_members).  With both events given they take the kernel's own
+// begin / end timestamps.  Returns a hipError_t (0 = ok).
+template <int PDE, int H, bool ENS, bool SETS, bool SAW>
+inline int fused20d_launch(const F20dLaunch& a, const f20d_nu_t<SETS, SAW, PDE == PDE_ADR>& nu) {
+  if (!w20_layout_ok(a.nd, H, PDE == 1) || (!ENS && a.n_members != 1)) return (int)hipErrorInvalidValue;
+  const size_t lds = fused20d_lds_bytes(H, a.nd.n_theta);
   static unsigned long long attr_set = 0;
   if (first_call_on_device(attr_set)) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  const int n_tiles = sd.n_pad / 64;
-  auto* const kern = n_wg >= n_tiles ? k_fused20d<PDE, H, true> : k_fused20d<PDE, H, false>;
-  if (ev_start && ev_stop)
-    hipExtLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, ev_start, ev_stop, 0, th, xs, ts, tgt, part,
-                          row_index, R, n_tiles, lbx, lbt, sx, st, nu, sd, stamps, w20_desc(H, PDE == 1));
-  else
-    hipLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles, lbx,
-                       lbt, sx, st, nu, sd, stamps, w20_desc(H, PDE == 1));
-  return (int)hipGetLastError();
-}
-
-// the weighted evaluation of pde 0 (self-adaptive weights, SaArgs): the solo launch plan; returns a hipError_t
-template <int H>
-inline int fused20d_sa_launch(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
-                              const double* tgt, double lbx, double lbt, double sx, double st, const SaArgs& sa,
-                              double* part, int R, int n_wg, const int* row_index, hipStream_t stream,
-                              hipEvent_t ev_start, hipEvent_t ev_stop) {
-  if (!w20_layout_ok(nd, H, false)) return (int)hipErrorInvalidValue;
-  const size_t lds = fused20d_lds_bytes(H, nd.n_theta);
-  static unsigned long long attr_set = 0;
-  if (first_call_on_device(attr_set)) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<0, H, false, false, false, true>,
+    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, false, ENS, SETS, SAW>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)k_fused20d<0, H, true, false, false, true>,
+      e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, true, ENS, SETS, SAW>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
-  const int n_tiles = sd.n_pad / 64;
-  auto* const kern = n_wg >= n_tiles ? k_fused20d<0, H, true, false, false, true> : k_fused20d<0, H, false, false, false, true>;
-  if (ev_start && ev_stop)
-    hipExtLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, ev_start, ev_stop, 0, th, xs, ts, tgt, part,
-                          row_index, R, n_tiles, lbx, lbt, sx, st, sa, sd, (long long*)nullptr, w20_desc(H, false));
+  const int n_tiles = a.sd.n_pad / 64;
+  auto* const kern = a.n_wg >= n_tiles ? k_fused20d<PDE, H, true, ENS, SETS, SAW> : k_fused20d<PDE, H, false, ENS, SETS, SAW>;
+  const dim3 grid(a.n_wg, a.n_members);
+  if (a.ev_start && a.ev_stop)
+    hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, a.stream, a.ev_start, a.ev_stop, 0, a.th, a.xs, a.ts, a.tgt, a.part,
+                          a.row_index, a.R, n_tiles, a.lbx, a.lbt, a.sx, a.st, nu, a.sd, a.stamps, w20_desc(H, PDE == 1));
   else
-    hipLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles, lbx,
-                       lbt, sx, st, sa, sd, (long long*)nullptr, w20_desc(H, false));
-  return (int)hipGetLastError();
-}
-
-// one evaluation of the advection-diffusion-reaction kind (coefficients k, pair-interleaved boundary block): the solo
-// launch plan; returns a hipError_t
-template <int H>
-inline int fused20d_adr_launch(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
-                               const double* tgt, double lbx, double lbt, double sx, double st, const AdrCoef<double>& k,
-                               double* part, int R, int n_wg, const int* row_index, hipStream_t stream,
-                               hipEvent_t ev_start, hipEvent_t ev_stop) {
-  if (!w20_layout_ok(nd, H, false)) return (int)hipErrorInvalidValue;
-  const size_t lds = fused20d_lds_bytes(H, nd.n_theta);
-  static unsigned long long attr_set = 0;
-  if (first_call_on_device(attr_set)) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<PDE_ADR, H, false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)k_fused20d<PDE_ADR, H, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  const int n_tiles = sd.n_pad / 64;
-  auto* const kern = n_wg >= n_tiles ? k_fused20d<PDE_ADR, H, true> : k_fused20d<PDE_ADR, H, false>;
-  if (ev_start && ev_stop)
-    hipExtLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, ev_start, ev_stop, 0, th, xs, ts, tgt, part,
-                          row_index, R, n_tiles, lbx, lbt, sx, st, k, sd, (long long*)nullptr, w20_desc(H, false));
-  else
-    hipLaunchKernelGGL(kern, dim3(n_wg), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles, lbx,
-                       lbt, sx, st, k, sd, (long long*)nullptr, w20_desc(H, false));
-  return (int)hipGetLastError();
-}
-
-// one evaluation of n_members weight vectors on the shared point set (SETS: on [n_members][sd.n_pad] point sets, with
-// nu [n_members] on the device): the solo launch plan (n_wg, one-tile or tile loop) per member, grid (n_wg, n_members);
-// returns a hipError_t
-template <int PDE, int H, bool SETS = false>
-inline int fused20d_ens_launch(const NetDesc& nd, const SetDesc& sd, const double* th, const double* xs, const double* ts,
-                               const double* tgt, double lbx, double lbt, double sx, double st, f20d_nu_t<SETS> nu,
-                               double* part, int R, int n_wg, int n_members, const int* row_index, hipStream_t stream) {
-  if (!w20_layout_ok(nd, H, PDE == 1)) return (int)hipErrorInvalidValue;
-  const size_t lds = fused20d_lds_bytes(H, nd.n_theta);
-  static unsigned long long attr_set = 0;
-  if (first_call_on_device(attr_set)) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, false, true, SETS>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)k_fused20d<PDE, H, true, true, SETS>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  const int n_tiles = sd.n_pad / 64;
-  auto* const kern = n_wg >= n_tiles ? k_fused20d<PDE, H, true, true, SETS> : k_fused20d<PDE, H, false, true, SETS>;
-  hipLaunchKernelGGL(kern, dim3(n_wg, n_members), dim3(256), lds, stream, th, xs, ts, tgt, part, row_index, R, n_tiles,
-                     lbx, lbt, sx, st, nu, sd, (long long*)nullptr, w20_desc(H, PDE == 1));
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, a.stream, a.th, a.xs, a.ts, a.tgt, a.part, a.row_index, a.R, n_tiles,
+                       a.lbx, a.lbt, a.sx, a.st, nu, a.sd, a.stamps, w20_desc(H, PDE == 1));
   return (int)hipGetLastError();
 }
 

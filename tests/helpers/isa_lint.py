@@ -14,7 +14,9 @@ The sources keep clear of both by construction (`agd_put_after`'s dependency ope
 lint checks the RESULT: it extracts every gfx950 code object from the library's .hip_fatbin section, disassembles it with
 llvm-objdump and walks each kernel's control-flow graph forward from every matrix instruction / m0 write, counting wait
 states the way the recogniser does (one per instruction issued in between, N+1 for `s_nop N`).  A violation names kernel,
-offset and the two instructions.  `python tests/helpers/isa_lint.py [lib]` prints the report."""
+offset and the two instructions.  `python tests/helpers/isa_lint.py [lib]` prints the report;
+`python tests/helpers/isa_lint.py --listing <lib>` prints one line per kernel (instruction digest and register / LDS /
+scratch use, `kernel_listing`), for comparing the device code of two builds."""
 import os
 import re
 import struct
@@ -22,6 +24,7 @@ import subprocess
 import tempfile
 
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 OBJCOPY = "objcopy"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
@@ -200,8 +203,55 @@ def lint_library(lib):
     return n, seen, bad
 
 
+_META = (".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size")
+
+
+def kernel_resources(obj_bytes):
+    """{kernel: (VGPRs, AGPRs, SGPRs, LDS bytes, scratch bytes)} from the code object's AMDGPU metadata note"""
+    with tempfile.NamedTemporaryFile(suffix=".o") as fh:
+        fh.write(obj_bytes)
+        fh.flush()
+        text = subprocess.run([READELF, "--notes", fh.name], check=True, capture_output=True, text=True).stdout
+    out, cur = {}, None
+    for line in text.splitlines():                    # amdhsa.kernels: entries open with "  - ", their keys sit at four spaces
+        m = re.match(r"^  ([- ]) (\.\w+):\s*(.*?)\s*$", line)
+        if not m:
+            continue
+        if m.group(1) == "-":
+            cur = {}
+        if cur is not None:
+            cur[m.group(2)] = m.group(3)
+            if all(k in cur for k in _META + (".name",)):
+                out[cur[".name"]] = tuple(int(cur[k]) for k in _META)
+    return out
+
+
+def kernel_listing(lib):
+    """One line per kernel of `lib`: code-object index, mangled name, instruction count, sha256 (first 16 hex digits) over
+    (offset - kernel start, mnemonic, operands) of every instruction, and the resource metadata.  Two builds whose
+    listings are equal run the same device code with the same launch resources."""
+    import hashlib
+    lines = []
+    for index, blob in code_objects(lib):
+        res = kernel_resources(blob)
+        for name, body in sorted(disassemble(blob).items()):
+            if not body:
+                continue
+            h = hashlib.sha256()
+            for off, mn, ops, _ in body:
+                h.update(("%x %s %s\n" % (off - body[0][0], mn, ops)).encode())
+            r = res.get(name)
+            lines.append("%d %s insns=%d sha=%s %s" % (
+                index, name, len(body), h.hexdigest()[:16],
+                "vgpr=%d agpr=%d sgpr=%d lds=%d scratch=%d" % r if r else "(no metadata: not a kernel)"))
+    return lines
+
+
 if __name__ == "__main__":
     import sys
+    if len(sys.argv) > 2 and sys.argv[1] == "--listing":            # python tests/helpers/isa_lint.py --listing <lib>
+        print("\n".join(kernel_listing(sys.argv[2])))
+        sys.exit(0)
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
         os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "pinns-tf2.0_amd", "pinn_native",
         "libpinn_hip.so")

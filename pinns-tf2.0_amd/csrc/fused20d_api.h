@@ -13,12 +13,20 @@ namespace pinn {
 constexpr int fused20d_blocks(int H) { return 5 + (H - 1) * 30 + 6; }
 // the flat weight vector is brought into LDS by LDS-DMA in whole 1-KiB pieces (128 doubles)
 inline size_t fused20d_weight_doubles(int n_theta) { return ((size_t)n_theta + 127) / 128 * 128; }
-// one-tile launches (workgroups >= tiles) keep no accumulators: every wave parks the UNFOLDED partial blocks of one phase of
-// the reverse sweep (<= 30 blocks x 64 lanes) in a staging area, double buffered, and the workgroup sums them phase by phase
-constexpr int FUSED20D_STAGE_WAVE = 30 * 64;                    // doubles per wave and buffer
+// one-tile launches (workgroups >= tiles) keep no accumulators: every wave parks the blocks of one phase of the reverse sweep
+// (<= 30) in a staging area, double buffered, and the workgroup sums them phase by phase.  PINN_ONETILE_SUM
+// (kernels_fused20d.h) -- 0, the default: unfolded, all 64 lanes; 1: the blocks folded in registers, 16 totals per block and
+// wave; 2: folded, no double buffer -- every block of the sweep has a place of its own, summed once behind the sweep
+#ifndef PINN_ONETILE_SUM
+#define PINN_ONETILE_SUM 0
+#endif
+constexpr int FUSED20D_STAGE_WAVE = PINN_ONETILE_SUM ? 30 * 16 : 30 * 64;   // doubles per wave and buffer
 constexpr int FUSED20D_STAGE_BUF = 4 * FUSED20D_STAGE_WAVE;     // doubles per buffer (four waves)
+constexpr int fused20d_stage_doubles(int n_hidden) {
+  return PINN_ONETILE_SUM == 2 ? fused20d_blocks(n_hidden) * 64 : 2 * FUSED20D_STAGE_BUF;
+}
 inline size_t fused20d_lds_bytes(int n_hidden, int n_theta) {
-  const size_t acc = (size_t)4 * fused20d_blocks(n_hidden) * 16, stage = (size_t)2 * FUSED20D_STAGE_BUF;
+  const size_t acc = (size_t)4 * fused20d_blocks(n_hidden) * 16, stage = (size_t)fused20d_stage_doubles(n_hidden);
   return (fused20d_weight_doubles(n_theta) + (acc > stage ? acc : stage) + 4 * 256) * sizeof(double);   // + loss-part slots
 }
 

@@ -74,6 +74,22 @@
 #define PINN_PA_LOOP 1           // the pinned GEMV loops in the tile-loop variants too: N_f = 10^6 1868 -> 1851 us, same box
                                  // (profiles/r06_ab_loopvariants.txt; with the ds_bpermute rotations of rounds 2-5 this was a loss)
 #endif
+// PINN_ONETILE_SUM (defined in fused20d_api.h: it sizes the staging area): how a one-tile launch adds the four blocks and the
+// four waves of a gradient entry
+//  0  (default) every lane parks its unfolded partial, 30 x 64 doubles per wave and phase; the workgroup adds 4 waves x 4
+//     blocks per entry once per reverse layer, 16 ds_read_b128 per thread
+//  1  the four blocks folded in registers first (two DPP row rotations), the 16 lanes that hold the total park it, entry-major
+//     with the four waves adjacent: a quarter of the LDS bytes, 4 ds_read_b128 per thread and layer
+//  2  the fold of 1, every phase in a region of its own, no per-layer barrier: one sum behind the sweep
+// All three form (b0 + b1) + (b2 + b3) per wave and ((w0 + w1) + w2) + w3 over the waves: bit-identical rows
+// (tests/test_gpu_onetile_fold.py builds 1 and 2 and compares).  Both folds LOST: + 1.8 and + 1.5 us per step on the headline
+// (profiles/onetile_fold_ab.txt section 1) -- the 1 050 instructions they add cost more than the LDS traffic they save.
+#ifndef PINN_ROW_STORE_WT
+#define PINN_ROW_STORE_WT 1      // the one-tile row stores as write-through stores (agent-scope relaxed atomic store: sc1), spread
+                                 // over the reverse sweep: the launch does not end with the rows dirty in the L2s, which the
+                                 // reduction behind it otherwise waits for.  Same values; measured against the parent's plain
+                                 // stores in profiles/onetile_fold_ab.txt section 2.  0: plain stores
+#endif
 #ifndef PINN_OPAQUE_TILE_D
 #define PINN_OPAQUE_TILE_D 0
 #endif
@@ -242,7 +258,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
     }
   }
   double* const gacc_all = wl + nwp;                  // tile loop: 4 x NBLK x 16 accumulators; one tile: 2 staging buffers
-  double* const lacc_all = gacc_all + (ONE_TILE ? 2 * FUSED20D_STAGE_BUF : 4 * NBLK * 16);
+  double* const lacc_all = gacc_all + (ONE_TILE ? fused20d_stage_doubles(H) : 4 * NBLK * 16);
 
 #if PINN_ROT_MFMA
 #define PINN_TO_POINTS(X) mfma444((X), ident, 0.0)
@@ -346,9 +362,19 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
     auto grad_fetch = [&](const int blk) { return (ONE_TILE || PINN_GACC_ATOMIC) ? 0.0 : gacc[blk * 16 + ge]; };
     // One tile per workgroup: nothing is accumulated, so the four blocks are not folded in registers (2 x 2 DPP moves + 2
     // adds per block, 1 300 instructions per tile): every lane parks its own partial in the phase's staging buffer
-    // (entry-major: the four blocks of an entry adjacent), and phase_sum adds blocks and waves with the whole workgroup.
+    // (entry-major: the four blocks of an entry adjacent), and phase_issue / phase_finish add blocks and waves with the whole
+    // workgroup.  (PINN_ONETILE_SUM = 1, 2, measured and dropped: ROR4 then ROR8, block 1 parks (b1 + b0) + (b3 + b2).)
     int phase_first = 0;
-    double* stage_w = gacc_all + wave * FUSED20D_STAGE_WAVE;
+    constexpr int PARK_BLOCK = 1;
+    // phase p of the reverse sweep (0: dense H, H - d: layer d's 30 blocks, H: dense 0) -> its first block / its staging area
+    // (the waves are FUSED20D_STAGE_WAVE apart when every lane parks, adjacent doubles when the totals do)
+    constexpr int STAGE_WAVE_STRIDE = PINN_ONETILE_SUM ? 1 : FUSED20D_STAGE_WAVE;
+#if PINN_ONETILE_SUM == 2
+#define PINN_PHASE_STAGE(P) ((P) == 0 ? BLK_H : (P) == H ? 0 : 5 + (H - (P) - 1) * 30) * 64
+#else
+#define PINN_PHASE_STAGE(P) ((P) & 1) * FUSED20D_STAGE_BUF
+#endif
+    double* stage_w = gacc_all + wave * STAGE_WAVE_STRIDE;
     // Tile loop (PINN_GACC_ATOMIC): the folded total sits in all four lanes of an entry; the lanes of block 0 add it into the
     // wave's accumulator with ONE ds_add_f64 (16 distinct addresses, one adder per address and tile: no conflict,
     // bit-reproducible) instead of a ds_read of the old value long before, a v_add_f64 and a ds_write.  A group's stores
@@ -390,10 +416,50 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
                        : "memory");
       }
 #endif
+#if PINN_ONETILE_SUM
+      if constexpr (ONE_TILE) {
+        const unsigned addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(stage_w + ge * 4);
+        constexpr unsigned long long park = 0x000f000f000f000full << (4 * PARK_BLOCK);
+        unsigned long long saved;
+        if (pend_n == 6)
+          asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[mk]\n\t"
+                       "ds_write2st64_b64 %[a], %[d0], %[d1] offset0:%[o0] offset1:%[o1]\n\t"
+                       "ds_write2st64_b64 %[a], %[d2], %[d3] offset0:%[o2] offset1:%[o3]\n\t"
+                       "ds_write2st64_b64 %[a], %[d4], %[d5] offset0:%[o4] offset1:%[o5]\n\t"
+                       "s_mov_b64 exec, %[sv]"
+                       : [sv] "=&s"(saved)
+                       : [a] "v"(addr), [mk] "s"(park), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
+                         [d2] "v"(pend_D[2]), [d3] "v"(pend_D[3]), [d4] "v"(pend_D[4]), [d5] "v"(pend_D[5]),
+                         [o0] "i"(pend_off[0]), [o1] "i"(pend_off[1]), [o2] "i"(pend_off[2]), [o3] "i"(pend_off[3]),
+                         [o4] "i"(pend_off[4]), [o5] "i"(pend_off[5])
+                       : "memory");
+        else
+          asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[mk]\n\t"
+                       "ds_write2st64_b64 %[a], %[d0], %[d1] offset0:%[o0] offset1:%[o1]\n\t"
+                       "ds_write2st64_b64 %[a], %[d2], %[d3] offset0:%[o2] offset1:%[o3]\n\t"
+                       "ds_write_b64 %[a], %[d4] offset:%[o4] * 512\n\t"
+                       "s_mov_b64 exec, %[sv]"
+                       : [sv] "=&s"(saved)
+                       : [a] "v"(addr), [mk] "s"(park), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
+                         [d2] "v"(pend_D[2]), [d3] "v"(pend_D[3]), [d4] "v"(pend_D[4]),
+                         [o0] "i"(pend_off[0]), [o1] "i"(pend_off[1]), [o2] "i"(pend_off[2]), [o3] "i"(pend_off[3]),
+                         [o4] "i"(pend_off[4])
+                       : "memory");
+      }
+#endif
       pend_n = 0;
     };
     auto grad_store = [&](double D, const double old, const int blk) {
+#if PINN_ONETILE_SUM
+      if (ONE_TILE) {
+        D += dpp_mov<DPP_ROW_ROR4>(D);
+        D += dpp_mov<DPP_ROW_ROR8>(D);
+        pend_D[pend_n] = D; pend_off[pend_n] = blk - phase_first; ++pend_n;   // in blocks of 64 doubles (ds_write2st64_b64), parked by gacc_flush below
+        return;
+      }
+#else
       if (ONE_TILE) { stage_w[(blk - phase_first) * 64 + sput] = D; return; }
+#endif
 #if PINN_GACC_ATOMIC && PINN_FOLD_STAGES < 2
       if (PINN_FOLD_STAGES == 1) D += dpp_mov<DPP_ROW_ROR8>(D);       // the LDS adder does the rest of the fold
 #else
@@ -419,42 +485,72 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
       }
     }
     double* __restrict__ const row1 = part + (size_t)blockIdx.x * R;
-    // sum of one phase: all four waves have parked their NB blocks in buffer `buf`; entry e of the phase = 4 waves x 4
+    // sum of one phase p: all four waves have parked its blocks in the phase's staging area; entry e of the phase = 4 waves x 4
     // blocks in fixed order -> its place in the workgroup's gradient row.  to_index(e) = flat parameter index or -1.
     //   phase_issue   barrier (all four waves have parked the phase) + the 16 reads of this thread's two entries
     //   phase_finish  4 waves x 4 blocks added in fixed order, stored at the entry's place in the workgroup's gradient row
     // Threads without a second entry read a clamped address and store nothing (no divergent branch around the reads).
+    // Folded settings: an entry is the four waves' totals, ps_lo[k][0] = (w0, w1), ps_hi[k][0] = (w2, w3), 4 reads; their
+    // parking stores are inline asm, which hipcc's wait-count pass does not count, so the wait in front of the barrier is
+    // written out; with PINN_ONETILE_SUM = 2 issue and finish do nothing and all phases are summed behind the sweep.
     typedef double d2 __attribute__((ext_vector_type(2)));
-    d2 ps_lo[2][4], ps_hi[2][4];
-    auto phase_issue = [&](const int n_entries, const int buf) {
-      __syncthreads();
-      const double* __restrict__ const sb = gacc_all + buf * FUSED20D_STAGE_BUF;
+    constexpr int PS_W = PINN_ONETILE_SUM ? 1 : 4;
+    d2 ps_lo[2][PS_W], ps_hi[2][PS_W];
+    auto phase_reads = [&](const int n_entries, const int p) {
+      const double* __restrict__ const sb = gacc_all + PINN_PHASE_STAGE(p);
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         if (256 * k >= n_entries) continue;
         const int e = tid + 256 * k < n_entries ? tid + 256 * k : n_entries - 1;
+#if PINN_ONETILE_SUM
+        ps_lo[k][0] = *reinterpret_cast<const d2*>(sb + 4 * e);
+        ps_hi[k][0] = *reinterpret_cast<const d2*>(sb + 4 * e + 2);
+#else
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
           ps_lo[k][w] = *reinterpret_cast<const d2*>(sb + w * FUSED20D_STAGE_WAVE + 4 * e);
           ps_hi[k][w] = *reinterpret_cast<const d2*>(sb + w * FUSED20D_STAGE_WAVE + 4 * e + 2);
         }
+#endif
       }
     };
-    auto phase_finish = [&](const int n_entries, auto to_index) {
+    auto parked_barrier = [&]() {
+      if (PINN_ONETILE_SUM) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __syncthreads();
+    };
+    auto phase_issue = [&](const int n_entries, const int p) {
+      if (PINN_ONETILE_SUM == 2) return;                 // summed behind the sweep
+      parked_barrier();
+      phase_reads(n_entries, p);
+    };
+    auto phase_adds = [&](const int n_entries, auto to_index) {
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         if (256 * k >= n_entries) continue;
         const int e = tid + 256 * k;
         const int idx = e < n_entries ? to_index(e, k) : -1;
         double v = 0.0;
+#if PINN_ONETILE_SUM
+        v = ((ps_lo[k][0].x + ps_lo[k][0].y) + ps_hi[k][0].x) + ps_hi[k][0].y;
+#else
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
           const double t = (ps_lo[k][w].x + ps_lo[k][w].y) + (ps_hi[k][w].x + ps_hi[k][w].y);
           v = w == 0 ? t : v + t;
         }
-        if (idx >= 0) row1[idx] = v;     // (as a nontemporal store -- the row streaming past the L2 -- the Adam step was 0.6 us
-                                         //  LONGER, profiles/r06_ab_loopvariants.txt)
+#endif
+        // (as a nontemporal store -- the row streaming past the L2 -- the Adam step was 0.6 us LONGER,
+        //  profiles/r06_ab_loopvariants.txt; written through, it is shorter: PINN_ROW_STORE_WT)
+#if PINN_ROW_STORE_WT
+        if (idx >= 0) __hip_atomic_store(row1 + idx, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+        if (idx >= 0) row1[idx] = v;
+#endif
       }
+    };
+    auto phase_finish = [&](const int n_entries, auto to_index) {
+      if (PINN_ONETILE_SUM == 2) return;
+      phase_adds(n_entries, to_index);
     };
     auto idx_dense_h = [&](const int e, int) {
       const int m = e >> 4, i = (e >> 2) & 3, j = e & 3;
@@ -646,7 +742,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
         }
         D[5] = mfma444(onesA, sbT[0], 0.0);
         phase_first = BLK_H;                                   // phase 0 of the reverse sweep: buffer 0
-        stage_w = gacc_all + wave * FUSED20D_STAGE_WAVE;
+        stage_w = gacc_all + PINN_PHASE_STAGE(0) + wave * STAGE_WAVE_STRIDE;
 #pragma unroll
         for (int m = 0; m < 6; ++m) grad_store(D[m], old[m], BLK_H + m);
         gacc_flush();
@@ -664,7 +760,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
       // pre-activation adjoints of layer d, and their point-major (rotated) copies for the weight gradient
       double zb[4][5], zbT[4][5];
       if constexpr (ONE_TILE && PA && PINN_ROT_IN_GEMV == 2)
-        phase_issue(d == H - 1 ? 6 * 16 : 30 * 16, d == H - 1 ? 0 : (H - d - 1) & 1);
+        phase_issue(d == H - 1 ? 6 * 16 : 30 * 16, H - d - 1);
 #pragma unroll
       for (int n = 0; n < 5; ++n) {
         double a, zp, zq, zr;
@@ -690,7 +786,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
         else phase_finish(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[d + 1] + rel_hidden[k]; });
       };
       if constexpr (ONE_TILE) {
-        if (!(PA && PINN_ROT_IN_GEMV == 2)) phase_issue(d == H - 1 ? 6 * 16 : 30 * 16, d == H - 1 ? 0 : (H - d - 1) & 1);
+        if (!(PA && PINN_ROT_IN_GEMV == 2)) phase_issue(d == H - 1 ? 6 * 16 : 30 * 16, H - d - 1);
         if (!(PA && PINN_ROT_IN_GEMV == 1)) finish_prev();
       }
       STAMP2(d == 4, 21);
@@ -749,7 +845,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
       // 256-VGPR limit, and with all of them live hipcc sank the accumulator fetches next to their uses)
       const int base = 5 + (d - 1) * 30;
       phase_first = base;                                      // phase H - d: buffers alternate
-      stage_w = gacc_all + ((H - d) & 1) * FUSED20D_STAGE_BUF + wave * FUSED20D_STAGE_WAVE;
+      stage_w = gacc_all + PINN_PHASE_STAGE(H - d) + wave * STAGE_WAVE_STRIDE;
 #define PINN_ROTATED_INPUTS(M, O4)                                                                          \
   do {                                                                                                      \
     double a_, zp_, zq_, zr_;                                                                               \
@@ -811,7 +907,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
         bT[0][n] = PINN_TO_POINTS(bh); bT[1][n] = PINN_TO_POINTS(bp); bT[2][n] = PINN_TO_POINTS(bq);
       }
       if constexpr (ONE_TILE) {                                // layer 1's phase
-        phase_issue(30 * 16, (H - 1) & 1);
+        phase_issue(30 * 16, H - 1);
         phase_finish(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[1] + rel_hidden[k]; });
       }
       double D[5], old[5];
@@ -824,16 +920,29 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
 #pragma unroll
       for (int n = 0; n < 5; ++n) D[n] = mfma444(Aq, bT[2][n], D[n]);
       phase_first = 0;                                         // phase H
-      stage_w = gacc_all + (H & 1) * FUSED20D_STAGE_BUF + wave * FUSED20D_STAGE_WAVE;
+      stage_w = gacc_all + PINN_PHASE_STAGE(H) + wave * STAGE_WAVE_STRIDE;
 #pragma unroll
       for (int n = 0; n < 5; ++n) grad_store(D[n], old[n], n);
       gacc_flush();
       if constexpr (ONE_TILE) {
-        phase_issue(5 * 16, H & 1);
-        phase_finish(5 * 16, [&](const int e, int) {
+        auto idx_dense_0 = [&](const int e, int) {
           const int f = 4 * (e >> 4) + (e & 3), i = (e >> 2) & 3;
           return i == 0 ? nd.off_w[0] + f : i == 1 ? nd.off_w[0] + FW + f : i == 2 ? nd.off_b[0] + f : -1;
-        });
+        };
+        phase_issue(5 * 16, H);
+        phase_finish(5 * 16, idx_dense_0);
+        if constexpr (PINN_ONETILE_SUM == 2) {           // every phase is parked in its own region: one barrier, H + 1 sums
+          parked_barrier();
+          phase_reads(6 * 16, 0);
+          phase_adds(6 * 16, idx_dense_h);
+#pragma unroll
+          for (int d = H - 1; d >= 1; --d) {
+            phase_reads(30 * 16, H - d);
+            phase_adds(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[d] + rel_hidden[k]; });
+          }
+          phase_reads(5 * 16, H);
+          phase_adds(5 * 16, idx_dense_0);
+        }
       }
     }
     if (ONE_TILE) break;
@@ -841,6 +950,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
   STAMP(2 * H + 1);
 #undef PINN_LANE_INDICES
 #undef PINN_TO_POINTS
+#undef PINN_PHASE_STAGE
 
   // -------------------------------------------------------------------- one gradient row per workgroup
   {

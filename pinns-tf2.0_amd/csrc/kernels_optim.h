@@ -9,15 +9,25 @@ namespace pinn {
 
 // gl[c] = sum over rows of part[row*R + c] in a fixed order (bit-reproducible).
 // gl layout: [0, n_theta) gradient | n_theta+0..2 loss parts (residual, data, boundary).
-// Block = 64 columns x 16 row-slices (row r belongs to slice r & 15): 1024 threads, each with up to
-// 8 independent loads in flight; the slices are combined through LDS in index order.
-// Grid = ceil(R / 64) blocks.
+// Block = 64 columns x 16 row-slices (row r belongs to slice r & 15): 1024 threads; the slices are combined through LDS
+// in index order.  Grid = ceil(R / 64) blocks.
+// A thread of slice q owns rows q, q + 16, ...; accumulator k of its eight takes rows q + 16 k, q + 16 k + 128, ... in that
+// order.  PINN_REDUCE_ONE_ROUND = 1 requests the 16 rows of every 256 (predicated) before the first wait: one memory round
+// trip for any launch of up to 256 rows.  0 is the earlier schedule: 8 loads per round, and each row of the tail behind a
+// branch and a wait of its own -- at the headline's 158 rows three dependent round trips.  Same sums, bit for bit
+// (tests/test_gpu_reduce_one_round.py); the A/B is profiles/reduce_one_round_ab.txt.
+#ifndef PINN_REDUCE_ONE_ROUND
+#define PINN_REDUCE_ONE_ROUND 1
+#endif
 constexpr int RED_COLS = 64;
 constexpr int RED_SLICES = 16;
 constexpr int RED_THREADS = RED_COLS * RED_SLICES;   // (measured: 8 / 16 / 32 columns per workgroup, i.e. 8x / 4x / 2x the
                                                      //  workgroups, are no faster: f64 Adam step 41.9 / 40.9 / 40.6 vs 40.9 us; neither are two columns per thread
                                                      //  on an even row pitch, 512 threads, bit-identical sums: 41.3 vs 40.8 us, f32 29.3 vs 28.3; nor non-temporal row
-                                                     //  loads: 41.9 vs 40.8 us -- part of the rows is still in an L2)
+                                                     //  loads: 41.9 vs 40.8 us -- part of the rows is still in an L2.  None of these touched the
+                                                     //  chain of dependent load rounds inside a thread; PINN_REDUCE_ONE_ROUND does: headline step
+                                                     //  44.31 -> 43.63 us at 158 rows, nothing at 128 rows, where the loop was one round already:
+                                                     //  profiles/reduce_one_round_ab.txt)
 
 template <typename real>
 __device__ __forceinline__ double reduce_column(const real* __restrict__ part, int n_rows, int R,
@@ -25,6 +35,25 @@ __device__ __forceinline__ double reduce_column(const real* __restrict__ part, i
   const int cl = threadIdx.x & 63;
   double a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, a6 = 0, a7 = 0;
   if (c < R) {
+#if PINN_REDUCE_ONE_ROUND
+    // q = threadIdx.x >> 6 is the wave's number, so row numbers and predicates are uniform (scalar branches round the loads).
+    // With per-lane row numbers the 16 address pairs live next to the 16 values: 95 VGPRs, and k_reduce_xgmi spills (200 B)
+    const unsigned lane_off = (unsigned)c * (unsigned)sizeof(real);
+    for (int r0 = __builtin_amdgcn_readfirstlane(q); r0 < n_rows; r0 += 16 * RED_SLICES) {
+      real v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        v[i] = (r0 + i * RED_SLICES < n_rows)
+                   ? *(const real*)((const char*)(part + (size_t)(r0 + i * RED_SLICES) * R) + lane_off) : real(0);
+      // an absent row keeps the accumulator (a + 0.0 would turn a -0.0 into +0.0); rows r0 + 128.. follow rows r0.. as in the loop below
+#define PINN_RED_ADD(a, i) a = (r0 + (i) * RED_SLICES < n_rows) ? a + (double)v[i] : a
+      PINN_RED_ADD(a0, 0); PINN_RED_ADD(a1, 1); PINN_RED_ADD(a2, 2); PINN_RED_ADD(a3, 3);
+      PINN_RED_ADD(a4, 4); PINN_RED_ADD(a5, 5); PINN_RED_ADD(a6, 6); PINN_RED_ADD(a7, 7);
+      PINN_RED_ADD(a0, 8); PINN_RED_ADD(a1, 9); PINN_RED_ADD(a2, 10); PINN_RED_ADD(a3, 11);
+      PINN_RED_ADD(a4, 12); PINN_RED_ADD(a5, 13); PINN_RED_ADD(a6, 14); PINN_RED_ADD(a7, 15);
+#undef PINN_RED_ADD
+    }
+#else
     const real* __restrict__ p = part + c;
     int r = q;
     for (; r + 7 * RED_SLICES < n_rows; r += 8 * RED_SLICES) {
@@ -40,6 +69,7 @@ __device__ __forceinline__ double reduce_column(const real* __restrict__ part, i
     if (r + 4 * RED_SLICES < n_rows) a4 += (double)p[(size_t)(r + 4 * RED_SLICES) * R];
     if (r + 5 * RED_SLICES < n_rows) a5 += (double)p[(size_t)(r + 5 * RED_SLICES) * R];
     if (r + 6 * RED_SLICES < n_rows) a6 += (double)p[(size_t)(r + 6 * RED_SLICES) * R];
+#endif
   }
   sh[q][cl] = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
   __syncthreads();

@@ -1,0 +1,455 @@
+"""Entrywise gradient comparison (test infrastructure, numpy only).
+
+The suite's other gradient checks use one number, max|grad - ref| / max|ref|: every entry is judged against the largest
+entry of the flat vector, so an error on a small entry -- a lambda gradient, a lost collocation point -- stays below the
+float32 tolerance.  Here each entry is judged on its own rounding scale
+
+    A = |h|^T |zb| + |p|^T |zpb| + |q|^T |zqb| + |r|^T |zrb|,     A_b = sum |zb|,
+
+the reverse sweep's last contraction with absolute values, summed over every term of the loss (lambda entries:
+sum |fb u u_x| and sum |fb c2 u_xx|).  The adjoints themselves are the ordinary ones.
+
+  restate(kind, w, layers, lb, ub, sets, dtype)  the oracle's Taylor forward + reverse sweep (oracle/mlp.py, oracle/pde.py)
+                                                 with all arithmetic in `dtype` -> (loss, flat_grad, A)
+  blocks(layers, kind)                           names, slices and shapes of the flat layout: W0, b0, ..., lam1, lam2
+  entry_dev(grad, ref, A, layout)                worst |grad_i - ref_i| / A_i with its block and (row, col)
+  plain_error(case, dtype)                       worst entry of restate(dtype) against restate(wider)
+  mutants(case, dtype)                           wrong gradients a comparator has to catch
+  CASES, K, bound(case, dtype)                   the cases of tests/test_gpu_grad_entries.py and the allowances
+
+Bound of a case: K[(family, dtype)] * max(plain_error(case, dtype), 32 u), u the unit roundoff.  K is the kernels'
+allowance over plain arithmetic of the same width (another summation order: tiles, matrix-instruction accumulation, row
+slices; faster elementary functions).  It is 3 x the largest ratio entry_dev / max(plain_error, 32 u) measured on an
+MI355X (profiles/grad_entries_measured.jsonl), rounded up to one significant digit; tests/test_grad_entries_host.py fails
+if a K is so loose that a mutant passes.
+"""
+import functools
+
+import numpy as np
+
+NU = 0.01 / np.pi
+LB, UB = np.array([-1.0, 0.0]), np.array([1.0, 0.99])          # the domain of tests/test_gpu_fuzz.py
+
+# ---- allowances ---------------------------------------------------------------------------------------------------
+# family -> which kernels: "w20" k_fused20m / k_fused20 / k_fused20d (+ generic), "wide" k_wide_* / k_t16_fused / k_t16_*
+# at the Schrodinger net, "t16" the shape-generic k_t16_* sweeps and their halves (+ k_t16_fused, generic).
+# K = 3 x the largest ratio entry_dev / max(plain_error, 32 u) measured on an MI355X, rounded up to one significant digit.
+# The largest ratio is taken over everything these K are asserted on: the cases below and the shapes of
+# tests/test_gpu_fuzz.py (all in profiles/grad_entries_measured.jsonl).
+#                      K      largest ratio on CASES: path, case, entry     | on the fuzz shapes: path, shape, entry
+K = {
+    ("w20", "f32"): 9,    # 2.93: 1, burgers 4x20 (3, 61), W2[2,13]         | 1.08: 2, burgers_ide 10x20 700, W6[10,7]
+    ("w20", "f64"): 8,    # 2.44: 7, burgers 8x20 (3, 61), W3[12,5]         | 1.33: 1, burgers_ide 8x20 78, W3[19,15]
+    ("wide", "f32"): 7,   # 1.73: 3, schrodinger 33 000, W4[94,0]           | 2.03: 3, schrodinger 4x100 29, W1[59,7]
+    ("wide", "f64"): 6,   # 1.30: 8, schrodinger 333 / 1 pair, W1[45,90]    | 1.84: 6, schrodinger 4x100 29, W1[59,7]
+    ("t16", "f32"): 20,   # 1.22: 6, burgers 3x65, W0[1,18]                 | 3.48: 0, burgers 4x100 28, b0[0,81]
+    ("t16", "f64"): 20,   # 1.49: 8, burgers 3x65, b1[0,29]                 | 5.13: 5, schrodinger 5x93 1123 (*), W4[56,25]
+}
+# (*) more than LONGDOUBLE_POINTS points: against the float64 restatement and the assumed 64 u (below), so the figure holds
+# the restatement's own rounding too.
+# What caps them (tests/test_grad_entries_host.py): the weakest mutant is 134 x (w20), 219 x (wide), 61 x (t16) the float32
+# yardstick and > 1e10 x the float64 one.
+FLOOR_ULPS = 32.0            # the lowest plain error seen (28 u float32, 29 u float64): tiny nets are exact by luck
+# float64 sets of more than LONGDOUBLE_POINTS points have no 80-bit reference (too slow for a test); they are compared
+# with the float64 restatement, whose own error is taken as 64 u: the top of what plain float64 measured against
+# longdouble on 300 ... 10 000 points (3e-15 ... 7e-15)
+LONGDOUBLE_POINTS = 1000
+ASSUMED_F64_ULPS = 64.0
+
+DTYPES = {"f32": np.float32, "f64": np.float64}
+
+
+def unit_roundoff(dtype):
+    return float(np.finfo(dtype).eps) / 2.0
+
+
+def longdouble_is_wider():
+    return float(np.finfo(np.longdouble).eps) <= 1e-18
+
+
+# ---- layout -------------------------------------------------------------------------------------------------------
+def blocks(layers, kind):
+    """-> [(name, slice, shape)] of the reference's flat layout: per dense layer W ([fan_in, fan_out], row-major) then b;
+    burgers_ide appends lambda_1, lambda_2"""
+    out, off = [], 0
+    for i, (fi, fo) in enumerate(zip(layers[:-1], layers[1:])):
+        out.append(("W%d" % i, slice(off, off + fi * fo), (fi, fo)))
+        off += fi * fo
+        out.append(("b%d" % i, slice(off, off + fo), (1, fo)))
+        off += fo
+    if kind == "burgers_ide":
+        out.append(("lam1", slice(off, off + 1), (1, 1)))
+        out.append(("lam2", slice(off + 1, off + 2), (1, 1)))
+    return out
+
+
+def locate(i, layout):
+    for name, sl, shape in layout:
+        if sl.start <= i < sl.stop:
+            return name, divmod(i - sl.start, shape[1])
+    raise IndexError(i)
+
+
+def entry_dev(grad, ref, A, layout):
+    """-> (worst |grad_i - ref_i| / A_i, block name, (row, col)).  An entry whose scale A_i is zero has no term at all
+    and must be equal exactly: otherwise the deviation is inf, at that entry."""
+    grad, ref, A = (np.asarray(x, dtype=np.float64) for x in (grad, ref, A))
+    assert grad.shape == ref.shape == A.shape, (grad.shape, ref.shape, A.shape)
+    diff = np.abs(grad - ref)
+    diff[~np.isfinite(grad)] = np.inf
+    dev = np.where(A > 0, diff / np.where(A > 0, A, 1.0), np.where(diff > 0, np.inf, 0.0))
+    i = int(np.argmax(dev))
+    name, rc = locate(i, layout)
+    return float(dev[i]), name, rc
+
+
+# ---- the sweep in any dtype ---------------------------------------------------------------------------------------
+def _unpack(w, layers, dt):
+    out, off = [], 0
+    for fi, fo in zip(layers[:-1], layers[1:]):
+        out.append((w[off:off + fi * fo].reshape(fi, fo).astype(dt), w[off + fi * fo:off + fi * fo + fo].astype(dt)))
+        off += fi * fo + fo
+    return out
+
+
+def _tanh(z, formula):
+    if formula:                       # tanh_r5 of the float32 kernels: 1 - 2 / (1 + e^{2z}), in the sweep's dtype
+        one = z.dtype.type(1)
+        return one - (one + one) / (one + np.exp(z + z))
+    return np.tanh(z)
+
+
+def _forward(params, X, lb, s, formula):
+    """oracle.mlp.taylor_forward in the dtype of `params`"""
+    dt = params[0][0].dtype.type
+    h = s * (X - lb) - dt(1)
+    p, q, r = np.zeros_like(h), np.zeros_like(h), np.zeros_like(h)
+    p[:, 0] = s[0]
+    q[:, 1] = s[1]
+    cache, L = [], len(params)
+    for i, (W, b) in enumerate(params):
+        z, zp, zq, zr = h @ W + b, p @ W, q @ W, r @ W
+        if i < L - 1:
+            a = _tanh(z, formula)
+            d1 = dt(1) - a * a
+            d2 = dt(-2) * a * d1
+            cache.append((h, p, q, r, a, zp, zq, zr))
+            h, p, q, r = a, d1 * zp, d1 * zq, d2 * zp * zp + d1 * zr
+        else:
+            cache.append((h, p, q, r, None, zp, zq, zr))
+            h, p, q, r = z, zp, zq, zr
+    return (h, p, q, r), cache
+
+
+def _abs64(x):
+    return np.abs(x).astype(np.float64)
+
+
+def _backward(params, cache, hb, pb, qb, rb, G, A):
+    """oracle.mlp.taylor_backward in the dtype of `params`, accumulated into G [(dW, db)]; the same contractions over the
+    points with absolute values (in float64: a scale needs no more) into A"""
+    dt = params[0][0].dtype.type
+    for i in range(len(params) - 1, -1, -1):
+        W, _ = params[i]
+        h, p, q, r, a, zp, zq, zr = cache[i]
+        if a is not None:
+            d1 = dt(1) - a * a
+            d2 = dt(-2) * a * d1
+            d3 = dt(-2) * d1 * (dt(1) - dt(3) * a * a)
+            zb = d1 * hb + d2 * (zp * pb + zq * qb + zr * rb) + d3 * zp * zp * rb
+            zpb = d1 * pb + dt(2) * d2 * zp * rb
+            zqb, zrb = d1 * qb, d1 * rb
+        else:
+            zb, zpb, zqb, zrb = hb, pb, qb, rb
+        G[i][0] += h.T @ zb + p.T @ zpb + q.T @ zqb + r.T @ zrb
+        G[i][1] += zb.sum(axis=0)
+        A[i][0] += (_abs64(h).T @ _abs64(zb) + _abs64(p).T @ _abs64(zpb) + _abs64(q).T @ _abs64(zqb)
+                    + _abs64(r).T @ _abs64(zrb))
+        A[i][1] += _abs64(zb).sum(axis=0)
+        if i > 0:
+            hb, pb, qb, rb = zb @ W.T, zpb @ W.T, zqb @ W.T, zrb @ W.T
+
+
+def restate(kind, w, layers, lb, ub, sets, dtype, tanh_formula=False):
+    """Loss, flat gradient and entrywise scale A of `kind` in {burgers, burgers_ide, schrodinger} with all arithmetic in
+    `dtype` (np.float32, np.float64, np.longdouble); points, targets and weights are cast first, as the engine does.
+
+    sets: burgers      X_f, X_u, u, nu
+          burgers_ide  X_u, u                (w ends with lambda_1, lambda_2)
+          schrodinger  X_f, X_lb, X_ub, X0, uv0
+          optional n_f (n_u, n_b): the denominator of the collocation (data, boundary) mean, where it is not the number
+          of rows handed over (a set with points dropped keeps the full set's denominator, as a kernel that loses a
+          point does)
+    tanh_formula: tanh as 1 - 2 / (1 + e^{2z}) (the float32 kernels' tanh_r5)"""
+    dt = np.dtype(dtype).type
+    wide = np.longdouble if dt is np.longdouble else np.float64
+    lbd = np.asarray(lb, dtype=wide)
+    s = (2 / (np.asarray(ub, dtype=wide) - lbd)).astype(dt)        # the engine: 2 / (ub - lb) in float64, then cast
+    lbd = lbd.astype(dt)
+    w = np.asarray(w, dtype=np.float64)
+    cast = lambda x: np.asarray(x, dtype=np.float64).astype(dt)
+    n_net = sum(a * b + b for a, b in zip(layers[:-1], layers[1:]))
+    params = _unpack(w[:n_net], layers, dt)
+    G = [[np.zeros(W.shape, dt), np.zeros(b.shape, dt)] for W, b in params]
+    A = [[np.zeros(W.shape), np.zeros(b.shape)] for W, b in params]
+    tail_g, tail_a = [], []
+    zero = lambda x: np.zeros_like(x)
+
+    if kind == "burgers":
+        X_f, X_u, u, nu = cast(sets["X_f"]), cast(sets["X_u"]), cast(sets["u"]), dt(sets["nu"])
+        n_f, n_u = dt(sets.get("n_f", X_f.shape[0])), dt(sets.get("n_u", u.size))
+        (h, p, q, r), cache = _forward(params, X_f, lbd, s, tanh_formula)
+        f = q + h * p - nu * r
+        fb = dt(2) * f / n_f
+        _backward(params, cache, fb * p, fb * h, fb, -nu * fb, G, A)
+        (hu, _, _, _), cache = _forward(params, X_u, lbd, s, tanh_formula)
+        d = hu - u
+        _backward(params, cache, dt(2) * d / n_u, zero(d), zero(d), zero(d), G, A)
+        loss = np.sum(d * d) / n_u + np.sum(f * f) / n_f
+    elif kind == "burgers_ide":
+        X_u, u = cast(sets["X_u"]), cast(sets["u"])
+        n = dt(sets.get("n_u", X_u.shape[0]))
+        l1, l2 = dt(w[-2]), dt(w[-1])
+        c2 = np.exp(l2)
+        (h, p, q, r), cache = _forward(params, X_u, lbd, s, tanh_formula)
+        f = q + l1 * h * p - c2 * r
+        d = h - u
+        fb = dt(2) * f / n
+        _backward(params, cache, fb * l1 * p + dt(2) * d / n, fb * l1 * h, fb, -c2 * fb, G, A)
+        t1, t2 = fb * h * p, fb * (-c2) * r
+        tail_g, tail_a = [np.sum(t1), np.sum(t2)], [np.sum(_abs64(t1)), np.sum(_abs64(t2))]
+        loss = np.sum(d * d) / n + np.sum(f * f) / n
+    elif kind == "schrodinger":
+        X_f, X0, uv0 = cast(sets["X_f"]), cast(sets["X0"]), cast(sets["uv0"])
+        X_lb, X_ub = cast(sets["X_lb"]), cast(sets["X_ub"])
+        n_f, n_0 = dt(sets.get("n_f", X_f.shape[0])), dt(sets.get("n_u", X0.shape[0]))
+        n_b = dt(sets.get("n_b", X_lb.shape[0]))
+        (h, p, q, r), cache = _forward(params, X_f, lbd, s, tanh_formula)
+        u, v = h[:, 0:1], h[:, 1:2]
+        h2 = u * u + v * v
+        f_u = q[:, 0:1] + dt(0.5) * r[:, 1:2] + h2 * v
+        f_v = q[:, 1:2] - dt(0.5) * r[:, 0:1] - h2 * u
+        gu, gv = dt(2) * f_u / n_f, dt(2) * f_v / n_f
+        hb = np.concatenate([gu * dt(2) * u * v - gv * (dt(3) * u * u + v * v),
+                             gu * (u * u + dt(3) * v * v) - gv * dt(2) * u * v], axis=1)
+        _backward(params, cache, hb, zero(hb), np.concatenate([gu, gv], axis=1),
+                  np.concatenate([dt(-0.5) * gv, dt(0.5) * gu], axis=1), G, A)
+        loss = (np.sum(f_u * f_u) + np.sum(f_v * f_v)) / n_f
+        (h0, _, _, _), cache = _forward(params, X0, lbd, s, tanh_formula)
+        d0 = h0 - uv0
+        _backward(params, cache, dt(2) * d0 / n_0, zero(d0), zero(d0), zero(d0), G, A)
+        loss = loss + np.sum(d0[:, 0] ** 2) / n_0 + np.sum(d0[:, 1] ** 2) / n_0
+        if X_lb.shape[0]:
+            (hl, pl, _, _), cl = _forward(params, X_lb, lbd, s, tanh_formula)
+            (hu, pu, _, _), cu = _forward(params, X_ub, lbd, s, tanh_formula)
+            dh, dp = hl - hu, pl - pu
+            _backward(params, cl, dt(2) * dh / n_b, dt(2) * dp / n_b, zero(dh), zero(dh), G, A)
+            _backward(params, cu, dt(-2) * dh / n_b, dt(-2) * dp / n_b, zero(dh), zero(dh), G, A)
+            loss = loss + (np.sum(dh ** 2) + np.sum(dp ** 2)) / n_b
+    else:
+        raise ValueError(kind)
+    flat = lambda T, tail: np.concatenate([np.concatenate([W.ravel(), b.ravel()]) for W, b in T] + [np.asarray(tail)])
+    grad = flat(G, np.array(tail_g, dtype=dt))
+    assert grad.dtype == np.dtype(dt), grad.dtype               # nothing was promoted on the way
+    return loss, grad, flat(A, np.array(tail_a, dtype=np.float64))
+
+
+# ---- cases --------------------------------------------------------------------------------------------------------
+def _case(family, kind, W, H, n_f, n_u, n_b=0, lam=None, seed=0, paths=None, drop=1):
+    n_out = 2 if kind == "schrodinger" else 1
+    cid = "%s-%dx%d-f%d-u%d" % (kind, H, W, n_f, n_u) + ("-b%d" % n_b if n_b else "") + \
+          ("-lam%g_%g" % lam if lam else "")
+    return {"id": cid, "family": family, "kind": kind, "layers": [2] + [W] * H + [n_out], "n_f": n_f, "n_u": n_u,
+            "n_b": n_b, "lam": lam, "seed": seed, "paths": paths, "drop": drop}
+
+
+def _cases():
+    out, seed = [], 7000
+    nxt = lambda: seed + len(out)
+    # width 20: k_fused20m (2), k_fused20 (1), generic (0); float64 k_fused20d (7).  (3, 61) one partial tile,
+    # (61, 700) one tile per workgroup, ragged; (100, 16300) 257 tiles, the first launch the tile loop serves
+    for H in (4, 8):
+        for n_u, n_f in ((3, 61), (61, 700), (100, 16300)):
+            big = n_f > LONGDOUBLE_POINTS
+            out.append(_case("w20", "burgers", 20, H, n_f, n_u, seed=nxt(), drop=64 if big else 1,
+                             paths={"f32": (2, 1, 0)} if big else {"f32": (2, 1, 0), "f64": (7, 1, 0)}))
+    out.append(_case("w20", "burgers", 20, 10, 700, 61, seed=nxt(), paths={"f32": (2, 1, 0), "f64": (1, 0)}))
+    for n_u in (700, 16400):
+        for lam in ((0.6, -4.5), (0.0, -6.0)):
+            big = n_u > LONGDOUBLE_POINTS
+            out.append(_case("w20", "burgers_ide", 20, 8, 0, n_u, lam=lam, seed=nxt(), drop=64 if big else 1,
+                             paths={"f32": (2, 1, 0)} if big else {"f32": (2, 1, 0), "f64": (7, 1, 0)}))
+    # the Schrodinger net: k_wide_* (3), shape-generic (4), generic (0); float64 k_t16_fused (8)
+    for n_b in (1, 17):
+        out.append(_case("wide", "schrodinger", 100, 4, 333, 50, n_b=n_b, seed=nxt(),
+                         paths={"f32": (3, 4, 0), "f64": (8, 4, 0)}))
+    # two 32 768-point chunks; as in the tile-loop cases the lost unit is 64 points (one of 33 000 points moves an entry
+    # by 7e-6 of A, which is plain float32's own rounding)
+    out.append(_case("wide", "schrodinger", 100, 4, 33000, 50, n_b=17, seed=nxt(), drop=64, paths={"f32": (3, 4)}))
+    # shape-generic sweeps, their halves (5, 6), the fused float64 sweep where it is eligible (width >= 65, >= 2 hidden
+    # layers), generic
+    t16 = lambda W, H: {"f32": (4, 5, 6, 0), "f64": (8, 4, 5, 6, 0) if W >= 65 and H >= 2 else (4, 5, 6, 0)}
+    # (a chain of three 1-wide layers with one weight near zero is a constant: no single point then moves its gradient.
+    # The seed of that case is the first from 7015 whose W1, W2, W3 all exceed 0.25 in magnitude.)
+    for W in (1, 24, 65, 97, 128):
+        for H in (1, 3):
+            out.append(_case("t16", "burgers", W, H, 333, 17, seed=7019 if (W, H) == (1, 3) else nxt(), paths=t16(W, H)))
+    out.append(_case("t16", "burgers_ide", 68, 2, 0, 300, lam=(0.6, -4.5), seed=nxt(), paths=t16(68, 2)))
+    out.append(_case("t16", "schrodinger", 116, 2, 200, 17, n_b=5, seed=nxt(), paths=t16(116, 2)))
+    for c in out:
+        assert "f64" not in c["paths"] or n_points(c) <= LONGDOUBLE_POINTS, c["id"]
+    return out
+
+
+def n_points(case):
+    return case["n_f"] + case["n_u"] + 2 * case["n_b"]
+
+
+def make_case(kind, layers, n_f, n_u, n_b, lam, rs, lb=LB, ub=UB):
+    """weights 0.9 / sqrt(max(W, 2)) N(0, 1), biases included, uniform points, N(0, 1) targets: as tests/test_gpu_fuzz.py
+    -> (w, sets)"""
+    W = layers[1]
+    P = sum(a * b + b for a, b in zip(layers[:-1], layers[1:]))
+    w = 0.9 / np.sqrt(max(W, 2)) * rs.standard_normal(P)
+    pts = lambda n: np.column_stack([rs.uniform(lb[0], ub[0], n), rs.uniform(lb[1], ub[1], n)])
+    X_f, X_u = pts(n_f), pts(n_u)
+    u = rs.standard_normal((n_u, layers[-1]))
+    if kind == "burgers":
+        return w, {"X_f": X_f, "X_u": X_u, "u": u, "nu": NU}
+    if kind == "burgers_ide":
+        return np.concatenate([w, lam]), {"X_u": X_u, "u": u}
+    tb = rs.uniform(lb[1], ub[1], (n_b, 1))
+    return w, {"X_f": X_f, "X0": X_u, "uv0": u, "X_lb": np.hstack([0 * tb + lb[0], tb]),
+               "X_ub": np.hstack([0 * tb + ub[0], tb])}
+
+
+CASES = _cases()
+CASE_BY_ID = {c["id"]: c for c in CASES}
+assert len(CASE_BY_ID) == len(CASES)
+
+
+@functools.lru_cache(maxsize=None)
+def case_inputs(cid):
+    c = CASE_BY_ID[cid]
+    return make_case(c["kind"], c["layers"], c["n_f"], c["n_u"], c["n_b"], c["lam"], np.random.RandomState(c["seed"]))
+
+
+def wider(dtype):
+    return np.float64 if np.dtype(dtype) == np.float32 else np.longdouble
+
+
+def _restate_case(c, dtype, sets=None, tanh_formula=False):
+    w, s = case_inputs(c["id"])
+    return restate(c["kind"], w, c["layers"], LB, UB, s if sets is None else sets, dtype, tanh_formula)
+
+
+@functools.lru_cache(maxsize=None)
+def _wide(cid, dtype_name):
+    return _restate_case(CASE_BY_ID[cid], wider(DTYPES[dtype_name]))
+
+
+def _shared(x):
+    x = np.asarray(x, dtype=np.float64)
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def reference(cid, dtype_name):
+    """-> (loss, grad, A) of the case in the type wider than `dtype_name`, as float64 (computed once, read-only)"""
+    loss, g, A = _wide(cid, dtype_name)
+    return float(loss), _shared(g), _shared(A)
+
+
+def dev_against_wide(g, ref, A, layout):
+    """entry_dev with the difference taken in the reference's type (a longdouble reference is not rounded first)"""
+    return entry_dev(np.asarray(g, dtype=ref.dtype) - ref, np.zeros(ref.shape), A, layout)
+
+
+@functools.lru_cache(maxsize=None)
+def plain_error(cid, dtype_name):
+    """worst entry of the plain sweep in `dtype_name` against the same sweep in the wider type, in units of A"""
+    c = CASE_BY_ID[cid]
+    _, g, _ = _restate_case(c, DTYPES[dtype_name])
+    _, gw, A = _wide(cid, dtype_name)
+    return dev_against_wide(g, gw, A, blocks(c["layers"], c["kind"]))[0]
+
+
+def yardstick(cid, dtype_name):
+    """max(plain_error, 32 u): what K multiplies"""
+    return max(plain_error(cid, dtype_name), FLOOR_ULPS * unit_roundoff(DTYPES[dtype_name]))
+
+
+def bound(cid, dtype_name):
+    return K[(CASE_BY_ID[cid]["family"], dtype_name)] * yardstick(cid, dtype_name)
+
+
+def family_of(path, layers, dtype_name):
+    """the K family of a kernel path on a net (tests/test_gpu_fuzz.py: shapes that are not in CASES)"""
+    if path in (1, 2, 7) or (path == 0 and layers[1] == 20):
+        return "w20"
+    return "wide" if layers[1] == 100 and layers[-1] == 2 and len(layers) == 6 else "t16"
+
+
+def judge(kind, w, layers, sets, dtype_name, lb=LB, ub=UB):
+    """for inputs outside CASES -> (ref_loss, ref_grad, A, yardstick, layout): the reference in the wider type and
+    max(plain error, 32 u).  A float64 set of more than LONGDOUBLE_POINTS points is compared with the float64
+    restatement itself, and its plain error is taken as ASSUMED_F64_ULPS u."""
+    dt = DTYPES[dtype_name]
+    u = unit_roundoff(dt)
+    layout = blocks(layers, kind)
+    n = sum(np.shape(sets[k])[0] for k in ("X_f", "X_u", "X0", "X_lb", "X_ub") if k in sets)
+    loss, g, A = restate(kind, w, layers, lb, ub, sets, dt)
+    if dtype_name == "f64" and (n > LONGDOUBLE_POINTS or not longdouble_is_wider()):
+        return float(loss), _shared(g), _shared(A), max(ASSUMED_F64_ULPS, FLOOR_ULPS) * u, layout
+    lw, gw, Aw = restate(kind, w, layers, lb, ub, sets, wider(dt))
+    plain = dev_against_wide(g, gw, Aw, layout)[0]
+    return float(lw), _shared(gw), _shared(Aw), max(plain, FLOOR_ULPS * u), layout
+
+
+# ---- mutants ------------------------------------------------------------------------------------------------------
+def _dropped(kind, sets, what, n):
+    """the sets with the last n collocation points ("points"; burgers_ide: data points) or boundary pairs ("pairs") left
+    out and the denominators of the full sets kept"""
+    s = dict(sets)
+    if what == "pairs":
+        s["n_b"] = sets["X_lb"].shape[0]
+        s["X_lb"], s["X_ub"] = sets["X_lb"][:-n], sets["X_ub"][:-n]
+    elif kind == "burgers_ide":
+        s["n_u"] = sets["X_u"].shape[0]
+        s["X_u"], s["u"] = sets["X_u"][:-n], sets["u"][:-n]
+    else:
+        s["n_f"] = sets["X_f"].shape[0]
+        s["X_f"] = sets["X_f"][:-n]
+    return s
+
+
+def percentile_entry(A, q=0.10):
+    """index of the entry at the q-quantile of the nonzero scales"""
+    idx = np.argsort(A, kind="stable")
+    idx = idx[A[idx] > 0]
+    return int(idx[int(q * idx.size)])
+
+
+@functools.lru_cache(maxsize=None)
+def mutants(cid, dtype_name):
+    """-> {name: gradient (float64)}: wrong gradients in the reference's type that the bound has to reject
+      a  the last collocation point dropped (burgers_ide: data point; a tile-loop case: the last 64), recomputed
+      b  1 % on the entry at the 10th percentile of A
+      c  one periodic boundary pair dropped, recomputed (Schrodinger)
+      d  1 % on the lambda_2 entry (identification)"""
+    c = CASE_BY_ID[cid]
+    wide = wider(DTYPES[dtype_name])
+    _, sets = case_inputs(cid)
+    _, ref, A = reference(cid, dtype_name)
+    out = {"a": np.asarray(_restate_case(c, wide, _dropped(c["kind"], sets, "points", c["drop"]))[1], dtype=np.float64)}
+    b = ref.copy()
+    b[percentile_entry(A)] *= 1.01
+    out["b"] = b
+    if c["kind"] == "schrodinger":
+        out["c"] = np.asarray(_restate_case(c, wide, _dropped(c["kind"], sets, "pairs", 1))[1], dtype=np.float64)
+    if c["kind"] == "burgers_ide":
+        d = ref.copy()
+        d[-1] *= 1.01
+        out["d"] = d
+    return out

@@ -3,8 +3,14 @@
 the engine can choose for a shape (generic, HBM-stash width-20, register-stash 8x20, wide MFMA, shape-generic MFMA
 tile16 -- also each of its halves paired with the generic other half, paths 5 and 6) is hit by some case, and for
 shapes with several eligible families all of them are compared."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import grad_entries as ge  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -14,6 +20,16 @@ LB, UB = np.array([-1.0, 0.0]), np.array([1.0, 0.99])
 
 def rel(a, b):
     return np.max(np.abs(np.asarray(a) - np.asarray(b))) / max(np.max(np.abs(b)), 1e-300)
+
+
+def assert_entries(grad, judged, path, layers, dtype, record):
+    """every entry on its own rounding scale (tests/helpers/grad_entries.py): the lambda gradients, 1e-5 of the largest
+    entry, are invisible to rel()"""
+    _, g_ref, A, yard, layout = judged
+    dev, block, (row, col) = ge.entry_dev(grad, g_ref, A, layout)
+    k = ge.K[(ge.family_of(path, layers, dtype), dtype)]
+    record(path=path, entry_dev=dev, yardstick=yard, ratio=dev / yard, block=block, row=row, col=col)
+    assert dev <= k * yard, "path %d: %s[%d,%d] is off by %.3e of its scale, bound %.3e" % (path, block, row, col, dev, k * yard)
 
 
 def cases():
@@ -38,7 +54,7 @@ def cases():
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 @pytest.mark.parametrize("pde_kind,W,H,n_f,n_u,seed", cases())
-def test_random_shapes_against_oracle(pde_kind, W, H, n_f, n_u, seed, dtype):
+def test_random_shapes_against_oracle(pde_kind, W, H, n_f, n_u, seed, dtype, record):
     import pinn_native
     from oracle import pde
     rs = np.random.RandomState(seed)
@@ -54,16 +70,20 @@ def test_random_shapes_against_oracle(pde_kind, W, H, n_f, n_u, seed, dtype):
     if pde_kind == "burgers":
         eng.set_collocation(X_f); eng.set_data(X_u, u); eng.set_pde_params(NU)
         ref = pde.burgers_loss_grad(w, layers, LB, UB, X_f, X_u, u, NU)
+        sets = {"X_f": X_f, "X_u": X_u, "u": u, "nu": NU}
     elif pde_kind == "burgers_ide":
         w = np.concatenate([w, [0.6, -4.5]])
         eng.set_data(X_u, u)
         ref = pde.burgers_ide_loss_grad(w, layers, LB, UB, X_u, u)
+        sets = {"X_u": X_u, "u": u}
     else:
         n_b = int(rs.randint(1, 40))
         tb = rs.uniform(LB[1], UB[1], (n_b, 1))
         X_lb, X_ub = np.hstack([0 * tb + LB[0], tb]), np.hstack([0 * tb + UB[0], tb])
         eng.set_collocation(X_f); eng.set_data(X_u, u); eng.set_boundary(X_lb, X_ub)
         ref = pde.schrodinger_loss_grad(w, layers, LB, UB, X_f, X_lb, X_ub, X_u, u)
+        sets = {"X_f": X_f, "X0": X_u, "uv0": u, "X_lb": X_lb, "X_ub": X_ub}
+    judged = ge.judge(pde_kind, w, layers, sets, dtype, LB, UB)
     tl, tg = (1e-11, 1e-10) if dtype == "f64" else (2e-5, 5e-5)
     default = eng.kernel_path()
     tried = 0
@@ -79,6 +99,7 @@ def test_random_shapes_against_oracle(pde_kind, W, H, n_f, n_u, seed, dtype):
         loss, grad, _ = eng.loss_grad()
         assert abs(loss - ref[0]) <= tl * max(abs(ref[0]), 1e-3), (path, loss, ref[0])
         assert rel(grad, ref[1]) <= tg, (path, rel(grad, ref[1]))
+        assert_entries(grad, judged, path, layers, dtype, record)
     assert tried >= 1
     eng.close()
 
@@ -138,7 +159,7 @@ def test_shape_generic_path_trains_like_the_reference_implementation():
 @pytest.mark.parametrize("pde_kind", ["burgers", "burgers_ide"])
 @pytest.mark.parametrize("H", [4, 6, 10])
 @pytest.mark.parametrize("n_pts", [700, 40000])
-def test_register_stash_kernels_at_other_depths(dtype, pde_kind, H, n_pts):
+def test_register_stash_kernels_at_other_depths(dtype, pde_kind, H, n_pts, record):
     """hp["layers"] is free-form in the reference (1d-burgers/inf_cont_burgers.py:23-43): 4x20, 6x20 and 10x20 nets run
     on the register-stash kernels too (k_fused20m: depths 4, 6, 8, 10; k_fused20d: 4, 6, 8 -- its AGPR stash of
     (H - 2) x 40 registers ends at 8), one tile per workgroup (700 points) and persistent multi-tile (40000 points),
@@ -158,17 +179,20 @@ def test_register_stash_kernels_at_other_depths(dtype, pde_kind, H, n_pts):
         u = rs.standard_normal((61, 1))
         eng.set_collocation(X_f); eng.set_data(X_u, u); eng.set_pde_params(NU)
         ref = pde.burgers_loss_grad(w, layers, LB, UB, X_f, X_u, u, NU)
+        sets = {"X_f": X_f, "X_u": X_u, "u": u, "nu": NU}
     else:
         w = np.concatenate([w, [0.6, -4.5]])
         X_u = pts(n_pts)
         u = rs.standard_normal((n_pts, 1))
         eng.set_data(X_u, u)
         ref = pde.burgers_ide_loss_grad(w, layers, LB, UB, X_u, u)
+        sets = {"X_u": X_u, "u": u}
     eng.set_weights(w)
     loss, grad, _ = eng.loss_grad()
     tl, tg = (1e-11, 1e-10) if dtype == "f64" else (2e-5, 5e-5)
     assert abs(loss - ref[0]) <= tl * abs(ref[0]), (loss, ref[0])
     assert rel(grad, ref[1]) <= tg, rel(grad, ref[1])
+    assert_entries(np.array(grad, copy=True), ge.judge(pde_kind, w, layers, sets, dtype, LB, UB), want_path, layers, dtype, record)
     loss2, grad2, _ = eng.loss_grad()
     assert loss2 == loss and np.array_equal(grad, grad2)
     eng.adam_init(0.01); la = eng.adam_run(3)                   # the packed weight image follows the optimiser

@@ -16,12 +16,15 @@ sum |fb u u_x| and sum |fb c2 u_xx|).  The adjoints themselves are the ordinary 
   plain_error(case, dtype)                       worst entry of restate(dtype) against restate(wider)
   mutants(case, dtype)                           wrong gradients a comparator has to catch
   CASES, K, bound(case, dtype)                   the cases of tests/test_gpu_grad_entries.py and the allowances
+  SAT_CASES, refusal(case), first_admitted_seed  the cases in the tail of tanh (part of CASES) and what admits them
+  formula_error, yardstick(case, dtype, path)    a saturated case judges a path by its own tanh formula
 
 Bound of a case: K[(family, dtype)] * max(plain_error(case, dtype), 32 u), u the unit roundoff.  K is the kernels'
 allowance over plain arithmetic of the same width (another summation order: tiles, matrix-instruction accumulation, row
 slices; faster elementary functions).  It is 3 x the largest ratio entry_dev / max(plain_error, 32 u) measured on an
 MI355X (profiles/grad_entries_measured.jsonl), rounded up to one significant digit; tests/test_grad_entries_host.py fails
-if a K is so loose that a mutant passes.
+if a K is so loose that a mutant passes.  A saturated case: K_SAT (where a family has one, else K) *
+max(plain_error, formula_error, 32 u), the formula being that of the kernel path (formula_of).
 """
 import functools
 
@@ -49,6 +52,21 @@ K = {
 # the restatement's own rounding too.
 # What caps them (tests/test_grad_entries_host.py): the weakest mutant is 134 x (w20), 219 x (wide), 61 x (t16) the float32
 # yardstick and > 1e10 x the float64 one.
+# Saturated cases (below) start from the same K.  Where a family measured more than K / 3 there by honest rounding of its
+# documented formula, it gets an allowance of its own here by the same rule (3 x the largest measured ratio, one significant
+# digit up), still capped by the mutants (SAT_MUTANT_MARGIN); K itself never moves.
+#                         K_SAT  largest ratio on SAT_CASES: path, case, entry
+K_SAT = {
+    ("wide", "f64"): 10,  # 3.01: 4 (8: 3.00), schrodinger 4x100 first layer x 27, W0[1,88].  Unit 88 (bias 4.2) sits at
+                          # |z| = 3.0 ... 5.4 at EVERY point, so each term of its entries carries d1 = 1 - a^2 at a few
+                          # 1e-4 ... 1e-3, and an absolute error in a shows there as |2 a da| / d1.  tanh_d's quotient form
+                          # is good to 1.48 u absolutely (tests/test_gpu_tanh_range.py), the library's tanh of path 0 and
+                          # of the plain restatement to 0.5 u: path 0 measures 0.64 at the same case.  Plain float64 numpy
+                          # with the same form (restate(..., tanh_formula="bf")) is off by 1.74e-14 of A at the same
+                          # entry, the kernels by 1.52e-14: honest rounding of the documented formula, nothing to fix.
+}
+# Every other family stayed below K / 3 on the saturated cases: w20 1.48 (float32: 2, 8x20 (3, 61), W0[0,14]) and 1.24
+# (float64: 7, same entry), wide float32 0.87 (3, first layer x 27, b0[34]), t16 0.71 / 0.59 (6, 3x65 x 22, b0[44]).
 FLOOR_ULPS = 32.0            # the lowest plain error seen (28 u float32, 29 u float64): tiny nets are exact by luck
 # float64 sets of more than LONGDOUBLE_POINTS points have no 80-bit reference (too slow for a test); they are compared
 # with the float64 restatement, whose own error is taken as 64 u: the top of what plain float64 measured against
@@ -113,9 +131,14 @@ def _unpack(w, layers, dt):
 
 
 def _tanh(z, formula):
+    one = z.dtype.type(1)
+    if formula == "bf":               # tanh_bf of k_fused20: sign(z) (1 - t) / (1 + t), t = e^{-2|z|}
+        az = np.abs(z)
+        t = np.exp(-(az + az))
+        return np.copysign((one - t) / (one + t), z)
     if formula:                       # tanh_r5 of the float32 kernels: 1 - 2 / (1 + e^{2z}), in the sweep's dtype
-        one = z.dtype.type(1)
-        return one - (one + one) / (one + np.exp(z + z))
+        with np.errstate(over="ignore"):
+            return one - (one + one) / (one + np.exp(z + z))
     return np.tanh(z)
 
 
@@ -180,7 +203,8 @@ def restate(kind, w, layers, lb, ub, sets, dtype, tanh_formula=False):
           optional n_f (n_u, n_b): the denominator of the collocation (data, boundary) mean, where it is not the number
           of rows handed over (a set with points dropped keeps the full set's denominator, as a kernel that loses a
           point does)
-    tanh_formula: tanh as 1 - 2 / (1 + e^{2z}) (the float32 kernels' tanh_r5)"""
+    tanh_formula: True or "r5": tanh as 1 - 2 / (1 + e^{2z}) (the float32 kernels' tanh_r5); "bf": as
+                  sign(z) (1 - t) / (1 + t), t = e^{-2|z|} (k_fused20's tanh_bf)"""
     dt = np.dtype(dtype).type
     wide = np.longdouble if dt is np.longdouble else np.float64
     lbd = np.asarray(lb, dtype=wide)
@@ -255,12 +279,14 @@ def restate(kind, w, layers, lb, ub, sets, dtype, tanh_formula=False):
 
 
 # ---- cases --------------------------------------------------------------------------------------------------------
-def _case(family, kind, W, H, n_f, n_u, n_b=0, lam=None, seed=0, paths=None, drop=1):
+def _case(family, kind, W, H, n_f, n_u, n_b=0, lam=None, seed=0, paths=None, drop=1, gain0=None, gain=None):
+    """gain0 / gain: a saturated case (make_case); its `seed` is the base the admission search counts up from"""
     n_out = 2 if kind == "schrodinger" else 1
     cid = "%s-%dx%d-f%d-u%d" % (kind, H, W, n_f, n_u) + ("-b%d" % n_b if n_b else "") + \
-          ("-lam%g_%g" % lam if lam else "")
+          ("-lam%g_%g" % lam if lam else "") + ("-gain0x%g" % gain0 if gain0 else "") + ("-gainx%g" % gain if gain else "")
     return {"id": cid, "family": family, "kind": kind, "layers": [2] + [W] * H + [n_out], "n_f": n_f, "n_u": n_u,
-            "n_b": n_b, "lam": lam, "seed": seed, "paths": paths, "drop": drop}
+            "n_b": n_b, "lam": lam, "seed": seed, "paths": paths, "drop": drop, "gain0": gain0, "gain": gain,
+            "sat": bool(gain0 or gain)}
 
 
 def _cases():
@@ -301,16 +327,71 @@ def _cases():
     return out
 
 
+# ---- saturated cases ----------------------------------------------------------------------------------------------
+# The cases above keep every hidden pre-activation below |z| ~ 1.3, where tanh is close to linear.  These put a share of
+# them into its tail (make_case: gain0, gain), on every path again.  How well such a net is conditioned varies a lot with the
+# draw (plain float32: 10 u ... 2400 u), so a draw is ADMITTED only if, in every dtype the case runs in,
+#   max |z| >= 5, at least 1 % of the hidden pre-activations beyond |z| = 3, a gain0 case at least one beyond 9.01 (where
+#   float32 tanh rounds to 1),
+#   its yardstick is at most 256 u (8 x FLOOR_ULPS),
+#   every mutant is at least 10 x its bound;
+# the seed is the first one from the case's base seed that is (first_admitted_seed: a function, never a hand-picked
+# number; its results are recorded in SAT_SEEDS at the end of this file), and it is written into the case id.
+# tests/test_grad_entries_host.py asserts all of it, the search included.
+SAT_MAX_Z, SAT_TAIL_Z, SAT_TAIL_SHARE, SAT_F32_ONE = 5.0, 3.0, 0.01, 9.01
+SAT_YARDSTICK_ULPS = 8 * FLOOR_ULPS
+SAT_MUTANT_MARGIN = 10.0
+SAT_SEARCH_SPAN = 64         # seeds tried before the search gives up (an error: the case as specified has no admissible draw)
+GAIN0 = 12.0
+
+
+def gain0_for(W):
+    """12 up to width 24.  Weights are drawn as 0.9 / sqrt(W), so at widths 65 and 100 a first layer times 12 stays below
+    |z| = 9.01 (64 draws each: none admitted, max |z| 5 ... 8); those take 12 sqrt(W / 20), a whole number: the first-layer
+    scale of the width-20 cases"""
+    return GAIN0 if W <= 24 else float(round(GAIN0 * np.sqrt(W / 20.0)))
+
+
+def _saturated_specs():
+    out, seed = [], 8000
+    nxt = lambda: seed + 100 * len(out)            # base seeds: the searches do not meet
+    w20 = {"f32": (2, 1, 0), "f64": (7, 1, 0)}
+    for H in (4, 8):
+        for n_u, n_f in ((3, 61), (61, 700)):
+            out.append(_case("w20", "burgers", 20, H, n_f, n_u, seed=nxt(), paths=w20, gain0=GAIN0))
+    out.append(_case("w20", "burgers", 20, 8, 700, 61, seed=nxt(), paths=w20, gain=3.0))
+    out.append(_case("w20", "burgers", 20, 10, 700, 61, seed=nxt(), paths={"f32": (2, 1, 0), "f64": (1, 0)}, gain0=GAIN0))
+    out.append(_case("w20", "burgers_ide", 20, 8, 0, 700, lam=(0.6, -4.5), seed=nxt(), paths=w20, gain0=GAIN0))
+    out.append(_case("w20", "burgers", 20, 8, 16300, 100, seed=nxt(), drop=64, paths={"f32": (2, 1, 0)}, gain0=GAIN0))
+    for opt in ({"gain": 3.0}, {"gain0": gain0_for(100)}):
+        out.append(_case("wide", "schrodinger", 100, 4, 333, 50, n_b=17, seed=nxt(),
+                         paths={"f32": (3, 4, 0), "f64": (8, 4, 0)}, **opt))
+    t16 = lambda W, H: {"f32": (4, 5, 6, 0), "f64": (8, 4, 5, 6, 0) if W >= 65 and H >= 2 else (4, 5, 6, 0)}
+    for W in (24, 65):
+        for opt in ({"gain": 2.5}, {"gain0": gain0_for(W)}):
+            out.append(_case("t16", "burgers", W, 3, 333, 17, seed=nxt(), paths=t16(W, 3), **opt))
+    for c in out:
+        assert "f64" not in c["paths"] or n_points(c) <= LONGDOUBLE_POINTS, c["id"]
+    return out
+
+
 def n_points(case):
     return case["n_f"] + case["n_u"] + 2 * case["n_b"]
 
 
-def make_case(kind, layers, n_f, n_u, n_b, lam, rs, lb=LB, ub=UB):
+def make_case(kind, layers, n_f, n_u, n_b, lam, rs, lb=LB, ub=UB, gain0=None, gain=None):
     """weights 0.9 / sqrt(max(W, 2)) N(0, 1), biases included, uniform points, N(0, 1) targets: as tests/test_gpu_fuzz.py
-    -> (w, sets)"""
+    -> (w, sets).  Two ways into the tail of tanh (the draws are the same with and without them):
+      gain0  W0 and b0 times gain0: sharp first-layer features, as at a shock (|z| up to 8 ... 15 in the first layer)
+      gain   every weight and bias times gain (2.5 ... 3: |z| up to 5 ... 8 in every layer; uniform gains much beyond 3,
+             or large biases alone, make the net ill-conditioned rather than saturated)"""
     W = layers[1]
     P = sum(a * b + b for a, b in zip(layers[:-1], layers[1:]))
     w = 0.9 / np.sqrt(max(W, 2)) * rs.standard_normal(P)
+    if gain:
+        w *= gain
+    if gain0:
+        w[:3 * W] *= gain0                                       # W0 [2, W] and b0 [W] lead the flat layout
     pts = lambda n: np.column_stack([rs.uniform(lb[0], ub[0], n), rs.uniform(lb[1], ub[1], n)])
     X_f, X_u = pts(n_f), pts(n_u)
     u = rs.standard_normal((n_u, layers[-1]))
@@ -331,7 +412,8 @@ assert len(CASE_BY_ID) == len(CASES)
 @functools.lru_cache(maxsize=None)
 def case_inputs(cid):
     c = CASE_BY_ID[cid]
-    return make_case(c["kind"], c["layers"], c["n_f"], c["n_u"], c["n_b"], c["lam"], np.random.RandomState(c["seed"]))
+    return make_case(c["kind"], c["layers"], c["n_f"], c["n_u"], c["n_b"], c["lam"], np.random.RandomState(c["seed"]),
+                     gain0=c["gain0"], gain=c["gain"])
 
 
 def wider(dtype):
@@ -375,13 +457,49 @@ def plain_error(cid, dtype_name):
     return dev_against_wide(g, gw, A, blocks(c["layers"], c["kind"]))[0]
 
 
-def yardstick(cid, dtype_name):
-    """max(plain_error, 32 u): what K multiplies"""
-    return max(plain_error(cid, dtype_name), FLOOR_ULPS * unit_roundoff(DTYPES[dtype_name]))
+@functools.lru_cache(maxsize=None)
+def formula_error(cid, dtype_name, formula):
+    """plain_error with tanh by one of the kernels' formulas ("r5", "bf": restate) instead of the library's"""
+    c = CASE_BY_ID[cid]
+    _, g, _ = _restate_case(c, DTYPES[dtype_name], tanh_formula=formula)
+    _, gw, A = _wide(cid, dtype_name)
+    return dev_against_wide(g, gw, A, blocks(c["layers"], c["kind"]))[0]
 
 
-def bound(cid, dtype_name):
-    return K[(CASE_BY_ID[cid]["family"], dtype_name)] * yardstick(cid, dtype_name)
+def formula_of(path, dtype_name):
+    """the tanh formula a saturated case judges a kernel path by: its own, not a kinder one.  k_fused20 (1) has tanh_bf in
+    both types (so path 1 is judged by "bf" in float64 as well: an extension of the float32-only rule for tanh_r5, which can
+    only raise that yardstick, never lower it); k_fused20m (2) and k_wide_* (3) have tanh_r5.  The others call the library,
+    or in float64 tanh_d (paths 7, 8, 4-6).  tanh_d has the quotient form too and is good to 1.48 u absolutely, not to the
+    library's 0.5 u, but the formula error is part of the yardstick in float32 only, so its paths are judged by plain tanh:
+    what the form costs on a unit that is saturated everywhere shows as a ratio, and is why K_SAT exists."""
+    if path == 1:
+        return "bf"
+    return "r5" if dtype_name == "f32" and path in (2, 3) else None
+
+
+def yardstick(cid, dtype_name, path=None):
+    """what the allowance multiplies: max(plain_error, 32 u).  A saturated case: max(plain_error, formula_error, 32 u) with
+    the formula of `path` (formula_of); without a path, the largest over the case's paths."""
+    c = CASE_BY_ID[cid]
+    y = max(plain_error(cid, dtype_name), FLOOR_ULPS * unit_roundoff(DTYPES[dtype_name]))
+    if c["sat"]:
+        for f in sorted({formula_of(p, dtype_name) for p in (c["paths"][dtype_name] if path is None else (path,))} - {None}):
+            y = max(y, formula_error(cid, dtype_name, f))
+    return y
+
+
+def allowance(cid, dtype_name):
+    """K of the case's family; a saturated case: K_SAT where the family has one.  It is keyed by family and dtype like K, so
+    K_SAT[("wide", "f64")] = 10 also covers path 0 (library tanh: 0.64 measured) and the x 3 case (0.61), which would pass
+    at K = 6: only paths 4 and 8 on the first-layer x 27 case need it."""
+    c = CASE_BY_ID[cid]
+    key = (c["family"], dtype_name)
+    return K_SAT.get(key, K[key]) if c["sat"] else K[key]
+
+
+def bound(cid, dtype_name, path=None):
+    return allowance(cid, dtype_name) * yardstick(cid, dtype_name, path)
 
 
 def family_of(path, layers, dtype_name):
@@ -453,3 +571,106 @@ def mutants(cid, dtype_name):
         d[-1] *= 1.01
         out["d"] = d
     return out
+
+
+# ---- admission of the saturated cases -----------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def preactivation_stats(cid, dtype_name):
+    """-> (max |z|, share of |z| > 3, number of |z| > 9.01) over every hidden pre-activation at every point of the case,
+    with the forward pass in `dtype_name`"""
+    c = CASE_BY_ID[cid]
+    dt = DTYPES[dtype_name]
+    w, sets = case_inputs(cid)
+    params = _unpack(np.asarray(w, dtype=np.float64), c["layers"], dt)
+    s = (2 / (UB - LB)).astype(dt)
+    zs = []
+    for key in ("X_f", "X_u", "X0", "X_lb", "X_ub"):
+        if key in sets and np.shape(sets[key])[0]:
+            h = s * (np.asarray(sets[key]).astype(dt) - LB.astype(dt)) - dt(1)
+            for W, b in params[:-1]:
+                z = h @ W + b
+                zs.append(np.abs(z).ravel())
+                h = np.tanh(z)
+    z = np.concatenate(zs).astype(np.float64)
+    return float(z.max()), float(np.mean(z > SAT_TAIL_Z)), int(np.sum(z > SAT_F32_ONE))
+
+
+def _dtypes_judged(c):
+    return [d for d in ("f32", "f64") if d in c["paths"] and (d == "f32" or longdouble_is_wider())]
+
+
+def refusal(cid):
+    """-> None if the (saturated) case meets the admission conditions in every dtype it runs in, else the first one it
+    misses, in words.  Cheapest conditions first.  (float64 is judged where np.longdouble is wider: elsewhere the float64
+    tests skip.)"""
+    c = CASE_BY_ID[cid]
+    for d in _dtypes_judged(c):
+        zmax, share, n_one = preactivation_stats(cid, d)
+        if zmax < SAT_MAX_Z or share < SAT_TAIL_SHARE:
+            return "%s: max |z| %.2f, %.2f %% beyond 3" % (d, zmax, 100 * share)
+        if c["gain0"] and n_one < 1:
+            return "%s: no |z| beyond %.2f" % (d, SAT_F32_ONE)
+    for d in _dtypes_judged(c):
+        u = unit_roundoff(DTYPES[d])
+        if yardstick(cid, d) > SAT_YARDSTICK_ULPS * u:
+            return "%s: yardstick %.0f u" % (d, yardstick(cid, d) / u)
+        _, ref, A = reference(cid, d)
+        layout = blocks(c["layers"], c["kind"])
+        for name, g in sorted(mutants(cid, d).items()):
+            dev = entry_dev(g, ref, A, layout)[0]
+            if not dev >= SAT_MUTANT_MARGIN * bound(cid, d):
+                return "%s: mutant %s is %.1f x the bound" % (d, name, dev / bound(cid, d))
+    return None
+
+
+@functools.lru_cache(maxsize=None)
+def first_admitted_seed(base_id):
+    """-> (seed, ((refused seed, why), ...)): the first seed from the base seed of the saturated case `base_id` that
+    refusal() lets through.  Run once per process; the candidates it refused leave CASE_BY_ID again.
+    The result depends on the host a little: float64 is judged only where np.longdouble is wider, and a draw next to a
+    threshold (one refused draw has a float32 yardstick of 258 u against the cap of 256 u) can fall on the other side
+    under a numpy whose float32 exp / tanh round differently.  Hence SAT_SEEDS below."""
+    spec = next(c for c in SAT_SPECS if c["id"] == base_id)
+    refused = []
+    for seed in range(spec["seed"], spec["seed"] + SAT_SEARCH_SPAN):
+        c = dict(spec, seed=seed, id="%s-s%d" % (base_id, seed), base_id=base_id)
+        listed = c["id"] in CASE_BY_ID
+        CASE_BY_ID.setdefault(c["id"], c)
+        why = refusal(c["id"])
+        if why is None:
+            if not listed:
+                del CASE_BY_ID[c["id"]]
+            return seed, tuple(refused)
+        if not listed:
+            del CASE_BY_ID[c["id"]]
+        refused.append((seed, why))
+    raise RuntimeError("%s: no admissible draw in %d seeds: %s" % (base_id, SAT_SEARCH_SPAN, refused))
+
+
+# What first_admitted_seed() returns for every saturated case.  The case ids are formed from this record, not from a search at
+# import, so that collecting a test file costs nothing (the search is 15 s and up to 25 draws a case), a search that fails
+# cannot take the other cases' collection with it, and the ids in profiles/grad_entries_measured.jsonl are the same on
+# every host.  It is a record, not a choice: tests/test_grad_entries_host.py runs the search and fails if any seed here
+# is not the one it finds (after a change to K_SAT, to a threshold or to make_case, run it and copy what it reports).
+SAT_SEEDS = {
+    "burgers-4x20-f61-u3-gain0x12": 8003,
+    "burgers-4x20-f700-u61-gain0x12": 8100,
+    "burgers-8x20-f61-u3-gain0x12": 8203,
+    "burgers-8x20-f700-u61-gain0x12": 8300,
+    "burgers-8x20-f700-u61-gainx3": 8402,
+    "burgers-10x20-f700-u61-gain0x12": 8503,
+    "burgers_ide-8x20-f0-u700-lam0.6_-4.5-gain0x12": 8600,
+    "burgers-8x20-f16300-u100-gain0x12": 8703,
+    "schrodinger-4x100-f333-u50-b17-gainx3": 8802,
+    "schrodinger-4x100-f333-u50-b17-gain0x27": 8909,
+    "burgers-3x24-f333-u17-gainx2.5": 9002,
+    "burgers-3x24-f333-u17-gain0x12": 9104,
+    "burgers-3x65-f333-u17-gainx2.5": 9224,
+    "burgers-3x65-f333-u17-gain0x22": 9320,
+}
+SAT_SPECS = _saturated_specs()
+assert [c["id"] for c in SAT_SPECS] == list(SAT_SEEDS)
+SAT_CASES = [dict(c, seed=SAT_SEEDS[c["id"]], id="%s-s%d" % (c["id"], SAT_SEEDS[c["id"]]), base_id=c["id"]) for c in SAT_SPECS]
+CASES = CASES + SAT_CASES
+CASE_BY_ID.update((c["id"], c) for c in SAT_CASES)
+assert len(CASE_BY_ID) == len(CASES)

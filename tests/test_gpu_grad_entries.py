@@ -2,7 +2,9 @@
 gradient entry on its own rounding scale A_i (tests/helpers/grad_entries.py), bound K[(family, dtype)] x max(plain error of
 the same width, 32 u).  The cases are the smallest that reach each code path: one partial tile, one ragged tile per
 workgroup, the tile loop's first launch (257 tiles), identification with lambda = (0.6, -4.5) and (0, -6), the Schrodinger
-net with 1 and 17 boundary pairs and over two chunks, the shape-generic sweeps at widths 1, 24, 65, 97, 128.  The global
+net with 1 and 17 boundary pairs and over two chunks, the shape-generic sweeps at widths 1, 24, 65, 97, 128 -- and, on the
+same paths, nets whose hidden pre-activations reach into the tail of tanh (ge.SAT_CASES: first layer times 12, or every
+weight times 2.5 ... 3; max |z| 5 ... 17, 1 ... 17 % beyond 3), each path judged by its own tanh formula.  The global
 criterion max|g - ref| / max|ref| stays asserted at the tolerances of tests/test_gpu_fuzz.py, next to the loss and
 run-to-run bit equality.  tests/test_grad_entries_host.py shows that the bounds used here reject a dropped point, a dropped
 boundary pair and 1 % on a small entry or on the lambda_2 entry."""
@@ -37,7 +39,7 @@ def test_gradient_entries_on_every_path(cid, dtype, record):
         pytest.skip("np.longdouble is no wider than float64 on this host: no reference for the float64 kernels")
     case = ge.CASE_BY_ID[cid]
     ref_loss, ref, A = ge.reference(cid, dtype)
-    plain, bound = ge.plain_error(cid, dtype), ge.bound(cid, dtype)
+    plain = ge.plain_error(cid, dtype)
     layout = ge.blocks(case["layers"], case["kind"])
     tl, tg = (1e-11, 1e-10) if dtype == "f64" else (2e-5, 5e-5)
     eng, w = engine_for(case, dtype)
@@ -49,9 +51,11 @@ def test_gradient_entries_on_every_path(cid, dtype, record):
         grad = np.array(grad, copy=True)
         dev, block, (row, col) = ge.entry_dev(grad, ref, A, layout)
         glob = np.max(np.abs(grad - ref)) / np.max(np.abs(ref))
-        ratio = dev / ge.yardstick(cid, dtype)
-        record(case=cid, dtype=dtype, path=path, entry_dev=dev, plain_error=plain, ratio=ratio, block=block, row=row,
-               col=col, glob=glob)
+        # a saturated case judges a path by its own tanh formula (ge.formula_of); the others have one yardstick
+        yard, bound = ge.yardstick(cid, dtype, path), ge.bound(cid, dtype, path)
+        ratio = dev / yard
+        record(case=cid, dtype=dtype, path=path, entry_dev=dev, plain_error=plain, yardstick=yard, ratio=ratio, block=block,
+               row=row, col=col, glob=glob)
         print("%s %s path %d: entry_dev %.3e at %s[%d,%d], plain %.3e, ratio %.2f, global %.3e"
               % (cid, dtype, path, dev, block, row, col, plain, ratio, glob))
         assert dev <= bound, "path %d: %s[%d,%d] is off by %.3e of its scale, bound %.3e (plain %s arithmetic: %.3e)" % (

@@ -101,7 +101,93 @@ def test_plain_floor_and_every_mutant_is_above_the_bound(cid, dtype):
     for name, g in sorted(found.items()):
         dev, block, rc = ge.entry_dev(g, ref, A, layout)
         assert dev > bound, "mutant %s (worst at %s%s: %.3e of its scale) passes the bound %.3e = K %g x %.3e" % (
-            name, block, rc, dev, bound, ge.K[(case["family"], dtype)], ge.yardstick(cid, dtype))
+            name, block, rc, dev, bound, ge.allowance(cid, dtype), ge.yardstick(cid, dtype))
+
+
+SAT_DTYPES = [(c["id"], d) for c in ge.SAT_CASES for d in ("f32", "f64") if d in c["paths"]]
+
+
+def test_the_saturated_cases_are_the_listed_ones_on_the_listed_paths():
+    """4x20 and 8x20 at (3, 61) and (61, 700), 8x20 with a uniform gain, 10x20, identification, the tile loop, the
+    Schrodinger net both ways, widths 24 and 65 both ways; none of them displaces a case from before"""
+    assert len(ge.SAT_CASES) == 14 and all(c["sat"] for c in ge.SAT_CASES)
+    assert [c for c in ge.CASES if not c["sat"]] == ge.CASES[:len(ge.CASES) - 14]
+    by = lambda fam: [c for c in ge.SAT_CASES if c["family"] == fam]
+    assert len(by("w20")) == 8 and len(by("wide")) == 2 and len(by("t16")) == 4
+    for c in by("w20"):
+        assert c["paths"]["f32"] == (2, 1, 0) and c["paths"].get("f64") in ((7, 1, 0), (1, 0), None)
+    assert [c["paths"] for c in by("wide")] == [{"f32": (3, 4, 0), "f64": (8, 4, 0)}] * 2
+    assert [c["paths"]["f64"][0] for c in by("t16")] == [4, 4, 8, 8]
+    assert sum(1 for c in ge.SAT_CASES if c["gain0"]) == 10 and sum(1 for c in ge.SAT_CASES if c["gain"]) == 4
+    assert all(bool(c["gain0"]) != bool(c["gain"]) for c in ge.SAT_CASES)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in ge.SAT_CASES])
+def test_saturated_seed_is_the_first_admitted_one(cid):
+    """the search, run here from the case's base seed, ends at the seed recorded in SAT_SEEDS (the one in the id); every
+    earlier seed was refused by refusal() with a reason; and the gains really reached the weights (the draws are those of
+    the ungained net).  A host without a wider longdouble judges float32 only and may admit an earlier draw."""
+    need_longdouble("f64")
+    case = ge.CASE_BY_ID[cid]
+    spec = next(c for c in ge.SAT_SPECS if c["id"] == case["base_id"])
+    seed, refused = ge.first_admitted_seed(case["base_id"])
+    assert seed == ge.SAT_SEEDS[case["base_id"]] == case["seed"], "the search finds %d (refused: %s)" % (seed, refused)
+    assert cid == "%s-s%d" % (case["base_id"], seed)
+    assert [s for s, _ in refused] == list(range(spec["seed"], seed)) and all(why for _, why in refused)
+    assert ge.refusal(cid) is None
+    assert set(ge.CASE_BY_ID) == {c["id"] for c in ge.CASES}                 # the refused candidates are gone again
+    w, _ = ge.case_inputs(cid)
+    w0, _ = ge.make_case(case["kind"], case["layers"], case["n_f"], case["n_u"], case["n_b"], case["lam"],
+                         np.random.RandomState(seed))
+    W = case["layers"][1]
+    g_first, g_rest = (case["gain0"] or 1.0) * (case["gain"] or 1.0), case["gain"] or 1.0
+    n_net = w.size - (2 if case["kind"] == "burgers_ide" else 0)
+    assert np.array_equal(w[:3 * W], g_first * w0[:3 * W]) and np.array_equal(w[3 * W:n_net], g_rest * w0[3 * W:n_net])
+    assert np.array_equal(w[n_net:], w0[n_net:])
+
+
+@pytest.mark.parametrize("cid,dtype", SAT_DTYPES)
+def test_saturated_case_meets_the_admission_conditions(cid, dtype):
+    """in the tail of tanh, well enough conditioned to be a yardstick, and with every mutant 10 x above the bound of
+    every path (the largest yardstick of the case's paths)"""
+    need_longdouble(dtype)
+    case = ge.CASE_BY_ID[cid]
+    u = ge.unit_roundoff(ge.DTYPES[dtype])
+    zmax, share, n_one = ge.preactivation_stats(cid, dtype)
+    print("%s %s: max|z| %.2f, %.2f %% beyond 3, %d beyond 9.01; plain %.0f u, yardsticks %s" % (
+        cid, dtype, zmax, 100 * share, n_one, ge.plain_error(cid, dtype) / u,
+        {p: round(ge.yardstick(cid, dtype, p) / u) for p in case["paths"][dtype]}))
+    assert zmax >= 5.0 and share >= 0.01
+    if case["gain0"]:
+        assert n_one >= 1
+    assert ge.yardstick(cid, dtype) <= 256 * u == 8 * ge.FLOOR_ULPS * u
+    for path in case["paths"][dtype]:
+        y = ge.yardstick(cid, dtype, path)
+        assert ge.FLOOR_ULPS * u <= y <= ge.yardstick(cid, dtype) and y >= ge.plain_error(cid, dtype)
+        f = ge.formula_of(path, dtype)
+        assert f == {(1, "f32"): "bf", (1, "f64"): "bf", (2, "f32"): "r5", (3, "f32"): "r5"}.get((path, dtype))
+        if f:
+            assert y >= ge.formula_error(cid, dtype, f)
+    _, ref, A = ge.reference(cid, dtype)
+    layout = ge.blocks(case["layers"], case["kind"])
+    for name, g in sorted(ge.mutants(cid, dtype).items()):
+        dev = ge.entry_dev(g, ref, A, layout)[0]
+        assert dev >= 10 * ge.bound(cid, dtype), (name, dev / ge.bound(cid, dtype))
+    assert ge.allowance(cid, dtype) >= ge.K[(case["family"], dtype)]        # K_SAT is an addition for these cases only
+
+
+def test_tanh_formulas_agree_with_tanh_and_differ_in_the_tail():
+    """the three forms of _tanh in float32 against float64 tanh on z = -12 ... 12: each within 4 u absolutely (r5: 1 + e
+    and the quotient near 2 round at 2 u), the quotient forms odd, and not all the same numbers"""
+    z = np.linspace(-12, 12, 4801).astype(np.float32)
+    ref = np.tanh(z.astype(np.float64))
+    got = {f: ge._tanh(z, f) for f in (False, "r5", "bf")}
+    assert got["r5"].dtype == np.float32 and np.array_equal(got["r5"], ge._tanh(z, True))
+    for f, a in got.items():
+        assert a.dtype == np.float32 and np.max(np.abs(a - ref)) <= 4 * ge.unit_roundoff(np.float32), f
+        assert np.all(np.abs(a) <= 1)
+    assert np.array_equal(got["bf"], -got["bf"][::-1]) and np.array_equal(got[False], -got[False][::-1])
+    assert not np.array_equal(got["r5"], got["bf"]) and not np.array_equal(got["bf"], got[False])
 
 
 def test_the_global_criterion_misses_a_lost_point_that_the_entrywise_one_finds():

@@ -374,16 +374,10 @@ static bool t16_bwd_on(const pinn_ctx* c) { return c->path == KP_T16 || c->path 
 //   widths <= 64, float32: few groups (<= 3 per CU: every group resident at once) -> weights straight from L2, three
 //     workgroups per CU; many groups -> weights staged in LDS, two workgroups per CU;
 //   widths <= 64, float64: weights from L2 (the LDS copy would leave room for one workgroup per CU only), two per CU;
-//   widths > 64: two per CU (float32: weights in LDS; float64: from L2, LDS is full).
-// widths above 64 in float32: 1 = the eight-wave variant with the weights read from L2 (as float64 does), 0 = round 2's
-// four waves with the layer's weights staged in LDS
-#ifndef T16_F32_WIDE8
-#define T16_F32_WIDE8 1
-#endif
-static constexpr bool T16_WIDE_F32_LDS = !T16_F32_WIDE8;
+//   widths > 64: the eight-wave variants, weights from L2, one workgroup per CU (float64: LDS is full; float32: round 2's
+//     four waves with the layer's weights staged in LDS, two per CU, were dropped for it).
 static bool t16_lds_weights(const pinn_ctx* c, int pts) {
-  if (c->nd.width > 64) return c->dtype != PINN_F64 && T16_WIDE_F32_LDS;
-  if (c->dtype == PINN_F64) return false;
+  if (c->nd.width > 64 || c->dtype == PINN_F64) return false;
   return pts / 16 > 3 * c->n_cu;
 }
 static int t16_wgs(const pinn_ctx* c, int pts) {
@@ -395,9 +389,8 @@ static int t16_wgs(const pinn_ctx* c, int pts) {
   const size_t rs = c->dtype == PINN_F64 ? 8 : 4;
   size_t lds;
   if (c->nd.width > 64) {
-    const bool wl = rs == 4 && T16_WIDE_F32_LDS;
-    lds = t16_fwd_lds<8>(rs, wl) > t16_bwd_lds<8>(rs, wl) ? t16_fwd_lds<8>(rs, wl) : t16_bwd_lds<8>(rs, wl);
-    if (!wl) per_cu = 1;                       // the eight-wave variants: one workgroup = two waves per SIMD
+    lds = t16_fwd_lds<8>(rs, false) > t16_bwd_lds<8>(rs, false) ? t16_fwd_lds<8>(rs, false) : t16_bwd_lds<8>(rs, false);
+    per_cu = 1;                                // the eight-wave variants: one workgroup = two waves per SIMD
   } else {
     const bool wl = t16_lds_weights(c, pts);
     lds = t16_fwd_lds<4>(rs, wl) > t16_bwd_lds<4>(rs, wl) ? t16_fwd_lds<4>(rs, wl) : t16_bwd_lds<4>(rs, wl);
@@ -611,11 +604,11 @@ static dim3 xg_grid(const pinn_ctx* c, int R, int n_slots = 0) {
 template <typename real>
 static int launch_reduce(pinn_ctx* c, int n_rows, const AdamFuse* af) {
   const TileScratch ts = tile_scratch(c);
-  const dim3 rgrid((c->R + RED_COLS - 1) / RED_COLS + (ts.gscr ? SLOT_SPLIT * ts.n_slots : 0));
+  const dim3 rgrid((c->R + RED_COLS - 1) / RED_COLS + (ts.gscr ? ts.n_slots : 0));
   if (c->xg.on) {   // rows -> vector -> every peer's mailbox -> sum over ranks (-> Adam), one launch
     if (++c->xg.seq == 0) c->xg.seq = 2;          // 32-bit wrap: skip 0, keep the parity alternating
     const unsigned int seq = c->xg.seq;
-    const dim3 xgrid = xg_grid(c, c->R, ts.gscr ? SLOT_SPLIT * ts.n_slots : 0);
+    const dim3 xgrid = xg_grid(c, c->R, ts.gscr ? ts.n_slots : 0);
     if (af)
       hipLaunchKernelGGL((k_reduce_xgmi<real, true>), xgrid, dim3(RED_THREADS), 0, c->stream, (const real*)c->part,
                          n_rows, c->R, c->gl, c->xg.peers, seq, XG_TIMEOUT_TICKS, c->xg.err, c->nd.n_theta, c->theta,
@@ -646,8 +639,8 @@ template <typename real, int NT, bool WLDS>
 static int t16_launch_fwd(pinn_ctx* c, const void* xs, const void* ts, int n_pad, int chunk, void* O, int base, int pts,
                           real lbx, real lbt, real sx, real st) {
   static unsigned long long attr = 0;
-  // eight waves per workgroup where LDS admits one workgroup per CU only (float64, widths above 64): two waves per SIMD
-  constexpr int NWV = (NT == 8 && !WLDS) ? T16_WIDE_WAVES : 4;
+  // eight waves per workgroup where LDS admits one workgroup per CU only (widths above 64): two waves per SIMD
+  constexpr int NWV = (NT == 8 && !WLDS) ? 8 : 4;
   const size_t lds = t16_fwd_lds<NT>(sizeof(real), WLDS, NWV);
   if (first_call_on_device(attr))
     HIPCHK(hipFuncSetAttribute((const void*)k_t16_fwd<real, NT, WLDS, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -660,7 +653,7 @@ static int t16_launch_fwd(pinn_ctx* c, const void* xs, const void* ts, int n_pad
 template <typename real, int NT, int PDE, bool WLDS>
 static int t16_launch_bwd(pinn_ctx* c, int base, int pts, real lbx, real lbt, real sx, real st, int accumulate) {
   static unsigned long long attr = 0;
-  constexpr int NWV = (NT == 8 && !WLDS) ? T16_WIDE_WAVES : 4;
+  constexpr int NWV = (NT == 8 && !WLDS) ? 8 : 4;
   const size_t lds = t16_bwd_lds<NT>(sizeof(real), WLDS);
   if (first_call_on_device(attr))
     HIPCHK(hipFuncSetAttribute((const void*)k_t16_bwd<real, NT, PDE, WLDS, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -678,9 +671,9 @@ static int t16_launch_bwd(pinn_ctx* c, int base, int pts, real lbx, real lbt, re
 template <typename real>
 static int t16_fwd(pinn_ctx* c, const void* xs, const void* ts, int n_pad, int chunk, void* O, int base, int pts,
                    real lbx, real lbt, real sx, real st) {
-  // widths up to 64: four feature tiles; up to 128: eight (in float64 the weights then stay in L2: LDS is full)
+  // widths up to 64: four feature tiles; up to 128: eight (the weights then stay in L2)
   if (c->nd.width > 64)
-    return t16_launch_fwd<real, 8, sizeof(real) == 4 && T16_WIDE_F32_LDS>(c, xs, ts, n_pad, chunk, O, base, pts, lbx, lbt, sx, st);
+    return t16_launch_fwd<real, 8, false>(c, xs, ts, n_pad, chunk, O, base, pts, lbx, lbt, sx, st);
   if (!t16_lds_weights(c, pts))
     return t16_launch_fwd<real, 4, false>(c, xs, ts, n_pad, chunk, O, base, pts, lbx, lbt, sx, st);
   return t16_launch_fwd<real, 4, true>(c, xs, ts, n_pad, chunk, O, base, pts, lbx, lbt, sx, st);
@@ -702,7 +695,7 @@ static int forward_chunk(pinn_ctx* c, const void* xs, const void* ts, int n_pad,
 template <typename real, int PDE>
 static int t16_bwd(pinn_ctx* c, int base, int pts, real lbx, real lbt, real sx, real st, int accumulate) {
   if (c->nd.width > 64)
-    return t16_launch_bwd<real, 8, PDE, sizeof(real) == 4 && T16_WIDE_F32_LDS>(c, base, pts, lbx, lbt, sx, st, accumulate);
+    return t16_launch_bwd<real, 8, PDE, false>(c, base, pts, lbx, lbt, sx, st, accumulate);
   if (!t16_lds_weights(c, pts))
     return t16_launch_bwd<real, 4, PDE, false>(c, base, pts, lbx, lbt, sx, st, accumulate);
   return t16_launch_bwd<real, 4, PDE, true>(c, base, pts, lbx, lbt, sx, st, accumulate);

@@ -21,7 +21,7 @@
 // round 6 that move is ONE matrix instruction with the 4 x 4 identity as B -- it swaps the slot field with the two LOW
 // point bits (PINN_TO_POINTS below; rounds 2-5: a ds_bpermute pair per value, 642 per tile on the LDS pipe), 40 values
 // per layer.  The four blocks then hold partial sums over the points with the same HIGH point bits.
-//   tile loop (more tiles than workgroups): the blocks are folded with two DPP row rotations and added into a per-wave
+//   tile loop (more tiles than workgroups): the blocks are folded with a DPP row rotation and added (ds_add_f64) into a per-wave
 //     accumulator in LDS (221 blocks x 16 values = 28 KB per wave, persistent over the workgroup's tiles; summed over the
 //     four waves in fixed order at the end);
 //   one tile per workgroup: nothing is accumulated -- every lane parks its partial in a double-buffered staging area and
@@ -44,36 +44,38 @@
 #include "kernels_fused20.h"
 #include "fused20d_api.h"
 
-// 1: the tile loop re-reads the lane index through an opaque asm once per tile (what stopped the address hoisting of
-// k_wide_bwd / k_t16_fused).  Here it takes the tile-loop variants from 256 VGPRs + 6-11 AGPR spill slots to 238-242 / 0
-// and is 1 % SLOWER (same-box A/B, N_f = 10^6: 1991 / 2000 vs 1971 / 1978 us per Adam step): off.
-#ifndef PINN_PATTERN_AHEAD
-#define PINN_PATTERN_AHEAD 1     // the GEMV loops pinned step by step (sched_barrier), weight patterns requested in pairs two
-                                 // steps ahead (0: hipcc's placement -- it sinks every ds_read next to its consumer).  Round 4:
-                                 // 40.8 -> 40.5 us per Adam step at N_f = 10^4, and 1.6 % SLOWER in the tile-loop variants
-                                 // (PINN_PA_LOOP below turned that round 6)
-#endif
-#ifndef PINN_ROT_IN_GEMV
-#define PINN_ROT_IN_GEMV 2       // where a reverse layer's 40 operand moves (PINN_TO_POINTS) and the one-tile phase sum stand:
-                                 //  0  moves in front of the sum, the whole sum in front of the GEMV
-                                 //  1  moves inside the GEMV (one per pinned step), barrier + reads in front of it, adds behind
-                                 //  2  as 1, barrier + reads in front of the adjoint arithmetic (pure VALU) as well
-                                 // same-box: 36.9 / 35.6 / 35.0 us with the ds_bpermute moves (profiles/r06_ab_onetile_v3, _v4)
-#endif
 #ifndef PINN_FOLD_STAGES
 #define PINN_FOLD_STAGES 1       // tile loop: DPP fold stages in front of the ds_add_f64.  1 = the blocks are folded once (b with
                                  // b ^ 2) and the lanes of blocks 0 and 1 add into the accumulator -- two lanes per address in one
                                  // LDS instruction (resolved in lane order: run-to-run bit equality is asserted by the tile-loop
-                                 // tests).  Same box, N_f = 10^6: 2 stages 1778 us, 1 stage 1738 us, 0 stages (four lanes per
-                                 // address) 2110 us (profiles/r06_ab_foldstages.txt)
+                                 // tests).  2 = folded twice, the lanes of block 0 add: one adder per address, deterministic by
+                                 // construction.  Same box, N_f = 10^6: 2 stages 1778 us, 1 stage 1738 us
+                                 // (profiles/r06_ab_foldstages.txt)
 #endif
 #ifndef PINN_GACC_ATOMIC
-#define PINN_GACC_ATOMIC 1       // tile loop: gradient accumulators updated by ds_add_f64 from the lanes of block 0 (0: read-add-write)
+#define PINN_GACC_ATOMIC 1       // tile loop: gradient accumulators updated by ds_add_f64 (0: read-add-write, the old value fetched by
+                                 // grad_fetch ahead of the matrix instructions; profiles/r06_ab_gacc_atomic.txt).  Settled, and
+                                 // kept whole all the same: without the `old` values handed to grad_store (zeros in this
+                                 // setting) six one-tile kernels of the -DPINN_ONETILE_SUM=2 build, which a test compares bit
+                                 // for bit, come out with another schedule (profiles/retire_switches_device_code.txt)
 #endif
-#ifndef PINN_PA_LOOP
-#define PINN_PA_LOOP 1           // the pinned GEMV loops in the tile-loop variants too: N_f = 10^6 1868 -> 1851 us, same box
-                                 // (profiles/r06_ab_loopvariants.txt; with the ds_bpermute rotations of rounds 2-5 this was a loss)
-#endif
+static_assert(PINN_FOLD_STAGES == 1 || PINN_FOLD_STAGES == 2, "PINN_FOLD_STAGES: 1 (product) or 2; the unfolded form is retired");
+// Tried and dropped (one line each; the arms were in the sources up to 7a77e26, profiles/retire_switches_device_code.txt):
+//   GEMV loops left to hipcc's placement (it sinks every ds_read next to its consumer) instead of pinned step by step with
+//     the weight patterns requested two steps ahead: round 4 40.8 -> 40.5 us per Adam step at N_f = 10^4 for the pinned form;
+//     in the tile-loop variants N_f = 10^6 1868 -> 1851 us since round 6 (profiles/r06_ab_loopvariants.txt; with the
+//     ds_bpermute moves of rounds 2-5 it was a 1.6 % loss there)
+//   a reverse layer's 40 operand moves and the whole one-tile phase sum in front of the GEMV (36.9 us), or the moves inside
+//     the GEMV with barrier + reads in front of it and the adds behind it (35.6 us), against the order below (35.0 us)
+//     (profiles/r06_ab_onetile_v3, _v4)
+//   tile loop: no DPP fold in front of the ds_add_f64 (four lanes per address): 2110 us against 1738
+//     (profiles/r06_ab_foldstages.txt)
+//   the operand move as a ds_bpermute pair instead of the identity-B matrix instruction (rounds 2-5; profiles/r06_ab_rotmfma.txt)
+//   the tile loop re-reading the lane index through an opaque asm once per tile (what stopped the address hoisting of
+//     k_wide_bwd / k_t16_fused): 256 VGPRs + 6-11 AGPR spill slots -> 238-242 / 0 and 1 % SLOWER (same-box A/B, N_f = 10^6:
+//     1991 / 2000 vs 1971 / 1978 us per Adam step, profiles/r04_opaque_lane_ab.txt)
+//   the four waves of a workgroup started w x 640 cycles apart (s_sleep), so that they do not meet at the LDS pipe: with the
+//     per-phase barriers 36.6 -> 37.0 us (profiles/r06_ab_stagger.txt)
 // PINN_ONETILE_SUM (defined in fused20d_api.h: it sizes the staging area): how a one-tile launch adds the four blocks and the
 // four waves of a gradient entry
 //  0  (default) every lane parks its unfolded partial, 30 x 64 doubles per wave and phase; the workgroup adds 4 waves x 4
@@ -90,9 +92,6 @@
                                  // reduction behind it otherwise waits for.  Same values; measured against the parent's plain
                                  // stores in profiles/onetile_fold_ab.txt section 2.  0: plain stores
 #endif
-#ifndef PINN_OPAQUE_TILE_D
-#define PINN_OPAQUE_TILE_D 0
-#endif
 
 // finer timeline inside reverse layer 4 and forward layer 4 (slots 20..30 of the wave's 32), profiling build -DPINN_STAMPS2 only
 #if defined(PINN_STAMPS) && defined(PINN_STAMPS2)
@@ -104,8 +103,9 @@
 namespace pinn {
 
 // (Ablation builds -- one ingredient compiled out at a time, wrong results by construction, only times are read -- are not part
-// of the product sources since round 5: `git apply -R profiles/ablation_scaffolding.patch` puts the -DPINN_ABL / -DPINN_ABLD /
-// -DT16_ABL switches back for profiles/ablate_*.py; their results are under profiles/*ablate*.txt.)
+// of the product sources since round 5.  profiles/ablation_scaffolding.patch holds the -DPINN_ABL / -DPINN_ABLD / -DT16_ABL
+// switches of profiles/ablate_*.py; it is not kept up with these sources: it reverse-applies to the tree at ee3788e; check that
+// commit out for the ablation builds.  Their results are under profiles/*ablate*.txt.)
 
 // a double parked in the accumulation half of the register file (two 32-bit AGPRs)
 struct agd { int lo, hi; };
@@ -140,13 +140,6 @@ __device__ __forceinline__ double mfma444(const double a, const double b, const 
   return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
 }
 
-// value of lane (src4 >> 2) -- any permutation of the wave, 2 x ds_bpermute_b32
-__device__ __forceinline__ double lane_fetch(const double x, const int src4) {
-  const int lo = __builtin_amdgcn_ds_bpermute(src4, __double2loint(x));
-  const int hi = __builtin_amdgcn_ds_bpermute(src4, __double2hiint(x));
-  return __hiloint2double(hi, lo);
-}
-
 constexpr int DPP_ROW_ROR4 = 0x124, DPP_ROW_ROR8 = 0x128;
 
 // The weight-gradient blocks contract over POINTS, so both their operands need the point index where the matrix instruction
@@ -158,11 +151,9 @@ constexpr int DPP_ROW_ROR4 = 0x124, DPP_ROW_ROR8 = 0x128;
 // i.e. the slot field and the low two point bits of the lane index change places inside every block -- exactly a valid
 // operand layout for the gradient blocks (contraction over the low point bits, one block per high-point-bit value; both
 // operands and the "ones" / (hx, ht, 1) patterns of the bias and first-layer blocks use the same convention).  Products
-// with 1.0 and sums with zeros are exact, so the moved value is bit-identical to the bpermute's.  One instruction of the
-// matrix pipe (16 cycles, no LDS round trip, no address register) instead of two of the LDS pipe.
-#ifndef PINN_ROT_MFMA
-#define PINN_ROT_MFMA 1          // 0: the ds_bpermute pair
-#endif
+// with 1.0 and sums with zeros are exact, so a FINITE moved value is bit-identical to the lane copy's, except that -0.0
+// arrives as +0.0 (-0.0 + 0.0); an Inf or NaN in one lane becomes NaN in the other three lanes of its group (Inf x 0).  One
+// instruction of the matrix pipe (16 cycles, no LDS round trip, no address register) instead of two of the LDS pipe.
 
 // tanh(x) = sign(x) (1 - t) / (1 + t), t = e^{-2|x|}: the denominator lies in (1, 2], so the quotient needs none of
 // the scaling / fix-up of an IEEE division: v_rcp_f64 seed + two Newton steps (relative error < 1e-30 before the
@@ -244,7 +235,6 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
   constexpr W20Desc nd_const = w20_desc(H, PDE == 1);
   const W20Desc nd = ONE_TILE ? nd_const : nd_arg;
   constexpr int NBLK = fused20d_blocks(H);
-  constexpr bool PA = PINN_PATTERN_AHEAD && (ONE_TILE || PINN_PA_LOOP);   // the pinned GEMV loops (patterns two steps ahead)
   constexpr int BLK_H = 5 + (H - 1) * 30;            // first block of dense H
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   double* const wl = reinterpret_cast<double*>(lds_raw);
@@ -260,16 +250,12 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
   double* const gacc_all = wl + nwp;                  // tile loop: 4 x NBLK x 16 accumulators; one tile: 2 staging buffers
   double* const lacc_all = gacc_all + (ONE_TILE ? fused20d_stage_doubles(H) : 4 * NBLK * 16);
 
-#if PINN_ROT_MFMA
 #define PINN_TO_POINTS(X) mfma444((X), ident, 0.0)
-#else
-#define PINN_TO_POINTS(X) lane_fetch((X), rot4)
-#endif
   STAMP(0);
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // per-lane indices as a macro: the tile loop re-derives them from an opaque copy of the lane index once per tile
-  // (PINN_OPAQUE_LANE), so that hipcc does not carry the ~30 per-lane LDS addresses they feed across the loop
+  // per-lane indices as a macro: derived here for the prologue and the epilogue, and again inside the tile loop (declared
+  // once in front of the loop instead, the same values, all 48 instantiations come out with another schedule)
 #define PINN_LANE_INDICES(L)                                                                                          \
   const int lane = (L);                                                                                                \
   const int q = lane & 15;                 /* point of this wave's 16 */                                              \
@@ -277,13 +263,12 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
   const int i4 = lane & 3;                 /* row / column slot of the A patterns and of the gradient blocks */       \
   const int pf = s * FW + i4;              /* forward pattern:  W[4m + s][4n + i4] */                                 \
   const int pr = i4 * FW + s;              /* reverse pattern:  W[4m + i4][4n + s] */                                 \
-  const int rot4 = (((lane >> 2) | (lane << 4)) & 63) << 2;   /* lane-index rotation by two bits (bpermute address) */ \
   const double ident = s == i4 ? 1.0 : 0.0;                    /* 4 x 4 identity as a B operand: the transposing matrix instruction */ \
   const int ge = s * 4 + i4;               /* this lane's entry (i, j) of a gradient block */                         \
   double* const lacc = lacc_all + wave * 256 + lane;                        /* [k * 64]: l_res, l_dat, dl0, dl1 */     \
   const int sput = (s * 4 + i4) * 4 + ((lane >> 2) & 3);   /* one-tile staging slot: entry-major, the four blocks of an entry adjacent */ \
   const double onesA = i4 == 0 ? 1.0 : 0.0;                     /* rotated "ones" in-group: row 0 = 1 (bias gradients) */ \
-  (void)q; (void)pf; (void)pr; (void)rot4; (void)ident; (void)ge; (void)lacc; (void)onesA; (void)s; (void)sput
+  (void)q; (void)pf; (void)pr; (void)ident; (void)ge; (void)lacc; (void)onesA; (void)s; (void)sput
   PINN_LANE_INDICES(tid & 63);
   double* const gacc = gacc_all + wave * (NBLK * 16);
 
@@ -338,27 +323,17 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
   // slots per lane behind the gradient accumulators: one read-modify-write per tile instead of eight registers held
   // across the whole kernel (which cost the identification variant 20 B of scratch per lane)
 
-  // Gradient blocks.  D = this lane's partial sum over the four points of its block b; the four blocks of an entry
-  // are folded with two DPP row rotations -- commutative, so the four lanes of an entry end with bit-identical
-  // totals and may all store (same value, same address: no exec masking, no branch).  The old accumulator values
-  // are fetched BEFORE the matrix instructions that produce D (grad_fetch), so no LDS round trip is exposed.
-  // (Tried: ds_add_f64 with the four lanes of an entry hitting one address, no fold, no read-modify-write --
+  // Gradient blocks.  D = this lane's partial sum over the four points of its block b.  Tile loop: the four blocks of an
+  // entry are folded with DPP row rotations and added into the wave's accumulator by ds_add_f64 (grad_store / gacc_flush
+  // below; PINN_GACC_ATOMIC = 0: the old accumulator values are fetched BEFORE the matrix instructions that produce D,
+  // grad_fetch, and old + D is written back).  One tile: parked, and summed by the whole workgroup (phase_issue / phase_finish).
+  // (Tried in round 2: ds_add_f64 with the four lanes of an entry hitting one address, no fold, no read-modify-write --
   //  221 instructions instead of ~3000, bit-reproducible over 200 runs, and 14 % SLOWER: 49.8 vs 43.7 us per step.)
 
   STAMP(1);
-#ifdef PINN_STAGGER
-  // experiment: the four waves of a workgroup run the same instruction stream in step and meet at the LDS pipe; wave w starts
-  // w x PINN_STAGGER x 64 cycles late
-  if (wave == 1) __builtin_amdgcn_s_sleep(PINN_STAGGER);
-  if (wave == 2) { __builtin_amdgcn_s_sleep(PINN_STAGGER); __builtin_amdgcn_s_sleep(PINN_STAGGER); }
-  if (wave == 3) { __builtin_amdgcn_s_sleep(PINN_STAGGER); __builtin_amdgcn_s_sleep(PINN_STAGGER); __builtin_amdgcn_s_sleep(PINN_STAGGER); }
-#endif
 
   for (; tile < n_tiles; tile += gridDim.x) {
-    // (PINN_OPAQUE_TILE_D, off by default: see the macro)
-    int lane_o = tid & 63;
-    if (!ONE_TILE && PINN_OPAQUE_TILE_D) asm volatile("" : "+v"(lane_o));
-    PINN_LANE_INDICES(lane_o);
+    PINN_LANE_INDICES(tid & 63);
     auto grad_fetch = [&](const int blk) { return (ONE_TILE || PINN_GACC_ATOMIC) ? 0.0 : gacc[blk * 16 + ge]; };
     // One tile per workgroup: nothing is accumulated, so the four blocks are not folded in registers (2 x 2 DPP moves + 2
     // adds per block, 1 300 instructions per tile): every lane parks its own partial in the phase's staging buffer
@@ -375,14 +350,14 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
 #define PINN_PHASE_STAGE(P) ((P) & 1) * FUSED20D_STAGE_BUF
 #endif
     double* stage_w = gacc_all + wave * STAGE_WAVE_STRIDE;
-    // Tile loop (PINN_GACC_ATOMIC): the folded total sits in all four lanes of an entry; the lanes of block 0 add it into the
-    // wave's accumulator with ONE ds_add_f64 (16 distinct addresses, one adder per address and tile: no conflict,
-    // bit-reproducible) instead of a ds_read of the old value long before, a v_add_f64 and a ds_write.  A group's stores
-    // share one hand-set execution-mask region: as `if (block 0) atomic` every store became its own basic block (two scalar
+    // Tile loop (PINN_GACC_ATOMIC): after PINN_FOLD_STAGES DPP folds the lanes of blocks 0 and 1 (one fold: two lanes per address, resolved in
+    // lane order) or of block 0 (two folds: one adder per address and tile) add the total into the wave's accumulator with
+    // ONE ds_add_f64.  A group's stores share one hand-set execution-mask region: as `if (block 0) atomic` every store became its own basic block (two scalar
     // instructions each, and the stash reads the compiler shares between a layer's rotated inputs and the next layer's
     // adjoints were issued twice: 9 233 -> 9 766 instructions).  LDS operations the compiler does not see only make its own
     // lgkmcnt waits conservative (the queue is in order).  (The UNFOLDED form -- four lanes per address -- was 14 % slower
     // in round 2; this one follows the fold.)
+    constexpr unsigned long long FOLD_LANES = PINN_FOLD_STAGES == 2 ? 0x000f000f000f000full : 0x00ff00ff00ff00ffull;
     double pend_D[6] = {0, 0, 0, 0, 0, 0};
     int pend_off[6] = {0, 0, 0, 0, 0, 0}, pend_n = 0;
     auto gacc_flush = [&]() {
@@ -397,7 +372,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
                        "ds_add_f64 %[a], %[d4] offset:%[o4]\n\tds_add_f64 %[a], %[d5] offset:%[o5]\n\t"
                        "s_mov_b64 exec, %[sv]"
                        : [sv] "=&s"(saved)
-                       : [a] "v"(addr), [mk] "s"(PINN_FOLD_STAGES == 2 ? 0x000f000f000f000full : PINN_FOLD_STAGES == 1 ? 0x00ff00ff00ff00ffull : 0xffffffffffffffffull), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
+                       : [a] "v"(addr), [mk] "s"(FOLD_LANES), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
                          [d2] "v"(pend_D[2]), [d3] "v"(pend_D[3]), [d4] "v"(pend_D[4]), [d5] "v"(pend_D[5]),
                          [o0] "i"(pend_off[0]), [o1] "i"(pend_off[1]), [o2] "i"(pend_off[2]), [o3] "i"(pend_off[3]),
                          [o4] "i"(pend_off[4]), [o5] "i"(pend_off[5])
@@ -409,7 +384,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
                        "ds_add_f64 %[a], %[d4] offset:%[o4]\n\t"
                        "s_mov_b64 exec, %[sv]"
                        : [sv] "=&s"(saved)
-                       : [a] "v"(addr), [mk] "s"(PINN_FOLD_STAGES == 2 ? 0x000f000f000f000full : PINN_FOLD_STAGES == 1 ? 0x00ff00ff00ff00ffull : 0xffffffffffffffffull), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
+                       : [a] "v"(addr), [mk] "s"(FOLD_LANES), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
                          [d2] "v"(pend_D[2]), [d3] "v"(pend_D[3]), [d4] "v"(pend_D[4]),
                          [o0] "i"(pend_off[0]), [o1] "i"(pend_off[1]), [o2] "i"(pend_off[2]), [o3] "i"(pend_off[3]),
                          [o4] "i"(pend_off[4])
@@ -460,16 +435,13 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
 #else
       if (ONE_TILE) { stage_w[(blk - phase_first) * 64 + sput] = D; return; }
 #endif
-#if PINN_GACC_ATOMIC && PINN_FOLD_STAGES < 2
-      if (PINN_FOLD_STAGES == 1) D += dpp_mov<DPP_ROW_ROR8>(D);       // the LDS adder does the rest of the fold
-#else
       D += dpp_mov<DPP_ROW_ROR8>(D);
-      D += dpp_mov<DPP_ROW_ROR4>(D);
-#endif
 #if PINN_GACC_ATOMIC
+      if (PINN_FOLD_STAGES == 2) D += dpp_mov<DPP_ROW_ROR4>(D);       // (1: the LDS adder does the rest of the fold)
       pend_D[pend_n] = D; pend_off[pend_n] = blk * 128; ++pend_n;      // added by gacc_flush below, one execution-mask region per group
       (void)old;
 #else
+      D += dpp_mov<DPP_ROW_ROR4>(D);
       gacc[blk * 16 + ge] = old + D;
 #endif
     };
@@ -597,7 +569,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
       // consume them (sched_barrier pins the order).  Left to itself hipcc sinks every ds_read next to its consumer --
       // `ds_read2_b64; s_waitcnt lgkmcnt(0); v_mfma` 259 times per tile (round-4 ISA count) -- and a lone wave then
       // sits out the LDS latency in front of each group of matrix instructions.
-      if constexpr (PA) {
+      {
         // (requested in PAIRS -- steps t + 2 and t + 3 at every even t -- so that two patterns travel in one ds_read2_b64:
         //  13 LDS instructions per GEMV instead of 25)
         auto fpat = [&](const int t) { return wd[80 * (t % 5) + 4 * (t / 5)]; };
@@ -614,16 +586,6 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
 #pragma unroll
           for (int c = 0; c < 4; ++c) acc[c][n] = mfma444(A, in[c][m], acc[c][n]);
           __builtin_amdgcn_sched_barrier(0);
-        }
-      } else {
-#pragma unroll
-        for (int n = 0; n < 5; ++n) {
-#pragma unroll
-          for (int m = 0; m < 5; ++m) {
-            const double A = wd[80 * m + 4 * n];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[c][n] = mfma444(A, in[c][m], acc[c][n]);
-          }
         }
       }
       STAMP2(d == 4, 29);
@@ -757,43 +719,36 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
     STAMP(H + 1);
 #pragma unroll
     for (int d = H - 1; d >= 1; --d) {
-      // pre-activation adjoints of layer d, and their point-major (rotated) copies for the weight gradient
+      // pre-activation adjoints of layer d; their point-major (moved) copies for the weight gradient are made inside the GEMV.
+      // One tile: the barrier and the 16 reads of the previous phase's sum stand in front of the adjoint arithmetic (pure
+      // VALU), which hides their LDS round trip.
       double zb[4][5], zbT[4][5];
-      if constexpr (ONE_TILE && PA && PINN_ROT_IN_GEMV == 2)
-        phase_issue(d == H - 1 ? 6 * 16 : 30 * 16, H - d - 1);
+      if constexpr (ONE_TILE) phase_issue(d == H - 1 ? 6 * 16 : 30 * 16, H - d - 1);
 #pragma unroll
       for (int n = 0; n < 5; ++n) {
         double a, zp, zq, zr;
         if (d == H - 1) { a = top[n][0]; zp = top[n][1]; zq = top[n][2]; zr = top[n][3]; }
         else { a = agd_get(stash[d][n][0]); zp = agd_get(stash[d][n][1]); zq = agd_get(stash[d][n][2]); zr = agd_get(stash[d][n][3]); }
         preact_adjoint_d(a, zp, zq, zr, ob[0][n], ob[1][n], ob[2][n], ob[3][n], zb[0][n], zb[1][n], zb[2][n], zb[3][n]);
-        if constexpr (!(PA && PINN_ROT_IN_GEMV)) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) zbT[c][n] = PINN_TO_POINTS(zb[c][n]);
-        }
       }
       STAMP2(d == 4, 20);
       // One tile: the phase before this one is summed HERE, not where its last block was parked -- the stash entries of
       // layer d, read a first time for that phase's rotated inputs, are still in registers for the adjoints above (a
       // barrier in between would end their basic block and cost a second v_accvgpr_read each).
-      // The LDS pipe is the second bottleneck of this kernel (a ds_bpermute costs a wave ~31 cycles of it with four waves
-      // on the CU, a ds_read_b128 ~53: profiles/r01_ubench_lds_rates.txt, r06_stamps2_new.txt), and it runs beside the
-      // matrix pipe: the barrier and the 16 reads of the sum go in front of the reverse GEMV, this layer's 40 lane rotations
-      // -- needed only by the weight-gradient blocks behind the GEMV -- are issued two per GEMV step, and the adds and
-      // stores of the sum follow the GEMV.
+      // The LDS pipe is the second bottleneck of this kernel (a ds_read_b128 costs a wave ~53 cycles of it with four waves on
+      // the CU: profiles/r01_ubench_lds_rates.txt, r06_stamps2_new.txt), and it runs beside the matrix pipe: the adds and
+      // stores of the sum stand in front of the reverse GEMV, and this layer's 40 operand moves -- needed only by the
+      // weight-gradient blocks behind the GEMV -- are issued one per pinned GEMV step.
+      // (finish_prev stays a lambda: written out in place, the one-tile instantiations come out 14-19 instructions longer)
       auto finish_prev = [&]() {
         if (d == H - 1) phase_finish(6 * 16, idx_dense_h);
         else phase_finish(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[d + 1] + rel_hidden[k]; });
       };
-      if constexpr (ONE_TILE) {
-        if (!(PA && PINN_ROT_IN_GEMV == 2)) phase_issue(d == H - 1 ? 6 * 16 : 30 * 16, H - d - 1);
-        if (!(PA && PINN_ROT_IN_GEMV == 1)) finish_prev();
-      }
+      if constexpr (ONE_TILE) finish_prev();
       STAMP2(d == 4, 21);
-      // the first in-group's inputs of the weight-gradient blocks: formed here, rotated in the last steps of the GEMV
-      constexpr bool ROT_FIRST = PA && PINN_ROT_IN_GEMV;
+      // the first in-group's inputs of the weight-gradient blocks: formed here, moved in the last steps of the GEMV
       double cur[4] = {0.0, 0.0, 0.0, 0.0}, first_nat[4] = {0.0, 0.0, 0.0, 0.0};
-      if constexpr (ROT_FIRST) {
+      {
         double a_, zp_, zq_, zr_;
         if (d - 1 == 0) {
           a_ = a0[0]; zp_ = sx * wl[nd.off_w[0] + s]; zq_ = st * wl[nd.off_w[0] + FW + s]; zr_ = 0.0;
@@ -809,7 +764,7 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
       for (int m = 0; m < 5; ++m) {
         ob[0][m] = ob[1][m] = ob[2][m] = ob[3][m] = 0.0;
       }
-      if constexpr (PA) {
+      {
         auto rpat = [&](const int t) { return wd[80 * (t / 5) + 4 * (t % 5)]; };
         double Aq[4] = {rpat(0), rpat(1), 0.0, 0.0};
 #pragma unroll
@@ -820,25 +775,14 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
             if (t + 2 < 25) Aq[(t + 2) & 3] = rpat(t + 2);
             if (t + 3 < 25) Aq[(t + 3) & 3] = rpat(t + 3);
           }
-          if (PINN_ROT_IN_GEMV && t < 20) zbT[t / 5][t % 5] = PINN_TO_POINTS(zb[t / 5][t % 5]);   // one rotation (two ds_bpermute) per step
-          if (PINN_ROT_IN_GEMV && t >= 20 && t < 24) cur[t - 20] = PINN_TO_POINTS(first_nat[t - 20]);
+          if (t < 20) zbT[t / 5][t % 5] = PINN_TO_POINTS(zb[t / 5][t % 5]);   // one operand move per step
+          if (t >= 20 && t < 24) cur[t - 20] = PINN_TO_POINTS(first_nat[t - 20]);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int c = 0; c < 4; ++c) ob[c][m] = mfma444(A, zb[c][n], ob[c][m]);
           __builtin_amdgcn_sched_barrier(0);
         }
-      } else {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) {
-#pragma unroll
-          for (int n = 0; n < 5; ++n) {
-            const double A = wd[80 * m + 4 * n];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) ob[c][m] = mfma444(A, zb[c][n], ob[c][m]);
-          }
-        }
       }
-      if constexpr (ONE_TILE && PA && PINN_ROT_IN_GEMV == 1) finish_prev();
       STAMP2(d == 4, 22);
       // dW_d[4m + i][4n + j]: the A operands are the layer-(d-1) output channels, rotated -- produced one in-group
       // ahead of the matrix instructions that consume them (20 values live instead of 40: the kernel sits at the
@@ -861,7 +805,6 @@ __global__ __launch_bounds__(256) void k_fused20d(const double* __restrict__ th,
     O4[0] = PINN_TO_POINTS(h_); O4[1] = PINN_TO_POINTS(p_);                                             \
     O4[2] = PINN_TO_POINTS(q_); O4[3] = PINN_TO_POINTS(r_);                                             \
   } while (0)
-      if constexpr (!ROT_FIRST) PINN_ROTATED_INPUTS(0, cur);
 #pragma unroll
       for (int m = 0; m < 5; ++m) {          // five independent accumulator chains per in-group
         double D[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, old[5], nxt[4] = {0.0, 0.0, 0.0, 0.0};

@@ -39,18 +39,12 @@
 #include <hip/hip_ext.h>
 #include "kernels_fused20.h"
 
-// 1: the tile loop re-reads the lane index through an opaque asm once per tile, so that hipcc does not carry the LDS
-// addresses it feeds across the loop: same-box A/B at N_f = 10^6 1307 / 1316 vs 1333 / 1337 us per Adam step (-1.7 %),
-// the 10-layer tile-loop variant's scratch 216 -> 136 B per lane
-#ifndef PINN_OPAQUE_TILE_M
-#define PINN_OPAQUE_TILE_M 1
-#endif
-
 namespace pinn {
 
 // (Ablation builds -- one ingredient compiled out at a time, wrong results by construction, only times are read -- are not part
-// of the product sources since round 5: `git apply -R profiles/ablation_scaffolding.patch` puts the -DPINN_ABL / -DPINN_ABLD /
-// -DT16_ABL switches back for profiles/ablate_*.py; their results are under profiles/*ablate*.txt.)
+// of the product sources since round 5.  profiles/ablation_scaffolding.patch holds the -DPINN_ABL / -DPINN_ABLD / -DT16_ABL
+// switches of profiles/ablate_*.py; it is not kept up with these sources: it reverse-applies to the tree at ee3788e; check that
+// commit out for the ablation builds.  Their results are under profiles/*ablate*.txt.)
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -296,9 +290,10 @@ __global__ PINN_F20M_BOUNDS void k_fused20m(const float* __restrict__ th, const 
 
   for (; tile < n_tiles; tile += gridDim.x) {
     // tile loop: lane index re-read through an opaque asm once per tile, per-lane indices re-derived -- keeps hipcc from
-    // carrying the LDS addresses they feed across the loop (kernels_fused20d.h; the 10-layer tile-loop variant spilled)
+    // carrying the LDS addresses they feed across the loop: same-box A/B at N_f = 10^6 1307 / 1316 vs 1333 / 1337 us per
+    // Adam step (-1.7 %), the 10-layer tile-loop variant's scratch 216 -> 136 B per lane (profiles/r04_opaque_lane_ab.txt)
     int lane_o = tid & 63;
-    if (!ONE_TILE && PINN_OPAQUE_TILE_M) asm volatile("" : "+v"(lane_o));
+    if (!ONE_TILE) asm volatile("" : "+v"(lane_o));
     PINN_LANE_INDICES_M(lane_o);
     const int pt = tile * 64 + lane;
     const float hx = fmaf(sx, x - lbx, -1.0f), ht = fmaf(st, t - lbt, -1.0f);

@@ -116,19 +116,19 @@ struct TileScratch {
   }
 };
 
-// sums of one HALF of slot e (lanes 32 h .. 32 h + 31 of the tile: 1 KB of every 2 KB block) over the n_rows workgroup
-// blocks, fixed order (32 slices of rows, then the slices in index order); tot[comp] valid in the threads of slice 0
-// (threadIdx.x < 32), whose tile lane is L.  Two workgroups per slot: 294 workgroups for cfg 4 instead of 147 -- one per slot
-// left 109 CUs idle in a launch that is pure streaming (17.7 us for 75 MB, profiles/r05_cfg4_kernel_stats_v7.txt).
-constexpr int SLOT_SPLIT = 1;     // (2, half a slot per workgroup, 294 workgroups for cfg 4: 20.3 us against 17.4 -- 1 KB pieces stream worse)
+// sums of slot e (the 64 lanes of the tile: every 2 KB block) over the n_rows workgroup blocks, fixed order (slices of rows,
+// then the slices in index order); tot[comp] valid in the threads of slice 0 (threadIdx.x < 64), whose tile lane is L.  One
+// workgroup per slot: 147 workgroups for cfg 4, which leaves 109 CUs idle in a launch that is pure streaming (17.7 us for
+// 75 MB, profiles/r05_cfg4_kernel_stats_v7.txt).  (Tried and dropped: half a slot per workgroup, 294 workgroups for cfg 4:
+// 20.3 us against 17.4 -- 1 KB pieces stream worse.)
 __device__ __forceinline__ void reduce_slot(const TileScratch& ts, const int n_rows, const int sb, double (*sh)[RED_COLS],
                                             double (&tot)[4], int& e, int& L) {
   using V4 = vec4<double>;
-  constexpr int LW = 64 / SLOT_SPLIT, NSL = RED_THREADS / LW;     // lanes per workgroup, row slices
-  e = sb / SLOT_SPLIT;
-  const int h = sb - e * SLOT_SPLIT, q = threadIdx.x / LW, l = threadIdx.x - q * LW;
-  L = h * LW + l;
-  double* const shf = &sh[0][0];                                  // [NSL][LW]
+  constexpr int NSL = RED_THREADS / 64;                           // row slices
+  e = sb;
+  const int q = threadIdx.x / 64, l = threadIdx.x - q * 64;
+  L = l;
+  double* const shf = &sh[0][0];                                  // [NSL][64]
   const V4* __restrict__ p = reinterpret_cast<const V4*>(ts.gscr + (size_t)e * 256) + L;
   const size_t sv = (size_t)(ts.stride / 4);
   V4 a[8];
@@ -157,14 +157,40 @@ __device__ __forceinline__ void reduce_slot(const TileScratch& ts, const int n_r
 #pragma unroll
   for (int comp = 0; comp < 4; ++comp) {
     if (comp) __syncthreads();
-    shf[q * LW + l] = part4[comp];
+    shf[q * 64 + l] = part4[comp];
     __syncthreads();
     tot[comp] = 0;
     if (q == 0) {
 #pragma unroll
-      for (int i = 0; i < NSL; ++i) tot[comp] += shf[i * LW + l];
+      for (int i = 0; i < NSL; ++i) tot[comp] += shf[i * 64 + l];
     }
   }
+}
+
+// One Adam step of entry i in the form of TF-2.0 ResourceApplyAdam (reference call site
+// utils/neuralnetwork.py:114): m += (1-b1)(g-m); v += (1-b2)(g^2-v); theta -= alpha*m/(sqrt(v)+eps), alpha =
+// lr*sqrt(1-b2^t)/(1-b1^t) computed by the host.  Every kernel that steps weights calls this one function, so a member of
+// an ensemble, a rank of a data-parallel group and a solo context run the same arithmetic.  Returns the new weight.
+__device__ __forceinline__ double adam_entry(const int i, const double g, double* __restrict__ theta,
+                                             double* __restrict__ m, double* __restrict__ v, const double alpha,
+                                             const double b1, const double b2, const double eps) {
+  const double mi = m[i] + (1.0 - b1) * (g - m[i]);
+  const double vi = v[i] + (1.0 - b2) * (g * g - v[i]);
+  m[i] = mi;
+  v[i] = vi;
+  const double t = theta[i] - alpha * mi / (sqrt(vi) + eps);
+  theta[i] = t;
+  return t;
+}
+// ... and the copies of the new weight the sweeps read: the working-precision vector and the packed float32 image
+template <typename real>
+__device__ __forceinline__ void adam_step(const int i, const double g, double* __restrict__ theta,
+                                          real* __restrict__ theta_r, double* __restrict__ m, double* __restrict__ v,
+                                          const double alpha, const double b1, const double b2, const double eps,
+                                          const NetDesc& nd, float* __restrict__ img) {
+  const double t = adam_entry(i, g, theta, m, v, alpha, b1, b2, eps);
+  theta_r[i] = (real)t;
+  pack_store_any(nd, img, i, (float)t);
 }
 
 // Non-finite guard (SURVEY 5 "failure detection"; the reference has none: a NaN loss just propagates,
@@ -183,11 +209,11 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce_rows(const real* __restr
                                                              TileScratch ts = TileScratch{}) {
   __shared__ double sh[RED_SLICES][RED_COLS];
   const int q = threadIdx.x >> 6, n_cb = (R + RED_COLS - 1) / RED_COLS;
-  if ((int)blockIdx.x >= n_cb) {               // half a slot of k_t16_fused's scratch (grid = n_cb + SLOT_SPLIT ts.n_slots)
+  if ((int)blockIdx.x >= n_cb) {               // a slot of k_t16_fused's scratch (grid = n_cb + ts.n_slots)
     double tot[4];
     int e, L;
     reduce_slot(ts, n_rows, blockIdx.x - n_cb, sh, tot, e, L);
-    if (threadIdx.x < 64 / SLOT_SPLIT) {
+    if (threadIdx.x < 64) {
 #pragma unroll
       for (int comp = 0; comp < 4; ++comp) {
         const int c = ts.column(e, L, comp);
@@ -222,23 +248,16 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce_adam(const real* __restr
     gl[c] = g;
     note_nonfinite(g, c, n, eval_no, nonfinite);
     if (c < n) {
-      const double mi = m[c] + (1.0 - b1) * (g - m[c]);
-      const double vi = v[c] + (1.0 - b2) * (g * g - v[c]);
-      m[c] = mi;
-      v[c] = vi;
-      const double t = theta[c] - alpha * mi / (sqrt(vi) + eps);
-      theta[c] = t;
-      theta_r[c] = (real)t;
-      pack_store_any(nd, img, c, (float)t);
+      adam_step(c, g, theta, theta_r, m, v, alpha, b1, b2, eps, nd, img);
     } else if (loss3 && c < n + 3) {
       loss3[c - n] = g;
     }
   };
-  if ((int)blockIdx.x >= n_cb) {               // half a slot of k_t16_fused's scratch (grid = n_cb + SLOT_SPLIT ts.n_slots)
+  if ((int)blockIdx.x >= n_cb) {               // a slot of k_t16_fused's scratch (grid = n_cb + ts.n_slots)
     double tot[4];
     int e, L;
     reduce_slot(ts, n_rows, blockIdx.x - n_cb, sh, tot, e, L);
-    if (threadIdx.x < 64 / SLOT_SPLIT) {
+    if (threadIdx.x < 64) {
 #pragma unroll
       for (int comp = 0; comp < 4; ++comp) {
         const int c = ts.column(e, L, comp);
@@ -301,21 +320,13 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce_adam_ens(const double* _
   gl[c] = g;
   note_nonfinite(g, c, n, eval_no, nonfinite + mem);
   if (c < n) {
-    const double mi = m[c] + (1.0 - b1) * (g - m[c]);
-    const double vi = v[c] + (1.0 - b2) * (g * g - v[c]);
-    m[c] = mi;
-    v[c] = vi;
-    const double t = theta[c] - alpha * mi / (sqrt(vi) + eps);
-    theta[c] = t;
-    theta_r[c] = t;
+    theta_r[c] = adam_entry(c, g, theta, m, v, alpha, b1, b2, eps);
   } else if (loss3 && c < n + 3) {
     loss3[(size_t)mem * 3 + c - n] = g;
   }
 }
 
-// TF-2.0 ResourceApplyAdam (reference call site
-// utils/neuralnetwork.py:114): m += (1-b1)(g-m); v += (1-b2)(g^2-v);
-// theta -= alpha*m/(sqrt(v)+eps), alpha = lr*sqrt(1-b2^t)/(1-b1^t) computed by the host.
+// The Adam step as a launch of its own (behind an all-reduce of gl)
 template <typename real>
 __global__ void k_adam(int n, const double* __restrict__ gl, double* __restrict__ theta,
                        real* __restrict__ theta_r, double* __restrict__ m,
@@ -325,15 +336,7 @@ __global__ void k_adam(int n, const double* __restrict__ gl, double* __restrict_
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < 3 && loss3) loss3[i] = gl[n_theta + i];
   if (i >= n) return;
-  const double g = gl[i];
-  const double mi = m[i] + (1.0 - b1) * (g - m[i]);
-  const double vi = v[i] + (1.0 - b2) * (g * g - v[i]);
-  m[i] = mi;
-  v[i] = vi;
-  const double t = theta[i] - alpha * mi / (sqrt(vi) + eps);
-  theta[i] = t;
-  theta_r[i] = (real)t;
-  pack_store_any(nd, img, i, (float)t);
+  adam_step(i, gl[i], theta, theta_r, m, v, alpha, b1, b2, eps, nd, img);
 }
 
 template <typename real>
@@ -566,9 +569,6 @@ __global__ __launch_bounds__(256) void k_zero_list(ZeroList zl) {
   }
 }
 
-#ifndef LBC_SGB
-#define LBC_SGB 1
-#endif
 constexpr int LBC_THREADS = 1024;  // k_lbc_coef: 16 waves stage the Gram matrices, wave 0 runs the recursion
 constexpr int LBC_ROWS = 4;        // ceil(62 / 16) matrix rows per thread
 constexpr int LBD_THREADS = 1024;  // k_lbc_dots: n = 3021 is three strides of a 1024-thread block
@@ -910,11 +910,9 @@ __global__ __launch_bounds__(LBC_THREADS) void k_lbc_coef_apply(
           bacc -= al_i * ub[c8 & 1][k];
           yq0 -= al_i * yb[c8 & 1][k];
           if (c8 > 0) { ub[(c8 - 1) & 1][k] = rowU[8 * (c8 - 1) + k]; yb[(c8 - 1) & 1][k] = rowY[8 * (c8 - 1) + k]; }
-#if LBC_SGB
           __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);      // broadcast
           __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);    // the two fetches sit in the broadcast's hazard slots
           __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);      // fma, fma
-#endif
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -936,11 +934,9 @@ __global__ __launch_bounds__(LBC_THREADS) void k_lbc_coef_apply(
           const double c_i = read_lane(eacc, 8 * c8 + k);
           eacc -= c_i * lb[c8 & 1][k];
           if (c8 + 1 < NCH) lb[(c8 + 1) & 1][k] = rowL[8 * (c8 + 1) + k];     // (chunk top + 1: finite, never used)
-#if LBC_SGB
           __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);
           __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           __builtin_amdgcn_sched_group_barrier(0x2, 1, 0);
-#endif
           __builtin_amdgcn_sched_barrier(0);
         }
       }

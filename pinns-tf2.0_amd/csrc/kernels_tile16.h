@@ -24,39 +24,38 @@
 
 namespace pinn {
 
+// (Ablation builds -- one ingredient compiled out at a time, wrong results by construction, only times are read -- are not part
+// of the product sources since round 5.  profiles/ablation_scaffolding.patch holds the -DPINN_ABL / -DPINN_ABLD / -DT16_ABL
+// switches of profiles/ablate_*.py; it is not kept up with these sources: it reverse-applies to the tree at ee3788e; check that
+// commit out for the ablation builds.  Their results are under profiles/*ablate*.txt.)
+
+// T16_AHEAD 1: the eight-wave reverse sweep fetches the row entries of all its dW tiles, and the next layer's stash, ahead of
+// the matrix instructions -- measured 8 us SLOWER on cfg 4 float64 (605 vs 597 us, same box, profiles/r03_t16_ab.txt): with
+// two waves per SIMD the other wave already covers those latencies and the extra live registers cost more.  The switch stays
+// although it is settled: its single-trip `ti` loop around k_t16_bwd's tile loop shapes the code hipcc generates -- flattened,
+// all 18 k_t16_bwd instantiations change (+2..35 instructions, +2 VGPRs, 20 B of scratch in two;
+// profiles/retire_switches_device_code.txt).
+#ifndef T16_AHEAD
+#define T16_AHEAD 0
+#endif
+
+// Tried and dropped (the arms were in the sources up to 7a77e26, profiles/retire_switches_device_code.txt):
+//   four waves per workgroup for the float64 sweeps above width 64 (the round-2 kernels) instead of eight
+//     (profiles/r03_ablate_t16_f64_w8.txt)
+//   the eight-wave reverse sweep fetching the row entries of a fresh row's first group, which are the zeros this workgroup
+//     has just written
+//   LDS operands of the layer GEMMs requested two k-steps ahead instead of one: 254-256 VGPRs in k_t16_fused and 1.5 %
+//     SLOWER there (same box, cfg 4 float64 410.5 vs 417.3 us per step), within +-0.5 % on the two-kernel sweeps
+//   the four-wave variants (widths <= 64) on hand-written chunk loops (weights fetched one chunk of four k-steps ahead,
+//     two chunks in the eight-wave variants: 583 vs 605 us on cfg 4 float64, profiles/r03_t16_ab.txt, r03_t16_depth.txt) and
+//     one-chain gradient tiles instead of t16_gemm_l2 / the two-chain tiles: same-box A/B (profiles/r04_t16_gemm4_ab.txt)
+//     2x50^4x1 f64 142.5 -> 130.5 us, f32 80.9 -> 74.5; 2x64^6x1 f64 241.8 -> 229.5; register counts keep the launch
+//     plan's workgroups per CU (f32 forward 112 VGPRs: occupancy 3 -> 4)
+
 // tanh of the MFMA sweeps.  float64: the library tanh() is several hundred instructions with branches -- at width 100
 // a lane evaluates 8 of them per layer behind 12.8 k cycles of matrix instructions, on a SIMD that holds one wave, so
 // they were a third of the forward sweep (cfg 4 float64: 286 us -> profiles/r03_time_cfg4.txt); tanh_d is the
 // exp + Newton-quotient form of k_fused20d (relative error < 1e-16 before the final rounding).  float32 keeps tanhf.
-// (Ablation builds -- one ingredient compiled out at a time, wrong results by construction, only times are read -- are not part
-// of the product sources since round 5: `git apply -R profiles/ablation_scaffolding.patch` puts the -DPINN_ABL / -DPINN_ABLD /
-// -DT16_ABL switches back for profiles/ablate_*.py; their results are under profiles/*ablate*.txt.)
-#ifndef T16_WIDE_WAVES
-#define T16_WIDE_WAVES 8       // waves per workgroup of the float64 sweeps above width 64 (4 = the round-2 kernels)
-#endif
-#ifndef T16_SKIP_FIRST
-#define T16_SKIP_FIRST 1
-#endif
-#ifndef T16_AHEAD
-#define T16_AHEAD 0            // 1: the eight-wave reverse sweep fetches the row entries of all its dW tiles, and the next
-#endif                         // layer's stash, ahead of the matrix instructions -- measured 8 us SLOWER on cfg 4 float64
-                               // (605 vs 597 us, same box, profiles/r03_t16_ab.txt): with two waves per SIMD the other
-                               // wave already covers those latencies and the extra live registers cost more
-#ifndef T16_B_AHEAD
-#define T16_B_AHEAD 1          // LDS operands of the layer GEMMs requested this many k-steps ahead (1 or 2).  Two: 254-256
-                               // VGPRs in k_t16_fused and 1.5 % SLOWER there (same box, cfg 4 float64 410.5 vs 417.3 us per
-                               // step), within +-0.5 % on the two-kernel sweeps: the LDS latency is already covered
-#endif
-#ifndef T16_GEMM4
-#define T16_GEMM4 1            // 1: the four-wave variants (widths <= 64) also use t16_gemm_l2 / the two-chain gradient tiles
-#endif                         // where their weights come from L2: same-box A/B (profiles/r04_t16_gemm4_ab.txt) 2x50^4x1 f64
-                               // 142.5 -> 130.5 us, f32 80.9 -> 74.5; 2x64^6x1 f64 241.8 -> 229.5; register counts keep
-                               // the launch plan's workgroups per CU (f32 forward 112 VGPRs: occupancy 3 -> 4)
-#ifndef T16_DEPTH
-#define T16_DEPTH 2            // eight-wave variants: chunks of four k-steps of L2-resident weights in flight ahead of the
-                               // one in use (2 vs 1: 583 vs 605 us on cfg 4 float64, profiles/r03_t16_ab.txt); the
-                               // four-wave variants keep 1 (2, 3, 4 measured there: no gain, profiles/r03_t16_depth.txt)
-#endif
 template <typename real> __device__ __forceinline__ real tanh_mm(real z);
 template <> __device__ __forceinline__ float tanh_mm<float>(float z) { return tanhf(z); }
 template <> __device__ __forceinline__ double tanh_mm<double>(double z) {
@@ -88,17 +87,6 @@ __device__ __forceinline__ real sum16(real v) {        // sum over the 16 lanes 
   return v;
 }
 
-// One layer GEMM of a 16-row feature tile with the weights read straight from L2 (round 4; the eight-wave sweeps and
-// k_t16_fused):  acc_c[r] += sum_k A(row, k) B_c[k][point m],  A(row, k) = Wm[row * W + k] if TRANSPOSED (adjoint GEMM)
-// else Wm[k * W + row] (forward GEMM); `ra` = this lane's row (16 tile + m), B rows are vec4 (four Taylor channels).
-//  * k-steps whose four rows k = 4 s + g all exist (s < W / 4) run UNGUARDED in chunks of four: plain loads (a padded
-//    output row ra >= W reads row W - 1; its results are discarded by the caller), three weight buffers in rotation --
-//    the loop is unrolled by three, no register copies, and the wait before a chunk is for loads issued two chunks
-//    earlier.  (Guarded loads compile to a predicated branch each, 8 instructions, and make every k-step its own basic
-//    block whose ds_read is waited for right before its four matrix instructions.)
-//  * the B operands of k-step s + 1 are requested from LDS BEFORE the matrix instructions of k-step s (sched_barrier
-//    pins it);
-//  * at most three unguarded and one guarded (W % 4 != 0) k-step remain for the tail.
 // Matrix instructions of one k-step of a layer GEMM: weight `w` (this lane's A operand in the 16x16x4 pattern: row
 // row0 + (lane & 15), k-step row lane >> 4) times the four channels of `b`.
 //   STRIPS = false: the wave owns a 16-row tile, one v_mfma_f64_16x16x4 per channel (64 cycles each).
@@ -188,9 +176,6 @@ __device__ __forceinline__ void t16_gemm_l2(const real* __restrict__ Wm, const v
   real w0[4], w1[4], w2[4];
   if (nfc > 0) { fetch(0, w0); fetch(1, w1); }
   V4 bc = bp[0];
-#if T16_B_AHEAD == 2
-  V4 bn = bp[4 * PD];
-#endif
   real ws[3] = {0, 0, 0};                                         // STRIPS: the current k-step's weights, one per strip
   auto spread = [&](const real w, real (&dst)[3]) {
     if constexpr (STRIPS) { dst[0] = t16_quad_bcast<0>(w); dst[1] = t16_quad_bcast<1>(w); dst[2] = t16_quad_bcast<2>(w); }
@@ -200,18 +185,11 @@ __device__ __forceinline__ void t16_gemm_l2(const real* __restrict__ Wm, const v
     fetch(c + 2, fill);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-#if T16_B_AHEAD == 2
-      const V4 bn2 = bp[(4 * c + u + 2) * 4 * PD];                // rows of the k-step after next (inside the LDS allocation)
-#else
       const V4 bn = bp[(4 * c + u + 1) * 4 * PD];                 // next k-step's rows (always inside the tile)
-#endif
       __builtin_amdgcn_sched_barrier(0);
       t16_mma_kstep<real, STRIPS>(cur[u], ws, u < 3 ? cur[u + 1] : nxt[0], bc, ns, a0, a1, a2, a3);   // (after the last chunk: a harmless re-read)
       __builtin_amdgcn_sched_barrier(0);
       bc = bn;
-#if T16_B_AHEAD == 2
-      bn = bn2;
-#endif
     }
   };
   for (int c = 0; c < nfc; c += 3) {
@@ -335,40 +313,8 @@ __global__ __launch_bounds__(64 * NWV) void k_t16_fwd(NetDesc nd, const real* __
             a2 = t16_mfma<real, acc_t>(a, b.z, a2);
             a3 = t16_mfma<real, acc_t>(a, b.w, a3);
           }
-        } else if constexpr (NWV == 8 || T16_GEMM4) {
-          t16_gemm_l2<real, false, PD, acc_t>(Wl, Tin, W, ja, m, g, a0, a1, a2, a3);
         } else {
-          // weights straight from L2: the A operands of a chunk of four k-steps are fetched one chunk ahead, so their
-          // latency (several hundred cycles) hides under the 16 matrix instructions of the chunk in flight instead
-          // of stalling every chunk.  A last partial chunk runs on zero weights and the zero rows k >= W of the tile.
-          const int nchunks = (ksteps + 3) >> 2;
-          // T16_DEPTH chunks in flight: an L2 hit costs ~1.5 k cycles here, one chunk of float64 matrix instructions
-          // lasts 1 k (ablation, profiles/r03_ablate_t16_f64.txt: with one chunk ahead every chunk stalled)
-          constexpr int DEPTH = NWV == 8 ? T16_DEPTH : 1;
-          real wq[DEPTH + 1][4];
-          auto fetch = [&](int c, real (&dst)[4]) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { const int k = 4 * (4 * c + u) + g; dst[u] = (k < W && ja < W) ? Wl[k * W + ja] : real(0); }
-          };
-#pragma unroll
-          for (int q = 0; q < DEPTH; ++q) fetch(q, wq[q]);
-          for (int c = 0; c < nchunks; ++c) {
-            fetch(c + DEPTH, wq[DEPTH]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              if (NWV == 8 && 4 * c + u >= ksteps) break;          // last chunk: only the k-steps that exist (uniform)
-              const V4 b = Tin[(4 * (4 * c + u) + g) * PD + m];
-              a0 = t16_mfma<real, acc_t>(wq[0][u], b.x, a0);
-              a1 = t16_mfma<real, acc_t>(wq[0][u], b.y, a1);
-              a2 = t16_mfma<real, acc_t>(wq[0][u], b.z, a2);
-              a3 = t16_mfma<real, acc_t>(wq[0][u], b.w, a3);
-            }
-#pragma unroll
-            for (int q = 0; q < DEPTH; ++q) {
-#pragma unroll
-              for (int u = 0; u < 4; ++u) wq[q][u] = wq[q + 1][u];
-            }
-          }
+          t16_gemm_l2<real, false, PD, acc_t>(Wl, Tin, W, ja, m, g, a0, a1, a2, a3);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -551,12 +497,12 @@ __global__ __launch_bounds__(64 * NWV) void k_t16_bwd(NetDesc nd, SetDesc sd, co
           else {
             // the first group of a fresh row adds to the zeros this workgroup has just written: nothing to fetch
             // (eight-wave variants; one fifth of the row reads at five groups per workgroup)
-            old[r] = (k < W && j < W && !(NWV == 8 && T16_SKIP_FIRST && !accumulate && grp == (int)blockIdx.x))
+            old[r] = (k < W && j < W && !(NWV == 8 && !accumulate && grp == (int)blockIdx.x))
                          ? row[nd.off_w[d] + k * W + j] : real(0);
           }
         }
         acc_t acc = {0, 0, 0, 0};
-        if constexpr (NWV == 8 || T16_GEMM4) {
+        {
           // (round 4, as k_t16_fused) two accumulator chains instead of one 16-deep dependent chain, and the operands
           // of quarter s4 + 1 requested from LDS before the matrix instructions of quarter s4
           acc_t acc2 = {0, 0, 0, 0};
@@ -576,15 +522,6 @@ __global__ __launch_bounds__(64 * NWV) void k_t16_bwd(NetDesc nd, SetDesc sd, co
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) acc[r] += acc2[r];
-        } else {
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) {
-            const V4 A = TI[(16 * rt + m) * PD + 4 * s4 + g], B = Bcur[(16 * ct + m) * PD + 4 * s4 + g];
-            acc = t16_mfma<real, acc_t>(A.x, B.x, acc);
-            acc = t16_mfma<real, acc_t>(A.y, B.y, acc);
-            acc = t16_mfma<real, acc_t>(A.z, B.z, acc);
-            acc = t16_mfma<real, acc_t>(A.w, B.w, acc);
-          }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -637,35 +574,8 @@ __global__ __launch_bounds__(64 * NWV) void k_t16_bwd(NetDesc nd, SetDesc sd, co
             a2 = t16_mfma<real, acc_t>(a, b.z, a2);
             a3 = t16_mfma<real, acc_t>(a, b.w, a3);
           }
-        } else if constexpr (NWV == 8 || T16_GEMM4) {
+        } else {
           t16_gemm_l2<real, true, PD, acc_t>(Wd, Bcur, W, k, m, g, a0, a1, a2, a3);
-        } else {                              // weights from L2, fetched one chunk of four k-steps ahead (see k_t16_fwd)
-          const int nchunks = (ksteps + 3) >> 2;
-          constexpr int DEPTH = NWV == 8 ? T16_DEPTH : 1;
-          real wq[DEPTH + 1][4];
-          auto fetch = [&](int c, real (&dst)[4]) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { const int jj = 4 * (4 * c + u) + g; dst[u] = (k < W && jj < W) ? Wd[k * W + jj] : real(0); }
-          };
-#pragma unroll
-          for (int q = 0; q < DEPTH; ++q) fetch(q, wq[q]);
-          for (int c = 0; c < nchunks; ++c) {
-            fetch(c + DEPTH, wq[DEPTH]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              if (NWV == 8 && 4 * c + u >= ksteps) break;
-              const V4 b = Bcur[(4 * (4 * c + u) + g) * PD + m];
-              a0 = t16_mfma<real, acc_t>(wq[0][u], b.x, a0);
-              a1 = t16_mfma<real, acc_t>(wq[0][u], b.y, a1);
-              a2 = t16_mfma<real, acc_t>(wq[0][u], b.z, a2);
-              a3 = t16_mfma<real, acc_t>(wq[0][u], b.w, a3);
-            }
-#pragma unroll
-            for (int q = 0; q < DEPTH; ++q) {
-#pragma unroll
-              for (int u = 0; u < 4; ++u) wq[q][u] = wq[q + 1][u];
-            }
-          }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {

@@ -220,9 +220,7 @@ __global__ __launch_bounds__(512) void k_t16_fused(NetDesc nd, SetDesc sd, const
   const int ksteps = (W + 3) / 4;
   const int row0 = deal.row0[wave], ns = deal.ns[wave];           // wave-uniform: this wave's rows of the layer GEMMs (T16Deal)
   const bool tile_live = ns > 0;
-#ifndef T16_STRIP_PRIO
-#define T16_STRIP_PRIO 3
-#endif
+  constexpr int T16_STRIP_PRIO = 3;
   // A strips wave shares its SIMD with a tile wave.  With equal priority the arbiter alternates between them instruction
   // by instruction: every 16-cycle strip instruction then queues behind one 64-cycle tile instruction -- 200 x 80 cycles
   // for 3.3 k of matrix time (profiles/r05_t16f_stamps_edge_v6.txt: strips GEMM 14.8 k, the tile wave's 9.9 k).  Raised

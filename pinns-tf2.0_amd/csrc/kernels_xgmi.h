@@ -106,20 +106,13 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce_xgmi(const real* __restr
     gl[c] = tot;
     if (ADAM) {
       if (c < n) {
-        const double mi = m[c] + (1.0 - b1) * (tot - m[c]);
-        const double vi = v[c] + (1.0 - b2) * (tot * tot - v[c]);
-        m[c] = mi;
-        v[c] = vi;
-        const double t = theta[c] - alpha * mi / (sqrt(vi) + eps);
-        theta[c] = t;
-        theta_r[c] = (real)t;
-        pack_store_any(nd, img, c, (float)t);
+        adam_step(c, tot, theta, theta_r, m, v, alpha, b1, b2, eps, nd, img);
       } else if (loss3 && c < n + 3) {
         loss3[c - n] = tot;
       }
     }
   };
-  const int n_blocks = n_cb + (ts.gscr ? SLOT_SPLIT * ts.n_slots : 0);   // column blocks, then the half slots of k_t16_fused's scratch
+  const int n_blocks = n_cb + (ts.gscr ? ts.n_slots : 0);   // column blocks, then the slots of k_t16_fused's scratch
   for (int cb = blockIdx.x; cb < n_blocks; cb += gridDim.x) {
     if (cb != (int)blockIdx.x) __syncthreads();           // sh of the previous block has been consumed
     // the columns this thread finishes: four of a scratch slot or one of a column block -- ONE copy of the exchange below
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce_xgmi(const real* __restr
       double tot4[4];
       int e, L;
       reduce_slot(ts, n_rows, cb - n_cb, sh, tot4, e, L);
-      if (threadIdx.x < 64 / SLOT_SPLIT) {
+      if (threadIdx.x < 64) {
         c0 = ts.column(e, L, 0); c1 = ts.column(e, L, 1); c2 = ts.column(e, L, 2); c3 = ts.column(e, L, 3);
         g0 = tot4[0]; g1 = tot4[1]; g2 = tot4[2]; g3 = tot4[3];
       }

@@ -3,8 +3,9 @@
 
     python profiles/ablate_fused20m.py --build [DIR]     # CPU: one libpinn_hip_abl{n}.so per variant (default DIR: pinn_native/abl, git-ignored)
     python profiles/ablate_fused20m.py [DIR]             # GPU: times them
-Since round 5 the -D switches these builds use are not in csrc/ any more: run `git apply -R profiles/ablation_scaffolding.patch`
-first (and `git checkout pinns-tf2.0_amd/csrc` afterwards); the patch was cut from the round-5 sources."""
+Since round 5 the -D switches these builds use are not in csrc/ any more.  profiles/ablation_scaffolding.patch holds them; it was
+cut from the round-5 sources and is not kept up with csrc/: it reverse-applies to the tree at ee3788e; check that commit out for
+the ablation builds (`git checkout ee3788e && git apply -R profiles/ablation_scaffolding.patch`)."""
 import os
 import subprocess
 import sys

@@ -3,8 +3,9 @@ N_f = 20000): -DT16_ABL=n builds of csrc/kernels_tile16.h with one ingredient co
 construction; only the kernel durations are read, from rocprofv3 --kernel-trace).
     python profiles/ablate_t16.py --build [DIR]     # CPU: one libpinn_hip_t16abl{n}.so per variant (DIR default pinn_native/abl)
     python profiles/ablate_t16.py [DIR]             # GPU: rocprofv3 over profiles/time_cfg4.py per variant
-Since round 5 the -D switches these builds use are not in csrc/ any more: run `git apply -R profiles/ablation_scaffolding.patch`
-first (and `git checkout pinns-tf2.0_amd/csrc` afterwards); the patch was cut from the round-5 sources."""
+Since round 5 the -D switches these builds use are not in csrc/ any more.  profiles/ablation_scaffolding.patch holds them; it was
+cut from the round-5 sources and is not kept up with csrc/: it reverse-applies to the tree at ee3788e; check that commit out for
+the ablation builds (`git checkout ee3788e && git apply -R profiles/ablation_scaffolding.patch`)."""
 import os, subprocess, sys, sqlite3, glob, shutil
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "pinns-tf2.0_amd")

@@ -4,8 +4,9 @@ one exchange-tile pair, 72 KB LDS, __launch_bounds__(256, 2), grid = 2 x CUs; re
 product kernel, float32, in the throughput regime.
     hipcc ... -DPINN_ABL=8 -c csrc/engine.hip; link with the two other units -> pinn_native/abl/libpinn_hip_abl8.so
     python profiles/ablate_two_wg.py
-Since round 5 the -D switches these builds use are not in csrc/ any more: run `git apply -R profiles/ablation_scaffolding.patch`
-first (and `git checkout pinns-tf2.0_amd/csrc` afterwards); the patch was cut from the round-5 sources."""
+Since round 5 the -D switches these builds use are not in csrc/ any more.  profiles/ablation_scaffolding.patch holds them; it was
+cut from the round-5 sources and is not kept up with csrc/: it reverse-applies to the tree at ee3788e; check that commit out for
+the ablation builds (`git checkout ee3788e && git apply -R profiles/ablation_scaffolding.patch`)."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = r'''

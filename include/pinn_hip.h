@@ -44,7 +44,17 @@ enum {
    * collocation set may be empty.  Kernel paths 0 (any shape, float32 / float64) and 7 (float64, width 20, 4 / 6 / 8
    * hidden layers: the default there); PINN_EUNSUPPORTED for the other paths, self-adaptive weights and ensembles.
    * (Additive: one enum value, no new entry point; the ABI version stays 6.) */
-  PINN_PDE_ADR = 5
+  PINN_PDE_ADR = 5,
+  /* the same equation and loss with TRAINABLE coefficients (identification from data).  The weight vector is
+   * [net | a0, a1, log nu, r1, r2, r3] (pinn_num_params = net + 6, always all six, in this order; nu = exp(log nu) stays
+   * positive); pinn_get_weights / pinn_set_weights carry the tail as PINN_PDE_BURGERS_IDE carries its two lambdas.
+   * pinn_set_pde_params takes the six RAW values (nu > 0) and writes the tail, pinn_get_pde_params returns them;
+   * pinn_set_pde_trainable chooses which are trained (default: none).  The gradient entry of a frozen coefficient is
+   * exactly 0.0, so Adam and L-BFGS leave its value bit-identical.  The residual is taken on the collocation set (hand the
+   * data points over as collocation points for the usual identification loss).  Kernel paths 0 and 7 as PINN_PDE_ADR;
+   * PINN_EUNSUPPORTED for the other paths, self-adaptive weights, ensembles and communicators.
+   * (Additive: one enum value, two entry points; the ABI version stays 6.) */
+  PINN_PDE_ADR_IDE = 6
 };
 enum { PINN_F32 = 0, PINN_F64 = 1 };
 enum {
@@ -119,8 +129,17 @@ int pinn_disc_predict(pinn_ctx* c, int set, const double* x, int64_t n, double* 
 
 /* get_params (inf_cont_burgers.py:92): p[0] = nu for PINN_PDE_BURGERS and PINN_PDE_BURGERS_DISC.
  * PINN_PDE_ADR: n must be 6, p = [a0, a1, nu, r1, r2, r3], all finite; otherwise PINN_EINVAL and the context keeps the
- * coefficients it had (a new context holds Burgers', [0, 1, 0.01 / pi, 0, 0, 0]). */
+ * coefficients it had (a new context holds Burgers', [0, 1, 0.01 / pi, 0, 0, 0]).
+ * PINN_PDE_ADR_IDE: n must be 6, RAW p = [a0, a1, nu, r1, r2, r3], all finite and nu > 0 (otherwise PINN_EINVAL, nothing
+ * changed): written to the tail of the weight vector, log nu in the nu slot. */
 int pinn_set_pde_params(pinn_ctx* c, const double* p, int n);
+/* the current values: n = 6 raw coefficients for PINN_PDE_ADR and PINN_PDE_ADR_IDE (nu as exp of the stored log nu: what
+ * training has made of them), n = 1 (nu) for every other kind */
+int pinn_get_pde_params(pinn_ctx* c, double* p, int n);
+/* PINN_PDE_ADR_IDE: bit k of mask set = coefficient k of (a0, a1, nu, r1, r2, r3) is trained; a new context trains none
+ * (mask 0).  PINN_EINVAL for a mask outside 0..63, PINN_EUNSUPPORTED for every other kind; the context is unchanged then.
+ * Takes effect at the next evaluation; a running Adam / L-BFGS state is not reset.  (Additive: the ABI version stays 6.) */
+int pinn_set_pde_trainable(pinn_ctx* c, int mask);
 
 /* get_weights / set_weights (utils/neuralnetwork.py:68-89) */
 int pinn_set_weights(pinn_ctx* c, const double* w, int64_t n);

@@ -129,6 +129,7 @@ struct pinn_ctx {
   int n_layers = 0;
   double lb[2]{}, ub[2]{}, nu = 0.0;
   double adr[6]{};                   // PINN_PDE_ADR: a0, a1, nu, r1, r2, r3 (pinn_set_pde_params)
+  int adr_mask = 0;                  // PINN_PDE_ADR_IDE: bit k set = coefficient k is trained (pinn_set_pde_trainable)
 
   // host copies of the point sets (float64, as handed over)
   std::vector<double> Xf, Xu, U, Xlo, Xhi;
@@ -291,18 +292,26 @@ static bool has_lambdas(int pde) { return pde == PINN_PDE_BURGERS_IDE || pde == 
 // advection-diffusion-reaction with run-time coefficients: template value PDE_ADR of the continuous kernels
 // (kernels_generic.h); it runs on the generic path 0 and, float64 width 20, on k_fused20d (path 7)
 static bool is_adr(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR; }
+// the same equation with trainable coefficients: template value PDE_ADR_IDE, the six coefficients are the tail of theta
+// ([a0, a1, log nu, r1, r2, r3]); the same two paths
+static bool is_adr_ide(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR_IDE; }
+static bool adr_family(const pinn_ctx* c) { return is_adr(c) || is_adr_ide(c); }
+// trailing equation parameters of the flat weight vector
+static int tail_len(int pde) { return has_lambdas(pde) ? 2 : pde == PINN_PDE_ADR_IDE ? 6 : 0; }
 // what a kernel of kind PDE takes in the place of the scalar nu
 template <typename real, int PDE>
 static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
   if constexpr (PDE == PDE_ADR)
     return AdrCoef<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5]};
+  else if constexpr (PDE == PDE_ADR_IDE)
+    return AdrIdeArg{c->adr_mask};
   else
     return (real)c->nu;
 }
 
 // the fused kernel serves width-20 Burgers nets whose staged weights fit the 160 KiB LDS
 static bool fused_ok(const pinn_ctx* c) {
-  if (!fused20_supported(c->nd) || c->pde == PINN_PDE_SCHRODINGER || is_disc(c) || is_adr(c)) return false;
+  if (!fused20_supported(c->nd) || c->pde == PINN_PDE_SCHRODINGER || is_disc(c) || adr_family(c)) return false;
   const size_t lds = c->dtype == PINN_F64 ? fused20_lds_bytes<double>(c->nd.n_hidden)
                                           : fused20_lds_bytes<float>(c->nd.n_hidden);
   return lds <= 160 * 1024;
@@ -310,7 +319,7 @@ static bool fused_ok(const pinn_ctx* c) {
 
 // the register-stash kernel: float32, width 20, instantiated depths, weights + tiles within LDS
 static bool fused_regs_ok(const pinn_ctx* c) {
-  return c->dtype == PINN_F32 && fused20_supported(c->nd) && c->pde != PINN_PDE_SCHRODINGER && !is_disc(c) && !is_adr(c) &&
+  return c->dtype == PINN_F32 && fused20_supported(c->nd) && c->pde != PINN_PDE_SCHRODINGER && !is_disc(c) && !adr_family(c) &&
          fused20m_depth_ok(c->nd.n_hidden) && fused20m_lds_bytes(c->nd.n_hidden) <= 160 * 1024;
 }
 
@@ -366,7 +375,7 @@ static const PathInfo PATHS[KP_COUNT] = {
 static const KernelPath PATH_PREFERENCE[] = {KP_FUSED20M, KP_FUSED20D, KP_FUSED20, KP_WIDE, KP_T16_FUSED, KP_T16, KP_GENERIC};
 // the adr kind's two implementations
 static bool adr_has_path(KernelPath p) { return p == KP_GENERIC || p == KP_FUSED20D; }
-static bool path_ok(const pinn_ctx* c, KernelPath p) { return PATHS[p].ok(c) && (!is_adr(c) || adr_has_path(p)); }
+static bool path_ok(const pinn_ctx* c, KernelPath p) { return PATHS[p].ok(c) && (!adr_family(c) || adr_has_path(p)); }
 
 static bool t16_fwd_on(const pinn_ctx* c) { return c->path == KP_T16 || c->path == KP_T16_FWD; }
 static bool t16_bwd_on(const pinn_ctx* c) { return c->path == KP_T16 || c->path == KP_T16_BWD || c->path == KP_T16_FUSED; }
@@ -466,7 +475,7 @@ static int ensure_sets(pinn_ctx* c) {
   const int NO = c->nd.n_out;
   if (c->pde == PINN_PDE_BURGERS_IDE)
     REQUIRE(n_f == 0, "identification evaluates the residual at the data points; no collocation set");
-  if (c->pde != PINN_PDE_SCHRODINGER && !is_adr(c)) REQUIRE(n_b == 0, "boundary pairs are Schrodinger-only");
+  if (c->pde != PINN_PDE_SCHRODINGER && !adr_family(c)) REQUIRE(n_b == 0, "boundary pairs are Schrodinger-only");
   const int n_all = 2 * n_b + n_u + n_f;
   REQUIRE(n_all > 0, "no training points set");
   const int n_pad = (n_all + 63) / 64 * 64;
@@ -480,7 +489,7 @@ static int ensure_sets(pinn_ctx* c) {
 
   std::vector<double> hx(n_pad), ht(n_pad), htg((size_t)NO * n_pad, 0.0);
   int g = 0;
-  if (is_adr(c)) {      // pair-interleaved [lo_0, hi_0, lo_1, hi_1, ...] on every kernel path: the partner of point g is g ^ 1
+  if (adr_family(c)) {      // pair-interleaved [lo_0, hi_0, lo_1, hi_1, ...] on every kernel path: the partner of point g is g ^ 1
     for (int i = 0; i < n_b; ++i, g += 2) {
       hx[g] = c->Xlo[2 * i]; ht[g] = c->Xlo[2 * i + 1];
       hx[g + 1] = c->Xhi[2 * i]; ht[g + 1] = c->Xhi[2 * i + 1];
@@ -743,6 +752,7 @@ static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
     if (weighted) { if (int e = sa_prepare(c)) return e; }
     const F20dLaunch a = fused20d_args(c, ev4);
     if constexpr (PDE == PDE_ADR) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR>(c));
+    else if constexpr (PDE == PDE_ADR_IDE) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_IDE>(c));
     else if (weighted) rc = fused20d_launch_any(a, SaArgs{(double)c->nu, c->sa.buf, af ? af->alpha_sa : 0.0});
     else rc = fused20d_launch_any(PDE, a, (double)c->nu);
   }
@@ -754,7 +764,7 @@ static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
 template <typename real, int PDE>
 static int launch_fused20m(pinn_ctx* c, hipEvent_t* ev4) {
   int rc = hipErrorInvalidValue;
-  if constexpr (sizeof(real) == 4 && PDE != 2 && PDE != PDE_ADR) {
+  if constexpr (sizeof(real) == 4 && PDE != 2 && !pde_is_adr(PDE)) {
     const InMap<float> m(c);
     hipEvent_t const e0 = ev4 ? ev4[0] : nullptr, e1 = ev4 ? ev4[1] : nullptr;
     if (c->nd.n_hidden == 8)
@@ -774,7 +784,7 @@ static int launch_fused20m(pinn_ctx* c, hipEvent_t* ev4) {
 template <typename real, int PDE>
 static int launch_fused20(pinn_ctx* c, hipEvent_t* ev4) {
   int rc = hipErrorInvalidValue;
-  if constexpr (PDE != PDE_ADR) {
+  if constexpr (!pde_is_adr(PDE)) {
     const InMap<real> m(c);
     rc = fused20_launch<real, PDE>(c->nd, c->sd, (const real*)c->theta_r, (const real*)c->xs, (const real*)c->ts,
                                    (const real*)c->tgt, m.lbx, m.lbt, m.sx, m.st, (real)c->nu, (vec4<real>*)c->S,
@@ -789,7 +799,7 @@ static int launch_fused20(pinn_ctx* c, hipEvent_t* ev4) {
 // recorded in front of the kernel, behind a pre-pass.
 template <typename real, int PDE>
 static int chunk_t16_fused(pinn_ctx* c, const InMap<real>& m, hipEvent_t ev1, int base, int pts, int ci) {
-  if constexpr (sizeof(real) == 8 && PDE != PDE_ADR) {
+  if constexpr (sizeof(real) == 8 && !pde_is_adr(PDE)) {
     const SetDesc& sd = c->sd;
     const int rows_cap = t16_wgs(c, c->chunk);
     const int wgs = t16_wgs(c, pts) < rows_cap ? t16_wgs(c, pts) : rows_cap;
@@ -859,7 +869,7 @@ static int chunk_fwd(pinn_ctx* c, const InMap<real>& m, int base, int pts) {
 template <typename real, int PDE>
 static int chunk_bwd(pinn_ctx* c, const InMap<real>& m, int base, int pts, int accumulate) {
   const SetDesc& sd = c->sd;
-  if constexpr (PDE != PDE_ADR) {
+  if constexpr (!pde_is_adr(PDE)) {
     if (t16_bwd_on(c)) return t16_bwd<real, PDE>(c, base, pts, m.lbx, m.lbt, m.sx, m.st, accumulate);
   }
   if constexpr (sizeof(real) == 4 && PDE == 2) {
@@ -1065,6 +1075,7 @@ static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
     case PINN_PDE_BURGERS: rc = launch_sweeps<REAL, 0>(c, ev4, af); break;       \
     case PINN_PDE_BURGERS_IDE: rc = launch_sweeps<REAL, 1>(c, ev4, af); break;   \
     case PINN_PDE_ADR: rc = launch_sweeps<REAL, PDE_ADR>(c, ev4, af); break;     \
+    case PINN_PDE_ADR_IDE: rc = launch_sweeps<REAL, PDE_ADR_IDE>(c, ev4, af); break; \
     default: rc = launch_sweeps<REAL, 2>(c, ev4, af); break;                     \
   }
   if (is_disc(c)) rc = disc_eval_any(c, ev4, af);
@@ -1356,8 +1367,8 @@ static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) 
   // 2. residuals at the current weights: pinn_residual_at's forward sweep and k_residual
   if (int rc = forward_taylor(c, c->rad.px, c->rad.pt, n_pad, n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS, c->rad.O)) return rc;
 #define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid_m, block, 0, c->stream, 0, (int)M, n_pad, (const vec4<REAL>*)c->rad.O, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->rad.f, NO)
-  if (f64) { if (c->pde == PINN_PDE_SCHRODINGER) RES(double, 2); else if (is_adr(c)) RES(double, PDE_ADR); else RES(double, 0); }
-  else { if (c->pde == PINN_PDE_SCHRODINGER) RES(float, 2); else if (is_adr(c)) RES(float, PDE_ADR); else RES(float, 0); }
+  if (f64) { if (c->pde == PINN_PDE_SCHRODINGER) RES(double, 2); else if (is_adr(c)) RES(double, PDE_ADR); else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 0); }
+  else { if (c->pde == PINN_PDE_SCHRODINGER) RES(float, 2); else if (is_adr(c)) RES(float, PDE_ADR); else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 0); }
 #undef RES
   HIPCHK(hipGetLastError());
   // 3.-4. weights and their CDF
@@ -1418,12 +1429,24 @@ int pinn_device_info(int device, char* name, int cap, int* n_cu, int64_t* hbm_by
   return 0;
 }
 
+// PINN_PDE_ADR_IDE: raw [a0, a1, nu, r1, r2, r3] -> the tail of theta (log nu in the nu slot) and its compute-dtype mirror
+static int adr_ide_write_tail(pinn_ctx* c, const double* p) {
+  double tail[6];
+  for (int i = 0; i < 6; ++i) tail[i] = i == 2 ? std::log(p[i]) : p[i];
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(c->theta + c->nd.n_net, tail, sizeof(tail), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));       // tail lives on this stack
+  if (int rc = cast_weights(c)) return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* lb,
                 const double* ub, int pde_kind, int dtype, int device) {
   REQUIRE(out && layers && lb && ub, "null argument");
   REQUIRE(n_layers >= 3 && n_layers <= MAX_DENSE + 1, "need 3..%d layer sizes, got %d", MAX_DENSE + 1, n_layers);
   REQUIRE(dtype == PINN_F32 || dtype == PINN_F64, "dtype must be PINN_F32 or PINN_F64");
-  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADR, "unknown pde kind %d", pde_kind);
+  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADR_IDE, "unknown pde kind %d", pde_kind);
   const bool disc = pde_kind == PINN_PDE_BURGERS_DISC || pde_kind == PINN_PDE_BURGERS_DISC_IDE;
   if (disc) REQUIRE(layers[0] == 1, "discrete-time models take one input (x), got %d", layers[0]);
   else REQUIRE(layers[0] == 2, "input dimension must be 2 (x, t), got %d", layers[0]);
@@ -1459,7 +1482,7 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
     nd.off_b[d] = off; off += layers[d + 1];
   }
   nd.n_net = off;
-  nd.n_theta = off + (has_lambdas(pde_kind) ? 2 : 0);
+  nd.n_theta = off + tail_len(pde_kind);
   c->R = nd.n_theta + LOSS_SLOTS;
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete c; return fail(PINN_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
@@ -1519,6 +1542,9 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   }
   for (KernelPath p : PATH_PREFERENCE)      // (KP_GENERIC, the last, takes every net)
     if (path_ok(c, p)) { c->path = p; break; }
+  if (is_adr_ide(c)) {      // starts as Burgers too, every coefficient frozen
+    if (int rc = adr_ide_write_tail(c, c->adr)) { pinn_destroy(c); return rc; }
+  }
   *out = c;
   return 0;
 }
@@ -1653,7 +1679,7 @@ int pinn_set_data(pinn_ctx* c, const double* X_u, const double* u, int64_t n, in
 int pinn_set_boundary(pinn_ctx* c, const double* X_lb, const double* X_ub, int64_t n, int64_t n_total) {
   if (c && is_disc(c)) return fail(PINN_EINVAL, "pinn_set_boundary: discrete-time models take stage sets (pinn_disc_set_stage)");
   REQUIRE(c && ((X_lb && X_ub) || n == 0) && n >= 0 && n_total >= n, "bad boundary arguments");
-  REQUIRE(c->pde == PINN_PDE_SCHRODINGER || is_adr(c) || n == 0, "boundary pairs are Schrodinger-only");
+  REQUIRE(c->pde == PINN_PDE_SCHRODINGER || adr_family(c) || n == 0, "boundary pairs are Schrodinger-only");
   c->Xlo.assign(X_lb, X_lb + 2 * n);
   c->Xhi.assign(X_ub, X_ub + 2 * n);
   c->nb_total = n_total;
@@ -1670,7 +1696,39 @@ int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
     c->nu = p[2];
     return 0;
   }
+  if (is_adr_ide(c)) {  // raw a0, a1, nu, r1, r2, r3 -> the tail of theta; nothing changes on a refusal
+    REQUIRE(n == 6, "pinn_set_pde_params: the adr_ide kind takes 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
+    for (int i = 0; i < 6; ++i) REQUIRE(std::isfinite(p[i]), "pinn_set_pde_params: coefficient %d is not finite", i);
+    REQUIRE(p[2] > 0.0, "pinn_set_pde_params: the adr_ide kind stores log nu, so nu must be positive (got %g)", p[2]);
+    return adr_ide_write_tail(c, p);
+  }
   c->nu = p[0];
+  return 0;
+}
+
+int pinn_get_pde_params(pinn_ctx* c, double* p, int n) {
+  REQUIRE(c && p, "null");
+  if (is_adr(c) || is_adr_ide(c)) REQUIRE(n == 6, "pinn_get_pde_params: this kind has 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
+  else REQUIRE(n == 1, "pinn_get_pde_params: this kind has 1 parameter (nu), got %d", n);
+  if (is_adr_ide(c)) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(p, c->theta + c->nd.n_net, 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    p[2] = std::exp(p[2]);
+  } else if (is_adr(c)) {
+    for (int i = 0; i < 6; ++i) p[i] = c->adr[i];
+  } else {
+    p[0] = c->nu;
+  }
+  return 0;
+}
+
+int pinn_set_pde_trainable(pinn_ctx* c, int mask) {
+  REQUIRE(c, "null");
+  if (!is_adr_ide(c))
+    return fail(PINN_EUNSUPPORTED, "pinn_set_pde_trainable: only the adr_ide kind (pde 6) has trainable coefficients to choose from");
+  REQUIRE(mask >= 0 && mask <= 63, "pinn_set_pde_trainable: mask %d is outside 0..63 (bit k = coefficient k of a0, a1, nu, r1, r2, r3)", mask);
+  c->adr_mask = mask;
   return 0;
 }
 
@@ -2270,8 +2328,8 @@ int pinn_residual(pinn_ctx* c, double* f, int64_t n) {
   if (int rc2 = forward_taylor(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O)) return rc2;
   const dim3 grid((cnt + 255) / 256), block(256);
 #define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, first, cnt, sd.n_pad, (const vec4<REAL>*)c->O, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->f_out, NO)
-  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) RES(double, PDE_ADR); else RES(double, 2); }
-  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) RES(float, PDE_ADR); else RES(float, 2); }
+  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) RES(double, PDE_ADR); else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
+  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) RES(float, PDE_ADR); else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
 #undef RES
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)cnt * NO * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2291,8 +2349,8 @@ int pinn_residual_at(pinn_ctx* c, const double* X, int64_t n, double* f) {
   if ((size_t)n * NO > c->cap_f) { if (dev_alloc(&c->f_out, (size_t)n * NO * 8)) return PINN_EHIP; c->cap_f = (size_t)n * NO; }
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
 #define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, 0, (int)n, n_pad, (const vec4<REAL>*)c->Oe, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->f_out, NO)
-  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) RES(double, PDE_ADR); else RES(double, 2); }
-  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) RES(float, PDE_ADR); else RES(float, 2); }
+  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) RES(double, PDE_ADR); else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
+  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) RES(float, PDE_ADR); else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
 #undef RES
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)n * NO * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2312,6 +2370,7 @@ int pinn_comm_unique_id(char* id128) {
 int pinn_comm_init(pinn_ctx* c, const char* id128, int n_ranks, int rank) {
   REQUIRE(c && id128 && n_ranks >= 1 && rank >= 0 && rank < n_ranks, "bad communicator arguments");
   if (c->sa.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: self-adaptive weights are single-device (pinn_sa_disable first)");
+  if (is_adr_ide(c)) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
   HIPCHK(hipSetDevice(c->device));
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
   xg_release(c);
@@ -2328,6 +2387,8 @@ int pinn_comm_xgmi_export(pinn_ctx* c, int n_ranks, int rank, char* handle64) {
           "bad arguments (at most %d ranks)", XG_MAX_RANKS);
   if (c->sa.on)
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: self-adaptive weights are single-device (pinn_sa_disable first)");
+  if (is_adr_ide(c))
+    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is expected to be 64 bytes");
   HIPCHK(hipSetDevice(c->device));
   xg_release(c);
@@ -2505,6 +2566,9 @@ int pinn_set_kernel_path(pinn_ctx* c, int path) {
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: self-adaptive weights run on kernel path 7 only (pinn_sa_disable first)");
   if (is_adr(c) && !adr_has_path(p))
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: the adr kind (pde 5) runs on kernel paths 0 and 7 only; path %d "
+                "(%s) has no variant for it", path, PATHS[p].name);
+  if (is_adr_ide(c) && !adr_has_path(p))
+    return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: the adr_ide kind (pde 6) runs on kernel paths 0 and 7 only; path %d "
                 "(%s) has no variant for it", path, PATHS[p].name);
   REQUIRE(PATHS[p].ok(c), "%s", PATHS[p].needs);
   c->path = p;

@@ -85,4 +85,8 @@ int fused20d_launch_any(const F20dLaunch& a, const SaArgs& sa);
 // block pair-interleaved
 int fused20d_launch_any(const F20dLaunch& a, const AdrCoef<double>& k);
 
+// one evaluation of the same kind with trainable coefficients (k_fused20d_ide<PDE_ADR_IDE, H, .>): the coefficients are the six
+// entries behind the net's scalars in th, k.mask says which of their gradient entries are written (the others are 0.0)
+int fused20d_launch_any(const F20dLaunch& a, const AdrIdeArg& k);
+
 }  // namespace pinn

@@ -74,7 +74,8 @@ template <> struct FusedTraits<double> {
 // arguments are preloaded into SGPRs: -mllvm -amdgpu-kernarg-preload-count, pinn_native.COMMON_FLAGS).  The launch
 // wrappers check the engine's NetDesc against it (w20_layout_ok).
 struct W20Desc { int off_w[MAX_DENSE]; int off_b[MAX_DENSE]; int n_net; int n_theta; };
-constexpr W20Desc w20_desc(int H, bool lambdas) {
+// (n_tail: trailing equation parameters behind the net's scalars -- 0, 2 lambdas or the six adr coefficients, pde_n_tail)
+constexpr W20Desc w20_desc(int H, int n_tail) {
   W20Desc r{};
   int off = 0, in = 2;
   for (int d = 0; d <= H; ++d) {
@@ -84,11 +85,11 @@ constexpr W20Desc w20_desc(int H, bool lambdas) {
     in = out;
   }
   r.n_net = off;
-  r.n_theta = off + (lambdas ? 2 : 0);
+  r.n_theta = off + n_tail;
   return r;
 }
-inline bool w20_layout_ok(const NetDesc& nd, int H, bool lambdas) {
-  const W20Desc w = w20_desc(H, lambdas);
+inline bool w20_layout_ok(const NetDesc& nd, int H, int n_tail) {
+  const W20Desc w = w20_desc(H, n_tail);
   if (nd.n_hidden != H || nd.width != FW || nd.n_out != 1 || nd.n_net != w.n_net || nd.n_theta != w.n_theta) return false;
   for (int d = 0; d <= H; ++d)
     if (nd.off_w[d] != w.off_w[d] || nd.off_b[d] != w.off_b[d]) return false;

@@ -200,7 +200,7 @@ __global__ PINN_F20M_BOUNDS void k_fused20m(const float* __restrict__ th, const 
                                             const float* __restrict__ tgt, float* __restrict__ part, int R,
                                             int n_tiles, float lbx, float lbt, float sx, float st, float nu,
                                             SetDesc sd, long long* __restrict__ stamps) {
-  constexpr W20Desc nd = w20_desc(H, PDE == 1);      // (pointers + R + n_tiles = the 14 preloaded argument dwords)
+  constexpr W20Desc nd = w20_desc(H, pde_n_tail(PDE));      // (pointers + R + n_tiles = the 14 preloaded argument dwords)
   constexpr int RS4 = 65;
   constexpr int BUFV = FROWS * RS4;                 // v4f elements per exchange buffer
   constexpr int NW = ((H - 1) * WIMG + 1023) / 1024 * 1024;   // floats of weight image (whole rounds of 4 DMA pieces)
@@ -590,7 +590,7 @@ inline int fused20m_launch(const NetDesc& nd, const SetDesc& sd, const float* th
                            float sx, float st, float nu, float* part, int R, int n_wg,
                            hipStream_t stream, long long* stamps = nullptr, hipEvent_t ev_start = nullptr,
                            hipEvent_t ev_stop = nullptr) {
-  if (!w20_layout_ok(nd, H, PDE == 1)) return (int)hipErrorInvalidValue;
+  if (!w20_layout_ok(nd, H, pde_n_tail(PDE))) return (int)hipErrorInvalidValue;
   const size_t lds = fused20m_lds_bytes(H);
   static unsigned long long attr_set = 0;
   if (first_call_on_device(attr_set)) {

@@ -23,7 +23,7 @@ struct NetDesc {
   int off_w[MAX_DENSE];      // offsets into the flat weight vector (reference layout)
   int off_b[MAX_DENSE];
   int n_net;                 // number of network scalars (without lambdas)
-  int n_theta;               // n_net (+2 for identification)
+  int n_theta;               // n_net (+2 for identification, +6 for PDE_ADR_IDE: pde_n_tail)
   int img_kind;              // packed weight image kept by the optimiser kernels: 0 none, 1 k_fused20m, 2 wide
 };
 
@@ -43,13 +43,30 @@ struct SetDesc {
 // every other instantiation is what it was.  Boundary pairs of this kind are stored pair-interleaved,
 // [lo_0, hi_0, lo_1, hi_1, ...]: the partner of point g is g ^ 1.
 constexpr int PDE_ADR = 3;
+// Template number of the same equation with TRAINABLE coefficients (PINN_PDE_ADR_IDE = 6 of the C interface): the six
+// coefficients are the tail of the weight vector, th[n_net + k] = a0, a1, log nu, r1, r2, r3 (nu = exp keeps it positive, as
+// PDE == 1 parametrises Burgers' viscosity), read by the kernels where PDE == 1 reads its two lambdas.  In the place of the
+// scalar nu travels one int: bit k set = coefficient k is trained; the gradient entry of a frozen coefficient is written
+// as exactly 0.0 (the optimisers then leave it where it is: Adam's m and v stay 0, every L-BFGS direction is 0 there).
+//   enum -> template value:  PINN_PDE_ADR 5 -> PDE_ADR 3,  PINN_PDE_ADR_IDE 6 -> PDE_ADR_IDE 4
+constexpr int PDE_ADR_IDE = 4;
+constexpr bool pde_is_adr(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_IDE; }
+// trailing equation parameters of the weight vector: 2 lambdas (PDE 1), six coefficients (PDE_ADR_IDE)
+constexpr int pde_n_tail(int PDE) { return PDE == 1 ? 2 : PDE == PDE_ADR_IDE ? 6 : 0; }
 template <typename real> struct AdrCoef { real a0, a1, nu, r1, r2, r3; };
+struct AdrIdeArg { int mask; };
 template <typename real, int PDE>
-using pde_coef_t = typename std::conditional<PDE == PDE_ADR, AdrCoef<real>, real>::type;
+using pde_coef_t = typename std::conditional<PDE == PDE_ADR, AdrCoef<real>,
+                                             typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, real>::type>::type;
 template <typename real> __device__ __forceinline__ real coef_nu(real nu) { return nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrCoef<real>& k) { return k.nu; }
+template <typename real> __device__ __forceinline__ real coef_nu(const AdrIdeArg&) { return real(0); }
 template <typename real> __device__ __forceinline__ AdrCoef<real> coef_adr(real) { return AdrCoef<real>{0, 0, 0, 0, 0, 0}; }
 template <typename real> __device__ __forceinline__ AdrCoef<real> coef_adr(const AdrCoef<real>& k) { return k; }
+// the current coefficients of PDE_ADR_IDE from the tail of the weight vector
+template <typename real> __device__ __forceinline__ AdrCoef<real> coef_adr_tail(const real* __restrict__ tail) {
+  return AdrCoef<real>{tail[0], tail[1], exp(tail[2]), tail[3], tail[4], tail[5]};
+}
 // residual of the new kind from the four Taylor channels of a point
 template <typename real>
 __device__ __forceinline__ real adr_residual(const AdrCoef<real>& k, const vec4<real>& o) {
@@ -161,7 +178,8 @@ __device__ __forceinline__ int point_class_adr(const SetDesc& sd, int g) {
 
 // Per-point loss contributions and output adjoints.
 //   sb[o] <- (h_bar, p_bar, q_bar, r_bar) of output o;  lt[0..2] <- (f, data, boundary) loss parts
-//   dl[0..1] <- d/d lambda_1, d/d lambda_2 contributions (identification only)
+//   dl[0..1] <- d/d lambda_1, d/d lambda_2 contributions (identification only); PDE_ADR_IDE: dl[0..5] <- d/d (a0, a1,
+//   log nu, r1, r2, r3), the caller's array holds six
 // point_seeds_own: the same with the point's OWN outputs handed in (ou, and ov for two-output nets) instead of read from
 // O -- a fused kernel has them on chip; O is read only for the partner of a periodic-boundary pair
 template <typename real, int PDE>
@@ -184,13 +202,14 @@ __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_
                                                 const vec4<real>& ov, const vec4<real>* __restrict__ O,
                                                 const real* __restrict__ tgt, real c1, real c2,
                                                 vec4<real> sb[2], real lt[3], real dl[2], const AdrCoef<real>& k) {
-  const int cls = PDE == PDE_ADR ? point_class_adr(sd, g) : point_class(sd, g);
+  const int cls = pde_is_adr(PDE) ? point_class_adr(sd, g) : point_class(sd, g);
   sb[0] = sb[1] = vec4<real>{0, 0, 0, 0};
   lt[0] = lt[1] = lt[2] = real(0);
   dl[0] = dl[1] = real(0);
+  if constexpr (PDE == PDE_ADR_IDE) dl[2] = dl[3] = dl[4] = dl[5] = real(0);
   if (cls == CLS_PAD) return;
   const real inv_nf = (real)sd.inv_nf, inv_nu = (real)sd.inv_nu, inv_nb = (real)sd.inv_nb;
-  if constexpr (PDE == PDE_ADR) {   // advection-diffusion-reaction, run-time coefficients, periodic pairs (g, g ^ 1)
+  if constexpr (pde_is_adr(PDE)) {   // advection-diffusion-reaction, run-time coefficients, periodic pairs (g, g ^ 1)
     const vec4<real> o = ou;
     if (cls == CLS_COL) {
       const real u = o.x, adv = k.a0 + k.a1 * u;
@@ -199,6 +218,10 @@ __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_
       lt[0] = f * f * inv_nf;
       sb[0].x = fb * (k.a1 * o.y + k.r1 + u * (real(2) * k.r2 + real(3) * k.r3 * u));
       sb[0].y = fb * adv; sb[0].z = fb; sb[0].w = -k.nu * fb;
+      if constexpr (PDE == PDE_ADR_IDE) {      // f is linear in a0, a1, r1, r2, r3; d nu / d log nu = nu
+        dl[0] = fb * o.y; dl[1] = fb * u * o.y; dl[2] = -fb * k.nu * o.w;
+        dl[3] = fb * u; dl[4] = fb * u * u; dl[5] = fb * u * u * u;
+      }
     } else if (cls == CLS_DATA) {
       const real dd = o.x - tgt[g];
       lt[1] = dd * dd * inv_nu;
@@ -307,8 +330,9 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
   if (PDE == 1) { c1 = th[nd.n_net]; c2 = exp(th[nd.n_net + 1]); }
 
   vec4<real> sb[2];
-  real lt[3], dl[2];
+  real lt[3], dl[PDE == PDE_ADR_IDE ? 6 : 2];
   if constexpr (PDE == PDE_ADR) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr<real>(nu));
+  else if constexpr (PDE == PDE_ADR_IDE) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr_tail<real>(th + nd.n_net));
   else point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl);
 
   auto put = [&](int idx, real v) {   // lane-uniform idx; executed by one lane
@@ -320,6 +344,13 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
     if (PDE == 1) {
       const real g1 = wave_sum(dl[0]), g2 = wave_sum(dl[1]);
       if (lane == 0) { put(nd.n_net, g1); put(nd.n_net + 1, g2); }
+    }
+    if constexpr (PDE == PDE_ADR_IDE) {      // the six tail entries; a frozen coefficient's is exactly 0.0
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        const real gk = wave_sum(dl[k]);
+        if (lane == 0) put(nd.n_net + k, ((nu.mask >> k) & 1) ? gk : real(0));
+      }
     }
   }
 
@@ -433,6 +464,8 @@ __global__ void k_residual(int first, int n, int n_pad, const vec4<real>* __rest
   const int g = first + i;
   if constexpr (PDE == PDE_ADR) {
     f[i] = (double)adr_residual(nu, O[g]);
+  } else if constexpr (PDE == PDE_ADR_IDE) {
+    f[i] = (double)adr_residual(coef_adr_tail<real>(th + n_net), O[g]);
   } else if (PDE == 2) {
     const vec4<real> ou = O[g], ov = O[(size_t)n_pad + g];
     const real u = ou.x, v = ov.x, h2 = u * u + v * v;

@@ -16,12 +16,41 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _REPO = os.path.dirname(os.path.dirname(_HERE))
 LIB_PATH = os.environ.get("PINN_HIP_LIB") or os.path.join(_HERE, "libpinn_hip.so")
-SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_wide.h", "kernels_predict20.h",
+SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_fused20d_kernel.h", "kernels_wide.h", "kernels_predict20.h",
            "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h"]
 HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
 PDE_KINDS = {"burgers": 0, "burgers_ide": 1, "schrodinger": 2, "burgers_disc": 3, "burgers_disc_ide": 4, "adr": 5}
+# the kinds added since, in a table of their own: PDE_KINDS is pinned as the six kinds 0..5 (tests/test_adr_host.py)
+PDE_KINDS_MORE = {"adr_ide": 6}
+
+
+def pde_kind(name):
+    """name -> enum value of include/pinn_hip.h (PDE_KINDS and PDE_KINDS_MORE); ValueError with the table otherwise"""
+    kinds = dict(PDE_KINDS, **PDE_KINDS_MORE)
+    if name not in kinds:
+        raise ValueError("pde must be one of %s" % sorted(kinds))
+    return kinds[name]
+
+
 DTYPES = {"f32": 0, "f64": 1, "float32": 0, "float64": 1}
+
+ADR_COEFF_NAMES = ("a0", "a1", "nu", "r1", "r2", "r3")     # order of the coefficients, and of the tail of "adr_ide" weights
+
+
+def adr_trainable_mask(names_or_mask):
+    """names from ADR_COEFF_NAMES (or an int mask, passed through) -> bit mask of pinn_set_pde_trainable"""
+    if isinstance(names_or_mask, (int, np.integer)):
+        return int(names_or_mask)
+    if isinstance(names_or_mask, str):
+        names_or_mask = [names_or_mask]
+    mask = 0
+    for name in names_or_mask:
+        if name not in ADR_COEFF_NAMES:
+            raise ValueError("unknown adr coefficient %r: choose from %s" % (name, ", ".join(ADR_COEFF_NAMES)))
+        mask |= 1 << ADR_COEFF_NAMES.index(name)
+    return mask
+
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -164,6 +193,8 @@ _SIGNATURES = {
     "pinn_set_boundary": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p,
                                          ctypes.c_int64, ctypes.c_int64]),
     "pinn_set_pde_params": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int]),
+    "pinn_get_pde_params": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int]),
+    "pinn_set_pde_trainable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "pinn_set_weights": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
     "pinn_get_weights": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
     "pinn_loss_grad": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p]),
@@ -402,8 +433,7 @@ class Engine(object):
     def __init__(self, layers, lb, ub, pde="burgers", dtype="f32", device=0):
         self._lib = load()
         self._h = ctypes.c_void_p()
-        if pde not in PDE_KINDS:
-            raise ValueError("pde must be one of %s" % sorted(PDE_KINDS))
+        kind = pde_kind(pde)
         if dtype not in DTYPES:
             raise ValueError("dtype must be one of %s" % sorted(DTYPES))
         self.layers = [int(v) for v in layers]
@@ -413,7 +443,7 @@ class Engine(object):
         self.n_in = self.layers[0]
         lb, ub = _f64(lb, (self.n_in,)), _f64(ub, (self.n_in,))
         self._check(self._lib.pinn_create(ctypes.byref(self._h), arr, len(self.layers), _dp(lb),
-                                          _dp(ub), PDE_KINDS[pde], DTYPES[dtype], int(device)))
+                                          _dp(ub), kind, DTYPES[dtype], int(device)))
         n = ctypes.c_int64(0)
         self._check(self._lib.pinn_num_params(self._h, ctypes.byref(n)))
         self.n_params = n.value
@@ -500,6 +530,18 @@ class Engine(object):
     def set_pde_params(self, *p):
         p = _f64(p)
         self._check(self._lib.pinn_set_pde_params(self._h, _dp(p), p.size))
+
+    def get_pde_params(self):
+        """the current raw equation parameters: six coefficients (a0, a1, nu, r1, r2, r3) for "adr" and "adr_ide" (the
+        trained values, nu = exp of the stored log nu), [nu] otherwise"""
+        p = np.empty(6 if self.pde in ("adr", "adr_ide") else 1, dtype=np.float64)
+        self._check(self._lib.pinn_get_pde_params(self._h, _dp(p), p.size))
+        return p
+
+    def set_pde_trainable(self, names_or_mask):
+        """pde "adr_ide": which coefficients are trained -- names from ADR_COEFF_NAMES or a bit mask (bit k = name k); the
+        others stay frozen at their values, bit for bit"""
+        self._check(self._lib.pinn_set_pde_trainable(self._h, adr_trainable_mask(names_or_mask)))
 
     # ---- weights ---------------------------------------------------------------------------
     def set_weights(self, w):
@@ -759,8 +801,7 @@ class Ensemble(object):
     def __init__(self, layers, lb, ub, n_members, pde="burgers", dtype="f64", device=0):
         self._lib = load()
         self._h = ctypes.c_void_p()
-        if pde not in PDE_KINDS:
-            raise ValueError("pde must be one of %s" % sorted(PDE_KINDS))
+        kind = pde_kind(pde)
         if dtype not in DTYPES:
             raise ValueError("dtype must be one of %s" % sorted(DTYPES))
         self.layers = [int(v) for v in layers]
@@ -768,7 +809,7 @@ class Ensemble(object):
         arr = (ctypes.c_int * len(self.layers))(*self.layers)
         lb, ub = _f64(lb, (2,)), _f64(ub, (2,))
         self._check(self._lib.pinn_ens_create(ctypes.byref(self._h), arr, len(self.layers), _dp(lb), _dp(ub),
-                                              PDE_KINDS[pde], DTYPES[dtype], int(device), int(n_members)))
+                                              kind, DTYPES[dtype], int(device), int(n_members)))
         k, n = ctypes.c_int(0), ctypes.c_int64(0)
         self._check(self._lib.pinn_ens_size(self._h, ctypes.byref(k), ctypes.byref(n)))
         self.n_members, self.n_params = k.value, n.value

@@ -10,8 +10,9 @@ return shapes (numpy arrays where the reference returns eager tensors).
 
 What changes: there is no TensorFlow, so a subclass cannot spell its PDE with GradientTapes.
 It names one of the engine's residual kinds instead (`pde="burgers" | "burgers_ide" |
-"schrodinger" | "burgers_disc" | "burgers_disc_ide" | "adr"`; the last is u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 = 0
-with fixed coefficients the subclass hands to `self._engine.set_pde_params(a0, a1, nu, r1, r2, r3)`) and the engine evaluates forward, u_t/u_x/u_xx, residual, loss and the flat
+"schrodinger" | "burgers_disc" | "burgers_disc_ide" | "adr" | "adr_ide"`; "adr" is u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 = 0
+with fixed coefficients the subclass hands to `self._engine.set_pde_params(a0, a1, nu, r1, r2, r3)`, "adr_ide" the same
+equation with the coefficients named in hp["adr_trainable"] learned from the data, see _adr_ide_options) and the engine evaluates forward, u_t/u_x/u_xx, residual, loss and the flat
 gradient on the GPU (csrc/).  Extra, optional hp keys: "dtype" ("f64" default = the reference's
 arithmetic, neuralnetwork.py:24-26 | "f32" = the throughput mode north_star sanctions) for the
 kernel arithmetic, "device" (HIP ordinal), "nt_guard" (see nt_optimization), "resample_every" / "resample" / "rad_*"
@@ -80,7 +81,7 @@ def _resample_options(hp, pde):
     if mode == "rad":
         if int(hp.get("resample_every", 0)) <= 0:
             raise ValueError('hp["resample"] = "rad" redraws every hp["resample_every"] epochs; resample_every must be > 0')
-        if pde not in ("burgers", "schrodinger", "adr"):
+        if pde not in ("burgers", "schrodinger", "adr", "adr_ide"):
             raise ValueError('hp["resample"] = "rad" needs a collocation set; the %s model has none' % pde)
     return mode, int(k), float(c), None if pool is None else int(pool)
 
@@ -115,6 +116,32 @@ def _sa_options(hp, pde):
     if not (np.isfinite(init_u) and np.isfinite(init_f)):
         raise ValueError('hp["sa_init"] must be finite (got %r)' % (init,))
     return float(lr), init_u, init_f
+
+
+ADR_NAMES = ("a0", "a1", "nu", "r1", "r2", "r3")
+
+
+def _adr_ide_options(hp):
+    """pde "adr_ide" (the adr equation with trainable coefficients): hp["adr_trainable"] = names from a0, a1, nu, r1, r2, r3
+    (default: none; the others stay frozen at their start values, bit for bit), hp["adr_init"] = the six raw start values
+    (default Burgers', [0, 1, 0.01 / pi, 0, 0, 0]; nu > 0 because its logarithm is what is trained).  Refused here, before any
+    device work, with the offending key named.  -> (names in the order of ADR_NAMES, six floats)"""
+    names = hp.get("adr_trainable", [])
+    if isinstance(names, str) or not isinstance(names, (list, tuple)):
+        raise ValueError('hp["adr_trainable"] must be a list of names from %s (got %r)' % (", ".join(ADR_NAMES), names))
+    for n in names:
+        if n not in ADR_NAMES:
+            raise ValueError('hp["adr_trainable"]: unknown coefficient %r; choose from %s' % (n, ", ".join(ADR_NAMES)))
+    init = hp.get("adr_init", [0.0, 1.0, 0.01 / np.pi, 0.0, 0.0, 0.0])
+    try:
+        init = [float(v) for v in init]
+    except (TypeError, ValueError):
+        raise ValueError('hp["adr_init"] must be six numbers [a0, a1, nu, r1, r2, r3] (got %r)' % (init,))
+    if len(init) != 6 or not all(np.isfinite(v) for v in init):
+        raise ValueError('hp["adr_init"] must be six finite numbers [a0, a1, nu, r1, r2, r3] (got %r)' % (init,))
+    if not init[2] > 0.0:
+        raise ValueError('hp["adr_init"]: nu (entry 2) must be > 0, its logarithm is the trained parameter (got %r)' % (init[2],))
+    return tuple(n for n in ADR_NAMES if n in names), tuple(init)
 
 
 class _AdamConfig(object):
@@ -177,6 +204,7 @@ class NeuralNetwork(object):
             self.pde = pde
         self._resample, self._rad_k, self._rad_c, self._rad_pool = _resample_options(hp, self.pde)
         self._sa = _sa_options(hp, self.pde)
+        self._adr_ide = _adr_ide_options(hp) if self.pde == "adr_ide" else None
 
         # L-BFGS configuration, same fields as the reference (neuralnetwork.py:13-17)
         self.nt_config = Struct()
@@ -196,9 +224,9 @@ class NeuralNetwork(object):
 
         # one rank of a torchrun launch = one shard of the point sets on GPU LOCAL_RANK (module docstring); the
         # discrete-time models hold <= 256 points and stay replicated
-        if self.pde == "adr" and parallel.env_world()[0] > 1 and bool(hp.get("data_parallel", True)):
-            raise ValueError('pde "adr": a data-parallel launch (world > 1) is not supported for this kind; run one process, '
-                             'or set hp["data_parallel"] = false for independent replicas')
+        if self.pde in ("adr", "adr_ide") and parallel.env_world()[0] > 1 and bool(hp.get("data_parallel", True)):
+            raise ValueError('pde "%s": a data-parallel launch (world > 1) is not supported for this kind; run one process, '
+                             'or set hp["data_parallel"] = false for independent replicas' % self.pde)
         self._dp = None if self.pde.startswith("burgers_disc") else parallel.from_env(bool(hp.get("data_parallel", True)))
         self.is_root = parallel.is_root()
         world, _, local_rank = parallel.env_world()
@@ -221,6 +249,8 @@ class NeuralNetwork(object):
                 self.sizes_b.append(int(width if i != 0 else self.layers[1]))
 
         self._engine.set_weights(self._initial_weights(hp))
+        if self._adr_ide:
+            self._engine.set_pde_trainable(list(self._adr_ide[0]))
         if hp.get("init_weights"):                   # resume from a checkpoint written by save_weights
             self.load_weights(hp["init_weights"])
         self._engine.adam_init(self.tf_optimizer.learning_rate, self.tf_optimizer.beta_1,
@@ -275,7 +305,12 @@ class NeuralNetwork(object):
         return sum(fi * fo + fo for fi, fo in zip(self.layers[:-1], self.layers[1:]))
 
     def _extra_params(self):
-        """Trainable scalars appended after the network weights (identification: lambdas)."""
+        """Trainable scalars appended after the network weights (identification: lambdas; "adr_ide": the six coefficients,
+        log nu in the nu slot)."""
+        if self._adr_ide:
+            tail = np.array(self._adr_ide[1], dtype=np.float64)
+            tail[2] = np.log(tail[2])
+            return tail
         return np.zeros(0)
 
     def _initial_weights(self, hp):
@@ -346,10 +381,17 @@ class NeuralNetwork(object):
         return self._split(self._engine.get_weights())
 
     def get_params(self, numpy=False):
+        if self._adr_ide:                        # the six raw coefficients as training has left them
+            p = self._engine.get_pde_params()
+            return tuple(float(v) for v in p) if numpy else tuple(p)
         return []
 
     def _log_custom(self):
-        """Text appended to a logged progress line (the identification scripts print their lambdas)."""
+        """Text appended to a logged progress line (the identification scripts print their lambdas; "adr_ide": the
+        trainable coefficients)."""
+        if self._adr_ide and self._adr_ide[0]:
+            p = self._engine.get_pde_params()
+            return "  " + "  ".join("%s = %.5e" % (n, p[ADR_NAMES.index(n)]) for n in self._adr_ide[0])
         return ""
 
     def get_weights(self, convert_to_tensor=True):
@@ -426,7 +468,7 @@ class NeuralNetwork(object):
         the enqueue / collect pair (_adam_chunk alone), periodic resampling.  The restart guard goes along: its way back is a device-side snapshot behind every chunk."""
         cls = type(self)
         chunk_ok = cls._adam_chunk is NeuralNetwork._adam_chunk or cls._adam_collect is not NeuralNetwork._adam_collect
-        return (self._async_log and cls._log_custom is NeuralNetwork._log_custom and chunk_ok
+        return (self._async_log and cls._log_custom is NeuralNetwork._log_custom and not self._adr_ide and chunk_ok
                 and hasattr(self._engine, "adam_enqueue"))
 
     def _log_boundaries(self, total, freq):

@@ -44,7 +44,7 @@ def kernels_of(lib):
                 if cur is not None and line[:1] in " \t" and line.strip():
                     ins = line.split("//")[0].strip()
                     ins = re.sub(r"<[^>]*\+0x[0-9a-f]+>", "", ins)
-                    if ins:
+                    if ins and ins != "...":         # ("...": the disassembler's mark for the zero padding behind a kernel)
                         cur.append(ins)
             notes = run(os.path.join(LLVM, "llvm-readelf"), "--notes", path)
             for blk in notes.split("- .agpr_count:")[1:]:

@@ -366,6 +366,36 @@ int pinn_sa_get_weights(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, 
 int pinn_sa_adam_init(pinn_ctx* c, double lr);
 int pinn_sa_disable(pinn_ctx* c);
 
+/* Per-point loss weights of the adr kind (PINN_PDE_ADR), fixed or self-adaptive (McClenny & Braga-Neto, arXiv:2009.04544):
+ *   L = (1/N_f) sum_i lam_f,i^2 f_i^2 + (1/N_u) sum_j lam_u,j^2 (u_j - u*_j)^2
+ *       + (1/N_b) sum_p lam_b,p^2 [(u(lo_p) - u(hi_p))^2 + (u_x(lo_p) - u_x(hi_p))^2]
+ * with the global denominators of the plain loss; a periodic pair has ONE weight.  pinn_loss_grad's terms are the three
+ * weighted parts.  A static term weight W on a class is lam = sqrt(W) on its points with rate 0.  With a rate above 0 every
+ * Adam step descends in the network weights and ascends in that class's lam from one evaluation:
+ * dL/dlam = 2 lam r^2 / N (r^2 = f^2, (u - u*)^2 or a pair's two squares), stepped by
+ * rate sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps) with the step counter, b1, b2 and eps of pinn_adam_init; every lam has
+ * its own moments, a class with rate 0 is not touched.  The ascent runs inside the loss+gradient kernel (no extra launch).
+ * L-BFGS, pinn_loss_grad, pinn_predict, pinn_error_l2, pinn_residual, pinn_residual_at and pinn_rad_collocation read the
+ * weights and never move them; the residual calls and the adaptive draw see the unweighted f.
+ *   pinn_pw_set        enables the weighted loss; lam_u [n_u] in the order of pinn_set_data's rows, lam_f [n_f] in the order
+ *                      of the collocation set (what pinn_get_collocation returns), lam_b [n_b] one per pair in the order of
+ *                      pinn_set_boundary's rows.  The counts must equal the current local set sizes (0 for an empty set);
+ *                      a NULL array with the right count means all ones.  Zeroes all moments.
+ *   pinn_pw_get        reads them back (same shapes; a NULL array is skipped); PINN_EINVAL while the weights are off
+ *   pinn_pw_adam_init  the ascent's rates per class (default 0, 0, 0: fixed weights)
+ *   pinn_pw_disable    back to the plain kernel: results bit-identical to a context that never enabled the weights
+ * pinn_set_collocation, pinn_lhs_collocation and pinn_rad_collocation reset the collocation weights to 1 and their moments to
+ * 0, pinn_set_data the data weights, pinn_set_boundary the pairs'; the other classes keep theirs.  Refusals, before any
+ * device work, the context unchanged: PINN_EUNSUPPORTED for any kind but PINN_PDE_ADR, float32, a kernel path other than 7 or
+ * a communicator (pinn_comm_init, pinn_comm_xgmi_export and pinn_set_kernel_path to another path are refused the same way
+ * while the weights are on); PINN_EINVAL for counts that differ from the set sizes, non-finite weights, a negative or
+ * non-finite rate.  (Additive: the ABI version stays 6.) */
+int pinn_pw_set(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam_f, int64_t n_f, const double* lam_b,
+                int64_t n_b);
+int pinn_pw_get(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, int64_t n_f, double* lam_b, int64_t n_b);
+int pinn_pw_adam_init(pinn_ctx* c, double rate_u, double rate_f, double rate_b);
+int pinn_pw_disable(pinn_ctx* c);
+
 #ifdef __cplusplus
 }
 #endif

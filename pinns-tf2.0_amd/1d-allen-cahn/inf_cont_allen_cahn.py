@@ -8,6 +8,12 @@ dict or JSON file, prep_data, a Logger whose error metric is reduced on the devi
 engine's "adr" kind, f = u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 with [0, 0, 1e-4, -5, 0, 5]; the loss is
 mean f^2 + mean (u - u0)^2 at the initial points + mean [(u(-1,t) - u(1,t))^2 + (u_x(-1,t) - u_x(1,t))^2] over the wall pairs.
 The exact field comes from allencahnutil's Fourier split-step solver, computed at start-up and cached under results/.
+
+Loss weights (hp["point_weights"], utils/neuralnetwork.py _pw_options; off in the default hp).  The two usual recipes for this
+equation, whose plain loss tends to settle in u = 0:
+    a fixed weight W on the initial condition   "point_weights": true, "pw_init": [sqrt(W), 1, 1]       (e.g. [10, 1, 1])
+    self-adaptive weights (arXiv:2009.04544)    "point_weights": true, "pw_lr": [lr_0, lr_f, 0]         (e.g. [0.05, 0.01, 0])
+pw_init / pw_lr are [initial points, collocation points, wall pairs]; fit() prints where the weights ended.
 """
 import json
 import os

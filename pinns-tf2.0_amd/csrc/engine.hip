@@ -250,6 +250,17 @@ struct pinn_ctx {
     int n_u = 0, n_f = 0;
     double k[3] = {0.0, 0.0, 0.0};
   } sa;
+  // per-point loss weights of the adr kind (pinn_pw_*, k_fused20d_pw): the device array of fused20d_api.h (PW_CONST header,
+  // then (lambda, m, v) by point index), laid out for n_b pairs, n_u data and n_f collocation points; hdr: the header as
+  // uploaded; reset_*: that class's set was replaced since (pw_prepare puts its weights back to 1)
+  struct {
+    bool on = false, reset_u = false, reset_f = false, reset_b = false;
+    double rate[3] = {0.0, 0.0, 0.0};          // data, collocation, pairs
+    double* buf = nullptr;
+    size_t cap = 0;
+    int n_b = 0, n_u = 0, n_f = 0;
+    double hdr[PW_CONST] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  } pw;
 
   // discrete-time models (pde 3, 4): stage sets as handed over, device copies, scratch
   struct DiscSet { std::vector<double> x, t, M; int q = 0; bool has_M = false; };
@@ -553,6 +564,7 @@ struct AdamFuse {          // single-GPU Adam step applied by the reduction kern
   double alpha;
   double* loss3;
   double alpha_sa = 0.0;   // self-adaptive weights: the ascent's step size, applied by the evaluation kernel (0: none)
+  double bc_pw = 0.0;      // adr point weights: the step's bias-correction factor sqrt(1 - b2^t) / (1 - b1^t) (0: none)
 };
 
 // self-adaptive weights: (re)build the device array for the assembled set when a class's set was replaced (its weights
@@ -585,6 +597,59 @@ static int sa_prepare(pinn_ctx* c) {
   HIPCHK(hipStreamSynchronize(c->stream));
   c->sa.n_u = sd.n_u; c->sa.n_f = sd.n_f; c->sa.reset_u = c->sa.reset_f = false;
   c->sa.k[0] = c->b1; c->sa.k[1] = c->b2; c->sa.k[2] = c->eps;
+  return 0;
+}
+
+// adr point weights: the header of the device array as the kernel reads it (fused20d_api.h: the rate at 3 + point class)
+static void pw_header(const pinn_ctx* c, double* h) {
+  for (int i = 0; i < PW_CONST; ++i) h[i] = 0.0;
+  h[0] = c->b1; h[1] = c->b2; h[2] = c->eps;
+  h[3 + CLS_BLO] = c->pw.rate[2]; h[3 + CLS_DATA] = c->pw.rate[0]; h[3 + CLS_COL] = c->pw.rate[1];
+}
+
+// adr point weights: (re)build the device array for the assembled set when a class's set was replaced (its weights back to
+// 1, its moments to 0; the other classes keep theirs), or rewrite its header when the ascent's constants or rates changed.
+// Synchronous, and only then: the common case returns at once.
+static int pw_prepare(pinn_ctx* c) {
+  const SetDesc& sd = c->sd;
+  const bool keep_b = c->pw.buf && !c->pw.reset_b && c->pw.n_b == sd.n_b;
+  const bool keep_u = c->pw.buf && !c->pw.reset_u && c->pw.n_u == sd.n_u;
+  const bool keep_f = c->pw.buf && !c->pw.reset_f && c->pw.n_f == sd.n_f;
+  double hdr[PW_CONST];
+  pw_header(c, hdr);
+  if (keep_b && keep_u && keep_f) {
+    if (memcmp(hdr, c->pw.hdr, sizeof hdr) == 0) return 0;
+    HIPCHK(hipMemcpyAsync(c->pw.buf, hdr, sizeof hdr, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(c->pw.hdr, hdr, sizeof hdr);
+    return 0;
+  }
+  std::vector<double> old;
+  if (keep_b || keep_u || keep_f) {
+    old.resize(pw_doubles(2 * c->pw.n_b + c->pw.n_u + c->pw.n_f));
+    HIPCHK(hipMemcpyAsync(old.data(), c->pw.buf, old.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  std::vector<double> h(pw_doubles(sd.n_all), 0.0);
+  memcpy(h.data(), hdr, sizeof hdr);
+  // class by class: n points from old index o0 to new index n0
+  auto fill = [&](bool keep, size_t n0, size_t o0, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+      for (int e = 0; e < 3; ++e)
+        h[PW_CONST + 3 * (n0 + i) + e] = keep ? old[PW_CONST + 3 * (o0 + i) + e] : (e == 0 ? 1.0 : 0.0);
+  };
+  fill(keep_b, 0, 0, (size_t)2 * sd.n_b);
+  fill(keep_u, (size_t)2 * sd.n_b, (size_t)2 * c->pw.n_b, (size_t)sd.n_u);
+  fill(keep_f, (size_t)2 * sd.n_b + sd.n_u, (size_t)2 * c->pw.n_b + c->pw.n_u, (size_t)sd.n_f);
+  if (h.size() * 8 > c->pw.cap) {
+    if (dev_alloc(&c->pw.buf, h.size() * 8)) return PINN_EHIP;
+    c->pw.cap = h.size() * 8;
+  }
+  HIPCHK(hipMemcpyAsync(c->pw.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->pw.n_b = sd.n_b; c->pw.n_u = sd.n_u; c->pw.n_f = sd.n_f;
+  c->pw.reset_b = c->pw.reset_u = c->pw.reset_f = false;
+  memcpy(c->pw.hdr, hdr, sizeof hdr);
   return 0;
 }
 
@@ -750,8 +815,13 @@ static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   if constexpr (sizeof(real) == 8 && PDE != 2) {
     const bool weighted = PDE == 0 && c->sa.on;     // an Adam step moves the weights too
     if (weighted) { if (int e = sa_prepare(c)) return e; }
+    const bool pw = PDE == PDE_ADR && c->pw.on;      // the adr kind's point weights; an Adam step moves them too
+    if (pw) { if (int e = pw_prepare(c)) return e; }
     const F20dLaunch a = fused20d_args(c, ev4);
-    if constexpr (PDE == PDE_ADR) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR>(c));
+    if constexpr (PDE == PDE_ADR) {
+      if (pw) rc = fused20d_launch_any(a, AdrPwArgs{pde_coef<double, PDE_ADR>(c), c->pw.buf, af ? af->bc_pw : 0.0});
+      else rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR>(c));
+    }
     else if constexpr (PDE == PDE_ADR_IDE) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_IDE>(c));
     else if (weighted) rc = fused20d_launch_any(a, SaArgs{(double)c->nu, c->sa.buf, af ? af->alpha_sa : 0.0});
     else rc = fused20d_launch_any(PDE, a, (double)c->nu);
@@ -1559,7 +1629,7 @@ int pinn_destroy(pinn_ctx* c) {
                   c->O, c->ZA, c->ZB, c->part, c->xe, c->te, c->Oe, c->f_out, c->loss_hist, c->snap,
                   c->lb_state, c->lb_x, c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al,
                   c->lb_q, c->lb_log_loss, c->lb_log_iter, c->lb_SY, c->lb_YY, c->lb_dots, c->lb_cs,
-                  c->lb_cy, c->lb_ex, c->img, c->row_index, c->sa.buf, c->d_ginfo, c->d_M[0], c->d_M[1], c->d_MT[0], c->d_MT[1],
+                  c->lb_cy, c->lb_ex, c->img, c->row_index, c->sa.buf, c->pw.buf, c->d_ginfo, c->d_M[0], c->d_M[1], c->d_MT[0], c->d_MT[1],
                   c->d_Ast, c->d_A3, c->d_U3, c->d_Nn, c->d_R, c->d_dAp, c->d_lossp, c->d_lamp,
                   c->pred, c->d_ref, c->err_partial, c->err_res, c->d_nonfinite, c->t16_bsync, c->t16_gscr,
                   c->rad.cx, c->rad.ct, c->rad.px, c->rad.pt, c->rad.O, c->rad.f, c->rad.w, c->rad.bsum, c->rad.tot};
@@ -1591,6 +1661,7 @@ int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_to
   c->lhs.on = false;
   c->rad.on = false;
   c->sa.reset_f = true;
+  c->pw.reset_f = true;
   c->sets_dirty = true;
   return 0;
 }
@@ -1606,6 +1677,7 @@ int pinn_lhs_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   c->lhs.on = true; c->lhs.n_design = n_design; c->lhs.first = first; c->lhs.count = count; c->lhs.seed = seed;
   c->rad.on = false;
   c->sa.reset_f = true;
+  c->pw.reset_f = true;
   c->Xf.clear();
   c->nf_total = n_design;
   c->sd.inv_nf = 1.0 / (double)n_design;
@@ -1632,6 +1704,7 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   c->lhs.on = false;
   c->rad.on = true; c->rad.n_design = n_design; c->rad.first = first; c->rad.count = count;
   c->sa.reset_f = true;
+  c->pw.reset_f = true;
   c->Xf.clear();
   c->nf_total = n_design;
   c->sd.inv_nf = 1.0 / (double)n_design;
@@ -1672,6 +1745,7 @@ int pinn_set_data(pinn_ctx* c, const double* X_u, const double* u, int64_t n, in
   c->U.assign(u, u + (size_t)c->nd.n_out * n);
   c->nu_total = n_total;
   c->sa.reset_u = true;
+  c->pw.reset_u = true;
   c->sets_dirty = true;
   return 0;
 }
@@ -1683,6 +1757,7 @@ int pinn_set_boundary(pinn_ctx* c, const double* X_lb, const double* X_ub, int64
   c->Xlo.assign(X_lb, X_lb + 2 * n);
   c->Xhi.assign(X_ub, X_ub + 2 * n);
   c->nb_total = n_total;
+  c->pw.reset_b = true;
   c->sets_dirty = true;
   return 0;
 }
@@ -1876,6 +1951,8 @@ static int adam_issue(pinn_ctx* c, int n_steps, bool record, int* ticket) {
       AdamFuse af{alpha, slot};
       if (c->sa.on && c->sa.lr > 0.0)             // self-adaptive weights: the ascent, same counter, same form
         af.alpha_sa = c->sa.lr * std::sqrt(1.0 - std::pow(c->b2, t)) / (1.0 - std::pow(c->b1, t));
+      if (c->pw.on && (c->pw.rate[0] > 0.0 || c->pw.rate[1] > 0.0 || c->pw.rate[2] > 0.0))   // adr point weights, likewise
+        af.bc_pw = std::sqrt(1.0 - std::pow(c->b2, t)) / (1.0 - std::pow(c->b1, t));
       int rc = eval_loss_grad(c, &af);
       if (rc) return rc;
       continue;
@@ -2370,6 +2447,7 @@ int pinn_comm_unique_id(char* id128) {
 int pinn_comm_init(pinn_ctx* c, const char* id128, int n_ranks, int rank) {
   REQUIRE(c && id128 && n_ranks >= 1 && rank >= 0 && rank < n_ranks, "bad communicator arguments");
   if (c->sa.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: self-adaptive weights are single-device (pinn_sa_disable first)");
+  if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: point weights are single-device (pinn_pw_disable first)");
   if (is_adr_ide(c)) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
   HIPCHK(hipSetDevice(c->device));
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
@@ -2387,6 +2465,8 @@ int pinn_comm_xgmi_export(pinn_ctx* c, int n_ranks, int rank, char* handle64) {
           "bad arguments (at most %d ranks)", XG_MAX_RANKS);
   if (c->sa.on)
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: self-adaptive weights are single-device (pinn_sa_disable first)");
+  if (c->pw.on)
+    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: point weights are single-device (pinn_pw_disable first)");
   if (is_adr_ide(c))
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is expected to be 64 bytes");
@@ -2564,6 +2644,8 @@ int pinn_set_kernel_path(pinn_ctx* c, int path) {
   const KernelPath p = (KernelPath)path;
   if (c->sa.on && p != KP_FUSED20D)
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: self-adaptive weights run on kernel path 7 only (pinn_sa_disable first)");
+  if (c->pw.on && p != KP_FUSED20D)
+    return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: point weights run on kernel path 7 only (pinn_pw_disable first)");
   if (is_adr(c) && !adr_has_path(p))
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: the adr kind (pde 5) runs on kernel paths 0 and 7 only; path %d "
                 "(%s) has no variant for it", path, PATHS[p].name);
@@ -2724,6 +2806,94 @@ int pinn_sa_disable(pinn_ctx* c) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// per-point loss weights of the adr kind (include/pinn_hip.h pinn_pw_*; k_fused20d_pw, fused20d_api.h)
+// ------------------------------------------------------------------------------------------
+// what the weighted kernel serves: the adr kind in float64 on kernel path 7, one device; checked before any device work
+static int pw_supported(const pinn_ctx* c, const char* who) {
+  if (c->pde != PINN_PDE_ADR) return fail(PINN_EUNSUPPORTED, "%s: point weights are for the adr kind (pde 5) only", who);
+  if (c->dtype != PINN_F64) return fail(PINN_EUNSUPPORTED, "%s: point weights need float64", who);
+  if (c->path != KP_FUSED20D)
+    return fail(PINN_EUNSUPPORTED, "%s: point weights need kernel path 7 (this context runs path %d)", who, (int)c->path);
+  if (c->comm || c->xg.box)
+    return fail(PINN_EUNSUPPORTED, "%s: point weights are single-device; this context has a communicator", who);
+  return 0;
+}
+
+// counts against the local set sizes as ensure_sets will assemble them; a NULL array is allowed with the right count
+static int pw_check_counts(const pinn_ctx* c, const char* who, int64_t n_u, int64_t n_f, int64_t n_b) {
+  int64_t cu, cf;
+  sa_counts(c, &cu, &cf);
+  const int64_t cb = (int64_t)(c->Xlo.size() / 2);
+  REQUIRE(n_u == cu && n_f == cf && n_b == cb,
+          "%s: %lld / %lld / %lld weights for %lld data points, %lld collocation points and %lld boundary pairs", who,
+          (long long)n_u, (long long)n_f, (long long)n_b, (long long)cu, (long long)cf, (long long)cb);
+  return 0;
+}
+
+int pinn_pw_set(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam_f, int64_t n_f, const double* lam_b,
+                int64_t n_b) {
+  REQUIRE(c, "null");
+  if (int rc = pw_supported(c, "pinn_pw_set")) return rc;
+  if (int rc = pw_check_counts(c, "pinn_pw_set", n_u, n_f, n_b)) return rc;
+  for (int64_t j = 0; lam_u && j < n_u; ++j) REQUIRE(std::isfinite(lam_u[j]), "pinn_pw_set: lam_u[%lld] is not finite", (long long)j);
+  for (int64_t i = 0; lam_f && i < n_f; ++i) REQUIRE(std::isfinite(lam_f[i]), "pinn_pw_set: lam_f[%lld] is not finite", (long long)i);
+  for (int64_t p = 0; lam_b && p < n_b; ++p) REQUIRE(std::isfinite(lam_b[p]), "pinn_pw_set: lam_b[%lld] is not finite", (long long)p);
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = ensure_sets(c)) return rc;
+  const SetDesc& sd = c->sd;
+  std::vector<double> h(pw_doubles(sd.n_all), 0.0);
+  pw_header(c, h.data());
+  // a pair's weight lives in the lo point's entry: both lanes read it, the lo lane steps it, pinn_pw_get returns it.  The hi
+  // point's entry is never read; it gets the same start value on purpose, as pw_prepare's class-wide reset writes both, so
+  // that a dump of the array shows no stray value
+  for (int64_t p = 0; p < 2 * n_b; ++p) h[PW_CONST + 3 * p] = lam_b ? lam_b[p / 2] : 1.0;
+  for (int64_t j = 0; j < n_u; ++j) h[PW_CONST + 3 * (2 * n_b + j)] = lam_u ? lam_u[j] : 1.0;
+  for (int64_t i = 0; i < n_f; ++i) h[PW_CONST + 3 * (2 * n_b + n_u + i)] = lam_f ? lam_f[i] : 1.0;
+  if (h.size() * 8 > c->pw.cap) {
+    if (dev_alloc(&c->pw.buf, h.size() * 8)) return PINN_EHIP;
+    c->pw.cap = h.size() * 8;
+  }
+  HIPCHK(hipMemcpyAsync(c->pw.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->pw.n_b = sd.n_b; c->pw.n_u = sd.n_u; c->pw.n_f = sd.n_f;
+  c->pw.reset_b = c->pw.reset_u = c->pw.reset_f = false;
+  memcpy(c->pw.hdr, h.data(), sizeof c->pw.hdr);
+  c->pw.on = true;
+  return 0;
+}
+
+int pinn_pw_get(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, int64_t n_f, double* lam_b, int64_t n_b) {
+  REQUIRE(c, "null");
+  REQUIRE(c->pw.on, "pinn_pw_get: point weights are off (pinn_pw_set)");
+  if (int rc = pw_check_counts(c, "pinn_pw_get", n_u, n_f, n_b)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = ensure_sets(c)) return rc;
+  if (int rc = pw_prepare(c)) return rc;            // a replaced set reads back as ones
+  std::vector<double> h(pw_doubles(c->sd.n_all));
+  HIPCHK(hipMemcpyAsync(h.data(), c->pw.buf, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int64_t p = 0; lam_b && p < n_b; ++p) lam_b[p] = h[PW_CONST + 3 * (2 * p)];
+  for (int64_t j = 0; lam_u && j < n_u; ++j) lam_u[j] = h[PW_CONST + 3 * (2 * n_b + j)];
+  for (int64_t i = 0; lam_f && i < n_f; ++i) lam_f[i] = h[PW_CONST + 3 * (2 * n_b + n_u + i)];
+  return 0;
+}
+
+int pinn_pw_adam_init(pinn_ctx* c, double rate_u, double rate_f, double rate_b) {
+  REQUIRE(c, "null");
+  if (int rc = pw_supported(c, "pinn_pw_adam_init")) return rc;
+  const double r[3] = {rate_u, rate_f, rate_b};
+  for (int i = 0; i < 3; ++i)
+    REQUIRE(std::isfinite(r[i]) && r[i] >= 0.0, "pinn_pw_adam_init: rate %d (%g) must be finite and >= 0", i, r[i]);
+  for (int i = 0; i < 3; ++i) c->pw.rate[i] = r[i];
+  return 0;
+}
+
+int pinn_pw_disable(pinn_ctx* c) {
+  REQUIRE(c, "null");
+  c->pw.on = false;
+  return 0;
+}
 
 // ------------------------------------------------------------------------------------------
 // ensembles: K members of one float64 Burgers net (kernel path 7) trained side by side on one point set

@@ -89,4 +89,19 @@ int fused20d_launch_any(const F20dLaunch& a, const AdrCoef<double>& k);
 // entries behind the net's scalars in th, k.mask says which of their gradient entries are written (the others are 0.0)
 int fused20d_launch_any(const F20dLaunch& a, const AdrIdeArg& k);
 
+// Per-point loss weights of the adr kind (k_fused20d_pw<PDE_ADR, H, ., false, false, true>, pinn_pw_*).  lam holds PW_CONST
+// doubles -- beta1, beta2, eps of the ascent, then the ascent rate by point class at 3 + class (CLS_BLO: the pairs' rate,
+// CLS_BHI: 0, CLS_DATA, CLS_COL, CLS_PAD: 0), so a lane picks its rate without a branch -- then (lambda, m, v) by POINT INDEX of
+// the assembled set, [2 n_b pair-interleaved | n_u | n_f][3]: pair p's one entry stands at its lo point, 2 p (the entry at
+// 2 p + 1 is unused).  bc = sqrt(1 - b2^t) / (1 - b1^t) of an Adam step, by value, so a queued step needs no copy; 0 = the
+// weights are only read (loss_grad, L-BFGS, all rates 0).
+constexpr int PW_CONST = 8;
+inline size_t pw_doubles(int n_all) { return (size_t)3 * n_all + PW_CONST; }
+struct AdrPwArgs {
+  AdrCoef<double> k;
+  double* lam;
+  double bc;
+};
+int fused20d_launch_any(const F20dLaunch& a, const AdrPwArgs& k);
+
 }  // namespace pinn

@@ -57,4 +57,14 @@ int fused20d_launch_any(const F20dLaunch& a, const AdrIdeArg& k) {
   }
 }
 
+// the adr kind with per-point loss weights: solo launch only
+int fused20d_launch_any(const F20dLaunch& a, const AdrPwArgs& k) {
+  switch (a.nd.n_hidden) {
+    case 4: return fused20d_launch<PDE_ADR, 4, false, false, true>(a, k);
+    case 6: return fused20d_launch<PDE_ADR, 6, false, false, true>(a, k);
+    case 8: return fused20d_launch<PDE_ADR, 8, false, false, true>(a, k);
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
 }  // namespace pinn

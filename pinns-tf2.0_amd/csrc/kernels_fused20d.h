@@ -227,13 +227,19 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
 // four slot lanes of a point hold the same o[0..3] and only the slot-0 lanes touch the loss-part slots, so slot lanes 1-3
 // of quarter 0 sum d/d (a0, a1, log nu) beside loss_f, those of quarter 1 d/d (r1, r2, r3) beside the data part; each DPP
 // row of a quarter is reduced on its own (row16_sum, fixed order) and the per-wave hand-over grows from 4 to 9 values.
+// PDE == PDE_ADR with SAW (per-point loss weights, pinn_pw_*), solo launch, under the kernel name k_fused20d_pw: the slot carries
+// AdrPwArgs -- the six coefficients, the weight array and the step's bias-correction factor (0: the weights are only read).
+// The array is indexed by the point (fused20d_api.h): a pair's two lanes read the lo point's entry, so both seed with the
+// pair's one lambda, and only the slot-0 lane of the lo point steps it.  Coefficients, 1 / n_b and the array's header are
+// parked per wave as PDE_ADR_IDE parks its values, in both variants; inv_n * lambda^2 is formed as SAW forms it for pde 0.
 template <bool SETS, bool SAW = false, int PDE = 0>
-using f20d_nu_t = typename std::conditional<PDE == PDE_ADR, AdrCoef<double>, typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type>::type>::type;
+using f20d_nu_t = typename std::conditional<PDE == PDE_ADR && SAW, AdrPwArgs, typename std::conditional<PDE == PDE_ADR, AdrCoef<double>, typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type>::type>::type>::type;
 __device__ __forceinline__ double f20d_nu(double nu) { return nu; }
 __device__ __forceinline__ double f20d_nu(const AdrIdeArg&) { return 0.0; }
 __device__ __forceinline__ double f20d_nu(const AdrCoef<double>& k) { return k.nu; }
 __device__ __forceinline__ double f20d_nu(const double* nu) { return nu[blockIdx.y]; }   // wave-uniform
 __device__ __forceinline__ double f20d_nu(const SaArgs& a) { return a.nu; }
+__device__ __forceinline__ double f20d_nu(const AdrPwArgs& a) { return a.k.nu; }
 
 #define PINN_F20D_KERNEL k_fused20d
 #include "kernels_fused20d_kernel.h"
@@ -242,15 +248,20 @@ __device__ __forceinline__ double f20d_nu(const SaArgs& a) { return a.nu; }
 #define PINN_F20D_KERNEL k_fused20d_ide
 #include "kernels_fused20d_kernel.h"
 #undef PINN_F20D_KERNEL
+// and under a third, instantiated for PDE_ADR with SAW only: the adr kind with per-point loss weights
+#define PINN_F20D_KERNEL k_fused20d_pw
+#include "kernels_fused20d_kernel.h"
+#undef PINN_F20D_KERNEL
 
 // One loss+gradient evaluation by k_fused20d<PDE, H, ., ENS, SETS, SAW> (F20dLaunch, fused20d_api.h; nu: the variant's
 // coefficient argument).  Every member runs the solo launch plan: the one-tile instantiation when each tile has a workgroup
 // of its own, the tile loop otherwise, on a grid of (n_wg, n_members).  With both events given they take the kernel's own
 // begin / end timestamps.  Returns a hipError_t (0 = ok).
-// the kernel of a variant under its name: k_fused20d_ide for PDE_ADR_IDE, k_fused20d otherwise
+// the kernel of a variant under its name: k_fused20d_ide for PDE_ADR_IDE, k_fused20d_pw for weighted PDE_ADR, k_fused20d otherwise
 template <int PDE, int H, bool ONE_TILE, bool ENS, bool SETS, bool SAW>
 inline auto* f20d_kernel() {
   if constexpr (PDE == PDE_ADR_IDE) return &k_fused20d_ide<PDE, H, ONE_TILE, ENS, SETS, SAW>;
+  else if constexpr (PDE == PDE_ADR && SAW) return &k_fused20d_pw<PDE, H, ONE_TILE, ENS, SETS, SAW>;
   else return &k_fused20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
 }
 

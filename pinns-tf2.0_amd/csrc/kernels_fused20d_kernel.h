@@ -2,6 +2,7 @@
 // k_fused20d for every kind the library had, k_fused20d_ide for PDE_ADR_IDE.  The text is one, so an instantiation of either
 // name is what a single template would give; the second name exists because the set of k_fused20d<...> instantiations in the
 // library is pinned (tests/test_isa_hazards.py counts them), and the trainable-coefficient kind is an addition beside it.
+// k_fused20d_pw, the third name: PDE_ADR with per-point loss weights (SAW), pinn_pw_*.
 // No include guard: it is meant to be included more than once.
 template <int PDE, int H, bool ONE_TILE, bool ENS = false, bool SETS = false, bool SAW = false>
 __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict__ th, const double* __restrict__ xs,
@@ -11,8 +12,9 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
                                                   f20d_nu_t<SETS, SAW, PDE> nu, SetDesc sd,
                                                   long long* __restrict__ stamps, W20Desc nd_arg) {
   static_assert(ENS || !SETS, "per-member point sets are an ensemble launch");
-  static_assert(!pde_is_adr(PDE) || (!ENS && !SETS && !SAW), "advection-diffusion-reaction: solo launch, plain loss");
-  static_assert(!SAW || (PDE == 0 && !ENS), "self-adaptive weights: Burgers inference, solo launch");
+  static_assert(!pde_is_adr(PDE) || (!ENS && !SETS && (!SAW || PDE == PDE_ADR)),
+                "advection-diffusion-reaction: solo launch; point weights for the fixed-coefficient kind only");
+  static_assert(!SAW || ((PDE == 0 || PDE == PDE_ADR) && !ENS), "point weights: Burgers inference or adr, solo launch");
   // weight offsets: compile-time constants in the one-tile variant (immediate operands; Adam step 41.9 -> 40.8 us with
   // the preloaded pointers); the tile-loop variant keeps them in SGPRs -- with immediates its schedule came out 9 %
   // slower (N_f = 10^6: 2104 vs 1930 us per step, same box)
@@ -86,7 +88,8 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
   double* sa_lam_p = nullptr;
   double sa_alpha = 0.0;
   if constexpr (SAW) {
-    sa_lam_p = nu.lam; sa_alpha = nu.alpha;
+    sa_lam_p = nu.lam;
+    if constexpr (PDE == PDE_ADR) sa_alpha = nu.bc; else sa_alpha = nu.alpha;
     if constexpr (!ONE_TILE) asm volatile("" : "+v"(sa_lam_p), "+v"(sa_alpha));
   }
   const double inv_nf = sd.inv_nf, inv_nu = sd.inv_nu;
@@ -95,7 +98,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
   // (lacc[192..], used when PDE == 1 only) and reads it back per tile through an opaque address, wave-uniform.  One tile
   // per workgroup: they stay in scalar registers.
   double* adr_park = nullptr;
-  if constexpr (PDE == PDE_ADR && !ONE_TILE) {
+  if constexpr (PDE == PDE_ADR && !ONE_TILE && !SAW) {
     adr_park = lacc_all + wave * 256 + 192;
     if ((tid & 63) == 0) {
       adr_park[0] = nu.a0; adr_park[1] = nu.a1; adr_park[2] = nu.nu; adr_park[3] = nu.r1; adr_park[4] = nu.r2;
@@ -109,6 +112,17 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       adr_park[0] = tail[0]; adr_park[1] = tail[1]; adr_park[2] = exp(tail[2]); adr_park[3] = tail[3]; adr_park[4] = tail[4];
       adr_park[5] = tail[5]; adr_park[6] = sd.inv_nb; adr_park[7] = (double)nu.mask;
     }
+  }
+  // PDE_ADR with point weights, both variants: the same seven, and behind them the array's header (beta1, beta2, eps and the
+  // ascent rates by point class, fused20d_api.h PW_CONST) -- a lane picks its class's rate by one LDS read
+  if constexpr (PDE == PDE_ADR && SAW) {
+    adr_park = lacc_all + wave * 256 + 192;
+    const AdrCoef<double> k0 = nu.k;
+    if ((tid & 63) == 0) {
+      adr_park[0] = k0.a0; adr_park[1] = k0.a1; adr_park[2] = k0.nu; adr_park[3] = k0.r1; adr_park[4] = k0.r2;
+      adr_park[5] = k0.r3; adr_park[6] = sd.inv_nb;
+    }
+    if ((tid & 63) < PW_CONST) adr_park[8 + (tid & 63)] = sa_lam_p[tid & 63];
   }
   (void)adr_park;
   // per-lane partial sums of the loss parts and of the two lambda gradients (slot-0 lanes only) live in LDS, four
@@ -325,6 +339,11 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
     // round trip
     double sa_lam = 1.0, sa_m = 0.0, sa_v = 0.0;
     double* sa_row = nullptr;
+    if constexpr (SAW && PDE == PDE_ADR) {   // indexed by the point; both points of a periodic pair read the lo point's entry
+      const int e = pt < sd.n_all ? pt : 0;
+      sa_row = sa_lam_p + PW_CONST + 3 * (e < 2 * sd.n_b ? e & ~1 : e);
+      sa_lam = sa_row[0]; sa_m = sa_row[1]; sa_v = sa_row[2];
+    } else
     if constexpr (SAW) {      // (padding lanes read point 0's entry, unused: no branch, no saved execution mask)
       sa_row = sa_lam_p + SA_CONST + 3 * (pt < sd.n_all ? pt : 0);
       sa_lam = sa_row[0]; sa_m = sa_row[1]; sa_v = sa_row[2];
@@ -406,7 +425,55 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
 
     // ------------------------------------------------------------------ seeds + loss parts
     double sb[4] = {0.0, 0.0, 0.0, 0.0};
-    if constexpr (PDE == PDE_ADR) {
+    if constexpr (PDE == PDE_ADR && SAW) {
+      // PDE_ADR's seeds with inv_n * lambda^2 where inv_n stands (a product of its own, never contracted into a neighbour:
+      // lambda = 1 gives the plain kernel's bits); a pair's two lanes hold the pair's one lambda
+      const double pu = dpp_mov<DPP_QUAD_XOR1>(o[0]), pp = dpp_mov<DPP_QUAD_XOR1>(o[1]);
+      const double* kp = adr_park;
+      asm volatile("" : "+v"(kp));
+      const AdrCoef<double> kc{kp[0], kp[1], kp[2], kp[3], kp[4], kp[5]};
+      const int cls = point_class_adr(sd, pt);
+      double wf, wu, wb, r2 = 0.0;
+      {
+#pragma clang fp contract(off)
+        const double l2 = sa_lam * sa_lam;
+        wf = inv_nf * l2; wu = inv_nu * l2; wb = kp[6] * l2;
+      }
+      if (cls == CLS_COL) {
+        const double u = o[0], adv = kc.a0 + kc.a1 * u;
+        const double f = o[2] + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
+        const double fbar = 2.0 * f * wf;
+        if (s == 0) lacc[0] += f * f * wf;
+        sb[0] = fbar * (kc.a1 * o[1] + kc.r1 + u * (2.0 * kc.r2 + 3.0 * kc.r3 * u));
+        sb[1] = fbar * adv; sb[2] = fbar; sb[3] = -kc.nu * fbar;
+        r2 = f * f * inv_nf;
+      } else if (cls == CLS_DATA) {
+        const double dd = o[0] - tgt[pt];
+        if (s == 0) lacc[64] += dd * dd * wu;
+        sb[0] = 2.0 * dd * wu;
+        r2 = dd * dd * inv_nu;
+      } else if (cls != CLS_PAD) {
+        const double du = o[0] - pu, dp = o[1] - pp;
+        if (s == 0 && cls == CLS_BLO) lacc[128] += (du * du + dp * dp) * wb;
+        sb[0] = 2.0 * du * wb; sb[1] = 2.0 * dp * wb;
+        r2 = (du * du + dp * dp) * kp[6];
+      }
+      // one Adam ascent step on lambda from this evaluation (TF form, as k_reduce_adam steps theta): the slot-0 lane of a
+      // data or collocation point and of a pair's lo point.  The header holds the rate at 3 + class, 0.0 for hi points and
+      // padding, so a class with rate 0 is never written
+      if (sa_alpha != 0.0) {
+        const double step = sa_alpha * kp[8 + 3 + cls];
+        if (step != 0.0 && s == 0) {
+          const double g = 2.0 * sa_lam * r2;
+          const double mi = sa_m + (1.0 - kp[8]) * (g - sa_m);
+          const double vi = sa_v + (1.0 - kp[9]) * (g * g - sa_v);
+          sa_row[0] = sa_lam + step * mi / (sqrt(vi) + kp[10]);
+          sa_row[1] = mi;
+          sa_row[2] = vi;
+        }
+      }
+    } else if constexpr (PDE == PDE_ADR) {
+      // (the weighted block above is this block's twin, seed for seed: a change to the seeds here belongs there too)
       // partner of a boundary pair: pt ^ 1 is lane ^ 1 (pt = tile * 64 + wave * 16 + q), same slot.  The moves are
       // unconditional (no divergent branch around a cross-lane move); their results count in the boundary class only.
       const double pu = dpp_mov<DPP_QUAD_XOR1>(o[0]), pp = dpp_mov<DPP_QUAD_XOR1>(o[1]);

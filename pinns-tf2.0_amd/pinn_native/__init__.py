@@ -284,6 +284,13 @@ _SIGNATURES = {
     "pinn_sa_get_weights": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, _c_double_p, ctypes.c_int64]),
     "pinn_sa_adam_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
     "pinn_sa_disable": (ctypes.c_int, [ctypes.c_void_p]),
+    # per-point loss weights of the adr kind (include/pinn_hip.h: pinn_pw_*)
+    "pinn_pw_set": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, _c_double_p, ctypes.c_int64,
+                                   _c_double_p, ctypes.c_int64]),
+    "pinn_pw_get": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, _c_double_p, ctypes.c_int64,
+                                   _c_double_p, ctypes.c_int64]),
+    "pinn_pw_adam_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "pinn_pw_disable": (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 
@@ -506,6 +513,31 @@ class Engine(object):
 
     def sa_disable(self):
         self._check(self._lib.pinn_sa_disable(self._h))
+
+    # ---- per-point loss weights of the adr kind (include/pinn_hip.h pinn_pw_*) --------------------------------------------
+    def pw_set(self, lam_u=None, lam_f=None, lam_b=None):
+        """Enable the weighted loss of the adr kind: one weight per data point (rows of set_data), per collocation point
+        (rows of get_collocation) and per boundary pair (rows of set_boundary); None = all ones.  Resets the weights' Adam
+        moments."""
+        arrs = [None if a is None else _f64(a).ravel() for a in (lam_u, lam_f, lam_b)]
+        args = []
+        for a, n in zip(arrs, (self.n_u, self.n_f, self.n_b)):
+            args += [None if a is None else _dp(a), n if a is None else a.size]
+        self._check(self._lib.pinn_pw_set(self._h, *args))
+
+    def pw_get(self):
+        """-> (lam_u [n_u], lam_f [n_f], lam_b [n_b])"""
+        out = [np.empty(n, dtype=np.float64) for n in (self.n_u, self.n_f, self.n_b)]
+        self._check(self._lib.pinn_pw_get(self._h, _dp(out[0]), out[0].size, _dp(out[1]), out[1].size,
+                                          _dp(out[2]), out[2].size))
+        return tuple(out)
+
+    def pw_adam_init(self, rate_u=0.0, rate_f=0.0, rate_b=0.0):
+        """ascent rates of the data, collocation and pair weights in every Adam step (0: that class is held fixed)"""
+        self._check(self._lib.pinn_pw_adam_init(self._h, float(rate_u), float(rate_f), float(rate_b)))
+
+    def pw_disable(self):
+        self._check(self._lib.pinn_pw_disable(self._h))
 
     def get_collocation(self):
         X = np.empty((self.n_f, 2), dtype=np.float64)

@@ -47,6 +47,8 @@ class NeuralNetworkEnsemble(object):
         if hp.get("sa_weights", False):
             raise ValueError('hp["sa_weights"]: self-adaptive point weights are for single models (NeuralNetwork), not '
                              'ensembles')
+        if hp.get("point_weights", False):
+            raise ValueError('hp["point_weights"]: point weights are for single "adr" models (NeuralNetwork), not ensembles')
         self.pde = pde
         self.layers = [int(v) for v in hp["layers"]]
         self.ub = np.asarray(ub, dtype=np.float64)

@@ -17,7 +17,8 @@ gradient on the GPU (csrc/).  Extra, optional hp keys: "dtype" ("f64" default = 
 arithmetic, neuralnetwork.py:24-26 | "f32" = the throughput mode north_star sanctions) for the
 kernel arithmetic, "device" (HIP ordinal), "nt_guard" (see nt_optimization), "resample_every" / "resample" / "rad_*"
 (device-side redraws of the collocation set, see _resample_options), "sa_weights" / "sa_lr" / "sa_init" (self-adaptive
-point weights, see _sa_options).  Host interchange stays float64.
+point weights, see _sa_options), "point_weights" / "pw_init" / "pw_lr" (fixed or self-adaptive per-point loss weights of
+the "adr" kind, see _pw_options).  Host interchange stays float64.
 
 Data parallel (north_star; the reference has no distributed code): launched as
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 1d-burgers/inf_cont_burgers.py [hp.json]
@@ -118,6 +119,52 @@ def _sa_options(hp, pde):
     return float(lr), init_u, init_f
 
 
+def _pw_options(hp, pde):
+    """hp["point_weights"] = true: per-point loss weights of the "adr" kind (Engine.pw_set): every data point, collocation
+    point and periodic pair has a weight lambda and counts with lambda^2.  hp["pw_init"] = [data, collocation, boundary]
+    start values or one number for all (default 1): a static term weight W on a class is sqrt(W) here.  hp["pw_lr"], the
+    same shapes (default 0 = fixed): a class with a rate above 0 is self-adaptive (McClenny & Braga-Neto, arXiv:2009.04544) --
+    every Adam step ascends in its lambdas while it descends in the network weights, and L-BFGS then minimises the weighted
+    loss with the lambdas frozen.  Float64 "adr" on one device with the layers of the float64 width-20 kernel (kernel
+    path 7: hidden width 20; 4, 6 or 8 hidden layers), the only one that takes the weights; redraws of the collocation set (hp["resample_every"]) reset
+    that class to 1, so they go with a plain collocation class only (init 1, rate 0).  Anything else is refused here, before
+    any engine is made, with the offending key named.  -> None (off) or ((init_u, init_f, init_b), (lr_u, lr_f, lr_b))."""
+    if not hp.get("point_weights", False):
+        return None
+    if pde != "adr":
+        raise ValueError('hp["point_weights"]: point weights are for the "adr" kind; the %s model is not supported' % pde)
+    if hp.get("dtype", "f64") not in ("f64", "float64"):
+        raise ValueError('hp["point_weights"]: point weights need hp["dtype"] = "f64" (got %r)' % (hp.get("dtype"),))
+    if hp.get("sa_weights", False):
+        raise ValueError('hp["point_weights"] and hp["sa_weights"] exclude each other: "sa_weights" is the Burgers form, '
+                         '"point_weights" with hp["pw_lr"] the self-adaptive form of the "adr" kind')
+    layers = [int(v) for v in hp["layers"]]
+    if layers[0] != 2 or layers[-1] != 1 or len(layers) - 2 not in (4, 6, 8) or any(w != 20 for w in layers[1:-1]):
+        raise ValueError('hp["point_weights"]: point weights run on the float64 width-20 kernel only; hp["layers"] must be '
+                         '[2, 20 x 4, 6 or 8, 1] (got %r)' % (hp["layers"],))
+
+    def three(key, default):
+        val = hp.get(key, default)
+        if isinstance(val, (list, tuple)):
+            vals = list(val)
+        else:
+            vals = [val] * 3
+        ok = len(vals) == 3 and all(not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+                                    and np.isfinite(v) for v in vals)
+        if not ok:
+            raise ValueError('hp["%s"] must be [data, collocation, boundary] finite numbers or one finite number (got %r)'
+                             % (key, val))
+        return tuple(float(v) for v in vals)
+
+    init, lr = three("pw_init", 1.0), three("pw_lr", 0.0)
+    if min(lr) < 0:
+        raise ValueError('hp["pw_lr"] must be >= 0 (got %r)' % (hp.get("pw_lr"),))
+    if int(hp.get("resample_every", 0)) > 0 and (init[1] != 1.0 or lr[1] != 0.0):
+        raise ValueError('hp["point_weights"]: a redraw (hp["resample"], hp["resample_every"] > 0) resets the collocation '
+                         'weights to 1; it goes with a plain collocation class only (hp["pw_init"][1] = 1, hp["pw_lr"][1] = 0)')
+    return init, lr
+
+
 ADR_NAMES = ("a0", "a1", "nu", "r1", "r2", "r3")
 
 
@@ -204,6 +251,7 @@ class NeuralNetwork(object):
             self.pde = pde
         self._resample, self._rad_k, self._rad_c, self._rad_pool = _resample_options(hp, self.pde)
         self._sa = _sa_options(hp, self.pde)
+        self._pw = _pw_options(hp, self.pde)
         self._adr_ide = _adr_ide_options(hp) if self.pde == "adr_ide" else None
 
         # L-BFGS configuration, same fields as the reference (neuralnetwork.py:13-17)
@@ -257,6 +305,8 @@ class NeuralNetwork(object):
                                self.tf_optimizer.beta_2, self.tf_optimizer.epsilon)
         if self._sa:
             self._engine.sa_adam_init(self._sa[0])
+        if self._pw:
+            self._engine.pw_adam_init(*self._pw[1])
         self._bound = None
         self.logger = logger
         # optional: re-draw the collocation set on the device every k Adam epochs (not in the reference, which
@@ -636,6 +686,10 @@ class NeuralNetwork(object):
             self._bind(X_u, u)
             eng = self._engine
             eng.sa_set_weights(np.full(eng.n_u, self._sa[1]), np.full(eng.n_f, self._sa[2]))
+        if self._pw:                # likewise: the start values once per fit, on the sets it trains
+            self._bind(X_u, u)
+            eng = self._engine
+            eng.pw_set(np.full(eng.n_u, self._pw[0][0]), np.full(eng.n_f, self._pw[0][1]), np.full(eng.n_b, self._pw[0][2]))
         self.tf_optimization(X_u, u)
         self.nt_optimization(X_u, u)
         self.logger.log_train_end(self.tf_epochs + self.nt_config.maxIter)
@@ -645,6 +699,10 @@ class NeuralNetwork(object):
         bad = self._engine.status()[1]
         if bad:
             print("warning: the loss became non-finite at evaluation %d" % bad, file=sys.stderr)
+        if self._pw and self.is_root:       # where the weights ended (fixed classes read back as set)
+            stats = lambda a: "min %.4e median %.4e max %.4e" % (a.min(), np.median(a), a.max()) if a.size else "none"  # noqa: E731
+            lam_u, lam_f, lam_b = self.get_point_weights()
+            print("Point weights: data %s | collocation %s | boundary %s" % (stats(lam_u), stats(lam_f), stats(lam_b)))
 
     def predict(self, X_star):
         return self._engine.predict(_as_points(X_star, self))
@@ -655,6 +713,13 @@ class NeuralNetwork(object):
         if not self._sa:
             raise ValueError('self-adaptive weights are off (hp["sa_weights"])')
         return self._engine.sa_get_weights()
+
+    def get_point_weights(self):
+        """(lambda_u [N_u], lambda_f [N_f], lambda_b [N_b]): the per-point loss weights (hp["point_weights"]) in the order of
+        the data rows, of the collocation set and of the boundary pairs"""
+        if not self._pw:
+            raise ValueError('point weights are off (hp["point_weights"])')
+        return self._engine.pw_get()
 
     def error_l2(self, X_star, reference, modulus=False):
         """The scripts' error metric ||reference - model(X_star)||_2 / ||reference||_2

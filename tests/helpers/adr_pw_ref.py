@@ -1,0 +1,127 @@
+"""numpy float64 restatement of the adr kind with per-point loss weights (include/pinn_hip.h pinn_pw_*, k_fused20d_pw of
+pinns-tf2.0_amd/csrc/kernels_fused20d.h): adr_ref.adr_loss_grad with the three lambda classes, in the manner of sa_ref.py.
+
+    L = (1/N_f) sum_i lam_f,i^2 f_i^2 + (1/N_u) sum_j lam_u,j^2 (u_j - u*_j)^2
+        + (1/N_b) sum_p lam_b,p^2 [(u(lo_p) - u(hi_p))^2 + (u_x(lo_p) - u_x(hi_p))^2]
+
+its gradient in theta, its gradients in the lambdas (dL/dlam = 2 lam r^2 / N; a pair has one lambda and r^2 = du^2 + dp^2),
+and Adam steps that descend in theta and ascend in the lambdas from one evaluation, one rate per class, in the TF form
+k_reduce_adam uses (m += (1-b1)(g-m), v += (1-b2)(g^2-v), step rate sqrt(1-b2^t) / (1-b1^t) m / (sqrt(v)+eps)).
+
+The operations are adr_ref's in adr_ref's order with m = lam^2 multiplied in where adr_ref has the bare residual, so that
+lam = 1 reproduces adr_ref.adr_loss_grad bit for bit (tests/test_adr_pw_host.py)."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from oracle import mlp  # noqa: E402
+
+
+def _col(lam, n):
+    return np.ones((n, 1)) if lam is None else np.asarray(lam, dtype=np.float64).reshape(n, 1)
+
+
+def loss_grad(w, layers, lb, ub, X_f, X_u, u, X_lo, X_hi, coeffs, lam_u=None, lam_f=None, lam_b=None):
+    """-> (loss, grad_theta, terms = (mse_f, mse_u, mse_b), (dL/dlam_u, dL/dlam_f, dL/dlam_b)); X_u / X_lo may be None or
+    empty, a lam of None is all ones"""
+    a0, a1, nu, r1, r2, r3 = (float(v) for v in coeffs)
+    lb, ub = np.asarray(lb, dtype=np.float64), np.asarray(ub, dtype=np.float64)
+    params = mlp.unpack(w, layers)
+    N_f = X_f.shape[0]
+    lf = _col(lam_f, N_f)
+    mf = lf * lf
+    (h, p, q, r), cache = mlp.taylor_forward(params, X_f, lb, ub)
+    f = q + (a0 + a1 * h) * p - nu * r + r1 * h + r2 * h * h + r3 * h * h * h
+    mse_f = np.sum(mf * (f * f)) / N_f
+    fb = 2.0 * (mf * f) / N_f
+    grads = mlp.taylor_backward(params, cache, fb * (a1 * p + r1 + 2.0 * r2 * h + 3.0 * r3 * h * h), fb * (a0 + a1 * h),
+                                fb, -nu * fb)
+    dlam_f = (2.0 * lf * (f * f) / N_f).ravel()
+    mse_u = mse_b = 0.0
+    dlam_u, dlam_b = np.zeros(0), np.zeros(0)
+    if X_u is not None and len(X_u):
+        N_u = X_u.shape[0]
+        lu = _col(lam_u, N_u)
+        mu = lu * lu
+        d = mlp.forward_value(params, X_u, lb, ub) - np.asarray(u, dtype=np.float64).reshape(-1, 1)
+        mse_u = np.sum(mu * (d * d)) / N_u
+        grads = mlp.add_grads(grads, mlp.value_backward(params, X_u, lb, ub, 2.0 * (mu * d) / N_u))
+        dlam_u = (2.0 * lu * (d * d) / N_u).ravel()
+    if X_lo is not None and len(X_lo):
+        N_b = X_lo.shape[0]
+        lbd = _col(lam_b, N_b)
+        mb = lbd * lbd
+        (hl, pl, _, _), cl = mlp.taylor_forward(params, X_lo, lb, ub)
+        (hu, pu, _, _), cu = mlp.taylor_forward(params, X_hi, lb, ub)
+        dh, dp = hl - hu, pl - pu
+        mse_b = (np.sum(mb * (dh * dh)) + np.sum(mb * (dp * dp))) / N_b
+        z = np.zeros_like(dh)
+        grads = mlp.add_grads(grads, mlp.taylor_backward(params, cl, 2.0 * (mb * dh) / N_b, 2.0 * (mb * dp) / N_b, z, z))
+        grads = mlp.add_grads(grads, mlp.taylor_backward(params, cu, -2.0 * (mb * dh) / N_b, -2.0 * (mb * dp) / N_b, z, z))
+        dlam_b = (2.0 * lbd * (dh * dh + dp * dp) / N_b).ravel()
+    return mse_f + mse_u + mse_b, mlp.pack(grads), (mse_f, mse_u, mse_b), (dlam_u, dlam_f, dlam_b)
+
+
+def loss_only(*a, **kw):
+    return loss_grad(*a, **kw)[0]
+
+
+def adam(w, lam_u, lam_f, lam_b, n_steps, layers, lb, ub, X_f, X_u, u, X_lo, X_hi, coeffs, lr, rates, b1=0.9, b2=0.999,
+         eps=1e-7):
+    """n_steps Adam steps from zero moments (step counter from 1): theta descends at lr, the lambdas ascend at
+    rates = (data, collocation, pairs), a class with rate 0 is not touched; -> (w, (lam_u, lam_f, lam_b), losses)"""
+    w = np.array(w, dtype=np.float64)
+    lam = [np.array(x, dtype=np.float64).ravel() for x in (lam_u, lam_f, lam_b)]
+    m, v = np.zeros_like(w), np.zeros_like(w)
+    ml, vl = [np.zeros_like(x) for x in lam], [np.zeros_like(x) for x in lam]
+    losses = []
+    for t in range(1, n_steps + 1):
+        loss, g, _, gl = loss_grad(w, layers, lb, ub, X_f, X_u, u, X_lo, X_hi, coeffs, lam[0], lam[1], lam[2])
+        losses.append(loss)
+        scale = np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+        m += (1.0 - b1) * (g - m)
+        v += (1.0 - b2) * (g * g - v)
+        w = w - (lr * scale) * m / (np.sqrt(v) + eps)
+        for k in range(3):
+            if rates[k] > 0 and lam[k].size:
+                ml[k] += (1.0 - b1) * (gl[k] - ml[k])
+                vl[k] += (1.0 - b2) * (gl[k] * gl[k] - vl[k])
+                lam[k] = lam[k] + (rates[k] * scale) * ml[k] / (np.sqrt(vl[k]) + eps)
+    return w, tuple(lam), np.array(losses)
+
+
+# ---- the trajectory case shared by tests/test_adr_pw_host.py (conditioning) and tests/test_gpu_adr_pw.py (the device run) ----
+LB, UB = np.array([-1.0, 0.0]), np.array([1.0, 1.0])
+TRAJ_RATES, TRAJ_LR, TRAJ_STEPS = (0.05, 0.02, 0.01), 1e-3, 50
+
+
+def trajectory_case(H, seed=11, n_f=2000, n_u=100, n_b=7):
+    """-> dict: layers, w0, the three sets (data on t = 0) and lambdas ~ U(0.5, 2) of the 50-step trajectory test"""
+    from oracle import init
+    rs = np.random.RandomState(seed)
+    layers = [2] + [20] * H + [1]
+    w0 = init.glorot_flat(layers) + 0.05 * rs.standard_normal(sum(a * b + b for a, b in zip(layers[:-1], layers[1:])))
+    X_f = LB + (UB - LB) * rs.uniform(size=(n_f, 2))
+    X_u = np.column_stack([rs.uniform(-1, 1, n_u), np.zeros(n_u)])
+    u = (X_u[:, 0:1] ** 2) * np.cos(np.pi * X_u[:, 0:1])
+    tb = rs.uniform(0, 1, n_b)
+    X_lo, X_hi = np.column_stack([np.full(n_b, -1.0), tb]), np.column_stack([np.full(n_b, 1.0), tb])
+    lam = [rs.uniform(0.5, 2.0, n) for n in (n_u, n_f, n_b)]
+    return dict(layers=layers, w0=w0, X_f=X_f, X_u=X_u, u=u, X_lo=X_lo, X_hi=X_hi, lam_u=lam[0], lam_f=lam[1], lam_b=lam[2])
+
+
+def run_trajectory(case, coeffs, perm=None):
+    """adam() on a trajectory case; perm = (pu, pf, pb) row permutations of the three classes (the sums then run in another
+    order, nothing else changes) -> (w, (lam_u, lam_f, lam_b) in the ORIGINAL row order, losses)"""
+    c = case
+    pu, pf, pb = perm if perm is not None else [np.arange(len(c[k])) for k in ("lam_u", "lam_f", "lam_b")]
+    w, lam, losses = adam(c["w0"], c["lam_u"][pu], c["lam_f"][pf], c["lam_b"][pb], TRAJ_STEPS, c["layers"], LB, UB,
+                          c["X_f"][pf], c["X_u"][pu], c["u"][pu], c["X_lo"][pb], c["X_hi"][pb], coeffs, TRAJ_LR, TRAJ_RATES)
+    out = []
+    for l, p in zip(lam, (pu, pf, pb)):
+        o = np.empty_like(l)
+        o[p] = l
+        out.append(o)
+    return w, tuple(out), losses

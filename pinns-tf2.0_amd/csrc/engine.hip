@@ -119,6 +119,19 @@ enum KernelPath : int {
   KP_COUNT
 };
 
+// Host side of a per-point weight array of fused20d_api.h: a header, then (lambda, m, v) per point, class behind class.
+// hdr: the header as uploaded, n_hdr doubles of it; n[k]: the entries class k is laid out for; reset[k]: that class's set was
+// replaced since (lam_prepare puts its weights back to 1).  A surface that has no pairs leaves that class empty.
+enum { LAM_PAIRS, LAM_DATA, LAM_COL, LAM_CLASSES };
+struct LamStore {
+  double* buf = nullptr;
+  size_t cap = 0;
+  int n_hdr = 0;
+  double hdr[PW_CONST] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // the longer of the two headers; the rest stays 0
+  int n[LAM_CLASSES] = {0, 0, 0};
+  bool reset[LAM_CLASSES] = {false, false, false};
+};
+
 struct pinn_ctx {
   int device = 0, dtype = PINN_F32, pde = PINN_PDE_BURGERS;
   KernelPath path = KP_GENERIC;
@@ -239,27 +252,18 @@ struct pinn_ctx {
     size_t cap_pool = 0;
   } rad;
 
-  // self-adaptive point weights (pinn_sa_*, k_fused20d's SAW variants): the device array of fused20d_api.h (SA_CONST
-  // constants, then (lambda, m, v) per point of the assembled set), laid out for n_u data and n_f collocation points with the
-  // ascent constants k; reset_u / reset_f: that class's set was replaced since (sa_prepare puts its weights back to 1)
+  // self-adaptive point weights (pinn_sa_*, k_fused20d<0, H, ., false, false, true>): SA_CONST header, data and collocation points
   struct {
-    bool on = false, reset_u = false, reset_f = false;
+    bool on = false;
     double lr = 0.0;
-    double* buf = nullptr;
-    size_t cap = 0;
-    int n_u = 0, n_f = 0;
-    double k[3] = {0.0, 0.0, 0.0};
+    LamStore arr;
   } sa;
-  // per-point loss weights of the adr kind (pinn_pw_*, k_fused20d_pw): the device array of fused20d_api.h (PW_CONST header,
-  // then (lambda, m, v) by point index), laid out for n_b pairs, n_u data and n_f collocation points; hdr: the header as
-  // uploaded; reset_*: that class's set was replaced since (pw_prepare puts its weights back to 1)
+  // per-point loss weights of the adr kind (pinn_pw_*, k_fused20d<PDE_ADR, H, ., false, false, true>): PW_CONST header, two
+  // entries per pair, data and collocation points
   struct {
-    bool on = false, reset_u = false, reset_f = false, reset_b = false;
+    bool on = false;
     double rate[3] = {0.0, 0.0, 0.0};          // data, collocation, pairs
-    double* buf = nullptr;
-    size_t cap = 0;
-    int n_b = 0, n_u = 0, n_f = 0;
-    double hdr[PW_CONST] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    LamStore arr;
   } pw;
 
   // discrete-time models (pde 3, 4): stage sets as handed over, device copies, scratch
@@ -567,90 +571,81 @@ struct AdamFuse {          // single-GPU Adam step applied by the reduction kern
   double bc_pw = 0.0;      // adr point weights: the step's bias-correction factor sqrt(1 - b2^t) / (1 - b1^t) (0: none)
 };
 
-// self-adaptive weights: (re)build the device array for the assembled set when a class's set was replaced (its weights
-// back to 1, its moments to 0; the other class keeps its values) or the ascent constants changed.  Synchronous, and only
-// then: the common case returns at once.
-static int sa_prepare(pinn_ctx* c) {
-  const SetDesc& sd = c->sd;
-  const bool keep_u = c->sa.buf && !c->sa.reset_u && c->sa.n_u == sd.n_u;
-  const bool keep_f = c->sa.buf && !c->sa.reset_f && c->sa.n_f == sd.n_f;
-  const bool k_same = c->sa.k[0] == c->b1 && c->sa.k[1] == c->b2 && c->sa.k[2] == c->eps;
-  if (keep_u && keep_f && k_same) return 0;
-  std::vector<double> old;
-  if (keep_u || keep_f) {
-    old.resize(sa_doubles(c->sa.n_u + c->sa.n_f));
-    HIPCHK(hipMemcpyAsync(old.data(), c->sa.buf, old.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+// A per-point weight array as the assembled set wants it now: the header as the kernel reads it and the entries per class
+// (LamStore).  The two surfaces differ in this and in nothing else.
+struct LamLayout {
+  int n_hdr;
+  double hdr[PW_CONST];
+  int n[LAM_CLASSES];
+  size_t at(int k) const {                       // first double of class k's entries
+    size_t o = (size_t)n_hdr;
+    for (int j = 0; j < k; ++j) o += (size_t)3 * n[j];
+    return o;
   }
-  std::vector<double> h(sa_doubles(sd.n_u + sd.n_f), 0.0);
-  h[0] = c->b1; h[1] = c->b2; h[2] = c->eps;
-  for (int j = 0; j < sd.n_u; ++j)
-    for (int e = 0; e < 3; ++e) h[SA_CONST + 3 * j + e] = keep_u ? old[SA_CONST + 3 * j + e] : (e == 0 ? 1.0 : 0.0);
-  for (int i = 0; i < sd.n_f; ++i)
-    for (int e = 0; e < 3; ++e)
-      h[SA_CONST + 3 * (sd.n_u + i) + e] = keep_f ? old[SA_CONST + 3 * (c->sa.n_u + i) + e] : (e == 0 ? 1.0 : 0.0);
-  if (h.size() * 8 > c->sa.cap) {
-    if (dev_alloc(&c->sa.buf, h.size() * 8)) return PINN_EHIP;
-    c->sa.cap = h.size() * 8;
+  size_t doubles() const { return at(LAM_CLASSES); }
+};
+// self-adaptive weights: Adam's constants; data and collocation points
+static LamLayout sa_layout(const pinn_ctx* c) {
+  return LamLayout{SA_CONST, {c->b1, c->b2, c->eps}, {0, c->sd.n_u, c->sd.n_f}};
+}
+// adr point weights: the constants, then the ascent rate at 3 + point class (fused20d_api.h).  The pairs are stored
+// pair-interleaved, one entry per POINT: a pair counts twice
+static LamLayout pw_layout(const pinn_ctx* c) {
+  LamLayout L{PW_CONST, {c->b1, c->b2, c->eps}, {2 * c->sd.n_b, c->sd.n_u, c->sd.n_f}};
+  L.hdr[3 + CLS_BLO] = c->pw.rate[2]; L.hdr[3 + CLS_DATA] = c->pw.rate[0]; L.hdr[3 + CLS_COL] = c->pw.rate[1];
+  return L;
+}
+
+// start values: h holds L.doubles() doubles, the entries filled in; the header is written here.  Synchronous.
+static int lam_upload(pinn_ctx* c, LamStore& s, const LamLayout& L, std::vector<double>& h) {
+  memcpy(h.data(), L.hdr, L.n_hdr * sizeof(double));
+  if (h.size() * 8 > s.cap) {
+    if (dev_alloc(&s.buf, h.size() * 8)) return PINN_EHIP;
+    s.cap = h.size() * 8;
   }
-  HIPCHK(hipMemcpyAsync(c->sa.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->sa.n_u = sd.n_u; c->sa.n_f = sd.n_f; c->sa.reset_u = c->sa.reset_f = false;
-  c->sa.k[0] = c->b1; c->sa.k[1] = c->b2; c->sa.k[2] = c->eps;
+  for (int k = 0; k < LAM_CLASSES; ++k) { s.n[k] = L.n[k]; s.reset[k] = false; }
+  s.n_hdr = L.n_hdr;
+  memcpy(s.hdr, L.hdr, sizeof s.hdr);
   return 0;
 }
 
-// adr point weights: the header of the device array as the kernel reads it (fused20d_api.h: the rate at 3 + point class)
-static void pw_header(const pinn_ctx* c, double* h) {
-  for (int i = 0; i < PW_CONST; ++i) h[i] = 0.0;
-  h[0] = c->b1; h[1] = c->b2; h[2] = c->eps;
-  h[3 + CLS_BLO] = c->pw.rate[2]; h[3 + CLS_DATA] = c->pw.rate[0]; h[3 + CLS_COL] = c->pw.rate[1];
+// the array as the device holds it, in the layout it was uploaded with.  Synchronous.
+static int lam_download(pinn_ctx* c, const LamStore& s, std::vector<double>& h) {
+  h.resize((size_t)s.n_hdr + (size_t)3 * s.n[0] + (size_t)3 * s.n[1] + (size_t)3 * s.n[2]);
+  HIPCHK(hipMemcpyAsync(h.data(), s.buf, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
-// adr point weights: (re)build the device array for the assembled set when a class's set was replaced (its weights back to
-// 1, its moments to 0; the other classes keep theirs), or rewrite its header when the ascent's constants or rates changed.
+// (Re)build the device array for the assembled set when a class's set was replaced (its weights back to 1, its moments to 0;
+// the other classes keep theirs), or rewrite its header alone when only the ascent's constants or rates changed.
 // Synchronous, and only then: the common case returns at once.
-static int pw_prepare(pinn_ctx* c) {
-  const SetDesc& sd = c->sd;
-  const bool keep_b = c->pw.buf && !c->pw.reset_b && c->pw.n_b == sd.n_b;
-  const bool keep_u = c->pw.buf && !c->pw.reset_u && c->pw.n_u == sd.n_u;
-  const bool keep_f = c->pw.buf && !c->pw.reset_f && c->pw.n_f == sd.n_f;
-  double hdr[PW_CONST];
-  pw_header(c, hdr);
-  if (keep_b && keep_u && keep_f) {
-    if (memcmp(hdr, c->pw.hdr, sizeof hdr) == 0) return 0;
-    HIPCHK(hipMemcpyAsync(c->pw.buf, hdr, sizeof hdr, hipMemcpyHostToDevice, c->stream));
+static int lam_prepare(pinn_ctx* c, LamStore& s, const LamLayout& L) {
+  bool keep[LAM_CLASSES], keep_all = true, keep_any = false;
+  for (int k = 0; k < LAM_CLASSES; ++k) {
+    keep[k] = s.buf && !s.reset[k] && s.n[k] == L.n[k];
+    keep_all = keep_all && keep[k];
+    keep_any = keep_any || (keep[k] && L.n[k] > 0);
+  }
+  if (keep_all) {
+    if (memcmp(L.hdr, s.hdr, sizeof s.hdr) == 0) return 0;
+    HIPCHK(hipMemcpyAsync(s.buf, L.hdr, L.n_hdr * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(c->pw.hdr, hdr, sizeof hdr);
+    memcpy(s.hdr, L.hdr, sizeof s.hdr);
     return 0;
   }
   std::vector<double> old;
-  if (keep_b || keep_u || keep_f) {
-    old.resize(pw_doubles(2 * c->pw.n_b + c->pw.n_u + c->pw.n_f));
-    HIPCHK(hipMemcpyAsync(old.data(), c->pw.buf, old.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+  if (keep_any) { if (int rc = lam_download(c, s, old)) return rc; }
+  std::vector<double> h(L.doubles(), 0.0);
+  size_t from = (size_t)s.n_hdr;                   // class k's entries in the old layout
+  for (int k = 0; k < LAM_CLASSES; ++k) {
+    double* const to = h.data() + L.at(k);
+    for (size_t i = 0; i < (size_t)3 * L.n[k]; ++i) to[i] = keep[k] ? old[from + i] : (i % 3 == 0 ? 1.0 : 0.0);
+    from += (size_t)3 * s.n[k];
   }
-  std::vector<double> h(pw_doubles(sd.n_all), 0.0);
-  memcpy(h.data(), hdr, sizeof hdr);
-  // class by class: n points from old index o0 to new index n0
-  auto fill = [&](bool keep, size_t n0, size_t o0, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-      for (int e = 0; e < 3; ++e)
-        h[PW_CONST + 3 * (n0 + i) + e] = keep ? old[PW_CONST + 3 * (o0 + i) + e] : (e == 0 ? 1.0 : 0.0);
-  };
-  fill(keep_b, 0, 0, (size_t)2 * sd.n_b);
-  fill(keep_u, (size_t)2 * sd.n_b, (size_t)2 * c->pw.n_b, (size_t)sd.n_u);
-  fill(keep_f, (size_t)2 * sd.n_b + sd.n_u, (size_t)2 * c->pw.n_b + c->pw.n_u, (size_t)sd.n_f);
-  if (h.size() * 8 > c->pw.cap) {
-    if (dev_alloc(&c->pw.buf, h.size() * 8)) return PINN_EHIP;
-    c->pw.cap = h.size() * 8;
-  }
-  HIPCHK(hipMemcpyAsync(c->pw.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->pw.n_b = sd.n_b; c->pw.n_u = sd.n_u; c->pw.n_f = sd.n_f;
-  c->pw.reset_b = c->pw.reset_u = c->pw.reset_f = false;
-  memcpy(c->pw.hdr, hdr, sizeof hdr);
-  return 0;
+  return lam_upload(c, s, L, h);
 }
 
 // k_t16_fused (KP_T16_FUSED) leaves the hidden-layer weight gradients in its tile-major scratch: the reductions read them there
@@ -814,16 +809,16 @@ static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   int rc = hipErrorInvalidValue;
   if constexpr (sizeof(real) == 8 && PDE != 2) {
     const bool weighted = PDE == 0 && c->sa.on;     // an Adam step moves the weights too
-    if (weighted) { if (int e = sa_prepare(c)) return e; }
+    if (weighted) { if (int e = lam_prepare(c, c->sa.arr, sa_layout(c))) return e; }
     const bool pw = PDE == PDE_ADR && c->pw.on;      // the adr kind's point weights; an Adam step moves them too
-    if (pw) { if (int e = pw_prepare(c)) return e; }
+    if (pw) { if (int e = lam_prepare(c, c->pw.arr, pw_layout(c))) return e; }
     const F20dLaunch a = fused20d_args(c, ev4);
     if constexpr (PDE == PDE_ADR) {
-      if (pw) rc = fused20d_launch_any(a, AdrPwArgs{pde_coef<double, PDE_ADR>(c), c->pw.buf, af ? af->bc_pw : 0.0});
+      if (pw) rc = fused20d_launch_any(a, AdrPwArgs{pde_coef<double, PDE_ADR>(c), c->pw.arr.buf, af ? af->bc_pw : 0.0});
       else rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR>(c));
     }
     else if constexpr (PDE == PDE_ADR_IDE) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_IDE>(c));
-    else if (weighted) rc = fused20d_launch_any(a, SaArgs{(double)c->nu, c->sa.buf, af ? af->alpha_sa : 0.0});
+    else if (weighted) rc = fused20d_launch_any(a, SaArgs{(double)c->nu, c->sa.arr.buf, af ? af->alpha_sa : 0.0});
     else rc = fused20d_launch_any(PDE, a, (double)c->nu);
   }
   if (rc) return fail(PINN_EHIP, "fused20d launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -1629,7 +1624,7 @@ int pinn_destroy(pinn_ctx* c) {
                   c->O, c->ZA, c->ZB, c->part, c->xe, c->te, c->Oe, c->f_out, c->loss_hist, c->snap,
                   c->lb_state, c->lb_x, c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al,
                   c->lb_q, c->lb_log_loss, c->lb_log_iter, c->lb_SY, c->lb_YY, c->lb_dots, c->lb_cs,
-                  c->lb_cy, c->lb_ex, c->img, c->row_index, c->sa.buf, c->pw.buf, c->d_ginfo, c->d_M[0], c->d_M[1], c->d_MT[0], c->d_MT[1],
+                  c->lb_cy, c->lb_ex, c->img, c->row_index, c->sa.arr.buf, c->pw.arr.buf, c->d_ginfo, c->d_M[0], c->d_M[1], c->d_MT[0], c->d_MT[1],
                   c->d_Ast, c->d_A3, c->d_U3, c->d_Nn, c->d_R, c->d_dAp, c->d_lossp, c->d_lamp,
                   c->pred, c->d_ref, c->err_partial, c->err_res, c->d_nonfinite, c->t16_bsync, c->t16_gscr,
                   c->rad.cx, c->rad.ct, c->rad.px, c->rad.pt, c->rad.O, c->rad.f, c->rad.w, c->rad.bsum, c->rad.tot};
@@ -1660,8 +1655,7 @@ int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_to
   c->nf_total = n_total;
   c->lhs.on = false;
   c->rad.on = false;
-  c->sa.reset_f = true;
-  c->pw.reset_f = true;
+  c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
   c->sets_dirty = true;
   return 0;
 }
@@ -1676,8 +1670,7 @@ int pinn_lhs_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   const bool same_shape = c->lhs.on && !c->sets_dirty && c->lhs.count == count;
   c->lhs.on = true; c->lhs.n_design = n_design; c->lhs.first = first; c->lhs.count = count; c->lhs.seed = seed;
   c->rad.on = false;
-  c->sa.reset_f = true;
-  c->pw.reset_f = true;
+  c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
   c->Xf.clear();
   c->nf_total = n_design;
   c->sd.inv_nf = 1.0 / (double)n_design;
@@ -1703,8 +1696,7 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   if (int rc = rad_alloc(c, count, n_pool)) return rc;
   c->lhs.on = false;
   c->rad.on = true; c->rad.n_design = n_design; c->rad.first = first; c->rad.count = count;
-  c->sa.reset_f = true;
-  c->pw.reset_f = true;
+  c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
   c->Xf.clear();
   c->nf_total = n_design;
   c->sd.inv_nf = 1.0 / (double)n_design;
@@ -1744,8 +1736,7 @@ int pinn_set_data(pinn_ctx* c, const double* X_u, const double* u, int64_t n, in
   c->Xu.assign(X_u, X_u + 2 * n);
   c->U.assign(u, u + (size_t)c->nd.n_out * n);
   c->nu_total = n_total;
-  c->sa.reset_u = true;
-  c->pw.reset_u = true;
+  c->sa.arr.reset[LAM_DATA] = c->pw.arr.reset[LAM_DATA] = true;
   c->sets_dirty = true;
   return 0;
 }
@@ -1757,7 +1748,7 @@ int pinn_set_boundary(pinn_ctx* c, const double* X_lb, const double* X_ub, int64
   c->Xlo.assign(X_lb, X_lb + 2 * n);
   c->Xhi.assign(X_ub, X_ub + 2 * n);
   c->nb_total = n_total;
-  c->pw.reset_b = true;
+  c->pw.arr.reset[LAM_PAIRS] = true;
   c->sets_dirty = true;
   return 0;
 }
@@ -2757,18 +2748,11 @@ int pinn_sa_set_weights(pinn_ctx* c, const double* lam_u, int64_t n_u, const dou
   for (int64_t i = 0; i < n_f; ++i) REQUIRE(std::isfinite(lam_f[i]), "pinn_sa_set_weights: lam_f[%lld] is not finite", (long long)i);
   HIPCHK(hipSetDevice(c->device));
   if (int rc = ensure_sets(c)) return rc;
-  std::vector<double> h(sa_doubles(c->sd.n_u + c->sd.n_f), 0.0);
-  h[0] = c->b1; h[1] = c->b2; h[2] = c->eps;
-  for (int64_t j = 0; j < n_u; ++j) h[SA_CONST + 3 * j] = lam_u[j];
-  for (int64_t i = 0; i < n_f; ++i) h[SA_CONST + 3 * (n_u + i)] = lam_f[i];
-  if (h.size() * 8 > c->sa.cap) {
-    if (dev_alloc(&c->sa.buf, h.size() * 8)) return PINN_EHIP;
-    c->sa.cap = h.size() * 8;
-  }
-  HIPCHK(hipMemcpyAsync(c->sa.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->sa.n_u = c->sd.n_u; c->sa.n_f = c->sd.n_f; c->sa.reset_u = c->sa.reset_f = false;
-  c->sa.k[0] = c->b1; c->sa.k[1] = c->b2; c->sa.k[2] = c->eps;
+  const LamLayout L = sa_layout(c);
+  std::vector<double> h(L.doubles(), 0.0);
+  for (int64_t j = 0; j < n_u; ++j) h[L.at(LAM_DATA) + 3 * j] = lam_u[j];
+  for (int64_t i = 0; i < n_f; ++i) h[L.at(LAM_COL) + 3 * i] = lam_f[i];
+  if (int rc = lam_upload(c, c->sa.arr, L, h)) return rc;
   c->sa.on = true;
   return 0;
 }
@@ -2783,12 +2767,12 @@ int pinn_sa_get_weights(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, 
           (long long)n_u, (long long)n_f, (long long)cu, (long long)cf);
   HIPCHK(hipSetDevice(c->device));
   if (int rc = ensure_sets(c)) return rc;
-  if (int rc = sa_prepare(c)) return rc;            // a replaced set reads back as ones
-  std::vector<double> h(sa_doubles(c->sd.n_u + c->sd.n_f));
-  HIPCHK(hipMemcpyAsync(h.data(), c->sa.buf, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (int64_t j = 0; j < n_u; ++j) lam_u[j] = h[SA_CONST + 3 * j];
-  for (int64_t i = 0; i < n_f; ++i) lam_f[i] = h[SA_CONST + 3 * (n_u + i)];
+  const LamLayout L = sa_layout(c);
+  if (int rc = lam_prepare(c, c->sa.arr, L)) return rc;            // a replaced set reads back as ones
+  std::vector<double> h;
+  if (int rc = lam_download(c, c->sa.arr, h)) return rc;
+  for (int64_t j = 0; j < n_u; ++j) lam_u[j] = h[L.at(LAM_DATA) + 3 * j];
+  for (int64_t i = 0; i < n_f; ++i) lam_f[i] = h[L.at(LAM_COL) + 3 * i];
   return 0;
 }
 
@@ -2807,7 +2791,7 @@ int pinn_sa_disable(pinn_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------
-// per-point loss weights of the adr kind (include/pinn_hip.h pinn_pw_*; k_fused20d_pw, fused20d_api.h)
+// per-point loss weights of the adr kind (include/pinn_hip.h pinn_pw_*; k_fused20d<PDE_ADR, ..> with SAW, fused20d_api.h)
 // ------------------------------------------------------------------------------------------
 // what the weighted kernel serves: the adr kind in float64 on kernel path 7, one device; checked before any device work
 static int pw_supported(const pinn_ctx* c, const char* who) {
@@ -2841,24 +2825,15 @@ int pinn_pw_set(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam
   for (int64_t p = 0; lam_b && p < n_b; ++p) REQUIRE(std::isfinite(lam_b[p]), "pinn_pw_set: lam_b[%lld] is not finite", (long long)p);
   HIPCHK(hipSetDevice(c->device));
   if (int rc = ensure_sets(c)) return rc;
-  const SetDesc& sd = c->sd;
-  std::vector<double> h(pw_doubles(sd.n_all), 0.0);
-  pw_header(c, h.data());
+  const LamLayout L = pw_layout(c);
+  std::vector<double> h(L.doubles(), 0.0);
   // a pair's weight lives in the lo point's entry: both lanes read it, the lo lane steps it, pinn_pw_get returns it.  The hi
-  // point's entry is never read; it gets the same start value on purpose, as pw_prepare's class-wide reset writes both, so
+  // point's entry is never read; it gets the same start value on purpose, as lam_prepare's class-wide reset writes both, so
   // that a dump of the array shows no stray value
-  for (int64_t p = 0; p < 2 * n_b; ++p) h[PW_CONST + 3 * p] = lam_b ? lam_b[p / 2] : 1.0;
-  for (int64_t j = 0; j < n_u; ++j) h[PW_CONST + 3 * (2 * n_b + j)] = lam_u ? lam_u[j] : 1.0;
-  for (int64_t i = 0; i < n_f; ++i) h[PW_CONST + 3 * (2 * n_b + n_u + i)] = lam_f ? lam_f[i] : 1.0;
-  if (h.size() * 8 > c->pw.cap) {
-    if (dev_alloc(&c->pw.buf, h.size() * 8)) return PINN_EHIP;
-    c->pw.cap = h.size() * 8;
-  }
-  HIPCHK(hipMemcpyAsync(c->pw.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->pw.n_b = sd.n_b; c->pw.n_u = sd.n_u; c->pw.n_f = sd.n_f;
-  c->pw.reset_b = c->pw.reset_u = c->pw.reset_f = false;
-  memcpy(c->pw.hdr, h.data(), sizeof c->pw.hdr);
+  for (int64_t p = 0; p < 2 * n_b; ++p) h[L.at(LAM_PAIRS) + 3 * p] = lam_b ? lam_b[p / 2] : 1.0;
+  for (int64_t j = 0; j < n_u; ++j) h[L.at(LAM_DATA) + 3 * j] = lam_u ? lam_u[j] : 1.0;
+  for (int64_t i = 0; i < n_f; ++i) h[L.at(LAM_COL) + 3 * i] = lam_f ? lam_f[i] : 1.0;
+  if (int rc = lam_upload(c, c->pw.arr, L, h)) return rc;
   c->pw.on = true;
   return 0;
 }
@@ -2869,13 +2844,13 @@ int pinn_pw_get(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, int64_t 
   if (int rc = pw_check_counts(c, "pinn_pw_get", n_u, n_f, n_b)) return rc;
   HIPCHK(hipSetDevice(c->device));
   if (int rc = ensure_sets(c)) return rc;
-  if (int rc = pw_prepare(c)) return rc;            // a replaced set reads back as ones
-  std::vector<double> h(pw_doubles(c->sd.n_all));
-  HIPCHK(hipMemcpyAsync(h.data(), c->pw.buf, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (int64_t p = 0; lam_b && p < n_b; ++p) lam_b[p] = h[PW_CONST + 3 * (2 * p)];
-  for (int64_t j = 0; lam_u && j < n_u; ++j) lam_u[j] = h[PW_CONST + 3 * (2 * n_b + j)];
-  for (int64_t i = 0; lam_f && i < n_f; ++i) lam_f[i] = h[PW_CONST + 3 * (2 * n_b + n_u + i)];
+  const LamLayout L = pw_layout(c);
+  if (int rc = lam_prepare(c, c->pw.arr, L)) return rc;            // a replaced set reads back as ones
+  std::vector<double> h;
+  if (int rc = lam_download(c, c->pw.arr, h)) return rc;
+  for (int64_t p = 0; lam_b && p < n_b; ++p) lam_b[p] = h[L.at(LAM_PAIRS) + 3 * (2 * p)];
+  for (int64_t j = 0; lam_u && j < n_u; ++j) lam_u[j] = h[L.at(LAM_DATA) + 3 * j];
+  for (int64_t i = 0; lam_f && i < n_f; ++i) lam_f[i] = h[L.at(LAM_COL) + 3 * i];
   return 0;
 }
 

@@ -71,7 +71,6 @@ int fused20d_ens_launch_any(int pde, const F20dLaunch& a, const double* nu_k);
 // written back.  (Three values and one interleaved array: with eight arguments, or per-class arrays, the tile-loop
 // variants spilled SGPRs.)
 constexpr int SA_CONST = 4;
-inline size_t sa_doubles(int n_all) { return (size_t)3 * n_all + SA_CONST; }
 struct SaArgs {
   double nu;
   double* lam;
@@ -85,18 +84,17 @@ int fused20d_launch_any(const F20dLaunch& a, const SaArgs& sa);
 // block pair-interleaved
 int fused20d_launch_any(const F20dLaunch& a, const AdrCoef<double>& k);
 
-// one evaluation of the same kind with trainable coefficients (k_fused20d_ide<PDE_ADR_IDE, H, .>): the coefficients are the six
+// one evaluation of the same kind with trainable coefficients (k_fused20d<PDE_ADR_IDE, H, .>): the coefficients are the six
 // entries behind the net's scalars in th, k.mask says which of their gradient entries are written (the others are 0.0)
 int fused20d_launch_any(const F20dLaunch& a, const AdrIdeArg& k);
 
-// Per-point loss weights of the adr kind (k_fused20d_pw<PDE_ADR, H, ., false, false, true>, pinn_pw_*).  lam holds PW_CONST
+// Per-point loss weights of the adr kind (k_fused20d<PDE_ADR, H, ., false, false, true>, pinn_pw_*).  lam holds PW_CONST
 // doubles -- beta1, beta2, eps of the ascent, then the ascent rate by point class at 3 + class (CLS_BLO: the pairs' rate,
 // CLS_BHI: 0, CLS_DATA, CLS_COL, CLS_PAD: 0), so a lane picks its rate without a branch -- then (lambda, m, v) by POINT INDEX of
 // the assembled set, [2 n_b pair-interleaved | n_u | n_f][3]: pair p's one entry stands at its lo point, 2 p (the entry at
 // 2 p + 1 is unused).  bc = sqrt(1 - b2^t) / (1 - b1^t) of an Adam step, by value, so a queued step needs no copy; 0 = the
 // weights are only read (loss_grad, L-BFGS, all rates 0).
 constexpr int PW_CONST = 8;
-inline size_t pw_doubles(int n_all) { return (size_t)3 * n_all + PW_CONST; }
 struct AdrPwArgs {
   AdrCoef<double> k;
   double* lam;

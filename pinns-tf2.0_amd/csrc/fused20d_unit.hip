@@ -25,46 +25,29 @@ void fused20d_row_index(const NetDesc& nd, int H, int* out) {
   }
 }
 
-// variant (ENS, SETS, SAW, ADR) at the depth of the net: PDE_ADR, pde 0 (the weighted loss) or pde 0 / 1
-template <int H, bool ENS, bool SETS, bool SAW, bool ADR>
-static int launch_h(int pde, const F20dLaunch& a, const f20d_nu_t<SETS, SAW, ADR ? PDE_ADR : 0>& nu) {
-  if constexpr (ADR) return fused20d_launch<PDE_ADR, H, ENS, SETS, SAW>(a, nu);
-  else if constexpr (SAW) return fused20d_launch<0, H, ENS, SETS, SAW>(a, nu);
-  else return pde == 1 ? fused20d_launch<1, H, ENS, SETS, SAW>(a, nu) : fused20d_launch<0, H, ENS, SETS, SAW>(a, nu);
-}
-template <bool ENS, bool SETS, bool SAW, bool ADR>
-static int launch_depth(int pde, const F20dLaunch& a, const f20d_nu_t<SETS, SAW, ADR ? PDE_ADR : 0>& nu) {
+// k_fused20d<PDE, H, ., ENS, SETS, SAW> at the depth of the net
+template <int PDE, bool ENS, bool SETS, bool SAW>
+static int launch_depth(const F20dLaunch& a, const f20d_nu_t<SETS, SAW, PDE>& nu) {
   switch (a.nd.n_hidden) {     // the AGPR stash holds (H - 2) x 40 registers: depths up to 8 fit the 256 of a wave
-    case 4: return launch_h<4, ENS, SETS, SAW, ADR>(pde, a, nu);
-    case 6: return launch_h<6, ENS, SETS, SAW, ADR>(pde, a, nu);
-    case 8: return launch_h<8, ENS, SETS, SAW, ADR>(pde, a, nu);
+    case 4: return fused20d_launch<PDE, 4, ENS, SETS, SAW>(a, nu);
+    case 6: return fused20d_launch<PDE, 6, ENS, SETS, SAW>(a, nu);
+    case 8: return fused20d_launch<PDE, 8, ENS, SETS, SAW>(a, nu);
     default: return (int)hipErrorInvalidValue;
   }
+}
+// the Burgers kinds share their entry points: pde 0 or 1 at run time
+template <bool ENS, bool SETS>
+static int launch_burgers(int pde, const F20dLaunch& a, const f20d_nu_t<SETS>& nu) {
+  return pde == 1 ? launch_depth<1, ENS, SETS, false>(a, nu) : launch_depth<0, ENS, SETS, false>(a, nu);
 }
 
-int fused20d_launch_any(int pde, const F20dLaunch& a, double nu) { return launch_depth<false, false, false, false>(pde, a, nu); }
-int fused20d_ens_launch_any(int pde, const F20dLaunch& a, double nu) { return launch_depth<true, false, false, false>(pde, a, nu); }
-int fused20d_ens_launch_any(int pde, const F20dLaunch& a, const double* nu_k) { return launch_depth<true, true, false, false>(pde, a, nu_k); }
-int fused20d_launch_any(const F20dLaunch& a, const SaArgs& sa) { return launch_depth<false, false, true, false>(0, a, sa); }
-int fused20d_launch_any(const F20dLaunch& a, const AdrCoef<double>& k) { return launch_depth<false, false, false, true>(0, a, k); }
-// the trainable-coefficient kind: solo launch only
-int fused20d_launch_any(const F20dLaunch& a, const AdrIdeArg& k) {
-  switch (a.nd.n_hidden) {
-    case 4: return fused20d_launch<PDE_ADR_IDE, 4, false, false, false>(a, k);
-    case 6: return fused20d_launch<PDE_ADR_IDE, 6, false, false, false>(a, k);
-    case 8: return fused20d_launch<PDE_ADR_IDE, 8, false, false, false>(a, k);
-    default: return (int)hipErrorInvalidValue;
-  }
-}
-
-// the adr kind with per-point loss weights: solo launch only
-int fused20d_launch_any(const F20dLaunch& a, const AdrPwArgs& k) {
-  switch (a.nd.n_hidden) {
-    case 4: return fused20d_launch<PDE_ADR, 4, false, false, true>(a, k);
-    case 6: return fused20d_launch<PDE_ADR, 6, false, false, true>(a, k);
-    case 8: return fused20d_launch<PDE_ADR, 8, false, false, true>(a, k);
-    default: return (int)hipErrorInvalidValue;
-  }
-}
+int fused20d_launch_any(int pde, const F20dLaunch& a, double nu) { return launch_burgers<false, false>(pde, a, nu); }
+int fused20d_ens_launch_any(int pde, const F20dLaunch& a, double nu) { return launch_burgers<true, false>(pde, a, nu); }
+int fused20d_ens_launch_any(int pde, const F20dLaunch& a, const double* nu_k) { return launch_burgers<true, true>(pde, a, nu_k); }
+// solo launches only: the weighted loss of pde 0, the adr kind, its trainable coefficients, its per-point weights
+int fused20d_launch_any(const F20dLaunch& a, const SaArgs& sa) { return launch_depth<0, false, false, true>(a, sa); }
+int fused20d_launch_any(const F20dLaunch& a, const AdrCoef<double>& k) { return launch_depth<PDE_ADR, false, false, false>(a, k); }
+int fused20d_launch_any(const F20dLaunch& a, const AdrIdeArg& k) { return launch_depth<PDE_ADR_IDE, false, false, false>(a, k); }
+int fused20d_launch_any(const F20dLaunch& a, const AdrPwArgs& k) { return launch_depth<PDE_ADR, false, false, true>(a, k); }
 
 }  // namespace pinn

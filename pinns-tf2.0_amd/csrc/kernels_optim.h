@@ -276,7 +276,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce_adam(const real* __restr
 // ---- ensembles: K members sharing the point set, float64, kernel path 7 (grid.y = member) ------------------------------
 // The member kernels below are k_reduce_rows / k_reduce_adam with per-member bases and the same per-column arithmetic, so a
 // member's gradient, moments and weights are bit-identical to a solo engine's.  Layouts: part [K][n_rows][R], gl [K][R],
-// theta / m / v [K][n], theta_r [K][sw] (sw = fused20d_weight_doubles(n): the LDS-DMA pieces of k_fused20d_ens),
+// theta / m / v [K][n], theta_r [K][sw] (sw = fused20d_weight_doubles(n): the LDS-DMA pieces of k_fused20d's ENS variants),
 // loss3 [K][3] (per step), nonfinite [K].
 constexpr int ENS_MAX = 64;
 struct EnsStep {

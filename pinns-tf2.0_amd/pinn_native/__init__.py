@@ -16,21 +16,18 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _REPO = os.path.dirname(os.path.dirname(_HERE))
 LIB_PATH = os.environ.get("PINN_HIP_LIB") or os.path.join(_HERE, "libpinn_hip.so")
-SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_fused20d_kernel.h", "kernels_wide.h", "kernels_predict20.h",
+SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_wide.h", "kernels_predict20.h",
            "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h"]
 HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
-PDE_KINDS = {"burgers": 0, "burgers_ide": 1, "schrodinger": 2, "burgers_disc": 3, "burgers_disc_ide": 4, "adr": 5}
-# the kinds added since, in a table of their own: PDE_KINDS is pinned as the six kinds 0..5 (tests/test_adr_host.py)
-PDE_KINDS_MORE = {"adr_ide": 6}
+PDE_KINDS = {"burgers": 0, "burgers_ide": 1, "schrodinger": 2, "burgers_disc": 3, "burgers_disc_ide": 4, "adr": 5, "adr_ide": 6}
 
 
 def pde_kind(name):
-    """name -> enum value of include/pinn_hip.h (PDE_KINDS and PDE_KINDS_MORE); ValueError with the table otherwise"""
-    kinds = dict(PDE_KINDS, **PDE_KINDS_MORE)
-    if name not in kinds:
-        raise ValueError("pde must be one of %s" % sorted(kinds))
-    return kinds[name]
+    """name -> enum value of include/pinn_hip.h (PDE_KINDS); ValueError with the table otherwise"""
+    if name not in PDE_KINDS:
+        raise ValueError("pde must be one of %s" % sorted(PDE_KINDS))
+    return PDE_KINDS[name]
 
 
 DTYPES = {"f32": 0, "f64": 1, "float32": 0, "float64": 1}

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the trainable-coefficient residual on the float64 register-stash kernel: k_fused20d_ide<ADR_IDE, 8> (pde "adr_ide", all
+"""Cost of the trainable-coefficient residual on the float64 register-stash kernel: k_fused20d<ADR_IDE, 8> (pde "adr_ide", all
 six coefficients trained) against the unchanged k_fused20d<ADR, 8> (pde "adr") on the same points, weights and coefficients,
 in one process.  Cases: N_f = 10^4 (one tile per workgroup) and 10^6 (the tile loop), each without boundary pairs and with 200
 periodic pairs.  Per case: warm-up, then --blocks alternating blocks of --reps loss+gradient evaluations (adr, adr_ide, adr,

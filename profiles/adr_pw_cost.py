@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the per-point loss weights of the adr kind on the float64 register-stash kernel: k_fused20d_pw<ADR, 8, ., SAW>
+"""Cost of the per-point loss weights of the adr kind on the float64 register-stash kernel: k_fused20d<ADR, 8, ., SAW>
 against the unchanged k_fused20d<ADR, 8> on the same points and weights, in one process (built like profiles/adr_cost.py).
 Cases: N_f = 10^4 (one tile per workgroup) and 10^6 (the tile loop), without boundary pairs and with 200 periodic pairs.
 Arms, all timed inside Adam steps (theta rate 1e-12, so the weights stay where they are):

@@ -1,4 +1,4 @@
-"""numpy float64 restatement of the adr kind with per-point loss weights (include/pinn_hip.h pinn_pw_*, k_fused20d_pw of
+"""numpy float64 restatement of the adr kind with per-point loss weights (include/pinn_hip.h pinn_pw_*, k_fused20d<PDE_ADR, .., SAW> of
 pinns-tf2.0_amd/csrc/kernels_fused20d.h): adr_ref.adr_loss_grad with the three lambda classes, in the manner of sa_ref.py.
 
     L = (1/N_f) sum_i lam_f,i^2 f_i^2 + (1/N_u) sum_j lam_u,j^2 (u_j - u*_j)^2

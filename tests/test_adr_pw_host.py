@@ -1,4 +1,4 @@
-"""CPU: per-point loss weights of the adr kind (include/pinn_hip.h pinn_pw_*, k_fused20d_pw of csrc/kernels_fused20d.h,
+"""CPU: per-point loss weights of the adr kind (include/pinn_hip.h pinn_pw_*, k_fused20d<PDE_ADR, .., SAW> of csrc/kernels_fused20d.h,
 pinn_native.Engine.pw_*, utils/neuralnetwork.py hp["point_weights"]) without a device.
 
   * tests/helpers/adr_pw_ref.py, the numpy restatement the GPU tests use: with unit weights it IS adr_ref.adr_loss_grad (bit for

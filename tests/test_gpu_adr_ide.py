@@ -3,7 +3,7 @@ restatement tests/helpers/adr_ide_ref.py (pinned on the CPU by tests/test_adr_id
 
   theta = [net | a0, a1, log nu, r1, r2, r3];  f and the loss are those of "adr";  a frozen coefficient's gradient entry is 0.0
 
-Float64 on the generic kernels (path 0) and on the six k_fused20d_ide variants (path 7: k_fused20d's text for PDE_ADR_IDE), float32 on path 0.  Tolerances on
+Float64 on the generic kernels (path 0) and on the six k_fused20d<PDE_ADR_IDE, H, .> variants (path 7), float32 on path 0.  Tolerances on
 the loss, the whole-vector gradient and the residual are TOL of tests/test_gpu_adr.py; the six tail entries are judged each
 on its own scale A_k = sum |fb df/dp_k| with K of tests/helpers/grad_entries.py."""
 import functools

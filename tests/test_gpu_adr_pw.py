@@ -1,4 +1,4 @@
-"""GPU: per-point loss weights of the adr kind (pinn_pw_*, k_fused20d_pw<PDE_ADR, H, ., SAW>, float64, kernel path 7) against
+"""GPU: per-point loss weights of the adr kind (pinn_pw_*, k_fused20d<PDE_ADR, H, ., SAW>, float64, kernel path 7) against
 the numpy restatement tests/helpers/adr_pw_ref.py (pinned on the CPU by tests/test_adr_pw_host.py).
 
     L = (1/N_f) sum lam_f^2 f^2 + (1/N_u) sum lam_u^2 (u - u*)^2 + (1/N_b) sum lam_b^2 [du^2 + du_x^2]   (one lam per pair)
@@ -214,6 +214,41 @@ def test_only_adam_moves_the_weights_and_lbfgs_minimises_the_weighted_loss(recor
     got = eng.pw_get()
     assert np.array_equal(got[0], lam[0]) and np.array_equal(got[2], lam[2]) and np.all(got[1] == 1.0) and got[1].shape == (3000,)
     eng.close()
+
+
+def test_new_adam_constants_rewrite_the_header_and_keep_weights_and_moments():
+    """Two contexts alike (4 x 20, 3 pairs, N_u = 5, N_f = 70: two 64-point tiles, the second ragged, one tile per workgroup),
+    all three rates on.  After 3 steps both get pinn_adam_init with the constants they had; the second gets other (beta1, beta2,
+    eps) first, reads its weights (which brings the array's header up to date) and then the old constants again, so its header
+    is rewritten twice before the next step.  Network weights and all lambdas stay equal bit for bit after every step: lambda,
+    m and v of every point and pair survived the rewrites.  One tile per workgroup only: nothing here forces another launch
+    plan.  Last, one step with the second context under the other constants: its lambdas must then differ, so the header it
+    wrote is the one the kernel reads."""
+    k, consts = 3, (1e-3, 0.9, 0.999, 1e-7)
+    c = case_of(4, 70, 3, 5)
+    a, b = make(c, adr_ref.ALLEN_CAHN), make(c, adr_ref.ALLEN_CAHN)
+    for e in (a, b):
+        e.adam_init(*consts)
+        e.pw_adam_init(0.05, 0.02, 0.01)
+
+    def step_and_compare():
+        for _ in range(k):
+            assert np.array_equal(a.adam_run(1), b.adam_run(1))
+            assert np.array_equal(a.get_weights(), b.get_weights())
+            assert lams_equal(a.pw_get(), b.pw_get())
+
+    step_and_compare()
+    assert not np.array_equal(a.pw_get()[1], c["lam_f"])            # the ascent is on
+    a.adam_init(*consts)
+    b.adam_init(1e-3, 0.8, 0.99, 1e-5)
+    assert lams_equal(a.pw_get(), b.pw_get())
+    b.adam_init(*consts)
+    step_and_compare()
+    a.adam_init(*consts)
+    b.adam_init(1e-3, 0.8, 0.99, 1e-5)
+    a.adam_run(1), b.adam_run(1)
+    assert not any(np.array_equal(x, y) for x, y in zip(a.pw_get(), b.pw_get()))
+    a.close(); b.close()
 
 
 # ---- 5. set replacement resets exactly its class; refusals -----------------------------------------------------------------

@@ -37,10 +37,10 @@ def _sets(n_f, n_u=100, seed=0):
     return X_f, X_u, u
 
 
-def _engine(H, n_f, seed=0, w=None):
+def _engine(H, n_f, seed=0, w=None, n_u=100):
     import pinn_native
     from oracle import init
-    X_f, X_u, u = _sets(n_f, seed=seed)
+    X_f, X_u, u = _sets(n_f, n_u=n_u, seed=seed)
     eng = pinn_native.Engine(_layers(H), LB, UB, pde="burgers", dtype="f64")
     assert eng.kernel_path() == 7
     eng.set_collocation(X_f)
@@ -134,6 +134,42 @@ def test_only_adam_moves_the_weights_and_disable_restores_plain_bits(n_f):
     a, b = plain.loss_grad(), eng.loss_grad()
     assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
     eng.close(); plain.close()
+
+
+def test_new_adam_constants_rewrite_the_header_and_keep_weights_and_moments():
+    """Two contexts alike (4 x 20, N_u = 5, N_f = 70: two 64-point tiles, the second ragged, one tile per workgroup), ascent on.
+    After 3 steps both get pinn_adam_init with the constants they had; the second gets other (beta1, beta2, eps) first, reads
+    its weights (which brings the array's header up to date) and then the old constants again, so its header is rewritten twice
+    before the next step.  Network weights and all lambdas stay equal bit for bit after every step: lambda, m and v of every
+    point survived the rewrites.  One tile per workgroup only: nothing here forces another launch plan.  Last, one step with
+    the second context under the other constants: its lambdas must then differ, so the header it wrote is the one the
+    kernel reads."""
+    k, consts = 3, (1e-3, 0.9, 0.999, 1e-7)
+    rs = np.random.RandomState(3)
+    lam_u, lam_f = rs.uniform(0.5, 2.0, 5), rs.uniform(0.5, 2.0, 70)
+    a, b = _engine(4, 70, n_u=5)[0], _engine(4, 70, n_u=5)[0]
+    for e in (a, b):
+        e.sa_set_weights(lam_u, lam_f)
+        e.sa_adam_init(0.05)
+
+    def step_and_compare():
+        for _ in range(k):
+            assert np.array_equal(a.adam_run(1), b.adam_run(1))
+            assert np.array_equal(a.get_weights(), b.get_weights())
+            assert all(np.array_equal(x, y) for x, y in zip(a.sa_get_weights(), b.sa_get_weights()))
+
+    step_and_compare()
+    assert not np.array_equal(a.sa_get_weights()[1], lam_f)         # the ascent is on
+    a.adam_init(*consts)
+    b.adam_init(1e-3, 0.8, 0.99, 1e-5)
+    assert all(np.array_equal(x, y) for x, y in zip(a.sa_get_weights(), b.sa_get_weights()))
+    b.adam_init(*consts)
+    step_and_compare()
+    a.adam_init(*consts)
+    b.adam_init(1e-3, 0.8, 0.99, 1e-5)
+    a.adam_run(1), b.adam_run(1)
+    assert not any(np.array_equal(x, y) for x, y in zip(a.sa_get_weights(), b.sa_get_weights()))
+    a.close(); b.close()
 
 
 def test_replacing_a_set_resets_its_class_and_refusals_leave_the_context_usable():

@@ -87,8 +87,8 @@ def test_no_scratch_in_the_kernels_that_serve_the_baseline_configs_or_the_exchan
 @needs_tools
 def test_the_kernel_listing_names_every_kernel_with_its_digest_and_resources():
     """`isa_lint.py --listing`: what two builds are compared by (profiles/refactor_paths_device_code.txt).  Every kernel has
-    a line, with metadata from the code object's notes; k_fused20d's 48 variants sit in their own code
-    object; the listing of one library is the same twice."""
+    a line, with metadata from the code object's notes; k_fused20d's 60 variants sit in their own code
+    object, all under that one name; the listing of one library is the same twice."""
     import re
     import pinn_native
     if not os.path.exists(isa_lint.READELF):
@@ -98,5 +98,6 @@ def test_the_kernel_listing_names_every_kernel_with_its_digest_and_resources():
     assert len(lines) > 50 and len(set(lines)) == len(lines)
     form = re.compile(r"^\d+ \S+ insns=\d+ sha=[0-9a-f]{16} vgpr=\d+ agpr=\d+ sgpr=\d+ lds=\d+ scratch=\d+$")
     assert all(form.match(l) for l in lines), [l for l in lines if not form.match(l)][:3]
-    assert sum("k_fused20dI" in l for l in lines) == 48 and len({l.split()[0] for l in lines if "k_fused20dI" in l}) == 1
+    assert sum("k_fused20dI" in l for l in lines) == 60 and len({l.split()[0] for l in lines if "k_fused20dI" in l}) == 1
+    assert not [l for l in lines if "k_fused20d_" in l.split()[1]]
     assert lines == isa_lint.kernel_listing(pinn_native.LIB_PATH)

@@ -396,6 +396,29 @@ int pinn_pw_get(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, int64_t 
 int pinn_pw_adam_init(pinn_ctx* c, double rate_u, double rate_f, double rate_b);
 int pinn_pw_disable(pinn_ctx* c);
 
+/* Robin points of the adr kind (PINN_PDE_ADR): a fourth point class.  Point j is a location (x_j, t_j) with three numbers
+ * (alpha_j, beta_j, g_j); its residual and the loss are
+ *   r_j = alpha_j u(x_j, t_j) + beta_j u_x(x_j, t_j) - g_j
+ *   L   = mean_f f^2 + mean_u (u - u*)^2 + mean_b [(u_lo - u_hi)^2 + (u_x,lo - u_x,hi)^2] + (1 / N_w) sum_j r_j^2
+ * with N_w = n_total, the global count.  The coefficients are per point: (1, 0, g) is a Dirichlet value, (0, 1, g) a Neumann
+ * flux, (h, 1, g) a Robin wall; g may differ from point to point (time-dependent wall data), and a point may lie inside the
+ * domain (a derivative observation).  The Robin part is ADDED to the boundary part: pinn_loss_grad's terms[2] = periodic
+ * part + Robin part; the gradient row keeps its layout.  Float32 and float64, kernel paths 0 and 7.
+ *   pinn_set_robin       X_w [n][2] = (x, t), alpha, beta, g [n]; replaces the class, n = 0 removes it -- from then on every
+ *                        result is bit-identical to a context that never had Robin points.  The points survive
+ *                        pinn_set_collocation, pinn_lhs_collocation, pinn_rad_collocation, pinn_set_data and
+ *                        pinn_set_boundary; they are no collocation points (pinn_get_collocation, pinn_residual and the
+ *                        adaptive draw do not see them).
+ *   pinn_robin_residual  r_j at the current weights, forward only; n must be the local count (n = 0: nothing is written)
+ * Refusals, before any device work, the context unchanged: PINN_EUNSUPPORTED for any kind but PINN_PDE_ADR (PINN_PDE_ADR_IDE
+ * included), while point weights are on (and pinn_pw_set is refused while Robin points are present), a kernel path other
+ * than 0 or 7, a communicator (pinn_comm_init and pinn_comm_xgmi_export are refused the same way while Robin points are
+ * present); PINN_EINVAL for null arrays with n > 0, n < 0 or n_total < n, a non-finite coordinate or coefficient, a point
+ * with alpha = beta = 0 (it constrains nothing), a buffer of another length.  (Additive: the ABI version stays 6.) */
+int pinn_set_robin(pinn_ctx* c, const double* X_w /*[n][2]*/, const double* alpha, const double* beta, const double* g,
+                   int64_t n, int64_t n_total);
+int pinn_robin_residual(pinn_ctx* c, double* out /*[n]*/, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -266,6 +266,19 @@ struct pinn_ctx {
     LamStore arr;
   } pw;
 
+  // Robin points of the adr kind (pinn_set_robin; template value PDE_ADR_ROBIN of the kernels): as handed over, and the
+  // (alpha, beta) pairs on the device in the compute dtype.  The block stands behind the collocation block of the assembled
+  // set: points first .. first + n - 1 (ensure_sets)
+  struct {
+    std::vector<double> X, alpha, beta, g;
+    int64_t n_total = 0;
+    void* ab = nullptr;
+    size_t cap = 0;
+    int first = 0, n = 0;
+    double* out = nullptr;             // pinn_robin_residual's device buffer
+    size_t cap_out = 0;
+  } robin;
+
   // discrete-time models (pde 3, 4): stage sets as handed over, device copies, scratch
   struct DiscSet { std::vector<double> x, t, M; int q = 0; bool has_M = false; };
   DiscSet dset[2];
@@ -318,6 +331,10 @@ template <typename real, int PDE>
 static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
   if constexpr (PDE == PDE_ADR)
     return AdrCoef<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5]};
+  else if constexpr (PDE == PDE_ADR_ROBIN)
+    return AdrRobinArg<real>{AdrCoef<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5]},
+                             (const real*)c->robin.ab, c->robin.first, c->robin.n,
+                             (real)(c->robin.n_total > 0 ? 1.0 / (double)c->robin.n_total : 0.0)};
   else if constexpr (PDE == PDE_ADR_IDE)
     return AdrIdeArg{c->adr_mask};
   else
@@ -481,7 +498,9 @@ static int lhs_fill(pinn_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------
-// training-set assembly: [boundary-lo | boundary-hi | data | collocation | pad]
+// training-set assembly: [boundary-lo | boundary-hi | data | collocation | pad]; the adr kind's Robin points, if any, are a
+// block of their own between the collocation block and the padding.  SetDesc does not count them (sd.n_all ends the
+// collocation block, as every kernel's point classes expect); sd.n_pad covers them
 // ------------------------------------------------------------------------------------------
 static int ensure_sets(pinn_ctx* c) {
   if (!c->sets_dirty) return 0;
@@ -493,7 +512,8 @@ static int ensure_sets(pinn_ctx* c) {
   if (c->pde != PINN_PDE_SCHRODINGER && !adr_family(c)) REQUIRE(n_b == 0, "boundary pairs are Schrodinger-only");
   const int n_all = 2 * n_b + n_u + n_f;
   REQUIRE(n_all > 0, "no training points set");
-  const int n_pad = (n_all + 63) / 64 * 64;
+  const int n_w = is_adr(c) ? (int)(c->robin.X.size() / 2) : 0;
+  const int n_pad = (n_all + n_w + 63) / 64 * 64;
   REQUIRE(2 * n_b <= CHUNK_POINTS / 2, "too many boundary pairs for one chunk (%d)", n_b);
   SetDesc sd{};
   sd.n_b = n_b; sd.n_u = n_u; sd.n_f = n_f; sd.n_all = n_all; sd.n_pad = n_pad;
@@ -519,6 +539,13 @@ static int ensure_sets(pinn_ctx* c) {
   }
   if (!c->lhs.on && !c->rad.on)
     for (int i = 0; i < n_f; ++i, ++g) { hx[g] = c->Xf[2 * i]; ht[g] = c->Xf[2 * i + 1]; }
+  if (c->lhs.on || c->rad.on)                                      // filled on the device, below
+    for (int i = 0; i < n_f; ++i, ++g) { hx[g] = c->lb[0]; ht[g] = c->lb[1]; }
+  c->robin.first = n_all; c->robin.n = n_w;
+  for (int j = 0; j < n_w; ++j, ++g) {                             // g_j rides in tgt at the point's own index
+    hx[g] = c->robin.X[2 * j]; ht[g] = c->robin.X[2 * j + 1];
+    htg[g] = c->robin.g[j];
+  }
   for (; g < n_pad; ++g) { hx[g] = c->lb[0]; ht[g] = c->lb[1]; }   // inert padding (zero seeds); LHS slots filled below
   if (c->rad.on && c->rad.filled && n_f > 0) {                     // the last adaptive draw, kept through re-assemblies
     const size_t off = (size_t)(2 * n_b + n_u);
@@ -538,6 +565,15 @@ static int ensure_sets(pinn_ctx* c) {
   if (upload_real(c, c->xs, hx.data(), n_pad)) return PINN_EHIP;
   if (upload_real(c, c->ts, ht.data(), n_pad)) return PINN_EHIP;
   if (upload_real(c, c->tgt, htg.data(), (size_t)NO * n_pad)) return PINN_EHIP;
+  if (n_w > 0) {
+    std::vector<double> hab((size_t)2 * n_w);
+    for (int j = 0; j < n_w; ++j) { hab[2 * j] = c->robin.alpha[j]; hab[2 * j + 1] = c->robin.beta[j]; }
+    if (hab.size() > c->robin.cap) {
+      if (dev_alloc(&c->robin.ab, hab.size() * rs)) return PINN_EHIP;
+      c->robin.cap = hab.size();
+    }
+    if (upload_real(c, c->robin.ab, hab.data(), hab.size())) return PINN_EHIP;
+  }
   if (c->lhs.on) { if (int rc = lhs_fill(c)) return rc; }
 
   c->chunk = n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS;
@@ -817,6 +853,7 @@ static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
       if (pw) rc = fused20d_launch_any(a, AdrPwArgs{pde_coef<double, PDE_ADR>(c), c->pw.arr.buf, af ? af->bc_pw : 0.0});
       else rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR>(c));
     }
+    else if constexpr (PDE == PDE_ADR_ROBIN) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_ROBIN>(c));
     else if constexpr (PDE == PDE_ADR_IDE) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_IDE>(c));
     else if (weighted) rc = fused20d_launch_any(a, SaArgs{(double)c->nu, c->sa.arr.buf, af ? af->alpha_sa : 0.0});
     else rc = fused20d_launch_any(PDE, a, (double)c->nu);
@@ -1139,7 +1176,8 @@ static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
   switch (c->pde) {                                                          \
     case PINN_PDE_BURGERS: rc = launch_sweeps<REAL, 0>(c, ev4, af); break;       \
     case PINN_PDE_BURGERS_IDE: rc = launch_sweeps<REAL, 1>(c, ev4, af); break;   \
-    case PINN_PDE_ADR: rc = launch_sweeps<REAL, PDE_ADR>(c, ev4, af); break;     \
+    case PINN_PDE_ADR: rc = c->robin.n > 0 ? launch_sweeps<REAL, PDE_ADR_ROBIN>(c, ev4, af)  /* the parent's kernels without */ \
+                                           : launch_sweeps<REAL, PDE_ADR>(c, ev4, af); break; \
     case PINN_PDE_ADR_IDE: rc = launch_sweeps<REAL, PDE_ADR_IDE>(c, ev4, af); break; \
     default: rc = launch_sweeps<REAL, 2>(c, ev4, af); break;                     \
   }
@@ -1627,7 +1665,8 @@ int pinn_destroy(pinn_ctx* c) {
                   c->lb_cy, c->lb_ex, c->img, c->row_index, c->sa.arr.buf, c->pw.arr.buf, c->d_ginfo, c->d_M[0], c->d_M[1], c->d_MT[0], c->d_MT[1],
                   c->d_Ast, c->d_A3, c->d_U3, c->d_Nn, c->d_R, c->d_dAp, c->d_lossp, c->d_lamp,
                   c->pred, c->d_ref, c->err_partial, c->err_res, c->d_nonfinite, c->t16_bsync, c->t16_gscr,
-                  c->rad.cx, c->rad.ct, c->rad.px, c->rad.pt, c->rad.O, c->rad.f, c->rad.w, c->rad.bsum, c->rad.tot};
+                  c->rad.cx, c->rad.ct, c->rad.px, c->rad.pt, c->rad.O, c->rad.f, c->rad.w, c->rad.bsum, c->rad.tot,
+                  c->robin.ab, c->robin.out};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& p : c->pend) {
     if (p.h_state) (void)hipHostFree(p.h_state);
@@ -1750,6 +1789,63 @@ int pinn_set_boundary(pinn_ctx* c, const double* X_lb, const double* X_ub, int64
   c->nb_total = n_total;
   c->pw.arr.reset[LAM_PAIRS] = true;
   c->sets_dirty = true;
+  return 0;
+}
+
+// Robin points of the adr kind: alpha u + beta u_x = g at (x_j, t_j).  Every refusal stands in front of any device work and
+// leaves the context as it was (the arrays are looked at first: they need no context); n = 0 removes the class.
+int pinn_set_robin(pinn_ctx* c, const double* X_w, const double* alpha, const double* beta, const double* g, int64_t n,
+                   int64_t n_total) {
+  REQUIRE(n >= 0 && n_total >= n, "pinn_set_robin: bad counts (n %lld, n_total %lld)", (long long)n, (long long)n_total);
+  REQUIRE(n <= (1 << 30), "pinn_set_robin: too many points (%lld)", (long long)n);
+  REQUIRE(n == 0 || (X_w && alpha && beta && g), "pinn_set_robin: null array");
+  for (int64_t j = 0; j < n; ++j) {
+    REQUIRE(std::isfinite(X_w[2 * j]) && std::isfinite(X_w[2 * j + 1]), "pinn_set_robin: point %lld is not finite", (long long)j);
+    REQUIRE(std::isfinite(alpha[j]) && std::isfinite(beta[j]) && std::isfinite(g[j]),
+            "pinn_set_robin: alpha, beta or g of point %lld is not finite", (long long)j);
+    REQUIRE(alpha[j] != 0.0 || beta[j] != 0.0, "pinn_set_robin: point %lld has alpha = beta = 0: it constrains nothing", (long long)j);
+  }
+  REQUIRE(c, "pinn_set_robin: null context");
+  if (c->pde == PINN_PDE_ADR_IDE)
+    return fail(PINN_EUNSUPPORTED, "pinn_set_robin: Robin points are for the adr kind (pde 5) only; the adr_ide kind (pde 6) has no variant for them");
+  if (!is_adr(c)) return fail(PINN_EUNSUPPORTED, "pinn_set_robin: Robin points are for the adr kind (pde 5) only");
+  if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_set_robin: point weights do not cover Robin points (pinn_pw_disable first)");
+  if (!adr_has_path(c->path))
+    return fail(PINN_EUNSUPPORTED, "pinn_set_robin: Robin points run on kernel paths 0 and 7 only (this context runs path %d)", (int)c->path);
+  if (c->comm || c->xg.box)
+    return fail(PINN_EUNSUPPORTED, "pinn_set_robin: Robin points are single-device; this context has a communicator");
+  c->robin.X.assign(X_w, X_w + 2 * n);
+  c->robin.alpha.assign(alpha, alpha + n);
+  c->robin.beta.assign(beta, beta + n);
+  c->robin.g.assign(g, g + n);
+  c->robin.n_total = n_total;
+  if (n == 0) c->robin.n = 0;
+  c->sets_dirty = true;
+  return 0;
+}
+
+// r_j = alpha_j u + beta_j u_x - g_j at the current weights: the generic forward sweep over the set, then k_robin_residual
+int pinn_robin_residual(pinn_ctx* c, double* out, int64_t n) {
+  REQUIRE(c, "null");
+  if (!is_adr(c)) return fail(PINN_EUNSUPPORTED, "pinn_robin_residual: Robin points are for the adr kind (pde 5) only");
+  REQUIRE(n == (int64_t)(c->robin.X.size() / 2), "pinn_robin_residual: buffer holds %lld values, the context has %lld Robin points",
+          (long long)n, (long long)(c->robin.X.size() / 2));
+  if (n == 0) return 0;
+  REQUIRE(out, "null");
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = ensure_sets(c)) return rc;
+  if ((size_t)n > c->robin.cap_out) { if (dev_alloc(&c->robin.out, (size_t)n * 8)) return PINN_EHIP; c->robin.cap_out = (size_t)n; }
+  if (int rc = forward_taylor(c, c->xs, c->ts, c->sd.n_pad, c->chunk, c->O)) return rc;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (c->dtype == PINN_F64)
+    hipLaunchKernelGGL((k_robin_residual<double>), grid, block, 0, c->stream, pde_coef<double, PDE_ADR_ROBIN>(c),
+                       (const vec4<double>*)c->O, (const double*)c->tgt, c->robin.out);
+  else
+    hipLaunchKernelGGL((k_robin_residual<float>), grid, block, 0, c->stream, pde_coef<float, PDE_ADR_ROBIN>(c),
+                       (const vec4<float>*)c->O, (const float*)c->tgt, c->robin.out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, c->robin.out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 
@@ -2440,6 +2536,7 @@ int pinn_comm_init(pinn_ctx* c, const char* id128, int n_ranks, int rank) {
   if (c->sa.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: self-adaptive weights are single-device (pinn_sa_disable first)");
   if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: point weights are single-device (pinn_pw_disable first)");
   if (is_adr_ide(c)) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
+  if (!c->robin.X.empty()) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: Robin points are single-device (pinn_set_robin with n = 0 first)");
   HIPCHK(hipSetDevice(c->device));
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
   xg_release(c);
@@ -2458,6 +2555,8 @@ int pinn_comm_xgmi_export(pinn_ctx* c, int n_ranks, int rank, char* handle64) {
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: self-adaptive weights are single-device (pinn_sa_disable first)");
   if (c->pw.on)
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: point weights are single-device (pinn_pw_disable first)");
+  if (!c->robin.X.empty())
+    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: Robin points are single-device (pinn_set_robin with n = 0 first)");
   if (is_adr_ide(c))
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is expected to be 64 bytes");
@@ -2819,6 +2918,8 @@ int pinn_pw_set(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam
                 int64_t n_b) {
   REQUIRE(c, "null");
   if (int rc = pw_supported(c, "pinn_pw_set")) return rc;
+  if (!c->robin.X.empty())
+    return fail(PINN_EUNSUPPORTED, "pinn_pw_set: point weights do not cover Robin points; remove them first (pinn_set_robin with n = 0)");
   if (int rc = pw_check_counts(c, "pinn_pw_set", n_u, n_f, n_b)) return rc;
   for (int64_t j = 0; lam_u && j < n_u; ++j) REQUIRE(std::isfinite(lam_u[j]), "pinn_pw_set: lam_u[%lld] is not finite", (long long)j);
   for (int64_t i = 0; lam_f && i < n_f; ++i) REQUIRE(std::isfinite(lam_f[i]), "pinn_pw_set: lam_f[%lld] is not finite", (long long)i);

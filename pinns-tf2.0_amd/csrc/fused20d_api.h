@@ -102,4 +102,9 @@ struct AdrPwArgs {
 };
 int fused20d_launch_any(const F20dLaunch& a, const AdrPwArgs& k);
 
+// one evaluation of the adr kind with Robin points (k_fused20d<PDE_ADR_ROBIN, H, .>, kernels_generic.h AdrRobinArg): the set
+// is [pairs | data | collocation | robin | pad], a.sd counts the first three classes and a.sd.n_pad covers all four; k.ab is a
+// device array of 2 k.n doubles, 16-byte aligned; g_j stands in tgt at the Robin point's own index.  Launch only with k.n > 0.
+int fused20d_launch_any(const F20dLaunch& a, const AdrRobinArg<double>& k);
+
 }  // namespace pinn

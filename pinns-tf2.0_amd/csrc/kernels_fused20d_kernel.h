@@ -1,0 +1,882 @@
+// kernels_fused20d_kernel.h -- the body of k_fused20d, included by kernels_fused20d.h once per kernel NAME (PINN_F20D_KERNEL):
+// k_fused20d for every kind and variant but one, k_robin20d for PDE_ADR_ROBIN (the adr kind with Robin points).  The text is
+// one, so an instantiation of either name is what a single template gives; the second name exists because the set of
+// k_fused20d<...> instantiations in the library is pinned (tests/test_isa_hazards.py counts them) and the Robin variants
+// are an addition beside it.  (Not a __device__ body called from two kernels: such a wrapper changed the schedule of the
+// existing instantiations.)  No include guard: it is meant to be included more than once.
+template <int PDE, int H, bool ONE_TILE, bool ENS = false, bool SETS = false, bool SAW = false>
+__global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict__ th, const double* __restrict__ xs,
+                                                  const double* __restrict__ ts, const double* __restrict__ tgt,
+                                                  double* __restrict__ part, const int* __restrict__ row_index, int R,
+                                                  int n_tiles, double lbx, double lbt, double sx, double st,
+                                                  f20d_nu_t<SETS, SAW, PDE> nu, SetDesc sd,
+                                                  long long* __restrict__ stamps, W20Desc nd_arg) {
+  static_assert(ENS || !SETS, "per-member point sets are an ensemble launch");
+  static_assert(!pde_is_adr(PDE) || (!ENS && !SETS && (!SAW || PDE == PDE_ADR)),
+                "advection-diffusion-reaction: solo launch; point weights for the fixed-coefficient kind only");
+  static_assert(!SAW || ((PDE == 0 || PDE == PDE_ADR) && !ENS), "point weights: Burgers inference or adr, solo launch");
+  static_assert(PDE != PDE_ADR_ROBIN || (!ENS && !SETS && !SAW),
+                "Robin points: the fixed-coefficient adr kind only, solo launch, no point weights");
+  // weight offsets: compile-time constants in the one-tile variant (immediate operands; Adam step 41.9 -> 40.8 us with
+  // the preloaded pointers); the tile-loop variant keeps them in SGPRs -- with immediates its schedule came out 9 %
+  // slower (N_f = 10^6: 2104 vs 1930 us per step, same box)
+  constexpr W20Desc nd_const = w20_desc(H, pde_n_tail(PDE));
+  const W20Desc nd = ONE_TILE ? nd_const : nd_arg;
+  constexpr int NBLK = fused20d_blocks(H);
+  constexpr int BLK_H = 5 + (H - 1) * 30;            // first block of dense H
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  double* const wl = reinterpret_cast<double*>(lds_raw);
+  const int nwp = (nd.n_theta + 127) / 128 * 128;
+  if constexpr (ENS) {
+    th += (size_t)blockIdx.y * nwp;
+    part += (size_t)blockIdx.y * gridDim.x * R;
+    if constexpr (SETS) {                             // before the first tile's coordinate prefetch below
+      const size_t po = (size_t)blockIdx.y * sd.n_pad;
+      xs += po; ts += po; tgt += po;
+    }
+  }
+  double* const gacc_all = wl + nwp;                  // tile loop: 4 x NBLK x 16 accumulators; one tile: 2 staging buffers
+  double* const lacc_all = gacc_all + (ONE_TILE ? fused20d_stage_doubles(H) : 4 * NBLK * 16);
+
+#define PINN_TO_POINTS(X) mfma444((X), ident, 0.0)
+  STAMP(0);
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // per-lane indices as a macro: derived here for the prologue and the epilogue, and again inside the tile loop (declared
+  // once in front of the loop instead, the same values, every instantiation comes out with another schedule)
+#define PINN_LANE_INDICES(L)                                                                                          \
+  const int lane = (L);                                                                                                \
+  const int q = lane & 15;                 /* point of this wave's 16 */                                              \
+  const int s = lane >> 4;                 /* feature slot: feature = 4 * group + s */                                \
+  const int i4 = lane & 3;                 /* row / column slot of the A patterns and of the gradient blocks */       \
+  const int pf = s * FW + i4;              /* forward pattern:  W[4m + s][4n + i4] */                                 \
+  const int pr = i4 * FW + s;              /* reverse pattern:  W[4m + i4][4n + s] */                                 \
+  const double ident = s == i4 ? 1.0 : 0.0;                    /* 4 x 4 identity as a B operand: the transposing matrix instruction */ \
+  const int ge = s * 4 + i4;               /* this lane's entry (i, j) of a gradient block */                         \
+  double* const lacc = lacc_all + wave * 256 + lane;                        /* [k * 64]: l_res, l_dat, dl0, dl1 */     \
+  const int sput = (s * 4 + i4) * 4 + ((lane >> 2) & 3);   /* one-tile staging slot: entry-major, the four blocks of an entry adjacent */ \
+  const double onesA = i4 == 0 ? 1.0 : 0.0;                     /* rotated "ones" in-group: row 0 = 1 (bias gradients) */ \
+  (void)q; (void)pf; (void)pr; (void)ident; (void)ge; (void)lacc; (void)onesA; (void)s; (void)sput
+  PINN_LANE_INDICES(tid & 63);
+  double* const gacc = gacc_all + wave * (NBLK * 16);
+
+  // first tile's coordinates: issued ahead of the weight staging, so the two round trips overlap
+  int tile = blockIdx.x;
+  double x = 0.0, t = 0.0;
+  if (tile < n_tiles) { x = xs[tile * 64 + wave * 16 + q]; t = ts[tile * 64 + wave * 16 + q]; }
+
+  // ---- flat weight vector -> LDS by asynchronous LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave instruction, no
+  // registers; the engine pads the vector's allocation to whole pieces), gradient accumulators <- 0 meanwhile
+  for (int c = wave; c < nwp / 128; c += 4)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(th + c * 128 + lane * 2),
+                                     (__attribute__((address_space(3))) void*)(wl + c * 128), 16, 0, 0);
+  {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    if (ONE_TILE) {                                    // the staging buffers are written before they are read: loss parts only
+      d2* const z = reinterpret_cast<d2*>(lacc_all);
+      for (int i = tid; i < 2 * 256; i += 256) z[i] = d2{0.0, 0.0};
+    } else {
+      d2* const z = reinterpret_cast<d2*>(gacc_all);
+      for (int i = tid; i < 2 * NBLK * 16 + 2 * 256; i += 256) z[i] = d2{0.0, 0.0};   // + the loss-part slots behind them
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  double c1 = 1.0, c2 = f20d_nu(nu);
+  if (PDE == 1) { c1 = wl[nd.n_net]; c2 = exp(wl[nd.n_net + 1]); }
+  // SAW, tile loop: the weight array and the ascent step size are held in vector registers (an opaque move): the tile-loop
+  // variants use 96 of the 106 scalar registers already, and with these four more they spilled 2-4 of them
+  double* sa_lam_p = nullptr;
+  double sa_alpha = 0.0;
+  if constexpr (SAW) {
+    sa_lam_p = nu.lam;
+    if constexpr (PDE == PDE_ADR) sa_alpha = nu.bc; else sa_alpha = nu.alpha;
+    if constexpr (!ONE_TILE) asm volatile("" : "+v"(sa_lam_p), "+v"(sa_alpha));
+  }
+  const double inv_nf = sd.inv_nf, inv_nu = sd.inv_nu;
+  // PDE_ADR, tile loop: the six coefficients and 1 / n_b would take 14 more scalar registers than the 96 of 106 these
+  // variants use already (6 of them spilled): every wave parks its own copy in the fourth quarter of its loss-part slots
+  // (lacc[192..], used when PDE == 1 only) and reads it back per tile through an opaque address, wave-uniform.  One tile
+  // per workgroup: they stay in scalar registers.
+  double* adr_park = nullptr;
+  if constexpr (PDE == PDE_ADR && !ONE_TILE && !SAW) {
+    adr_park = lacc_all + wave * 256 + 192;
+    if ((tid & 63) == 0) {
+      adr_park[0] = nu.a0; adr_park[1] = nu.a1; adr_park[2] = nu.nu; adr_park[3] = nu.r1; adr_park[4] = nu.r2;
+      adr_park[5] = nu.r3; adr_park[6] = sd.inv_nb;
+    }
+  }
+  // PDE_ADR_ROBIN, tile loop: the same seven and the Robin block's first point, length and 1 / N_w; the (alpha, beta) array's
+  // address in vector registers (an opaque move), as SAW holds its array's
+  const double* rb_ab = nullptr;
+  if constexpr (PDE == PDE_ADR_ROBIN) {
+    rb_ab = nu.ab;
+    if constexpr (!ONE_TILE) {
+      asm volatile("" : "+v"(rb_ab));
+      adr_park = lacc_all + wave * 256 + 192;
+      if ((tid & 63) == 0) {
+        adr_park[0] = nu.k.a0; adr_park[1] = nu.k.a1; adr_park[2] = nu.k.nu; adr_park[3] = nu.k.r1; adr_park[4] = nu.k.r2;
+        adr_park[5] = nu.k.r3; adr_park[6] = sd.inv_nb; adr_park[7] = (double)nu.first; adr_park[8] = (double)nu.n;
+        adr_park[9] = nu.inv_nw;
+      }
+    }
+  }
+  (void)rb_ab;
+  if constexpr (PDE == PDE_ADR_IDE) {
+    adr_park = lacc_all + wave * 256 + 192;
+    if ((tid & 63) == 0) {
+      const double* const tail = wl + nd.n_theta - 6;
+      adr_park[0] = tail[0]; adr_park[1] = tail[1]; adr_park[2] = exp(tail[2]); adr_park[3] = tail[3]; adr_park[4] = tail[4];
+      adr_park[5] = tail[5]; adr_park[6] = sd.inv_nb; adr_park[7] = (double)nu.mask;
+    }
+  }
+  // PDE_ADR with point weights, both variants: the same seven, and behind them the array's header (beta1, beta2, eps and the
+  // ascent rates by point class, fused20d_api.h PW_CONST) -- a lane picks its class's rate by one LDS read
+  if constexpr (PDE == PDE_ADR && SAW) {
+    adr_park = lacc_all + wave * 256 + 192;
+    const AdrCoef<double> k0 = nu.k;
+    if ((tid & 63) == 0) {
+      adr_park[0] = k0.a0; adr_park[1] = k0.a1; adr_park[2] = k0.nu; adr_park[3] = k0.r1; adr_park[4] = k0.r2;
+      adr_park[5] = k0.r3; adr_park[6] = sd.inv_nb;
+    }
+    if ((tid & 63) < PW_CONST) adr_park[8 + (tid & 63)] = sa_lam_p[tid & 63];
+  }
+  (void)adr_park;
+  // per-lane partial sums of the loss parts and of the two lambda gradients (slot-0 lanes only) live in LDS, four
+  // slots per lane behind the gradient accumulators: one read-modify-write per tile instead of eight registers held
+  // across the whole kernel (which cost the identification variant 20 B of scratch per lane)
+
+  // Gradient blocks.  D = this lane's partial sum over the four points of its block b.  Tile loop: the four blocks of an
+  // entry are folded with DPP row rotations and added into the wave's accumulator by ds_add_f64 (grad_store / gacc_flush
+  // below; PINN_GACC_ATOMIC = 0: the old accumulator values are fetched BEFORE the matrix instructions that produce D,
+  // grad_fetch, and old + D is written back).  One tile: parked, and summed by the whole workgroup (phase_issue / phase_finish).
+  // (Tried in round 2: ds_add_f64 with the four lanes of an entry hitting one address, no fold, no read-modify-write --
+  //  221 instructions instead of ~3000, bit-reproducible over 200 runs, and 14 % SLOWER: 49.8 vs 43.7 us per step.)
+
+  STAMP(1);
+
+  for (; tile < n_tiles; tile += gridDim.x) {
+    PINN_LANE_INDICES(tid & 63);
+    auto grad_fetch = [&](const int blk) { return (ONE_TILE || PINN_GACC_ATOMIC) ? 0.0 : gacc[blk * 16 + ge]; };
+    // One tile per workgroup: nothing is accumulated, so the four blocks are not folded in registers (2 x 2 DPP moves + 2
+    // adds per block, 1 300 instructions per tile): every lane parks its own partial in the phase's staging buffer
+    // (entry-major: the four blocks of an entry adjacent), and phase_issue / phase_finish add blocks and waves with the whole
+    // workgroup.  (PINN_ONETILE_SUM = 1, 2, measured and dropped: ROR4 then ROR8, block 1 parks (b1 + b0) + (b3 + b2).)
+    int phase_first = 0;
+    constexpr int PARK_BLOCK = 1;
+    // phase p of the reverse sweep (0: dense H, H - d: layer d's 30 blocks, H: dense 0) -> its first block / its staging area
+    // (the waves are FUSED20D_STAGE_WAVE apart when every lane parks, adjacent doubles when the totals do)
+    constexpr int STAGE_WAVE_STRIDE = PINN_ONETILE_SUM ? 1 : FUSED20D_STAGE_WAVE;
+#if PINN_ONETILE_SUM == 2
+#define PINN_PHASE_STAGE(P) ((P) == 0 ? BLK_H : (P) == H ? 0 : 5 + (H - (P) - 1) * 30) * 64
+#else
+#define PINN_PHASE_STAGE(P) ((P) & 1) * FUSED20D_STAGE_BUF
+#endif
+    double* stage_w = gacc_all + wave * STAGE_WAVE_STRIDE;
+    // Tile loop (PINN_GACC_ATOMIC): after PINN_FOLD_STAGES DPP folds the lanes of blocks 0 and 1 (one fold: two lanes per address, resolved in
+    // lane order) or of block 0 (two folds: one adder per address and tile) add the total into the wave's accumulator with
+    // ONE ds_add_f64.  A group's stores share one hand-set execution-mask region: as `if (block 0) atomic` every store became its own basic block (two scalar
+    // instructions each, and the stash reads the compiler shares between a layer's rotated inputs and the next layer's
+    // adjoints were issued twice: 9 233 -> 9 766 instructions).  LDS operations the compiler does not see only make its own
+    // lgkmcnt waits conservative (the queue is in order).  (The UNFOLDED form -- four lanes per address -- was 14 % slower
+    // in round 2; this one follows the fold.)
+    constexpr unsigned long long FOLD_LANES = PINN_FOLD_STAGES == 2 ? 0x000f000f000f000full : 0x00ff00ff00ff00ffull;
+    double pend_D[6] = {0, 0, 0, 0, 0, 0};
+    int pend_off[6] = {0, 0, 0, 0, 0, 0}, pend_n = 0;
+    auto gacc_flush = [&]() {
+#if PINN_GACC_ATOMIC
+      if constexpr (!ONE_TILE) {
+        const unsigned addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(gacc + ge);
+        unsigned long long saved;
+        if (pend_n == 6)
+          asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[mk]\n\t"
+                       "ds_add_f64 %[a], %[d0] offset:%[o0]\n\tds_add_f64 %[a], %[d1] offset:%[o1]\n\t"
+                       "ds_add_f64 %[a], %[d2] offset:%[o2]\n\tds_add_f64 %[a], %[d3] offset:%[o3]\n\t"
+                       "ds_add_f64 %[a], %[d4] offset:%[o4]\n\tds_add_f64 %[a], %[d5] offset:%[o5]\n\t"
+                       "s_mov_b64 exec, %[sv]"
+                       : [sv] "=&s"(saved)
+                       : [a] "v"(addr), [mk] "s"(FOLD_LANES), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
+                         [d2] "v"(pend_D[2]), [d3] "v"(pend_D[3]), [d4] "v"(pend_D[4]), [d5] "v"(pend_D[5]),
+                         [o0] "i"(pend_off[0]), [o1] "i"(pend_off[1]), [o2] "i"(pend_off[2]), [o3] "i"(pend_off[3]),
+                         [o4] "i"(pend_off[4]), [o5] "i"(pend_off[5])
+                       : "memory");
+        else
+          asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[mk]\n\t"
+                       "ds_add_f64 %[a], %[d0] offset:%[o0]\n\tds_add_f64 %[a], %[d1] offset:%[o1]\n\t"
+                       "ds_add_f64 %[a], %[d2] offset:%[o2]\n\tds_add_f64 %[a], %[d3] offset:%[o3]\n\t"
+                       "ds_add_f64 %[a], %[d4] offset:%[o4]\n\t"
+                       "s_mov_b64 exec, %[sv]"
+                       : [sv] "=&s"(saved)
+                       : [a] "v"(addr), [mk] "s"(FOLD_LANES), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
+                         [d2] "v"(pend_D[2]), [d3] "v"(pend_D[3]), [d4] "v"(pend_D[4]),
+                         [o0] "i"(pend_off[0]), [o1] "i"(pend_off[1]), [o2] "i"(pend_off[2]), [o3] "i"(pend_off[3]),
+                         [o4] "i"(pend_off[4])
+                       : "memory");
+      }
+#endif
+#if PINN_ONETILE_SUM
+      if constexpr (ONE_TILE) {
+        const unsigned addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(stage_w + ge * 4);
+        constexpr unsigned long long park = 0x000f000f000f000full << (4 * PARK_BLOCK);
+        unsigned long long saved;
+        if (pend_n == 6)
+          asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[mk]\n\t"
+                       "ds_write2st64_b64 %[a], %[d0], %[d1] offset0:%[o0] offset1:%[o1]\n\t"
+                       "ds_write2st64_b64 %[a], %[d2], %[d3] offset0:%[o2] offset1:%[o3]\n\t"
+                       "ds_write2st64_b64 %[a], %[d4], %[d5] offset0:%[o4] offset1:%[o5]\n\t"
+                       "s_mov_b64 exec, %[sv]"
+                       : [sv] "=&s"(saved)
+                       : [a] "v"(addr), [mk] "s"(park), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
+                         [d2] "v"(pend_D[2]), [d3] "v"(pend_D[3]), [d4] "v"(pend_D[4]), [d5] "v"(pend_D[5]),
+                         [o0] "i"(pend_off[0]), [o1] "i"(pend_off[1]), [o2] "i"(pend_off[2]), [o3] "i"(pend_off[3]),
+                         [o4] "i"(pend_off[4]), [o5] "i"(pend_off[5])
+                       : "memory");
+        else
+          asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[mk]\n\t"
+                       "ds_write2st64_b64 %[a], %[d0], %[d1] offset0:%[o0] offset1:%[o1]\n\t"
+                       "ds_write2st64_b64 %[a], %[d2], %[d3] offset0:%[o2] offset1:%[o3]\n\t"
+                       "ds_write_b64 %[a], %[d4] offset:%[o4] * 512\n\t"
+                       "s_mov_b64 exec, %[sv]"
+                       : [sv] "=&s"(saved)
+                       : [a] "v"(addr), [mk] "s"(park), [d0] "v"(pend_D[0]), [d1] "v"(pend_D[1]),
+                         [d2] "v"(pend_D[2]), [d3] "v"(pend_D[3]), [d4] "v"(pend_D[4]),
+                         [o0] "i"(pend_off[0]), [o1] "i"(pend_off[1]), [o2] "i"(pend_off[2]), [o3] "i"(pend_off[3]),
+                         [o4] "i"(pend_off[4])
+                       : "memory");
+      }
+#endif
+      pend_n = 0;
+    };
+    auto grad_store = [&](double D, const double old, const int blk) {
+#if PINN_ONETILE_SUM
+      if (ONE_TILE) {
+        D += dpp_mov<DPP_ROW_ROR4>(D);
+        D += dpp_mov<DPP_ROW_ROR8>(D);
+        pend_D[pend_n] = D; pend_off[pend_n] = blk - phase_first; ++pend_n;   // in blocks of 64 doubles (ds_write2st64_b64), parked by gacc_flush below
+        return;
+      }
+#else
+      if (ONE_TILE) { stage_w[(blk - phase_first) * 64 + sput] = D; return; }
+#endif
+      D += dpp_mov<DPP_ROW_ROR8>(D);
+#if PINN_GACC_ATOMIC
+      if (PINN_FOLD_STAGES == 2) D += dpp_mov<DPP_ROW_ROR4>(D);       // (1: the LDS adder does the rest of the fold)
+      pend_D[pend_n] = D; pend_off[pend_n] = blk * 128; ++pend_n;      // added by gacc_flush below, one execution-mask region per group
+      (void)old;
+#else
+      D += dpp_mov<DPP_ROW_ROR4>(D);
+      gacc[blk * 16 + ge] = old + D;
+#endif
+    };
+    // entries of a hidden layer's 30 blocks, relative to the layer's first weight: the same for every layer, derived once.
+    // Thread t owns entries t and t + 256 of a phase.
+    int rel_hidden[2] = {-1, -1};
+    if (ONE_TILE) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int e = tid + 256 * k, bl = e >> 4, i = (e >> 2) & 3, j = e & 3;
+        if (bl < 25) { const int m = bl / 5, n = bl - 5 * m; rel_hidden[k] = (4 * m + i) * FW + 4 * n + j; }
+        else if (bl < 30 && i == 0) rel_hidden[k] = FW * FW + 4 * (bl - 25) + j;       // the bias row follows the kernel
+      }
+    }
+    double* __restrict__ const row1 = part + (size_t)blockIdx.x * R;
+    // sum of one phase p: all four waves have parked its blocks in the phase's staging area; entry e of the phase = 4 waves x 4
+    // blocks in fixed order -> its place in the workgroup's gradient row.  to_index(e) = flat parameter index or -1.
+    //   phase_issue   barrier (all four waves have parked the phase) + the 16 reads of this thread's two entries
+    //   phase_finish  4 waves x 4 blocks added in fixed order, stored at the entry's place in the workgroup's gradient row
+    // Threads without a second entry read a clamped address and store nothing (no divergent branch around the reads).
+    // Folded settings: an entry is the four waves' totals, ps_lo[k][0] = (w0, w1), ps_hi[k][0] = (w2, w3), 4 reads; their
+    // parking stores are inline asm, which hipcc's wait-count pass does not count, so the wait in front of the barrier is
+    // written out; with PINN_ONETILE_SUM = 2 issue and finish do nothing and all phases are summed behind the sweep.
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    constexpr int PS_W = PINN_ONETILE_SUM ? 1 : 4;
+    d2 ps_lo[2][PS_W], ps_hi[2][PS_W];
+    auto phase_reads = [&](const int n_entries, const int p) {
+      const double* __restrict__ const sb = gacc_all + PINN_PHASE_STAGE(p);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        if (256 * k >= n_entries) continue;
+        const int e = tid + 256 * k < n_entries ? tid + 256 * k : n_entries - 1;
+#if PINN_ONETILE_SUM
+        ps_lo[k][0] = *reinterpret_cast<const d2*>(sb + 4 * e);
+        ps_hi[k][0] = *reinterpret_cast<const d2*>(sb + 4 * e + 2);
+#else
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          ps_lo[k][w] = *reinterpret_cast<const d2*>(sb + w * FUSED20D_STAGE_WAVE + 4 * e);
+          ps_hi[k][w] = *reinterpret_cast<const d2*>(sb + w * FUSED20D_STAGE_WAVE + 4 * e + 2);
+        }
+#endif
+      }
+    };
+    auto parked_barrier = [&]() {
+      if (PINN_ONETILE_SUM) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __syncthreads();
+    };
+    auto phase_issue = [&](const int n_entries, const int p) {
+      if (PINN_ONETILE_SUM == 2) return;                 // summed behind the sweep
+      parked_barrier();
+      phase_reads(n_entries, p);
+    };
+    auto phase_adds = [&](const int n_entries, auto to_index) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        if (256 * k >= n_entries) continue;
+        const int e = tid + 256 * k;
+        const int idx = e < n_entries ? to_index(e, k) : -1;
+        double v = 0.0;
+#if PINN_ONETILE_SUM
+        v = ((ps_lo[k][0].x + ps_lo[k][0].y) + ps_hi[k][0].x) + ps_hi[k][0].y;
+#else
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const double t = (ps_lo[k][w].x + ps_lo[k][w].y) + (ps_hi[k][w].x + ps_hi[k][w].y);
+          v = w == 0 ? t : v + t;
+        }
+#endif
+        // (as a nontemporal store -- the row streaming past the L2 -- the Adam step was 0.6 us LONGER,
+        //  profiles/r06_ab_loopvariants.txt; written through, it is shorter: PINN_ROW_STORE_WT)
+#if PINN_ROW_STORE_WT
+        if (idx >= 0) __hip_atomic_store(row1 + idx, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+        if (idx >= 0) row1[idx] = v;
+#endif
+      }
+    };
+    auto phase_finish = [&](const int n_entries, auto to_index) {
+      if (PINN_ONETILE_SUM == 2) return;
+      phase_adds(n_entries, to_index);
+    };
+    auto idx_dense_h = [&](const int e, int) {
+      const int m = e >> 4, i = (e >> 2) & 3, j = e & 3;
+      return j != 0 ? -1 : m < 5 ? nd.off_w[H] + 4 * m + i : (i == 0 ? nd.off_b[H] : -1);
+    };
+    const int pt = tile * 64 + wave * 16 + q;
+    // SAW: this point's weight (and, in an Adam step, its moments), requested here so that the forward sweep hides the
+    // round trip
+    double sa_lam = 1.0, sa_m = 0.0, sa_v = 0.0;
+    double* sa_row = nullptr;
+    if constexpr (SAW && PDE == PDE_ADR) {   // indexed by the point; both points of a periodic pair read the lo point's entry
+      const int e = pt < sd.n_all ? pt : 0;
+      sa_row = sa_lam_p + PW_CONST + 3 * (e < 2 * sd.n_b ? e & ~1 : e);
+      sa_lam = sa_row[0]; sa_m = sa_row[1]; sa_v = sa_row[2];
+    } else
+    if constexpr (SAW) {      // (padding lanes read point 0's entry, unused: no branch, no saved execution mask)
+      sa_row = sa_lam_p + SA_CONST + 3 * (pt < sd.n_all ? pt : 0);
+      sa_lam = sa_row[0]; sa_m = sa_row[1]; sa_v = sa_row[2];
+    }
+    const double hx = __builtin_fma(sx, x - lbx, -1.0), ht = __builtin_fma(st, t - lbt, -1.0);
+    {
+      const int nt = tile + gridDim.x;
+      if (!ONE_TILE && nt < n_tiles) { x = xs[nt * 64 + wave * 16 + q]; t = ts[nt * 64 + wave * 16 + q]; }
+    }
+
+    // ------------------------------------------------------------------ forward
+    double in[4][5];                         // [channel h,p,q,r][group]: outputs of the layer below, own (slot, point)
+    double a0[5];                            // layer 0: tanh outputs (its z_x, z_t are weight constants, z_xx = 0)
+    agd stash[H][5][4];                      // AGPR-resident, layers 1..H-2
+    double top[5][4];                        // last hidden layer's stash entry, live across the seeds
+#pragma unroll
+    for (int n = 0; n < 5; ++n) {            // dense 0: p0 = (sx, 0), q0 = (0, st), r0 = 0
+      const int f = 4 * n + s;
+      const double w0x = wl[nd.off_w[0] + f], w0t = wl[nd.off_w[0] + FW + f], b0 = wl[nd.off_b[0] + f];
+      const double a = tanh_d(__builtin_fma(hx, w0x, __builtin_fma(ht, w0t, b0)));
+      a0[n] = a;
+      channels_d(a, sx * w0x, st * w0t, 0.0, in[0][n], in[1][n], in[2][n], in[3][n]);
+    }
+#pragma unroll
+    for (int d = 1; d < H; ++d) {
+      const double* __restrict__ wd = wl + nd.off_w[d] + pf;
+      double acc[4][5];
+#pragma unroll
+      for (int n = 0; n < 5; ++n) {
+        acc[0][n] = wl[nd.off_b[d] + 4 * n + s];
+        acc[1][n] = acc[2][n] = acc[3][n] = 0.0;
+      }
+      // The 25 weight patterns of the layer are requested from LDS TWO steps ahead of the four matrix instructions that
+      // consume them (sched_barrier pins the order).  Left to itself hipcc sinks every ds_read next to its consumer --
+      // `ds_read2_b64; s_waitcnt lgkmcnt(0); v_mfma` 259 times per tile (round-4 ISA count) -- and a lone wave then
+      // sits out the LDS latency in front of each group of matrix instructions.
+      {
+        // (requested in PAIRS -- steps t + 2 and t + 3 at every even t -- so that two patterns travel in one ds_read2_b64:
+        //  13 LDS instructions per GEMV instead of 25)
+        auto fpat = [&](const int t) { return wd[80 * (t % 5) + 4 * (t / 5)]; };
+        double Aq[4] = {fpat(0), fpat(1), 0.0, 0.0};
+#pragma unroll
+        for (int t = 0; t < 25; ++t) {
+          const int n = t / 5, m = t - 5 * n;
+          const double A = Aq[t & 3];
+          if ((t & 1) == 0) {
+            if (t + 2 < 25) Aq[(t + 2) & 3] = fpat(t + 2);
+            if (t + 3 < 25) Aq[(t + 3) & 3] = fpat(t + 3);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[c][n] = mfma444(A, in[c][m], acc[c][n]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      STAMP2(d == 4, 29);
+#pragma unroll
+      for (int n = 0; n < 5; ++n) {
+        const double a = tanh_d(acc[0][n]);
+        channels_d(a, acc[1][n], acc[2][n], acc[3][n], in[0][n], in[1][n], in[2][n], in[3][n]);
+        if (d < H - 1) {       // a is a VALU result; z_x, z_t, z_xx are raw matrix results (see agd_put_after)
+          stash[d][n][0] = agd_put(a); stash[d][n][1] = agd_put_after(acc[1][n], in[1][n]);
+          stash[d][n][2] = agd_put_after(acc[2][n], in[2][n]); stash[d][n][3] = agd_put_after(acc[3][n], in[3][n]);
+        } else {
+          top[n][0] = a; top[n][1] = acc[1][n]; top[n][2] = acc[2][n]; top[n][3] = acc[3][n];
+        }
+      }
+      STAMP(1 + d);
+    }
+    // linear output layer: the pattern does not depend on the row, so all four slot lanes of a point get
+    // o = (u, u_x, u_t, u_xx)
+    double o[4] = {wl[nd.off_b[H]], 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+      const double A = wl[nd.off_w[H] + 4 * m + s];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = mfma444(A, in[c][m], o[c]);
+    }
+
+    // ------------------------------------------------------------------ seeds + loss parts
+    double sb[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (PDE == PDE_ADR && SAW) {
+      // PDE_ADR's seeds with inv_n * lambda^2 where inv_n stands (a product of its own, never contracted into a neighbour:
+      // lambda = 1 gives the plain kernel's bits); a pair's two lanes hold the pair's one lambda
+      const double pu = dpp_mov<DPP_QUAD_XOR1>(o[0]), pp = dpp_mov<DPP_QUAD_XOR1>(o[1]);
+      const double* kp = adr_park;
+      asm volatile("" : "+v"(kp));
+      const AdrCoef<double> kc{kp[0], kp[1], kp[2], kp[3], kp[4], kp[5]};
+      const int cls = point_class_adr(sd, pt);
+      double wf, wu, wb, r2 = 0.0;
+      {
+#pragma clang fp contract(off)
+        const double l2 = sa_lam * sa_lam;
+        wf = inv_nf * l2; wu = inv_nu * l2; wb = kp[6] * l2;
+      }
+      if (cls == CLS_COL) {
+        const double u = o[0], adv = kc.a0 + kc.a1 * u;
+        const double f = o[2] + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
+        const double fbar = 2.0 * f * wf;
+        if (s == 0) lacc[0] += f * f * wf;
+        sb[0] = fbar * (kc.a1 * o[1] + kc.r1 + u * (2.0 * kc.r2 + 3.0 * kc.r3 * u));
+        sb[1] = fbar * adv; sb[2] = fbar; sb[3] = -kc.nu * fbar;
+        r2 = f * f * inv_nf;
+      } else if (cls == CLS_DATA) {
+        const double dd = o[0] - tgt[pt];
+        if (s == 0) lacc[64] += dd * dd * wu;
+        sb[0] = 2.0 * dd * wu;
+        r2 = dd * dd * inv_nu;
+      } else if (cls != CLS_PAD) {
+        const double du = o[0] - pu, dp = o[1] - pp;
+        if (s == 0 && cls == CLS_BLO) lacc[128] += (du * du + dp * dp) * wb;
+        sb[0] = 2.0 * du * wb; sb[1] = 2.0 * dp * wb;
+        r2 = (du * du + dp * dp) * kp[6];
+      }
+      // one Adam ascent step on lambda from this evaluation (TF form, as k_reduce_adam steps theta): the slot-0 lane of a
+      // data or collocation point and of a pair's lo point.  The header holds the rate at 3 + class, 0.0 for hi points and
+      // padding, so a class with rate 0 is never written
+      if (sa_alpha != 0.0) {
+        const double step = sa_alpha * kp[8 + 3 + cls];
+        if (step != 0.0 && s == 0) {
+          const double g = 2.0 * sa_lam * r2;
+          const double mi = sa_m + (1.0 - kp[8]) * (g - sa_m);
+          const double vi = sa_v + (1.0 - kp[9]) * (g * g - sa_v);
+          sa_row[0] = sa_lam + step * mi / (sqrt(vi) + kp[10]);
+          sa_row[1] = mi;
+          sa_row[2] = vi;
+        }
+      }
+    } else if constexpr (pde_adr_fixed(PDE)) {
+      // (the weighted block above is this block's twin, seed for seed: a change to the seeds here belongs there too)
+      // partner of a boundary pair: pt ^ 1 is lane ^ 1 (pt = tile * 64 + wave * 16 + q), same slot.  The moves are
+      // unconditional (no divergent branch around a cross-lane move); their results count in the boundary class only.
+      const double pu = dpp_mov<DPP_QUAD_XOR1>(o[0]), pp = dpp_mov<DPP_QUAD_XOR1>(o[1]);
+      AdrCoef<double> kc;
+      double inv_nb;
+      int rb_j = -1, rb_n = 0;               // PDE_ADR_ROBIN: this point's place in the Robin block, the block's length
+      double inv_nw = 0.0;
+      if constexpr (ONE_TILE) {
+        if constexpr (PDE == PDE_ADR_ROBIN) { kc = nu.k; rb_j = pt - nu.first; rb_n = nu.n; inv_nw = nu.inv_nw; }
+        else kc = nu;
+        inv_nb = sd.inv_nb;
+      } else {
+        const double* kp = adr_park;
+        asm volatile("" : "+v"(kp));
+        kc = AdrCoef<double>{kp[0], kp[1], kp[2], kp[3], kp[4], kp[5]};
+        inv_nb = kp[6];
+        if constexpr (PDE == PDE_ADR_ROBIN) { rb_j = pt - (int)kp[7]; rb_n = (int)kp[8]; inv_nw = kp[9]; }
+      }
+      (void)rb_j; (void)rb_n; (void)inv_nw;
+      const int cls = point_class_adr(sd, pt);
+      if (cls == CLS_COL) {
+        const double u = o[0], adv = kc.a0 + kc.a1 * u;
+        const double f = o[2] + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
+        const double fbar = 2.0 * f * inv_nf;
+        if (s == 0) lacc[0] += f * f * inv_nf;
+        sb[0] = fbar * (kc.a1 * o[1] + kc.r1 + u * (2.0 * kc.r2 + 3.0 * kc.r3 * u));
+        sb[1] = fbar * adv; sb[2] = fbar; sb[3] = -kc.nu * fbar;
+      } else if (cls == CLS_DATA) {
+        const double dd = o[0] - tgt[pt];
+        if (s == 0) lacc[64] += dd * dd * inv_nu;
+        sb[0] = 2.0 * dd * inv_nu;
+      } else if (cls != CLS_PAD) {       // own minus partner: +2 (lo - hi) / n_b at lo, -2 (lo - hi) / n_b at hi
+        const double du = o[0] - pu, dp = o[1] - pp;
+        if (s == 0 && cls == CLS_BLO) lacc[128] += (du * du + dp * dp) * inv_nb;
+        sb[0] = 2.0 * du * inv_nb; sb[1] = 2.0 * dp * inv_nb;
+      } else if constexpr (PDE == PDE_ADR_ROBIN) {
+        // the Robin block stands behind the collocation block (CLS_PAD by sd's counts): r = alpha u + beta u_x - g
+        if ((unsigned)rb_j < (unsigned)rb_n) {
+          typedef double d2 __attribute__((ext_vector_type(2)));
+          const d2 ab = *reinterpret_cast<const d2*>(rb_ab + 2 * rb_j);
+          const double r = ab.x * o[0] + ab.y * o[1] - tgt[pt];
+          if (s == 0) lacc[128] += r * r * inv_nw;
+          sb[0] = 2.0 * r * ab.x * inv_nw; sb[1] = 2.0 * r * ab.y * inv_nw;
+        }
+      }
+    } else if constexpr (PDE == PDE_ADR_IDE) {
+      // PDE_ADR's seeds with the parked coefficients; slot lanes 1-3 of a collocation point add its six coefficient
+      // derivatives where only the slot-0 lane adds a loss part (selects, no branch on the slot)
+      const double pu = dpp_mov<DPP_QUAD_XOR1>(o[0]), pp = dpp_mov<DPP_QUAD_XOR1>(o[1]);
+      const double* kp = adr_park;
+      asm volatile("" : "+v"(kp));
+      const AdrCoef<double> kc{kp[0], kp[1], kp[2], kp[3], kp[4], kp[5]};
+      const double inv_nb = kp[6];
+      const int cls = point_class_adr(sd, pt);
+      if (cls == CLS_COL) {
+        const double u = o[0], adv = kc.a0 + kc.a1 * u;
+        const double f = o[2] + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
+        const double fbar = 2.0 * f * inv_nf;
+        const double fu = fbar * u;
+        // (picked by bit masks of the slot, not by compares: three more condition masks in scalar registers made the
+        //  tile-loop variants spill)
+        const int m0 = ((s ^ 0) - 1) >> 31, m1 = ((s ^ 1) - 1) >> 31, m2 = ((s ^ 2) - 1) >> 31;      // -1 where s == k
+        lacc[0] += bit_pick(m0, f * f * inv_nf, bit_pick(m1, fbar * o[1], bit_pick(m2, fu * o[1], -(fbar * kc.nu) * o[3])));
+        lacc[64] += bit_pick(m0, 0.0, bit_pick(m1, fu, bit_pick(m2, fu * u, fu * u * u)));
+        sb[0] = fbar * (kc.a1 * o[1] + kc.r1 + u * (2.0 * kc.r2 + 3.0 * kc.r3 * u));
+        sb[1] = fbar * adv; sb[2] = fbar; sb[3] = -kc.nu * fbar;
+      } else if (cls == CLS_DATA) {
+        const double dd = o[0] - tgt[pt];
+        if (s == 0) lacc[64] += dd * dd * inv_nu;
+        sb[0] = 2.0 * dd * inv_nu;
+      } else if (cls != CLS_PAD) {
+        const double du = o[0] - pu, dp = o[1] - pp;
+        if (s == 0 && cls == CLS_BLO) lacc[128] += (du * du + dp * dp) * inv_nb;
+        sb[0] = 2.0 * du * inv_nb; sb[1] = 2.0 * dp * inv_nb;
+      }
+    } else {
+      // (SAW: pde 0 has no boundary pairs; classing without n_b saves the tile-loop variants a scalar register)
+      const int cls = SAW ? (pt < sd.n_u ? CLS_DATA : pt < sd.n_all ? CLS_COL : CLS_PAD) : point_class(sd, pt);
+      const bool res = (PDE == 0) ? (cls == CLS_COL) : (cls == CLS_DATA);
+      // SAW: inv_n * lambda^2 as a product of its own (never contracted into a neighbour), so lambda = 1 gives inv_n itself
+      // and every bit downstream is the plain kernel's
+      double wf = inv_nf, wu = inv_nu, r2 = 0.0;
+      if constexpr (SAW) {
+#pragma clang fp contract(off)
+        const double l2 = sa_lam * sa_lam;
+        wf = inv_nf * l2; wu = inv_nu * l2;
+      }
+      if (res) {
+        const double wgt = (PDE == 0) ? wf : inv_nu;
+        const double f = o[2] + c1 * o[0] * o[1] - c2 * o[3];
+        const double fbar = 2.0 * f * wgt;
+        if (s == 0) {
+          lacc[0] += f * f * wgt;
+          if (PDE == 1) { lacc[128] += fbar * o[0] * o[1]; lacc[192] -= fbar * c2 * o[3]; }
+        }
+        sb[0] = fbar * c1 * o[1]; sb[1] = fbar * c1 * o[0]; sb[2] = fbar; sb[3] = -c2 * fbar;
+        if constexpr (SAW) r2 = f * f;
+      }
+      if (cls == CLS_DATA) {
+        const double dd = o[0] - tgt[pt];
+        if (s == 0) lacc[64] += dd * dd * wu;
+        sb[0] += 2.0 * dd * wu;
+        if constexpr (SAW) r2 = dd * dd;
+      }
+      if constexpr (SAW) {
+        // one Adam ascent step on lambda from this evaluation (TF form, as k_reduce_adam steps theta), slot-0 lane only
+        if (sa_alpha != 0.0 && s == 0 && pt < sd.n_all) {
+          const double* const k = sa_lam_p;                        // beta1, beta2, eps
+          const double g = 2.0 * sa_lam * r2 * (cls == CLS_DATA ? inv_nu : inv_nf);
+          const double mi = sa_m + (1.0 - k[0]) * (g - sa_m);
+          const double vi = sa_v + (1.0 - k[1]) * (g * g - sa_v);
+          sa_row[0] = sa_lam + sa_alpha * mi / (sqrt(vi) + k[2]);
+          sa_row[1] = mi;
+          sa_row[2] = vi;
+        }
+      }
+    }
+
+    // ------------------------------------------------------------------ reverse sweep
+    double ob[4][5];                         // adjoint of the outputs of the layer below, own (slot, point)
+    {  // dense H (linear, one output): z_bar = sb.  dW_H[k] = sum IN_c[k] sb_c, db_H = sum sb_h
+      double sbT[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) sbT[c] = PINN_TO_POINTS(s == 0 ? sb[c] : 0.0);     // column 0 only
+      {
+        double D[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, old[6];
+#pragma unroll
+        for (int m = 0; m < 6; ++m) old[m] = grad_fetch(BLK_H + m);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+          for (int m = 0; m < 5; ++m) D[m] = mfma444(PINN_TO_POINTS(in[c][m]), sbT[c], D[m]);
+        }
+        D[5] = mfma444(onesA, sbT[0], 0.0);
+        phase_first = BLK_H;                                   // phase 0 of the reverse sweep: buffer 0
+        stage_w = gacc_all + PINN_PHASE_STAGE(0) + wave * STAGE_WAVE_STRIDE;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) grad_store(D[m], old[m], BLK_H + m);
+        gacc_flush();
+      }
+#pragma unroll
+      for (int n = 0; n < 5; ++n) {
+        const double w = wl[nd.off_w[H] + 4 * n + s];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ob[c][n] = sb[c] * w;
+      }
+    }
+    STAMP(H + 1);
+#pragma unroll
+    for (int d = H - 1; d >= 1; --d) {
+      // pre-activation adjoints of layer d; their point-major (moved) copies for the weight gradient are made inside the GEMV.
+      // One tile: the barrier and the 16 reads of the previous phase's sum stand in front of the adjoint arithmetic (pure
+      // VALU), which hides their LDS round trip.
+      double zb[4][5], zbT[4][5];
+      if constexpr (ONE_TILE) phase_issue(d == H - 1 ? 6 * 16 : 30 * 16, H - d - 1);
+#pragma unroll
+      for (int n = 0; n < 5; ++n) {
+        double a, zp, zq, zr;
+        if (d == H - 1) { a = top[n][0]; zp = top[n][1]; zq = top[n][2]; zr = top[n][3]; }
+        else { a = agd_get(stash[d][n][0]); zp = agd_get(stash[d][n][1]); zq = agd_get(stash[d][n][2]); zr = agd_get(stash[d][n][3]); }
+        preact_adjoint_d(a, zp, zq, zr, ob[0][n], ob[1][n], ob[2][n], ob[3][n], zb[0][n], zb[1][n], zb[2][n], zb[3][n]);
+      }
+      STAMP2(d == 4, 20);
+      // One tile: the phase before this one is summed HERE, not where its last block was parked -- the stash entries of
+      // layer d, read a first time for that phase's rotated inputs, are still in registers for the adjoints above (a
+      // barrier in between would end their basic block and cost a second v_accvgpr_read each).
+      // The LDS pipe is the second bottleneck of this kernel (a ds_read_b128 costs a wave ~53 cycles of it with four waves on
+      // the CU: profiles/r01_ubench_lds_rates.txt, r06_stamps2_new.txt), and it runs beside the matrix pipe: the adds and
+      // stores of the sum stand in front of the reverse GEMV, and this layer's 40 operand moves -- needed only by the
+      // weight-gradient blocks behind the GEMV -- are issued one per pinned GEMV step.
+      // (finish_prev stays a lambda: written out in place, the one-tile instantiations come out 14-19 instructions longer)
+      auto finish_prev = [&]() {
+        if (d == H - 1) phase_finish(6 * 16, idx_dense_h);
+        else phase_finish(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[d + 1] + rel_hidden[k]; });
+      };
+      if constexpr (ONE_TILE) finish_prev();
+      STAMP2(d == 4, 21);
+      // the first in-group's inputs of the weight-gradient blocks: formed here, moved in the last steps of the GEMV
+      double cur[4] = {0.0, 0.0, 0.0, 0.0}, first_nat[4] = {0.0, 0.0, 0.0, 0.0};
+      {
+        double a_, zp_, zq_, zr_;
+        if (d - 1 == 0) {
+          a_ = a0[0]; zp_ = sx * wl[nd.off_w[0] + s]; zq_ = st * wl[nd.off_w[0] + FW + s]; zr_ = 0.0;
+        } else {
+          a_ = agd_get(stash[d - 1][0][0]); zp_ = agd_get(stash[d - 1][0][1]);
+          zq_ = agd_get(stash[d - 1][0][2]); zr_ = agd_get(stash[d - 1][0][3]);
+        }
+        channels_d(a_, zp_, zq_, zr_, first_nat[0], first_nat[1], first_nat[2], first_nat[3]);
+      }
+      // adjoint of the layer-(d-1) outputs: in_bar[4m + i] = sum_j z_bar_j W_d[4m + i][j]
+      const double* __restrict__ wd = wl + nd.off_w[d] + pr;
+#pragma unroll
+      for (int m = 0; m < 5; ++m) {
+        ob[0][m] = ob[1][m] = ob[2][m] = ob[3][m] = 0.0;
+      }
+      {
+        auto rpat = [&](const int t) { return wd[80 * (t / 5) + 4 * (t % 5)]; };
+        double Aq[4] = {rpat(0), rpat(1), 0.0, 0.0};
+#pragma unroll
+        for (int t = 0; t < 25; ++t) {
+          const int m = t / 5, n = t - 5 * m;
+          const double A = Aq[t & 3];
+          if ((t & 1) == 0) {
+            if (t + 2 < 25) Aq[(t + 2) & 3] = rpat(t + 2);
+            if (t + 3 < 25) Aq[(t + 3) & 3] = rpat(t + 3);
+          }
+          if (t < 20) zbT[t / 5][t % 5] = PINN_TO_POINTS(zb[t / 5][t % 5]);   // one operand move per step
+          if (t >= 20 && t < 24) cur[t - 20] = PINN_TO_POINTS(first_nat[t - 20]);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) ob[c][m] = mfma444(A, zb[c][n], ob[c][m]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      STAMP2(d == 4, 22);
+      // dW_d[4m + i][4n + j]: the A operands are the layer-(d-1) output channels, rotated -- produced one in-group
+      // ahead of the matrix instructions that consume them (20 values live instead of 40: the kernel sits at the
+      // 256-VGPR limit, and with all of them live hipcc sank the accumulator fetches next to their uses)
+      const int base = 5 + (d - 1) * 30;
+      phase_first = base;                                      // phase H - d: buffers alternate
+      stage_w = gacc_all + PINN_PHASE_STAGE(H - d) + wave * STAGE_WAVE_STRIDE;
+#define PINN_ROTATED_INPUTS(M, O4)                                                                          \
+  do {                                                                                                      \
+    double a_, zp_, zq_, zr_;                                                                               \
+    if (d - 1 == 0) {                                                                                       \
+      const int f_ = 4 * (M) + s;                                                                           \
+      a_ = a0[M]; zp_ = sx * wl[nd.off_w[0] + f_]; zq_ = st * wl[nd.off_w[0] + FW + f_]; zr_ = 0.0;         \
+    } else {                                                                                                \
+      a_ = agd_get(stash[d - 1][M][0]); zp_ = agd_get(stash[d - 1][M][1]);                                  \
+      zq_ = agd_get(stash[d - 1][M][2]); zr_ = agd_get(stash[d - 1][M][3]);                                 \
+    }                                                                                                       \
+    double h_, p_, q_, r_;                                                                                  \
+    channels_d(a_, zp_, zq_, zr_, h_, p_, q_, r_);                                                          \
+    O4[0] = PINN_TO_POINTS(h_); O4[1] = PINN_TO_POINTS(p_);                                             \
+    O4[2] = PINN_TO_POINTS(q_); O4[3] = PINN_TO_POINTS(r_);                                             \
+  } while (0)
+#pragma unroll
+      for (int m = 0; m < 5; ++m) {          // five independent accumulator chains per in-group
+        double D[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, old[5], nxt[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int n = 0; n < 5; ++n) old[n] = grad_fetch(base + m * 5 + n);
+        if (m + 1 < 5) PINN_ROTATED_INPUTS((m + 1 < 5 ? m + 1 : 4), nxt);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+          for (int n = 0; n < 5; ++n) D[n] = mfma444(cur[c], zbT[c][n], D[n]);
+        }
+#pragma unroll
+        for (int n = 0; n < 5; ++n) grad_store(D[n], old[n], base + m * 5 + n);
+        gacc_flush();
+#pragma unroll
+        for (int c = 0; c < 4; ++c) cur[c] = nxt[c];
+        STAMP2(d == 4, 23 + m);
+      }
+#undef PINN_ROTATED_INPUTS
+      {
+        double D[5], old[5];
+#pragma unroll
+        for (int n = 0; n < 5; ++n) old[n] = grad_fetch(base + 25 + n);
+#pragma unroll
+        for (int n = 0; n < 5; ++n) D[n] = mfma444(onesA, zbT[0][n], 0.0);
+#pragma unroll
+        for (int n = 0; n < 5; ++n) grad_store(D[n], old[n], base + 25 + n);
+        gacc_flush();
+      }
+      STAMP(2 * H + 1 - d);
+    }
+    {  // dense 0: inputs (hx, ht, 1) in channel h, (sx, 0, 0) in channel p, (0, st, 0) in channel q
+      const double hxT = PINN_TO_POINTS(hx), htT = PINN_TO_POINTS(ht);
+      const double Ah = i4 == 0 ? hxT : i4 == 1 ? htT : i4 == 2 ? 1.0 : 0.0;
+      const double Ap = i4 == 0 ? sx : 0.0, Aq = i4 == 1 ? st : 0.0;
+      double bT[3][5];
+#pragma unroll
+      for (int n = 0; n < 5; ++n) {
+        const int f = 4 * n + s;
+        double bh, bp, bq, br;
+        preact_adjoint_d(a0[n], sx * wl[nd.off_w[0] + f], st * wl[nd.off_w[0] + FW + f], 0.0, ob[0][n], ob[1][n],
+                         ob[2][n], ob[3][n], bh, bp, bq, br);
+        bT[0][n] = PINN_TO_POINTS(bh); bT[1][n] = PINN_TO_POINTS(bp); bT[2][n] = PINN_TO_POINTS(bq);
+      }
+      if constexpr (ONE_TILE) {                                // layer 1's phase
+        phase_issue(30 * 16, H - 1);
+        phase_finish(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[1] + rel_hidden[k]; });
+      }
+      double D[5], old[5];
+#pragma unroll
+      for (int n = 0; n < 5; ++n) old[n] = grad_fetch(n);
+#pragma unroll
+      for (int n = 0; n < 5; ++n) D[n] = mfma444(Ah, bT[0][n], 0.0);
+#pragma unroll
+      for (int n = 0; n < 5; ++n) D[n] = mfma444(Ap, bT[1][n], D[n]);
+#pragma unroll
+      for (int n = 0; n < 5; ++n) D[n] = mfma444(Aq, bT[2][n], D[n]);
+      phase_first = 0;                                         // phase H
+      stage_w = gacc_all + PINN_PHASE_STAGE(H) + wave * STAGE_WAVE_STRIDE;
+#pragma unroll
+      for (int n = 0; n < 5; ++n) grad_store(D[n], old[n], n);
+      gacc_flush();
+      if constexpr (ONE_TILE) {
+        auto idx_dense_0 = [&](const int e, int) {
+          const int f = 4 * (e >> 4) + (e & 3), i = (e >> 2) & 3;
+          return i == 0 ? nd.off_w[0] + f : i == 1 ? nd.off_w[0] + FW + f : i == 2 ? nd.off_b[0] + f : -1;
+        };
+        phase_issue(5 * 16, H);
+        phase_finish(5 * 16, idx_dense_0);
+        if constexpr (PINN_ONETILE_SUM == 2) {           // every phase is parked in its own region: one barrier, H + 1 sums
+          parked_barrier();
+          phase_reads(6 * 16, 0);
+          phase_adds(6 * 16, idx_dense_h);
+#pragma unroll
+          for (int d = H - 1; d >= 1; --d) {
+            phase_reads(30 * 16, H - d);
+            phase_adds(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[d] + rel_hidden[k]; });
+          }
+          phase_reads(5 * 16, H);
+          phase_adds(5 * 16, idx_dense_0);
+        }
+      }
+    }
+    if (ONE_TILE) break;
+  }
+  STAMP(2 * H + 1);
+#undef PINN_LANE_INDICES
+#undef PINN_TO_POINTS
+#undef PINN_PHASE_STAGE
+
+  // -------------------------------------------------------------------- one gradient row per workgroup
+  {
+    // row_index[e]: flat parameter index of entry e of the block list (-1: padding), built once on the host;
+    // fetched first so that its (cold) latency hides under the wave sums and the two barriers  (it does: prefetching
+    // the table into LDS with the weights' DMA changed nothing -- Adam step 40.79 vs 40.81 us, same box)
+    constexpr int NE = NBLK * 16, NIT = ONE_TILE ? 1 : (NE + 255) / 256;   // (one tile: the row was written phase by phase)
+    int idx[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int e = tid + 256 * it;
+      idx[it] = (!ONE_TILE && e < NE) ? row_index[e] : -1;
+    }
+    // PDE_ADR_IDE: quarters 0 and 1 hold four sums each, one per DPP row (= slot): [loss_f, a0, a1, log nu], [data, r1, r2, r3]
+    const double t0 = PDE == PDE_ADR_IDE ? row16_sum(lacc[0]) : wave_sum(lacc[0]);
+    const double t1 = PDE == PDE_ADR_IDE ? row16_sum(lacc[64]) : wave_sum(lacc[64]);
+    const double t2 = (PDE == 1 || pde_is_adr(PDE)) ? wave_sum(lacc[128]) : 0.0, t3 = PDE == 1 ? wave_sum(lacc[192]) : 0.0;
+    double ide_mask = 0.0;
+    if constexpr (PDE == PDE_ADR_IDE) ide_mask = lacc_all[wave * 256 + 192 + 7];      // this wave's own parked copy
+    __syncthreads();                                   // every wave's accumulators are final
+    double* const scal = wl;                           // the weight copy is dead: 4 x 4 loss / lambda partials (PDE_ADR_IDE: 4 x 9)
+    if constexpr (PDE == PDE_ADR_IDE) {                // per wave: loss_f, data, pairs, then the six coefficient sums
+      const int sl = lane >> 4;
+      if ((lane & 15) == 0) {
+        if (sl == 0) { scal[wave * 9 + 0] = t0; scal[wave * 9 + 1] = t1; scal[wave * 9 + 2] = t2; }
+        else { scal[wave * 9 + 2 + sl] = t0; scal[wave * 9 + 5 + sl] = t1; }
+      }
+    } else
+    if (lane == 0) { scal[wave * 4 + 0] = t0; scal[wave * 4 + 1] = t1; scal[wave * 4 + 2] = t2; scal[wave * 4 + 3] = t3; }
+    __syncthreads();
+    double* __restrict__ row = part + (size_t)blockIdx.x * R;
+    if (!ONE_TILE) {
+      double v[NIT];
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int e = tid + 256 * it;
+        const int ee = e < NE ? e : 0;
+        v[it] = ((gacc_all[ee] + gacc_all[NE + ee]) + gacc_all[2 * NE + ee]) + gacc_all[3 * NE + ee];
+      }
+#pragma unroll
+      for (int it = 0; it < NIT; ++it)
+        if (idx[it] >= 0) row[idx[it]] = v[it];
+    } else if (blockIdx.x >= n_tiles) {                // (cannot happen: the launch plan gives every workgroup a tile)
+      for (int i = tid; i < nd.n_theta; i += 256) row[i] = 0.0;
+    }
+    if constexpr (PDE == PDE_ADR_IDE) {
+      if (tid < 9) {
+        const double v = ((scal[tid] + scal[9 + tid]) + scal[18 + tid]) + scal[27 + tid];
+        if (tid < 3) row[nd.n_theta + tid] = v;
+        else row[nd.n_theta - 9 + tid] = (((int)ide_mask >> (tid - 3)) & 1) ? v : 0.0;     // a frozen coefficient: exactly 0.0
+      }
+    } else
+    if (tid < 4) {
+      const double v = ((scal[tid] + scal[4 + tid]) + scal[8 + tid]) + scal[12 + tid];
+      if (tid == 0) { row[nd.n_theta + 0] = v; if (!pde_adr_fixed(PDE)) row[nd.n_theta + 2] = 0.0; }
+      if (tid == 1) row[nd.n_theta + 1] = v;
+      if (pde_adr_fixed(PDE) && tid == 2) row[nd.n_theta + 2] = v;     // the periodic pairs' part (+ the Robin part)
+      if (PDE == 1 && tid == 2) row[nd.n_net] = v;
+      if (PDE == 1 && tid == 3) row[nd.n_net + 1] = v;
+    }
+  }
+  STAMP(2 * H + 2);
+}

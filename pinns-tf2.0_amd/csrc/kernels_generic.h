@@ -28,7 +28,8 @@ struct NetDesc {
 };
 
 // Training-set geometry for one evaluation.  Points are stored in class order
-// [boundary-lo | boundary-hi | data | collocation | pad].
+// [boundary-lo | boundary-hi | data | collocation | pad].  (PDE_ADR_ROBIN: a Robin block stands between the collocation block
+// and the padding; it is not counted here -- n_all ends the collocation block, n_pad covers the Robin block -- see AdrRobinArg.)
 struct SetDesc {
   int n_b, n_u, n_f;         // local counts
   int n_all;                 // 2*n_b + n_u + n_f
@@ -50,17 +51,35 @@ constexpr int PDE_ADR = 3;
 // as exactly 0.0 (the optimisers then leave it where it is: Adam's m and v stay 0, every L-BFGS direction is 0 there).
 //   enum -> template value:  PINN_PDE_ADR 5 -> PDE_ADR 3,  PINN_PDE_ADR_IDE 6 -> PDE_ADR_IDE 4
 constexpr int PDE_ADR_IDE = 4;
-constexpr bool pde_is_adr(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_IDE; }
+// Template number of PINN_PDE_ADR with Robin points present (pinn_set_robin): PDE_ADR's kernels with a fourth point class,
+//   r_j = alpha_j u + beta_j u_x - g_j,   loss part (1 / N_w) sum r_j^2 added to the boundary part.
+// The class is a block of its own BEHIND the collocation block, [pairs | data | collocation | robin | pad]: SetDesc and every
+// offset of the other classes stay what they are (sd.n_all still ends the collocation block; n_pad covers the Robin block).
+// Where PDE_ADR passes its six coefficients travels AdrRobinArg: the coefficients, the (alpha, beta) pairs indexed by point -
+// first, the block's first point and length and 1 / N_w; g_j rides in tgt at the point's own index.  A template value of
+// its own, not a flag: no instantiation of another kind changes its name, its arguments or an instruction.  The engine
+// dispatches here only while the local Robin count is > 0.
+constexpr int PDE_ADR_ROBIN = 5;
+constexpr bool pde_is_adr(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_IDE || PDE == PDE_ADR_ROBIN; }
+// the kinds whose six coefficients are run-time constants (PDE_ADR_IDE reads them from the weight vector)
+constexpr bool pde_adr_fixed(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_ROBIN; }
 // trailing equation parameters of the weight vector: 2 lambdas (PDE 1), six coefficients (PDE_ADR_IDE)
 constexpr int pde_n_tail(int PDE) { return PDE == 1 ? 2 : PDE == PDE_ADR_IDE ? 6 : 0; }
 template <typename real> struct AdrCoef { real a0, a1, nu, r1, r2, r3; };
 struct AdrIdeArg { int mask; };
+template <typename real> struct AdrRobinArg {
+  AdrCoef<real> k;
+  const real* ab;      // [n][2]: (alpha_j, beta_j) of Robin point first + j
+  int first, n;        // the Robin block: points first .. first + n - 1
+  real inv_nw;         // 1 / GLOBAL Robin count
+};
 template <typename real, int PDE>
-using pde_coef_t = typename std::conditional<PDE == PDE_ADR, AdrCoef<real>,
-                                             typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, real>::type>::type;
+using pde_coef_t = typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<real>, typename std::conditional<PDE == PDE_ADR, AdrCoef<real>,
+                                             typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, real>::type>::type>::type;
 template <typename real> __device__ __forceinline__ real coef_nu(real nu) { return nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrCoef<real>& k) { return k.nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrIdeArg&) { return real(0); }
+template <typename real> __device__ __forceinline__ real coef_nu(const AdrRobinArg<real>& a) { return a.k.nu; }
 template <typename real> __device__ __forceinline__ AdrCoef<real> coef_adr(real) { return AdrCoef<real>{0, 0, 0, 0, 0, 0}; }
 template <typename real> __device__ __forceinline__ AdrCoef<real> coef_adr(const AdrCoef<real>& k) { return k; }
 // the current coefficients of PDE_ADR_IDE from the tail of the weight vector
@@ -187,26 +206,39 @@ __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_
                                                 const vec4<real>& ov, const vec4<real>* __restrict__ O,
                                                 const real* __restrict__ tgt, real c1, real c2,
                                                 vec4<real> sb[2], real lt[3], real dl[2],
-                                                const AdrCoef<real>& k = AdrCoef<real>{0, 0, 0, 0, 0, 0});
+                                                const AdrCoef<real>& k = AdrCoef<real>{0, 0, 0, 0, 0, 0},
+                                                const AdrRobinArg<real>* rb = nullptr);
 template <typename real, int PDE>
 __device__ __forceinline__ void point_seeds(const SetDesc& sd, int g, int n_pad,
                                             const vec4<real>* __restrict__ O,
                                             const real* __restrict__ tgt, real c1, real c2,
                                             vec4<real> sb[2], real lt[3], real dl[2],
-                                            const AdrCoef<real>& k = AdrCoef<real>{0, 0, 0, 0, 0, 0}) {
+                                            const AdrCoef<real>& k = AdrCoef<real>{0, 0, 0, 0, 0, 0},
+                                            const AdrRobinArg<real>* rb = nullptr) {
   const vec4<real> ou = O[g], ov = PDE == 2 ? O[(size_t)n_pad + g] : vec4<real>{0, 0, 0, 0};
-  point_seeds_own<real, PDE>(sd, g, n_pad, ou, ov, O, tgt, c1, c2, sb, lt, dl, k);
+  point_seeds_own<real, PDE>(sd, g, n_pad, ou, ov, O, tgt, c1, c2, sb, lt, dl, k, rb);
 }
 template <typename real, int PDE>
 __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_pad, const vec4<real>& ou,
                                                 const vec4<real>& ov, const vec4<real>* __restrict__ O,
                                                 const real* __restrict__ tgt, real c1, real c2,
-                                                vec4<real> sb[2], real lt[3], real dl[2], const AdrCoef<real>& k) {
+                                                vec4<real> sb[2], real lt[3], real dl[2], const AdrCoef<real>& k,
+                                                const AdrRobinArg<real>* rb) {
   const int cls = pde_is_adr(PDE) ? point_class_adr(sd, g) : point_class(sd, g);
   sb[0] = sb[1] = vec4<real>{0, 0, 0, 0};
   lt[0] = lt[1] = lt[2] = real(0);
   dl[0] = dl[1] = real(0);
   if constexpr (PDE == PDE_ADR_IDE) dl[2] = dl[3] = dl[4] = dl[5] = real(0);
+  if constexpr (PDE == PDE_ADR_ROBIN) {   // the Robin block stands behind the collocation block (CLS_PAD by sd's counts)
+    const int j = g - rb->first;
+    if ((unsigned)j < (unsigned)rb->n) {  // r = alpha u + beta u_x - g; its square counts in the boundary part
+      const real al = rb->ab[2 * j], be = rb->ab[2 * j + 1];
+      const real r = al * ou.x + be * ou.y - tgt[g];
+      lt[2] = r * r * rb->inv_nw;
+      sb[0].x = real(2) * r * al * rb->inv_nw; sb[0].y = real(2) * r * be * rb->inv_nw;
+      return;
+    }
+  }
   if (cls == CLS_PAD) return;
   const real inv_nf = (real)sd.inv_nf, inv_nu = (real)sd.inv_nu, inv_nb = (real)sd.inv_nb;
   if constexpr (pde_is_adr(PDE)) {   // advection-diffusion-reaction, run-time coefficients, periodic pairs (g, g ^ 1)
@@ -332,6 +364,7 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
   vec4<real> sb[2];
   real lt[3], dl[PDE == PDE_ADR_IDE ? 6 : 2];
   if constexpr (PDE == PDE_ADR) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr<real>(nu));
+  else if constexpr (PDE == PDE_ADR_ROBIN) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, nu.k, &nu);
   else if constexpr (PDE == PDE_ADR_IDE) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr_tail<real>(th + nd.n_net));
   else point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl);
 
@@ -477,6 +510,17 @@ __global__ void k_residual(int first, int n, int n_pad, const vec4<real>* __rest
     const vec4<real> o = O[g];
     f[i] = (double)(o.z + c1 * o.x * o.y - c2 * o.w);
   }
+}
+
+// Robin residuals r_j = alpha_j u + beta_j u_x - g_j at the stored Robin points from the forward outputs
+// (pinn_robin_residual): forward only, no seeds
+template <typename real>
+__global__ void k_robin_residual(AdrRobinArg<real> rb, const vec4<real>* __restrict__ O, const real* __restrict__ tgt,
+                                 double* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= rb.n) return;
+  const vec4<real> o = O[rb.first + j];
+  out[j] = (double)(rb.ab[2 * j] * o.x + rb.ab[2 * j + 1] * o.y - tgt[rb.first + j]);
 }
 
 }  // namespace pinn

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _REPO = os.path.dirname(os.path.dirname(_HERE))
 LIB_PATH = os.environ.get("PINN_HIP_LIB") or os.path.join(_HERE, "libpinn_hip.so")
-SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_wide.h", "kernels_predict20.h",
+SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_fused20d_kernel.h", "kernels_wide.h", "kernels_predict20.h",
            "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h"]
 HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
@@ -288,6 +288,10 @@ _SIGNATURES = {
                                    _c_double_p, ctypes.c_int64]),
     "pinn_pw_adam_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
     "pinn_pw_disable": (ctypes.c_int, [ctypes.c_void_p]),
+    # Robin points of the adr kind (include/pinn_hip.h: pinn_set_robin, pinn_robin_residual)
+    "pinn_set_robin": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64,
+                                      ctypes.c_int64]),
+    "pinn_robin_residual": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
 }
 
 
@@ -451,7 +455,7 @@ class Engine(object):
         n = ctypes.c_int64(0)
         self._check(self._lib.pinn_num_params(self._h, ctypes.byref(n)))
         self.n_params = n.value
-        self.n_f = self.n_u = self.n_b = 0
+        self.n_f = self.n_u = self.n_b = self.n_w = 0
 
     def _check(self, rc):
         if rc != 0:
@@ -555,6 +559,40 @@ class Engine(object):
         self.n_b = X_lb.shape[0]
         self._check(self._lib.pinn_set_boundary(self._h, _dp(X_lb), _dp(X_ub), self.n_b,
                                                 self.n_b if n_total is None else int(n_total)))
+
+    def set_robin(self, X_w, alpha, beta, g, n_total=None):
+        """Robin points of the adr kind: alpha u + beta u_x = g at the rows (x, t) of X_w; alpha, beta and g are arrays of one
+        value per point or scalars (broadcast).  (1, 0, g) is a Dirichlet value, (0, 1, g) a flux, (h, 1, g) a Robin wall.
+        An empty X_w removes the class.  Their part of the loss is added to terms[2] of loss_grad."""
+        X_w = _f64(X_w)
+        if X_w.size % 2 or (X_w.ndim > 1 and X_w.shape[-1] != 2):
+            raise ValueError("X_w must be [n, 2] rows (x, t), got shape %s" % (X_w.shape,))
+        X_w = np.ascontiguousarray(X_w.reshape(-1, 2))
+        n = X_w.shape[0]
+        cols = []
+        for name, v in (("alpha", alpha), ("beta", beta), ("g", g)):
+            v = _f64(v)
+            if v.size != 1 and v.size != n:
+                raise ValueError("%s must be a scalar or hold one value per Robin point (%d), got %d" % (name, n, v.size))
+            v = np.ascontiguousarray(np.broadcast_to(v.reshape(-1), (n,)))
+            if not np.all(np.isfinite(v)):
+                raise ValueError("%s must be finite" % name)
+            cols.append(v)
+        if not np.all(np.isfinite(X_w)):
+            raise ValueError("X_w must be finite")
+        if np.any((cols[0] == 0.0) & (cols[1] == 0.0)):
+            raise ValueError("a Robin point with alpha = beta = 0 constrains nothing")
+        if n_total is not None and int(n_total) < n:
+            raise ValueError("n_total (%d) is smaller than the local count (%d)" % (int(n_total), n))
+        self._check(self._lib.pinn_set_robin(self._h, _dp(X_w), _dp(cols[0]), _dp(cols[1]), _dp(cols[2]), n,
+                                             n if n_total is None else int(n_total)))
+        self.n_w = n
+
+    def robin_residual(self):
+        """r_j = alpha_j u + beta_j u_x - g_j at the Robin points, current weights -> [n_w]"""
+        r = np.empty(self.n_w, dtype=np.float64)
+        self._check(self._lib.pinn_robin_residual(self._h, _dp(r), r.size))
+        return r
 
     def set_pde_params(self, *p):
         p = _f64(p)
@@ -806,7 +844,7 @@ class Engine(object):
 
     def debug_stamps(self):
         """(profiling build) -> int64 array [n_waves, 32] of s_memtime ticks for one evaluation"""
-        n_wg = (2 * self.n_b + self.n_u + self.n_f + 63) // 64
+        n_wg = (2 * self.n_b + self.n_u + self.n_f + getattr(self, "n_w", 0) + 63) // 64
         buf = np.zeros((n_wg * 4, 32), dtype=np.int64)
         n = ctypes.c_int64(0)
         self._check(self._lib.pinn_debug_stamps(

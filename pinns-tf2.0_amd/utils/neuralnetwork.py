@@ -339,6 +339,20 @@ class NeuralNetwork(object):
         else:
             self._engine.set_boundary(X_lb, X_ub)
 
+    def _set_robin(self, X_w, alpha, beta, g):
+        """Robin points of the "adr" kind, alpha u + beta u_x = g at the rows (x, t) of X_w (Engine.set_robin; scalars
+        broadcast): Dirichlet (1, 0, g), Neumann (0, 1, g), Robin (h, 1, g).  Their mean square is added to the boundary
+        part of the loss.  One device; not combined with hp["point_weights"].  Redraws of the collocation set
+        (hp["resample"]) leave them in place."""
+        if self.pde != "adr":
+            raise ValueError('_set_robin: Robin points are for the "adr" kind; the %s model is not supported' % self.pde)
+        if self._pw:
+            raise ValueError('_set_robin: Robin points are not combined with hp["point_weights"] (the weights cover data, '
+                             'collocation points and periodic pairs only)')
+        if self._dp:
+            raise ValueError('_set_robin: Robin points run on one device; a data-parallel launch is not supported')
+        self._engine.set_robin(X_w, alpha, beta, g)
+
     def _residual_collocation(self):
         """f at ALL collocation points [N_f, n_out], on every rank (a shard holds only its block: the replicated
         weights are evaluated at the full set instead)"""

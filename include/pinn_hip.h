@@ -419,6 +419,31 @@ int pinn_set_robin(pinn_ctx* c, const double* X_w /*[n][2]*/, const double* alph
                    int64_t n, int64_t n_total);
 int pinn_robin_residual(pinn_ctx* c, double* out /*[n]*/, int64_t n);
 
+/* Source term of the adr kind (PINN_PDE_ADR): a right-hand side s(x, t), given as one value per LOCAL collocation point.  The
+ * residual of collocation point i and the loss are
+ *   f_i = u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 - s_i
+ *   L   = mean_f f^2 + (data, pairs and Robin parts as without a source)
+ * With s = N[u*] for a closed-form u*, u* is the exact solution of any member of the family with any wall kind (the method
+ * of manufactured solutions).  The gradient row, terms and every optimiser call keep their layout.  Float32 and float64,
+ * kernel paths 0 and 7; Robin points may be present.
+ *   pinn_set_source   s [n], n = the local collocation count; replaces the source.  s == NULL with n == 0 removes it -- from
+ *                     then on every result is bit-identical to a context that never had a source.  A source of zeros gives
+ *                     those bits too.  The source survives pinn_set_data, pinn_set_boundary, pinn_set_robin and
+ *                     pinn_set_pde_params.
+ * Stale rule: pinn_set_collocation and pinn_lhs_collocation replace the points, not the values, so a present source
+ * becomes STALE.  While it is stale pinn_loss_grad, the Adam and L-BFGS entry points (enqueue forms included) and
+ * pinn_residual return PINN_ESTATE and launch nothing; pinn_get_collocation still works -- it hands out the new points --
+ * and pinn_set_source with values at them, or with n = 0, clears the state.
+ * Residuals: pinn_residual (over the set) returns f including - s.  pinn_residual_at cannot know s at foreign points: it
+ * returns the operator part N[u]; subtract s there yourself.
+ * Refusals, before any device work, the context unchanged: PINN_EINVAL for a null array with n > 0, n < 0 or a non-finite
+ * value (whatever the context is), and for n other than the local collocation count; PINN_EUNSUPPORTED for any kind but
+ * PINN_PDE_ADR (PINN_PDE_ADR_IDE included), while point weights are on (and pinn_pw_set is refused while a source is
+ * present), a kernel path other than 0 or 7, a communicator (pinn_comm_init and pinn_comm_xgmi_export are refused the same
+ * way while a source is present).  pinn_rad_collocation is refused with PINN_EUNSUPPORTED while a source is present -- the
+ * pool's residuals would lack s -- and does NOT make the source stale.  (Additive: the ABI version stays 6.) */
+int pinn_set_source(pinn_ctx* c, const double* s /*[n]*/, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -279,6 +279,15 @@ struct pinn_ctx {
     size_t cap_out = 0;
   } robin;
 
+  // source term of the adr kind (pinn_set_source; template value PDE_ADR_SRC of the kernels): s_i as handed over, one value per
+  // local collocation point.  ensure_sets places them in tgt at the collocation indices.  stale: the collocation points were
+  // replaced since (pinn_set_collocation, pinn_lhs_collocation) -- the values belong to other points, nothing evaluates until
+  // pinn_set_source is called again
+  struct {
+    std::vector<double> s;
+    bool on = false, stale = false;
+  } src;
+
   // discrete-time models (pde 3, 4): stage sets as handed over, device copies, scratch
   struct DiscSet { std::vector<double> x, t, M; int q = 0; bool has_M = false; };
   DiscSet dset[2];
@@ -335,10 +344,24 @@ static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
     return AdrRobinArg<real>{AdrCoef<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5]},
                              (const real*)c->robin.ab, c->robin.first, c->robin.n,
                              (real)(c->robin.n_total > 0 ? 1.0 / (double)c->robin.n_total : 0.0)};
+  else if constexpr (PDE == PDE_ADR_SRC)   // the set's own residuals: s by set index is tgt itself
+    return AdrSrcArg<real>{pde_coef<real, PDE_ADR_ROBIN>(c), (const real*)c->tgt};
   else if constexpr (PDE == PDE_ADR_IDE)
     return AdrIdeArg{c->adr_mask};
   else
     return (real)c->nu;
+}
+
+// a source whose points were replaced: refused in front of every evaluation, nothing launched
+static int src_fresh(const pinn_ctx* c, const char* who) {
+  if (c->src.on && c->src.stale)
+    return fail(PINN_ESTATE, "%s: the collocation points were replaced since the source term was set; its values belong to the "
+                "old points -- call pinn_set_source with values at the new points (pinn_get_collocation), or with n = 0", who);
+  return 0;
+}
+// local collocation count as the next assembly will see it
+static int64_t n_colloc(const pinn_ctx* c) {
+  return c->lhs.on ? c->lhs.count : c->rad.on ? c->rad.count : (int64_t)(c->Xf.size() / 2);
 }
 
 // the fused kernel serves width-20 Burgers nets whose staged weights fit the 160 KiB LDS
@@ -541,6 +564,11 @@ static int ensure_sets(pinn_ctx* c) {
     for (int i = 0; i < n_f; ++i, ++g) { hx[g] = c->Xf[2 * i]; ht[g] = c->Xf[2 * i + 1]; }
   if (c->lhs.on || c->rad.on)                                      // filled on the device, below
     for (int i = 0; i < n_f; ++i, ++g) { hx[g] = c->lb[0]; ht[g] = c->lb[1]; }
+  if (is_adr(c) && c->src.on && !c->src.stale) {                   // s_i rides in tgt at the collocation point's own index
+    REQUIRE((int)c->src.s.size() == n_f, "the source term holds %lld values, the collocation set %d points",
+            (long long)c->src.s.size(), n_f);
+    for (int i = 0; i < n_f; ++i) htg[(size_t)(2 * n_b + n_u) + i] = c->src.s[i];
+  }
   c->robin.first = n_all; c->robin.n = n_w;
   for (int j = 0; j < n_w; ++j, ++g) {                             // g_j rides in tgt at the point's own index
     hx[g] = c->robin.X[2 * j]; ht[g] = c->robin.X[2 * j + 1];
@@ -854,6 +882,7 @@ static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
       else rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR>(c));
     }
     else if constexpr (PDE == PDE_ADR_ROBIN) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_ROBIN>(c));
+    else if constexpr (PDE == PDE_ADR_SRC) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_SRC>(c));
     else if constexpr (PDE == PDE_ADR_IDE) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_IDE>(c));
     else if (weighted) rc = fused20d_launch_any(a, SaArgs{(double)c->nu, c->sa.arr.buf, af ? af->alpha_sa : 0.0});
     else rc = fused20d_launch_any(PDE, a, (double)c->nu);
@@ -1166,7 +1195,9 @@ static int disc_eval_any(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
 }
 
 static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
-  int rc = is_disc(c) ? disc_ensure(c) : ensure_sets(c);
+  int rc = src_fresh(c, "evaluation");          // (the entry points refuse by their own name before they get here)
+  if (rc) return rc;
+  rc = is_disc(c) ? disc_ensure(c) : ensure_sets(c);
   if (rc) return rc;
   c->n_evals += 1;
   hipEvent_t* ev4 = nullptr;
@@ -1176,7 +1207,8 @@ static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
   switch (c->pde) {                                                          \
     case PINN_PDE_BURGERS: rc = launch_sweeps<REAL, 0>(c, ev4, af); break;       \
     case PINN_PDE_BURGERS_IDE: rc = launch_sweeps<REAL, 1>(c, ev4, af); break;   \
-    case PINN_PDE_ADR: rc = c->robin.n > 0 ? launch_sweeps<REAL, PDE_ADR_ROBIN>(c, ev4, af)  /* the parent's kernels without */ \
+    case PINN_PDE_ADR: rc = c->src.on ? launch_sweeps<REAL, PDE_ADR_SRC>(c, ev4, af)         /* source (+ Robin points) */ \
+                          : c->robin.n > 0 ? launch_sweeps<REAL, PDE_ADR_ROBIN>(c, ev4, af)  /* the parent's kernels without */ \
                                            : launch_sweeps<REAL, PDE_ADR>(c, ev4, af); break; \
     case PINN_PDE_ADR_IDE: rc = launch_sweeps<REAL, PDE_ADR_IDE>(c, ev4, af); break; \
     default: rc = launch_sweeps<REAL, 2>(c, ev4, af); break;                     \
@@ -1694,6 +1726,7 @@ int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_to
   c->nf_total = n_total;
   c->lhs.on = false;
   c->rad.on = false;
+  if (c->src.on) c->src.stale = true;            // the values belonged to the old points
   c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
   c->sets_dirty = true;
   return 0;
@@ -1707,6 +1740,7 @@ int pinn_lhs_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
           (long long)count);
   HIPCHK(hipSetDevice(c->device));
   const bool same_shape = c->lhs.on && !c->sets_dirty && c->lhs.count == count;
+  if (c->src.on) c->src.stale = true;            // the fill writes xs and ts only
   c->lhs.on = true; c->lhs.n_design = n_design; c->lhs.first = first; c->lhs.count = count; c->lhs.seed = seed;
   c->rad.on = false;
   c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
@@ -1727,6 +1761,9 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
           "bad design geometry (n_design %lld, first %lld, count %lld)", (long long)n_design, (long long)first,
           (long long)count);
   REQUIRE(n_pool >= 1 && n_pool <= RAD_POOL_MAX, "pinn_rad_collocation: n_pool %lld is outside 1..2^24", (long long)n_pool);
+  if (c->src.on)                                  // refused first: the source is not made stale, the context stays usable
+    return fail(PINN_EUNSUPPORTED, "pinn_rad_collocation: the adaptive draw is not combined with a source term -- the pool's "
+                "residuals would lack s (pinn_set_source with n = 0 first)");
   REQUIRE(k >= 1 && k <= 4, "pinn_rad_collocation: k %d is outside 1..4", k);
   REQUIRE(std::isfinite(c_add) && c_add >= 0.0 && c_add <= 64.0, "pinn_rad_collocation: c %g is outside [0, 64]", c_add);
   HIPCHK(hipSetDevice(c->device));
@@ -1849,6 +1886,43 @@ int pinn_robin_residual(pinn_ctx* c, double* out, int64_t n) {
   return 0;
 }
 
+// Source term of the adr kind: f_i = N[u](x_i, t_i) - s_i at local collocation point i.  Every refusal stands in front of any
+// device work and leaves the context as it was (the array is looked at first: it needs no context); n = 0 removes the source.
+int pinn_set_source(pinn_ctx* c, const double* s, int64_t n) {
+  REQUIRE(n >= 0, "pinn_set_source: bad count (n %lld)", (long long)n);
+  REQUIRE(n <= (1 << 30), "pinn_set_source: too many values (%lld)", (long long)n);
+  REQUIRE(n == 0 || s, "pinn_set_source: null array");
+  for (int64_t i = 0; i < n; ++i) REQUIRE(std::isfinite(s[i]), "pinn_set_source: value %lld is not finite", (long long)i);
+  REQUIRE(c, "pinn_set_source: null context");
+  if (c->pde == PINN_PDE_ADR_IDE)
+    return fail(PINN_EUNSUPPORTED, "pinn_set_source: a source term is for the adr kind (pde 5) only; the adr_ide kind (pde 6) has no variant for it");
+  if (!is_adr(c)) return fail(PINN_EUNSUPPORTED, "pinn_set_source: a source term is for the adr kind (pde 5) only");
+  if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_set_source: point weights are not combined with a source term (pinn_pw_disable first)");
+  if (!adr_has_path(c->path))
+    return fail(PINN_EUNSUPPORTED, "pinn_set_source: a source term runs on kernel paths 0 and 7 only (this context runs path %d)", (int)c->path);
+  if (c->comm || c->xg.box)
+    return fail(PINN_EUNSUPPORTED, "pinn_set_source: a source term is single-device; this context has a communicator");
+  REQUIRE(n == 0 || n == n_colloc(c), "pinn_set_source: %lld values for %lld local collocation points", (long long)n,
+          (long long)n_colloc(c));
+  HIPCHK(hipSetDevice(c->device));
+  // the set is assembled and the block has this length: one copy into the collocation block of tgt (zeros on removal), no
+  // re-assembly; an in-place LHS redraw leaves the set in this state too
+  const bool in_place = !c->sets_dirty && c->tgt && (n == 0 || c->sd.n_f == n);
+  if (in_place && c->sd.n_f > 0) {
+    const size_t off = (size_t)(2 * c->sd.n_b + c->sd.n_u), rs = real_size(c);
+    if (n == 0) {
+      HIPCHK(hipMemsetAsync((char*)c->tgt + off * rs, 0, (size_t)c->sd.n_f * rs, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+    } else if (upload_real(c, (char*)c->tgt + off * rs, s, (size_t)n)) return PINN_EHIP;
+  }
+  if (n == 0) { c->src.s.clear(); c->src.s.shrink_to_fit(); }
+  else c->src.s.assign(s, s + n);
+  c->src.on = n > 0;
+  c->src.stale = false;
+  if (!in_place) c->sets_dirty = true;
+  return 0;
+}
+
 int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
   REQUIRE(c && p && n >= 1, "bad pde params");
   if (is_adr(c)) {      // a0, a1, nu, r1, r2, r3; nothing changes on a refusal
@@ -1943,6 +2017,7 @@ int pinn_get_weights(pinn_ctx* c, double* w, int64_t n) {
 
 int pinn_loss_grad(pinn_ctx* c, double* loss, double* grad, double* terms) {
   REQUIRE(c, "null");
+  if (int rc0 = src_fresh(c, "pinn_loss_grad")) return rc0;
   HIPCHK(hipSetDevice(c->device));
   const Range rg("pinn_loss_grad");
   int rc = eval_loss_grad(c);
@@ -2009,6 +2084,7 @@ static int pend_reserve(pinn_ctx* c, int kind, size_t n_loss, size_t n_iter, boo
 // n_steps Adam iterations into the stream.  record = false: nothing is kept (pinn_adam_run with losses == NULL).
 static int adam_issue(pinn_ctx* c, int n_steps, bool record, int* ticket) {
   REQUIRE(c && n_steps >= 0, "bad arguments");
+  if (int rc0 = src_fresh(c, "pinn_adam_run / pinn_adam_enqueue")) return rc0;
   REQUIRE(c->adam_ready, "pinn_adam_init has not been called");
   HIPCHK(hipSetDevice(c->device));
   const Range rg("pinn_adam_run");
@@ -2118,6 +2194,7 @@ static int lbfgs_begin_setup(pinn_ctx* c, int max_iter, double lr, int n_corr, d
                              double max_eval, bool* eval) {
   *eval = false;
   REQUIRE(c && max_iter >= 0 && n_corr >= 1 && lr > 0, "bad L-BFGS arguments");
+  if (int rc0 = src_fresh(c, "pinn_lbfgs_begin")) return rc0;
   HIPCHK(hipSetDevice(c->device));
   const size_t n = c->nd.n_theta;
   c->lb_max_iter = max_iter; c->lb_lr = lr; c->lb_ncorr = n_corr;
@@ -2210,6 +2287,7 @@ int pinn_lbfgs_begin(pinn_ctx* c, int max_iter, double lr, int n_corr, double to
 static int lbfgs_open(pinn_ctx* c, int n_iters, int* ticket, pinn_ctx::Pending** pp, int* window_out) {
   *pp = nullptr;
   REQUIRE(c && n_iters >= 0, "bad arguments");
+  if (int rc0 = src_fresh(c, "pinn_lbfgs_run / pinn_lbfgs_enqueue")) return rc0;
   REQUIRE(c->lb_ready, "pinn_lbfgs_begin has not been called");
   HIPCHK(hipSetDevice(c->device));
   pinn_ctx::Pending* p = nullptr;
@@ -2478,6 +2556,7 @@ int pinn_disc_predict(pinn_ctx* c, int set, const double* x, int64_t n, double* 
 int pinn_residual(pinn_ctx* c, double* f, int64_t n) {
   if (c && is_disc(c)) return fail(PINN_EUNSUPPORTED, "pinn_residual: not defined for discrete-time models");
   REQUIRE(c && f, "null");
+  if (int rc0 = src_fresh(c, "pinn_residual")) return rc0;
   HIPCHK(hipSetDevice(c->device));
   int rc = ensure_sets(c);
   if (rc) return rc;
@@ -2492,8 +2571,8 @@ int pinn_residual(pinn_ctx* c, double* f, int64_t n) {
   if (int rc2 = forward_taylor(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O)) return rc2;
   const dim3 grid((cnt + 255) / 256), block(256);
 #define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, first, cnt, sd.n_pad, (const vec4<REAL>*)c->O, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->f_out, NO)
-  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) RES(double, PDE_ADR); else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
-  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) RES(float, PDE_ADR); else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
+  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) { if (c->src.on) RES(double, PDE_ADR_SRC); else RES(double, PDE_ADR); } else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
+  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) { if (c->src.on) RES(float, PDE_ADR_SRC); else RES(float, PDE_ADR); } else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
 #undef RES
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)cnt * NO * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2513,8 +2592,11 @@ int pinn_residual_at(pinn_ctx* c, const double* X, int64_t n, double* f) {
   if ((size_t)n * NO > c->cap_f) { if (dev_alloc(&c->f_out, (size_t)n * NO * 8)) return PINN_EHIP; c->cap_f = (size_t)n * NO; }
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
 #define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, 0, (int)n, n_pad, (const vec4<REAL>*)c->Oe, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->f_out, NO)
-  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) RES(double, PDE_ADR); else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
-  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) RES(float, PDE_ADR); else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
+  // a context with a source: s is not known at foreign points -- the operator part N[u], AdrSrcArg's null form
+#define RES_AT_SRC(REAL) hipLaunchKernelGGL((k_residual<REAL, PDE_ADR_SRC>), grid, block, 0, c->stream, 0, (int)n, n_pad, (const vec4<REAL>*)c->Oe, (const REAL*)c->theta_r, c->nd.n_net, AdrSrcArg<REAL>{pde_coef<REAL, PDE_ADR_ROBIN>(c), nullptr}, c->f_out, NO)
+  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) { if (c->src.on) RES_AT_SRC(double); else RES(double, PDE_ADR); } else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
+  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) { if (c->src.on) RES_AT_SRC(float); else RES(float, PDE_ADR); } else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
+#undef RES_AT_SRC
 #undef RES
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)n * NO * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2537,6 +2619,7 @@ int pinn_comm_init(pinn_ctx* c, const char* id128, int n_ranks, int rank) {
   if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: point weights are single-device (pinn_pw_disable first)");
   if (is_adr_ide(c)) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
   if (!c->robin.X.empty()) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: Robin points are single-device (pinn_set_robin with n = 0 first)");
+  if (c->src.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: a source term is single-device (pinn_set_source with n = 0 first)");
   HIPCHK(hipSetDevice(c->device));
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
   xg_release(c);
@@ -2557,6 +2640,8 @@ int pinn_comm_xgmi_export(pinn_ctx* c, int n_ranks, int rank, char* handle64) {
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: point weights are single-device (pinn_pw_disable first)");
   if (!c->robin.X.empty())
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: Robin points are single-device (pinn_set_robin with n = 0 first)");
+  if (c->src.on)
+    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: a source term is single-device (pinn_set_source with n = 0 first)");
   if (is_adr_ide(c))
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is expected to be 64 bytes");
@@ -2920,6 +3005,8 @@ int pinn_pw_set(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam
   if (int rc = pw_supported(c, "pinn_pw_set")) return rc;
   if (!c->robin.X.empty())
     return fail(PINN_EUNSUPPORTED, "pinn_pw_set: point weights do not cover Robin points; remove them first (pinn_set_robin with n = 0)");
+  if (c->src.on)
+    return fail(PINN_EUNSUPPORTED, "pinn_pw_set: point weights are not combined with a source term; remove it first (pinn_set_source with n = 0)");
   if (int rc = pw_check_counts(c, "pinn_pw_set", n_u, n_f, n_b)) return rc;
   for (int64_t j = 0; lam_u && j < n_u; ++j) REQUIRE(std::isfinite(lam_u[j]), "pinn_pw_set: lam_u[%lld] is not finite", (long long)j);
   for (int64_t i = 0; lam_f && i < n_f; ++i) REQUIRE(std::isfinite(lam_f[i]), "pinn_pw_set: lam_f[%lld] is not finite", (long long)i);

@@ -107,4 +107,9 @@ int fused20d_launch_any(const F20dLaunch& a, const AdrPwArgs& k);
 // device array of 2 k.n doubles, 16-byte aligned; g_j stands in tgt at the Robin point's own index.  Launch only with k.n > 0.
 int fused20d_launch_any(const F20dLaunch& a, const AdrRobinArg<double>& k);
 
+// one evaluation of the adr kind with a source term (k_src20d<PDE_ADR_SRC, H, .>, kernels_generic.h AdrSrcArg): the same set,
+// s_i in a.tgt at the collocation point's own index; the Robin part of k is as above, k.n may be 0 (k.ab is not read then);
+// k.src is not read by this kernel.  Launch only while a source is present.
+int fused20d_launch_any(const F20dLaunch& a, const AdrSrcArg<double>& k);
+
 }  // namespace pinn

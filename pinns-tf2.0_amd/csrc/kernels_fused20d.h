@@ -239,8 +239,12 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
 // registers left, too few to hold two more doubles across the forward sweep) and g = tgt[pt], its slot-0 lane adds
 // r^2 / N_w to the boundary slot lacc[128], and it seeds sb[0] and sb[1].  Tile loop: first, length and 1 / N_w are parked
 // behind the other seven in lacc[192..] (slots 7-9) and the array's address is held in vector registers, as SAW holds its own.
+// PDE == PDE_ADR_SRC (PDE_ADR with a source term, kernels_generic.h; instantiated under the name k_src20d): PDE_ADR_ROBIN's
+// text -- the slot carries AdrSrcArg<double>, the Robin count may be 0 -- with one more operation in the collocation class:
+// f is formed as PDE_ADR forms it, then s_i = tgt[pt] is subtracted, uncontracted (a zero source gives PDE_ADR's bits).  The
+// value is loaded at the seed block.  No seed formula changes.
 template <bool SETS, bool SAW = false, int PDE = 0>
-using f20d_nu_t = typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<double>, typename std::conditional<PDE == PDE_ADR && SAW, AdrPwArgs, typename std::conditional<PDE == PDE_ADR, AdrCoef<double>, typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type>::type>::type>::type>::type;
+using f20d_nu_t = typename std::conditional<PDE == PDE_ADR_SRC, AdrSrcArg<double>, typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<double>, typename std::conditional<PDE == PDE_ADR && SAW, AdrPwArgs, typename std::conditional<PDE == PDE_ADR, AdrCoef<double>, typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type>::type>::type>::type>::type>::type;
 __device__ __forceinline__ double f20d_nu(double nu) { return nu; }
 __device__ __forceinline__ double f20d_nu(const AdrIdeArg&) { return 0.0; }
 __device__ __forceinline__ double f20d_nu(const AdrCoef<double>& k) { return k.nu; }
@@ -256,10 +260,15 @@ __device__ __forceinline__ double f20d_nu(const AdrRobinArg<double>& a) { return
 #define PINN_F20D_KERNEL k_robin20d
 #include "kernels_fused20d_kernel.h"
 #undef PINN_F20D_KERNEL
+// and under the name the source-term variants are instantiated with (PDE_ADR_SRC only)
+#define PINN_F20D_KERNEL k_src20d
+#include "kernels_fused20d_kernel.h"
+#undef PINN_F20D_KERNEL
 // kernel <PDE, H, ONE_TILE, ENS, SETS, SAW> by its name in the library
 template <int PDE, int H, bool ONE_TILE, bool ENS, bool SETS, bool SAW>
 constexpr auto f20d_kernel() {
   if constexpr (PDE == PDE_ADR_ROBIN) return &k_robin20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
+  else if constexpr (PDE == PDE_ADR_SRC) return &k_src20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
   else return &k_fused20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
 }
 

@@ -1,8 +1,9 @@
 // kernels_fused20d_kernel.h -- the body of k_fused20d, included by kernels_fused20d.h once per kernel NAME (PINN_F20D_KERNEL):
-// k_fused20d for every kind and variant but one, k_robin20d for PDE_ADR_ROBIN (the adr kind with Robin points).  The text is
-// one, so an instantiation of either name is what a single template gives; the second name exists because the set of
-// k_fused20d<...> instantiations in the library is pinned (tests/test_isa_hazards.py counts them) and the Robin variants
-// are an addition beside it.  (Not a __device__ body called from two kernels: such a wrapper changed the schedule of the
+// k_fused20d for every kind and variant but two, k_robin20d for PDE_ADR_ROBIN (the adr kind with Robin points), k_src20d for
+// PDE_ADR_SRC (the adr kind with a source term).  The text is
+// one, so an instantiation of any name is what a single template gives; the other names exist because the set of
+// k_fused20d<...> instantiations in the library is pinned (tests/test_isa_hazards.py counts them) and the Robin and source
+// variants are additions beside it.  (Not a __device__ body called from two kernels: such a wrapper changed the schedule of the
 // existing instantiations.)  No include guard: it is meant to be included more than once.
 template <int PDE, int H, bool ONE_TILE, bool ENS = false, bool SETS = false, bool SAW = false>
 __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict__ th, const double* __restrict__ xs,
@@ -17,6 +18,8 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
   static_assert(!SAW || ((PDE == 0 || PDE == PDE_ADR) && !ENS), "point weights: Burgers inference or adr, solo launch");
   static_assert(PDE != PDE_ADR_ROBIN || (!ENS && !SETS && !SAW),
                 "Robin points: the fixed-coefficient adr kind only, solo launch, no point weights");
+  static_assert(PDE != PDE_ADR_SRC || (!ENS && !SETS && !SAW),
+                "source term: the fixed-coefficient adr kind only, solo launch, no point weights");
   // weight offsets: compile-time constants in the one-tile variant (immediate operands; Adam step 41.9 -> 40.8 us with
   // the preloaded pointers); the tile-loop variant keeps them in SGPRs -- with immediates its schedule came out 9 %
   // slower (N_f = 10^6: 2104 vs 1930 us per step, same box)
@@ -107,10 +110,10 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       adr_park[5] = nu.r3; adr_park[6] = sd.inv_nb;
     }
   }
-  // PDE_ADR_ROBIN, tile loop: the same seven and the Robin block's first point, length and 1 / N_w; the (alpha, beta) array's
+  // PDE_ADR_ROBIN and PDE_ADR_SRC, tile loop: the same seven and the Robin block's first point, length and 1 / N_w; the (alpha, beta) array's
   // address in vector registers (an opaque move), as SAW holds its array's
   const double* rb_ab = nullptr;
-  if constexpr (PDE == PDE_ADR_ROBIN) {
+  if constexpr (pde_adr_robin(PDE)) {
     rb_ab = nu.ab;
     if constexpr (!ONE_TILE) {
       asm volatile("" : "+v"(rb_ab));
@@ -497,10 +500,10 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       const double pu = dpp_mov<DPP_QUAD_XOR1>(o[0]), pp = dpp_mov<DPP_QUAD_XOR1>(o[1]);
       AdrCoef<double> kc;
       double inv_nb;
-      int rb_j = -1, rb_n = 0;               // PDE_ADR_ROBIN: this point's place in the Robin block, the block's length
+      int rb_j = -1, rb_n = 0;               // PDE_ADR_ROBIN, PDE_ADR_SRC: this point's place in the Robin block, the block's length
       double inv_nw = 0.0;
       if constexpr (ONE_TILE) {
-        if constexpr (PDE == PDE_ADR_ROBIN) { kc = nu.k; rb_j = pt - nu.first; rb_n = nu.n; inv_nw = nu.inv_nw; }
+        if constexpr (pde_adr_robin(PDE)) { kc = nu.k; rb_j = pt - nu.first; rb_n = nu.n; inv_nw = nu.inv_nw; }
         else kc = nu;
         inv_nb = sd.inv_nb;
       } else {
@@ -508,13 +511,19 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
         asm volatile("" : "+v"(kp));
         kc = AdrCoef<double>{kp[0], kp[1], kp[2], kp[3], kp[4], kp[5]};
         inv_nb = kp[6];
-        if constexpr (PDE == PDE_ADR_ROBIN) { rb_j = pt - (int)kp[7]; rb_n = (int)kp[8]; inv_nw = kp[9]; }
+        if constexpr (pde_adr_robin(PDE)) { rb_j = pt - (int)kp[7]; rb_n = (int)kp[8]; inv_nw = kp[9]; }
       }
       (void)rb_j; (void)rb_n; (void)inv_nw;
       const int cls = point_class_adr(sd, pt);
       if (cls == CLS_COL) {
         const double u = o[0], adv = kc.a0 + kc.a1 * u;
-        const double f = o[2] + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
+        double f = o[2] + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
+        if constexpr (PDE == PDE_ADR_SRC) {
+          // minus the source s_i = tgt[pt], loaded here (the one-tile adr variants have no vector registers to hold it across
+          // the forward sweep) and subtracted as an operation of its own: a zero source gives PDE_ADR's bits
+#pragma clang fp contract(off)
+          f = f - tgt[pt];
+        }
         const double fbar = 2.0 * f * inv_nf;
         if (s == 0) lacc[0] += f * f * inv_nf;
         sb[0] = fbar * (kc.a1 * o[1] + kc.r1 + u * (2.0 * kc.r2 + 3.0 * kc.r3 * u));
@@ -527,7 +536,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
         const double du = o[0] - pu, dp = o[1] - pp;
         if (s == 0 && cls == CLS_BLO) lacc[128] += (du * du + dp * dp) * inv_nb;
         sb[0] = 2.0 * du * inv_nb; sb[1] = 2.0 * dp * inv_nb;
-      } else if constexpr (PDE == PDE_ADR_ROBIN) {
+      } else if constexpr (pde_adr_robin(PDE)) {
         // the Robin block stands behind the collocation block (CLS_PAD by sd's counts): r = alpha u + beta u_x - g
         if ((unsigned)rb_j < (unsigned)rb_n) {
           typedef double d2 __attribute__((ext_vector_type(2)));

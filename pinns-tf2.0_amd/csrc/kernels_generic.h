@@ -60,9 +60,19 @@ constexpr int PDE_ADR_IDE = 4;
 // its own, not a flag: no instantiation of another kind changes its name, its arguments or an instruction.  The engine
 // dispatches here only while the local Robin count is > 0.
 constexpr int PDE_ADR_ROBIN = 5;
-constexpr bool pde_is_adr(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_IDE || PDE == PDE_ADR_ROBIN; }
+// Template number of PINN_PDE_ADR with a source term present (pinn_set_source): the residual of collocation point i is
+//   f_i = u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 - s_i,
+// s_i riding in tgt at the point's own index (data targets and the Robin g_j ride there already; the slots of the
+// collocation block are zero otherwise).  No seed formula changes: df/d(u, u_x, u_t, u_xx) do not depend on s.  A superset of
+// PDE_ADR_ROBIN -- AdrSrcArg is AdrRobinArg and a source pointer, the Robin count may be 0 -- so a source with Robin walls needs
+// no second family.  The subtraction is an operation of its own, never contracted into f: a zero source gives PDE_ADR's bits.
+// The engine dispatches here only while a source is present.
+constexpr int PDE_ADR_SRC = 6;
+constexpr bool pde_is_adr(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_IDE || PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC; }
 // the kinds whose six coefficients are run-time constants (PDE_ADR_IDE reads them from the weight vector)
-constexpr bool pde_adr_fixed(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_ROBIN; }
+constexpr bool pde_adr_fixed(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC; }
+// the kinds that carry a Robin block behind the collocation block
+constexpr bool pde_adr_robin(int PDE) { return PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC; }
 // trailing equation parameters of the weight vector: 2 lambdas (PDE 1), six coefficients (PDE_ADR_IDE)
 constexpr int pde_n_tail(int PDE) { return PDE == 1 ? 2 : PDE == PDE_ADR_IDE ? 6 : 0; }
 template <typename real> struct AdrCoef { real a0, a1, nu, r1, r2, r3; };
@@ -73,9 +83,14 @@ template <typename real> struct AdrRobinArg {
   int first, n;        // the Robin block: points first .. first + n - 1
   real inv_nw;         // 1 / GLOBAL Robin count
 };
+// PDE_ADR_SRC: AdrRobinArg's content (n may be 0) and, for k_residual alone, the source by SET index -- the training kernels
+// read s from their tgt argument.  src == nullptr: the operator part N[u] (residuals at foreign points, pinn_residual_at)
+template <typename real> struct AdrSrcArg : AdrRobinArg<real> {
+  const real* src;
+};
 template <typename real, int PDE>
-using pde_coef_t = typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<real>, typename std::conditional<PDE == PDE_ADR, AdrCoef<real>,
-                                             typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, real>::type>::type>::type;
+using pde_coef_t = typename std::conditional<PDE == PDE_ADR_SRC, AdrSrcArg<real>, typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<real>, typename std::conditional<PDE == PDE_ADR, AdrCoef<real>,
+                                             typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, real>::type>::type>::type>::type;
 template <typename real> __device__ __forceinline__ real coef_nu(real nu) { return nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrCoef<real>& k) { return k.nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrIdeArg&) { return real(0); }
@@ -229,7 +244,7 @@ __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_
   lt[0] = lt[1] = lt[2] = real(0);
   dl[0] = dl[1] = real(0);
   if constexpr (PDE == PDE_ADR_IDE) dl[2] = dl[3] = dl[4] = dl[5] = real(0);
-  if constexpr (PDE == PDE_ADR_ROBIN) {   // the Robin block stands behind the collocation block (CLS_PAD by sd's counts)
+  if constexpr (pde_adr_robin(PDE)) {     // the Robin block stands behind the collocation block (CLS_PAD by sd's counts)
     const int j = g - rb->first;
     if ((unsigned)j < (unsigned)rb->n) {  // r = alpha u + beta u_x - g; its square counts in the boundary part
       const real al = rb->ab[2 * j], be = rb->ab[2 * j + 1];
@@ -245,7 +260,11 @@ __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_
     const vec4<real> o = ou;
     if (cls == CLS_COL) {
       const real u = o.x, adv = k.a0 + k.a1 * u;
-      const real f = adr_residual(k, o);
+      real f = adr_residual(k, o);
+      if constexpr (PDE == PDE_ADR_SRC) {      // minus the source, an operation of its own (s = 0: PDE_ADR's bits)
+#pragma clang fp contract(off)
+        f = f - tgt[g];
+      }
       const real fb = real(2) * f * inv_nf;
       lt[0] = f * f * inv_nf;
       sb[0].x = fb * (k.a1 * o.y + k.r1 + u * (real(2) * k.r2 + real(3) * k.r3 * u));
@@ -364,7 +383,7 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
   vec4<real> sb[2];
   real lt[3], dl[PDE == PDE_ADR_IDE ? 6 : 2];
   if constexpr (PDE == PDE_ADR) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr<real>(nu));
-  else if constexpr (PDE == PDE_ADR_ROBIN) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, nu.k, &nu);
+  else if constexpr (pde_adr_robin(PDE)) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, nu.k, &nu);
   else if constexpr (PDE == PDE_ADR_IDE) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr_tail<real>(th + nd.n_net));
   else point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl);
 
@@ -497,6 +516,13 @@ __global__ void k_residual(int first, int n, int n_pad, const vec4<real>* __rest
   const int g = first + i;
   if constexpr (PDE == PDE_ADR) {
     f[i] = (double)adr_residual(nu, O[g]);
+  } else if constexpr (PDE == PDE_ADR_SRC) {
+    real r = adr_residual(nu.k, O[g]);
+    if (nu.src) {
+#pragma clang fp contract(off)
+      r = r - nu.src[g];
+    }
+    f[i] = (double)r;
   } else if constexpr (PDE == PDE_ADR_IDE) {
     f[i] = (double)adr_residual(coef_adr_tail<real>(th + n_net), O[g]);
   } else if (PDE == 2) {

@@ -292,6 +292,8 @@ _SIGNATURES = {
     "pinn_set_robin": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64,
                                       ctypes.c_int64]),
     "pinn_robin_residual": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
+    # source term of the adr kind (include/pinn_hip.h: pinn_set_source)
+    "pinn_set_source": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
 }
 
 
@@ -456,6 +458,7 @@ class Engine(object):
         self._check(self._lib.pinn_num_params(self._h, ctypes.byref(n)))
         self.n_params = n.value
         self.n_f = self.n_u = self.n_b = self.n_w = 0
+        self._has_source = False
 
     def _check(self, rc):
         if rc != 0:
@@ -588,6 +591,29 @@ class Engine(object):
                                              n if n_total is None else int(n_total)))
         self.n_w = n
 
+    def set_source(self, s):
+        """Source term of the adr kind: f_i = N[u](x_i, t_i) - s[i] at collocation point i (the rows of get_collocation).
+        None removes it.  A redraw of the collocation set makes a present source stale: evaluations are refused until
+        set_source is called again with values at the new points (get_collocation still works then)."""
+        if s is None:
+            self._check(self._lib.pinn_set_source(self._h, None, 0))
+            self._has_source = False
+            return
+        s = np.ascontiguousarray(_f64(s).reshape(-1))
+        if s.size != self.n_f:
+            raise ValueError("the source term must hold one value per collocation point (%d), got %d" % (self.n_f, s.size))
+        if s.size == 0:
+            raise ValueError("the source term is empty (None removes a source)")
+        if not np.all(np.isfinite(s)):
+            raise ValueError("the source term must be finite")
+        self._check(self._lib.pinn_set_source(self._h, _dp(s), s.size))
+        self._has_source = True
+
+    @property
+    def has_source(self):
+        """a source term is present (set_source), stale or not"""
+        return bool(getattr(self, "_has_source", False))
+
     def robin_residual(self):
         """r_j = alpha_j u + beta_j u_x - g_j at the Robin points, current weights -> [n_w]"""
         r = np.empty(self.n_w, dtype=np.float64)
@@ -681,12 +707,19 @@ class Engine(object):
         self._check(self._lib.pinn_residual(self._h, _dp(f), n))
         return f
 
-    def residual_at(self, X):
-        """f_model at arbitrary points X [n, 2] -> [n, n_out]"""
+    def residual_at(self, X, source=None):
+        """f_model at arbitrary points X [n, 2] -> [n, n_out].  A context with a source term (set_source) cannot know s at
+        foreign points: pass source = s(X) [n], subtracted here from the operator part the library returns."""
         X = _f64(X).reshape(-1, 2)
+        if source is None and self.has_source:
+            raise ValueError("residual_at: this context holds a source term; pass source = s at the rows of X")
+        if source is not None:
+            source = _f64(source).reshape(-1)
+            if source.size != X.shape[0]:
+                raise ValueError("residual_at: source must hold one value per point (%d), got %d" % (X.shape[0], source.size))
         f = np.empty((X.shape[0], self.n_out), dtype=np.float64)
         self._check(self._lib.pinn_residual_at(self._h, _dp(X), X.shape[0], _dp(f)))
-        return f
+        return f if source is None else f - source.reshape(-1, 1)
 
     # ---- optimisers ------------------------------------------------------------------------
     def adam_init(self, lr, beta1=0.9, beta2=0.999, eps=1e-7):

@@ -353,6 +353,32 @@ class NeuralNetwork(object):
             raise ValueError('_set_robin: Robin points run on one device; a data-parallel launch is not supported')
         self._engine.set_robin(X_w, alpha, beta, g)
 
+    def _set_source(self, s):
+        """Source term of the "adr" kind (Engine.set_source): f = N[u] - s at the collocation points.  s is an array of one
+        value per collocation point (call _set_collocation first), or a callable taking X [n, 2] = (x, t) and returning [n]
+        -- then every device redraw of the collocation set (hp["resample_every"] > 0, Latin hypercube) is followed by
+        get_collocation() and set_source(s(X)).  An array cannot follow a redraw.  None removes the source.  One device; not
+        combined with hp["resample"] = "rad" (the pool's residuals would lack s) or hp["point_weights"]."""
+        if self.pde != "adr":
+            raise ValueError('_set_source: a source term is for the "adr" kind; the %s model is not supported' % self.pde)
+        if self._resample == "rad":
+            raise ValueError('_set_source: a source term is not combined with hp["resample"] = "rad" (the adaptive draw\'s '
+                             'pool residuals would lack s)')
+        if self._pw:
+            raise ValueError('_set_source: a source term is not combined with hp["point_weights"]')
+        if self._dp:
+            raise ValueError('_set_source: a source term runs on one device; a data-parallel launch is not supported')
+        if s is not None and not callable(s) and self._resample_every > 0:
+            raise ValueError('_set_source: an array cannot follow the redraws of the collocation set '
+                             '(hp["resample_every"] > 0); pass a callable s(X)')
+        self._source_fn = s if callable(s) else None
+        if s is None:
+            self._engine.set_source(None)
+        elif callable(s):
+            self._engine.set_source(np.asarray(s(self._engine.get_collocation()), dtype=np.float64).reshape(-1))
+        else:
+            self._engine.set_source(s)
+
     def _residual_collocation(self):
         """f at ALL collocation points [N_f, n_out], on every rank (a shard holds only its block: the replicated
         weights are evaluated at the full set instead)"""
@@ -512,6 +538,9 @@ class NeuralNetwork(object):
                                                  c=self._rad_c, first=lo, count=hi - lo)
                 else:
                     self._engine.lhs_collocation(n_design, self._resample_seed + epoch, first=lo, count=hi - lo)
+                    if getattr(self, "_source_fn", None) is not None:      # the source at the new points (_set_source)
+                        X_new = self._engine.get_collocation()
+                        self._engine.set_source(np.asarray(self._source_fn(X_new), dtype=np.float64).reshape(-1))
                 self._X_f = None
             # run up to and including the next epoch that is logged, then sync once
             stop = min(self.tf_epochs, (epoch + freq - 1) // freq * freq + 1)

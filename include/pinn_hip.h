@@ -444,6 +444,35 @@ int pinn_robin_residual(pinn_ctx* c, double* out /*[n]*/, int64_t n);
  * pool's residuals would lack s -- and does NOT make the source stale.  (Additive: the ABI version stays 6.) */
 int pinn_set_source(pinn_ctx* c, const double* s /*[n]*/, int64_t n);
 
+/* Coefficient fields of the adr kind (PINN_PDE_ADR): variable media.  Each LOCAL collocation point i gets a row of six
+ * coefficients K_i = (a0, a1, nu, r1, r2, r3)_i, and the residual and the loss are
+ *   f_i = u_t + (a0_i + a1_i u) u_x - nu_i u_xx + r1_i u + r2_i u^2 + r3_i u^3 - s_i      (s_i = 0 without a source)
+ *   L   = mean_f f^2 + (data, pairs and Robin parts as without fields)
+ * A rod of two materials, a diffusivity nu(x), a prescribed velocity field a0(x, t), a reaction rate that depends on place or
+ * time; the conservative term -(nu(x) u_x)_x is the field nu with the field a0 = -nu'(x).  The table is dense, [n][6], no
+ * mask: a coefficient that does not vary is a constant column.  The gradient row, terms and every optimiser call keep their
+ * layout.  Float32 and float64, kernel paths 0 and 7; Robin points and a source may be present in any combination.
+ *   pinn_set_coef_fields   K [n][6], n = the local collocation count; replaces the fields.  K == NULL with n == 0 removes them
+ *                          -- from then on every result is bit-identical to a context that never had them.  A table whose
+ *                          every row is the context's constant set gives the bits of the context without fields.  The fields
+ *                          survive pinn_set_data, pinn_set_boundary, pinn_set_robin, pinn_set_source and pinn_set_pde_params.
+ * While fields are present the six constants of pinn_set_pde_params are read by no evaluation; the call stays allowed, its
+ * values are kept and count again after removal.
+ * Stale rule (the source's): pinn_set_collocation and pinn_lhs_collocation make present fields STALE.  While they are stale
+ * pinn_loss_grad, the Adam and L-BFGS entry points (enqueue forms included) and pinn_residual return PINN_ESTATE and launch
+ * nothing; pinn_get_collocation still works, and pinn_set_coef_fields with rows at the new points, or with n = 0, clears the
+ * state.  A source and fields may both be stale: each is cleared by its own setter, and the message names both.
+ * Residuals: pinn_residual (over the set) returns f with the rows, including - s_i.  pinn_residual_at returns
+ * PINN_EUNSUPPORTED while fields are present: the coefficients are not known at foreign points.
+ * Refusals, before any device work, the context unchanged: PINN_EINVAL for a null array with n > 0, n < 0 or a non-finite
+ * entry (whatever the context is -- a row is refused where pinn_set_pde_params would refuse it as a constant set), and for n
+ * other than the local collocation count; PINN_EUNSUPPORTED for any kind but PINN_PDE_ADR (PINN_PDE_ADR_IDE included), while
+ * point weights are on (and pinn_pw_set is refused while fields are present), a kernel path other than 0 or 7, a
+ * communicator (pinn_comm_init and pinn_comm_xgmi_export are refused the same way while fields are present).
+ * pinn_rad_collocation is refused with PINN_EUNSUPPORTED while fields are present and does NOT make them stale.
+ * (Additive: the ABI version stays 6.) */
+int pinn_set_coef_fields(pinn_ctx* c, const double* K /*[n][6]*/, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,46 @@ def source(X, coeffs):
     return u_t + (a0 + a1 * u) * u_x - nu * u_xx + r1 * u + r2 * u * u + r3 * u * u * u
 
 
+# variable media (1d-mms/inf_cont_mms_var.py, Engine.set_coef_fields): hp["medium"] names one of these coefficient fields
+MEDIA = ("graded_rod", "shear_flow", "graded_reaction")
+
+
+def medium_fields(X, medium):
+    """K [n, 6] = (a0, a1, nu, r1, r2, r3) at the rows (x, t) of X [n, 2]:
+      "graded_rod"       u_t - (nu(x) u_x)_x = s with nu(x) = 0.1 (1 + 0.8 tanh 8x): the conservative term is the field nu
+                         with the field a0 = -nu'(x) = -0.64 / cosh^2 8x
+      "shear_flow"       transport in the prescribed velocity field a0(x, t) = 0.7 + 0.3 sin(pi x) cos(pi t), nu = 0.05
+      "graded_reaction"  Allen-Cahn (nu = 1e-4, r3 = 5) with the rate r1(x) = -5 (1 + 0.5 x)"""
+    if medium not in MEDIA:
+        raise ValueError('hp["medium"] must be one of %s (got %r)' % (list(MEDIA), medium))
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 2)
+    x, t = X[:, 0], X[:, 1]
+    K = np.zeros((X.shape[0], 6))
+    if medium == "graded_rod":
+        th = np.tanh(8.0 * x)
+        K[:, 2] = 0.1 * (1.0 + 0.8 * th)
+        K[:, 0] = -0.64 * (1.0 - th * th)
+    elif medium == "shear_flow":
+        K[:, 0] = 0.7 + 0.3 * np.sin(np.pi * x) * np.cos(np.pi * t)
+        K[:, 2] = 0.05
+    else:
+        K[:, 2] = 1e-4
+        K[:, 3] = -5.0 * (1.0 + 0.5 * x)
+        K[:, 5] = 5.0
+    return K
+
+
+def source_var(X, K):
+    """s = N_K[u*] at the rows (x, t) of X [n, 2] with the rows K [n, 6] of coefficients -> [n]"""
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 2)
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (X.shape[0], 6):
+        raise ValueError("K must hold one row of six coefficients per point (%d), got shape %s" % (X.shape[0], K.shape))
+    a0, a1, nu, r1, r2, r3 = (K[:, j] for j in range(6))
+    u, u_x, u_t, u_xx = exact_channels(X[:, 0], X[:, 1])
+    return u_t + (a0 + a1 * u) * u_x - nu * u_xx + r1 * u + r2 * u * u + r3 * u * u * u
+
+
 def exact_field(n_x=N_X, n_t=N_T):
     """x [n_x, 1] (both walls included), t [n_t, 1], Exact_u [n_t, n_x]"""
     x, t = np.linspace(-1.0, 1.0, n_x).reshape(-1, 1), np.linspace(0.0, 1.0, n_t).reshape(-1, 1)

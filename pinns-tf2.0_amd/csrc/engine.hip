@@ -288,6 +288,17 @@ struct pinn_ctx {
     bool on = false, stale = false;
   } src;
 
+  // coefficient fields of the adr kind (pinn_set_coef_fields; template value PDE_ADR_VAR of the kernels): the table as handed
+  // over, K[6 i + j] = coefficient j of local collocation point i, and its device copy in the compute dtype (ensure_sets).
+  // stale: as the source's flag, for the same reason and cleared by this kind's own setter.  While on, c->adr is kept but not
+  // read by any evaluation
+  struct {
+    std::vector<double> K;
+    bool on = false, stale = false;
+    void* dev = nullptr;
+    size_t cap = 0;                    // entries the device array holds
+  } kf;
+
   // discrete-time models (pde 3, 4): stage sets as handed over, device copies, scratch
   struct DiscSet { std::vector<double> x, t, M; int q = 0; bool has_M = false; };
   DiscSet dset[2];
@@ -346,15 +357,27 @@ static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
                              (real)(c->robin.n_total > 0 ? 1.0 / (double)c->robin.n_total : 0.0)};
   else if constexpr (PDE == PDE_ADR_SRC)   // the set's own residuals: s by set index is tgt itself
     return AdrSrcArg<real>{pde_coef<real, PDE_ADR_ROBIN>(c), (const real*)c->tgt};
+  else if constexpr (PDE == PDE_ADR_VAR)   // the collocation slots of tgt are zero without a source
+    return AdrVarArg<real>{pde_coef<real, PDE_ADR_SRC>(c), (const real*)c->kf.dev};
   else if constexpr (PDE == PDE_ADR_IDE)
     return AdrIdeArg{c->adr_mask};
   else
     return (real)c->nu;
 }
 
-// a source whose points were replaced: refused in front of every evaluation, nothing launched
+// a source or coefficient fields whose points were replaced: refused in front of every evaluation, nothing launched.  One
+// check for both per-collocation-point kinds of value; each is cleared by its own setter
 static int src_fresh(const pinn_ctx* c, const char* who) {
-  if (c->src.on && c->src.stale)
+  const bool s_stale = c->src.on && c->src.stale, k_stale = c->kf.on && c->kf.stale;
+  if (s_stale && k_stale)
+    return fail(PINN_ESTATE, "%s: the collocation points were replaced since the source term and the coefficient fields were "
+                "set; their values belong to the old points -- call pinn_set_source and pinn_set_coef_fields with values at "
+                "the new points (pinn_get_collocation), or with n = 0", who);
+  if (k_stale)
+    return fail(PINN_ESTATE, "%s: the collocation points were replaced since the coefficient fields were set; their rows belong "
+                "to the old points -- call pinn_set_coef_fields with rows at the new points (pinn_get_collocation), or with "
+                "n = 0", who);
+  if (s_stale)
     return fail(PINN_ESTATE, "%s: the collocation points were replaced since the source term was set; its values belong to the "
                 "old points -- call pinn_set_source with values at the new points (pinn_get_collocation), or with n = 0", who);
   return 0;
@@ -569,6 +592,9 @@ static int ensure_sets(pinn_ctx* c) {
             (long long)c->src.s.size(), n_f);
     for (int i = 0; i < n_f; ++i) htg[(size_t)(2 * n_b + n_u) + i] = c->src.s[i];
   }
+  if (is_adr(c) && c->kf.on && !c->kf.stale)
+    REQUIRE((int)(c->kf.K.size() / 6) == n_f, "the coefficient fields hold %lld rows, the collocation set %d points",
+            (long long)(c->kf.K.size() / 6), n_f);
   c->robin.first = n_all; c->robin.n = n_w;
   for (int j = 0; j < n_w; ++j, ++g) {                             // g_j rides in tgt at the point's own index
     hx[g] = c->robin.X[2 * j]; ht[g] = c->robin.X[2 * j + 1];
@@ -601,6 +627,13 @@ static int ensure_sets(pinn_ctx* c) {
       c->robin.cap = hab.size();
     }
     if (upload_real(c, c->robin.ab, hab.data(), hab.size())) return PINN_EHIP;
+  }
+  if (is_adr(c) && c->kf.on && !c->kf.stale && n_f > 0) {           // the table, row i for collocation point 2 n_b + n_u + i
+    if (c->kf.K.size() > c->kf.cap) {
+      if (dev_alloc(&c->kf.dev, c->kf.K.size() * rs)) return PINN_EHIP;
+      c->kf.cap = c->kf.K.size();
+    }
+    if (upload_real(c, c->kf.dev, c->kf.K.data(), c->kf.K.size())) return PINN_EHIP;
   }
   if (c->lhs.on) { if (int rc = lhs_fill(c)) return rc; }
 
@@ -883,6 +916,7 @@ static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
     }
     else if constexpr (PDE == PDE_ADR_ROBIN) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_ROBIN>(c));
     else if constexpr (PDE == PDE_ADR_SRC) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_SRC>(c));
+    else if constexpr (PDE == PDE_ADR_VAR) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_VAR>(c));
     else if constexpr (PDE == PDE_ADR_IDE) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_IDE>(c));
     else if (weighted) rc = fused20d_launch_any(a, SaArgs{(double)c->nu, c->sa.arr.buf, af ? af->alpha_sa : 0.0});
     else rc = fused20d_launch_any(PDE, a, (double)c->nu);
@@ -1207,7 +1241,8 @@ static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
   switch (c->pde) {                                                          \
     case PINN_PDE_BURGERS: rc = launch_sweeps<REAL, 0>(c, ev4, af); break;       \
     case PINN_PDE_BURGERS_IDE: rc = launch_sweeps<REAL, 1>(c, ev4, af); break;   \
-    case PINN_PDE_ADR: rc = c->src.on ? launch_sweeps<REAL, PDE_ADR_SRC>(c, ev4, af)         /* source (+ Robin points) */ \
+    case PINN_PDE_ADR: rc = c->kf.on ? launch_sweeps<REAL, PDE_ADR_VAR>(c, ev4, af)          /* fields (+ source, + Robin) */ \
+                          : c->src.on ? launch_sweeps<REAL, PDE_ADR_SRC>(c, ev4, af)         /* source (+ Robin points) */ \
                           : c->robin.n > 0 ? launch_sweeps<REAL, PDE_ADR_ROBIN>(c, ev4, af)  /* the parent's kernels without */ \
                                            : launch_sweeps<REAL, PDE_ADR>(c, ev4, af); break; \
     case PINN_PDE_ADR_IDE: rc = launch_sweeps<REAL, PDE_ADR_IDE>(c, ev4, af); break; \
@@ -1698,7 +1733,7 @@ int pinn_destroy(pinn_ctx* c) {
                   c->d_Ast, c->d_A3, c->d_U3, c->d_Nn, c->d_R, c->d_dAp, c->d_lossp, c->d_lamp,
                   c->pred, c->d_ref, c->err_partial, c->err_res, c->d_nonfinite, c->t16_bsync, c->t16_gscr,
                   c->rad.cx, c->rad.ct, c->rad.px, c->rad.pt, c->rad.O, c->rad.f, c->rad.w, c->rad.bsum, c->rad.tot,
-                  c->robin.ab, c->robin.out};
+                  c->robin.ab, c->robin.out, c->kf.dev};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& p : c->pend) {
     if (p.h_state) (void)hipHostFree(p.h_state);
@@ -1727,6 +1762,7 @@ int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_to
   c->lhs.on = false;
   c->rad.on = false;
   if (c->src.on) c->src.stale = true;            // the values belonged to the old points
+  if (c->kf.on) c->kf.stale = true;
   c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
   c->sets_dirty = true;
   return 0;
@@ -1741,6 +1777,7 @@ int pinn_lhs_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   HIPCHK(hipSetDevice(c->device));
   const bool same_shape = c->lhs.on && !c->sets_dirty && c->lhs.count == count;
   if (c->src.on) c->src.stale = true;            // the fill writes xs and ts only
+  if (c->kf.on) c->kf.stale = true;
   c->lhs.on = true; c->lhs.n_design = n_design; c->lhs.first = first; c->lhs.count = count; c->lhs.seed = seed;
   c->rad.on = false;
   c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
@@ -1764,6 +1801,9 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   if (c->src.on)                                  // refused first: the source is not made stale, the context stays usable
     return fail(PINN_EUNSUPPORTED, "pinn_rad_collocation: the adaptive draw is not combined with a source term -- the pool's "
                 "residuals would lack s (pinn_set_source with n = 0 first)");
+  if (c->kf.on)                                   // the same: the pool's points have no rows
+    return fail(PINN_EUNSUPPORTED, "pinn_rad_collocation: the adaptive draw is not combined with coefficient fields -- the "
+                "coefficients are not known at the pool's points (pinn_set_coef_fields with n = 0 first)");
   REQUIRE(k >= 1 && k <= 4, "pinn_rad_collocation: k %d is outside 1..4", k);
   REQUIRE(std::isfinite(c_add) && c_add >= 0.0 && c_add <= 64.0, "pinn_rad_collocation: c %g is outside [0, 64]", c_add);
   HIPCHK(hipSetDevice(c->device));
@@ -1919,6 +1959,41 @@ int pinn_set_source(pinn_ctx* c, const double* s, int64_t n) {
   else c->src.s.assign(s, s + n);
   c->src.on = n > 0;
   c->src.stale = false;
+  if (!in_place) c->sets_dirty = true;
+  return 0;
+}
+
+// Coefficient fields of the adr kind: row i of K holds (a0, a1, nu, r1, r2, r3) of local collocation point i.  pinn_set_source's
+// order of refusals and its placement: the array first, then the context, nothing touched on a refusal; n = 0 removes them.
+int pinn_set_coef_fields(pinn_ctx* c, const double* K, int64_t n) {
+  REQUIRE(n >= 0, "pinn_set_coef_fields: bad count (n %lld)", (long long)n);
+  REQUIRE(n <= (1 << 28), "pinn_set_coef_fields: too many rows (%lld)", (long long)n);
+  REQUIRE(n == 0 || K, "pinn_set_coef_fields: null array");
+  // a row is refused where pinn_set_pde_params refuses a constant set of the adr kind: a coefficient that is not finite
+  for (int64_t i = 0; i < 6 * n; ++i)
+    REQUIRE(std::isfinite(K[i]), "pinn_set_coef_fields: coefficient %d of row %lld is not finite", (int)(i % 6), (long long)(i / 6));
+  REQUIRE(c, "pinn_set_coef_fields: null context");
+  if (c->pde == PINN_PDE_ADR_IDE)
+    return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: coefficient fields are for the adr kind (pde 5) only; the adr_ide kind (pde 6) has no variant for them");
+  if (!is_adr(c)) return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: coefficient fields are for the adr kind (pde 5) only");
+  if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: point weights are not combined with coefficient fields (pinn_pw_disable first)");
+  if (!adr_has_path(c->path))
+    return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: coefficient fields run on kernel paths 0 and 7 only (this context runs path %d)", (int)c->path);
+  if (c->comm || c->xg.box)
+    return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: coefficient fields are single-device; this context has a communicator");
+  REQUIRE(n == 0 || n == n_colloc(c), "pinn_set_coef_fields: %lld rows for %lld local collocation points", (long long)n,
+          (long long)n_colloc(c));
+  HIPCHK(hipSetDevice(c->device));
+  // the set is assembled and the block has this length: one copy into the device table, no re-assembly (an in-place LHS redraw
+  // leaves the set in this state too).  Removal needs no device work: the table is not read without fields
+  const bool in_place = !c->sets_dirty && c->tgt && (n == 0 || (c->sd.n_f == n && c->kf.cap >= (size_t)6 * n));
+  if (in_place && n > 0) {
+    if (upload_real(c, c->kf.dev, K, (size_t)6 * n)) return PINN_EHIP;
+  }
+  if (n == 0) { c->kf.K.clear(); c->kf.K.shrink_to_fit(); }
+  else c->kf.K.assign(K, K + 6 * n);
+  c->kf.on = n > 0;
+  c->kf.stale = false;
   if (!in_place) c->sets_dirty = true;
   return 0;
 }
@@ -2571,8 +2646,8 @@ int pinn_residual(pinn_ctx* c, double* f, int64_t n) {
   if (int rc2 = forward_taylor(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O)) return rc2;
   const dim3 grid((cnt + 255) / 256), block(256);
 #define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, first, cnt, sd.n_pad, (const vec4<REAL>*)c->O, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->f_out, NO)
-  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) { if (c->src.on) RES(double, PDE_ADR_SRC); else RES(double, PDE_ADR); } else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
-  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) { if (c->src.on) RES(float, PDE_ADR_SRC); else RES(float, PDE_ADR); } else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
+  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) { if (c->kf.on) RES(double, PDE_ADR_VAR); else if (c->src.on) RES(double, PDE_ADR_SRC); else RES(double, PDE_ADR); } else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
+  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) { if (c->kf.on) RES(float, PDE_ADR_VAR); else if (c->src.on) RES(float, PDE_ADR_SRC); else RES(float, PDE_ADR); } else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
 #undef RES
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)cnt * NO * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2583,6 +2658,9 @@ int pinn_residual(pinn_ctx* c, double* f, int64_t n) {
 int pinn_residual_at(pinn_ctx* c, const double* X, int64_t n, double* f) {
   if (c && is_disc(c)) return fail(PINN_EUNSUPPORTED, "pinn_residual_at: not defined for discrete-time models");
   REQUIRE(c && X && f && n >= 0, "bad arguments");
+  if (c->kf.on)
+    return fail(PINN_EUNSUPPORTED, "pinn_residual_at: this context holds coefficient fields, and the coefficients are not known at "
+                "foreign points (pinn_residual gives f over the set; pinn_set_coef_fields with n = 0 removes the fields)");
   HIPCHK(hipSetDevice(c->device));
   if (n == 0) return 0;
   const int NO = c->nd.n_out;
@@ -2620,6 +2698,7 @@ int pinn_comm_init(pinn_ctx* c, const char* id128, int n_ranks, int rank) {
   if (is_adr_ide(c)) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
   if (!c->robin.X.empty()) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: Robin points are single-device (pinn_set_robin with n = 0 first)");
   if (c->src.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: a source term is single-device (pinn_set_source with n = 0 first)");
+  if (c->kf.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: coefficient fields are single-device (pinn_set_coef_fields with n = 0 first)");
   HIPCHK(hipSetDevice(c->device));
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
   xg_release(c);
@@ -2642,6 +2721,8 @@ int pinn_comm_xgmi_export(pinn_ctx* c, int n_ranks, int rank, char* handle64) {
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: Robin points are single-device (pinn_set_robin with n = 0 first)");
   if (c->src.on)
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: a source term is single-device (pinn_set_source with n = 0 first)");
+  if (c->kf.on)
+    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: coefficient fields are single-device (pinn_set_coef_fields with n = 0 first)");
   if (is_adr_ide(c))
     return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is expected to be 64 bytes");
@@ -3007,6 +3088,8 @@ int pinn_pw_set(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam
     return fail(PINN_EUNSUPPORTED, "pinn_pw_set: point weights do not cover Robin points; remove them first (pinn_set_robin with n = 0)");
   if (c->src.on)
     return fail(PINN_EUNSUPPORTED, "pinn_pw_set: point weights are not combined with a source term; remove it first (pinn_set_source with n = 0)");
+  if (c->kf.on)
+    return fail(PINN_EUNSUPPORTED, "pinn_pw_set: point weights are not combined with coefficient fields; remove them first (pinn_set_coef_fields with n = 0)");
   if (int rc = pw_check_counts(c, "pinn_pw_set", n_u, n_f, n_b)) return rc;
   for (int64_t j = 0; lam_u && j < n_u; ++j) REQUIRE(std::isfinite(lam_u[j]), "pinn_pw_set: lam_u[%lld] is not finite", (long long)j);
   for (int64_t i = 0; lam_f && i < n_f; ++i) REQUIRE(std::isfinite(lam_f[i]), "pinn_pw_set: lam_f[%lld] is not finite", (long long)i);

@@ -112,4 +112,10 @@ int fused20d_launch_any(const F20dLaunch& a, const AdrRobinArg<double>& k);
 // k.src is not read by this kernel.  Launch only while a source is present.
 int fused20d_launch_any(const F20dLaunch& a, const AdrSrcArg<double>& k);
 
+// one evaluation of the adr kind with per-point coefficient fields (k_var20d<PDE_ADR_VAR, H, .>, kernels_generic.h
+// AdrVarArg): the same set; k.kf is the table of a.sd.n_f rows of six doubles, 16-byte aligned, row i for collocation point
+// 2 n_b + n_u + i; the collocation slots of a.tgt hold s_i or zeros; the Robin part of k is as above, k.n may be 0; k.k and
+// k.src are not read by this kernel.  Launch only while fields are present.
+int fused20d_launch_any(const F20dLaunch& a, const AdrVarArg<double>& k);
+
 }  // namespace pinn

@@ -44,12 +44,13 @@ static int launch_burgers(int pde, const F20dLaunch& a, const f20d_nu_t<SETS>& n
 int fused20d_launch_any(int pde, const F20dLaunch& a, double nu) { return launch_burgers<false, false>(pde, a, nu); }
 int fused20d_ens_launch_any(int pde, const F20dLaunch& a, double nu) { return launch_burgers<true, false>(pde, a, nu); }
 int fused20d_ens_launch_any(int pde, const F20dLaunch& a, const double* nu_k) { return launch_burgers<true, true>(pde, a, nu_k); }
-// solo launches only: the weighted loss of pde 0, the adr kind, its trainable coefficients, its per-point weights, its Robin points, its source term
+// solo launches only: the weighted loss of pde 0, the adr kind, its trainable coefficients, its per-point weights, its Robin points, its source term, its coefficient fields
 int fused20d_launch_any(const F20dLaunch& a, const SaArgs& sa) { return launch_depth<0, false, false, true>(a, sa); }
 int fused20d_launch_any(const F20dLaunch& a, const AdrCoef<double>& k) { return launch_depth<PDE_ADR, false, false, false>(a, k); }
 int fused20d_launch_any(const F20dLaunch& a, const AdrIdeArg& k) { return launch_depth<PDE_ADR_IDE, false, false, false>(a, k); }
 int fused20d_launch_any(const F20dLaunch& a, const AdrPwArgs& k) { return launch_depth<PDE_ADR, false, false, true>(a, k); }
 int fused20d_launch_any(const F20dLaunch& a, const AdrRobinArg<double>& k) { return launch_depth<PDE_ADR_ROBIN, false, false, false>(a, k); }
 int fused20d_launch_any(const F20dLaunch& a, const AdrSrcArg<double>& k) { return launch_depth<PDE_ADR_SRC, false, false, false>(a, k); }
+int fused20d_launch_any(const F20dLaunch& a, const AdrVarArg<double>& k) { return launch_depth<PDE_ADR_VAR, false, false, false>(a, k); }
 
 }  // namespace pinn

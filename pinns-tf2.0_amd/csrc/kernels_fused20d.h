@@ -243,8 +243,15 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
 // text -- the slot carries AdrSrcArg<double>, the Robin count may be 0 -- with one more operation in the collocation class:
 // f is formed as PDE_ADR forms it, then s_i = tgt[pt] is subtracted, uncontracted (a zero source gives PDE_ADR's bits).  The
 // value is loaded at the seed block.  No seed formula changes.
+// PDE == PDE_ADR_VAR (PDE_ADR with per-point coefficient fields, kernels_generic.h; instantiated under the name k_var20d):
+// PDE_ADR_SRC's text -- the slot carries AdrVarArg<double>, the Robin count may be 0, the collocation slots of tgt are zero
+// without a source -- with one change in the collocation class: the six coefficients are the point's own row of the table,
+// kf + 6 (pt - 2 n_b - n_u), three 16-byte loads issued at the seed block inside the collocation branch (the table has n_f
+// rows; no other lane touches it).  Residual, source subtraction and the four seeds keep their expressions, so a table of
+// constant rows gives PDE_ADR_SRC's bits.  1 / n_b, the Robin triple and the pair exchange are untouched.  Tile loop: the
+// table's address is held in vector registers, as the (alpha, beta) array's is.
 template <bool SETS, bool SAW = false, int PDE = 0>
-using f20d_nu_t = typename std::conditional<PDE == PDE_ADR_SRC, AdrSrcArg<double>, typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<double>, typename std::conditional<PDE == PDE_ADR && SAW, AdrPwArgs, typename std::conditional<PDE == PDE_ADR, AdrCoef<double>, typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type>::type>::type>::type>::type>::type;
+using f20d_nu_t = typename std::conditional<PDE == PDE_ADR_VAR, AdrVarArg<double>, typename std::conditional<PDE == PDE_ADR_SRC, AdrSrcArg<double>, typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<double>, typename std::conditional<PDE == PDE_ADR && SAW, AdrPwArgs, typename std::conditional<PDE == PDE_ADR, AdrCoef<double>, typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type>::type>::type>::type>::type>::type>::type;
 __device__ __forceinline__ double f20d_nu(double nu) { return nu; }
 __device__ __forceinline__ double f20d_nu(const AdrIdeArg&) { return 0.0; }
 __device__ __forceinline__ double f20d_nu(const AdrCoef<double>& k) { return k.nu; }
@@ -264,11 +271,16 @@ __device__ __forceinline__ double f20d_nu(const AdrRobinArg<double>& a) { return
 #define PINN_F20D_KERNEL k_src20d
 #include "kernels_fused20d_kernel.h"
 #undef PINN_F20D_KERNEL
+// and under the name the coefficient-field variants are instantiated with (PDE_ADR_VAR only)
+#define PINN_F20D_KERNEL k_var20d
+#include "kernels_fused20d_kernel.h"
+#undef PINN_F20D_KERNEL
 // kernel <PDE, H, ONE_TILE, ENS, SETS, SAW> by its name in the library
 template <int PDE, int H, bool ONE_TILE, bool ENS, bool SETS, bool SAW>
 constexpr auto f20d_kernel() {
   if constexpr (PDE == PDE_ADR_ROBIN) return &k_robin20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
   else if constexpr (PDE == PDE_ADR_SRC) return &k_src20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
+  else if constexpr (PDE == PDE_ADR_VAR) return &k_var20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
   else return &k_fused20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
 }
 

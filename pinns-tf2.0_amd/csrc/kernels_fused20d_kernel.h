@@ -1,9 +1,9 @@
 // kernels_fused20d_kernel.h -- the body of k_fused20d, included by kernels_fused20d.h once per kernel NAME (PINN_F20D_KERNEL):
-// k_fused20d for every kind and variant but two, k_robin20d for PDE_ADR_ROBIN (the adr kind with Robin points), k_src20d for
-// PDE_ADR_SRC (the adr kind with a source term).  The text is
+// k_fused20d for every kind and variant but three, k_robin20d for PDE_ADR_ROBIN (the adr kind with Robin points), k_src20d for
+// PDE_ADR_SRC (the adr kind with a source term), k_var20d for PDE_ADR_VAR (the adr kind with coefficient fields).  The text is
 // one, so an instantiation of any name is what a single template gives; the other names exist because the set of
-// k_fused20d<...> instantiations in the library is pinned (tests/test_isa_hazards.py counts them) and the Robin and source
-// variants are additions beside it.  (Not a __device__ body called from two kernels: such a wrapper changed the schedule of the
+// k_fused20d<...> instantiations in the library is pinned (tests/test_isa_hazards.py counts them) and the Robin, source and
+// coefficient-field variants are additions beside it.  (Not a __device__ body called from two kernels: such a wrapper changed the schedule of the
 // existing instantiations.)  No include guard: it is meant to be included more than once.
 template <int PDE, int H, bool ONE_TILE, bool ENS = false, bool SETS = false, bool SAW = false>
 __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict__ th, const double* __restrict__ xs,
@@ -20,6 +20,8 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
                 "Robin points: the fixed-coefficient adr kind only, solo launch, no point weights");
   static_assert(PDE != PDE_ADR_SRC || (!ENS && !SETS && !SAW),
                 "source term: the fixed-coefficient adr kind only, solo launch, no point weights");
+  static_assert(PDE != PDE_ADR_VAR || (!ENS && !SETS && !SAW),
+                "coefficient fields: the adr kind only, solo launch, no point weights (no SAW)");
   // weight offsets: compile-time constants in the one-tile variant (immediate operands; Adam step 41.9 -> 40.8 us with
   // the preloaded pointers); the tile-loop variant keeps them in SGPRs -- with immediates its schedule came out 9 %
   // slower (N_f = 10^6: 2104 vs 1930 us per step, same box)
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       adr_park[5] = nu.r3; adr_park[6] = sd.inv_nb;
     }
   }
-  // PDE_ADR_ROBIN and PDE_ADR_SRC, tile loop: the same seven and the Robin block's first point, length and 1 / N_w; the (alpha, beta) array's
+  // PDE_ADR_ROBIN, PDE_ADR_SRC and PDE_ADR_VAR, tile loop: the same seven and the Robin block's first point, length and 1 / N_w; the (alpha, beta) array's
   // address in vector registers (an opaque move), as SAW holds its array's
   const double* rb_ab = nullptr;
   if constexpr (pde_adr_robin(PDE)) {
@@ -126,6 +128,14 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
     }
   }
   (void)rb_ab;
+  // PDE_ADR_VAR: the coefficient table's address; tile loop: in vector registers too (the src variants sit at 104 of the 106
+  // scalar registers)
+  const double* kf_tab = nullptr;
+  if constexpr (PDE == PDE_ADR_VAR) {
+    kf_tab = nu.kf;
+    if constexpr (!ONE_TILE) asm volatile("" : "+v"(kf_tab));
+  }
+  (void)kf_tab;
   if constexpr (PDE == PDE_ADR_IDE) {
     adr_park = lacc_all + wave * 256 + 192;
     if ((tid & 63) == 0) {
@@ -493,14 +503,14 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
           sa_row[2] = vi;
         }
       }
-    } else if constexpr (pde_adr_fixed(PDE)) {
+    } else if constexpr (pde_adr_seed_block(PDE)) {
       // (the weighted block above is this block's twin, seed for seed: a change to the seeds here belongs there too)
       // partner of a boundary pair: pt ^ 1 is lane ^ 1 (pt = tile * 64 + wave * 16 + q), same slot.  The moves are
       // unconditional (no divergent branch around a cross-lane move); their results count in the boundary class only.
       const double pu = dpp_mov<DPP_QUAD_XOR1>(o[0]), pp = dpp_mov<DPP_QUAD_XOR1>(o[1]);
       AdrCoef<double> kc;
       double inv_nb;
-      int rb_j = -1, rb_n = 0;               // PDE_ADR_ROBIN, PDE_ADR_SRC: this point's place in the Robin block, the block's length
+      int rb_j = -1, rb_n = 0;               // PDE_ADR_ROBIN, _SRC, _VAR: this point's place in the Robin block, the block's length
       double inv_nw = 0.0;
       if constexpr (ONE_TILE) {
         if constexpr (pde_adr_robin(PDE)) { kc = nu.k; rb_j = pt - nu.first; rb_n = nu.n; inv_nw = nu.inv_nw; }
@@ -516,9 +526,18 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       (void)rb_j; (void)rb_n; (void)inv_nw;
       const int cls = point_class_adr(sd, pt);
       if (cls == CLS_COL) {
+        if constexpr (PDE == PDE_ADR_VAR) {
+          // the point's own six coefficients: row pt - 2 n_b - n_u of the table, three 16-byte loads issued here (the one-tile
+          // adr variants have no vector registers to hold six doubles across the forward sweep).  Inside this branch only:
+          // the table has n_f rows, no other lane may touch it.  The constants read above are dead in this variant.
+          typedef double d2 __attribute__((ext_vector_type(2)));
+          const d2* const kr = reinterpret_cast<const d2*>(kf_tab + 6 * (size_t)(pt - 2 * sd.n_b - sd.n_u));
+          const d2 k01 = kr[0], k23 = kr[1], k45 = kr[2];
+          kc = AdrCoef<double>{k01.x, k01.y, k23.x, k23.y, k45.x, k45.y};
+        }
         const double u = o[0], adv = kc.a0 + kc.a1 * u;
         double f = o[2] + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
-        if constexpr (PDE == PDE_ADR_SRC) {
+        if constexpr (pde_adr_src(PDE)) {
           // minus the source s_i = tgt[pt], loaded here (the one-tile adr variants have no vector registers to hold it across
           // the forward sweep) and subtracted as an operation of its own: a zero source gives PDE_ADR's bits
 #pragma clang fp contract(off)
@@ -880,9 +899,9 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
     } else
     if (tid < 4) {
       const double v = ((scal[tid] + scal[4 + tid]) + scal[8 + tid]) + scal[12 + tid];
-      if (tid == 0) { row[nd.n_theta + 0] = v; if (!pde_adr_fixed(PDE)) row[nd.n_theta + 2] = 0.0; }
+      if (tid == 0) { row[nd.n_theta + 0] = v; if (!pde_adr_seed_block(PDE)) row[nd.n_theta + 2] = 0.0; }
       if (tid == 1) row[nd.n_theta + 1] = v;
-      if (pde_adr_fixed(PDE) && tid == 2) row[nd.n_theta + 2] = v;     // the periodic pairs' part (+ the Robin part)
+      if (pde_adr_seed_block(PDE) && tid == 2) row[nd.n_theta + 2] = v;     // the periodic pairs' part (+ the Robin part)
       if (PDE == 1 && tid == 2) row[nd.n_net] = v;
       if (PDE == 1 && tid == 3) row[nd.n_net + 1] = v;
     }

@@ -68,11 +68,29 @@ constexpr int PDE_ADR_ROBIN = 5;
 // no second family.  The subtraction is an operation of its own, never contracted into f: a zero source gives PDE_ADR's bits.
 // The engine dispatches here only while a source is present.
 constexpr int PDE_ADR_SRC = 6;
-constexpr bool pde_is_adr(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_IDE || PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC; }
-// the kinds whose six coefficients are run-time constants (PDE_ADR_IDE reads them from the weight vector)
+// Template number of PINN_PDE_ADR with per-point coefficient fields present (pinn_set_coef_fields): local collocation point i
+// has a row of its own, K_i = (a0, a1, nu, r1, r2, r3)_i, and
+//   f_i = u_t + (a0_i + a1_i u) u_x - nu_i u_xx + r1_i u + r2_i u^2 + r3_i u^3 - s_i;
+// the seeds are PDE_ADR's with K_i where the constants stand.  The table is dense, [n_f][6] in the compute dtype, indexed by
+// the point's place in the collocation block (point - 2 n_b - n_u): only a collocation point may read it.  A superset of
+// PDE_ADR_SRC -- AdrVarArg is AdrSrcArg and the table's address; the Robin count may be 0 and the collocation slots of tgt are
+// zero without a source -- so one family serves fields with or without Robin walls, with or without a source.  The
+// expressions are PDE_ADR_SRC's, only the origin of the six operands differs: a table whose every row is the constant set
+// gives PDE_ADR_SRC's (and, with no source, PDE_ADR's) bits.  The engine dispatches here only while fields are present.
+constexpr int PDE_ADR_VAR = 7;
+constexpr bool pde_is_adr(int PDE) {
+  return PDE == PDE_ADR || PDE == PDE_ADR_IDE || PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR;
+}
+// the kinds whose six coefficients are run-time constants (PDE_ADR_IDE reads them from the weight vector, PDE_ADR_VAR from
+// its table): the predicate keeps this meaning, and PDE_ADR_VAR is not among them
 constexpr bool pde_adr_fixed(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC; }
+// the kinds that share k_fused20d's seed block and loss-row layout of PDE_ADR: the fixed ones and PDE_ADR_VAR, whose block
+// differs in where a collocation point's six coefficients come from and in nothing else
+constexpr bool pde_adr_seed_block(int PDE) { return pde_adr_fixed(PDE) || PDE == PDE_ADR_VAR; }
 // the kinds that carry a Robin block behind the collocation block
-constexpr bool pde_adr_robin(int PDE) { return PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC; }
+constexpr bool pde_adr_robin(int PDE) { return PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR; }
+// the kinds that subtract s_i = tgt[point] at a collocation point
+constexpr bool pde_adr_src(int PDE) { return PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR; }
 // trailing equation parameters of the weight vector: 2 lambdas (PDE 1), six coefficients (PDE_ADR_IDE)
 constexpr int pde_n_tail(int PDE) { return PDE == 1 ? 2 : PDE == PDE_ADR_IDE ? 6 : 0; }
 template <typename real> struct AdrCoef { real a0, a1, nu, r1, r2, r3; };
@@ -88,9 +106,20 @@ template <typename real> struct AdrRobinArg {
 template <typename real> struct AdrSrcArg : AdrRobinArg<real> {
   const real* src;
 };
+// PDE_ADR_VAR: AdrSrcArg's content (src is the set's tgt, zero in the collocation block without a source) and the
+// coefficient table, kf[6 * i + j] = coefficient j of local collocation point i; 16-byte aligned.  The constants k are not
+// read at a collocation point.  kf is touched by collocation points only: the table has n_f rows.
+template <typename real> struct AdrVarArg : AdrSrcArg<real> {
+  const real* kf;
+};
+// row i of the table (every load inside the caller's collocation branch)
+template <typename real> __device__ __forceinline__ AdrCoef<real> adr_row(const real* __restrict__ kf, int i) {
+  const real* __restrict__ r = kf + (size_t)6 * i;
+  return AdrCoef<real>{r[0], r[1], r[2], r[3], r[4], r[5]};
+}
 template <typename real, int PDE>
-using pde_coef_t = typename std::conditional<PDE == PDE_ADR_SRC, AdrSrcArg<real>, typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<real>, typename std::conditional<PDE == PDE_ADR, AdrCoef<real>,
-                                             typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, real>::type>::type>::type>::type;
+using pde_coef_t = typename std::conditional<PDE == PDE_ADR_VAR, AdrVarArg<real>, typename std::conditional<PDE == PDE_ADR_SRC, AdrSrcArg<real>, typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<real>, typename std::conditional<PDE == PDE_ADR, AdrCoef<real>,
+                                             typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, real>::type>::type>::type>::type>::type;
 template <typename real> __device__ __forceinline__ real coef_nu(real nu) { return nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrCoef<real>& k) { return k.nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrIdeArg&) { return real(0); }
@@ -222,23 +251,23 @@ __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_
                                                 const real* __restrict__ tgt, real c1, real c2,
                                                 vec4<real> sb[2], real lt[3], real dl[2],
                                                 const AdrCoef<real>& k = AdrCoef<real>{0, 0, 0, 0, 0, 0},
-                                                const AdrRobinArg<real>* rb = nullptr);
+                                                const AdrRobinArg<real>* rb = nullptr, const real* __restrict__ kf = nullptr);
 template <typename real, int PDE>
 __device__ __forceinline__ void point_seeds(const SetDesc& sd, int g, int n_pad,
                                             const vec4<real>* __restrict__ O,
                                             const real* __restrict__ tgt, real c1, real c2,
                                             vec4<real> sb[2], real lt[3], real dl[2],
                                             const AdrCoef<real>& k = AdrCoef<real>{0, 0, 0, 0, 0, 0},
-                                            const AdrRobinArg<real>* rb = nullptr) {
+                                            const AdrRobinArg<real>* rb = nullptr, const real* __restrict__ kf = nullptr) {
   const vec4<real> ou = O[g], ov = PDE == 2 ? O[(size_t)n_pad + g] : vec4<real>{0, 0, 0, 0};
-  point_seeds_own<real, PDE>(sd, g, n_pad, ou, ov, O, tgt, c1, c2, sb, lt, dl, k, rb);
+  point_seeds_own<real, PDE>(sd, g, n_pad, ou, ov, O, tgt, c1, c2, sb, lt, dl, k, rb, kf);
 }
 template <typename real, int PDE>
 __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_pad, const vec4<real>& ou,
                                                 const vec4<real>& ov, const vec4<real>* __restrict__ O,
                                                 const real* __restrict__ tgt, real c1, real c2,
-                                                vec4<real> sb[2], real lt[3], real dl[2], const AdrCoef<real>& k,
-                                                const AdrRobinArg<real>* rb) {
+                                                vec4<real> sb[2], real lt[3], real dl[2], const AdrCoef<real>& k_arg,
+                                                const AdrRobinArg<real>* rb, const real* __restrict__ kf) {
   const int cls = pde_is_adr(PDE) ? point_class_adr(sd, g) : point_class(sd, g);
   sb[0] = sb[1] = vec4<real>{0, 0, 0, 0};
   lt[0] = lt[1] = lt[2] = real(0);
@@ -259,9 +288,11 @@ __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_
   if constexpr (pde_is_adr(PDE)) {   // advection-diffusion-reaction, run-time coefficients, periodic pairs (g, g ^ 1)
     const vec4<real> o = ou;
     if (cls == CLS_COL) {
+      // PDE_ADR_VAR: the point's own row of the table (kf), read here and nowhere else -- the table ends with the block
+      const AdrCoef<real> k = PDE == PDE_ADR_VAR ? adr_row<real>(kf, g - 2 * sd.n_b - sd.n_u) : k_arg;
       const real u = o.x, adv = k.a0 + k.a1 * u;
       real f = adr_residual(k, o);
-      if constexpr (PDE == PDE_ADR_SRC) {      // minus the source, an operation of its own (s = 0: PDE_ADR's bits)
+      if constexpr (pde_adr_src(PDE)) {        // minus the source, an operation of its own (s = 0: PDE_ADR's bits)
 #pragma clang fp contract(off)
         f = f - tgt[g];
       }
@@ -383,6 +414,7 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
   vec4<real> sb[2];
   real lt[3], dl[PDE == PDE_ADR_IDE ? 6 : 2];
   if constexpr (PDE == PDE_ADR) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr<real>(nu));
+  else if constexpr (PDE == PDE_ADR_VAR) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, nu.k, &nu, nu.kf);
   else if constexpr (pde_adr_robin(PDE)) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, nu.k, &nu);
   else if constexpr (PDE == PDE_ADR_IDE) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr_tail<real>(th + nd.n_net));
   else point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl);
@@ -519,6 +551,13 @@ __global__ void k_residual(int first, int n, int n_pad, const vec4<real>* __rest
   } else if constexpr (PDE == PDE_ADR_SRC) {
     real r = adr_residual(nu.k, O[g]);
     if (nu.src) {
+#pragma clang fp contract(off)
+      r = r - nu.src[g];
+    }
+    f[i] = (double)r;
+  } else if constexpr (PDE == PDE_ADR_VAR) {   // over the set only (first = the collocation block's first point): row i, s by set index
+    real r = adr_residual(adr_row<real>(nu.kf, i), O[g]);
+    {
 #pragma clang fp contract(off)
       r = r - nu.src[g];
     }

@@ -294,6 +294,8 @@ _SIGNATURES = {
     "pinn_robin_residual": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
     # source term of the adr kind (include/pinn_hip.h: pinn_set_source)
     "pinn_set_source": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
+    # coefficient fields of the adr kind (include/pinn_hip.h: pinn_set_coef_fields)
+    "pinn_set_coef_fields": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
 }
 
 
@@ -459,6 +461,7 @@ class Engine(object):
         self.n_params = n.value
         self.n_f = self.n_u = self.n_b = self.n_w = 0
         self._has_source = False
+        self._has_coef_fields = False
 
     def _check(self, rc):
         if rc != 0:
@@ -613,6 +616,34 @@ class Engine(object):
     def has_source(self):
         """a source term is present (set_source), stale or not"""
         return bool(getattr(self, "_has_source", False))
+
+    def set_coef_fields(self, K):
+        """Coefficient fields of the adr kind: row i of K [n_f, 6] holds (a0, a1, nu, r1, r2, r3) of collocation point i (the
+        rows of get_collocation); the constants of set_pde_params are not read while fields are present.  None removes
+        them.  A redraw of the collocation set makes present fields stale: evaluations are refused until set_coef_fields is
+        called again with rows at the new points (get_collocation still works then)."""
+        if K is None:
+            self._check(self._lib.pinn_set_coef_fields(self._h, None, 0))
+            self._has_coef_fields = False
+            return
+        K = _f64(K)
+        if K.ndim != 2 or K.shape[1] != 6:
+            raise ValueError("the coefficient fields must be an [n_f, 6] array (a0, a1, nu, r1, r2, r3 per collocation point), "
+                             "got shape %s" % (K.shape,))
+        K = np.ascontiguousarray(K)
+        if K.shape[0] != self.n_f:
+            raise ValueError("the coefficient fields must hold one row per collocation point (%d), got %d" % (self.n_f, K.shape[0]))
+        if K.shape[0] == 0:
+            raise ValueError("the coefficient fields are empty (None removes them)")
+        if not np.all(np.isfinite(K)):
+            raise ValueError("the coefficient fields must be finite")
+        self._check(self._lib.pinn_set_coef_fields(self._h, _dp(K), K.shape[0]))
+        self._has_coef_fields = True
+
+    @property
+    def has_coef_fields(self):
+        """coefficient fields are present (set_coef_fields), stale or not"""
+        return bool(getattr(self, "_has_coef_fields", False))
 
     def robin_residual(self):
         """r_j = alpha_j u + beta_j u_x - g_j at the Robin points, current weights -> [n_w]"""

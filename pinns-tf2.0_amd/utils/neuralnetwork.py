@@ -379,6 +379,73 @@ class NeuralNetwork(object):
         else:
             self._engine.set_source(s)
 
+    def _set_coef_fields(self, k):
+        """Coefficient fields of the "adr" kind (Engine.set_coef_fields): collocation point i has its own six coefficients
+        (a0, a1, nu, r1, r2, r3)_i in f = N_K[u] - s.  k is
+          * an array [N_f, 6], one row per collocation point (call _set_collocation first);
+          * a callable taking X [n, 2] = (x, t) and returning [n, 6] -- then every device redraw of the collocation set
+            (hp["resample_every"] > 0, Latin hypercube) is followed by get_collocation() and set_coef_fields(k(X));
+          * a dict with keys among a0, a1, nu, r1, r2, r3, each value an array [N_f] or a callable X -> [n]; the columns not
+            named take the model's constant coefficients (Engine.get_pde_params).  A dict with a callable follows redraws
+            like a callable; its array columns cannot, so they are refused under hp["resample_every"] > 0 as an array is.
+        None removes the fields.  One device; not combined with hp["resample"] = "rad" (the coefficients are not known at
+        the pool's points) or hp["point_weights"]."""
+        if self.pde != "adr":
+            raise ValueError('_set_coef_fields: coefficient fields are for the "adr" kind; the %s model is not supported' % self.pde)
+        if self._resample == "rad":
+            raise ValueError('_set_coef_fields: coefficient fields are not combined with hp["resample"] = "rad" (the '
+                             'coefficients are not known at the adaptive draw\'s pool points)')
+        if self._pw:
+            raise ValueError('_set_coef_fields: coefficient fields are not combined with hp["point_weights"]')
+        if self._dp:
+            raise ValueError('_set_coef_fields: coefficient fields run on one device; a data-parallel launch is not supported')
+        fn = None
+        if isinstance(k, dict):
+            unknown = [n for n in k if n not in ADR_NAMES]
+            if unknown:
+                raise ValueError('_set_coef_fields: unknown coefficient %r; choose from %s' % (unknown[0], ", ".join(ADR_NAMES)))
+            if self._resample_every > 0 and any(not callable(v) for v in k.values()):
+                raise ValueError('_set_coef_fields: an array cannot follow the redraws of the collocation set '
+                                 '(hp["resample_every"] > 0); pass callables X -> [n] for the columns that vary')
+            cols = dict(k)
+
+            def fn(X):
+                K = np.tile(np.asarray(self._engine.get_pde_params(), dtype=np.float64).reshape(1, 6), (X.shape[0], 1))
+                for name, v in cols.items():
+                    col = np.asarray(v(X) if callable(v) else v, dtype=np.float64).reshape(-1)
+                    if col.size != X.shape[0]:
+                        raise ValueError('_set_coef_fields: column %r must hold one value per collocation point (%d), got %d'
+                                         % (name, X.shape[0], col.size))
+                    K[:, ADR_NAMES.index(name)] = col
+                return K
+            follows = any(callable(v) for v in cols.values())
+        elif callable(k):
+            fn, follows = k, True
+        else:
+            follows = False
+            if k is not None and self._resample_every > 0:
+                raise ValueError('_set_coef_fields: an array cannot follow the redraws of the collocation set '
+                                 '(hp["resample_every"] > 0); pass a callable k(X)')
+        self._coef_fields_fn = fn if follows else None
+        if k is None:
+            self._engine.set_coef_fields(None)
+        elif fn is not None:
+            self._engine.set_coef_fields(np.asarray(fn(self._engine.get_collocation()), dtype=np.float64))
+        else:
+            self._engine.set_coef_fields(k)
+
+    def _follow_redraw(self):
+        """after a device redraw of the collocation set: the source and the coefficient fields that were given as callables,
+        at the new points (_set_source, _set_coef_fields)"""
+        s_fn, k_fn = getattr(self, "_source_fn", None), getattr(self, "_coef_fields_fn", None)
+        if s_fn is None and k_fn is None:
+            return
+        X_new = self._engine.get_collocation()
+        if s_fn is not None:
+            self._engine.set_source(np.asarray(s_fn(X_new), dtype=np.float64).reshape(-1))
+        if k_fn is not None:
+            self._engine.set_coef_fields(np.asarray(k_fn(X_new), dtype=np.float64))
+
     def _residual_collocation(self):
         """f at ALL collocation points [N_f, n_out], on every rank (a shard holds only its block: the replicated
         weights are evaluated at the full set instead)"""
@@ -538,9 +605,7 @@ class NeuralNetwork(object):
                                                  c=self._rad_c, first=lo, count=hi - lo)
                 else:
                     self._engine.lhs_collocation(n_design, self._resample_seed + epoch, first=lo, count=hi - lo)
-                    if getattr(self, "_source_fn", None) is not None:      # the source at the new points (_set_source)
-                        X_new = self._engine.get_collocation()
-                        self._engine.set_source(np.asarray(self._source_fn(X_new), dtype=np.float64).reshape(-1))
+                    self._follow_redraw()      # the source and the coefficient fields at the new points
                 self._X_f = None
             # run up to and including the next epoch that is logged, then sync once
             stop = min(self.tf_epochs, (epoch + freq - 1) // freq * freq + 1)

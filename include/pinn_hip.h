@@ -265,6 +265,17 @@ int pinn_sync(pinn_ctx* c);
  * picks the fastest eligible family at pinn_create. */
 int pinn_set_kernel_path(pinn_ctx* c, int path);
 int pinn_get_kernel_path(pinn_ctx* c, int* path);
+/* Launch plan of kernel path 7 in float64: *split = 1 when the next evaluation takes the split one-tile launch, 0 otherwise.
+ * Split launch: beside the main workgroup of every 64-point tile, helper workgroups (one per pair of tiles) on compute units
+ * the launch would leave idle recompute the tile's forward sweep and write the weight-gradient columns of the last hidden
+ * and the output layer into the tile's gradient row; the main workgroup leaves those blocks out.  No workgroup waits for
+ * another; loss, gradient and every later bit are those of the plain launch.  It serves a solo context of the Burgers kinds
+ * (pde 0, 1) without self-adaptive weights when every tile has a workgroup of its own and
+ * tiles + ceil(tiles / 2) <= compute units; ensembles, the adr kinds and every other path never split (the kernel path
+ * reported stays 7).  Environment PINN_F64_SPLIT, read by pinn_create: "auto" (default), "0" = never, "1" = required --
+ * an evaluation, and this call, fail with PINN_EUNSUPPORTED where the kernel exists for the context but the tile count does
+ * not fit; any other value fails pinn_create.  Assembles the point sets if they changed.  (Additive: the ABI version stays 6.) */
+int pinn_get_f64_split(pinn_ctx* c, int* split);
 /* Profiling build (-DPINN_STAMPS) only: one evaluation with a per-wave s_memtime timeline of the
  * fused kernel; out[wave][32] ticks, n_waves = 4 x workgroups.  PINN_EUNSUPPORTED otherwise. */
 int pinn_debug_stamps(pinn_ctx* c, long long* out, int64_t cap, int64_t* n_waves);

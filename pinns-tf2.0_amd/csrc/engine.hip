@@ -158,6 +158,7 @@ struct pinn_ctx {
   float* img = nullptr;              // LDS weight image of k_fused20m (f32 only)
   int* row_index = nullptr;          // k_fused20d: entry of a wave's gradient block list -> flat parameter index
   int n_cu = 256, n_wg = 0;          // compute units; workgroups of the persistent kernel
+  int f64_split = -1;                // PINN_F64_SPLIT, read by pinn_create: -1 auto, 0 never, 1 required (split_plan)
   // device: scratch
   void *S = nullptr, *O = nullptr, *ZA = nullptr, *ZB = nullptr, *part = nullptr;
   size_t cap_S = 0, cap_O = 0, cap_Z = 0, cap_part = 0, cap_pts = 0;
@@ -900,6 +901,20 @@ static F20dLaunch fused20d_args(const pinn_ctx* c, hipEvent_t* ev4) {
                     c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr};
 }
 
+// Whether the next evaluation of c takes the split one-tile launch of path 7 (k_split20d, fused20d_api.h): 1 yes, 0 no,
+// -1 PINN_F64_SPLIT=1 asks for it where the kernel exists but the tile count does not fit.  The kernel exists for a solo
+// float64 context of the Burgers kinds on path 7 without point weights (ensembles launch through ens_eval, which never
+// splits); the tile count fits when every tile has a workgroup of its own and the helpers -- one per pair of tiles -- find
+// compute units beside them.  Needs c->sd and c->n_wg (ensure_sets).
+static int split_plan(const pinn_ctx* c) {
+  if (!fused20d_split_built() || c->f64_split == 0) return 0;
+  if (c->path != KP_FUSED20D || c->dtype != PINN_F64 || !c->own_stream) return 0;
+  if ((c->pde != PINN_PDE_BURGERS && c->pde != PINN_PDE_BURGERS_IDE) || c->sa.on || c->pw.on) return 0;
+  const int n_tiles = c->sd.n_pad / 64;
+  const bool fits = n_tiles > 0 && c->n_wg >= n_tiles && fused20d_split_grid(n_tiles) <= c->n_cu;
+  return fits ? 1 : c->f64_split == 1 ? -1 : 0;
+}
+
 // KP_FUSED20D: the plain, the weighted (self-adaptive) or the adr evaluation, one launch
 template <typename real, int PDE>
 static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
@@ -909,7 +924,14 @@ static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
     if (weighted) { if (int e = lam_prepare(c, c->sa.arr, sa_layout(c))) return e; }
     const bool pw = PDE == PDE_ADR && c->pw.on;      // the adr kind's point weights; an Adam step moves them too
     if (pw) { if (int e = lam_prepare(c, c->pw.arr, pw_layout(c))) return e; }
-    const F20dLaunch a = fused20d_args(c, ev4);
+    F20dLaunch a = fused20d_args(c, ev4);
+    if constexpr (PDE == 0 || PDE == 1) {
+      const int sp = split_plan(c);
+      if (sp < 0)
+        return fail(PINN_EUNSUPPORTED, "PINN_F64_SPLIT=1: %d tiles need %d workgroups, this device has %d compute units",
+                    c->sd.n_pad / 64, fused20d_split_grid(c->sd.n_pad / 64), c->n_cu);
+      a.split = sp == 1;
+    }
     if constexpr (PDE == PDE_ADR) {
       if (pw) rc = fused20d_launch_any(a, AdrPwArgs{pde_coef<double, PDE_ADR>(c), c->pw.arr.buf, af ? af->bc_pw : 0.0});
       else rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR>(c));
@@ -1658,6 +1680,12 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   if (e != hipSuccess) { delete c; return fail(PINN_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
   // debug knobs of k_t16_fused's boundary hand-over (tests/test_gpu_parity.py): force the pre-pass / shorten the wait
   // (a value that does not parse is an error, not a silent 0: zero ticks would make every hand-over expire at once)
+  // the split one-tile launch of path 7 (split_plan): auto (default), 0 = never, 1 = required where the kernel exists
+  if (const char* v = getenv("PINN_F64_SPLIT")) {
+    if (!strcmp(v, "0")) c->f64_split = 0;
+    else if (!strcmp(v, "1")) c->f64_split = 1;
+    else if (strcmp(v, "auto")) { delete c; return fail(PINN_EINVAL, "PINN_F64_SPLIT must be auto, 0 or 1 (got \"%s\")", v); }
+  }
   if (const char* v = getenv("PINN_T16_PREPASS")) {
     if (!(v[0] == '0' || v[0] == '1') || v[1]) { delete c; return fail(PINN_EINVAL, "PINN_T16_PREPASS must be 0 or 1 (got \"%s\")", v); }
     c->t16_prepass = v[0] == '1';
@@ -2921,7 +2949,9 @@ int pinn_debug_stamps(pinn_ctx* c, long long* out, int64_t cap, int64_t* n_waves
   HIPCHK(hipSetDevice(c->device));
   int rc = ensure_sets(c);
   if (rc) return rc;
-  const size_t n = (size_t)path_rows(c) * 4 * 32;
+  // (a split launch of path 7 has helper workgroups behind the rows' own: their stamps follow)
+  const int n_wgs = split_plan(c) == 1 ? fused20d_split_grid(c->sd.n_pad / 64) : path_rows(c);
+  const size_t n = (size_t)n_wgs * 4 * 32;
   REQUIRE((size_t)cap >= n, "stamp buffer too small: need %zu", n);
   if (dev_alloc(&c->stamps, n * 8)) return PINN_EHIP;
   HIPCHK(hipMemsetAsync(c->stamps, 0, n * 8, c->stream));
@@ -2977,6 +3007,18 @@ int pinn_debug_t16f_stamps(long long* out512) {
 int pinn_get_kernel_path(pinn_ctx* c, int* path) {
   REQUIRE(c && path, "null");
   *path = c->path;
+  return 0;
+}
+
+int pinn_get_f64_split(pinn_ctx* c, int* split) {
+  REQUIRE(c && split, "null");
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = ensure_sets(c)) return rc;
+  const int sp = split_plan(c);
+  if (sp < 0)
+    return fail(PINN_EUNSUPPORTED, "PINN_F64_SPLIT=1: %d tiles need %d workgroups, this device has %d compute units",
+                c->sd.n_pad / 64, fused20d_split_grid(c->sd.n_pad / 64), c->n_cu);
+  *split = sp;
   return 0;
 }
 

@@ -35,6 +35,42 @@ inline size_t fused20d_lds_bytes(int n_hidden, int n_theta) {
 void fused20d_row_index(const NetDesc& nd, int H, int* out);
 
 inline bool fused20d_depth_ok(int n_hidden) { return n_hidden == 4 || n_hidden == 6 || n_hidden == 8; }
+
+// The split one-tile launch (k_split20d, kernels_fused20d_kernel.h): beside the main workgroup of every tile, helper
+// workgroups on compute units the launch would leave idle recompute a tile's forward sweep and seeds -- same inputs, same
+// instructions, same bits -- and write the weight-gradient columns of the top of the reverse sweep into the tile's gradient
+// row; the main workgroup leaves those blocks out.  A helper serves two tiles, one after the other.  No workgroup waits for
+// another or reads what another wrote: rows, reduction and every bit downstream are those of the plain launch.
+// Who writes column idx of a gradient row of n_theta + F20D_LOSS_SLOTS doubles: the helper owns the last hidden layer's
+// kernel and bias and the output layer's, one contiguous range; the main workgroup owns the layers below, the equation's
+// trailing parameters and the loss parts.  Both roles take their store predicates from here (PINN_ROLE_OWNS).
+enum { F20D_MAIN = 0, F20D_HELPER = 1 };
+constexpr int F20D_LOSS_SLOTS = 4;
+constexpr int F20D_WIDTH = 20;         // == FW (kernels_fused20.h, checked in kernels_fused20d.h)
+constexpr int f20d_layer_first(int d) { return d == 0 ? 0 : 3 * F20D_WIDTH + (d - 1) * (F20D_WIDTH + 1) * F20D_WIDTH; }   // layer d's kernel
+constexpr int f20d_n_net(int H) { return f20d_layer_first(H) + F20D_WIDTH + 1; }
+constexpr int f20d_split_owner(int idx, int H, int n_tail) {
+  (void)n_tail;                        // (the trailing parameters stand behind the net: the main role's, like the loss parts)
+  return idx >= f20d_layer_first(H - 1) && idx < f20d_n_net(H) ? F20D_HELPER : F20D_MAIN;
+}
+// every column has one owner (the function is total), the helper's columns are exactly layers H - 1 and H, and neither set
+// is empty: what k_split20d static_asserts for every (PDE, H) it is instantiated with
+constexpr bool f20d_split_ok(int H, int n_tail) {
+  const int n = f20d_n_net(H) + n_tail + F20D_LOSS_SLOTS;
+  int n_main = 0, n_helper = 0;
+  for (int i = 0; i < n; ++i) {
+    const int o = f20d_split_owner(i, H, n_tail);
+    if (o != F20D_MAIN && o != F20D_HELPER) return false;
+    const bool top = i >= f20d_layer_first(H - 1) && i < f20d_n_net(H);
+    if ((o == F20D_HELPER) != top) return false;
+    (o == F20D_HELPER ? n_helper : n_main) += 1;
+  }
+  return H >= 3 && n_main + n_helper == n && n_helper == (F20D_WIDTH + 1) * F20D_WIDTH + F20D_WIDTH + 1 && n_main > 0;
+}
+// workgroups of a split launch over n_tiles tiles: one main workgroup per tile, one helper per pair of tiles
+constexpr int fused20d_split_grid(int n_tiles) { return n_tiles + (n_tiles + 1) / 2; }
+// whether this build holds k_split20d (the folded phase sums of -DPINN_ONETILE_SUM=1, 2 are profiling builds without it)
+constexpr bool fused20d_split_built() { return PINN_ONETILE_SUM == 0; }
 // Launch plan of path 7: 64-point tiles, persistent over n_wg = min(tiles, CUs) workgroups = partial gradient rows.
 
 // what every launch of k_fused20d takes besides its coefficient argument
@@ -50,6 +86,7 @@ struct F20dLaunch {
   hipStream_t stream;
   long long* stamps;             // -DPINN_STAMPS builds: the waves' clock stamps (nullptr: none)
   hipEvent_t ev_start, ev_stop;  // both set: attached to the launch itself
+  bool split = false;            // the split one-tile plan (pde 0 and 1, solo, n_wg >= tiles, fused20d_split_built() only)
 };
 
 // one loss+gradient evaluation, 4, 6 or 8 hidden layers; every entry point returns a hipError_t

@@ -260,6 +260,10 @@ __device__ __forceinline__ double f20d_nu(const SaArgs& a) { return a.nu; }
 __device__ __forceinline__ double f20d_nu(const AdrPwArgs& a) { return a.k.nu; }
 __device__ __forceinline__ double f20d_nu(const AdrRobinArg<double>& a) { return a.k.nu; }
 
+static_assert(F20D_WIDTH == FW && f20d_layer_first(1) == w20_desc(8, 0).off_w[1] && f20d_layer_first(7) == w20_desc(8, 2).off_w[7] &&
+              f20d_layer_first(4) == w20_desc(4, 0).off_w[4] && f20d_n_net(6) == w20_desc(6, 2).n_net,
+              "fused20d_api.h's layer offsets are the flat layout's");
+#define PINN_F20D_SPLIT 0
 #define PINN_F20D_KERNEL k_fused20d
 #include "kernels_fused20d_kernel.h"
 #undef PINN_F20D_KERNEL
@@ -275,6 +279,15 @@ __device__ __forceinline__ double f20d_nu(const AdrRobinArg<double>& a) { return
 #define PINN_F20D_KERNEL k_var20d
 #include "kernels_fused20d_kernel.h"
 #undef PINN_F20D_KERNEL
+#undef PINN_F20D_SPLIT
+// and, with the two roles compiled in, under the name of the split one-tile launch (pde 0 and 1, ONE_TILE, solo)
+#if PINN_ONETILE_SUM == 0
+#define PINN_F20D_SPLIT 1
+#define PINN_F20D_KERNEL k_split20d
+#include "kernels_fused20d_kernel.h"
+#undef PINN_F20D_KERNEL
+#undef PINN_F20D_SPLIT
+#endif
 // kernel <PDE, H, ONE_TILE, ENS, SETS, SAW> by its name in the library
 template <int PDE, int H, bool ONE_TILE, bool ENS, bool SETS, bool SAW>
 constexpr auto f20d_kernel() {
@@ -302,6 +315,29 @@ inline int fused20d_launch(const F20dLaunch& a, const f20d_nu_t<SETS, SAW, PDE>&
     if (e != hipSuccess) return (int)e;
   }
   const int n_tiles = a.sd.n_pad / 64;
+  if (a.split) {
+    // one main workgroup per tile and one helper per pair of tiles; the rows, R and n_wg are the plain launch's
+    if constexpr (fused20d_split_built() && (PDE == 0 || PDE == 1) && !ENS && !SETS && !SAW) {
+#if PINN_ONETILE_SUM == 0
+      if (a.n_wg < n_tiles) return (int)hipErrorInvalidValue;
+      auto* const ks = &k_split20d<PDE, H, true, false, false, false>;
+      static unsigned long long split_attr_set = 0;
+      if (first_call_on_device(split_attr_set)) {
+        const hipError_t e = hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+      }
+      const dim3 grid(fused20d_split_grid(n_tiles));
+      if (a.ev_start && a.ev_stop)
+        hipExtLaunchKernelGGL(ks, grid, dim3(256), lds, a.stream, a.ev_start, a.ev_stop, 0, a.th, a.xs, a.ts, a.tgt, a.part,
+                              a.row_index, a.R, n_tiles, a.lbx, a.lbt, a.sx, a.st, nu, a.sd, a.stamps, w20_desc(H, pde_n_tail(PDE)));
+      else
+        hipLaunchKernelGGL(ks, grid, dim3(256), lds, a.stream, a.th, a.xs, a.ts, a.tgt, a.part, a.row_index, a.R, n_tiles,
+                           a.lbx, a.lbt, a.sx, a.st, nu, a.sd, a.stamps, w20_desc(H, pde_n_tail(PDE)));
+      return (int)hipGetLastError();
+#endif
+    }
+    return (int)hipErrorInvalidValue;
+  }
   auto* const kern = a.n_wg >= n_tiles ? f20d_kernel<PDE, H, true, ENS, SETS, SAW>() : f20d_kernel<PDE, H, false, ENS, SETS, SAW>();
   const dim3 grid(a.n_wg, a.n_members);
   if (a.ev_start && a.ev_stop)

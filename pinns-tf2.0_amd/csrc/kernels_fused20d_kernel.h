@@ -5,6 +5,9 @@
 // k_fused20d<...> instantiations in the library is pinned (tests/test_isa_hazards.py counts them) and the Robin, source and
 // coefficient-field variants are additions beside it.  (Not a __device__ body called from two kernels: such a wrapper changed the schedule of the
 // existing instantiations.)  No include guard: it is meant to be included more than once.
+// A fifth inclusion, with PINN_F20D_SPLIT = 1, gives k_split20d: the one-tile kernel of pde 0 and 1 with two roles compiled in
+// (fused20d_api.h: the split launch).  The reverse sweep stands in kernels_fused20d_reverse.h, included below once per role;
+// with PINN_F20D_SPLIT = 0 it is included once, as the whole sweep, and every kernel comes out as it did when the text stood here.
 template <int PDE, int H, bool ONE_TILE, bool ENS = false, bool SETS = false, bool SAW = false>
 __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict__ th, const double* __restrict__ xs,
                                                   const double* __restrict__ ts, const double* __restrict__ tgt,
@@ -67,6 +70,18 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
 
   // first tile's coordinates: issued ahead of the weight staging, so the two round trips overlap
   int tile = blockIdx.x;
+#if PINN_F20D_SPLIT
+  // Two roles, chosen per workgroup (wave-uniform): blocks [0, n_tiles) are the main workgroups of tile blockIdx.x, block
+  // n_tiles + j is a helper that serves tile 2 j and then tile 2 j + 1 (where there is one).  A helper recomputes the tile's
+  // forward sweep and seeds from the kernel's inputs -- the same instructions, hence the same bits -- and writes the columns of
+  // the tile's gradient row that f20d_split_owner (fused20d_api.h) gives it; the main workgroup writes the others.  Neither
+  // waits for the other or reads what it wrote.
+  static_assert(ONE_TILE && !ENS && !SETS && !SAW && (PDE == 0 || PDE == 1) && PINN_ONETILE_SUM == 0,
+                "the split launch: one tile per workgroup, solo, Burgers kinds, unfolded phase sums");
+  static_assert(f20d_split_ok(H, pde_n_tail(PDE)), "every column of a gradient row has exactly one owner");
+  const bool helper = (int)blockIdx.x >= n_tiles;
+  if (helper) tile = 2 * ((int)blockIdx.x - n_tiles);
+#endif
   double x = 0.0, t = 0.0;
   if (tile < n_tiles) { x = xs[tile * 64 + wave * 16 + q]; t = ts[tile * 64 + wave * 16 + q]; }
 
@@ -169,7 +184,14 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
 
   STAMP(1);
 
-  for (; tile < n_tiles; tile += gridDim.x) {
+  for (; tile < n_tiles; tile += PINN_F20D_SPLIT ? 1 : gridDim.x) {
+#if PINN_F20D_SPLIT
+    // the helper's second tile makes this a real loop: the thread index is re-read through an opaque move once per tile, so
+    // that the per-lane addresses derived from it are formed inside the loop, not held (and spilled) across it
+    int tid_tile = threadIdx.x;
+    asm volatile("" : "+v"(tid_tile));
+    const int tid = tid_tile;
+#endif
     PINN_LANE_INDICES(tid & 63);
     auto grad_fetch = [&](const int blk) { return (ONE_TILE || PINN_GACC_ATOMIC) ? 0.0 : gacc[blk * 16 + ge]; };
     // One tile per workgroup: nothing is accumulated, so the four blocks are not folded in registers (2 x 2 DPP moves + 2
@@ -293,7 +315,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
         else if (bl < 30 && i == 0) rel_hidden[k] = FW * FW + 4 * (bl - 25) + j;       // the bias row follows the kernel
       }
     }
-    double* __restrict__ const row1 = part + (size_t)blockIdx.x * R;
+    double* __restrict__ const row1 = part + (size_t)(PINN_F20D_SPLIT ? tile : blockIdx.x) * R;
     // sum of one phase p: all four waves have parked its blocks in the phase's staging area; entry e of the phase = 4 waves x 4
     // blocks in fixed order -> its place in the workgroup's gradient row.  to_index(e) = flat parameter index or -1.
     //   phase_issue   barrier (all four waves have parked the phase) + the 16 reads of this thread's two entries
@@ -638,210 +660,29 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       }
     }
 
-    // ------------------------------------------------------------------ reverse sweep
-    double ob[4][5];                         // adjoint of the outputs of the layer below, own (slot, point)
-    {  // dense H (linear, one output): z_bar = sb.  dW_H[k] = sum IN_c[k] sb_c, db_H = sum sb_h
-      double sbT[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) sbT[c] = PINN_TO_POINTS(s == 0 ? sb[c] : 0.0);     // column 0 only
-      {
-        double D[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, old[6];
-#pragma unroll
-        for (int m = 0; m < 6; ++m) old[m] = grad_fetch(BLK_H + m);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-          for (int m = 0; m < 5; ++m) D[m] = mfma444(PINN_TO_POINTS(in[c][m]), sbT[c], D[m]);
-        }
-        D[5] = mfma444(onesA, sbT[0], 0.0);
-        phase_first = BLK_H;                                   // phase 0 of the reverse sweep: buffer 0
-        stage_w = gacc_all + PINN_PHASE_STAGE(0) + wave * STAGE_WAVE_STRIDE;
-#pragma unroll
-        for (int m = 0; m < 6; ++m) grad_store(D[m], old[m], BLK_H + m);
-        gacc_flush();
-      }
-#pragma unroll
-      for (int n = 0; n < 5; ++n) {
-        const double w = wl[nd.off_w[H] + 4 * n + s];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) ob[c][n] = sb[c] * w;
-      }
+    // ------------------------------------------------------------------ reverse sweep (kernels_fused20d_reverse.h)
+#if PINN_F20D_SPLIT
+    if (helper) {
+#define PINN_F20D_ROLE 2
+#include "kernels_fused20d_reverse.h"
+#undef PINN_F20D_ROLE
+    } else {
+#define PINN_F20D_ROLE 1
+#include "kernels_fused20d_reverse.h"
+#undef PINN_F20D_ROLE
     }
-    STAMP(H + 1);
-#pragma unroll
-    for (int d = H - 1; d >= 1; --d) {
-      // pre-activation adjoints of layer d; their point-major (moved) copies for the weight gradient are made inside the GEMV.
-      // One tile: the barrier and the 16 reads of the previous phase's sum stand in front of the adjoint arithmetic (pure
-      // VALU), which hides their LDS round trip.
-      double zb[4][5], zbT[4][5];
-      if constexpr (ONE_TILE) phase_issue(d == H - 1 ? 6 * 16 : 30 * 16, H - d - 1);
-#pragma unroll
-      for (int n = 0; n < 5; ++n) {
-        double a, zp, zq, zr;
-        if (d == H - 1) { a = top[n][0]; zp = top[n][1]; zq = top[n][2]; zr = top[n][3]; }
-        else { a = agd_get(stash[d][n][0]); zp = agd_get(stash[d][n][1]); zq = agd_get(stash[d][n][2]); zr = agd_get(stash[d][n][3]); }
-        preact_adjoint_d(a, zp, zq, zr, ob[0][n], ob[1][n], ob[2][n], ob[3][n], zb[0][n], zb[1][n], zb[2][n], zb[3][n]);
-      }
-      STAMP2(d == 4, 20);
-      // One tile: the phase before this one is summed HERE, not where its last block was parked -- the stash entries of
-      // layer d, read a first time for that phase's rotated inputs, are still in registers for the adjoints above (a
-      // barrier in between would end their basic block and cost a second v_accvgpr_read each).
-      // The LDS pipe is the second bottleneck of this kernel (a ds_read_b128 costs a wave ~53 cycles of it with four waves on
-      // the CU: profiles/r01_ubench_lds_rates.txt, r06_stamps2_new.txt), and it runs beside the matrix pipe: the adds and
-      // stores of the sum stand in front of the reverse GEMV, and this layer's 40 operand moves -- needed only by the
-      // weight-gradient blocks behind the GEMV -- are issued one per pinned GEMV step.
-      // (finish_prev stays a lambda: written out in place, the one-tile instantiations come out 14-19 instructions longer)
-      auto finish_prev = [&]() {
-        if (d == H - 1) phase_finish(6 * 16, idx_dense_h);
-        else phase_finish(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[d + 1] + rel_hidden[k]; });
-      };
-      if constexpr (ONE_TILE) finish_prev();
-      STAMP2(d == 4, 21);
-      // the first in-group's inputs of the weight-gradient blocks: formed here, moved in the last steps of the GEMV
-      double cur[4] = {0.0, 0.0, 0.0, 0.0}, first_nat[4] = {0.0, 0.0, 0.0, 0.0};
-      {
-        double a_, zp_, zq_, zr_;
-        if (d - 1 == 0) {
-          a_ = a0[0]; zp_ = sx * wl[nd.off_w[0] + s]; zq_ = st * wl[nd.off_w[0] + FW + s]; zr_ = 0.0;
-        } else {
-          a_ = agd_get(stash[d - 1][0][0]); zp_ = agd_get(stash[d - 1][0][1]);
-          zq_ = agd_get(stash[d - 1][0][2]); zr_ = agd_get(stash[d - 1][0][3]);
-        }
-        channels_d(a_, zp_, zq_, zr_, first_nat[0], first_nat[1], first_nat[2], first_nat[3]);
-      }
-      // adjoint of the layer-(d-1) outputs: in_bar[4m + i] = sum_j z_bar_j W_d[4m + i][j]
-      const double* __restrict__ wd = wl + nd.off_w[d] + pr;
-#pragma unroll
-      for (int m = 0; m < 5; ++m) {
-        ob[0][m] = ob[1][m] = ob[2][m] = ob[3][m] = 0.0;
-      }
-      {
-        auto rpat = [&](const int t) { return wd[80 * (t / 5) + 4 * (t % 5)]; };
-        double Aq[4] = {rpat(0), rpat(1), 0.0, 0.0};
-#pragma unroll
-        for (int t = 0; t < 25; ++t) {
-          const int m = t / 5, n = t - 5 * m;
-          const double A = Aq[t & 3];
-          if ((t & 1) == 0) {
-            if (t + 2 < 25) Aq[(t + 2) & 3] = rpat(t + 2);
-            if (t + 3 < 25) Aq[(t + 3) & 3] = rpat(t + 3);
-          }
-          if (t < 20) zbT[t / 5][t % 5] = PINN_TO_POINTS(zb[t / 5][t % 5]);   // one operand move per step
-          if (t >= 20 && t < 24) cur[t - 20] = PINN_TO_POINTS(first_nat[t - 20]);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) ob[c][m] = mfma444(A, zb[c][n], ob[c][m]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      STAMP2(d == 4, 22);
-      // dW_d[4m + i][4n + j]: the A operands are the layer-(d-1) output channels, rotated -- produced one in-group
-      // ahead of the matrix instructions that consume them (20 values live instead of 40: the kernel sits at the
-      // 256-VGPR limit, and with all of them live hipcc sank the accumulator fetches next to their uses)
-      const int base = 5 + (d - 1) * 30;
-      phase_first = base;                                      // phase H - d: buffers alternate
-      stage_w = gacc_all + PINN_PHASE_STAGE(H - d) + wave * STAGE_WAVE_STRIDE;
-#define PINN_ROTATED_INPUTS(M, O4)                                                                          \
-  do {                                                                                                      \
-    double a_, zp_, zq_, zr_;                                                                               \
-    if (d - 1 == 0) {                                                                                       \
-      const int f_ = 4 * (M) + s;                                                                           \
-      a_ = a0[M]; zp_ = sx * wl[nd.off_w[0] + f_]; zq_ = st * wl[nd.off_w[0] + FW + f_]; zr_ = 0.0;         \
-    } else {                                                                                                \
-      a_ = agd_get(stash[d - 1][M][0]); zp_ = agd_get(stash[d - 1][M][1]);                                  \
-      zq_ = agd_get(stash[d - 1][M][2]); zr_ = agd_get(stash[d - 1][M][3]);                                 \
-    }                                                                                                       \
-    double h_, p_, q_, r_;                                                                                  \
-    channels_d(a_, zp_, zq_, zr_, h_, p_, q_, r_);                                                          \
-    O4[0] = PINN_TO_POINTS(h_); O4[1] = PINN_TO_POINTS(p_);                                             \
-    O4[2] = PINN_TO_POINTS(q_); O4[3] = PINN_TO_POINTS(r_);                                             \
-  } while (0)
-#pragma unroll
-      for (int m = 0; m < 5; ++m) {          // five independent accumulator chains per in-group
-        double D[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, old[5], nxt[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int n = 0; n < 5; ++n) old[n] = grad_fetch(base + m * 5 + n);
-        if (m + 1 < 5) PINN_ROTATED_INPUTS((m + 1 < 5 ? m + 1 : 4), nxt);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-          for (int n = 0; n < 5; ++n) D[n] = mfma444(cur[c], zbT[c][n], D[n]);
-        }
-#pragma unroll
-        for (int n = 0; n < 5; ++n) grad_store(D[n], old[n], base + m * 5 + n);
-        gacc_flush();
-#pragma unroll
-        for (int c = 0; c < 4; ++c) cur[c] = nxt[c];
-        STAMP2(d == 4, 23 + m);
-      }
-#undef PINN_ROTATED_INPUTS
-      {
-        double D[5], old[5];
-#pragma unroll
-        for (int n = 0; n < 5; ++n) old[n] = grad_fetch(base + 25 + n);
-#pragma unroll
-        for (int n = 0; n < 5; ++n) D[n] = mfma444(onesA, zbT[0][n], 0.0);
-#pragma unroll
-        for (int n = 0; n < 5; ++n) grad_store(D[n], old[n], base + 25 + n);
-        gacc_flush();
-      }
-      STAMP(2 * H + 1 - d);
-    }
-    {  // dense 0: inputs (hx, ht, 1) in channel h, (sx, 0, 0) in channel p, (0, st, 0) in channel q
-      const double hxT = PINN_TO_POINTS(hx), htT = PINN_TO_POINTS(ht);
-      const double Ah = i4 == 0 ? hxT : i4 == 1 ? htT : i4 == 2 ? 1.0 : 0.0;
-      const double Ap = i4 == 0 ? sx : 0.0, Aq = i4 == 1 ? st : 0.0;
-      double bT[3][5];
-#pragma unroll
-      for (int n = 0; n < 5; ++n) {
-        const int f = 4 * n + s;
-        double bh, bp, bq, br;
-        preact_adjoint_d(a0[n], sx * wl[nd.off_w[0] + f], st * wl[nd.off_w[0] + FW + f], 0.0, ob[0][n], ob[1][n],
-                         ob[2][n], ob[3][n], bh, bp, bq, br);
-        bT[0][n] = PINN_TO_POINTS(bh); bT[1][n] = PINN_TO_POINTS(bp); bT[2][n] = PINN_TO_POINTS(bq);
-      }
-      if constexpr (ONE_TILE) {                                // layer 1's phase
-        phase_issue(30 * 16, H - 1);
-        phase_finish(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[1] + rel_hidden[k]; });
-      }
-      double D[5], old[5];
-#pragma unroll
-      for (int n = 0; n < 5; ++n) old[n] = grad_fetch(n);
-#pragma unroll
-      for (int n = 0; n < 5; ++n) D[n] = mfma444(Ah, bT[0][n], 0.0);
-#pragma unroll
-      for (int n = 0; n < 5; ++n) D[n] = mfma444(Ap, bT[1][n], D[n]);
-#pragma unroll
-      for (int n = 0; n < 5; ++n) D[n] = mfma444(Aq, bT[2][n], D[n]);
-      phase_first = 0;                                         // phase H
-      stage_w = gacc_all + PINN_PHASE_STAGE(H) + wave * STAGE_WAVE_STRIDE;
-#pragma unroll
-      for (int n = 0; n < 5; ++n) grad_store(D[n], old[n], n);
-      gacc_flush();
-      if constexpr (ONE_TILE) {
-        auto idx_dense_0 = [&](const int e, int) {
-          const int f = 4 * (e >> 4) + (e & 3), i = (e >> 2) & 3;
-          return i == 0 ? nd.off_w[0] + f : i == 1 ? nd.off_w[0] + FW + f : i == 2 ? nd.off_b[0] + f : -1;
-        };
-        phase_issue(5 * 16, H);
-        phase_finish(5 * 16, idx_dense_0);
-        if constexpr (PINN_ONETILE_SUM == 2) {           // every phase is parked in its own region: one barrier, H + 1 sums
-          parked_barrier();
-          phase_reads(6 * 16, 0);
-          phase_adds(6 * 16, idx_dense_h);
-#pragma unroll
-          for (int d = H - 1; d >= 1; --d) {
-            phase_reads(30 * 16, H - d);
-            phase_adds(30 * 16, [&](int, const int k) { return rel_hidden[k] < 0 ? -1 : nd.off_w[d] + rel_hidden[k]; });
-          }
-          phase_reads(5 * 16, H);
-          phase_adds(5 * 16, idx_dense_0);
-        }
-      }
-    }
+    if (helper && !(tile & 1)) continue;               // a helper's second tile (the loop's own test ends it where there is none)
+#else
+#define PINN_F20D_ROLE 0
+#include "kernels_fused20d_reverse.h"
+#undef PINN_F20D_ROLE
+#endif
     if (ONE_TILE) break;
   }
   STAMP(2 * H + 1);
+#if PINN_F20D_SPLIT
+  if (helper) return;                                  // a helper writes no loss parts (the whole workgroup leaves: no barrier is split)
+#endif
 #undef PINN_LANE_INDICES
 #undef PINN_TO_POINTS
 #undef PINN_PHASE_STAGE

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _REPO = os.path.dirname(os.path.dirname(_HERE))
 LIB_PATH = os.environ.get("PINN_HIP_LIB") or os.path.join(_HERE, "libpinn_hip.so")
-SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_fused20d_kernel.h", "kernels_wide.h", "kernels_predict20.h",
+SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_fused20d_kernel.h", "kernels_fused20d_reverse.h", "kernels_wide.h", "kernels_predict20.h",
            "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h"]
 HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
@@ -244,6 +244,7 @@ _SIGNATURES = {
     "pinn_sync": (ctypes.c_int, [ctypes.c_void_p]),
     "pinn_set_kernel_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "pinn_get_kernel_path": (ctypes.c_int, [ctypes.c_void_p, _c_int_p]),
+    "pinn_get_f64_split": (ctypes.c_int, [ctypes.c_void_p, _c_int_p]),
     "pinn_debug_coef_stamps": (ctypes.c_int, [ctypes.POINTER(ctypes.c_longlong)]),
     "pinn_debug_t16f_stamps": (ctypes.c_int, [ctypes.POINTER(ctypes.c_longlong)]),
     "pinn_debug_t16_deal": (ctypes.c_int, [ctypes.c_int, _c_int_p]),
@@ -909,6 +910,7 @@ class Engine(object):
     def debug_stamps(self):
         """(profiling build) -> int64 array [n_waves, 32] of s_memtime ticks for one evaluation"""
         n_wg = (2 * self.n_b + self.n_u + self.n_f + getattr(self, "n_w", 0) + 63) // 64
+        n_wg += (n_wg + 1) // 2                # a split launch of path 7 (f64_split): the helper workgroups' stamps follow
         buf = np.zeros((n_wg * 4, 32), dtype=np.int64)
         n = ctypes.c_int64(0)
         self._check(self._lib.pinn_debug_stamps(
@@ -919,6 +921,14 @@ class Engine(object):
         p = ctypes.c_int(0)
         self._check(self._lib.pinn_get_kernel_path(self._h, ctypes.byref(p)))
         return p.value
+
+    @property
+    def f64_split(self):
+        """True when the next evaluation takes the split one-tile launch of kernel path 7 (include/pinn_hip.h:
+        pinn_get_f64_split; environment PINN_F64_SPLIT = auto / 0 / 1, read when the engine is created).  Read-only."""
+        p = ctypes.c_int(0)
+        self._check(self._lib.pinn_get_f64_split(self._h, ctypes.byref(p)))
+        return bool(p.value)
 
 
 class Ensemble(object):
@@ -949,6 +959,8 @@ class Ensemble(object):
         if rc != 0:
             raise PinnNativeError("libpinn_hip: %s (code %d)" % (
                 self._lib.pinn_last_error().decode(errors="replace"), rc))
+
+    f64_split = False      # an ensemble launch never takes the split one-tile plan of a solo Engine (Engine.f64_split)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

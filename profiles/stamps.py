@@ -39,6 +39,12 @@ def main():
         path = eng.kernel_path()
         n_st = 2 * H + 3 if path in (2, 7) else 2 * H + 2
         st = eng.debug_stamps().astype(np.float64)
+    # split launch of path 7 (Engine.f64_split): the main workgroups' waves come first, one workgroup per tile; the helper
+    # workgroups' follow (one per pair of tiles) and are printed on their own at the end
+    helpers = None
+    if path == 7 and eng.f64_split:
+        n_main = (eng.n_u + eng.n_f + 63) // 64
+        helpers, st = st[4 * n_main:].reshape(-1, 4, 32), st[:4 * n_main]
     st = st[:, :n_st].reshape(-1, 4, n_st)              # [wg, wave, stamp]
     t0 = st[:, :, 0].min()
     names = (["stage weights + dense0"] + ["fwd dense %d" % d for d in range(1, H)] +
@@ -55,8 +61,33 @@ def main():
     for i, nme in enumerate(names):
         print("%-34s %10.0f %10.0f %10.0f" % (nme, np.median(per[:, i]), per[:, i].min(), per[:, i].max()))
     print("%-34s %10.0f" % ("sum of medians", np.median(per, axis=0).sum()))
+    if helpers is not None:
+        # helper stamps: 0 entry, 1 weights staged, 1 + d forward layer d done, H + 1 output + seeds + dense-H blocks, H + 2 layer
+        # H - 1's adjoints, moves and blocks, 19 / 31 end of the first / second tile (its last phase sum stored), 2 H + 1 exit;
+        # the forward and top stamps are those of the LAST tile served
+        print("# split launch: the table above is the MAIN role (no dense-%d blocks, reverse layer %d without its gradient blocks);"
+              " %d helper workgroups:" % (H, H - 1, helpers.shape[0]))
+        two = helpers[:, 0, 31] > 0                       # served a second tile
+        h_total = helpers[:, :, 2 * H + 1].max(axis=1) - helpers[:, :, 0].min(axis=1)
+        print("# helper duration ticks: min %.0f median %.0f max %.0f; %d of them served two tiles" % (
+            h_total.min(), np.median(h_total), h_total.max(), int(two.sum())))
+        hh = helpers[two] if two.any() else helpers
+        end_last = hh[:, :, 31] if two.any() else hh[:, :, 19]
+        start_last = hh[:, :, 19] if two.any() else hh[:, :, 1]
+        def hseg(a, b):
+            return np.median((b - a).max(axis=1))
+        rows = [("stage weights", hseg(hh[:, :, 0], hh[:, :, 1]))]
+        if two.any():
+            rows.append(("first tile (whole)", hseg(hh[:, :, 1], hh[:, :, 19])))
+        rows.append(("last tile: dense 0 + fwd dense 1", hseg(start_last, hh[:, :, 2])))
+        rows += [("last tile: fwd dense %d" % d, hseg(hh[:, :, d], hh[:, :, 1 + d])) for d in range(2, H)]
+        rows.append(("last tile: output + seeds + dW %d" % H, hseg(hh[:, :, H], hh[:, :, H + 1])))
+        rows.append(("last tile: layer %d adjoints + dW" % (H - 1), hseg(hh[:, :, H + 1], hh[:, :, H + 2])))
+        rows.append(("last tile: last phase sum", hseg(hh[:, :, H + 2], end_last)))
+        for nme, v in rows:
+            print("%-34s %10.0f" % (nme, v))
     if path == 7:
-        full = eng.debug_stamps().astype(np.float64).reshape(-1, 4, 32)
+        full = eng.debug_stamps().astype(np.float64).reshape(-1, 4, 32)[:st.shape[0]]
         if np.all(full[:, :, 20:28] > 0):                  # -DPINN_STAMPS2: inside reverse layer 4 and forward layer 4
             def seg(a, b):
                 return np.median((full[:, :, b] - full[:, :, a]).max(axis=1))

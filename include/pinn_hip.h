@@ -352,6 +352,33 @@ int pinn_ensk_set_pde_params(pinn_ens* e, const double* nu, int n_members);
  * seed seeds[k] become member k's collocation set */
 int pinn_ensk_lhs_collocation(pinn_ens* e, int64_t n_design, int64_t first, int64_t count, const uint64_t* seeds);
 
+/* Ensembles of the adr kind: K members of one float64 PINN_PDE_ADR net (kernel path 7, 2-20-...-20-1 with 4, 6 or 8 hidden
+ * layers), each with its OWN six coefficients a0, a1, nu, r1, r2, r3 -- Allen-Cahn over interface widths, Fisher-KPP over rho
+ * and D, seeds and learning rates for any of them -- on shared or per-member point sets, periodic pairs included.  The
+ * constructor returns an ordinary pinn_ens: every pinn_ens_ and pinn_ensk_ call above works on it as it is, except
+ * pinn_ensk_set_pde_params (a Burgers call: PINN_EUNSUPPORTED here); terms [k][2] of pinn_ens_loss_grad is member k's
+ * periodic part.  Member k ends bit-identical to a pinn_ctx of the adr kind given member k's weights, coefficients and points
+ * with the same calls.
+ * Coefficients: a new ensemble holds a new adr context's set, Burgers' [0, 1, 0.01 / pi, 0, 0, 0], for every member.
+ * pinn_ens_set_pde_params with n = 6 gives one set to all members; pinn_adr_ensk_set_params gives member k row k of
+ * p [K][6]; pinn_adr_ens_get_params reads the rows back.  Neither setter switches the ensemble to per-member point sets.
+ * Pairs: pinn_adr_ens_set_boundary is pinn_set_boundary for all members (per-member mode: broadcast);
+ * pinn_adr_ensk_set_boundary takes X_lb, X_ub [K][n][2], one common n, and switches to per-member mode as the pinn_ensk_ setters
+ * above do (every member starts from the shared sets, pairs included).
+ * Refusals, all before any device work and with nothing changed: a null argument or K outside 1..64 PINN_EINVAL, a shape
+ * other than the one above PINN_EUNSUPPORTED (the constructor); n != 6 or a coefficient that is not finite, n_members != K,
+ * counts out of range PINN_EINVAL; the three adr and the two boundary calls on a Burgers ensemble PINN_EUNSUPPORTED.
+ * pinn_ens_create itself keeps refusing pde 5 and 6.  Not for members: Robin points, a source term, coefficient fields, point
+ * weights, trainable coefficients, adaptive resampling, float32, other kernel paths, communicators.  (Additive: the ABI
+ * version stays 6; callers detect the feature by the presence of the symbols.  Named pinn_adr_: the sets of pinn_ens_ and
+ * pinn_ensk_ names are the Burgers ensemble's, complete as they stand.) */
+int pinn_adr_ens_create(pinn_ens** out, const int* layers, int n_layers, const double* lb, const double* ub, int device,
+                        int n_members);
+int pinn_adr_ens_set_boundary(pinn_ens* e, const double* X_lb, const double* X_ub, int64_t n, int64_t n_total);
+int pinn_adr_ensk_set_boundary(pinn_ens* e, const double* X_lb, const double* X_ub, int64_t n, int64_t n_total);
+int pinn_adr_ensk_set_params(pinn_ens* e, const double* p, int n_members);
+int pinn_adr_ens_get_params(pinn_ens* e, double* p, int n_members);
+
 /* Self-adaptive point weights (SA-PINN, McClenny & Braga-Neto, arXiv:2009.04544) for Burgers inference (pde 0) in float64 on
  * kernel path 7.  Every data point j and collocation point i gets a trainable weight, and the loss becomes
  *     L = (1/N_f) sum_i lam_f,i^2 f_i^2 + (1/N_u) sum_j lam_u,j^2 (u_j - u*_j)^2

@@ -3211,6 +3211,13 @@ struct pinn_ens {
   std::vector<double> k_nu;                    // [K]
   double *k_xs = nullptr, *k_ts = nullptr, *k_tgt = nullptr, *k_nud = nullptr;   // [K][n_pad] x 3, [K]
   size_t k_cap = 0;
+  // an ensemble of the adr kind (pinn_adr_ens_create): every member has its own six coefficients in BOTH modes -- the host
+  // rows [K][6] and the device table [K][ADR_ENS_ROW] k_adrens20d reads, there from creation and re-uploaded when dirty --
+  // and, in per-member mode, its own periodic pairs (one common n)
+  bool adr = false, coef_dirty = true;
+  std::vector<double> coef;                    // [K][6]
+  double* coef_d = nullptr;                    // [K][ADR_ENS_ROW]
+  std::vector<double> kXlo, kXhi;              // [K][n_b][2]
 };
 
 static void ens_free(pinn_ens* e) {
@@ -3222,7 +3229,7 @@ static void ens_free(pinn_ens* e) {
   }
   if (e->base) { (void)hipSetDevice(e->base->device); (void)hipStreamSynchronize(e->base->stream); }
   void* ptrs[] = {e->theta, e->theta_r, e->gl, e->m, e->v, e->nonfinite, e->part, e->loss_hist, e->k_xs, e->k_ts,
-                  e->k_tgt, e->k_nud};
+                  e->k_tgt, e->k_nud, e->coef_d};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (e->base) (void)pinn_destroy(e->base);
   delete e;
@@ -3233,11 +3240,13 @@ static void ens_to_k(pinn_ens* e) {
   if (e->k_mode) return;
   pinn_ctx* b = e->base;
   const size_t K = e->K;
-  e->kXf.clear(); e->kXu.clear(); e->kU.clear();
+  e->kXf.clear(); e->kXu.clear(); e->kU.clear(); e->kXlo.clear(); e->kXhi.clear();
   for (size_t k = 0; k < K; ++k) {
     e->kXf.insert(e->kXf.end(), b->Xf.begin(), b->Xf.end());
     e->kXu.insert(e->kXu.end(), b->Xu.begin(), b->Xu.end());
     e->kU.insert(e->kU.end(), b->U.begin(), b->U.end());
+    e->kXlo.insert(e->kXlo.end(), b->Xlo.begin(), b->Xlo.end());      // (the adr kind's pairs; empty for Burgers)
+    e->kXhi.insert(e->kXhi.end(), b->Xhi.begin(), b->Xhi.end());
   }
   e->k_seeds.assign(K, b->lhs.seed);
   e->k_nu.assign(K, b->nu);
@@ -3263,29 +3272,48 @@ static int ens_lhs_fill(pinn_ens* e) {
 }
 
 // ensure_sets for the ensemble: the base's SetDesc and plan, then (per-member mode) the [K][n_pad] sets, assembled as
-// ensure_sets assembles one: [data | collocation | pad]
+// ensure_sets assembles one: [lo_0, hi_0, lo_1, hi_1, ... (the adr kind) | data | collocation | pad]; the adr kind's
+// coefficient table in both modes
 static int ens_ensure_sets(pinn_ens* e) {
   pinn_ctx* b = e->base;
   if (b->sets_dirty) e->k_dirty = true;
   if (int rc = ensure_sets(b)) return rc;
-  if (!e->k_mode) return 0;
   const size_t K = e->K;
-  if (!e->k_nud) {
-    if (dev_alloc(&e->k_nud, K * 8)) return PINN_EHIP;
-    e->k_nu_dirty = true;
+  if (e->adr && e->coef_dirty) {               // both modes: the members' rows, padded to ADR_ENS_ROW doubles
+    std::vector<double> rows(K * ADR_ENS_ROW, 0.0);
+    for (size_t k = 0; k < K; ++k)
+      for (int j = 0; j < 6; ++j) rows[k * ADR_ENS_ROW + j] = e->coef[k * 6 + j];
+    if (upload_real(b, e->coef_d, rows.data(), rows.size())) return PINN_EHIP;
+    e->coef_dirty = false;
   }
-  if (e->k_nu_dirty) {
-    if (upload_real(b, e->k_nud, e->k_nu.data(), K)) return PINN_EHIP;
-    e->k_nu_dirty = false;
+  if (!e->k_mode) return 0;
+  if (!e->adr) {
+    if (!e->k_nud) {
+      if (dev_alloc(&e->k_nud, K * 8)) return PINN_EHIP;
+      e->k_nu_dirty = true;
+    }
+    if (e->k_nu_dirty) {
+      if (upload_real(b, e->k_nud, e->k_nu.data(), K)) return PINN_EHIP;
+      e->k_nu_dirty = false;
+    }
   }
   if (!e->k_dirty) return 0;
   const SetDesc& sd = b->sd;
-  const size_t n_pad = sd.n_pad, n_u = sd.n_u, n_f = sd.n_f;
+  const size_t n_pad = sd.n_pad, n_b = sd.n_b, n_u = sd.n_u, n_f = sd.n_f;
+  REQUIRE(e->kXlo.size() == K * 2 * n_b && e->kXhi.size() == K * 2 * n_b && e->kXu.size() == K * 2 * n_u &&
+          e->kU.size() == K * n_u && (b->lhs.on || e->kXf.size() == K * 2 * n_f),
+          "the members' point sets do not have the base's counts (%d pairs, %d data, %d collocation points)", sd.n_b, sd.n_u,
+          sd.n_f);
   std::vector<double> hx(K * n_pad), ht(K * n_pad), htg(K * n_pad, 0.0);
   for (size_t k = 0; k < K; ++k) {
     double *x = hx.data() + k * n_pad, *t = ht.data() + k * n_pad, *tg = htg.data() + k * n_pad;
     const double *xu = e->kXu.data() + k * 2 * n_u, *u = e->kU.data() + k * n_u, *xf = e->kXf.data() + k * 2 * n_f;
+    const double *xlo = e->kXlo.data() + k * 2 * n_b, *xhi = e->kXhi.data() + k * 2 * n_b;
     size_t g = 0;
+    for (size_t i = 0; i < n_b; ++i, g += 2) {   // the adr kind's pairs, interleaved as ensure_sets places them (Burgers: none)
+      x[g] = xlo[2 * i]; t[g] = xlo[2 * i + 1];
+      x[g + 1] = xhi[2 * i]; t[g + 1] = xhi[2 * i + 1];
+    }
     for (size_t i = 0; i < n_u; ++i, ++g) { x[g] = xu[2 * i]; t[g] = xu[2 * i + 1]; tg[g] = u[i]; }
     if (!b->lhs.on)
       for (size_t i = 0; i < n_f; ++i, ++g) { x[g] = xf[2 * i]; t[g] = xf[2 * i + 1]; }
@@ -3315,7 +3343,9 @@ static int ens_eval(pinn_ens* e, const bool* active, const double* alpha, double
   F20dLaunch a = fused20d_args(b, nullptr);
   a.th = e->theta_r; a.part = e->part; a.n_members = e->K;
   if (e->k_mode) { a.xs = e->k_xs; a.ts = e->k_ts; a.tgt = e->k_tgt; }
-  const int rc = e->k_mode ? fused20d_ens_launch_any(b->pde, a, (const double*)e->k_nud) : fused20d_ens_launch_any(b->pde, a, b->nu);
+  const int rc = e->adr    ? fused20d_ens_launch_any(a, AdrEnsArg{e->coef_d}, e->k_mode)
+                 : e->k_mode ? fused20d_ens_launch_any(b->pde, a, (const double*)e->k_nud)
+                             : fused20d_ens_launch_any(b->pde, a, b->nu);
   if (rc) return fail(PINN_EHIP, "ensemble fused20d launch failed: %s", hipGetErrorString((hipError_t)rc));
   EnsStep es{};
   for (int k = 0; k < e->K; ++k) {
@@ -3338,21 +3368,26 @@ static int ens_eval(pinn_ens* e, const bool* active, const double* alpha, double
   return 0;
 }
 
-int pinn_ens_create(pinn_ens** out, const int* layers, int n_layers, const double* lb, const double* ub, int pde_kind,
-                    int dtype, int device, int n_members) {
-  // every refusal comes before any device work
+// what both constructors refuse before any device work: a null argument and K outside 1..ENS_MAX (PINN_EINVAL), ...
+static int ens_check_args(pinn_ens** out, const int* layers, const double* lb, const double* ub, int n_members) {
   REQUIRE(out && layers && lb && ub, "null argument");
   REQUIRE(n_members >= 1 && n_members <= ENS_MAX, "ensemble size %d outside 1..%d", n_members, ENS_MAX);
-  if (dtype != PINN_F64)
-    return fail(PINN_EUNSUPPORTED, "ensembles are float64 only (kernel path 7); float32 is not supported");
-  if (pde_kind != PINN_PDE_BURGERS && pde_kind != PINN_PDE_BURGERS_IDE)
-    return fail(PINN_EUNSUPPORTED, "ensembles support Burgers inference and identification (pde 0, 1) only; "
-                                   "Schrodinger and discrete-time models are not supported");
+  return 0;
+}
+// ... and a net other than 2-20-...-20-1 with 4, 6 or 8 hidden layers (PINN_EUNSUPPORTED)
+static int ens_check_shape(const int* layers, int n_layers) {
   const int H = n_layers - 2;
   bool shape_ok = n_layers >= 3 && fused20d_depth_ok(H) && layers[0] == 2 && layers[n_layers - 1] == 1;
   for (int i = 1; shape_ok && i <= H; ++i) shape_ok = layers[i] == FW;
   if (!shape_ok)
     return fail(PINN_EUNSUPPORTED, "ensembles need the 2-%d-1 net with 4, 6 or 8 hidden layers of width %d", FW, FW);
+  return 0;
+}
+
+// the base, the blocks and the members of an ensemble of float64 contexts of pde_kind (the arguments are checked)
+static int ens_build(pinn_ens** out, const int* layers, int n_layers, const double* lb, const double* ub, int pde_kind,
+                     int device, int n_members) {
+  const int dtype = PINN_F64;
   *out = nullptr;
   pinn_ens* e = new pinn_ens();
   e->K = n_members;
@@ -3362,6 +3397,12 @@ int pinn_ens_create(pinn_ens** out, const int* layers, int n_layers, const doubl
   e->P = b->nd.n_theta;
   e->sw = (int)fused20d_weight_doubles(e->P);
   const size_t K = e->K, P = e->P;
+  if (pde_kind == PINN_PDE_ADR) {              // every row starts as a new adr context's coefficients
+    e->adr = true;
+    for (size_t k = 0; k < K; ++k) e->coef.insert(e->coef.end(), b->adr, b->adr + 6);
+    if (dev_alloc(&e->coef_d, K * ADR_ENS_ROW * 8)) { ens_free(e); return PINN_EHIP; }
+    e->coef_dirty = true;
+  }
   if (dev_alloc(&e->theta, K * P * 8) || dev_alloc(&e->m, K * P * 8) || dev_alloc(&e->v, K * P * 8) ||
       dev_alloc(&e->theta_r, K * e->sw * 8 + 1024) || dev_alloc(&e->gl, K * b->R * 8) ||
       dev_alloc(&e->nonfinite, K * 8)) { ens_free(e); return PINN_EHIP; }
@@ -3385,6 +3426,28 @@ int pinn_ens_create(pinn_ens** out, const int* layers, int n_layers, const doubl
   }
   *out = e;
   return 0;
+}
+
+int pinn_ens_create(pinn_ens** out, const int* layers, int n_layers, const double* lb, const double* ub, int pde_kind,
+                    int dtype, int device, int n_members) {
+  // every refusal comes before any device work
+  if (int rc = ens_check_args(out, layers, lb, ub, n_members)) return rc;
+  if (dtype != PINN_F64)
+    return fail(PINN_EUNSUPPORTED, "ensembles are float64 only (kernel path 7); float32 is not supported");
+  if (pde_kind != PINN_PDE_BURGERS && pde_kind != PINN_PDE_BURGERS_IDE)
+    return fail(PINN_EUNSUPPORTED, "ensembles support Burgers inference and identification (pde 0, 1) only; "
+                                   "Schrodinger and discrete-time models are not supported");
+  if (int rc = ens_check_shape(layers, n_layers)) return rc;
+  return ens_build(out, layers, n_layers, lb, ub, pde_kind, device, n_members);
+}
+
+// K members of the adr kind (float64, kernel path 7): pinn_ens_create's handle, refusals and blocks; every member has its
+// own six coefficients (pinn_ens_set_pde_params / pinn_adr_ensk_set_params), whether the point sets are shared or not
+int pinn_adr_ens_create(pinn_ens** out, const int* layers, int n_layers, const double* lb, const double* ub, int device,
+                        int n_members) {
+  if (int rc = ens_check_args(out, layers, lb, ub, n_members)) return rc;
+  if (int rc = ens_check_shape(layers, n_layers)) return rc;
+  return ens_build(out, layers, n_layers, lb, ub, PINN_PDE_ADR, device, n_members);
 }
 
 int pinn_ens_destroy(pinn_ens* e) {
@@ -3424,8 +3487,50 @@ int pinn_ens_set_data(pinn_ens* e, const double* X_u, const double* u, int64_t n
 
 int pinn_ens_set_pde_params(pinn_ens* e, const double* p, int n) {
   REQUIRE(e, "null");
-  if (int rc = pinn_set_pde_params(e->base, p, n)) return rc;
+  if (int rc = pinn_set_pde_params(e->base, p, n)) return rc;      // (the adr kind: n != 6 or a non-finite value is refused here)
+  if (e->adr) {                                                    // one set for all members; the mode stays what it is
+    for (int k = 0; k < e->K; ++k) memcpy(e->coef.data() + (size_t)k * 6, p, 6 * sizeof(double));
+    e->coef_dirty = true;
+    return 0;
+  }
   if (e->k_mode) { e->k_nu.assign((size_t)e->K, p[0]); e->k_nu_dirty = true; }
+  return 0;
+}
+
+// the adr kind: one coefficient set per member.  Nothing changes on a refusal, and the mode stays what it is
+int pinn_adr_ensk_set_params(pinn_ens* e, const double* p, int n_members) {
+  REQUIRE(e && p, "null argument");
+  if (!e->adr) return fail(PINN_EUNSUPPORTED, "pinn_adr_ensk_set_params: this is not an ensemble of the adr kind (pinn_adr_ens_create)");
+  REQUIRE(n_members == e->K, "pinn_adr_ensk_set_params: %d coefficient sets for %d members", n_members, e->K);
+  for (int i = 0; i < 6 * e->K; ++i)
+    REQUIRE(std::isfinite(p[i]), "pinn_adr_ensk_set_params: coefficient %d of member %d is not finite", i % 6, i / 6);
+  if (int rc = pinn_set_pde_params(e->base, p, 6)) return rc;      // the base keeps member 0's
+  e->coef.assign(p, p + (size_t)6 * e->K);
+  e->coef_dirty = true;
+  return 0;
+}
+
+int pinn_adr_ens_get_params(pinn_ens* e, double* p, int n_members) {
+  REQUIRE(e && p, "null argument");
+  if (!e->adr) return fail(PINN_EUNSUPPORTED, "pinn_adr_ens_get_params: this is not an ensemble of the adr kind (pinn_adr_ens_create)");
+  REQUIRE(n_members == e->K, "pinn_adr_ens_get_params: room for %d coefficient sets, the ensemble has %d members", n_members, e->K);
+  memcpy(p, e->coef.data(), (size_t)6 * e->K * sizeof(double));
+  return 0;
+}
+
+// the adr kind's periodic pairs: one set for all members (per-member mode: the same pairs in every member's slots) ...
+int pinn_adr_ens_set_boundary(pinn_ens* e, const double* X_lb, const double* X_ub, int64_t n, int64_t n_total) {
+  REQUIRE(e, "null");
+  if (!e->adr) return fail(PINN_EUNSUPPORTED, "pinn_adr_ens_set_boundary: boundary pairs are for ensembles of the adr kind (pinn_adr_ens_create)");
+  if (int rc = pinn_set_boundary(e->base, X_lb, X_ub, n, n_total)) return rc;
+  if (e->k_mode) {
+    e->kXlo.clear(); e->kXhi.clear();
+    for (int k = 0; k < e->K; ++k) {
+      e->kXlo.insert(e->kXlo.end(), X_lb, X_lb + 2 * n);
+      e->kXhi.insert(e->kXhi.end(), X_ub, X_ub + 2 * n);
+    }
+    e->k_dirty = true;
+  }
   return 0;
 }
 
@@ -3457,8 +3562,24 @@ int pinn_ensk_set_data(pinn_ens* e, const double* X_u, const double* u, int64_t 
   return 0;
 }
 
+// ... or one set per member, [K][n][2] each, one common n (CHUNK_POINTS / 4 pairs at the most, as ensure_sets asks)
+int pinn_adr_ensk_set_boundary(pinn_ens* e, const double* X_lb, const double* X_ub, int64_t n, int64_t n_total) {
+  REQUIRE(e && ((X_lb && X_ub) || n == 0), "null argument");
+  if (!e->adr) return fail(PINN_EUNSUPPORTED, "pinn_adr_ensk_set_boundary: boundary pairs are for ensembles of the adr kind (pinn_adr_ens_create)");
+  REQUIRE(n >= 0 && 2 * n <= CHUNK_POINTS / 2 && n_total >= n, "bad boundary arguments (n %lld, n_total %lld)", (long long)n,
+          (long long)n_total);
+  ens_to_k(e);
+  if (int rc = pinn_set_boundary(e->base, X_lb, X_ub, n, n_total)) return rc;     // member 0's: the SetDesc and the plan
+  e->kXlo.assign(X_lb, X_lb + (size_t)e->K * 2 * n);
+  e->kXhi.assign(X_ub, X_ub + (size_t)e->K * 2 * n);
+  e->k_dirty = true;
+  return 0;
+}
+
 int pinn_ensk_set_pde_params(pinn_ens* e, const double* nu, int n_members) {
   REQUIRE(e && nu, "null argument");
+  if (e->adr) return fail(PINN_EUNSUPPORTED, "pinn_ensk_set_pde_params: a viscosity per member is the Burgers ensemble's call; "
+                                             "an adr ensemble takes six coefficients per member (pinn_adr_ensk_set_params)");
   REQUIRE(n_members == e->K, "%d viscosities for %d members", n_members, e->K);
   ens_to_k(e);
   if (int rc = pinn_set_pde_params(e->base, nu, 1)) return rc;      // (identification: accepted and unused, as solo)

@@ -155,4 +155,10 @@ int fused20d_launch_any(const F20dLaunch& a, const AdrSrcArg<double>& k);
 // k.src are not read by this kernel.  Launch only while fields are present.
 int fused20d_launch_any(const F20dLaunch& a, const AdrVarArg<double>& k);
 
+// one evaluation of a.n_members members of the adr kind (k_adrens20d<PDE_ADR_ENS, H, ., true, sets>, kernels_generic.h
+// AdrEnsArg): k.coef is a device table of a.n_members rows of ADR_ENS_ROW doubles (a0, a1, nu, r1, r2, r3, two pads), member
+// m reads row m; sets = false: one point set for all, true: [n_members][sd.n_pad], every slice pair-interleaved as a solo
+// set.  Member m's rows are bit-identical to a solo PDE_ADR launch with row m's coefficients on member m's set.
+int fused20d_ens_launch_any(const F20dLaunch& a, const AdrEnsArg& k, bool sets);
+
 }  // namespace pinn

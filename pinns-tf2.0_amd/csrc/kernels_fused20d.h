@@ -250,6 +250,12 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
 // rows; no other lane touches it).  Residual, source subtraction and the four seeds keep their expressions, so a table of
 // constant rows gives PDE_ADR_SRC's bits.  1 / n_b, the Robin triple and the pair exchange are untouched.  Tile loop: the
 // table's address is held in vector registers, as the (alpha, beta) array's is.
+// PDE == PDE_ADR_ENS (PDE_ADR in an ensemble launch, kernels_generic.h; instantiated under the name k_adrens20d), ENS with or
+// without SETS: the slot carries AdrEnsArg, the address of the members' coefficient table [members][8].  Member m = blockIdx.y
+// reads its row at the very top of the kernel, wave-uniform (nothing in front of the loads writes memory, so they are
+// scalar loads); the six then stand where PDE_ADR's by-value AdrCoef stands -- in scalar registers in the one-tile variant,
+// parked with 1 / n_b in lacc[192..] in the tile loop -- and the seed block is PDE_ADR's text.  The member offsets of th, part
+// and (SETS) xs, ts, tgt are the Burgers ensemble's.
 template <bool SETS, bool SAW = false, int PDE = 0>
 using f20d_nu_t = typename std::conditional<PDE == PDE_ADR_VAR, AdrVarArg<double>, typename std::conditional<PDE == PDE_ADR_SRC, AdrSrcArg<double>, typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<double>, typename std::conditional<PDE == PDE_ADR && SAW, AdrPwArgs, typename std::conditional<PDE == PDE_ADR, AdrCoef<double>, typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type>::type>::type>::type>::type>::type>::type;
 __device__ __forceinline__ double f20d_nu(double nu) { return nu; }
@@ -259,11 +265,23 @@ __device__ __forceinline__ double f20d_nu(const double* nu) { return nu[blockIdx
 __device__ __forceinline__ double f20d_nu(const SaArgs& a) { return a.nu; }
 __device__ __forceinline__ double f20d_nu(const AdrPwArgs& a) { return a.k.nu; }
 __device__ __forceinline__ double f20d_nu(const AdrRobinArg<double>& a) { return a.k.nu; }
+__device__ __forceinline__ double f20d_nu(const AdrEnsArg&) { return 0.0; }               // (read from the member's row)
+// what a kernel holds of its member's row: the six coefficients (PDE_ADR_ENS), nothing at all (every other kind)
+struct F20dNoCoef {};
+template <int PDE> using f20d_ens_coef_t = typename std::conditional<PDE == PDE_ADR_ENS, AdrCoef<double>, F20dNoCoef>::type;
+// PDE_ADR_ENS's coefficient argument is NOT one more arm of f20d_nu_t: the alias stands in the kernels' parameter list, so
+// its text is part of every instantiation's mangled name, and a new arm would rename all of them (same code, other symbols).
+// k_adrens20d declares its slot with an alias of its own (PINN_F20D_ARG_T below; dependent on PDE, so that the arms of the
+// shared text this kind never takes stay unchecked), and the host side picks between the two with f20d_arg_t.
+template <int PDE> using f20d_ens_arg_t = typename std::conditional<PDE == PDE_ADR_ENS, AdrEnsArg, F20dNoCoef>::type;
+template <bool SETS, bool SAW, int PDE>
+using f20d_arg_t = typename std::conditional<PDE == PDE_ADR_ENS, AdrEnsArg, f20d_nu_t<SETS, SAW, PDE>>::type;
 
 static_assert(F20D_WIDTH == FW && f20d_layer_first(1) == w20_desc(8, 0).off_w[1] && f20d_layer_first(7) == w20_desc(8, 2).off_w[7] &&
               f20d_layer_first(4) == w20_desc(4, 0).off_w[4] && f20d_n_net(6) == w20_desc(6, 2).n_net,
               "fused20d_api.h's layer offsets are the flat layout's");
 #define PINN_F20D_SPLIT 0
+#define PINN_F20D_ARG_T f20d_nu_t<SETS, SAW, PDE>
 #define PINN_F20D_KERNEL k_fused20d
 #include "kernels_fused20d_kernel.h"
 #undef PINN_F20D_KERNEL
@@ -279,6 +297,14 @@ static_assert(F20D_WIDTH == FW && f20d_layer_first(1) == w20_desc(8, 0).off_w[1]
 #define PINN_F20D_KERNEL k_var20d
 #include "kernels_fused20d_kernel.h"
 #undef PINN_F20D_KERNEL
+// and under the name the ensemble variants of the adr kind are instantiated with (PDE_ADR_ENS only)
+#undef PINN_F20D_ARG_T
+#define PINN_F20D_ARG_T f20d_ens_arg_t<PDE>
+#define PINN_F20D_KERNEL k_adrens20d
+#include "kernels_fused20d_kernel.h"
+#undef PINN_F20D_KERNEL
+#undef PINN_F20D_ARG_T
+#define PINN_F20D_ARG_T f20d_nu_t<SETS, SAW, PDE>
 #undef PINN_F20D_SPLIT
 // and, with the two roles compiled in, under the name of the split one-tile launch (pde 0 and 1, ONE_TILE, solo)
 #if PINN_ONETILE_SUM == 0
@@ -288,12 +314,14 @@ static_assert(F20D_WIDTH == FW && f20d_layer_first(1) == w20_desc(8, 0).off_w[1]
 #undef PINN_F20D_KERNEL
 #undef PINN_F20D_SPLIT
 #endif
+#undef PINN_F20D_ARG_T
 // kernel <PDE, H, ONE_TILE, ENS, SETS, SAW> by its name in the library
 template <int PDE, int H, bool ONE_TILE, bool ENS, bool SETS, bool SAW>
 constexpr auto f20d_kernel() {
   if constexpr (PDE == PDE_ADR_ROBIN) return &k_robin20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
   else if constexpr (PDE == PDE_ADR_SRC) return &k_src20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
   else if constexpr (PDE == PDE_ADR_VAR) return &k_var20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
+  else if constexpr (PDE == PDE_ADR_ENS) return &k_adrens20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
   else return &k_fused20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
 }
 
@@ -302,7 +330,7 @@ constexpr auto f20d_kernel() {
 // of its own, the tile loop otherwise, on a grid of (n_wg, n_members).  With both events given they take the kernel's own
 // begin / end timestamps.  Returns a hipError_t (0 = ok).
 template <int PDE, int H, bool ENS, bool SETS, bool SAW>
-inline int fused20d_launch(const F20dLaunch& a, const f20d_nu_t<SETS, SAW, PDE>& nu) {
+inline int fused20d_launch(const F20dLaunch& a, const f20d_arg_t<SETS, SAW, PDE>& nu) {
   if (!w20_layout_ok(a.nd, H, pde_n_tail(PDE)) || (!ENS && a.n_members != 1)) return (int)hipErrorInvalidValue;
   const size_t lds = fused20d_lds_bytes(H, a.nd.n_theta);
   static unsigned long long attr_set = 0;

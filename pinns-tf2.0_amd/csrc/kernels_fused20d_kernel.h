@@ -5,6 +5,9 @@
 // k_fused20d<...> instantiations in the library is pinned (tests/test_isa_hazards.py counts them) and the Robin, source and
 // coefficient-field variants are additions beside it.  (Not a __device__ body called from two kernels: such a wrapper changed the schedule of the
 // existing instantiations.)  No include guard: it is meant to be included more than once.
+// One more inclusion gives k_adrens20d for PDE_ADR_ENS (the adr kind's ensemble members, ENS with or without SETS); there the
+// coefficient slot's type, PINN_F20D_ARG_T, is f20d_ens_arg_t<PDE> and not f20d_nu_t<SETS, SAW, PDE>, whose text is part of
+// every other kernel's mangled name (kernels_fused20d.h).
 // A fifth inclusion, with PINN_F20D_SPLIT = 1, gives k_split20d: the one-tile kernel of pde 0 and 1 with two roles compiled in
 // (fused20d_api.h: the split launch).  The reverse sweep stands in kernels_fused20d_reverse.h, included below once per role;
 // with PINN_F20D_SPLIT = 0 it is included once, as the whole sweep, and every kernel comes out as it did when the text stood here.
@@ -13,11 +16,13 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
                                                   const double* __restrict__ ts, const double* __restrict__ tgt,
                                                   double* __restrict__ part, const int* __restrict__ row_index, int R,
                                                   int n_tiles, double lbx, double lbt, double sx, double st,
-                                                  f20d_nu_t<SETS, SAW, PDE> nu, SetDesc sd,
+                                                  PINN_F20D_ARG_T nu, SetDesc sd,
                                                   long long* __restrict__ stamps, W20Desc nd_arg) {
   static_assert(ENS || !SETS, "per-member point sets are an ensemble launch");
-  static_assert(!pde_is_adr(PDE) || (!ENS && !SETS && (!SAW || PDE == PDE_ADR)),
+  static_assert(!pde_is_adr(PDE) || PDE == PDE_ADR_ENS || (!ENS && !SETS && (!SAW || PDE == PDE_ADR)),
                 "advection-diffusion-reaction: solo launch; point weights for the fixed-coefficient kind only");
+  static_assert(PDE != PDE_ADR_ENS || (ENS && !SAW && !PINN_F20D_SPLIT),
+                "adr ensemble members: an ensemble launch, shared or per-member point sets, no point weights");
   static_assert(!SAW || ((PDE == 0 || PDE == PDE_ADR) && !ENS), "point weights: Burgers inference or adr, solo launch");
   static_assert(PDE != PDE_ADR_ROBIN || (!ENS && !SETS && !SAW),
                 "Robin points: the fixed-coefficient adr kind only, solo launch, no point weights");
@@ -43,6 +48,14 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       xs += po; ts += po; tgt += po;
     }
   }
+  // PDE_ADR_ENS: this member's row of the coefficient table, wave-uniform, read here -- in front of everything that writes
+  // memory -- so that the six arrive by scalar loads and stand in scalar registers as PDE_ADR's by-value AdrCoef does
+  f20d_ens_coef_t<PDE> ens_k;
+  if constexpr (PDE == PDE_ADR_ENS) {
+    const double* __restrict__ const kr = nu.coef + (size_t)blockIdx.y * ADR_ENS_ROW;
+    ens_k = AdrCoef<double>{kr[0], kr[1], kr[2], kr[3], kr[4], kr[5]};
+  }
+  (void)ens_k;
   double* const gacc_all = wl + nwp;                  // tile loop: 4 x NBLK x 16 accumulators; one tile: 2 staging buffers
   double* const lacc_all = gacc_all + (ONE_TILE ? fused20d_stage_doubles(H) : 4 * NBLK * 16);
 
@@ -125,6 +138,14 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
     if ((tid & 63) == 0) {
       adr_park[0] = nu.a0; adr_park[1] = nu.a1; adr_park[2] = nu.nu; adr_park[3] = nu.r1; adr_park[4] = nu.r2;
       adr_park[5] = nu.r3; adr_park[6] = sd.inv_nb;
+    }
+  }
+  // PDE_ADR_ENS, tile loop: the same seven, the six from the member's row
+  if constexpr (PDE == PDE_ADR_ENS && !ONE_TILE) {
+    adr_park = lacc_all + wave * 256 + 192;
+    if ((tid & 63) == 0) {
+      adr_park[0] = ens_k.a0; adr_park[1] = ens_k.a1; adr_park[2] = ens_k.nu; adr_park[3] = ens_k.r1; adr_park[4] = ens_k.r2;
+      adr_park[5] = ens_k.r3; adr_park[6] = sd.inv_nb;
     }
   }
   // PDE_ADR_ROBIN, PDE_ADR_SRC and PDE_ADR_VAR, tile loop: the same seven and the Robin block's first point, length and 1 / N_w; the (alpha, beta) array's
@@ -536,6 +557,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       double inv_nw = 0.0;
       if constexpr (ONE_TILE) {
         if constexpr (pde_adr_robin(PDE)) { kc = nu.k; rb_j = pt - nu.first; rb_n = nu.n; inv_nw = nu.inv_nw; }
+        else if constexpr (PDE == PDE_ADR_ENS) kc = ens_k;
         else kc = nu;
         inv_nb = sd.inv_nb;
       } else {

@@ -78,15 +78,25 @@ constexpr int PDE_ADR_SRC = 6;
 // expressions are PDE_ADR_SRC's, only the origin of the six operands differs: a table whose every row is the constant set
 // gives PDE_ADR_SRC's (and, with no source, PDE_ADR's) bits.  The engine dispatches here only while fields are present.
 constexpr int PDE_ADR_VAR = 7;
+// Template number of PINN_PDE_ADR in an ensemble launch (pinn_adr_ens_create; k_fused20d's ENS variants only, instantiated
+// under the name k_adrens20d): PDE_ADR's equation, seeds and loss-row layout, with the six coefficients read per MEMBER.  Where
+// PDE_ADR passes its coefficients by value travels AdrEnsArg, the address of a device table [members][8] -- a0, a1, nu, r1,
+// r2, r3 and two pad doubles, so a row is 64 bytes -- and member m = blockIdx.y reads row m, wave-uniform, once in the
+// prologue.  The expressions are PDE_ADR's: a member's rows are the bits of a solo PDE_ADR launch with that member's
+// coefficients.  No generic-path kernel is instantiated with it.
+constexpr int PDE_ADR_ENS = 8;
+constexpr int ADR_ENS_ROW = 8;           // doubles per row of the table
 constexpr bool pde_is_adr(int PDE) {
-  return PDE == PDE_ADR || PDE == PDE_ADR_IDE || PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR;
+  return PDE == PDE_ADR || PDE == PDE_ADR_IDE || PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR ||
+         PDE == PDE_ADR_ENS;
 }
 // the kinds whose six coefficients are run-time constants (PDE_ADR_IDE reads them from the weight vector, PDE_ADR_VAR from
 // its table): the predicate keeps this meaning, and PDE_ADR_VAR is not among them
 constexpr bool pde_adr_fixed(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC; }
 // the kinds that share k_fused20d's seed block and loss-row layout of PDE_ADR: the fixed ones and PDE_ADR_VAR, whose block
 // differs in where a collocation point's six coefficients come from and in nothing else
-constexpr bool pde_adr_seed_block(int PDE) { return pde_adr_fixed(PDE) || PDE == PDE_ADR_VAR; }
+// (and PDE_ADR_ENS, whose six come from its member's row of a table)
+constexpr bool pde_adr_seed_block(int PDE) { return pde_adr_fixed(PDE) || PDE == PDE_ADR_VAR || PDE == PDE_ADR_ENS; }
 // the kinds that carry a Robin block behind the collocation block
 constexpr bool pde_adr_robin(int PDE) { return PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR; }
 // the kinds that subtract s_i = tgt[point] at a collocation point
@@ -111,6 +121,10 @@ template <typename real> struct AdrSrcArg : AdrRobinArg<real> {
 // read at a collocation point.  kf is touched by collocation points only: the table has n_f rows.
 template <typename real> struct AdrVarArg : AdrSrcArg<real> {
   const real* kf;
+};
+// PDE_ADR_ENS: the members' coefficient table, coef[ADR_ENS_ROW * m + j] = coefficient j of member m; 64-byte rows
+struct AdrEnsArg {
+  const double* coef;
 };
 // row i of the table (every load inside the caller's collocation branch)
 template <typename real> __device__ __forceinline__ AdrCoef<real> adr_row(const real* __restrict__ kf, int i) {

@@ -297,6 +297,13 @@ _SIGNATURES = {
     "pinn_set_source": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
     # coefficient fields of the adr kind (include/pinn_hip.h: pinn_set_coef_fields)
     "pinn_set_coef_fields": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
+    # ensembles of the adr kind (include/pinn_hip.h: pinn_adr_ens_create)
+    "pinn_adr_ens_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _c_int_p, ctypes.c_int, _c_double_p,
+                                           _c_double_p, ctypes.c_int, ctypes.c_int]),
+    "pinn_adr_ens_set_boundary": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int64]),
+    "pinn_adr_ensk_set_boundary": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int64]),
+    "pinn_adr_ensk_set_params": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int]),
+    "pinn_adr_ens_get_params": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int]),
 }
 
 
@@ -949,11 +956,14 @@ class Ensemble(object):
         self.pde = pde
         arr = (ctypes.c_int * len(self.layers))(*self.layers)
         lb, ub = _f64(lb, (2,)), _f64(ub, (2,))
-        self._check(self._lib.pinn_ens_create(ctypes.byref(self._h), arr, len(self.layers), _dp(lb), _dp(ub),
-                                              kind, DTYPES[dtype], int(device), int(n_members)))
+        self._check(self._create(arr, lb, ub, kind, DTYPES[dtype], int(device), int(n_members)))
         k, n = ctypes.c_int(0), ctypes.c_int64(0)
         self._check(self._lib.pinn_ens_size(self._h, ctypes.byref(k), ctypes.byref(n)))
         self.n_members, self.n_params = k.value, n.value
+
+    def _create(self, arr, lb, ub, kind, dtype, device, n_members):
+        return self._lib.pinn_ens_create(ctypes.byref(self._h), arr, len(self.layers), _dp(lb), _dp(ub), kind, dtype,
+                                         device, n_members)
 
     def _check(self, rc):
         if rc != 0:
@@ -1101,3 +1111,45 @@ class Ensemble(object):
         self._check(self._lib.pinn_ens_get_status(self._h, n.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                                   bad.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return n, bad
+
+
+class AdrEnsemble(Ensemble):
+    """K members of one float64 net of the adr kind (kernel path 7) trained side by side (include/pinn_hip.h:
+    pinn_adr_ens_create): Ensemble's surface, and every member with its own six coefficients (a0, a1, nu, r1, r2, r3) and,
+    per member or shared, periodic boundary pairs.  Member k ends bit-identical to an Engine(pde="adr") trained alone from
+    the same weights, coefficients and points with the same calls."""
+
+    def __init__(self, layers, lb, ub, n_members, device=0):
+        Ensemble.__init__(self, layers, lb, ub, n_members, pde="adr", dtype="f64", device=device)
+
+    def _create(self, arr, lb, ub, kind, dtype, device, n_members):
+        return self._lib.pinn_adr_ens_create(ctypes.byref(self._h), arr, len(self.layers), _dp(lb), _dp(ub), device,
+                                             n_members)
+
+    def set_boundary(self, X_lb, X_ub, n_total=None):
+        """periodic pairs: X_lb, X_ub [n, 2] for every member, or [K, n, 2]: member k's own pairs"""
+        X_lb, per = self._per_member(X_lb, "X_lb", 2)
+        X_ub, per_ub = self._per_member(X_ub, "X_ub", 2)
+        if per != per_ub or X_lb.shape != X_ub.shape:
+            raise ValueError("X_lb %s and X_ub %s must have one shape" % (X_lb.shape, X_ub.shape))
+        n = X_lb.shape[-2]
+        nt = n if n_total is None else int(n_total)
+        fn = self._lib.pinn_adr_ensk_set_boundary if per else self._lib.pinn_adr_ens_set_boundary
+        self._check(fn(self._h, _dp(X_lb), _dp(X_ub), n, nt))
+
+    def set_pde_params(self, *p):
+        """six numbers (a0, a1, nu, r1, r2, r3) for every member, or [K, 6]: member k's own row"""
+        if len(p) == 1 and np.ndim(p[0]) == 2:
+            rows = _f64(p[0])
+            if rows.shape != (self.n_members, 6):
+                raise ValueError("coefficients: per-member array must be [K=%d, 6], got %s" % (self.n_members, rows.shape))
+            self._check(self._lib.pinn_adr_ensk_set_params(self._h, _dp(rows), self.n_members))
+            return
+        p = _f64(p).reshape(-1)
+        self._check(self._lib.pinn_ens_set_pde_params(self._h, _dp(p), p.size))
+
+    def get_pde_params(self):
+        """-> [K, 6]"""
+        rows = np.empty((self.n_members, 6), dtype=np.float64)
+        self._check(self._lib.pinn_adr_ens_get_params(self._h, _dp(rows), self.n_members))
+        return rows

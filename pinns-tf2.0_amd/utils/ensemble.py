@@ -1,17 +1,20 @@
 """NeuralNetworkEnsemble: K Burgers PINNs trained side by side (several seeds, a learning-rate or viscosity sweep, bagged
 point sets, repeated identification runs) by one engine ensemble (pinn_native.Ensemble, include/pinn_hip.h pinn_ens_* /
-pinn_ensk_*).
+pinn_ensk_*), or K PINNs of the "adr" kind, each with its own six coefficients (pinn_native.AdrEnsemble,
+pinn_adr_ens_create): Allen-Cahn over interface widths, Fisher-KPP over rho and D.
 
-Scope: float64, kernel path 7 -- Burgers inference (pde "burgers") and identification ("burgers_ide"), 2-20-...-20-1 nets
-with 4, 6 or 8 hidden layers, one GPU.  The members share every hyperparameter except the per-member overrides in
-`members`:
+Scope: float64, kernel path 7 -- Burgers inference (pde "burgers"), identification ("burgers_ide") and the
+advection-diffusion-reaction kind with fixed coefficients ("adr"), 2-20-...-20-1 nets with 4, 6 or 8 hidden layers, one GPU.
+The members share every hyperparameter except the per-member overrides in `members`:
     seed, init_scale          the initial weights (member k's vector is exactly NeuralNetwork._initial_weights of hp
                               updated with member k's overrides)
     tf_lr, nt_lr, nt_epochs   Adam learning rate, L-BFGS learningRate and maxIter
-    nu                        the viscosity (overrides set_pde_params for that member; identification: unused)
+    nu                        the viscosity (overrides set_pde_params for that member; identification: unused; not "adr")
+    adr                       "adr" only: the member's six coefficients a0, a1, nu, r1, r2, r3 (overrides set_pde_params)
     resample_seed             the member's collocation redraws (hp["resample_every"]): seed resample_seed + epoch
 The point sets are shared, or one per member: set_collocation(X_f) and fit(X_u, u) take [n, 2] / [n, 1] arrays for
-all members or [K, n, 2] / [K, n, 1] arrays, member k's at index k (every member with the same n).
+all members or [K, n, 2] / [K, n, 1] arrays, member k's at index k (every member with the same n); so does
+_set_boundary(X_lb, X_ub), the periodic pairs of the "adr" kind.
 fit() follows NeuralNetwork.fit's float64 schedule (Adam tf_epochs with NeuralNetwork.tf_optimization's chunks and
 redraws, then L-BFGS with the same lbfgs_begin arguments) with no restart guard; member k ends bit-identical to a
 NeuralNetwork of its own hp trained alone on its own points.
@@ -23,14 +26,16 @@ import numpy as np
 
 sys.path.append(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from neuralnetwork import NeuralNetwork  # noqa: E402
-from pinn_native import Ensemble  # noqa: E402
+from pinn_native import AdrEnsemble, Ensemble  # noqa: E402
 
-MEMBER_KEYS = ("seed", "init_scale", "tf_lr", "nt_lr", "nt_epochs", "nu", "resample_seed")
+MEMBER_KEYS = ("seed", "init_scale", "tf_lr", "nt_lr", "nt_epochs", "nu", "adr", "resample_seed")
+ADR_DEFAULT = (0.0, 1.0, 0.01 / np.pi, 0.0, 0.0, 0.0)      # a new adr context's coefficients (Burgers)
 _LINE = "{tag} = {epoch:6d}  elapsed = {total}  loss min = {lo:.4e}  median = {med:.4e}  max = {hi:.4e}  {custom}"
 
 
 class NeuralNetworkEnsemble(object):
-    engine_class = Ensemble            # (the host tests put a stub here)
+    engine_class = Ensemble            # (the host tests put a stub here; pde "adr" builds adr_engine_class unless one stands here)
+    adr_engine_class = AdrEnsemble
 
     def __init__(self, hp, logger, ub, lb, members, pde="burgers"):
         if not members:
@@ -39,6 +44,13 @@ class NeuralNetworkEnsemble(object):
             bad = set(m) - set(MEMBER_KEYS)
             if bad:
                 raise ValueError("per-member overrides are %s; got %s" % (", ".join(MEMBER_KEYS), sorted(bad)))
+        for m in members:
+            if "nu" in m and pde == "adr":
+                raise ValueError('the member key "nu" is the Burgers kinds\'; an "adr" member takes "adr": six coefficients')
+            if "adr" in m and pde != "adr":
+                raise ValueError('the member key "adr" is for pde "adr"; the %s kind takes "nu"' % pde)
+            if "adr" in m and np.asarray(m["adr"], dtype=np.float64).shape != (6,):
+                raise ValueError('the member key "adr" takes six numbers (a0, a1, nu, r1, r2, r3), got %r' % (m["adr"],))
         if hp.get("dtype", "f64") not in ("f64", "float64"):
             raise ValueError("ensembles are float64 only")
         if hp.get("resample", "lhs") != "lhs":
@@ -66,12 +78,17 @@ class NeuralNetworkEnsemble(object):
         self.resample_seeds = np.array([int(h.get("resample_seed", 1234)) for h in self.member_hp], dtype=np.int64)
         self._n_design = 0
         device = hp.get("device", os.environ.get("PINN_DEVICE", 0))
-        self._engine = self.engine_class(self.layers, self.lb, self.ub, self.n_members, pde=pde, dtype="f64",
-                                         device=int(device))
+        if pde == "adr" and self.engine_class is Ensemble:
+            self._engine = self.adr_engine_class(self.layers, self.lb, self.ub, self.n_members, device=int(device))
+        else:
+            self._engine = self.engine_class(self.layers, self.lb, self.ub, self.n_members, pde=pde, dtype="f64",
+                                             device=int(device))
         self.initial_weights = self._member_weights()
         self._engine.set_weights(self.initial_weights)
         if any("nu" in m for m in members):      # per-member viscosities (a later set_pde_params keeps them)
             self.set_pde_params(float(hp.get("nu", 0.0)))
+        if any("adr" in m for m in members):     # per-member coefficients (a later set_pde_params keeps them)
+            self.set_pde_params(hp.get("adr", ADR_DEFAULT))
         self.adam_losses = np.zeros((0, self.n_members))
         self.nt_log = [([], []) for _ in range(self.n_members)]       # per member: L-BFGS (iterations, losses)
         self.nt_done = np.zeros(self.n_members, dtype=np.int32)
@@ -105,8 +122,31 @@ class NeuralNetworkEnsemble(object):
         self._engine.set_collocation(X_f)
         self._n_design = X_f.shape[-2]
 
+    def _set_boundary(self, X_lb, X_ub):
+        """periodic pairs of the "adr" kind: X_lb, X_ub [n, 2] for every member, or [K, n, 2]: member k's own pairs"""
+        if self.pde != "adr":
+            raise ValueError('_set_boundary: periodic pairs are for pde "adr"; the %s ensemble has none' % self.pde)
+        X_lb, X_ub = np.asarray(X_lb, dtype=np.float64), np.asarray(X_ub, dtype=np.float64)
+        if X_lb.ndim != 3:
+            X_lb, X_ub = X_lb.reshape(-1, 2), X_ub.reshape(-1, 2)
+        self._engine.set_boundary(X_lb, X_ub)
+
     def set_pde_params(self, nu):
-        """nu for every member (a member's "nu" override wins), or nu [K]"""
+        """nu for every member (a member's "nu" override wins), or nu [K]; pde "adr": six coefficients for every member (a
+        member's "adr" override wins), or [K, 6]"""
+        if self.pde == "adr":
+            p = np.asarray(nu, dtype=np.float64)
+            if p.shape != (6,) and p.shape != (self.n_members, 6):
+                raise ValueError("set_pde_params: six coefficients or [K=%d, 6], got %s" % (self.n_members, p.shape))
+            rows = np.broadcast_to(p, (self.n_members, 6)).copy()
+            for k, m in enumerate(self.members):
+                if "adr" in m:
+                    rows[k] = np.asarray(m["adr"], dtype=np.float64)
+            if p.ndim == 1 and not any("adr" in m for m in self.members):
+                self._engine.set_pde_params(p.copy())
+            else:
+                self._engine.set_pde_params(rows)
+            return
         nu_k = np.broadcast_to(np.asarray(nu, dtype=np.float64), (self.n_members,)).copy()
         for k, m in enumerate(self.members):
             if "nu" in m:

@@ -932,14 +932,8 @@ static int launch_fused20d(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
                     c->sd.n_pad / 64, fused20d_split_grid(c->sd.n_pad / 64), c->n_cu);
       a.split = sp == 1;
     }
-    if constexpr (PDE == PDE_ADR) {
-      if (pw) rc = fused20d_launch_any(a, AdrPwArgs{pde_coef<double, PDE_ADR>(c), c->pw.arr.buf, af ? af->bc_pw : 0.0});
-      else rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR>(c));
-    }
-    else if constexpr (PDE == PDE_ADR_ROBIN) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_ROBIN>(c));
-    else if constexpr (PDE == PDE_ADR_SRC) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_SRC>(c));
-    else if constexpr (PDE == PDE_ADR_VAR) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_VAR>(c));
-    else if constexpr (PDE == PDE_ADR_IDE) rc = fused20d_launch_any(a, pde_coef<double, PDE_ADR_IDE>(c));
+    if (pw) rc = fused20d_launch_any(a, AdrPwArgs{pde_coef<double, PDE_ADR>(c), c->pw.arr.buf, af ? af->bc_pw : 0.0});
+    else if constexpr (pde_is_adr(PDE)) rc = fused20d_launch_any(a, pde_coef<double, PDE>(c));
     else if (weighted) rc = fused20d_launch_any(a, SaArgs{(double)c->nu, c->sa.arr.buf, af ? af->alpha_sa : 0.0});
     else rc = fused20d_launch_any(PDE, a, (double)c->nu);
   }
@@ -3212,7 +3206,7 @@ struct pinn_ens {
   double *k_xs = nullptr, *k_ts = nullptr, *k_tgt = nullptr, *k_nud = nullptr;   // [K][n_pad] x 3, [K]
   size_t k_cap = 0;
   // an ensemble of the adr kind (pinn_adr_ens_create): every member has its own six coefficients in BOTH modes -- the host
-  // rows [K][6] and the device table [K][ADR_ENS_ROW] k_adrens20d reads, there from creation and re-uploaded when dirty --
+  // rows [K][6] and the device table [K][ADR_ENS_ROW] k_fused20d<PDE_ADR_ENS> reads, there from creation and re-uploaded when dirty --
   // and, in per-member mode, its own periodic pairs (one common n)
   bool adr = false, coef_dirty = true;
   std::vector<double> coef;                    // [K][6]

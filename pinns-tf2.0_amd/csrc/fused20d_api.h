@@ -89,7 +89,8 @@ struct F20dLaunch {
   bool split = false;            // the split one-tile plan (pde 0 and 1, solo, n_wg >= tiles, fused20d_split_built() only)
 };
 
-// one loss+gradient evaluation, 4, 6 or 8 hidden layers; every entry point returns a hipError_t
+// one loss+gradient evaluation, 4, 6 or 8 hidden layers; every entry point returns a hipError_t.  All of them launch the
+// one kernel name, k_fused20d, with the template arguments of their variant (kernels_fused20d_kernel.h)
 // pde 0: Burgers inference, 1: identification
 int fused20d_launch_any(int pde, const F20dLaunch& a, double nu);
 
@@ -144,18 +145,18 @@ int fused20d_launch_any(const F20dLaunch& a, const AdrPwArgs& k);
 // device array of 2 k.n doubles, 16-byte aligned; g_j stands in tgt at the Robin point's own index.  Launch only with k.n > 0.
 int fused20d_launch_any(const F20dLaunch& a, const AdrRobinArg<double>& k);
 
-// one evaluation of the adr kind with a source term (k_src20d<PDE_ADR_SRC, H, .>, kernels_generic.h AdrSrcArg): the same set,
+// one evaluation of the adr kind with a source term (k_fused20d<PDE_ADR_SRC, H, .>, kernels_generic.h AdrSrcArg): the same set,
 // s_i in a.tgt at the collocation point's own index; the Robin part of k is as above, k.n may be 0 (k.ab is not read then);
 // k.src is not read by this kernel.  Launch only while a source is present.
 int fused20d_launch_any(const F20dLaunch& a, const AdrSrcArg<double>& k);
 
-// one evaluation of the adr kind with per-point coefficient fields (k_var20d<PDE_ADR_VAR, H, .>, kernels_generic.h
+// one evaluation of the adr kind with per-point coefficient fields (k_fused20d<PDE_ADR_VAR, H, .>, kernels_generic.h
 // AdrVarArg): the same set; k.kf is the table of a.sd.n_f rows of six doubles, 16-byte aligned, row i for collocation point
 // 2 n_b + n_u + i; the collocation slots of a.tgt hold s_i or zeros; the Robin part of k is as above, k.n may be 0; k.k and
 // k.src are not read by this kernel.  Launch only while fields are present.
 int fused20d_launch_any(const F20dLaunch& a, const AdrVarArg<double>& k);
 
-// one evaluation of a.n_members members of the adr kind (k_adrens20d<PDE_ADR_ENS, H, ., true, sets>, kernels_generic.h
+// one evaluation of a.n_members members of the adr kind (k_fused20d<PDE_ADR_ENS, H, ., true, sets>, kernels_generic.h
 // AdrEnsArg): k.coef is a device table of a.n_members rows of ADR_ENS_ROW doubles (a0, a1, nu, r1, r2, r3, two pads), member
 // m reads row m; sets = false: one point set for all, true: [n_members][sd.n_pad], every slice pair-interleaved as a solo
 // set.  Member m's rows are bit-identical to a solo PDE_ADR launch with row m's coefficients on member m's set.

@@ -27,7 +27,7 @@ void fused20d_row_index(const NetDesc& nd, int H, int* out) {
 
 // k_fused20d<PDE, H, ., ENS, SETS, SAW> at the depth of the net
 template <int PDE, bool ENS, bool SETS, bool SAW>
-static int launch_depth(const F20dLaunch& a, const f20d_arg_t<SETS, SAW, PDE>& nu) {
+static int launch_depth(const F20dLaunch& a, const f20d_slot_t<PDE, SETS, SAW>& nu) {
   switch (a.nd.n_hidden) {     // the AGPR stash holds (H - 2) x 40 registers: depths up to 8 fit the 256 of a wave
     case 4: return fused20d_launch<PDE, 4, ENS, SETS, SAW>(a, nu);
     case 6: return fused20d_launch<PDE, 6, ENS, SETS, SAW>(a, nu);
@@ -35,9 +35,9 @@ static int launch_depth(const F20dLaunch& a, const f20d_arg_t<SETS, SAW, PDE>& n
     default: return (int)hipErrorInvalidValue;
   }
 }
-// the Burgers kinds share their entry points: pde 0 or 1 at run time
+// the Burgers kinds share their entry points (and their slot's type): pde 0 or 1 at run time
 template <bool ENS, bool SETS>
-static int launch_burgers(int pde, const F20dLaunch& a, const f20d_nu_t<SETS>& nu) {
+static int launch_burgers(int pde, const F20dLaunch& a, const f20d_slot_t<0, SETS, false>& nu) {
   return pde == 1 ? launch_depth<1, ENS, SETS, false>(a, nu) : launch_depth<0, ENS, SETS, false>(a, nu);
 }
 
@@ -52,7 +52,7 @@ int fused20d_launch_any(const F20dLaunch& a, const AdrPwArgs& k) { return launch
 int fused20d_launch_any(const F20dLaunch& a, const AdrRobinArg<double>& k) { return launch_depth<PDE_ADR_ROBIN, false, false, false>(a, k); }
 int fused20d_launch_any(const F20dLaunch& a, const AdrSrcArg<double>& k) { return launch_depth<PDE_ADR_SRC, false, false, false>(a, k); }
 int fused20d_launch_any(const F20dLaunch& a, const AdrVarArg<double>& k) { return launch_depth<PDE_ADR_VAR, false, false, false>(a, k); }
-// the adr kind's ensemble launch (k_adrens20d): a row of coefficients per member, the point set shared or one per member
+// the adr kind's ensemble launch: a row of coefficients per member, the point set shared or one per member
 int fused20d_ens_launch_any(const F20dLaunch& a, const AdrEnsArg& k, bool sets) {
   return sets ? launch_depth<PDE_ADR_ENS, true, true, false>(a, k) : launch_depth<PDE_ADR_ENS, true, false, false>(a, k);
 }

@@ -231,33 +231,40 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
 // The array is indexed by the point (fused20d_api.h): a pair's two lanes read the lo point's entry, so both seed with the
 // pair's one lambda, and only the slot-0 lane of the lo point steps it.  Coefficients, 1 / n_b and the array's header are
 // parked per wave as PDE_ADR_IDE parks its values, in both variants; inv_n * lambda^2 is formed as SAW forms it for pde 0.
-// PDE == PDE_ADR_ROBIN (PDE_ADR with Robin points, kernels_generic.h; instantiated under the name k_robin20d, see
-// kernels_fused20d_kernel.h), solo launch, no point weights: the slot carries
+// PDE == PDE_ADR_ROBIN (PDE_ADR with Robin points, kernels_generic.h), solo launch, no point weights: the slot carries
 // AdrRobinArg<double> -- the six coefficients, the (alpha, beta) array, the Robin block's first point and length, 1 / N_w.  The
 // seed block is PDE_ADR's with one more class branch behind the pairs' (the two DPP moves stay in front of it): a Robin lane
 // loads its (alpha, beta) pair (one 16-byte load, issued at the seed block: the one-tile ADR variants have 8 vector
 // registers left, too few to hold two more doubles across the forward sweep) and g = tgt[pt], its slot-0 lane adds
 // r^2 / N_w to the boundary slot lacc[128], and it seeds sb[0] and sb[1].  Tile loop: first, length and 1 / N_w are parked
 // behind the other seven in lacc[192..] (slots 7-9) and the array's address is held in vector registers, as SAW holds its own.
-// PDE == PDE_ADR_SRC (PDE_ADR with a source term, kernels_generic.h; instantiated under the name k_src20d): PDE_ADR_ROBIN's
+// PDE == PDE_ADR_SRC (PDE_ADR with a source term, kernels_generic.h): PDE_ADR_ROBIN's
 // text -- the slot carries AdrSrcArg<double>, the Robin count may be 0 -- with one more operation in the collocation class:
 // f is formed as PDE_ADR forms it, then s_i = tgt[pt] is subtracted, uncontracted (a zero source gives PDE_ADR's bits).  The
 // value is loaded at the seed block.  No seed formula changes.
-// PDE == PDE_ADR_VAR (PDE_ADR with per-point coefficient fields, kernels_generic.h; instantiated under the name k_var20d):
+// PDE == PDE_ADR_VAR (PDE_ADR with per-point coefficient fields, kernels_generic.h):
 // PDE_ADR_SRC's text -- the slot carries AdrVarArg<double>, the Robin count may be 0, the collocation slots of tgt are zero
 // without a source -- with one change in the collocation class: the six coefficients are the point's own row of the table,
 // kf + 6 (pt - 2 n_b - n_u), three 16-byte loads issued at the seed block inside the collocation branch (the table has n_f
 // rows; no other lane touches it).  Residual, source subtraction and the four seeds keep their expressions, so a table of
 // constant rows gives PDE_ADR_SRC's bits.  1 / n_b, the Robin triple and the pair exchange are untouched.  Tile loop: the
 // table's address is held in vector registers, as the (alpha, beta) array's is.
-// PDE == PDE_ADR_ENS (PDE_ADR in an ensemble launch, kernels_generic.h; instantiated under the name k_adrens20d), ENS with or
+// PDE == PDE_ADR_ENS (PDE_ADR in an ensemble launch, kernels_generic.h), ENS with or
 // without SETS: the slot carries AdrEnsArg, the address of the members' coefficient table [members][8].  Member m = blockIdx.y
 // reads its row at the very top of the kernel, wave-uniform (nothing in front of the loads writes memory, so they are
 // scalar loads); the six then stand where PDE_ADR's by-value AdrCoef stands -- in scalar registers in the one-tile variant,
 // parked with 1 / n_b in lacc[192..] in the tile loop -- and the seed block is PDE_ADR's text.  The member offsets of th, part
 // and (SETS) xs, ts, tgt are the Burgers ensemble's.
-template <bool SETS, bool SAW = false, int PDE = 0>
-using f20d_nu_t = typename std::conditional<PDE == PDE_ADR_VAR, AdrVarArg<double>, typename std::conditional<PDE == PDE_ADR_SRC, AdrSrcArg<double>, typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<double>, typename std::conditional<PDE == PDE_ADR && SAW, AdrPwArgs, typename std::conditional<PDE == PDE_ADR, AdrCoef<double>, typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, typename std::conditional<SETS, const double*, typename std::conditional<SAW, SaArgs, double>::type>::type>::type>::type>::type>::type>::type>::type;
+//
+// The type of the slot: what the kind passes everywhere (pde_coef_t) unless the variant puts something else there.  A trait
+// with a specialisation per exception: the kernels' mangled names spell F20dArg<PDE, SETS, SAW>::type and nothing about
+// which specialisations exist, so a new variant adds a line here (or to PdeCoef, kernels_generic.h) and renames no kernel.
+template <int PDE, bool SETS, bool SAW> struct F20dArg { using type = pde_coef_t<double, PDE>; };
+template <> struct F20dArg<0, true, false> { using type = const double*; };
+template <> struct F20dArg<1, true, false> { using type = const double*; };
+template <> struct F20dArg<0, false, true> { using type = SaArgs; };
+template <> struct F20dArg<PDE_ADR, false, true> { using type = AdrPwArgs; };
+template <int PDE, bool SETS, bool SAW> using f20d_slot_t = typename F20dArg<PDE, SETS, SAW>::type;
 __device__ __forceinline__ double f20d_nu(double nu) { return nu; }
 __device__ __forceinline__ double f20d_nu(const AdrIdeArg&) { return 0.0; }
 __device__ __forceinline__ double f20d_nu(const AdrCoef<double>& k) { return k.nu; }
@@ -267,46 +274,19 @@ __device__ __forceinline__ double f20d_nu(const AdrPwArgs& a) { return a.k.nu; }
 __device__ __forceinline__ double f20d_nu(const AdrRobinArg<double>& a) { return a.k.nu; }
 __device__ __forceinline__ double f20d_nu(const AdrEnsArg&) { return 0.0; }               // (read from the member's row)
 // what a kernel holds of its member's row: the six coefficients (PDE_ADR_ENS), nothing at all (every other kind)
-struct F20dNoCoef {};
-template <int PDE> using f20d_ens_coef_t = typename std::conditional<PDE == PDE_ADR_ENS, AdrCoef<double>, F20dNoCoef>::type;
-// PDE_ADR_ENS's coefficient argument is NOT one more arm of f20d_nu_t: the alias stands in the kernels' parameter list, so
-// its text is part of every instantiation's mangled name, and a new arm would rename all of them (same code, other symbols).
-// k_adrens20d declares its slot with an alias of its own (PINN_F20D_ARG_T below; dependent on PDE, so that the arms of the
-// shared text this kind never takes stay unchecked), and the host side picks between the two with f20d_arg_t.
-template <int PDE> using f20d_ens_arg_t = typename std::conditional<PDE == PDE_ADR_ENS, AdrEnsArg, F20dNoCoef>::type;
-template <bool SETS, bool SAW, int PDE>
-using f20d_arg_t = typename std::conditional<PDE == PDE_ADR_ENS, AdrEnsArg, f20d_nu_t<SETS, SAW, PDE>>::type;
+template <int PDE> struct F20dEnsCoef { struct type {}; };
+template <> struct F20dEnsCoef<PDE_ADR_ENS> { using type = AdrCoef<double>; };
+template <int PDE> using f20d_ens_coef_t = typename F20dEnsCoef<PDE>::type;
 
 static_assert(F20D_WIDTH == FW && f20d_layer_first(1) == w20_desc(8, 0).off_w[1] && f20d_layer_first(7) == w20_desc(8, 2).off_w[7] &&
               f20d_layer_first(4) == w20_desc(4, 0).off_w[4] && f20d_n_net(6) == w20_desc(6, 2).n_net,
               "fused20d_api.h's layer offsets are the flat layout's");
+// The kernel text, once under each of its two names: k_fused20d, and k_split20d with the two roles compiled in.
 #define PINN_F20D_SPLIT 0
-#define PINN_F20D_ARG_T f20d_nu_t<SETS, SAW, PDE>
 #define PINN_F20D_KERNEL k_fused20d
 #include "kernels_fused20d_kernel.h"
 #undef PINN_F20D_KERNEL
-// the same text under the name the Robin variants of the adr kind are instantiated with (PDE_ADR_ROBIN only)
-#define PINN_F20D_KERNEL k_robin20d
-#include "kernels_fused20d_kernel.h"
-#undef PINN_F20D_KERNEL
-// and under the name the source-term variants are instantiated with (PDE_ADR_SRC only)
-#define PINN_F20D_KERNEL k_src20d
-#include "kernels_fused20d_kernel.h"
-#undef PINN_F20D_KERNEL
-// and under the name the coefficient-field variants are instantiated with (PDE_ADR_VAR only)
-#define PINN_F20D_KERNEL k_var20d
-#include "kernels_fused20d_kernel.h"
-#undef PINN_F20D_KERNEL
-// and under the name the ensemble variants of the adr kind are instantiated with (PDE_ADR_ENS only)
-#undef PINN_F20D_ARG_T
-#define PINN_F20D_ARG_T f20d_ens_arg_t<PDE>
-#define PINN_F20D_KERNEL k_adrens20d
-#include "kernels_fused20d_kernel.h"
-#undef PINN_F20D_KERNEL
-#undef PINN_F20D_ARG_T
-#define PINN_F20D_ARG_T f20d_nu_t<SETS, SAW, PDE>
 #undef PINN_F20D_SPLIT
-// and, with the two roles compiled in, under the name of the split one-tile launch (pde 0 and 1, ONE_TILE, solo)
 #if PINN_ONETILE_SUM == 0
 #define PINN_F20D_SPLIT 1
 #define PINN_F20D_KERNEL k_split20d
@@ -314,31 +294,21 @@ static_assert(F20D_WIDTH == FW && f20d_layer_first(1) == w20_desc(8, 0).off_w[1]
 #undef PINN_F20D_KERNEL
 #undef PINN_F20D_SPLIT
 #endif
-#undef PINN_F20D_ARG_T
-// kernel <PDE, H, ONE_TILE, ENS, SETS, SAW> by its name in the library
-template <int PDE, int H, bool ONE_TILE, bool ENS, bool SETS, bool SAW>
-constexpr auto f20d_kernel() {
-  if constexpr (PDE == PDE_ADR_ROBIN) return &k_robin20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
-  else if constexpr (PDE == PDE_ADR_SRC) return &k_src20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
-  else if constexpr (PDE == PDE_ADR_VAR) return &k_var20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
-  else if constexpr (PDE == PDE_ADR_ENS) return &k_adrens20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
-  else return &k_fused20d<PDE, H, ONE_TILE, ENS, SETS, SAW>;
-}
 
 // One loss+gradient evaluation by k_fused20d<PDE, H, ., ENS, SETS, SAW> (F20dLaunch, fused20d_api.h; nu: the variant's
 // coefficient argument).  Every member runs the solo launch plan: the one-tile instantiation when each tile has a workgroup
 // of its own, the tile loop otherwise, on a grid of (n_wg, n_members).  With both events given they take the kernel's own
 // begin / end timestamps.  Returns a hipError_t (0 = ok).
 template <int PDE, int H, bool ENS, bool SETS, bool SAW>
-inline int fused20d_launch(const F20dLaunch& a, const f20d_arg_t<SETS, SAW, PDE>& nu) {
+inline int fused20d_launch(const F20dLaunch& a, const f20d_slot_t<PDE, SETS, SAW>& nu) {
   if (!w20_layout_ok(a.nd, H, pde_n_tail(PDE)) || (!ENS && a.n_members != 1)) return (int)hipErrorInvalidValue;
   const size_t lds = fused20d_lds_bytes(H, a.nd.n_theta);
   static unsigned long long attr_set = 0;
   if (first_call_on_device(attr_set)) {
-    hipError_t e = hipFuncSetAttribute((const void*)f20d_kernel<PDE, H, false, ENS, SETS, SAW>(),
+    hipError_t e = hipFuncSetAttribute((const void*)&k_fused20d<PDE, H, false, ENS, SETS, SAW>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)f20d_kernel<PDE, H, true, ENS, SETS, SAW>(),
+      e = hipFuncSetAttribute((const void*)&k_fused20d<PDE, H, true, ENS, SETS, SAW>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
@@ -366,7 +336,7 @@ inline int fused20d_launch(const F20dLaunch& a, const f20d_arg_t<SETS, SAW, PDE>
     }
     return (int)hipErrorInvalidValue;
   }
-  auto* const kern = a.n_wg >= n_tiles ? f20d_kernel<PDE, H, true, ENS, SETS, SAW>() : f20d_kernel<PDE, H, false, ENS, SETS, SAW>();
+  auto* const kern = a.n_wg >= n_tiles ? &k_fused20d<PDE, H, true, ENS, SETS, SAW> : &k_fused20d<PDE, H, false, ENS, SETS, SAW>;
   const dim3 grid(a.n_wg, a.n_members);
   if (a.ev_start && a.ev_stop)
     hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, a.stream, a.ev_start, a.ev_stop, 0, a.th, a.xs, a.ts, a.tgt, a.part,

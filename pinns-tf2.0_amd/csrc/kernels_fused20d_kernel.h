@@ -1,22 +1,20 @@
-// kernels_fused20d_kernel.h -- the body of k_fused20d, included by kernels_fused20d.h once per kernel NAME (PINN_F20D_KERNEL):
-// k_fused20d for every kind and variant but three, k_robin20d for PDE_ADR_ROBIN (the adr kind with Robin points), k_src20d for
-// PDE_ADR_SRC (the adr kind with a source term), k_var20d for PDE_ADR_VAR (the adr kind with coefficient fields).  The text is
-// one, so an instantiation of any name is what a single template gives; the other names exist because the set of
-// k_fused20d<...> instantiations in the library is pinned (tests/test_isa_hazards.py counts them) and the Robin, source and
-// coefficient-field variants are additions beside it.  (Not a __device__ body called from two kernels: such a wrapper changed the schedule of the
-// existing instantiations.)  No include guard: it is meant to be included more than once.
-// One more inclusion gives k_adrens20d for PDE_ADR_ENS (the adr kind's ensemble members, ENS with or without SETS); there the
-// coefficient slot's type, PINN_F20D_ARG_T, is f20d_ens_arg_t<PDE> and not f20d_nu_t<SETS, SAW, PDE>, whose text is part of
-// every other kernel's mangled name (kernels_fused20d.h).
-// A fifth inclusion, with PINN_F20D_SPLIT = 1, gives k_split20d: the one-tile kernel of pde 0 and 1 with two roles compiled in
-// (fused20d_api.h: the split launch).  The reverse sweep stands in kernels_fused20d_reverse.h, included below once per role;
-// with PINN_F20D_SPLIT = 0 it is included once, as the whole sweep, and every kernel comes out as it did when the text stood here.
+// kernels_fused20d_kernel.h -- the body of k_fused20d.  The text is one and the name is one: every kind and variant is a set
+// of template arguments <PDE, H, ONE_TILE, ENS, SETS, SAW> of k_fused20d, and the type of its coefficient slot comes from the
+// trait F20dArg (kernels_fused20d.h).  A new variant is a new set of arguments under the same name -- a new template value,
+// a specialisation of the trait where its slot differs -- and never one more inclusion.  It has to show, in the device-code
+// listing (tests/helpers/isa_lint.py --listing) before and after, that every earlier line is unchanged, and it adds its row
+// to the variant table of tests/test_isa_hazards.py, which pins the set of instantiations by their arguments.
+// kernels_fused20d.h includes the text a second time with PINN_F20D_SPLIT = 1, as k_split20d: the one-tile kernel of pde 0
+// and 1 with two roles compiled in (fused20d_api.h: the split launch), a preprocessor switch because the roles differ in
+// text.  The reverse sweep stands in kernels_fused20d_reverse.h, included below once per role; with PINN_F20D_SPLIT = 0 it
+// is included once, as the whole sweep.  (Not a __device__ body called from two kernels: such a wrapper changed the schedule
+// of the instantiations.)  No include guard: it is meant to be included twice.
 template <int PDE, int H, bool ONE_TILE, bool ENS = false, bool SETS = false, bool SAW = false>
 __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict__ th, const double* __restrict__ xs,
                                                   const double* __restrict__ ts, const double* __restrict__ tgt,
                                                   double* __restrict__ part, const int* __restrict__ row_index, int R,
                                                   int n_tiles, double lbx, double lbt, double sx, double st,
-                                                  PINN_F20D_ARG_T nu, SetDesc sd,
+                                                  f20d_slot_t<PDE, SETS, SAW> nu, SetDesc sd,
                                                   long long* __restrict__ stamps, W20Desc nd_arg) {
   static_assert(ENS || !SETS, "per-member point sets are an ensemble launch");
   static_assert(!pde_is_adr(PDE) || PDE == PDE_ADR_ENS || (!ENS && !SETS && (!SAW || PDE == PDE_ADR)),

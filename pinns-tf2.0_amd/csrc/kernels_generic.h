@@ -78,8 +78,8 @@ constexpr int PDE_ADR_SRC = 6;
 // expressions are PDE_ADR_SRC's, only the origin of the six operands differs: a table whose every row is the constant set
 // gives PDE_ADR_SRC's (and, with no source, PDE_ADR's) bits.  The engine dispatches here only while fields are present.
 constexpr int PDE_ADR_VAR = 7;
-// Template number of PINN_PDE_ADR in an ensemble launch (pinn_adr_ens_create; k_fused20d's ENS variants only, instantiated
-// under the name k_adrens20d): PDE_ADR's equation, seeds and loss-row layout, with the six coefficients read per MEMBER.  Where
+// Template number of PINN_PDE_ADR in an ensemble launch (pinn_adr_ens_create; k_fused20d's ENS variants
+// only): PDE_ADR's equation, seeds and loss-row layout, with the six coefficients read per MEMBER.  Where
 // PDE_ADR passes its coefficients by value travels AdrEnsArg, the address of a device table [members][8] -- a0, a1, nu, r1,
 // r2, r3 and two pad doubles, so a row is 64 bytes -- and member m = blockIdx.y reads row m, wave-uniform, once in the
 // prologue.  The expressions are PDE_ADR's: a member's rows are the bits of a solo PDE_ADR launch with that member's
@@ -131,9 +131,17 @@ template <typename real> __device__ __forceinline__ AdrCoef<real> adr_row(const 
   const real* __restrict__ r = kf + (size_t)6 * i;
   return AdrCoef<real>{r[0], r[1], r[2], r[3], r[4], r[5]};
 }
-template <typename real, int PDE>
-using pde_coef_t = typename std::conditional<PDE == PDE_ADR_VAR, AdrVarArg<real>, typename std::conditional<PDE == PDE_ADR_SRC, AdrSrcArg<real>, typename std::conditional<PDE == PDE_ADR_ROBIN, AdrRobinArg<real>, typename std::conditional<PDE == PDE_ADR, AdrCoef<real>,
-                                             typename std::conditional<PDE == PDE_ADR_IDE, AdrIdeArg, real>::type>::type>::type>::type>::type;
+// What a kernel of kind PDE takes in the place of the scalar nu: the scalar itself, or the adr value's own argument.  A trait
+// with one specialisation per value, not a chain of conditions: a kernel's mangled name then spells PdeCoef<real, PDE>::type
+// and nothing about which specialisations exist, so a new value adds its line here and renames no kernel.
+template <typename real, int PDE> struct PdeCoef { using type = real; };
+template <typename real> struct PdeCoef<real, PDE_ADR> { using type = AdrCoef<real>; };
+template <typename real> struct PdeCoef<real, PDE_ADR_IDE> { using type = AdrIdeArg; };
+template <typename real> struct PdeCoef<real, PDE_ADR_ROBIN> { using type = AdrRobinArg<real>; };
+template <typename real> struct PdeCoef<real, PDE_ADR_SRC> { using type = AdrSrcArg<real>; };
+template <typename real> struct PdeCoef<real, PDE_ADR_VAR> { using type = AdrVarArg<real>; };
+template <typename real> struct PdeCoef<real, PDE_ADR_ENS> { using type = AdrEnsArg; };
+template <typename real, int PDE> using pde_coef_t = typename PdeCoef<real, PDE>::type;
 template <typename real> __device__ __forceinline__ real coef_nu(real nu) { return nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrCoef<real>& k) { return k.nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrIdeArg&) { return real(0); }

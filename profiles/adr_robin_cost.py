@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cost of the Robin point class on the float64 register-stash kernel: k_fused20d<PDE_ADR, 8> (no Robin points: the kernel
-every earlier build runs) against k_robin20d<PDE_ADR_ROBIN, 8> with 400 Robin points (200 per wall) behind the same data
+every earlier build runs) against k_fused20d<PDE_ADR_ROBIN, 8> with 400 Robin points (200 per wall) behind the same data
 and collocation points, same weights, in one process.  Cases: N_f = 10^4 (one tile per workgroup) and 10^6 (the tile loop);
 the equation is the one of profiles/adr_cost.py (Burgers coefficients [0, 1, nu, 0, 0, 0], 100 data points, no pairs), so
 the figure without Robin points is comparable with adr_cost.json's "kernel_us_adr".  The 400 points are 6.25 more tiles of

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cost of the source term on the float64 register-stash kernel: k_fused20d<PDE_ADR, 8> (no source: the kernel every earlier
-build runs) against k_src20d<PDE_ADR_SRC, 8> with a source at every collocation point, same data and collocation points,
+build runs) against k_fused20d<PDE_ADR_SRC, 8> with a source at every collocation point, same data and collocation points,
 same weights, in one process.  Cases: N_f = 10^4 (one tile per workgroup) and 10^6 (the tile loop); the equation is the one of
 profiles/adr_cost.py and profiles/adr_robin_cost.py (Burgers coefficients [0, 1, nu, 0, 0, 0], 100 data points, no pairs, no
 Robin points), so the figure without a source is comparable with theirs.  The source costs one 8-byte load and one

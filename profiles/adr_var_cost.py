@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cost of per-point coefficient fields on the float64 register-stash kernel: k_fused20d<PDE_ADR, 8> (no fields: the kernel
-every earlier build runs, the yardstick) against k_var20d<PDE_ADR_VAR, 8> with a row of six coefficients at every collocation
+every earlier build runs, the yardstick) against k_fused20d<PDE_ADR_VAR, 8> with a row of six coefficients at every collocation
 point (every row the constant set: the same arithmetic on the same values), same data and collocation points, same weights, in
 one process.  Cases: N_f = 10^4 (one tile per workgroup) and 10^6 (the tile loop); the equation is the one of
 profiles/adr_cost.py, adr_robin_cost.py and adr_src_cost.py (Burgers coefficients [0, 1, nu, 0, 0, 0], 100 data points, no

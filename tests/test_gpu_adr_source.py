@@ -3,7 +3,7 @@ tests/helpers/adr_src_ref.py (pinned on the CPU by tests/test_adr_source_host.py
 
   f_i = u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 - s_i,   loss = mean_f f^2 + data, pairs, Robin parts
 
-Float64 on the generic kernels (path 0) and on k_src20d<PDE_ADR_SRC, H, .> (path 7, one tile per workgroup and tile loop),
+Float64 on the generic kernels (path 0) and on k_fused20d<PDE_ADR_SRC, H, .> (path 7, one tile per workgroup and tile loop),
 float32 on path 0.  Float64 bounds are tests/test_gpu_adr.py's TOL (loss 1e-12, gradient 1e-11, residual 1e-10), float32
 1e-5 / 2e-5 / 2e-4, each loss term to 10 x the loss bound.  The sets and weights are tests/test_gpu_adr_robin.py's; the
 source is s_i = sin(3 x_i) exp(-t_i) + 0.5, distinct at every point, so a value read at a shifted index fails."""

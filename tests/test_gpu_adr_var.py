@@ -3,7 +3,7 @@ restatement tests/helpers/adr_var_ref.py (pinned on the CPU by tests/test_adr_va
 
   f_i = u_t + (a0_i + a1_i u) u_x - nu_i u_xx + r1_i u + r2_i u^2 + r3_i u^3 - s_i,   loss = mean_f f^2 + data, pairs, Robin
 
-Float64 on the generic kernels (path 0) and on k_var20d<PDE_ADR_VAR, H, .> (path 7, one tile per workgroup and tile loop),
+Float64 on the generic kernels (path 0) and on k_fused20d<PDE_ADR_VAR, H, .> (path 7, one tile per workgroup and tile loop),
 float32 on path 0.  Float64 bounds are tests/test_gpu_adr.py's TOL (loss 1e-12, gradient 1e-11, residual 1e-10), float32
 1e-5 / 2e-5 / 2e-4, each loss term to 10 x the loss bound.  Sets, weights, cells and the test fields are
 tests/helpers/adr_var_cells.py's (the sets and weights of tests/test_gpu_adr_source.py): six columns distinct at every point,

@@ -1,4 +1,4 @@
-"""GPU: ensembles of the adr kind (pinn_native.AdrEnsemble, include/pinn_hip.h pinn_adr_ens_create; k_adrens20d): K members
+"""GPU: ensembles of the adr kind (pinn_native.AdrEnsemble, include/pinn_hip.h pinn_adr_ens_create; k_fused20d<PDE_ADR_ENS>): K members
 of one float64 net, each with its own six coefficients, on shared or per-member point sets with periodic pairs.  The
 yardstick is a solo Engine(pde="adr", dtype="f64") on kernel path 7 -- existing code, held against the numpy oracle by
 tests/test_gpu_adr.py -- and every comparison with it is == / np.array_equal: member k must be bit-identical to an Engine

@@ -87,8 +87,9 @@ def test_no_scratch_in_the_kernels_that_serve_the_baseline_configs_or_the_exchan
 @needs_tools
 def test_the_kernel_listing_names_every_kernel_with_its_digest_and_resources():
     """`isa_lint.py --listing`: what two builds are compared by (profiles/refactor_paths_device_code.txt).  Every kernel has
-    a line, with metadata from the code object's notes; k_fused20d's 60 variants sit in their own code
-    object, all under that one name; the listing of one library is the same twice."""
+    a line, with metadata from the code object's notes; k_fused20d's variants sit in their own code object, all under that
+    one name, and their template arguments are exactly the table below (a new variant adds its row); k_split20d, the same
+    text with the two roles compiled in, is the only other name there; the listing of one library is the same twice."""
     import re
     import pinn_native
     if not os.path.exists(isa_lint.READELF):
@@ -98,6 +99,26 @@ def test_the_kernel_listing_names_every_kernel_with_its_digest_and_resources():
     assert len(lines) > 50 and len(set(lines)) == len(lines)
     form = re.compile(r"^\d+ \S+ insns=\d+ sha=[0-9a-f]{16} vgpr=\d+ agpr=\d+ sgpr=\d+ lds=\d+ scratch=\d+$")
     assert all(form.match(l) for l in lines), [l for l in lines if not form.match(l)][:3]
-    assert sum("k_fused20dI" in l for l in lines) == 60 and len({l.split()[0] for l in lines if "k_fused20dI" in l}) == 1
-    assert not [l for l in lines if "k_fused20d_" in l.split()[1]]
+    # PDE -> the (ENS, SETS, SAW) it is built with; each row at H = 4, 6, 8, tile loop and one tile
+    variants = {0: [(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 0, 1)],        # Burgers inference: solo, ensembles, point weights
+                1: [(0, 0, 0), (1, 0, 0), (1, 1, 0)],                   # Burgers identification: solo, ensembles
+                3: [(0, 0, 0), (0, 0, 1)],                              # adr, and with point weights
+                4: [(0, 0, 0)], 5: [(0, 0, 0)], 6: [(0, 0, 0)], 7: [(0, 0, 0)],   # adr_ide, Robin, source, fields
+                8: [(1, 0, 0), (1, 1, 0)]}                              # adr ensembles
+    args = re.compile(r"^_ZN4pinn10k_(fused|split)20dILi(\d+)ELi(\d+)ELb([01])ELb([01])ELb([01])ELb([01])EE")
+
+    def built(kind):                      # (PDE, H, ONE_TILE, ENS, SETS, SAW) of every kernel of that name, in listing order
+        found = [args.match(l.split()[1]) for l in lines if "k_%s20dI" % kind in l]
+        assert all(found), [l for l in lines if "k_%s20dI" % kind in l and not args.match(l.split()[1])][:3]
+        return [tuple(int(v) for v in m.groups()[1:]) for m in found if m.group(1) == kind]
+    want = {(pde, H, one) + row for pde, rows in variants.items() for row in rows for H in (4, 6, 8) for one in (0, 1)}
+    fused, split = built("fused"), built("split")
+    assert len(want) == 90 and len(fused) == 90 and set(fused) == want, (sorted(set(fused) - want), sorted(want - set(fused)))
+    assert len(split) == 6 and set(split) == {(pde, H, 1, 0, 0, 0) for pde in (0, 1) for H in (4, 6, 8)}, split
+    obj = {l.split()[0] for l in lines if "k_fused20dI" in l}
+    assert len(obj) == 1
+    others = [l for l in lines if l.split()[0] in obj and "k_fused20dI" not in l and "k_split20dI" not in l]
+    assert not others, others[:3]
+    retired = ("k_robin20d", "k_src20d", "k_var20d", "k_adrens20d", "k_fused20d_")
+    assert not [l for l in lines if any(r in l.split()[1] for r in retired)]
     assert lines == isa_lint.kernel_listing(pinn_native.LIB_PATH)

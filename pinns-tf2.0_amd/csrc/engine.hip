@@ -14,6 +14,7 @@
 #include <cstring>
 #include <string>
 #include <chrono>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pinn_hip.h"
@@ -336,6 +337,14 @@ struct pinn_ctx {
 };
 
 static size_t real_size(const pinn_ctx* c) { return c->dtype == PINN_F64 ? 8 : 4; }
+// The compute type of c as a type: calls f with a value of it (auto r; using real = decltype(r)), so a launch that differs
+// between the two dtypes in `real` alone is written once.  Inlined by force, as by_kind below: the evaluation and the update
+// kernels are issued from the optimisers' step loops, where a one-tile step is as short as the host's own work.
+template <typename F>
+__attribute__((always_inline)) static inline auto by_real(const pinn_ctx* c, F&& f) {
+  if (c->dtype == PINN_F64) return f(double());
+  return f(float());
+}
 static bool is_disc(const pinn_ctx* c) { return c->pde == PINN_PDE_BURGERS_DISC || c->pde == PINN_PDE_BURGERS_DISC_IDE; }
 static bool has_lambdas(int pde) { return pde == PINN_PDE_BURGERS_IDE || pde == PINN_PDE_BURGERS_DISC_IDE; }
 // advection-diffusion-reaction with run-time coefficients: template value PDE_ADR of the continuous kernels
@@ -364,6 +373,56 @@ static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
     return AdrIdeArg{c->adr_mask};
   else
     return (real)c->nu;
+}
+
+// Where a kernel kind is asked for: the training evaluation (eval_loss_grad), the residual over the context's own set
+// (pinn_residual), the residual at points that are not the set's (pinn_residual_at; the pool of rad_draw)
+enum Where { AT_TRAINING, AT_SET, AT_FOREIGN };
+
+// The template value of the adr kernels that a context of the adr kind (pde 5) runs.  The three places differ on purpose:
+//   coefficient fields   have a row per collocation point of the set and none anywhere else: PDE_ADR_VAR never runs at
+//                        foreign points (it would index the table and tgt by a point that has no entry).  pinn_residual_at
+//                        and pinn_rad_collocation refuse such a context before they get here
+//   a source term        is in the same position, but PDE_ADR_SRC has a null form that leaves s out (launch_residual), so a
+//                        foreign point gets the operator part N[u].  pinn_rad_collocation refuses a source all the same
+//   Robin points         change the training kernels alone, which then walk a fourth point class; a residual is taken at
+//                        collocation points, so k_residual has no Robin form.  Training looks at the ASSEMBLED count
+//                        (robin.n, ensure_sets), as the kernels' argument does
+// Each kind is a superset of the one below it (kernels_generic.h), so the first extra present decides.
+static int adr_kind(const pinn_ctx* c, Where w) {
+  if (c->kf.on && w != AT_FOREIGN) return PDE_ADR_VAR;
+  if (c->src.on) return PDE_ADR_SRC;
+  if (c->robin.n > 0 && w == AT_TRAINING) return PDE_ADR_ROBIN;
+  return PDE_ADR;
+}
+// the template value of the continuous kernels for any context that has them (not the discrete-time models)
+static int pde_kind(const pinn_ctx* c, Where w) {
+  switch (c->pde) {
+    case PINN_PDE_BURGERS: return 0;
+    case PINN_PDE_BURGERS_IDE: return 1;
+    case PINN_PDE_ADR: return adr_kind(c, w);
+    case PINN_PDE_ADR_IDE: return PDE_ADR_IDE;
+    default: return 2;                     // Schrodinger
+  }
+}
+// (dtype of c, kind) as template arguments: calls f(real(), Kind<PDE>()) for the kind pde_kind answered.  A caller whose
+// kernels lack one of the kinds says so with an `if constexpr` of its own; nothing here instantiates a kernel
+template <int PDE> using Kind = std::integral_constant<int, PDE>;
+template <typename F>
+__attribute__((always_inline)) static inline int by_kind(const pinn_ctx* c, int kind, F&& f) {
+  return by_real(c, [&](auto r) __attribute__((always_inline)) -> int {
+    switch (kind) {
+      case 0: return f(r, Kind<0>());
+      case 1: return f(r, Kind<1>());
+      case 2: return f(r, Kind<2>());
+      case PDE_ADR: return f(r, Kind<PDE_ADR>());
+      case PDE_ADR_IDE: return f(r, Kind<PDE_ADR_IDE>());
+      case PDE_ADR_ROBIN: return f(r, Kind<PDE_ADR_ROBIN>());
+      case PDE_ADR_SRC: return f(r, Kind<PDE_ADR_SRC>());
+      case PDE_ADR_VAR: return f(r, Kind<PDE_ADR_VAR>());
+    }
+    return fail(PINN_EINVAL, "no kernel of kind %d", kind);
+  });
 }
 
 // a source or coefficient fields whose points were replaced: refused in front of every evaluation, nothing launched.  One
@@ -532,14 +591,12 @@ static int lhs_fill(pinn_ctx* c) {
   const uint64_t n = (uint64_t)c->lhs.n_design;
   const uint32_t lo = (uint32_t)c->lhs.seed, hi = (uint32_t)(c->lhs.seed >> 32);
   const dim3 grid((unsigned)((cnt + 255) / 256)), block(256);
-  if (c->dtype == PINN_F64)
-    hipLaunchKernelGGL((k_lhs_fill<double>), grid, block, 0, c->stream, (double*)c->xs + off, (double*)c->ts + off, cnt,
+  by_real(c, [&](auto r) {
+    using real = decltype(r);
+    hipLaunchKernelGGL((k_lhs_fill<real>), grid, block, 0, c->stream, (real*)c->xs + off, (real*)c->ts + off, cnt,
                        (uint64_t)c->lhs.first, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
                        c->ub[1] - c->lb[1]);
-  else
-    hipLaunchKernelGGL((k_lhs_fill<float>), grid, block, 0, c->stream, (float*)c->xs + off, (float*)c->ts + off, cnt,
-                       (uint64_t)c->lhs.first, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
-                       c->ub[1] - c->lb[1]);
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1094,9 +1151,10 @@ static int launch_chunks(pinn_ctx* c, hipEvent_t* ev4) {
 }
 
 // events of a sampled evaluation: [0] start, [1] forward done, [2] sweeps done; the one-launch paths attach [0] and [1] to
-// their kernel (its own begin and end)
+// their kernel (its own begin and end).  Out of line: each (dtype, kind) is a function of its own behind eval_loss_grad's
+// switch, so a step walks the code of its own kind and not one body that holds all sixteen
 template <typename real, int PDE>
-static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
+__attribute__((noinline)) static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   if (ev4 && !PATHS[c->path].one_launch) HIPCHK(hipEventRecord(ev4[0], c->stream));
   int rc;
   switch (c->path) {
@@ -1253,20 +1311,11 @@ static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
   hipEvent_t* ev4 = nullptr;
   if (c->timing && c->ev_used < c->ev_cap_evals && (c->ev_seen++ % c->ev_every) == 0)
     ev4 = &c->ev[(size_t)4 * c->ev_used];
-#define DISPATCH(REAL)                                                       \
-  switch (c->pde) {                                                          \
-    case PINN_PDE_BURGERS: rc = launch_sweeps<REAL, 0>(c, ev4, af); break;       \
-    case PINN_PDE_BURGERS_IDE: rc = launch_sweeps<REAL, 1>(c, ev4, af); break;   \
-    case PINN_PDE_ADR: rc = c->kf.on ? launch_sweeps<REAL, PDE_ADR_VAR>(c, ev4, af)          /* fields (+ source, + Robin) */ \
-                          : c->src.on ? launch_sweeps<REAL, PDE_ADR_SRC>(c, ev4, af)         /* source (+ Robin points) */ \
-                          : c->robin.n > 0 ? launch_sweeps<REAL, PDE_ADR_ROBIN>(c, ev4, af)  /* the parent's kernels without */ \
-                                           : launch_sweeps<REAL, PDE_ADR>(c, ev4, af); break; \
-    case PINN_PDE_ADR_IDE: rc = launch_sweeps<REAL, PDE_ADR_IDE>(c, ev4, af); break; \
-    default: rc = launch_sweeps<REAL, 2>(c, ev4, af); break;                     \
-  }
   if (is_disc(c)) rc = disc_eval_any(c, ev4, af);
-  else if (c->dtype == PINN_F64) { DISPATCH(double) } else { DISPATCH(float) }
-#undef DISPATCH
+  else
+    rc = by_kind(c, pde_kind(c, AT_TRAINING), [&](auto r, auto kind) {
+      return launch_sweeps<decltype(r), decltype(kind)::value>(c, ev4, af);
+    });
   if (rc) return rc;
   if (c->comm && !c->xg.on)
     NCCLCHK(ncclAllReduce(c->gl, c->gl, (size_t)c->R, ncclDouble, ncclSum, c->comm, c->stream));
@@ -1417,10 +1466,11 @@ static int xg_self_test(pinn_ctx* c, int* ok) {
 
 static int cast_weights(pinn_ctx* c) {
   const int n = c->nd.n_theta;
-  if (c->dtype == PINN_F64)
-    hipLaunchKernelGGL((k_cast_weights<double>), dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->theta, (double*)c->theta_r, c->nd, c->img);
-  else
-    hipLaunchKernelGGL((k_cast_weights<float>), dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->theta, (float*)c->theta_r, c->nd, c->img);
+  by_real(c, [&](auto r) {
+    using real = decltype(r);
+    hipLaunchKernelGGL((k_cast_weights<real>), dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->theta,
+                       (real*)c->theta_r, c->nd, c->img);
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1478,8 +1528,7 @@ static int forward_taylor(pinn_ctx* c, const void* xs, const void* ts, int n_pad
   if (need_S > c->cap_S) { if (dev_alloc(&c->S, need_S)) return PINN_EHIP; c->cap_S = need_S; }
   for (int base = 0; base < n_pad; base += chunk) {
     const int pts = (n_pad - base < chunk) ? n_pad - base : chunk;
-    const int rc = c->dtype == PINN_F64 ? forward_chunk<double>(c, xs, ts, n_pad, chunk, O, base, pts)
-                                        : forward_chunk<float>(c, xs, ts, n_pad, chunk, O, base, pts);
+    const int rc = by_real(c, [&](auto r) { return forward_chunk<decltype(r)>(c, xs, ts, n_pad, chunk, O, base, pts); });
     if (rc) return rc;
   }
   HIPCHK(hipGetLastError());
@@ -1497,10 +1546,35 @@ static int predict_values(pinn_ctx* c, int64_t n, int n_pad) {
   const int chunk = n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS;
   if (int rc = forward_taylor(c, c->xe, c->te, n_pad, chunk, c->Oe)) return rc;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (c->dtype == PINN_F64)
-    hipLaunchKernelGGL((k_pick_values<double>), grid, block, 0, c->stream, (const vec4<double>*)c->Oe, (int)n, n_pad, NO, c->pred);
-  else
-    hipLaunchKernelGGL((k_pick_values<float>), grid, block, 0, c->stream, (const vec4<float>*)c->Oe, (int)n, n_pad, NO, c->pred);
+  by_real(c, [&](auto r) {
+    using real = decltype(r);
+    hipLaunchKernelGGL((k_pick_values<real>), grid, block, 0, c->stream, (const vec4<real>*)c->Oe, (int)n, n_pad, NO,
+                       c->pred);
+  });
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// PDE residuals from Taylor outputs: points first .. first + count - 1 of O ([n_out][n_pad] vec4, forward_taylor) -> dst
+// ([count][n_out] float64, device), in the kind the place calls for (adr_kind).  Enqueues only.
+static int launch_residual(pinn_ctx* c, Where w, const void* O, int first, int count, int n_pad, double* dst) {
+  const dim3 grid((unsigned)((count + 255) / 256)), block(256);
+  const int rc = by_kind(c, pde_kind(c, w), [&](auto r, auto kind) {
+    using real = decltype(r);
+    constexpr int PDE = decltype(kind)::value;
+    if constexpr (PDE == PDE_ADR_ROBIN) {           // no such k_residual, and adr_kind answers it for training alone
+      return fail(PINN_EINVAL, "a residual has no Robin form");
+    } else {
+      pde_coef_t<real, PDE> coef = pde_coef<real, PDE>(c);
+      if constexpr (PDE == PDE_ADR_SRC) {           // s is not known at foreign points: the null form, N[u] alone
+        if (w == AT_FOREIGN) coef.src = nullptr;
+      }
+      hipLaunchKernelGGL((k_residual<real, PDE>), grid, block, 0, c->stream, first, count, n_pad, (const vec4<real>*)O,
+                         (const real*)c->theta_r, c->nd.n_net, coef, dst, c->nd.n_out);
+      return 0;
+    }
+  });
+  if (rc) return rc;
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1539,24 +1613,18 @@ static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) 
   const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
   const uint64_t n = (uint64_t)M;
   const dim3 grid_m((unsigned)((M + RAD_BLOCK - 1) / RAD_BLOCK)), block(RAD_BLOCK);
-  const bool f64 = c->dtype == PINN_F64;
   // 1. the pool: points [0, M) of the M-point design, in the compute dtype (k_lhs_fill, as pinn_lhs_collocation draws it)
-  if (f64)
-    hipLaunchKernelGGL((k_lhs_fill<double>), grid_m, block, 0, c->stream, (double*)c->rad.px, (double*)c->rad.pt, M,
+  by_real(c, [&](auto r) {
+    using real = decltype(r);
+    hipLaunchKernelGGL((k_lhs_fill<real>), grid_m, block, 0, c->stream, (real*)c->rad.px, (real*)c->rad.pt, M,
                        (uint64_t)0, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
                        c->ub[1] - c->lb[1]);
-  else
-    hipLaunchKernelGGL((k_lhs_fill<float>), grid_m, block, 0, c->stream, (float*)c->rad.px, (float*)c->rad.pt, M,
-                       (uint64_t)0, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
-                       c->ub[1] - c->lb[1]);
+  });
   HIPCHK(hipGetLastError());
   // 2. residuals at the current weights: pinn_residual_at's forward sweep and k_residual
-  if (int rc = forward_taylor(c, c->rad.px, c->rad.pt, n_pad, n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS, c->rad.O)) return rc;
-#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid_m, block, 0, c->stream, 0, (int)M, n_pad, (const vec4<REAL>*)c->rad.O, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->rad.f, NO)
-  if (f64) { if (c->pde == PINN_PDE_SCHRODINGER) RES(double, 2); else if (is_adr(c)) RES(double, PDE_ADR); else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 0); }
-  else { if (c->pde == PINN_PDE_SCHRODINGER) RES(float, 2); else if (is_adr(c)) RES(float, PDE_ADR); else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 0); }
-#undef RES
-  HIPCHK(hipGetLastError());
+  const int chunk = n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS;
+  if (int rc = forward_taylor(c, c->rad.px, c->rad.pt, n_pad, chunk, c->rad.O)) return rc;
+  if (int rc = launch_residual(c, AT_FOREIGN, c->rad.O, 0, (int)M, n_pad, c->rad.f)) return rc;
   // 3.-4. weights and their CDF
   HIPCHK(hipMemsetAsync(c->rad.tot, 0, sizeof(RadTotals), c->stream));
   hipLaunchKernelGGL(k_rad_mag, grid_m, block, 0, c->stream, (const double*)c->rad.f, NO, M, k, c->rad.w, c->rad.tot);
@@ -1566,18 +1634,95 @@ static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) 
   // 5. the draw
   const size_t off = (size_t)(2 * c->sd.n_b + c->sd.n_u);
   const dim3 grid_s((unsigned)((cnt + 255) / 256)), block_s(256);
-  if (f64)
-    hipLaunchKernelGGL((k_rad_select<double>), grid_s, block_s, 0, c->stream, (const double*)c->rad.px,
-                       (const double*)c->rad.pt, (const unsigned long long*)c->rad.w,
+  by_real(c, [&](auto r) {
+    using real = decltype(r);
+    hipLaunchKernelGGL((k_rad_select<real>), grid_s, block_s, 0, c->stream, (const real*)c->rad.px,
+                       (const real*)c->rad.pt, (const unsigned long long*)c->rad.w,
                        (const unsigned long long*)c->rad.bsum, (const RadTotals*)c->rad.tot, M, (uint64_t)c->rad.first,
-                       cnt, lo, hi, (double*)c->xs + off, (double*)c->ts + off, c->rad.cx, c->rad.ct);
-  else
-    hipLaunchKernelGGL((k_rad_select<float>), grid_s, block_s, 0, c->stream, (const float*)c->rad.px,
-                       (const float*)c->rad.pt, (const unsigned long long*)c->rad.w,
-                       (const unsigned long long*)c->rad.bsum, (const RadTotals*)c->rad.tot, M, (uint64_t)c->rad.first,
-                       cnt, lo, hi, (float*)c->xs + off, (float*)c->ts + off, c->rad.cx, c->rad.ct);
+                       cnt, lo, hi, (real*)c->xs + off, (real*)c->ts + off, c->rad.cx, c->rad.ct);
+  });
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The optional extras of a context, one row each: how to see that one is present, the phrases its refusals are built from
+// (whole phrases: "are" / "is" and "them" / "it" are the row's, no grammar is derived) and how the caller removes it.  The two
+// weight kinds belong to one kind of problem in float64 on kernel path 7 (weights_supported); the three extras of the adr
+// kind run on both of its paths, in both dtypes (adr_extra_gate).  Every extra is single-device.
+// ------------------------------------------------------------------------------------------
+enum { X_SA, X_PW, X_ROBIN, X_SRC, X_KF, X_COUNT };
+struct Extra {
+  bool (*present)(const pinn_ctx*);
+  const char* is;        // subject and verb
+  const char* runs;
+  const char* remove;    // the call that removes it
+  int home_pde;          // the one kind of problem it is for, and its name
+  const char* home;
+  const char* needs;     // the weight kinds only
+  const char* pron;      // the adr extras only: the object form, and point weights' refusal to stand beside it
+  const char* pw_clash;
+};
+static const Extra EXTRAS[X_COUNT] = {
+    {[](const pinn_ctx* c) { return c->sa.on; }, "self-adaptive weights are", "self-adaptive weights run",
+     "pinn_sa_disable", PINN_PDE_BURGERS, "Burgers inference (pde 0)", "self-adaptive weights need", nullptr, nullptr},
+    {[](const pinn_ctx* c) { return c->pw.on; }, "point weights are", "point weights run", "pinn_pw_disable", PINN_PDE_ADR,
+     "the adr kind (pde 5)", "point weights need", nullptr, nullptr},
+    {[](const pinn_ctx* c) { return !c->robin.X.empty(); }, "Robin points are", "Robin points run",
+     "pinn_set_robin with n = 0", PINN_PDE_ADR, "the adr kind (pde 5)", nullptr, "them",
+     "point weights do not cover Robin points"},
+    {[](const pinn_ctx* c) { return c->src.on; }, "a source term is", "a source term runs", "pinn_set_source with n = 0",
+     PINN_PDE_ADR, "the adr kind (pde 5)", nullptr, "it", "point weights are not combined with a source term"},
+    {[](const pinn_ctx* c) { return c->kf.on; }, "coefficient fields are", "coefficient fields run",
+     "pinn_set_coef_fields with n = 0", PINN_PDE_ADR, "the adr kind (pde 5)", nullptr, "them",
+     "point weights are not combined with coefficient fields"},
+};
+
+// a communicator is refused while any extra is present, and for the adr_ide kind.  That kind comes last: it can hold none of
+// the five (adr_extra_gate and weights_supported refuse them), so its place among them cannot be observed
+static int single_device_only(const pinn_ctx* c, const char* who) {
+  for (const Extra& x : EXTRAS)
+    if (x.present(c)) return fail(PINN_EUNSUPPORTED, "%s: %s single-device (%s first)", who, x.is, x.remove);
+  if (is_adr_ide(c))
+    return fail(PINN_EUNSUPPORTED, "%s: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch", who);
+  return 0;
+}
+
+// what a weighted kernel serves: its kind of problem in float64 on kernel path 7, one device; checked before any device work
+static int weights_supported(const pinn_ctx* c, const Extra& x, const char* who) {
+  if (c->pde != x.home_pde) return fail(PINN_EUNSUPPORTED, "%s: %s for %s only", who, x.is, x.home);
+  if (c->dtype != PINN_F64) return fail(PINN_EUNSUPPORTED, "%s: %s float64", who, x.needs);
+  if (c->path != KP_FUSED20D)
+    return fail(PINN_EUNSUPPORTED, "%s: %s kernel path 7 (this context runs path %d)", who, x.needs, (int)c->path);
+  if (c->comm || c->xg.box)
+    return fail(PINN_EUNSUPPORTED, "%s: %s single-device; this context has a communicator", who, x.is);
+  return 0;
+}
+
+// what the setter of an adr extra asks of the context, behind its own checks of the arrays (they need no context) and in
+// front of everything else: the adr kind, no point weights, one of its two paths, one device
+static int adr_extra_gate(const pinn_ctx* c, const Extra& x, const char* who) {
+  REQUIRE(c, "%s: null context", who);
+  if (c->pde == PINN_PDE_ADR_IDE)
+    return fail(PINN_EUNSUPPORTED, "%s: %s for %s only; the adr_ide kind (pde 6) has no variant for %s", who, x.is, x.home,
+                x.pron);
+  if (c->pde != x.home_pde) return fail(PINN_EUNSUPPORTED, "%s: %s for %s only", who, x.is, x.home);
+  if (EXTRAS[X_PW].present(c))
+    return fail(PINN_EUNSUPPORTED, "%s: %s (%s first)", who, x.pw_clash, EXTRAS[X_PW].remove);
+  if (!adr_has_path(c->path))
+    return fail(PINN_EUNSUPPORTED, "%s: %s on kernel paths 0 and 7 only (this context runs path %d)", who, x.runs,
+                (int)c->path);
+  if (c->comm || c->xg.box)
+    return fail(PINN_EUNSUPPORTED, "%s: %s single-device; this context has a communicator", who, x.is);
+  return 0;
+}
+
+// the collocation points were replaced: a source's values and the fields' rows belonged to the old points (nothing evaluates
+// until their setters are called again, src_fresh), and both weight stores start that class over
+static void colloc_replaced(pinn_ctx* c) {
+  if (c->src.on) c->src.stale = true;
+  if (c->kf.on) c->kf.stale = true;
+  c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1783,9 +1928,7 @@ int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_to
   c->nf_total = n_total;
   c->lhs.on = false;
   c->rad.on = false;
-  if (c->src.on) c->src.stale = true;            // the values belonged to the old points
-  if (c->kf.on) c->kf.stale = true;
-  c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
+  colloc_replaced(c);
   c->sets_dirty = true;
   return 0;
 }
@@ -1798,11 +1941,9 @@ int pinn_lhs_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
           (long long)count);
   HIPCHK(hipSetDevice(c->device));
   const bool same_shape = c->lhs.on && !c->sets_dirty && c->lhs.count == count;
-  if (c->src.on) c->src.stale = true;            // the fill writes xs and ts only
-  if (c->kf.on) c->kf.stale = true;
+  colloc_replaced(c);                            // the fill writes xs and ts only
   c->lhs.on = true; c->lhs.n_design = n_design; c->lhs.first = first; c->lhs.count = count; c->lhs.seed = seed;
   c->rad.on = false;
-  c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
   c->Xf.clear();
   c->nf_total = n_design;
   c->sd.inv_nf = 1.0 / (double)n_design;
@@ -1834,7 +1975,7 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   if (int rc = rad_alloc(c, count, n_pool)) return rc;
   c->lhs.on = false;
   c->rad.on = true; c->rad.n_design = n_design; c->rad.first = first; c->rad.count = count;
-  c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
+  colloc_replaced(c);                             // (no source and no fields here: refused above)
   c->Xf.clear();
   c->nf_total = n_design;
   c->sd.inv_nf = 1.0 / (double)n_design;
@@ -1899,20 +2040,14 @@ int pinn_set_robin(pinn_ctx* c, const double* X_w, const double* alpha, const do
   REQUIRE(n <= (1 << 30), "pinn_set_robin: too many points (%lld)", (long long)n);
   REQUIRE(n == 0 || (X_w && alpha && beta && g), "pinn_set_robin: null array");
   for (int64_t j = 0; j < n; ++j) {
-    REQUIRE(std::isfinite(X_w[2 * j]) && std::isfinite(X_w[2 * j + 1]), "pinn_set_robin: point %lld is not finite", (long long)j);
+    REQUIRE(std::isfinite(X_w[2 * j]) && std::isfinite(X_w[2 * j + 1]), "pinn_set_robin: point %lld is not finite",
+            (long long)j);
     REQUIRE(std::isfinite(alpha[j]) && std::isfinite(beta[j]) && std::isfinite(g[j]),
             "pinn_set_robin: alpha, beta or g of point %lld is not finite", (long long)j);
-    REQUIRE(alpha[j] != 0.0 || beta[j] != 0.0, "pinn_set_robin: point %lld has alpha = beta = 0: it constrains nothing", (long long)j);
+    REQUIRE(alpha[j] != 0.0 || beta[j] != 0.0, "pinn_set_robin: point %lld has alpha = beta = 0: it constrains nothing",
+            (long long)j);
   }
-  REQUIRE(c, "pinn_set_robin: null context");
-  if (c->pde == PINN_PDE_ADR_IDE)
-    return fail(PINN_EUNSUPPORTED, "pinn_set_robin: Robin points are for the adr kind (pde 5) only; the adr_ide kind (pde 6) has no variant for them");
-  if (!is_adr(c)) return fail(PINN_EUNSUPPORTED, "pinn_set_robin: Robin points are for the adr kind (pde 5) only");
-  if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_set_robin: point weights do not cover Robin points (pinn_pw_disable first)");
-  if (!adr_has_path(c->path))
-    return fail(PINN_EUNSUPPORTED, "pinn_set_robin: Robin points run on kernel paths 0 and 7 only (this context runs path %d)", (int)c->path);
-  if (c->comm || c->xg.box)
-    return fail(PINN_EUNSUPPORTED, "pinn_set_robin: Robin points are single-device; this context has a communicator");
+  if (int rc = adr_extra_gate(c, EXTRAS[X_ROBIN], "pinn_set_robin")) return rc;
   c->robin.X.assign(X_w, X_w + 2 * n);
   c->robin.alpha.assign(alpha, alpha + n);
   c->robin.beta.assign(beta, beta + n);
@@ -1927,21 +2062,24 @@ int pinn_set_robin(pinn_ctx* c, const double* X_w, const double* alpha, const do
 int pinn_robin_residual(pinn_ctx* c, double* out, int64_t n) {
   REQUIRE(c, "null");
   if (!is_adr(c)) return fail(PINN_EUNSUPPORTED, "pinn_robin_residual: Robin points are for the adr kind (pde 5) only");
-  REQUIRE(n == (int64_t)(c->robin.X.size() / 2), "pinn_robin_residual: buffer holds %lld values, the context has %lld Robin points",
-          (long long)n, (long long)(c->robin.X.size() / 2));
+  REQUIRE(n == (int64_t)(c->robin.X.size() / 2),
+          "pinn_robin_residual: buffer holds %lld values, the context has %lld Robin points", (long long)n,
+          (long long)(c->robin.X.size() / 2));
   if (n == 0) return 0;
   REQUIRE(out, "null");
   HIPCHK(hipSetDevice(c->device));
   if (int rc = ensure_sets(c)) return rc;
-  if ((size_t)n > c->robin.cap_out) { if (dev_alloc(&c->robin.out, (size_t)n * 8)) return PINN_EHIP; c->robin.cap_out = (size_t)n; }
+  if ((size_t)n > c->robin.cap_out) {
+    if (dev_alloc(&c->robin.out, (size_t)n * 8)) return PINN_EHIP;
+    c->robin.cap_out = (size_t)n;
+  }
   if (int rc = forward_taylor(c, c->xs, c->ts, c->sd.n_pad, c->chunk, c->O)) return rc;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (c->dtype == PINN_F64)
-    hipLaunchKernelGGL((k_robin_residual<double>), grid, block, 0, c->stream, pde_coef<double, PDE_ADR_ROBIN>(c),
-                       (const vec4<double>*)c->O, (const double*)c->tgt, c->robin.out);
-  else
-    hipLaunchKernelGGL((k_robin_residual<float>), grid, block, 0, c->stream, pde_coef<float, PDE_ADR_ROBIN>(c),
-                       (const vec4<float>*)c->O, (const float*)c->tgt, c->robin.out);
+  by_real(c, [&](auto r) {
+    using real = decltype(r);
+    hipLaunchKernelGGL((k_robin_residual<real>), grid, block, 0, c->stream, pde_coef<real, PDE_ADR_ROBIN>(c),
+                       (const vec4<real>*)c->O, (const real*)c->tgt, c->robin.out);
+  });
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, c->robin.out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1955,15 +2093,7 @@ int pinn_set_source(pinn_ctx* c, const double* s, int64_t n) {
   REQUIRE(n <= (1 << 30), "pinn_set_source: too many values (%lld)", (long long)n);
   REQUIRE(n == 0 || s, "pinn_set_source: null array");
   for (int64_t i = 0; i < n; ++i) REQUIRE(std::isfinite(s[i]), "pinn_set_source: value %lld is not finite", (long long)i);
-  REQUIRE(c, "pinn_set_source: null context");
-  if (c->pde == PINN_PDE_ADR_IDE)
-    return fail(PINN_EUNSUPPORTED, "pinn_set_source: a source term is for the adr kind (pde 5) only; the adr_ide kind (pde 6) has no variant for it");
-  if (!is_adr(c)) return fail(PINN_EUNSUPPORTED, "pinn_set_source: a source term is for the adr kind (pde 5) only");
-  if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_set_source: point weights are not combined with a source term (pinn_pw_disable first)");
-  if (!adr_has_path(c->path))
-    return fail(PINN_EUNSUPPORTED, "pinn_set_source: a source term runs on kernel paths 0 and 7 only (this context runs path %d)", (int)c->path);
-  if (c->comm || c->xg.box)
-    return fail(PINN_EUNSUPPORTED, "pinn_set_source: a source term is single-device; this context has a communicator");
+  if (int rc = adr_extra_gate(c, EXTRAS[X_SRC], "pinn_set_source")) return rc;
   REQUIRE(n == 0 || n == n_colloc(c), "pinn_set_source: %lld values for %lld local collocation points", (long long)n,
           (long long)n_colloc(c));
   HIPCHK(hipSetDevice(c->device));
@@ -1993,16 +2123,9 @@ int pinn_set_coef_fields(pinn_ctx* c, const double* K, int64_t n) {
   REQUIRE(n == 0 || K, "pinn_set_coef_fields: null array");
   // a row is refused where pinn_set_pde_params refuses a constant set of the adr kind: a coefficient that is not finite
   for (int64_t i = 0; i < 6 * n; ++i)
-    REQUIRE(std::isfinite(K[i]), "pinn_set_coef_fields: coefficient %d of row %lld is not finite", (int)(i % 6), (long long)(i / 6));
-  REQUIRE(c, "pinn_set_coef_fields: null context");
-  if (c->pde == PINN_PDE_ADR_IDE)
-    return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: coefficient fields are for the adr kind (pde 5) only; the adr_ide kind (pde 6) has no variant for them");
-  if (!is_adr(c)) return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: coefficient fields are for the adr kind (pde 5) only");
-  if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: point weights are not combined with coefficient fields (pinn_pw_disable first)");
-  if (!adr_has_path(c->path))
-    return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: coefficient fields run on kernel paths 0 and 7 only (this context runs path %d)", (int)c->path);
-  if (c->comm || c->xg.box)
-    return fail(PINN_EUNSUPPORTED, "pinn_set_coef_fields: coefficient fields are single-device; this context has a communicator");
+    REQUIRE(std::isfinite(K[i]), "pinn_set_coef_fields: coefficient %d of row %lld is not finite", (int)(i % 6),
+            (long long)(i / 6));
+  if (int rc = adr_extra_gate(c, EXTRAS[X_KF], "pinn_set_coef_fields")) return rc;
   REQUIRE(n == 0 || n == n_colloc(c), "pinn_set_coef_fields: %lld rows for %lld local collocation points", (long long)n,
           (long long)n_colloc(c));
   HIPCHK(hipSetDevice(c->device));
@@ -2219,10 +2342,11 @@ static int adam_issue(pinn_ctx* c, int n_steps, bool record, int* ticket) {
     }
     int rc = eval_loss_grad(c);                   // reduce -> RCCL all-reduce -> update
     if (rc) return rc;
-    if (c->dtype == PINN_F64)
-      hipLaunchKernelGGL((k_adam<double>), dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->gl, c->theta, (double*)c->theta_r, c->adam_m, c->adam_v, alpha, c->b1, c->b2, c->eps, slot, n, c->nd, c->img);
-    else
-      hipLaunchKernelGGL((k_adam<float>), dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->gl, c->theta, (float*)c->theta_r, c->adam_m, c->adam_v, alpha, c->b1, c->b2, c->eps, slot, n, c->nd, c->img);
+    by_real(c, [&](auto r) {
+      using real = decltype(r);
+      hipLaunchKernelGGL((k_adam<real>), dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->gl, c->theta,
+                         (real*)c->theta_r, c->adam_m, c->adam_v, alpha, c->b1, c->b2, c->eps, slot, n, c->nd, c->img);
+    });
   }
   HIPCHK(hipGetLastError());
   if (record) {
@@ -2416,8 +2540,8 @@ static int lbfgs_iter(pinn_ctx* c, bool* eval) {
       LbfgsState* st_out = c->lb_state + (c->lb_flip ^ 1);
       const size_t mm = (size_t)M1 * M1;
       // dot products of this iteration: already formed behind the evaluation's reduction (one partial set per
-      // 64-column tile; opt-in), or by k_lbc_dots (two half sets, one when n > 4096) -- also N > 1 ranks, the first iteration after pinn_lbfgs_begin,
-      // an evaluation issued by somebody else in between
+      // 64-column tile; opt-in), or by k_lbc_dots (two half sets, one when n > 4096) -- also N > 1 ranks, the first
+      // iteration after pinn_lbfgs_begin, an evaluation issued by somebody else in between
       int n_part;
       if (n <= 2 * 2 * LBD_THREADS) {                 // two workgroups per ring slot, one pair stride each
         hipLaunchKernelGGL(k_lbc_dots<2>, dim3(M1, 2), dim3(LBD_THREADS), 0, c->stream, n, M1, st_in,
@@ -2430,23 +2554,26 @@ static int lbfgs_iter(pinn_ctx* c, bool* eval) {
       }
       const double* pd = c->lb_dots;
       const dim3 agrid((n + 63) / 64);
-#define COEF_APPLY(REAL)                                                                           \
-      hipLaunchKernelGGL((k_lbc_coef_apply<REAL>), agrid, dim3(LBC_THREADS), lsh, c->stream, n, M1,   \
-                         c->lb_ncorr, c->lb_max_iter, c->lb_lr, c->lb_tol_x, c->lb_tol_fun,           \
-                         c->lb_max_eval, c->lb_post_pending ? 1 : 0, n, st_in, st_out, c->gl,         \
-                         pd, n_part, c->lb_SY + c->lb_flip * mm, c->lb_YY + c->lb_flip * mm,          \
-                         c->lb_ro + c->lb_flip * M1, c->lb_SY + (c->lb_flip ^ 1) * mm,                \
-                         c->lb_YY + (c->lb_flip ^ 1) * mm, c->lb_ro + (c->lb_flip ^ 1) * M1,          \
-                         c->lb_log_iter, c->lb_log_loss, c->lb_S, c->lb_Y, c->lb_d, c->lb_gold,       \
-                         c->lb_x, c->theta, (REAL*)c->theta_r, c->nd, c->img)
-      if (c->dtype == PINN_F64) COEF_APPLY(double); else COEF_APPLY(float);
-#undef COEF_APPLY
+      by_real(c, [&](auto r) {
+        using real = decltype(r);
+        hipLaunchKernelGGL((k_lbc_coef_apply<real>), agrid, dim3(LBC_THREADS), lsh, c->stream, n, M1,
+                           c->lb_ncorr, c->lb_max_iter, c->lb_lr, c->lb_tol_x, c->lb_tol_fun,
+                           c->lb_max_eval, c->lb_post_pending ? 1 : 0, n, st_in, st_out, c->gl,
+                           pd, n_part, c->lb_SY + c->lb_flip * mm, c->lb_YY + c->lb_flip * mm,
+                           c->lb_ro + c->lb_flip * M1, c->lb_SY + (c->lb_flip ^ 1) * mm,
+                           c->lb_YY + (c->lb_flip ^ 1) * mm, c->lb_ro + (c->lb_flip ^ 1) * M1,
+                           c->lb_log_iter, c->lb_log_loss, c->lb_S, c->lb_Y, c->lb_d, c->lb_gold,
+                           c->lb_x, c->theta, (real*)c->theta_r, c->nd, c->img);
+      });
       c->lb_post_pending = false;
       c->lb_flip ^= 1;
-    } else if (c->dtype == PINN_F64)
-      hipLaunchKernelGGL((k_lbfgs_step<double>), dim3(1), dim3(LB_THREADS), 0, c->stream, n, c->lb_max_iter, c->lb_ncorr, c->lb_lr, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_x, c->theta, (double*)c->theta_r, c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al, c->lb_q, c->nd, c->img);
-    else
-      hipLaunchKernelGGL((k_lbfgs_step<float>), dim3(1), dim3(LB_THREADS), 0, c->stream, n, c->lb_max_iter, c->lb_ncorr, c->lb_lr, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_x, c->theta, (float*)c->theta_r, c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al, c->lb_q, c->nd, c->img);
+    } else
+      by_real(c, [&](auto r) {
+        using real = decltype(r);
+        hipLaunchKernelGGL((k_lbfgs_step<real>), dim3(1), dim3(LB_THREADS), 0, c->stream, n, c->lb_max_iter, c->lb_ncorr,
+                           c->lb_lr, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_x, c->theta, (real*)c->theta_r,
+                           c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al, c->lb_q, c->nd, c->img);
+      });
     *eval = c->lb_iters_issued != c->lb_max_iter;                  // last iteration: no re-evaluation
   }
   return 0;
@@ -2664,14 +2791,12 @@ int pinn_residual(pinn_ctx* c, double* f, int64_t n) {
   REQUIRE(n == cnt, "residual buffer holds %lld points, the set has %d", (long long)n, cnt);
   if (cnt == 0) return 0;
   const int NO = c->nd.n_out;
-  if ((size_t)cnt * NO > c->cap_f) { if (dev_alloc(&c->f_out, (size_t)cnt * NO * 8)) return PINN_EHIP; c->cap_f = (size_t)cnt * NO; }
+  if ((size_t)cnt * NO > c->cap_f) {
+    if (dev_alloc(&c->f_out, (size_t)cnt * NO * 8)) return PINN_EHIP;
+    c->cap_f = (size_t)cnt * NO;
+  }
   if (int rc2 = forward_taylor(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O)) return rc2;
-  const dim3 grid((cnt + 255) / 256), block(256);
-#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, first, cnt, sd.n_pad, (const vec4<REAL>*)c->O, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->f_out, NO)
-  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) { if (c->kf.on) RES(double, PDE_ADR_VAR); else if (c->src.on) RES(double, PDE_ADR_SRC); else RES(double, PDE_ADR); } else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
-  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) { if (c->kf.on) RES(float, PDE_ADR_VAR); else if (c->src.on) RES(float, PDE_ADR_SRC); else RES(float, PDE_ADR); } else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
-#undef RES
-  HIPCHK(hipGetLastError());
+  if (int rc2 = launch_residual(c, AT_SET, c->O, first, cnt, sd.n_pad, c->f_out)) return rc2;
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)cnt * NO * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -2688,17 +2813,14 @@ int pinn_residual_at(pinn_ctx* c, const double* X, int64_t n, double* f) {
   const int NO = c->nd.n_out;
   int n_pad = 0;
   if (int rc = eval_points(c, X, n, &n_pad)) return rc;
-  if (int rc = forward_taylor(c, c->xe, c->te, n_pad, n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS, c->Oe)) return rc;
-  if ((size_t)n * NO > c->cap_f) { if (dev_alloc(&c->f_out, (size_t)n * NO * 8)) return PINN_EHIP; c->cap_f = (size_t)n * NO; }
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-#define RES(REAL, P) hipLaunchKernelGGL((k_residual<REAL, P>), grid, block, 0, c->stream, 0, (int)n, n_pad, (const vec4<REAL>*)c->Oe, (const REAL*)c->theta_r, c->nd.n_net, pde_coef<REAL, P>(c), c->f_out, NO)
-  // a context with a source: s is not known at foreign points -- the operator part N[u], AdrSrcArg's null form
-#define RES_AT_SRC(REAL) hipLaunchKernelGGL((k_residual<REAL, PDE_ADR_SRC>), grid, block, 0, c->stream, 0, (int)n, n_pad, (const vec4<REAL>*)c->Oe, (const REAL*)c->theta_r, c->nd.n_net, AdrSrcArg<REAL>{pde_coef<REAL, PDE_ADR_ROBIN>(c), nullptr}, c->f_out, NO)
-  if (c->dtype == PINN_F64) { if (c->pde == 0) RES(double, 0); else if (c->pde == 1) RES(double, 1); else if (is_adr(c)) { if (c->src.on) RES_AT_SRC(double); else RES(double, PDE_ADR); } else if (is_adr_ide(c)) RES(double, PDE_ADR_IDE); else RES(double, 2); }
-  else { if (c->pde == 0) RES(float, 0); else if (c->pde == 1) RES(float, 1); else if (is_adr(c)) { if (c->src.on) RES_AT_SRC(float); else RES(float, PDE_ADR); } else if (is_adr_ide(c)) RES(float, PDE_ADR_IDE); else RES(float, 2); }
-#undef RES_AT_SRC
-#undef RES
-  HIPCHK(hipGetLastError());
+  const int chunk = n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS;
+  if (int rc = forward_taylor(c, c->xe, c->te, n_pad, chunk, c->Oe)) return rc;
+  if ((size_t)n * NO > c->cap_f) {
+    if (dev_alloc(&c->f_out, (size_t)n * NO * 8)) return PINN_EHIP;
+    c->cap_f = (size_t)n * NO;
+  }
+  // (a context with a source: s is not known at foreign points, launch_residual leaves it out)
+  if (int rc = launch_residual(c, AT_FOREIGN, c->Oe, 0, (int)n, n_pad, c->f_out)) return rc;
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)n * NO * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -2715,12 +2837,7 @@ int pinn_comm_unique_id(char* id128) {
 
 int pinn_comm_init(pinn_ctx* c, const char* id128, int n_ranks, int rank) {
   REQUIRE(c && id128 && n_ranks >= 1 && rank >= 0 && rank < n_ranks, "bad communicator arguments");
-  if (c->sa.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: self-adaptive weights are single-device (pinn_sa_disable first)");
-  if (c->pw.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: point weights are single-device (pinn_pw_disable first)");
-  if (is_adr_ide(c)) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
-  if (!c->robin.X.empty()) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: Robin points are single-device (pinn_set_robin with n = 0 first)");
-  if (c->src.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: a source term is single-device (pinn_set_source with n = 0 first)");
-  if (c->kf.on) return fail(PINN_EUNSUPPORTED, "pinn_comm_init: coefficient fields are single-device (pinn_set_coef_fields with n = 0 first)");
+  if (int rc = single_device_only(c, "pinn_comm_init")) return rc;
   HIPCHK(hipSetDevice(c->device));
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
   xg_release(c);
@@ -2735,18 +2852,7 @@ int pinn_comm_init(pinn_ctx* c, const char* id128, int n_ranks, int rank) {
 int pinn_comm_xgmi_export(pinn_ctx* c, int n_ranks, int rank, char* handle64) {
   REQUIRE(c && handle64 && n_ranks >= 1 && n_ranks <= XG_MAX_RANKS && rank >= 0 && rank < n_ranks,
           "bad arguments (at most %d ranks)", XG_MAX_RANKS);
-  if (c->sa.on)
-    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: self-adaptive weights are single-device (pinn_sa_disable first)");
-  if (c->pw.on)
-    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: point weights are single-device (pinn_pw_disable first)");
-  if (!c->robin.X.empty())
-    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: Robin points are single-device (pinn_set_robin with n = 0 first)");
-  if (c->src.on)
-    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: a source term is single-device (pinn_set_source with n = 0 first)");
-  if (c->kf.on)
-    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: coefficient fields are single-device (pinn_set_coef_fields with n = 0 first)");
-  if (is_adr_ide(c))
-    return fail(PINN_EUNSUPPORTED, "pinn_comm_xgmi_export: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch");
+  if (int rc = single_device_only(c, "pinn_comm_xgmi_export")) return rc;
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is expected to be 64 bytes");
   HIPCHK(hipSetDevice(c->device));
   xg_release(c);
@@ -2920,10 +3026,10 @@ int pinn_set_kernel_path(pinn_ctx* c, int path) {
           "3 (wide MFMA sweeps), 4 (shape-generic MFMA sweeps), 5 / 6 (4's forward / reverse half with the generic other half), "
           "7 (fused width-20 float64, register stash), 8 (fused float64 MFMA sweep, widths 65..128, 2-4 hidden layers)");
   const KernelPath p = (KernelPath)path;
-  if (c->sa.on && p != KP_FUSED20D)
-    return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: self-adaptive weights run on kernel path 7 only (pinn_sa_disable first)");
-  if (c->pw.on && p != KP_FUSED20D)
-    return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: point weights run on kernel path 7 only (pinn_pw_disable first)");
+  for (const int k : {X_SA, X_PW})
+    if (EXTRAS[k].present(c) && p != KP_FUSED20D)
+      return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: %s on kernel path 7 only (%s first)", EXTRAS[k].runs,
+                  EXTRAS[k].remove);
   if (is_adr(c) && !adr_has_path(p))
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: the adr kind (pde 5) runs on kernel paths 0 and 7 only; path %d "
                 "(%s) has no variant for it", path, PATHS[p].name);
@@ -3019,18 +3125,6 @@ int pinn_get_f64_split(pinn_ctx* c, int* split) {
 // ------------------------------------------------------------------------------------------
 // self-adaptive point weights (include/pinn_hip.h pinn_sa_*; the SAW variants of k_fused20d, fused20d_api.h)
 // ------------------------------------------------------------------------------------------
-// what the weighted kernel serves: Burgers inference in float64 on kernel path 7, one device; checked before any device work
-static int sa_supported(const pinn_ctx* c, const char* who) {
-  if (c->pde != PINN_PDE_BURGERS)
-    return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights are for Burgers inference (pde 0) only", who);
-  if (c->dtype != PINN_F64) return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights need float64", who);
-  if (c->path != KP_FUSED20D)
-    return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights need kernel path 7 (this context runs path %d)", who, (int)c->path);
-  if (c->comm || c->xg.box)
-    return fail(PINN_EUNSUPPORTED, "%s: self-adaptive weights are single-device; this context has a communicator", who);
-  return 0;
-}
-
 // the local set sizes as ensure_sets will assemble them
 static void sa_counts(const pinn_ctx* c, int64_t* n_u, int64_t* n_f) {
   *n_u = (int64_t)(c->Xu.size() / 2);
@@ -3039,7 +3133,7 @@ static void sa_counts(const pinn_ctx* c, int64_t* n_u, int64_t* n_f) {
 
 int pinn_sa_set_weights(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam_f, int64_t n_f) {
   REQUIRE(c, "null");
-  if (int rc = sa_supported(c, "pinn_sa_set_weights")) return rc;
+  if (int rc = weights_supported(c, EXTRAS[X_SA], "pinn_sa_set_weights")) return rc;
   int64_t cu, cf;
   sa_counts(c, &cu, &cf);
   REQUIRE((lam_u || n_u == 0) && (lam_f || n_f == 0), "pinn_sa_set_weights: null weight array");
@@ -3079,7 +3173,7 @@ int pinn_sa_get_weights(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, 
 
 int pinn_sa_adam_init(pinn_ctx* c, double lr) {
   REQUIRE(c, "null");
-  if (int rc = sa_supported(c, "pinn_sa_adam_init")) return rc;
+  if (int rc = weights_supported(c, EXTRAS[X_SA], "pinn_sa_adam_init")) return rc;
   REQUIRE(std::isfinite(lr) && lr >= 0.0, "pinn_sa_adam_init: lr %g must be finite and >= 0", lr);
   c->sa.lr = lr;
   return 0;
@@ -3094,17 +3188,6 @@ int pinn_sa_disable(pinn_ctx* c) {
 // ------------------------------------------------------------------------------------------
 // per-point loss weights of the adr kind (include/pinn_hip.h pinn_pw_*; k_fused20d<PDE_ADR, ..> with SAW, fused20d_api.h)
 // ------------------------------------------------------------------------------------------
-// what the weighted kernel serves: the adr kind in float64 on kernel path 7, one device; checked before any device work
-static int pw_supported(const pinn_ctx* c, const char* who) {
-  if (c->pde != PINN_PDE_ADR) return fail(PINN_EUNSUPPORTED, "%s: point weights are for the adr kind (pde 5) only", who);
-  if (c->dtype != PINN_F64) return fail(PINN_EUNSUPPORTED, "%s: point weights need float64", who);
-  if (c->path != KP_FUSED20D)
-    return fail(PINN_EUNSUPPORTED, "%s: point weights need kernel path 7 (this context runs path %d)", who, (int)c->path);
-  if (c->comm || c->xg.box)
-    return fail(PINN_EUNSUPPORTED, "%s: point weights are single-device; this context has a communicator", who);
-  return 0;
-}
-
 // counts against the local set sizes as ensure_sets will assemble them; a NULL array is allowed with the right count
 static int pw_check_counts(const pinn_ctx* c, const char* who, int64_t n_u, int64_t n_f, int64_t n_b) {
   int64_t cu, cf;
@@ -3119,13 +3202,11 @@ static int pw_check_counts(const pinn_ctx* c, const char* who, int64_t n_u, int6
 int pinn_pw_set(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam_f, int64_t n_f, const double* lam_b,
                 int64_t n_b) {
   REQUIRE(c, "null");
-  if (int rc = pw_supported(c, "pinn_pw_set")) return rc;
-  if (!c->robin.X.empty())
-    return fail(PINN_EUNSUPPORTED, "pinn_pw_set: point weights do not cover Robin points; remove them first (pinn_set_robin with n = 0)");
-  if (c->src.on)
-    return fail(PINN_EUNSUPPORTED, "pinn_pw_set: point weights are not combined with a source term; remove it first (pinn_set_source with n = 0)");
-  if (c->kf.on)
-    return fail(PINN_EUNSUPPORTED, "pinn_pw_set: point weights are not combined with coefficient fields; remove them first (pinn_set_coef_fields with n = 0)");
+  if (int rc = weights_supported(c, EXTRAS[X_PW], "pinn_pw_set")) return rc;
+  for (const int k : {X_ROBIN, X_SRC, X_KF}) {
+    const Extra& x = EXTRAS[k];
+    if (x.present(c)) return fail(PINN_EUNSUPPORTED, "pinn_pw_set: %s; remove %s first (%s)", x.pw_clash, x.pron, x.remove);
+  }
   if (int rc = pw_check_counts(c, "pinn_pw_set", n_u, n_f, n_b)) return rc;
   for (int64_t j = 0; lam_u && j < n_u; ++j) REQUIRE(std::isfinite(lam_u[j]), "pinn_pw_set: lam_u[%lld] is not finite", (long long)j);
   for (int64_t i = 0; lam_f && i < n_f; ++i) REQUIRE(std::isfinite(lam_f[i]), "pinn_pw_set: lam_f[%lld] is not finite", (long long)i);
@@ -3163,7 +3244,7 @@ int pinn_pw_get(pinn_ctx* c, double* lam_u, int64_t n_u, double* lam_f, int64_t 
 
 int pinn_pw_adam_init(pinn_ctx* c, double rate_u, double rate_f, double rate_b) {
   REQUIRE(c, "null");
-  if (int rc = pw_supported(c, "pinn_pw_adam_init")) return rc;
+  if (int rc = weights_supported(c, EXTRAS[X_PW], "pinn_pw_adam_init")) return rc;
   const double r[3] = {rate_u, rate_f, rate_b};
   for (int i = 0; i < 3; ++i)
     REQUIRE(std::isfinite(r[i]) && r[i] >= 0.0, "pinn_pw_adam_init: rate %d (%g) must be finite and >= 0", i, r[i]);

@@ -136,21 +136,23 @@ def _ide_scale(layers, theta, X_f, dtype):
 
 
 def restate(case, dtype, inp=None, **totals):
-    """the case's kind in `dtype` -> the dict of restate_adr.  inp: other inputs than the case's own (mutants)"""
+    """the case's kind in `dtype` -> the dict of restate_adr.  inp: other inputs than the case's own (mutants, a rank's block);
+    totals: n_f_total, n_u_total, n_b_total, n_w_total (the kinds without Robin points take no n_w_total but None)"""
     x = inputs(case["id"]) if inp is None else inp
     L = case["layers"]
     none = lambda a: a if a is not None and len(a) else None      # noqa: E731
     if case["kind"] == "adr":
         return restate_adr(L, x["w"], case["coeffs"], x["X_f"], x["X_u"], x["u"], x["X_lo"], x["X_hi"], x["robin"], x["s"],
                            x["K"], dtype, **totals)
+    assert totals.pop("n_w_total", None) in (None, 0)
     if case["kind"] == "adr_ide":
         lo, g, A, ex = adr_ide_ref.restate(x["w"], L, LB, UB, x["X_f"], none(x["X_u"]), x["u"], none(x["X_lo"]), x["X_hi"],
                                            case["mask"], dtype, **totals)
         return {"loss": lo, "terms": (ex["mse_f"], ex["mse_u"], ex["mse_b"]), "grad": g, "A": A, "f": ex["f"],
                 "A_f": _ide_scale(L, x["w"], x["X_f"], dtype), "r": np.zeros(0), "A_r": np.zeros(0)}
-    assert case["kind"] == "adr_pw" and np.dtype(dtype) == np.float64 and not totals
+    assert case["kind"] == "adr_pw" and np.dtype(dtype) == np.float64
     lo, g, terms, _ = adr_pw_ref.loss_grad(x["w"], L, LB, UB, x["X_f"], none(x["X_u"]), x["u"], none(x["X_lo"]), x["X_hi"],
-                                           case["coeffs"], none(x["lam"][0]), x["lam"][1], none(x["lam"][2]))
+                                           case["coeffs"], none(x["lam"][0]), x["lam"][1], none(x["lam"][2]), **totals)
     return {"loss": lo, "terms": terms, "grad": g, "A": None, "f": None, "A_f": None, "r": np.zeros(0), "A_r": np.zeros(0)}
 
 
@@ -303,11 +305,18 @@ def make_inputs(case, seed=None):
 
 
 # ---- yardsticks -------------------------------------------------------------------------------------------------------------
-def has_wide(case, dtype_name):
-    """float32 is judged against float64; float64 against longdouble up to grad_entries.LONGDOUBLE_POINTS points"""
+def has_wide(case, dtype_name, n=None):
+    """float32 is judged against float64; float64 against longdouble up to grad_entries.LONGDOUBLE_POINTS points (n: the point
+    count of explicit inputs, where they are not the case's own)"""
     if case["kind"] == "adr_pw":
         return False                                                  # adr_pw_ref is float64 only
-    return dtype_name == "f32" or (n_points(case) <= ge.LONGDOUBLE_POINTS and ge.longdouble_is_wider())
+    n = n_points(case) if n is None else n
+    return dtype_name == "f32" or (n <= ge.LONGDOUBLE_POINTS and ge.longdouble_is_wider())
+
+
+def n_points_of(inp):
+    """n_points of explicit inputs (make_inputs' dict, or a block of it)"""
+    return 2 * len(inp["X_lo"]) + len(inp["X_u"]) + len(inp["X_f"]) + (len(inp["robin"][0]) if inp["robin"] else 0)
 
 
 def _scaled(got, ref, scale):
@@ -337,16 +346,40 @@ def _restated(cid, type_name):
     return restate(CASE_BY_ID[cid], {"f32": np.float32, "f64": np.float64, "ld": np.longdouble}[type_name])
 
 
-def reference(cid, dtype_name):
+_TYPES = {"f32": np.float32, "f64": np.float64, "ld": np.longdouble}
+
+
+def _wider_name(case, dtype_name, n=None):
+    return ("f64" if dtype_name == "f32" else "ld") if has_wide(case, dtype_name, n) else "f64"
+
+
+def reference(cid, dtype_name, inp=None, totals=None):
     """the restatement a device result in `dtype_name` is compared with: the wider type, or float64 itself for a float64 set
-    that is too large for an 80-bit run (cached: shared by every config, never written to)"""
-    case = CASE_BY_ID[cid]
-    return _restated(cid, ("f64" if dtype_name == "f32" else "ld") if has_wide(case, dtype_name) else "f64")
+    that is too large for an 80-bit run (cached: shared by every config, never written to).
+    inp, totals: explicit inputs and denominators (a rank's block, adr_shards.shard_inputs) -- `cid` is then the case itself or
+    its id, the rule for the wider type goes by the point count of `inp`, and nothing is cached here"""
+    if inp is None:
+        return _restated(cid, _wider_name(CASE_BY_ID[cid], dtype_name))
+    case = cid if isinstance(cid, dict) else CASE_BY_ID[cid]
+    return restate(case, _TYPES[_wider_name(case, dtype_name, n_points_of(inp))], inp, **(totals or {}))
+
+
+def yardsticks(cid, dtype_name, inp=None, totals=None, ref=None):
+    """-> {quantity: max(plain error, 32 u)}; a float64 set without an 80-bit run: grad_entries.ASSUMED_F64_ULPS u.
+    inp, totals: as reference() takes them; ref: reference(cid, dtype_name, inp, totals) where the caller holds it already"""
+    if inp is None:
+        return _yardsticks(cid, dtype_name)
+    case = cid if isinstance(cid, dict) else CASE_BY_ID[cid]
+    u = ge.unit_roundoff(ge.DTYPES[dtype_name])
+    if not has_wide(case, dtype_name, n_points_of(inp)):
+        return {q: max(ge.ASSUMED_F64_ULPS, ge.FLOOR_ULPS) * u for q in QUANTITIES}
+    ref = reference(case, dtype_name, inp, totals) if ref is None else ref
+    plain = deviations(restate(case, _TYPES[dtype_name], inp, **(totals or {})), ref)
+    return {q: max(plain[q], ge.FLOOR_ULPS * u) for q in QUANTITIES}
 
 
 @functools.lru_cache(maxsize=None)
-def yardsticks(cid, dtype_name):
-    """-> {quantity: max(plain error, 32 u)}; a float64 set without an 80-bit run: grad_entries.ASSUMED_F64_ULPS u"""
+def _yardsticks(cid, dtype_name):
     case = CASE_BY_ID[cid]
     u = ge.unit_roundoff(ge.DTYPES[dtype_name])
     if not has_wide(case, dtype_name):

@@ -46,9 +46,11 @@ def raw_coeffs(theta):
     return tail
 
 
-def restate(theta, layers, lb, ub, X_f, X_u, u, X_lo, X_hi, mask=ALL, dtype=np.float64, n_f_total=None):
+def restate(theta, layers, lb, ub, X_f, X_u, u, X_lo, X_hi, mask=ALL, dtype=np.float64, n_f_total=None, n_u_total=None,
+            n_b_total=None):
     """-> (loss, flat gradient [n_net + 6], A, extras) with all arithmetic in `dtype`; A is the entrywise rounding scale
-    of grad_entries (tail: sum |fb df/dp_k|, 0 where frozen); extras: f, mse_f, mse_u, mse_b"""
+    of grad_entries (tail: sum |fb df/dp_k|, 0 where frozen); extras: f, mse_f, mse_u, mse_b.  n_*_total: the denominator
+    of a class whose rows are a block of a larger set (a rank's shard), or that has lost rows (mutants)"""
     dt = np.dtype(dtype).type
     wide = np.longdouble if dt is np.longdouble else np.float64
     lbd = np.asarray(lb, dtype=wide)
@@ -77,14 +79,14 @@ def restate(theta, layers, lb, ub, X_f, X_u, u, X_lo, X_hi, mask=ALL, dtype=np.f
     zero = lambda x: np.zeros_like(x)
     if X_u is not None and len(X_u):
         X_u, u = cast(X_u).reshape(-1, 2), cast(u).reshape(-1, 1)
-        n_u = dt(X_u.shape[0])
+        n_u = dt(X_u.shape[0] if n_u_total is None else n_u_total)
         (hu, _, _, _), cu = ge._forward(params, X_u, lbd, s, False)
         d = hu - u
         ge._backward(params, cu, dt(2) * d / n_u, zero(d), zero(d), zero(d), G, A)
         mse_u = np.sum(d * d) / n_u
     if X_lo is not None and len(X_lo):
         X_lo, X_hi = cast(X_lo).reshape(-1, 2), cast(X_hi).reshape(-1, 2)
-        n_b = dt(X_lo.shape[0])
+        n_b = dt(X_lo.shape[0] if n_b_total is None else n_b_total)
         (hl, pl, _, _), cl = ge._forward(params, X_lo, lbd, s, False)
         (hh, ph, _, _), ch = ge._forward(params, X_hi, lbd, s, False)
         dh, dp = hl - hh, pl - ph

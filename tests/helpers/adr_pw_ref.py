@@ -23,14 +23,17 @@ def _col(lam, n):
     return np.ones((n, 1)) if lam is None else np.asarray(lam, dtype=np.float64).reshape(n, 1)
 
 
-def loss_grad(w, layers, lb, ub, X_f, X_u, u, X_lo, X_hi, coeffs, lam_u=None, lam_f=None, lam_b=None):
+def loss_grad(w, layers, lb, ub, X_f, X_u, u, X_lo, X_hi, coeffs, lam_u=None, lam_f=None, lam_b=None, n_f_total=None,
+              n_u_total=None, n_b_total=None):
     """-> (loss, grad_theta, terms = (mse_f, mse_u, mse_b), (dL/dlam_u, dL/dlam_f, dL/dlam_b)); X_u / X_lo may be None or
-    empty, a lam of None is all ones"""
+    empty, a lam of None is all ones.  n_*_total: the denominator N of a class whose rows are a block of a larger set (a
+    rank's shard), as in adr_ref.adr_loss_grad"""
     a0, a1, nu, r1, r2, r3 = (float(v) for v in coeffs)
     lb, ub = np.asarray(lb, dtype=np.float64), np.asarray(ub, dtype=np.float64)
     params = mlp.unpack(w, layers)
-    N_f = X_f.shape[0]
-    lf = _col(lam_f, N_f)
+    n_f = X_f.shape[0]
+    N_f = n_f if n_f_total is None else int(n_f_total)
+    lf = _col(lam_f, n_f)
     mf = lf * lf
     (h, p, q, r), cache = mlp.taylor_forward(params, X_f, lb, ub)
     f = q + (a0 + a1 * h) * p - nu * r + r1 * h + r2 * h * h + r3 * h * h * h
@@ -42,16 +45,16 @@ def loss_grad(w, layers, lb, ub, X_f, X_u, u, X_lo, X_hi, coeffs, lam_u=None, la
     mse_u = mse_b = 0.0
     dlam_u, dlam_b = np.zeros(0), np.zeros(0)
     if X_u is not None and len(X_u):
-        N_u = X_u.shape[0]
-        lu = _col(lam_u, N_u)
+        N_u = X_u.shape[0] if n_u_total is None else int(n_u_total)
+        lu = _col(lam_u, X_u.shape[0])
         mu = lu * lu
         d = mlp.forward_value(params, X_u, lb, ub) - np.asarray(u, dtype=np.float64).reshape(-1, 1)
         mse_u = np.sum(mu * (d * d)) / N_u
         grads = mlp.add_grads(grads, mlp.value_backward(params, X_u, lb, ub, 2.0 * (mu * d) / N_u))
         dlam_u = (2.0 * lu * (d * d) / N_u).ravel()
     if X_lo is not None and len(X_lo):
-        N_b = X_lo.shape[0]
-        lbd = _col(lam_b, N_b)
+        N_b = X_lo.shape[0] if n_b_total is None else int(n_b_total)
+        lbd = _col(lam_b, X_lo.shape[0])
         mb = lbd * lbd
         (hl, pl, _, _), cl = mlp.taylor_forward(params, X_lo, lb, ub)
         (hu, pu, _, _), cu = mlp.taylor_forward(params, X_hi, lb, ub)

@@ -144,11 +144,12 @@ def same_bits(a, b):
 
 
 # ---- 1. parity ----------------------------------------------------------------------------------------------------------------------
-def judge(record, case, dtype, path, got, tag):
-    """every quantity against the wider restatement on its own scale; -> {quantity: ratio deviation / yardstick}"""
+def judge(record, case, dtype, path, got, tag, ref=None, yard=None):
+    """every quantity against the wider restatement on its own scale; -> {quantity: ratio deviation / yardstick}.  ref, yard:
+    the restatement and yardsticks of other inputs than the case's own (a block of it, tests/test_gpu_adr_shards.py)"""
     cid = case["id"]
-    ref = af.reference(cid, dtype)
-    dev, yard = af.deviations(got, ref), af.yardsticks(cid, dtype)
+    ref = af.reference(cid, dtype) if ref is None else ref
+    dev, yard = af.deviations(got, ref), af.yardsticks(cid, dtype) if yard is None else yard
     k = af.allowance(case, path, dtype)
     u = ge.unit_roundoff(ge.DTYPES[dtype])
     ratio = {q: dev[q] / yard[q] for q in af.QUANTITIES}

@@ -1246,10 +1246,12 @@ static int disc_ensure(pinn_ctx* c) {
   if (dev_alloc(&c->d_dAp, (size_t)dd.n_chunks * 3 * dd.n_pad * dd.wp * rs) ||
       dev_alloc(&c->d_lossp, (size_t)G * dd.n_chunks * rs) ||
       dev_alloc(&c->d_lamp, (size_t)G * dd.n_chunks * 2 * rs)) return PINN_EHIP;
-  HIPCHK(hipMemset(c->d_lamp, 0, (size_t)G * dd.n_chunks * 2 * rs));
+  // cleared in stream order: the context's stream is non-blocking, so a hipMemset on the null stream (asynchronous to the
+  // host for device memory) is not ordered before the first evaluation's kernels and can wipe rows they have written
+  HIPCHK(hipMemsetAsync(c->d_lamp, 0, (size_t)G * dd.n_chunks * 2 * rs, c->stream));
   const size_t need_part = (size_t)G * c->R * rs;
   if (need_part > c->cap_part) { if (dev_alloc(&c->part, need_part)) return PINN_EHIP; c->cap_part = need_part; }
-  HIPCHK(hipMemset(c->part, 0, need_part));
+  HIPCHK(hipMemsetAsync(c->part, 0, need_part, c->stream));
   c->dd = dd;
   c->n_rows = G;
   c->sets_dirty = false;
@@ -2685,7 +2687,10 @@ int pinn_lbfgs_get_x(pinn_ctx* c, double* x, int64_t n) {
   REQUIRE(c && x && n == c->nd.n_theta, "bad arguments");
   REQUIRE(c->lb_x, "no L-BFGS run yet");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpy(x, c->lb_x, (size_t)n * 8, hipMemcpyDeviceToHost));
+  // in stream order, as pinn_get_weights: the context's stream is non-blocking, so a copy on the null stream would not wait
+  // for what pinn_lbfgs_begin or an enqueued chunk has still in flight (the copy of the start into lb_x, a step kernel)
+  HIPCHK(hipMemcpyAsync(x, c->lb_x, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -290,6 +290,10 @@ int pinn_debug_t16f_stamps(long long* out512);
  * owns (4 = a 16-row tile), out[48] = 1 when the last tile per side runs as strips.  tests/test_host_api.py checks that
  * every tile and every row is dealt exactly once for every width. */
 int pinn_debug_t16_deal(int W, int* out49);
+/* Device and pinned host blocks this process's engine owns right now, and their bytes (every build; no device is touched).
+ * Contexts and ensembles give back all they hold when destroyed: a test takes the pair before and after and compares.
+ * Either pointer may be NULL.  (Additive: the ABI version stays 6.) */
+int pinn_debug_live_buffers(int64_t* n, int64_t* bytes);
 
 /* Ensembles: K = n_members (1..64) copies of one float64 Burgers net (kernel path 7: pde 0 or 1, 2-20-...-20-1 with 4, 6
  * or 8 hidden layers) trained side by side on ONE point set with one set of PDE parameters -- seeds, learning-rate

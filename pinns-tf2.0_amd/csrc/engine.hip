@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/pinn_hip.h"
+#include "devbuf.h"
 #include "kernels_fused20.h"
 #include "kernels_fused20m.h"
 #include "fused20d_api.h"
@@ -125,8 +126,7 @@ enum KernelPath : int {
 // replaced since (lam_prepare puts its weights back to 1).  A surface that has no pairs leaves that class empty.
 enum { LAM_PAIRS, LAM_DATA, LAM_COL, LAM_CLASSES };
 struct LamStore {
-  double* buf = nullptr;
-  size_t cap = 0;
+  DevBuf<double> buf;
   int n_hdr = 0;
   double hdr[PW_CONST] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // the longer of the two headers; the rest stays 0
   int n[LAM_CLASSES] = {0, 0, 0};
@@ -152,41 +152,38 @@ struct pinn_ctx {
   SetDesc sd{};
 
   // device: training set (compute dtype)
-  void *xs = nullptr, *ts = nullptr, *tgt = nullptr;
-  // device: parameters / optimiser (float64) + compute-dtype mirror
-  double *theta = nullptr, *gl = nullptr, *adam_m = nullptr, *adam_v = nullptr;
-  void* theta_r = nullptr;
-  float* img = nullptr;              // LDS weight image of k_fused20m (f32 only)
-  int* row_index = nullptr;          // k_fused20d: entry of a wave's gradient block list -> flat parameter index
+  DevBuf<void> xs, ts, tgt;
+  // device: parameters / optimiser (float64) + compute-dtype mirror.  In an ensemble member theta, theta_r, gl, adam_m, adam_v
+  // and d_nonfinite (below) are views of the ensemble's blocks (ens_build)
+  DevBuf<double> theta, gl, adam_m, adam_v;
+  DevBuf<void> theta_r;
+  DevBuf<float> img;                 // LDS weight image of k_fused20m (f32 only)
+  DevBuf<int> row_index;             // k_fused20d: entry of a wave's gradient block list -> flat parameter index
   int n_cu = 256, n_wg = 0;          // compute units; workgroups of the persistent kernel
   int f64_split = -1;                // PINN_F64_SPLIT, read by pinn_create: -1 auto, 0 never, 1 required (split_plan)
   // device: scratch
-  void *S = nullptr, *O = nullptr, *ZA = nullptr, *ZB = nullptr, *part = nullptr;
-  size_t cap_S = 0, cap_O = 0, cap_Z = 0, cap_part = 0, cap_pts = 0;
+  DevBuf<void> S, O, ZA, ZB, part;
   int chunk = 0, n_rows = 0, R = 0;
   // device: evaluation-only scratch (predict)
-  void *xe = nullptr, *te = nullptr, *Oe = nullptr;
-  size_t cap_eval = 0;
-  double* f_out = nullptr;
-  size_t cap_f = 0;
+  DevBuf<void> xe, te, Oe;
+  DevBuf<double> f_out;
   // evaluation points / reference values of the last predict / error call, kept on the host (to recognise a repeat:
   // the scripts evaluate the same X_star grid again and again) and on the device
   std::vector<double> ev_X, ev_ref;
   int ev_n_pad = 0;
-  double *pred = nullptr, *d_ref = nullptr, *err_partial = nullptr, *err_res = nullptr;
-  size_t cap_pred = 0, cap_ref = 0, cap_errp = 0;
-  double* h_err = nullptr;           // pinned [3]
+  DevBuf<double> pred, d_ref, err_partial, err_res;
+  PinnedBuf<double> h_err;           // [3]
   // first evaluation (1-based count since pinn_create) whose reduced loss was not finite; 0 = none so far.
   // The reference has no such guard (a NaN loss just propagates, custom_lbfgs.py:154); this only records it.
-  unsigned long long* d_nonfinite = nullptr;
+  DevBuf<unsigned long long> d_nonfinite;
   unsigned long long n_evals = 0;
 
   // Adam
   double lr = 1e-3, b1 = 0.9, b2 = 0.999, eps = 1e-7;
   int64_t adam_t = 0;
   bool adam_ready = false, adam_want_terms = false;
-  double* loss_hist = nullptr;       // N_PENDING regions of cap_loss_hist steps x 3 loss parts (one per chunk in flight)
-  size_t cap_loss_hist = 0;
+  DevBuf<double> loss_hist;          // N_PENDING regions of hist_stride steps x 3 loss parts (one per chunk in flight)
+  size_t hist_stride = 0;            // layout, not a guard: where a ticket's region starts; follows the ring when it is replaced
 
   // Chunks of optimiser steps whose results the host has not collected yet (pinn_adam_enqueue / pinn_lbfgs_enqueue ->
   // ..._collect): the kernels of chunk k+1 are already in the stream while the host reads and logs chunk k, so a logging
@@ -198,12 +195,12 @@ struct pinn_ctx {
     int base = 0, issued_upto = 0;     // L-BFGS: first log entry of the window; iterations issued when it was enqueued
     bool want_terms = false;
     hipEvent_t ev = nullptr;
-    double* h_loss = nullptr; size_t cap_loss = 0;      // pinned
-    int* h_iter = nullptr; size_t cap_iter = 0;         // pinned
-    LbfgsState* h_state = nullptr;                      // pinned
+    PinnedBuf<double> h_loss;
+    PinnedBuf<int> h_iter;
+    PinnedBuf<LbfgsState> h_state;
   };
   static constexpr int N_SNAP = 4;     // pinn_weights_snapshot / _restore slots
-  double* snap = nullptr;
+  DevBuf<double> snap;
   unsigned snap_valid = 0;
   static constexpr int N_PENDING = 4;
   Pending pend[N_PENDING];
@@ -211,31 +208,29 @@ struct pinn_ctx {
   int lb_issued_at_read = 0;           // lb_iters_issued when lb_logged_read was last brought up to date
 
   // L-BFGS
-  LbfgsState* lb_state = nullptr;    // two copies (double buffered, see k_lbc_coef_apply); lb_flip = current
+  DevBuf<LbfgsState> lb_state;       // two copies (double buffered, see k_lbc_coef_apply); lb_flip = current
   int lb_flip = 0;
-  double *lb_x = nullptr, *lb_d = nullptr, *lb_gold = nullptr, *lb_S = nullptr, *lb_Y = nullptr,
-         *lb_ro = nullptr, *lb_al = nullptr, *lb_q = nullptr, *lb_log_loss = nullptr;
-  int* lb_log_iter = nullptr;
+  DevBuf<double> lb_x, lb_d, lb_gold, lb_S, lb_Y, lb_ro, lb_al, lb_q, lb_log_loss;
+  DevBuf<int> lb_log_iter;
   // (the host mirrors read back by pinn_lbfgs_run -- state + the log entries a chunk may have produced, three asynchronous
   //  copies behind ONE wait; two blocking hipMemcpy more cost ~25 us per call -- are the Pending buffers above)
-  int lb_max_iter = 0, lb_ncorr = 0, lb_cap_corr = 0, lb_cap_log = 0, lb_logged_read = 0;
+  int lb_max_iter = 0, lb_ncorr = 0, lb_logged_read = 0;
   double lb_lr = 1.0, lb_tol_fun = 0, lb_tol_x = 0, lb_max_eval = 0;
   int lb_iters_issued = 0;
   bool lb_post_pending = false;      // an evaluation whose break tests / log entry are still due
   bool lb_ready = false;
   // compact (Gram-matrix) mode
   int lb_mode = 1, lb_mode_active = 0, lb_M1 = 0;
-  double *lb_SY = nullptr, *lb_YY = nullptr, *lb_dots = nullptr, *lb_cs = nullptr, *lb_cy = nullptr;
-  LbcExtra* lb_ex = nullptr;
+  DevBuf<double> lb_SY, lb_YY, lb_dots, lb_cs, lb_cy;
+  DevBuf<LbcExtra> lb_ex;
   double t16_cost_full = T16_COST_FULL, t16_cost_strip = T16_COST_STRIP;   // k_t16_fused: weights of the gradient-tile dealing (t16_deal; PINN_T16_COSTS)
   long long t16_handover_ticks = 50000000ll;   // bound of that hand-over's wait, 100 MHz ticks (PINN_T16_HANDOVER_TICKS)
   bool t16_prepass_pinned = false;     // PINN_T16_PREPASS was given: the data-parallel default below does not apply
   bool t16_prepass = false;            // k_t16_fused: boundary outputs by a k_t16_fwd pre-pass instead of the in-kernel hand-over
                                        // (PINN_T16_PREPASS=1, or switched on for good after a hand-over that timed out)
-  unsigned int* t16_bsync = nullptr;   // k_t16_fused: boundary-group hand-over counter (never reset; t16_bcount = its value after the last launch)
+  DevBuf<unsigned int> t16_bsync;      // k_t16_fused: boundary-group hand-over counter (never reset; t16_bcount = its value after the last launch)
   unsigned int t16_bcount = 0;
-  double* t16_gscr = nullptr;          // k_t16_fused: tile-major weight-gradient scratch, one block per workgroup
-  size_t t16_gscr_bytes = 0;
+  DevBuf<double> t16_gscr;             // k_t16_fused: tile-major weight-gradient scratch, one block per workgroup
 
   // collocation set generated on the device (pinn_lhs_collocation) instead of handed over
   struct { bool on = false; int64_t n_design = 0, first = 0, count = 0; uint64_t seed = 0; } lhs;
@@ -245,13 +240,11 @@ struct pinn_ctx {
   struct {
     bool on = false, filled = false;
     int64_t n_design = 0, first = 0, count = 0;
-    double *cx = nullptr, *ct = nullptr;
-    size_t cap = 0;
-    void *px = nullptr, *pt = nullptr, *O = nullptr;
-    double* f = nullptr;
-    unsigned long long *w = nullptr, *bsum = nullptr;
-    RadTotals* tot = nullptr;
-    size_t cap_pool = 0;
+    DevBuf<double> cx, ct;
+    DevBuf<void> px, pt, O;
+    DevBuf<double> f;
+    DevBuf<unsigned long long> w, bsum;
+    DevBuf<RadTotals> tot;
   } rad;
 
   // self-adaptive point weights (pinn_sa_*, k_fused20d<0, H, ., false, false, true>): SA_CONST header, data and collocation points
@@ -274,11 +267,9 @@ struct pinn_ctx {
   struct {
     std::vector<double> X, alpha, beta, g;
     int64_t n_total = 0;
-    void* ab = nullptr;
-    size_t cap = 0;
+    DevBuf<void> ab;
     int first = 0, n = 0;
-    double* out = nullptr;             // pinn_robin_residual's device buffer
-    size_t cap_out = 0;
+    DevBuf<double> out;                // pinn_robin_residual's device buffer
   } robin;
 
   // source term of the adr kind (pinn_set_source; template value PDE_ADR_SRC of the kernels): s_i as handed over, one value per
@@ -297,28 +288,26 @@ struct pinn_ctx {
   struct {
     std::vector<double> K;
     bool on = false, stale = false;
-    void* dev = nullptr;
-    size_t cap = 0;                    // entries the device array holds
+    DevBuf<void> dev;
   } kf;
 
   // discrete-time models (pde 3, 4): stage sets as handed over, device copies, scratch
   struct DiscSet { std::vector<double> x, t, M; int q = 0; bool has_M = false; };
   DiscSet dset[2];
   DiscDesc dd{};
-  int* d_ginfo = nullptr;
-  void *d_M[2] = {nullptr, nullptr}, *d_MT[2] = {nullptr, nullptr};
-  void *d_Ast = nullptr, *d_A3 = nullptr, *d_U3 = nullptr, *d_Nn = nullptr, *d_R = nullptr, *d_dAp = nullptr,
-       *d_lossp = nullptr, *d_lamp = nullptr;
+  DevBuf<int> d_ginfo;
+  DevBuf<void> d_M[2], d_MT[2];        // empty: that stage set has no table
+  DevBuf<void> d_Ast, d_A3, d_U3, d_Nn, d_R, d_dAp, d_lossp, d_lamp;
 
   // RCCL
   ncclComm_t comm = nullptr;
   int n_ranks = 1, rank = 0;
   // peer-mapped mailbox all-reduce (kernels_xgmi.h); comm_mode: 0 none, 1 RCCL, 2 mailboxes
   struct {
-    void* box = nullptr;                      // this rank's mailbox (uncached, exported through hipIpc)
+    void* box = nullptr;                      // this rank's mailbox (uncached, exported through hipIpc): raw, xg_release frees it
     void* opened[XG_MAX_RANKS] = {};          // peers' mailboxes as mapped here (nullptr for own rank)
     XgPeers peers{};
-    int* err = nullptr;
+    DevBuf<int> err;
     unsigned int seq = 0;                     // evaluation counter; 0 is never used (an all-zero mailbox is invalid)
     bool attached = false, on = false;
     bool poisoned = false;                    // a peer was lost mid-step: weights / moments are a mix of two iterates
@@ -327,7 +316,7 @@ struct pinn_ctx {
   } xg;
 
   // per-wave phase timeline of the fused kernel (profiling build only)
-  long long* stamps = nullptr;
+  DevBuf<long long> stamps;
   // timing
   std::vector<hipEvent_t> ev;
   int ev_used = 0, ev_cap_evals = 0, ev_every = 1;
@@ -363,12 +352,12 @@ static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
     return AdrCoef<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5]};
   else if constexpr (PDE == PDE_ADR_ROBIN)
     return AdrRobinArg<real>{AdrCoef<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5]},
-                             (const real*)c->robin.ab, c->robin.first, c->robin.n,
+                             c->robin.ab.as<real>(), c->robin.first, c->robin.n,
                              (real)(c->robin.n_total > 0 ? 1.0 / (double)c->robin.n_total : 0.0)};
   else if constexpr (PDE == PDE_ADR_SRC)   // the set's own residuals: s by set index is tgt itself
-    return AdrSrcArg<real>{pde_coef<real, PDE_ADR_ROBIN>(c), (const real*)c->tgt};
+    return AdrSrcArg<real>{pde_coef<real, PDE_ADR_ROBIN>(c), c->tgt.as<real>()};
   else if constexpr (PDE == PDE_ADR_VAR)   // the collocation slots of tgt are zero without a source
-    return AdrVarArg<real>{pde_coef<real, PDE_ADR_SRC>(c), (const real*)c->kf.dev};
+    return AdrVarArg<real>{pde_coef<real, PDE_ADR_SRC>(c), c->kf.dev.as<real>()};
   else if constexpr (PDE == PDE_ADR_IDE)
     return AdrIdeArg{c->adr_mask};
   else
@@ -562,14 +551,6 @@ static int path_rows(const pinn_ctx* c) {
   }
 }
 
-template <typename T>
-static int dev_alloc(T** p, size_t bytes) {
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  HIPCHK(hipMalloc((void**)p, bytes ? bytes : 16));
-  return 0;
-}
-
 static int upload_real(pinn_ctx* c, void* dst, const double* src, size_t n) {
   if (c->dtype == PINN_F64) {
     HIPCHK(hipMemcpyAsync(dst, src, n * 8, hipMemcpyHostToDevice, c->stream));
@@ -593,7 +574,7 @@ static int lhs_fill(pinn_ctx* c) {
   const dim3 grid((unsigned)((cnt + 255) / 256)), block(256);
   by_real(c, [&](auto r) {
     using real = decltype(r);
-    hipLaunchKernelGGL((k_lhs_fill<real>), grid, block, 0, c->stream, (real*)c->xs + off, (real*)c->ts + off, cnt,
+    hipLaunchKernelGGL((k_lhs_fill<real>), grid, block, 0, c->stream, c->xs.as<real>() + off, c->ts.as<real>() + off, cnt,
                        (uint64_t)c->lhs.first, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
                        c->ub[1] - c->lb[1]);
   });
@@ -667,30 +648,21 @@ static int ensure_sets(pinn_ctx* c) {
   }
 
   const size_t rs = real_size(c);
-  if ((size_t)n_pad > c->cap_pts) {
-    if (dev_alloc(&c->xs, n_pad * rs)) return PINN_EHIP;
-    if (dev_alloc(&c->ts, n_pad * rs)) return PINN_EHIP;
-    if (dev_alloc(&c->tgt, (size_t)NO * n_pad * rs)) return PINN_EHIP;
-    if (dev_alloc(&c->O, (size_t)NO * n_pad * 4 * rs)) return PINN_EHIP;
-    c->cap_pts = n_pad;
-  }
+  HIPCHK(c->xs.reserve_bytes(n_pad * rs));
+  HIPCHK(c->ts.reserve_bytes(n_pad * rs));
+  HIPCHK(c->tgt.reserve_bytes((size_t)NO * n_pad * rs));
+  HIPCHK(c->O.reserve_bytes((size_t)NO * n_pad * 4 * rs));
   if (upload_real(c, c->xs, hx.data(), n_pad)) return PINN_EHIP;
   if (upload_real(c, c->ts, ht.data(), n_pad)) return PINN_EHIP;
   if (upload_real(c, c->tgt, htg.data(), (size_t)NO * n_pad)) return PINN_EHIP;
   if (n_w > 0) {
     std::vector<double> hab((size_t)2 * n_w);
     for (int j = 0; j < n_w; ++j) { hab[2 * j] = c->robin.alpha[j]; hab[2 * j + 1] = c->robin.beta[j]; }
-    if (hab.size() > c->robin.cap) {
-      if (dev_alloc(&c->robin.ab, hab.size() * rs)) return PINN_EHIP;
-      c->robin.cap = hab.size();
-    }
+    HIPCHK(c->robin.ab.reserve_bytes(hab.size() * rs));
     if (upload_real(c, c->robin.ab, hab.data(), hab.size())) return PINN_EHIP;
   }
   if (is_adr(c) && c->kf.on && !c->kf.stale && n_f > 0) {           // the table, row i for collocation point 2 n_b + n_u + i
-    if (c->kf.K.size() > c->kf.cap) {
-      if (dev_alloc(&c->kf.dev, c->kf.K.size() * rs)) return PINN_EHIP;
-      c->kf.cap = c->kf.K.size();
-    }
+    HIPCHK(c->kf.dev.reserve_bytes(c->kf.K.size() * rs));
     if (upload_real(c, c->kf.dev, c->kf.K.data(), c->kf.K.size())) return PINN_EHIP;
   }
   if (c->lhs.on) { if (int rc = lhs_fill(c)) return rc; }
@@ -705,13 +677,10 @@ static int ensure_sets(pinn_ctx* c) {
   const size_t need_S = stash == STASH_NONE ? 16 : H * W * stash_pts * 4 * rs;
   const size_t need_Z = stash == STASH_NONE ? 16 : W * (size_t)c->chunk * 4 * rs;
   const size_t need_part = (size_t)path_rows(c) * c->R * rs;
-  if (need_S > c->cap_S) { if (dev_alloc(&c->S, need_S)) return PINN_EHIP; c->cap_S = need_S; }
-  if (need_Z > c->cap_Z) {
-    if (dev_alloc(&c->ZA, need_Z)) return PINN_EHIP;
-    if (dev_alloc(&c->ZB, need_Z)) return PINN_EHIP;
-    c->cap_Z = need_Z;
-  }
-  if (need_part > c->cap_part) { if (dev_alloc(&c->part, need_part)) return PINN_EHIP; c->cap_part = need_part; }
+  HIPCHK(c->S.reserve_bytes(need_S));
+  HIPCHK(c->ZA.reserve_bytes(need_Z));
+  HIPCHK(c->ZB.reserve_bytes(need_Z));
+  HIPCHK(c->part.reserve_bytes(need_part));
   c->sets_dirty = false;
   return 0;
 }
@@ -754,10 +723,7 @@ static LamLayout pw_layout(const pinn_ctx* c) {
 // start values: h holds L.doubles() doubles, the entries filled in; the header is written here.  Synchronous.
 static int lam_upload(pinn_ctx* c, LamStore& s, const LamLayout& L, std::vector<double>& h) {
   memcpy(h.data(), L.hdr, L.n_hdr * sizeof(double));
-  if (h.size() * 8 > s.cap) {
-    if (dev_alloc(&s.buf, h.size() * 8)) return PINN_EHIP;
-    s.cap = h.size() * 8;
-  }
+  HIPCHK(s.buf.reserve(h.size()));
   HIPCHK(hipMemcpyAsync(s.buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (int k = 0; k < LAM_CLASSES; ++k) { s.n[k] = L.n[k]; s.reset[k] = false; }
@@ -834,12 +800,12 @@ static int launch_reduce(pinn_ctx* c, int n_rows, const AdamFuse* af) {
     const unsigned int seq = c->xg.seq;
     const dim3 xgrid = xg_grid(c, c->R, ts.gscr ? ts.n_slots : 0);
     if (af)
-      hipLaunchKernelGGL((k_reduce_xgmi<real, true>), xgrid, dim3(RED_THREADS), 0, c->stream, (const real*)c->part,
+      hipLaunchKernelGGL((k_reduce_xgmi<real, true>), xgrid, dim3(RED_THREADS), 0, c->stream, c->part.as<real>(),
                          n_rows, c->R, c->gl, c->xg.peers, seq, XG_TIMEOUT_TICKS, c->xg.err, c->nd.n_theta, c->theta,
-                         (real*)c->theta_r, c->adam_m, c->adam_v, af->alpha, c->b1, c->b2, c->eps, af->loss3, c->nd,
+                         c->theta_r.as<real>(), c->adam_m, c->adam_v, af->alpha, c->b1, c->b2, c->eps, af->loss3, c->nd,
                          c->img, ts);
     else
-      hipLaunchKernelGGL((k_reduce_xgmi<real, false>), xgrid, dim3(RED_THREADS), 0, c->stream, (const real*)c->part,
+      hipLaunchKernelGGL((k_reduce_xgmi<real, false>), xgrid, dim3(RED_THREADS), 0, c->stream, c->part.as<real>(),
                          n_rows, c->R, c->gl, c->xg.peers, seq, XG_TIMEOUT_TICKS, c->xg.err, 0, (double*)nullptr,
                          (real*)nullptr, (double*)nullptr, (double*)nullptr, 0.0, 0.0, 0.0, 0.0, (double*)nullptr,
                          c->nd, (float*)nullptr, ts);
@@ -847,12 +813,12 @@ static int launch_reduce(pinn_ctx* c, int n_rows, const AdamFuse* af) {
     return 0;
   }
   if (af)
-    hipLaunchKernelGGL((k_reduce_adam<real>), rgrid, dim3(RED_THREADS), 0, c->stream, (const real*)c->part,
-                       n_rows, c->R, c->gl, c->nd.n_theta, c->theta, (real*)c->theta_r, c->adam_m,
+    hipLaunchKernelGGL((k_reduce_adam<real>), rgrid, dim3(RED_THREADS), 0, c->stream, c->part.as<real>(),
+                       n_rows, c->R, c->gl, c->nd.n_theta, c->theta, c->theta_r.as<real>(), c->adam_m,
                        c->adam_v, af->alpha, c->b1, c->b2, c->eps, af->loss3, c->nd, c->img, c->n_evals,
                        c->d_nonfinite, ts);
   else
-    hipLaunchKernelGGL((k_reduce_rows<real>), rgrid, dim3(RED_THREADS), 0, c->stream, (const real*)c->part,
+    hipLaunchKernelGGL((k_reduce_rows<real>), rgrid, dim3(RED_THREADS), 0, c->stream, c->part.as<real>(),
                        n_rows, c->R, c->gl, c->nd.n_theta, c->n_evals, c->d_nonfinite, ts);
   HIPCHK(hipGetLastError());
   return 0;
@@ -870,8 +836,8 @@ static int t16_launch_fwd(pinn_ctx* c, const void* xs, const void* ts, int n_pad
     HIPCHK(hipFuncSetAttribute((const void*)k_t16_fwd<real, NT, WLDS, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds));
   hipLaunchKernelGGL((k_t16_fwd<real, NT, WLDS, NWV>), dim3(t16_wgs(c, pts)), dim3(64 * NWV), lds, c->stream, c->nd,
-                     (const real*)c->theta_r, (const real*)xs, (const real*)ts, base, n_pad, chunk,
-                     pts / 16, lbx, lbt, sx, st, (vec4<real>*)c->S, (vec4<real>*)O);
+                     c->theta_r.as<real>(), (const real*)xs, (const real*)ts, base, n_pad, chunk,
+                     pts / 16, lbx, lbt, sx, st, c->S.as<vec4<real>>(), (vec4<real>*)O);
   return 0;
 }
 template <typename real, int NT, int PDE, bool WLDS>
@@ -887,9 +853,9 @@ static int t16_launch_bwd(pinn_ctx* c, int base, int pts, real lbx, real lbt, re
   const int rows_cap = t16_wgs(c, c->chunk);
   const int wgs = t16_wgs(c, pts) < rows_cap ? t16_wgs(c, pts) : rows_cap;
   hipLaunchKernelGGL((k_t16_bwd<real, NT, PDE, WLDS, NWV>), dim3(wgs), dim3(64 * NWV), lds, c->stream, c->nd, c->sd,
-                     (const real*)c->theta_r, (const real*)c->xs, (const real*)c->ts, (const real*)c->tgt, base,
-                     c->sd.n_pad, c->chunk, pts / 16, lbx, lbt, sx, st, (real)c->nu, (const vec4<real>*)c->S,
-                     (const vec4<real>*)c->O, (real*)c->part, c->R, accumulate);
+                     c->theta_r.as<real>(), c->xs.as<real>(), c->ts.as<real>(), c->tgt.as<real>(), base,
+                     c->sd.n_pad, c->chunk, pts / 16, lbx, lbt, sx, st, (real)c->nu, c->S.as<vec4<real>>(),
+                     c->O.as<vec4<real>>(), c->part.as<real>(), c->R, accumulate);
   return 0;
 }
 template <typename real>
@@ -910,8 +876,8 @@ static int forward_chunk(pinn_ctx* c, const void* xs, const void* ts, int n_pad,
   if (tile16_ok(c) && c->nd.width >= 24)
     return t16_fwd<real>(c, xs, ts, n_pad, chunk, O, base, pts, lbx, lbt, sx, st);
   constexpr int JT = sizeof(real) == 4 ? 20 : 10;
-  hipLaunchKernelGGL((k_forward<real, JT>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, (const real*)c->theta_r,
-                     (const real*)xs, (const real*)ts, base, n_pad, chunk, lbx, lbt, sx, st, (vec4<real>*)c->S,
+  hipLaunchKernelGGL((k_forward<real, JT>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, c->theta_r.as<real>(),
+                     (const real*)xs, (const real*)ts, base, n_pad, chunk, lbx, lbt, sx, st, c->S.as<vec4<real>>(),
                      (vec4<real>*)O);
   return 0;
 }
@@ -933,8 +899,8 @@ static int t16_fused_launch(pinn_ctx* c, const SetDesc& sd, int base, int pts, i
     HIPCHK(hipFuncSetAttribute((const void*)k_t16_fused<PDE, H>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                160 * 1024));
   hipLaunchKernelGGL((k_t16_fused<PDE, H>), dim3(wgs), dim3(512), t16_fused_lds(c->nd.width, H, c->nd.n_out), c->stream, c->nd, sd,
-                     (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts, (const double*)c->tgt, base,
-                     sd.n_pad, pts / 16, lbx, lbt, sx, st, (double)c->nu, (vec4<double>*)c->O, (double*)c->part, c->R,
+                     c->theta_r.as<double>(), c->xs.as<double>(), c->ts.as<double>(), c->tgt.as<double>(), base,
+                     sd.n_pad, pts / 16, lbx, lbt, sx, st, (double)c->nu, c->O.as<vec4<double>>(), c->part.as<double>(), c->R,
                      ci > 0 ? 1 : 0, c->t16_bsync, c->t16_bcount, n_bg, c->t16_gscr, c->t16_handover_ticks,
                      t16_deal(c->nd.width, c->t16_cost_full, c->t16_cost_strip));
   HIPCHK(hipGetLastError());
@@ -953,8 +919,8 @@ struct InMap {
 // overrides the weights, the rows, the member count and, with per-member sets, the points.
 static F20dLaunch fused20d_args(const pinn_ctx* c, hipEvent_t* ev4) {
   const InMap<double> m(c);
-  return F20dLaunch{c->nd, c->sd, (const double*)c->theta_r, (const double*)c->xs, (const double*)c->ts,
-                    (const double*)c->tgt, m.lbx, m.lbt, m.sx, m.st, (double*)c->part, c->R, c->n_wg, 1, c->row_index,
+  return F20dLaunch{c->nd, c->sd, c->theta_r.as<double>(), c->xs.as<double>(), c->ts.as<double>(),
+                    c->tgt.as<double>(), m.lbx, m.lbt, m.sx, m.st, c->part.as<double>(), c->R, c->n_wg, 1, c->row_index,
                     c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr};
 }
 
@@ -1006,13 +972,13 @@ static int launch_fused20m(pinn_ctx* c, hipEvent_t* ev4) {
     const InMap<float> m(c);
     hipEvent_t const e0 = ev4 ? ev4[0] : nullptr, e1 = ev4 ? ev4[1] : nullptr;
     if (c->nd.n_hidden == 8)
-      rc = fused20m_launch<PDE, 8>(c->nd, c->sd, (const float*)c->theta_r, c->img, (const float*)c->xs,
-                                   (const float*)c->ts, (const float*)c->tgt, m.lbx, m.lbt, m.sx, m.st, (float)c->nu,
-                                   (float*)c->part, c->R, c->n_wg, c->stream, c->stamps, e0, e1);
+      rc = fused20m_launch<PDE, 8>(c->nd, c->sd, c->theta_r.as<float>(), c->img, c->xs.as<float>(),
+                                   c->ts.as<float>(), c->tgt.as<float>(), m.lbx, m.lbt, m.sx, m.st, (float)c->nu,
+                                   c->part.as<float>(), c->R, c->n_wg, c->stream, c->stamps, e0, e1);
     else
-      rc = fused20m_launch_depth(PDE, c->nd, c->sd, (const float*)c->theta_r, c->img, (const float*)c->xs,
-                                 (const float*)c->ts, (const float*)c->tgt, m.lbx, m.lbt, m.sx, m.st, (float)c->nu,
-                                 (float*)c->part, c->R, c->n_wg, c->stream, c->stamps, e0, e1);
+      rc = fused20m_launch_depth(PDE, c->nd, c->sd, c->theta_r.as<float>(), c->img, c->xs.as<float>(),
+                                 c->ts.as<float>(), c->tgt.as<float>(), m.lbx, m.lbt, m.sx, m.st, (float)c->nu,
+                                 c->part.as<float>(), c->R, c->n_wg, c->stream, c->stamps, e0, e1);
   }
   if (rc) return fail(PINN_EHIP, "fused20m launch failed: %s", hipGetErrorString((hipError_t)rc));
   return 0;
@@ -1024,9 +990,9 @@ static int launch_fused20(pinn_ctx* c, hipEvent_t* ev4) {
   int rc = hipErrorInvalidValue;
   if constexpr (!pde_is_adr(PDE)) {
     const InMap<real> m(c);
-    rc = fused20_launch<real, PDE>(c->nd, c->sd, (const real*)c->theta_r, (const real*)c->xs, (const real*)c->ts,
-                                   (const real*)c->tgt, m.lbx, m.lbt, m.sx, m.st, (real)c->nu, (vec4<real>*)c->S,
-                                   (real*)c->part, c->R, c->stream, c->stamps, ev4 ? ev4[0] : nullptr,
+    rc = fused20_launch<real, PDE>(c->nd, c->sd, c->theta_r.as<real>(), c->xs.as<real>(), c->ts.as<real>(),
+                                   c->tgt.as<real>(), m.lbx, m.lbt, m.sx, m.st, (real)c->nu, c->S.as<vec4<real>>(),
+                                   c->part.as<real>(), c->R, c->stream, c->stamps, ev4 ? ev4[0] : nullptr,
                                    ev4 ? ev4[1] : nullptr);
   }
   if (rc) return fail(PINN_EHIP, "fused20 launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -1051,12 +1017,12 @@ static int chunk_t16_fused(pinn_ctx* c, const InMap<real>& m, hipEvent_t ev1, in
             "k_t16_fused launch plan: %d workgroups for %d groups (rows %d, chunk %d)", wgs, pts / 16, rows_cap, ci);
     if (n_bg > wgs || (n_bg > 0 && c->t16_prepass)) {
       const size_t need_S = (size_t)c->nd.n_hidden * c->nd.width * (size_t)c->chunk * 4 * sizeof(double);   // (k_t16_fwd stashes)
-      if (need_S > c->cap_S) { if (dev_alloc(&c->S, need_S)) return PINN_EHIP; c->cap_S = need_S; }
+      HIPCHK(c->S.reserve_bytes(need_S));
       if (int rc = t16_fwd<real>(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O, 0, 16 * n_bg < pts ? 16 * n_bg : pts, m.lbx, m.lbt, m.sx, m.st)) return rc;
       n_bg = 0;
     }
     if (!c->t16_bsync) {
-      if (dev_alloc(&c->t16_bsync, 64)) return PINN_EHIP;
+      HIPCHK(c->t16_bsync.reserve(16));
       HIPCHK(hipMemsetAsync(c->t16_bsync, 0, 64, c->stream));
       c->t16_bcount = 0;
     }
@@ -1064,10 +1030,7 @@ static int chunk_t16_fused(pinn_ctx* c, const InMap<real>& m, hipEvent_t ev1, in
     {  // tile-major scratch of the hidden-layer weight gradients: one block per workgroup (kernels_tile16f.h)
       const size_t ntl = ((size_t)c->nd.width + 15) / 16;
       const size_t need = (size_t)rows_cap * (c->nd.n_hidden - 1) * ntl * ntl * 256 * sizeof(double);
-      if (need > c->t16_gscr_bytes) {
-        if (dev_alloc(&c->t16_gscr, need)) return PINN_EHIP;
-        c->t16_gscr_bytes = need;
-      }
+      HIPCHK(c->t16_gscr.reserve_bytes(need));
     }
     if (ev1) HIPCHK(hipEventRecord(ev1, c->stream));
     switch (c->nd.n_hidden) {            // the stash is a register array: the depth is a template parameter
@@ -1091,15 +1054,15 @@ static int chunk_fwd(pinn_ctx* c, const InMap<real>& m, int base, int pts) {
         HIPCHK(hipFuncSetAttribute((const void*)k_wide_fwd<100, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)wide_lds_bytes<100>()));
       hipLaunchKernelGGL((k_wide_fwd<100, 2>), dim3(wide_wgs(c, pts)), dim3(256), wide_lds_bytes<100>(), c->stream, c->nd,
-                         (const float*)c->theta_r, c->img, (const float*)c->xs, (const float*)c->ts, base, n_pad,
-                         c->chunk, pts / 16, m.lbx, m.lbt, m.sx, m.st, (vec4<float>*)c->S, (vec4<float>*)c->O);
+                         c->theta_r.as<float>(), c->img, c->xs.as<float>(), c->ts.as<float>(), base, n_pad,
+                         c->chunk, pts / 16, m.lbx, m.lbt, m.sx, m.st, c->S.as<vec4<float>>(), c->O.as<vec4<float>>());
       return 0;
     }
   }
   constexpr int JT = sizeof(real) == 4 ? 20 : 10;
-  hipLaunchKernelGGL((k_forward<real, JT>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, (const real*)c->theta_r,
-                     (const real*)c->xs, (const real*)c->ts, base, n_pad, c->chunk, m.lbx, m.lbt, m.sx, m.st,
-                     (vec4<real>*)c->S, (vec4<real>*)c->O);
+  hipLaunchKernelGGL((k_forward<real, JT>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, c->theta_r.as<real>(),
+                     c->xs.as<real>(), c->ts.as<real>(), base, n_pad, c->chunk, m.lbx, m.lbt, m.sx, m.st,
+                     c->S.as<vec4<real>>(), c->O.as<vec4<real>>());
   return 0;
 }
 
@@ -1117,17 +1080,17 @@ static int chunk_bwd(pinn_ctx* c, const InMap<real>& m, int base, int pts, int a
         HIPCHK(hipFuncSetAttribute((const void*)k_wide_bwd<100, 2, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)wide_lds_bytes<100>()));
       hipLaunchKernelGGL((k_wide_bwd<100, 2, 2, 4>), dim3(wide_wgs(c, pts)), dim3(256), wide_lds_bytes<100>(), c->stream,
-                         c->nd, sd, (const float*)c->theta_r, c->img, (const float*)c->xs, (const float*)c->ts,
-                         (const float*)c->tgt, base, sd.n_pad, c->chunk, pts / 16, m.lbx, m.lbt, m.sx, m.st, (float)c->nu,
-                         (const vec4<float>*)c->S, (const vec4<float>*)c->O, (float*)c->part, c->R, accumulate);
+                         c->nd, sd, c->theta_r.as<float>(), c->img, c->xs.as<float>(), c->ts.as<float>(),
+                         c->tgt.as<float>(), base, sd.n_pad, c->chunk, pts / 16, m.lbx, m.lbt, m.sx, m.st, (float)c->nu,
+                         c->S.as<vec4<float>>(), c->O.as<vec4<float>>(), c->part.as<float>(), c->R, accumulate);
       return 0;
     }
   }
   constexpr int KT = sizeof(real) == 4 ? 10 : 5;
   hipLaunchKernelGGL((k_backward<real, PDE, KT>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, sd,
-                     (const real*)c->theta_r, (const real*)c->xs, (const real*)c->ts, (const real*)c->tgt, base, sd.n_pad,
-                     c->chunk, m.lbx, m.lbt, m.sx, m.st, pde_coef<real, PDE>(c), (const vec4<real>*)c->S,
-                     (const vec4<real>*)c->O, (vec4<real>*)c->ZA, (vec4<real>*)c->ZB, (real*)c->part, c->R, accumulate);
+                     c->theta_r.as<real>(), c->xs.as<real>(), c->ts.as<real>(), c->tgt.as<real>(), base, sd.n_pad,
+                     c->chunk, m.lbx, m.lbt, m.sx, m.st, pde_coef<real, PDE>(c), c->S.as<vec4<real>>(),
+                     c->O.as<vec4<real>>(), c->ZA.as<vec4<real>>(), c->ZB.as<vec4<real>>(), c->part.as<real>(), c->R, accumulate);
   return 0;
 }
 
@@ -1183,8 +1146,8 @@ static int disc_upload_tables(pinn_ctx* c, int ldo) {
   const size_t rs = real_size(c);
   const int NO = c->nd.n_out;
   for (int s = 0; s < 2; ++s) {
-    if (c->d_M[s]) { (void)hipFree(c->d_M[s]); c->d_M[s] = nullptr; }
-    if (c->d_MT[s]) { (void)hipFree(c->d_MT[s]); c->d_MT[s] = nullptr; }
+    c->d_M[s].reset();                       // freed every time: an empty buffer tells the kernels that the set has no table
+    c->d_MT[s].reset();
     const pinn_ctx::DiscSet& ds = c->dset[s];
     if (!ds.has_M || ds.x.empty()) continue;
     std::vector<double> Mp((size_t)ldo * ldo, 0.0), MTp((size_t)ldo * ldo, 0.0);
@@ -1194,20 +1157,22 @@ static int disc_upload_tables(pinn_ctx* c, int ldo) {
         Mp[(size_t)j * ldo + k] = v;
         MTp[(size_t)k * ldo + j] = v;
       }
-    if (dev_alloc(&c->d_M[s], Mp.size() * rs) || dev_alloc(&c->d_MT[s], Mp.size() * rs)) return PINN_EHIP;
+    HIPCHK(c->d_M[s].reserve_bytes(Mp.size() * rs));
+    HIPCHK(c->d_MT[s].reserve_bytes(Mp.size() * rs));
     if (upload_real(c, c->d_M[s], Mp.data(), Mp.size()) || upload_real(c, c->d_MT[s], MTp.data(), MTp.size()))
       return PINN_EHIP;
   }
   return 0;
 }
 
-static int disc_alloc_scratch(pinn_ctx* c, const DiscDesc& dd, void** Ast, void** A3, void** U3, void** Nn,
-                              void** Rb) {
+static int disc_alloc_scratch(pinn_ctx* c, const DiscDesc& dd, DevBuf<void>* Ast, DevBuf<void>* A3, DevBuf<void>& U3,
+                              DevBuf<void>& Nn, DevBuf<void>& Rb) {
   const size_t rs = real_size(c), H = c->nd.n_hidden;
-  if (Ast && dev_alloc(Ast, H * 3 * (size_t)dd.n_pad * dd.wp * rs)) return PINN_EHIP;
-  if (A3 && dev_alloc(A3, 3 * (size_t)dd.n_pad * dd.wp * rs)) return PINN_EHIP;
-  if (dev_alloc(U3, 3 * (size_t)dd.n_pad * dd.ldo * rs) || dev_alloc(Nn, (size_t)dd.n_pad * dd.ldo * rs) ||
-      dev_alloc(Rb, (size_t)dd.n_pad * dd.ldo * rs)) return PINN_EHIP;
+  if (Ast) HIPCHK(Ast->reserve_bytes(H * 3 * (size_t)dd.n_pad * dd.wp * rs));
+  if (A3) HIPCHK(A3->reserve_bytes(3 * (size_t)dd.n_pad * dd.wp * rs));
+  HIPCHK(U3.reserve_bytes(3 * (size_t)dd.n_pad * dd.ldo * rs));
+  HIPCHK(Nn.reserve_bytes((size_t)dd.n_pad * dd.ldo * rs));
+  HIPCHK(Rb.reserve_bytes((size_t)dd.n_pad * dd.ldo * rs));
   return 0;
 }
 
@@ -1236,21 +1201,21 @@ static int disc_ensure(pinn_ctx* c) {
     }
   }
   const size_t rs = real_size(c);
-  if (dev_alloc(&c->xs, dd.n_pad * rs) || dev_alloc(&c->tgt, dd.n_pad * rs) ||
-      dev_alloc(&c->d_ginfo, G * sizeof(int))) return PINN_EHIP;
-  c->cap_pts = 0;
+  HIPCHK(c->xs.reserve_bytes(dd.n_pad * rs));
+  HIPCHK(c->tgt.reserve_bytes(dd.n_pad * rs));
+  HIPCHK(c->d_ginfo.reserve(G));
   if (upload_real(c, c->xs, hx.data(), dd.n_pad) || upload_real(c, c->tgt, ht.data(), dd.n_pad)) return PINN_EHIP;
   HIPCHK(hipMemcpy(c->d_ginfo, gi.data(), G * sizeof(int), hipMemcpyHostToDevice));
   if (disc_upload_tables(c, dd.ldo)) return PINN_EHIP;
-  if (disc_alloc_scratch(c, dd, &c->d_Ast, &c->d_A3, &c->d_U3, &c->d_Nn, &c->d_R)) return PINN_EHIP;
-  if (dev_alloc(&c->d_dAp, (size_t)dd.n_chunks * 3 * dd.n_pad * dd.wp * rs) ||
-      dev_alloc(&c->d_lossp, (size_t)G * dd.n_chunks * rs) ||
-      dev_alloc(&c->d_lamp, (size_t)G * dd.n_chunks * 2 * rs)) return PINN_EHIP;
+  if (disc_alloc_scratch(c, dd, &c->d_Ast, &c->d_A3, c->d_U3, c->d_Nn, c->d_R)) return PINN_EHIP;
+  HIPCHK(c->d_dAp.reserve_bytes((size_t)dd.n_chunks * 3 * dd.n_pad * dd.wp * rs));
+  HIPCHK(c->d_lossp.reserve_bytes((size_t)G * dd.n_chunks * rs));
+  HIPCHK(c->d_lamp.reserve_bytes((size_t)G * dd.n_chunks * 2 * rs));
   // cleared in stream order: the context's stream is non-blocking, so a hipMemset on the null stream (asynchronous to the
   // host for device memory) is not ordered before the first evaluation's kernels and can wipe rows they have written
   HIPCHK(hipMemsetAsync(c->d_lamp, 0, (size_t)G * dd.n_chunks * 2 * rs, c->stream));
   const size_t need_part = (size_t)G * c->R * rs;
-  if (need_part > c->cap_part) { if (dev_alloc(&c->part, need_part)) return PINN_EHIP; c->cap_part = need_part; }
+  HIPCHK(c->part.reserve_bytes(need_part));
   HIPCHK(hipMemsetAsync(c->part, 0, need_part, c->stream));
   c->dd = dd;
   c->n_rows = G;
@@ -1278,22 +1243,22 @@ static int disc_eval(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   const real c1 = real(1), c2 = (real)c->nu;
   if (int rc = disc_set_lds<real, NT>()) return rc;
   const dim3 grid(dd.n_groups, dd.n_chunks), block(256);
-  const real* th = (const real*)c->theta_r;
+  const real* th = c->theta_r.as<real>();
   if (ev4) HIPCHK(hipEventRecord(ev4[0], c->stream));
   hipLaunchKernelGGL((k_disc_fwd<real, NT>), grid, block, disc_fwd_lds<NT>(sizeof(real)), c->stream, c->nd, dd, th,
-                     (const real*)c->xs, lbx, sx, c1, c2, (real*)c->d_Ast, (real*)c->d_A3, (real*)c->d_U3,
-                     (real*)c->d_Nn, 1);
+                     c->xs.as<real>(), lbx, sx, c1, c2, c->d_Ast.as<real>(), c->d_A3.as<real>(), c->d_U3.as<real>(),
+                     c->d_Nn.as<real>(), 1);
   hipLaunchKernelGGL((k_disc_irk<real>), grid, block, 0, c->stream, dd, c->nd.n_out, c->d_ginfo,
-                     (const real*)c->d_MT[0], (const real*)c->d_MT[1], (const real*)c->d_Nn,
-                     (const real*)c->d_U3, (const real*)c->tgt, (real*)c->d_R, (real*)c->d_lossp, 0);
+                     c->d_MT[0].as<real>(), c->d_MT[1].as<real>(), c->d_Nn.as<real>(),
+                     c->d_U3.as<real>(), c->tgt.as<real>(), c->d_R.as<real>(), c->d_lossp.as<real>(), 0);
   if (ev4) HIPCHK(hipEventRecord(ev4[1], c->stream));
   hipLaunchKernelGGL((k_disc_bwd_out<real, NT>), grid, block, disc_out_lds<NT>(sizeof(real)), c->stream, c->nd, dd,
-                     th, c->d_ginfo, (const real*)c->d_M[0], (const real*)c->d_M[1], (const real*)c->d_R,
-                     (const real*)c->d_U3, (const real*)c->d_A3, c1, c2, (real*)c->part, c->R, (real*)c->d_dAp,
-                     (real*)c->d_lamp);
+                     th, c->d_ginfo, c->d_M[0].as<real>(), c->d_M[1].as<real>(), c->d_R.as<real>(),
+                     c->d_U3.as<real>(), c->d_A3.as<real>(), c1, c2, c->part.as<real>(), c->R, c->d_dAp.as<real>(),
+                     c->d_lamp.as<real>());
   hipLaunchKernelGGL((k_disc_bwd_hidden<real, NT>), dim3(dd.n_groups), block, disc_hid_lds<NT>(sizeof(real)),
-                     c->stream, c->nd, dd, th, c->d_ginfo, (const real*)c->xs, lbx, sx, (const real*)c->d_Ast,
-                     (const real*)c->d_dAp, (const real*)c->d_lossp, (const real*)c->d_lamp, (real*)c->part, c->R);
+                     c->stream, c->nd, dd, th, c->d_ginfo, c->xs.as<real>(), lbx, sx, c->d_Ast.as<real>(),
+                     c->d_dAp.as<real>(), c->d_lossp.as<real>(), c->d_lamp.as<real>(), c->part.as<real>(), c->R);
   if (ev4) HIPCHK(hipEventRecord(ev4[2], c->stream));
   HIPCHK(hipGetLastError());
   return launch_reduce<real>(c, dd.n_groups, af);
@@ -1335,38 +1300,32 @@ static int disc_predict_impl(pinn_ctx* c, int mode, int set, const double* x, in
   std::vector<double> hx(dd.n_pad, c->lb[0]);
   for (int64_t i = 0; i < n; ++i) hx[i] = x[i];
   std::vector<int> gi(G, disc_ginfo(set, 16));
-  void *xe = nullptr, *U3 = nullptr, *Nn = nullptr, *Rb = nullptr;
-  int* ge = nullptr;
-  int rc = 0;
+  DevBuf<void> xe, U3, Nn, Rb;                   // the call's own: freed on every return
+  DevBuf<int> ge;
   const size_t rs = sizeof(real);
-  if (dev_alloc(&xe, dd.n_pad * rs) || dev_alloc(&ge, G * sizeof(int)) ||
-      disc_alloc_scratch(c, dd, nullptr, nullptr, &U3, &Nn, &Rb)) rc = PINN_EHIP;
-  if (!rc && upload_real(c, xe, hx.data(), dd.n_pad)) rc = PINN_EHIP;
-  if (!rc && hipMemcpy(ge, gi.data(), G * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc = PINN_EHIP;
-  if (!rc) {
-    const real lbx = (real)c->lb[0], sx = (real)(2.0 / (c->ub[0] - c->lb[0]));
-    const size_t lds_f = disc_fwd_lds<NT>(rs);
-    rc = disc_set_lds<real, NT>();
-    if (!rc) {
-      const dim3 grid(dd.n_groups, dd.n_chunks), block(256);
-      hipLaunchKernelGGL((k_disc_fwd<real, NT>), grid, block, lds_f, c->stream, c->nd, dd, (const real*)c->theta_r,
-                         (const real*)xe, lbx, sx, real(1), (real)c->nu, (real*)nullptr, (real*)nullptr, (real*)U3,
-                         (real*)Nn, 0);
-      if (mode == 1)
-        hipLaunchKernelGGL((k_disc_irk<real>), grid, block, 0, c->stream, dd, NO, ge, (const real*)c->d_MT[0],
-                           (const real*)c->d_MT[1], (const real*)Nn, (const real*)U3, (const real*)nullptr,
-                           (real*)Rb, (real*)nullptr, 1);
-      std::vector<real> ho((size_t)dd.n_pad * dd.ldo);
-      if (hipMemcpyAsync(ho.data(), mode == 1 ? Rb : U3, ho.size() * rs, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-          hipStreamSynchronize(c->stream) != hipSuccess)
-        rc = fail(PINN_EHIP, "discrete-time predict failed: %s", hipGetErrorString(hipGetLastError()));
-      else
-        for (int64_t i = 0; i < n; ++i)
-          for (int j = 0; j < NO; ++j) out[(size_t)i * NO + j] = (double)ho[(size_t)i * dd.ldo + j];
-    }
-  }
-  for (void* ptr : {xe, U3, Nn, Rb, (void*)ge}) if (ptr) (void)hipFree(ptr);
-  return rc;
+  HIPCHK(xe.reserve_bytes(dd.n_pad * rs));
+  HIPCHK(ge.reserve(G));
+  if (disc_alloc_scratch(c, dd, nullptr, nullptr, U3, Nn, Rb)) return PINN_EHIP;
+  if (upload_real(c, xe, hx.data(), dd.n_pad)) return PINN_EHIP;
+  if (hipMemcpy(ge, gi.data(), G * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return PINN_EHIP;
+  const real lbx = (real)c->lb[0], sx = (real)(2.0 / (c->ub[0] - c->lb[0]));
+  const size_t lds_f = disc_fwd_lds<NT>(rs);
+  if (int rc = disc_set_lds<real, NT>()) return rc;
+  const dim3 grid(dd.n_groups, dd.n_chunks), block(256);
+  hipLaunchKernelGGL((k_disc_fwd<real, NT>), grid, block, lds_f, c->stream, c->nd, dd, c->theta_r.as<real>(),
+                     xe.as<real>(), lbx, sx, real(1), (real)c->nu, (real*)nullptr, (real*)nullptr, U3.as<real>(),
+                     Nn.as<real>(), 0);
+  if (mode == 1)
+    hipLaunchKernelGGL((k_disc_irk<real>), grid, block, 0, c->stream, dd, NO, ge.get(), c->d_MT[0].as<real>(),
+                       c->d_MT[1].as<real>(), Nn.as<real>(), U3.as<real>(), (const real*)nullptr, Rb.as<real>(),
+                       (real*)nullptr, 1);
+  std::vector<real> ho((size_t)dd.n_pad * dd.ldo);
+  if (hipMemcpyAsync(ho.data(), mode == 1 ? Rb.get() : U3.get(), ho.size() * rs, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return fail(PINN_EHIP, "discrete-time predict failed: %s", hipGetErrorString(hipGetLastError()));
+  for (int64_t i = 0; i < n; ++i)
+    for (int j = 0; j < NO; ++j) out[(size_t)i * NO + j] = (double)ho[(size_t)i * dd.ldo + j];
+  return 0;
 }
 
 static int disc_predict_any(pinn_ctx* c, int mode, int set, const double* x, int64_t n, double* out) {
@@ -1382,7 +1341,7 @@ static void xg_release(pinn_ctx* c) {
   for (int r = 0; r < XG_MAX_RANKS; ++r)
     if (c->xg.opened[r]) { (void)hipIpcCloseMemHandle(c->xg.opened[r]); c->xg.opened[r] = nullptr; }
   if (c->xg.box) { (void)hipFree(c->xg.box); c->xg.box = nullptr; }
-  if (c->xg.err) { (void)hipFree(c->xg.err); c->xg.err = nullptr; }
+  c->xg.err.reset();
   c->xg.attached = c->xg.on = false;
   c->xg.seq = 0;
   c->xg.sharing = 1;
@@ -1434,18 +1393,18 @@ static int xg_check(pinn_ctx* c) {
 static int xg_self_test(pinn_ctx* c, int* ok) {
   *ok = 0;
   const int R = c->R, n = c->xg.peers.n_ranks, me = c->xg.peers.rank;
-  double *vec = nullptr, *out = nullptr;
-  if (dev_alloc(&vec, (size_t)R * 8) || dev_alloc(&out, (size_t)R * 8)) return PINN_EHIP;
+  DevBuf<double> vec, out;
+  HIPCHK(vec.reserve(R));
+  HIPCHK(out.reserve(R));
   std::vector<double> h(R), got(R);
   bool good = true;
-  double* const gl_saved = c->gl;
   for (int round = 0; round < 6 && good; ++round) {
     for (int i = 0; i < R; ++i) h[i] = (double)((me + 1) * 1000 + (i % 97) + round);
     HIPCHK(hipMemcpyAsync(vec, h.data(), (size_t)R * 8, hipMemcpyHostToDevice, c->stream));
     if (++c->xg.seq == 0) c->xg.seq = 2;
     const unsigned int seq = c->xg.seq;
     hipLaunchKernelGGL((k_reduce_xgmi<double, false>), xg_grid(c, R), dim3(RED_THREADS), 0,
-                       c->stream, (const double*)vec, 1, R, out, c->xg.peers, seq, XG_TEST_TIMEOUT_TICKS, c->xg.err, 0,
+                       c->stream, (const double*)vec, 1, R, out.get(), c->xg.peers, seq, XG_TEST_TIMEOUT_TICKS, c->xg.err.get(), 0,
                        (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, 0.0, 0.0, 0.0, 0.0,
                        (double*)nullptr, c->nd, (float*)nullptr);
     HIPCHK(hipGetLastError());
@@ -1459,8 +1418,6 @@ static int xg_self_test(pinn_ctx* c, int* ok) {
       if (got[i] != want) good = false;
     }
   }
-  (void)gl_saved;
-  (void)hipFree(vec); (void)hipFree(out);
   if (!good) HIPCHK(hipMemsetAsync(c->xg.err, 0, sizeof(int), c->stream));
   *ok = good ? 1 : 0;
   return 0;
@@ -1471,7 +1428,7 @@ static int cast_weights(pinn_ctx* c) {
   by_real(c, [&](auto r) {
     using real = decltype(r);
     hipLaunchKernelGGL((k_cast_weights<real>), dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->theta,
-                       (real*)c->theta_r, c->nd, c->img);
+                       c->theta_r.as<real>(), c->nd, c->img);
   });
   HIPCHK(hipGetLastError());
   return 0;
@@ -1486,11 +1443,9 @@ static int eval_points(pinn_ctx* c, const double* X, int64_t n, int* n_pad_out) 
   const int n_pad = (int)((n + 63) / 64 * 64);
   *n_pad_out = n_pad;
   if ((size_t)n * 2 == c->ev_X.size() && c->ev_n_pad == n_pad && memcmp(c->ev_X.data(), X, (size_t)n * 16) == 0) return 0;
-  if ((size_t)n_pad > c->cap_eval) {
-    if (dev_alloc(&c->xe, n_pad * rs) || dev_alloc(&c->te, n_pad * rs) ||
-        dev_alloc(&c->Oe, (size_t)NO * n_pad * 4 * rs)) return PINN_EHIP;
-    c->cap_eval = n_pad;
-  }
+  HIPCHK(c->xe.reserve_bytes(n_pad * rs));
+  HIPCHK(c->te.reserve_bytes(n_pad * rs));
+  HIPCHK(c->Oe.reserve_bytes((size_t)NO * n_pad * 4 * rs));
   c->ev_X.clear();
   std::vector<double> hx(n_pad, c->lb[0]), ht(n_pad, c->lb[1]);
   for (int64_t i = 0; i < n; ++i) { hx[i] = X[2 * i]; ht[i] = X[2 * i + 1]; }
@@ -1509,13 +1464,13 @@ static int predict20_launch(pinn_ctx* c, const void* xs, const void* ts, int n_p
   if (c->dtype == PINN_F64) {
     const size_t lds = predict20_lds_bytes(c->nd, 8);
     const int wg = n_tiles < 4 * c->n_cu ? n_tiles : 4 * c->n_cu;
-    hipLaunchKernelGGL((k_fwd20d<NCH>), dim3(wg), dim3(256), lds, c->stream, c->nd, (const double*)c->theta_r,
+    hipLaunchKernelGGL((k_fwd20d<NCH>), dim3(wg), dim3(256), lds, c->stream, c->nd, c->theta_r.as<double>(),
                        (const double*)xs, (const double*)ts, n_tiles, c->lb[0], c->lb[1], sx, st,
                        (vec4<double>*)O4, out1);
   } else {
     const size_t lds = predict20_lds_bytes(c->nd, 4);
     const int wg = n_tiles < 8 * c->n_cu ? n_tiles : 8 * c->n_cu;
-    hipLaunchKernelGGL((k_fwd20f<NCH>), dim3(wg), dim3(64), lds, c->stream, c->nd, (const float*)c->theta_r,
+    hipLaunchKernelGGL((k_fwd20f<NCH>), dim3(wg), dim3(64), lds, c->stream, c->nd, c->theta_r.as<float>(),
                        (const float*)xs, (const float*)ts, n_tiles, (float)c->lb[0], (float)c->lb[1], (float)sx,
                        (float)st, (vec4<float>*)O4, out1);
   }
@@ -1527,7 +1482,7 @@ static int predict20_launch(pinn_ctx* c, const void* xs, const void* ts, int n_p
 static int forward_taylor(pinn_ctx* c, const void* xs, const void* ts, int n_pad, int chunk, void* O) {
   if (predict20_ok(c->nd) && !is_disc(c)) return predict20_launch<4>(c, xs, ts, n_pad, O, nullptr);
   const size_t need_S = (size_t)c->nd.n_hidden * c->nd.width * (size_t)chunk * 4 * real_size(c);
-  if (need_S > c->cap_S) { if (dev_alloc(&c->S, need_S)) return PINN_EHIP; c->cap_S = need_S; }
+  HIPCHK(c->S.reserve_bytes(need_S));
   for (int base = 0; base < n_pad; base += chunk) {
     const int pts = (n_pad - base < chunk) ? n_pad - base : chunk;
     const int rc = by_real(c, [&](auto r) { return forward_chunk<decltype(r)>(c, xs, ts, n_pad, chunk, O, base, pts); });
@@ -1540,17 +1495,14 @@ static int forward_taylor(pinn_ctx* c, const void* xs, const void* ts, int n_pad
 // network outputs at the current evaluation points -> c->pred ([n][n_out] float64, device)
 static int predict_values(pinn_ctx* c, int64_t n, int n_pad) {
   const int NO = c->nd.n_out;
-  if ((size_t)n_pad * NO > c->cap_pred) {
-    if (dev_alloc(&c->pred, (size_t)n_pad * NO * 8)) return PINN_EHIP;
-    c->cap_pred = (size_t)n_pad * NO;
-  }
+  HIPCHK(c->pred.reserve((size_t)n_pad * NO));
   if (predict20_ok(c->nd) && !is_disc(c)) return predict20_launch<1>(c, c->xe, c->te, n_pad, nullptr, c->pred);
   const int chunk = n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS;
   if (int rc = forward_taylor(c, c->xe, c->te, n_pad, chunk, c->Oe)) return rc;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   by_real(c, [&](auto r) {
     using real = decltype(r);
-    hipLaunchKernelGGL((k_pick_values<real>), grid, block, 0, c->stream, (const vec4<real>*)c->Oe, (int)n, n_pad, NO,
+    hipLaunchKernelGGL((k_pick_values<real>), grid, block, 0, c->stream, c->Oe.as<vec4<real>>(), (int)n, n_pad, NO,
                        c->pred);
   });
   HIPCHK(hipGetLastError());
@@ -1572,7 +1524,7 @@ static int launch_residual(pinn_ctx* c, Where w, const void* O, int first, int c
         if (w == AT_FOREIGN) coef.src = nullptr;
       }
       hipLaunchKernelGGL((k_residual<real, PDE>), grid, block, 0, c->stream, first, count, n_pad, (const vec4<real>*)O,
-                         (const real*)c->theta_r, c->nd.n_net, coef, dst, c->nd.n_out);
+                         c->theta_r.as<real>(), c->nd.n_net, coef, dst, c->nd.n_out);
       return 0;
     }
   });
@@ -1586,21 +1538,23 @@ static int launch_residual(pinn_ctx* c, Where w, const void* O, int first, int c
 // ------------------------------------------------------------------------------------------
 // the buffers of pinn_rad_collocation: grown only (a grow synchronises; a repeat at the same sizes only enqueues)
 static int rad_alloc(pinn_ctx* c, int64_t count, int64_t M) {
-  if ((size_t)count > c->rad.cap) {
-    if (dev_alloc(&c->rad.cx, (size_t)count * 8) || dev_alloc(&c->rad.ct, (size_t)count * 8)) return PINN_EHIP;
-    c->rad.cap = (size_t)count;
+  if (count > 0) {                               // (an empty draw allocates nothing)
+    HIPCHK(c->rad.cx.reserve((size_t)count));
+    HIPCHK(c->rad.ct.reserve((size_t)count));
   }
-  if (!c->rad.tot && dev_alloc(&c->rad.tot, sizeof(RadTotals))) return PINN_EHIP;
+  HIPCHK(c->rad.tot.reserve(1));
   const size_t n_pad = (size_t)((M + 63) / 64 * 64), rs = real_size(c), NO = (size_t)c->nd.n_out;
-  if (n_pad > c->rad.cap_pool) {
-    const size_t nb = (n_pad + RAD_BLOCK - 1) / RAD_BLOCK;
-    if (dev_alloc(&c->rad.px, n_pad * rs) || dev_alloc(&c->rad.pt, n_pad * rs) ||
-        dev_alloc(&c->rad.O, NO * n_pad * 4 * rs) || dev_alloc(&c->rad.f, NO * n_pad * 8) ||
-        dev_alloc(&c->rad.w, n_pad * 8) || dev_alloc(&c->rad.bsum, nb * 8)) return PINN_EHIP;
-    // pad points of the pool: finite, inert, never drawn
+  const size_t nb = (n_pad + RAD_BLOCK - 1) / RAD_BLOCK;
+  const bool grown = n_pad * rs > c->rad.px.capacity_bytes() || n_pad * rs > c->rad.pt.capacity_bytes();
+  HIPCHK(c->rad.px.reserve_bytes(n_pad * rs));
+  HIPCHK(c->rad.pt.reserve_bytes(n_pad * rs));
+  HIPCHK(c->rad.O.reserve_bytes(NO * n_pad * 4 * rs));
+  HIPCHK(c->rad.f.reserve(NO * n_pad));
+  HIPCHK(c->rad.w.reserve(n_pad));
+  HIPCHK(c->rad.bsum.reserve(nb));
+  if (grown) {                                   // pad points of a new pool: finite, inert, never drawn
     HIPCHK(hipMemsetAsync(c->rad.px, 0, n_pad * rs, c->stream));
     HIPCHK(hipMemsetAsync(c->rad.pt, 0, n_pad * rs, c->stream));
-    c->rad.cap_pool = n_pad;
   }
   return 0;
 }
@@ -1618,7 +1572,7 @@ static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) 
   // 1. the pool: points [0, M) of the M-point design, in the compute dtype (k_lhs_fill, as pinn_lhs_collocation draws it)
   by_real(c, [&](auto r) {
     using real = decltype(r);
-    hipLaunchKernelGGL((k_lhs_fill<real>), grid_m, block, 0, c->stream, (real*)c->rad.px, (real*)c->rad.pt, M,
+    hipLaunchKernelGGL((k_lhs_fill<real>), grid_m, block, 0, c->stream, c->rad.px.as<real>(), c->rad.pt.as<real>(), M,
                        (uint64_t)0, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
                        c->ub[1] - c->lb[1]);
   });
@@ -1638,10 +1592,10 @@ static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) 
   const dim3 grid_s((unsigned)((cnt + 255) / 256)), block_s(256);
   by_real(c, [&](auto r) {
     using real = decltype(r);
-    hipLaunchKernelGGL((k_rad_select<real>), grid_s, block_s, 0, c->stream, (const real*)c->rad.px,
-                       (const real*)c->rad.pt, (const unsigned long long*)c->rad.w,
+    hipLaunchKernelGGL((k_rad_select<real>), grid_s, block_s, 0, c->stream, c->rad.px.as<real>(),
+                       c->rad.pt.as<real>(), (const unsigned long long*)c->rad.w,
                        (const unsigned long long*)c->rad.bsum, (const RadTotals*)c->rad.tot, M, (uint64_t)c->rad.first,
-                       cnt, lo, hi, (real*)c->xs + off, (real*)c->ts + off, c->rad.cx, c->rad.ct);
+                       cnt, lo, hi, c->xs.as<real>() + off, c->ts.as<real>() + off, c->rad.cx, c->rad.ct);
   });
   HIPCHK(hipGetLastError());
   return 0;
@@ -1774,6 +1728,80 @@ static int adr_ide_write_tail(pinn_ctx* c, const double* p) {
   return 0;
 }
 
+// pinn_create behind its checks: the stream, the environment's knobs, the buffers every context has and the kernel path.
+// pinn_create destroys the context on any failure, so every return here is plain
+static int ctx_device_init(pinn_ctx* c) {
+  NetDesc& nd = c->nd;
+  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) { c->stream = nullptr; return fail(PINN_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
+  // debug knobs of k_t16_fused's boundary hand-over (tests/test_gpu_parity.py): force the pre-pass / shorten the wait
+  // (a value that does not parse is an error, not a silent 0: zero ticks would make every hand-over expire at once)
+  // the split one-tile launch of path 7 (split_plan): auto (default), 0 = never, 1 = required where the kernel exists
+  if (const char* v = getenv("PINN_F64_SPLIT")) {
+    if (!strcmp(v, "0")) c->f64_split = 0;
+    else if (!strcmp(v, "1")) c->f64_split = 1;
+    else if (strcmp(v, "auto")) return fail(PINN_EINVAL, "PINN_F64_SPLIT must be auto, 0 or 1 (got \"%s\")", v);
+  }
+  if (const char* v = getenv("PINN_T16_PREPASS")) {
+    if (!(v[0] == '0' || v[0] == '1') || v[1]) return fail(PINN_EINVAL, "PINN_T16_PREPASS must be 0 or 1 (got \"%s\")", v);
+    c->t16_prepass = v[0] == '1';
+    c->t16_prepass_pinned = true;
+  }
+  if (const char* v = getenv("PINN_T16_HANDOVER_TICKS")) {
+    char* end = nullptr;
+    const long long t = strtoll(v, &end, 10);
+    if (end == v || *end || t <= 0) return fail(PINN_EINVAL, "PINN_T16_HANDOVER_TICKS must be a positive integer of 100 MHz ticks (got \"%s\")", v);
+    c->t16_handover_ticks = t;
+  }
+  if (const char* v = getenv("PINN_T16_COSTS")) {
+    double a = 0, b = 0;
+    char tail = 0;
+    if (sscanf(v, "%lf,%lf%c", &a, &b, &tail) != 2 || !(a > 0 && b > 0)) return fail(PINN_EINVAL, "PINN_T16_COSTS must be two positive numbers \"full,strip\" (got \"%s\")", v);
+    c->t16_cost_full = a; c->t16_cost_strip = b;
+  }
+  const size_t n = nd.n_theta;
+  HIPCHK(c->theta.reserve(n));
+  HIPCHK(c->gl.reserve((size_t)c->R));
+  HIPCHK(c->adam_m.reserve(n));
+  HIPCHK(c->adam_v.reserve(n));
+  HIPCHK(c->theta_r.reserve_bytes(n * real_size(c) + 1024));   // + one LDS-DMA piece of slack
+  HIPCHK(hipMemsetAsync(c->theta, 0, n * 8, c->stream));
+  HIPCHK(hipMemsetAsync(c->theta_r, 0, n * real_size(c), c->stream));
+  HIPCHK(hipMemsetAsync(c->gl, 0, (size_t)c->R * 8, c->stream));
+  HIPCHK(c->d_nonfinite.reserve(1));
+  HIPCHK(hipMemsetAsync(c->d_nonfinite, 0, 8, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
+      c->n_cu = prop.multiProcessorCount;
+  }
+  if (fused_regs_ok(c)) {
+    const size_t nimg = fused20m_image_floats(nd.n_hidden);
+    HIPCHK(c->img.reserve(nimg));
+    HIPCHK(hipMemsetAsync(c->img, 0, nimg * 4, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  if (fused_regs_ok(c)) nd.img_kind = 1;
+  if (fused_f64_ok(c)) {
+    std::vector<int> ri((size_t)fused20d_blocks(nd.n_hidden) * 16);
+    fused20d_row_index(nd, nd.n_hidden, ri.data());
+    HIPCHK(c->row_index.reserve(ri.size()));
+    HIPCHK(hipMemcpy(c->row_index, ri.data(), ri.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  if (wide_ok(c)) {
+    const size_t nimg = wide_image_floats<100>(nd.n_hidden);
+    HIPCHK(c->img.reserve(nimg));
+    HIPCHK(hipMemsetAsync(c->img, 0, nimg * 4, c->stream));   // the zero padding is never rewritten
+    HIPCHK(hipStreamSynchronize(c->stream));
+    nd.img_kind = 2;
+  }
+  for (KernelPath p : PATH_PREFERENCE)      // (KP_GENERIC, the last, takes every net)
+    if (path_ok(c, p)) { c->path = p; break; }
+  if (is_adr_ide(c)) return adr_ide_write_tail(c, c->adr);      // starts as Burgers too, every coefficient frozen
+  return 0;
+}
+
 int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* lb,
                 const double* ub, int pde_kind, int dtype, int device) {
   REQUIRE(out && layers && lb && ub, "null argument");
@@ -1817,102 +1845,21 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   nd.n_net = off;
   nd.n_theta = off + tail_len(pde_kind);
   c->R = nd.n_theta + LOSS_SLOTS;
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) { delete c; return fail(PINN_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-  // debug knobs of k_t16_fused's boundary hand-over (tests/test_gpu_parity.py): force the pre-pass / shorten the wait
-  // (a value that does not parse is an error, not a silent 0: zero ticks would make every hand-over expire at once)
-  // the split one-tile launch of path 7 (split_plan): auto (default), 0 = never, 1 = required where the kernel exists
-  if (const char* v = getenv("PINN_F64_SPLIT")) {
-    if (!strcmp(v, "0")) c->f64_split = 0;
-    else if (!strcmp(v, "1")) c->f64_split = 1;
-    else if (strcmp(v, "auto")) { delete c; return fail(PINN_EINVAL, "PINN_F64_SPLIT must be auto, 0 or 1 (got \"%s\")", v); }
-  }
-  if (const char* v = getenv("PINN_T16_PREPASS")) {
-    if (!(v[0] == '0' || v[0] == '1') || v[1]) { delete c; return fail(PINN_EINVAL, "PINN_T16_PREPASS must be 0 or 1 (got \"%s\")", v); }
-    c->t16_prepass = v[0] == '1';
-    c->t16_prepass_pinned = true;
-  }
-  if (const char* v = getenv("PINN_T16_HANDOVER_TICKS")) {
-    char* end = nullptr;
-    const long long t = strtoll(v, &end, 10);
-    if (end == v || *end || t <= 0) { delete c; return fail(PINN_EINVAL, "PINN_T16_HANDOVER_TICKS must be a positive integer of 100 MHz ticks (got \"%s\")", v); }
-    c->t16_handover_ticks = t;
-  }
-  if (const char* v = getenv("PINN_T16_COSTS")) {
-    double a = 0, b = 0;
-    char tail = 0;
-    if (sscanf(v, "%lf,%lf%c", &a, &b, &tail) != 2 || !(a > 0 && b > 0)) { delete c; return fail(PINN_EINVAL, "PINN_T16_COSTS must be two positive numbers \"full,strip\" (got \"%s\")", v); }
-    c->t16_cost_full = a; c->t16_cost_strip = b;
-  }
-  const size_t n = nd.n_theta;
-  if (dev_alloc(&c->theta, n * 8) || dev_alloc(&c->gl, (size_t)c->R * 8) ||
-      dev_alloc(&c->adam_m, n * 8) || dev_alloc(&c->adam_v, n * 8) ||
-      dev_alloc(&c->theta_r, n * real_size(c) + 1024)) { delete c; return PINN_EHIP; }   // + one LDS-DMA piece of slack
-  HIPCHK(hipMemsetAsync(c->theta, 0, n * 8, c->stream));
-  HIPCHK(hipMemsetAsync(c->theta_r, 0, n * real_size(c), c->stream));
-  HIPCHK(hipMemsetAsync(c->gl, 0, (size_t)c->R * 8, c->stream));
-  if (dev_alloc(&c->d_nonfinite, 8)) { delete c; return PINN_EHIP; }
-  HIPCHK(hipMemsetAsync(c->d_nonfinite, 0, 8, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-      c->n_cu = prop.multiProcessorCount;
-  }
-  if (fused_regs_ok(c)) {
-    const size_t nimg = fused20m_image_floats(nd.n_hidden);
-    if (dev_alloc(&c->img, nimg * 4)) { delete c; return PINN_EHIP; }
-    HIPCHK(hipMemsetAsync(c->img, 0, nimg * 4, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  if (fused_regs_ok(c)) nd.img_kind = 1;
-  if (fused_f64_ok(c)) {
-    std::vector<int> ri((size_t)fused20d_blocks(nd.n_hidden) * 16);
-    fused20d_row_index(nd, nd.n_hidden, ri.data());
-    if (dev_alloc(&c->row_index, ri.size() * sizeof(int))) { delete c; return PINN_EHIP; }
-    HIPCHK(hipMemcpy(c->row_index, ri.data(), ri.size() * sizeof(int), hipMemcpyHostToDevice));
-  }
-  if (wide_ok(c)) {
-    const size_t nimg = wide_image_floats<100>(nd.n_hidden);
-    if (dev_alloc(&c->img, nimg * 4)) { delete c; return PINN_EHIP; }
-    HIPCHK(hipMemsetAsync(c->img, 0, nimg * 4, c->stream));   // the zero padding is never rewritten
-    HIPCHK(hipStreamSynchronize(c->stream));
-    nd.img_kind = 2;
-  }
-  for (KernelPath p : PATH_PREFERENCE)      // (KP_GENERIC, the last, takes every net)
-    if (path_ok(c, p)) { c->path = p; break; }
-  if (is_adr_ide(c)) {      // starts as Burgers too, every coefficient frozen
-    if (int rc = adr_ide_write_tail(c, c->adr)) { pinn_destroy(c); return rc; }
-  }
+  if (int rc = ctx_device_init(c)) { (void)pinn_destroy(c); return rc; }
   *out = c;
   return 0;
 }
 
+// The buffers go with `delete c` (devbuf.h): the device is current and the stream idle by then
 int pinn_destroy(pinn_ctx* c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   if (c->comm) ncclCommDestroy(c->comm);
   xg_release(c);
-  void* ptrs[] = {c->xs, c->ts, c->tgt, c->theta, c->gl, c->adam_m, c->adam_v, c->theta_r, c->S,
-                  c->O, c->ZA, c->ZB, c->part, c->xe, c->te, c->Oe, c->f_out, c->loss_hist, c->snap,
-                  c->lb_state, c->lb_x, c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al,
-                  c->lb_q, c->lb_log_loss, c->lb_log_iter, c->lb_SY, c->lb_YY, c->lb_dots, c->lb_cs,
-                  c->lb_cy, c->lb_ex, c->img, c->row_index, c->sa.arr.buf, c->pw.arr.buf, c->d_ginfo, c->d_M[0], c->d_M[1], c->d_MT[0], c->d_MT[1],
-                  c->d_Ast, c->d_A3, c->d_U3, c->d_Nn, c->d_R, c->d_dAp, c->d_lossp, c->d_lamp,
-                  c->pred, c->d_ref, c->err_partial, c->err_res, c->d_nonfinite, c->t16_bsync, c->t16_gscr,
-                  c->rad.cx, c->rad.ct, c->rad.px, c->rad.pt, c->rad.O, c->rad.f, c->rad.w, c->rad.bsum, c->rad.tot,
-                  c->robin.ab, c->robin.out, c->kf.dev};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  for (auto& p : c->pend) {
-    if (p.h_state) (void)hipHostFree(p.h_state);
-    if (p.h_loss) (void)hipHostFree(p.h_loss);
-    if (p.h_iter) (void)hipHostFree(p.h_iter);
-    if (p.ev) (void)hipEventDestroy(p.ev);
-  }
-  if (c->h_err) (void)hipHostFree(c->h_err);
+  for (auto& p : c->pend) if (p.ev) (void)hipEventDestroy(p.ev);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-  if (c->own_stream) (void)hipStreamDestroy(c->stream);
+  if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return 0;
 }
@@ -2001,8 +1948,8 @@ int pinn_get_collocation(pinn_ctx* c, double* X, int64_t n) {
   if (n == 0) return 0;
   const size_t off = (size_t)(2 * c->sd.n_b + c->sd.n_u), rs = real_size(c);
   std::vector<char> hx((size_t)n * rs), ht((size_t)n * rs);
-  HIPCHK(hipMemcpyAsync(hx.data(), (const char*)c->xs + off * rs, hx.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(ht.data(), (const char*)c->ts + off * rs, ht.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hx.data(), c->xs.as<char>() + off * rs, hx.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(ht.data(), c->ts.as<char>() + off * rs, ht.size(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (int64_t i = 0; i < n; ++i) {
     X[2 * i] = c->dtype == PINN_F64 ? ((const double*)hx.data())[i] : (double)((const float*)hx.data())[i];
@@ -2071,16 +2018,13 @@ int pinn_robin_residual(pinn_ctx* c, double* out, int64_t n) {
   REQUIRE(out, "null");
   HIPCHK(hipSetDevice(c->device));
   if (int rc = ensure_sets(c)) return rc;
-  if ((size_t)n > c->robin.cap_out) {
-    if (dev_alloc(&c->robin.out, (size_t)n * 8)) return PINN_EHIP;
-    c->robin.cap_out = (size_t)n;
-  }
+  HIPCHK(c->robin.out.reserve((size_t)n));
   if (int rc = forward_taylor(c, c->xs, c->ts, c->sd.n_pad, c->chunk, c->O)) return rc;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   by_real(c, [&](auto r) {
     using real = decltype(r);
     hipLaunchKernelGGL((k_robin_residual<real>), grid, block, 0, c->stream, pde_coef<real, PDE_ADR_ROBIN>(c),
-                       (const vec4<real>*)c->O, (const real*)c->tgt, c->robin.out);
+                       c->O.as<vec4<real>>(), c->tgt.as<real>(), c->robin.out);
   });
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, c->robin.out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2105,9 +2049,9 @@ int pinn_set_source(pinn_ctx* c, const double* s, int64_t n) {
   if (in_place && c->sd.n_f > 0) {
     const size_t off = (size_t)(2 * c->sd.n_b + c->sd.n_u), rs = real_size(c);
     if (n == 0) {
-      HIPCHK(hipMemsetAsync((char*)c->tgt + off * rs, 0, (size_t)c->sd.n_f * rs, c->stream));
+      HIPCHK(hipMemsetAsync(c->tgt.as<char>() + off * rs, 0, (size_t)c->sd.n_f * rs, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
-    } else if (upload_real(c, (char*)c->tgt + off * rs, s, (size_t)n)) return PINN_EHIP;
+    } else if (upload_real(c, c->tgt.as<char>() + off * rs, s, (size_t)n)) return PINN_EHIP;
   }
   if (n == 0) { c->src.s.clear(); c->src.s.shrink_to_fit(); }
   else c->src.s.assign(s, s + n);
@@ -2133,7 +2077,8 @@ int pinn_set_coef_fields(pinn_ctx* c, const double* K, int64_t n) {
   HIPCHK(hipSetDevice(c->device));
   // the set is assembled and the block has this length: one copy into the device table, no re-assembly (an in-place LHS redraw
   // leaves the set in this state too).  Removal needs no device work: the table is not read without fields
-  const bool in_place = !c->sets_dirty && c->tgt && (n == 0 || (c->sd.n_f == n && c->kf.cap >= (size_t)6 * n));
+  const bool in_place = !c->sets_dirty && c->tgt &&
+                        (n == 0 || (c->sd.n_f == n && c->kf.dev.capacity_bytes() >= (size_t)6 * n * real_size(c)));
   if (in_place && n > 0) {
     if (upload_real(c, c->kf.dev, K, (size_t)6 * n)) return PINN_EHIP;
   }
@@ -2209,7 +2154,7 @@ int pinn_weights_snapshot(pinn_ctx* c, int slot) {
   REQUIRE(c && slot >= 0 && slot < pinn_ctx::N_SNAP, "snapshot slot %d outside 0..%d", slot, pinn_ctx::N_SNAP - 1);
   HIPCHK(hipSetDevice(c->device));
   const size_t bytes = (size_t)c->nd.n_theta * 8;
-  if (!c->snap && dev_alloc(&c->snap, bytes * pinn_ctx::N_SNAP)) return PINN_EHIP;
+  HIPCHK(c->snap.reserve_bytes(bytes * pinn_ctx::N_SNAP));
   HIPCHK(hipMemcpyAsync(c->snap + (size_t)slot * c->nd.n_theta, c->theta, bytes, hipMemcpyDeviceToDevice, c->stream));
   c->snap_valid |= 1u << slot;
   return 0;
@@ -2283,21 +2228,9 @@ static int pend_reserve(pinn_ctx* c, int kind, size_t n_loss, size_t n_iter, boo
           pinn_ctx::N_PENDING);
   pinn_ctx::Pending& p = c->pend[c->tickets_issued % pinn_ctx::N_PENDING];
   if (!p.ev) HIPCHK(hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
-  if (n_loss > p.cap_loss) {
-    if (p.h_loss) (void)hipHostFree(p.h_loss);
-    p.h_loss = nullptr; p.cap_loss = 0;
-    const size_t cap = n_loss < 64 ? 64 : n_loss;
-    HIPCHK(hipHostMalloc((void**)&p.h_loss, cap * 8, hipHostMallocDefault));
-    p.cap_loss = cap;
-  }
-  if (n_iter > p.cap_iter) {
-    if (p.h_iter) (void)hipHostFree(p.h_iter);
-    p.h_iter = nullptr; p.cap_iter = 0;
-    const size_t cap = n_iter < 64 ? 64 : n_iter;
-    HIPCHK(hipHostMalloc((void**)&p.h_iter, cap * 4, hipHostMallocDefault));
-    p.cap_iter = cap;
-  }
-  if (want_state && !p.h_state) HIPCHK(hipHostMalloc((void**)&p.h_state, sizeof(LbfgsState), hipHostMallocDefault));
+  if (n_loss > 0) HIPCHK(p.h_loss.reserve(n_loss < 64 ? 64 : n_loss));      // at least 64 entries; nothing for none
+  if (n_iter > 0) HIPCHK(p.h_iter.reserve(n_iter < 64 ? 64 : n_iter));
+  if (want_state) HIPCHK(p.h_state.reserve(1));
   p.kind = kind;
   *out = &p;
   return 0;
@@ -2314,15 +2247,15 @@ static int adam_issue(pinn_ctx* c, int n_steps, bool record, int* ticket) {
   double* region = nullptr;
   if (record) {
     if (int rc = pend_reserve(c, 1, (size_t)3 * (n_steps > 0 ? n_steps : 1), 0, false, &p)) return rc;
-    if ((size_t)n_steps > c->cap_loss_hist) {
+    const size_t steps = n_steps < 16 ? 16 : n_steps;                  // at least 16 steps per region
+    if (steps * pinn_ctx::N_PENDING * 3 * 8 > c->loss_hist.capacity_bytes()) {
       // a larger ring: the chunks in flight finish first (their copies into the pinned buffers are then complete and the
       // tickets stay collectable), only then is the device ring replaced
       if (pend_outstanding(c) > 0) HIPCHK(hipStreamSynchronize(c->stream));
-      const size_t cap = n_steps < 16 ? 16 : n_steps;
-      if (dev_alloc(&c->loss_hist, cap * pinn_ctx::N_PENDING * 3 * 8)) return PINN_EHIP;
-      c->cap_loss_hist = cap;
+      HIPCHK(c->loss_hist.reserve(steps * pinn_ctx::N_PENDING * 3));
+      c->hist_stride = steps;
     }
-    region = c->loss_hist + (size_t)(c->tickets_issued % pinn_ctx::N_PENDING) * c->cap_loss_hist * 3;
+    region = c->loss_hist + (size_t)(c->tickets_issued % pinn_ctx::N_PENDING) * c->hist_stride * 3;
     p->n = n_steps;
     p->want_terms = c->adam_want_terms;
   }
@@ -2347,7 +2280,7 @@ static int adam_issue(pinn_ctx* c, int n_steps, bool record, int* ticket) {
     by_real(c, [&](auto r) {
       using real = decltype(r);
       hipLaunchKernelGGL((k_adam<real>), dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->gl, c->theta,
-                         (real*)c->theta_r, c->adam_m, c->adam_v, alpha, c->b1, c->b2, c->eps, slot, n, c->nd, c->img);
+                         c->theta_r.as<real>(), c->adam_m, c->adam_v, alpha, c->b1, c->b2, c->eps, slot, n, c->nd, c->img);
     });
   }
   HIPCHK(hipGetLastError());
@@ -2427,11 +2360,11 @@ static int lbfgs_begin_setup(pinn_ctx* c, int max_iter, double lr, int n_corr, d
   c->lb_iters_issued = 0; c->lb_logged_read = 0; c->lb_issued_at_read = 0; c->lb_post_pending = false;
   c->lb_ready = false;
   if (max_iter == 0) { c->lb_ready = true; return 0; }           // custom_lbfgs.py:43-44
-  if (!c->lb_state) {
-    if (dev_alloc(&c->lb_state, 2 * sizeof(LbfgsState)) || dev_alloc(&c->lb_x, n * 8) ||
-        dev_alloc(&c->lb_d, n * 8) || dev_alloc(&c->lb_gold, n * 8) || dev_alloc(&c->lb_q, n * 8))
-      return PINN_EHIP;
-  }
+  HIPCHK(c->lb_state.reserve(2));                                   // (sizes of a context's lifetime: allocated once)
+  HIPCHK(c->lb_x.reserve(n));
+  HIPCHK(c->lb_d.reserve(n));
+  HIPCHK(c->lb_gold.reserve(n));
+  HIPCHK(c->lb_q.reserve(n));
   const int M1 = n_corr + 1;                                       // ring slots (compact mode)
   c->lb_M1 = M1;
   // compact mode needs the two padded Gram matrices in LDS (<= 64 KiB) and one lane per slot
@@ -2441,15 +2374,16 @@ static int lbfgs_begin_setup(pinn_ctx* c, int max_iter, double lr, int n_corr, d
     HIPCHK(hipFuncSetAttribute((const void*)k_lbc_coef_apply<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     HIPCHK(hipFuncSetAttribute((const void*)k_lbc_coef_apply<double>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
-  if (n_corr > c->lb_cap_corr) {
-    if (dev_alloc(&c->lb_S, (size_t)M1 * ring_ld((int)n) * 8) || dev_alloc(&c->lb_Y, (size_t)M1 * ring_ld((int)n) * 8) ||
-        dev_alloc(&c->lb_ro, (size_t)2 * M1 * 8) || dev_alloc(&c->lb_al, (size_t)M1 * 8) ||
-        dev_alloc(&c->lb_SY, (size_t)2 * M1 * M1 * 8) || dev_alloc(&c->lb_YY, (size_t)2 * M1 * M1 * 8) ||
-        dev_alloc(&c->lb_dots, (size_t)2 * (5 * M1 + LBC_NSCAL) * 8) || dev_alloc(&c->lb_cs, (size_t)M1 * 8) ||
-        dev_alloc(&c->lb_cy, (size_t)M1 * 8) || dev_alloc(&c->lb_ex, sizeof(LbcExtra)))
-      return PINN_EHIP;
-    c->lb_cap_corr = n_corr;
-  }
+  HIPCHK(c->lb_S.reserve((size_t)M1 * ring_ld((int)n)));
+  HIPCHK(c->lb_Y.reserve((size_t)M1 * ring_ld((int)n)));
+  HIPCHK(c->lb_ro.reserve((size_t)2 * M1));
+  HIPCHK(c->lb_al.reserve((size_t)M1));
+  HIPCHK(c->lb_SY.reserve((size_t)2 * M1 * M1));
+  HIPCHK(c->lb_YY.reserve((size_t)2 * M1 * M1));
+  HIPCHK(c->lb_dots.reserve((size_t)2 * (5 * M1 + LBC_NSCAL)));
+  HIPCHK(c->lb_cs.reserve((size_t)M1));
+  HIPCHK(c->lb_cy.reserve((size_t)M1));
+  HIPCHK(c->lb_ex.reserve(1));
   {  // unused ring slots must read as finite; Gram matrices, coefficients, dots and the extra record start at zero
     static_assert(sizeof(LbcExtra) % 8 == 0, "LbcExtra is cleared as doubles");
     ZeroList zl{};
@@ -2459,18 +2393,14 @@ static int lbfgs_begin_setup(pinn_ctx* c, int max_iter, double lr, int n_corr, d
     add(c->lb_dots, (size_t)2 * (5 * M1 + LBC_NSCAL)); add(c->lb_ex, sizeof(LbcExtra) / 8);
     // the optimiser state starts as {0..., Hdiag = 1}: written by the same launch (no host buffer in flight)
     static_assert(sizeof(LbfgsState) % 8 == 0 && offsetof(LbfgsState, Hdiag) % 8 == 0, "LbfgsState is initialised as doubles");
-    zl.state = (double*)c->lb_state; zl.state_doubles = (int)(sizeof(LbfgsState) / 8);
+    zl.state = (double*)c->lb_state.get(); zl.state_doubles = (int)(sizeof(LbfgsState) / 8);
     zl.hdiag_index = (int)(offsetof(LbfgsState, Hdiag) / 8);
     hipLaunchKernelGGL(k_zero_list, dim3(256), dim3(256), 0, c->stream, zl);
     HIPCHK(hipGetLastError());
   }
   c->lb_flip = 0;
-  if (max_iter + 1 > c->lb_cap_log) {
-    if (dev_alloc(&c->lb_log_loss, (size_t)(max_iter + 1) * 8) ||
-        dev_alloc(&c->lb_log_iter, (size_t)(max_iter + 1) * 4))
-      return PINN_EHIP;
-    c->lb_cap_log = max_iter + 1;
-  }
+  HIPCHK(c->lb_log_loss.reserve((size_t)max_iter + 1));
+  HIPCHK(c->lb_log_iter.reserve((size_t)max_iter + 1));
   HIPCHK(hipMemcpyAsync(c->lb_x, c->theta, n * 8, hipMemcpyDeviceToDevice, c->stream));
   *eval = true;
   return 0;
@@ -2516,7 +2446,8 @@ static int lbfgs_open(pinn_ctx* c, int n_iters, int* ticket, pinn_ctx::Pending**
   pinn_ctx::Pending* p = nullptr;
   // one log entry per evaluation settled since the host last looked: the iterations issued since then, this chunk's, + 1
   int window = (c->lb_iters_issued - c->lb_issued_at_read) + n_iters + 1;
-  if (window > c->lb_cap_log - c->lb_logged_read) window = c->lb_cap_log - c->lb_logged_read;
+  const int log_room = (int)(c->lb_log_iter.capacity_bytes() / sizeof(int));   // entries the two log arrays hold
+  if (window > log_room - c->lb_logged_read) window = log_room - c->lb_logged_read;
   if (window < 0 || c->lb_max_iter == 0) window = 0;
   if (int rc = pend_reserve(c, 2, (size_t)window + 1, (size_t)window + 1, true, &p)) return rc;
   if (c->lb_max_iter == 0) {                                       // custom_lbfgs.py:43-44: nothing to do, done at once
@@ -2565,7 +2496,7 @@ static int lbfgs_iter(pinn_ctx* c, bool* eval) {
                            c->lb_ro + c->lb_flip * M1, c->lb_SY + (c->lb_flip ^ 1) * mm,
                            c->lb_YY + (c->lb_flip ^ 1) * mm, c->lb_ro + (c->lb_flip ^ 1) * M1,
                            c->lb_log_iter, c->lb_log_loss, c->lb_S, c->lb_Y, c->lb_d, c->lb_gold,
-                           c->lb_x, c->theta, (real*)c->theta_r, c->nd, c->img);
+                           c->lb_x, c->theta, c->theta_r.as<real>(), c->nd, c->img);
       });
       c->lb_post_pending = false;
       c->lb_flip ^= 1;
@@ -2573,7 +2504,7 @@ static int lbfgs_iter(pinn_ctx* c, bool* eval) {
       by_real(c, [&](auto r) {
         using real = decltype(r);
         hipLaunchKernelGGL((k_lbfgs_step<real>), dim3(1), dim3(LB_THREADS), 0, c->stream, n, c->lb_max_iter, c->lb_ncorr,
-                           c->lb_lr, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_x, c->theta, (real*)c->theta_r,
+                           c->lb_lr, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_x, c->theta, c->theta_r.as<real>(),
                            c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al, c->lb_q, c->nd, c->img);
       });
     *eval = c->lb_iters_issued != c->lb_max_iter;                  // last iteration: no re-evaluation
@@ -2721,16 +2652,16 @@ int pinn_error_l2(pinn_ctx* c, const double* X, const double* ref, int64_t n, in
   if (int rc = eval_points(c, X, n, &n_pad)) return rc;
   if (c->ev_ref.size() != n_ref || memcmp(c->ev_ref.data(), ref, n_ref * 8) != 0) {
     c->ev_ref.clear();
-    if (n_ref > c->cap_ref) { if (dev_alloc(&c->d_ref, n_ref * 8)) return PINN_EHIP; c->cap_ref = n_ref; }
+    HIPCHK(c->d_ref.reserve(n_ref));
     HIPCHK(hipMemcpyAsync(c->d_ref, ref, n_ref * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->ev_ref.assign(ref, ref + n_ref);
   }
   if (int rc = predict_values(c, n, n_pad)) return rc;
   const int nb = (int)((n_ref + ERR_SPAN - 1) / ERR_SPAN);
-  if ((size_t)nb > c->cap_errp) { if (dev_alloc(&c->err_partial, (size_t)nb * 16)) return PINN_EHIP; c->cap_errp = nb; }
-  if (!c->err_res && dev_alloc(&c->err_res, 3 * 8)) return PINN_EHIP;
-  if (!c->h_err) HIPCHK(hipHostMalloc((void**)&c->h_err, 3 * 8, hipHostMallocDefault));
+  HIPCHK(c->err_partial.reserve((size_t)nb * 2));
+  HIPCHK(c->err_res.reserve(3));
+  HIPCHK(c->h_err.reserve(3));
   hipLaunchKernelGGL(k_err_partial, dim3(nb), dim3(ERR_THREADS), 0, c->stream, (const double*)c->pred,
                      (const double*)c->d_ref, (long long)n_ref, NO, kind, c->err_partial);
   hipLaunchKernelGGL(k_err_final, dim3(1), dim3(64), 0, c->stream, (const double*)c->err_partial, nb, c->err_res);
@@ -2796,10 +2727,7 @@ int pinn_residual(pinn_ctx* c, double* f, int64_t n) {
   REQUIRE(n == cnt, "residual buffer holds %lld points, the set has %d", (long long)n, cnt);
   if (cnt == 0) return 0;
   const int NO = c->nd.n_out;
-  if ((size_t)cnt * NO > c->cap_f) {
-    if (dev_alloc(&c->f_out, (size_t)cnt * NO * 8)) return PINN_EHIP;
-    c->cap_f = (size_t)cnt * NO;
-  }
+  HIPCHK(c->f_out.reserve((size_t)cnt * NO));
   if (int rc2 = forward_taylor(c, c->xs, c->ts, sd.n_pad, c->chunk, c->O)) return rc2;
   if (int rc2 = launch_residual(c, AT_SET, c->O, first, cnt, sd.n_pad, c->f_out)) return rc2;
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)cnt * NO * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2820,10 +2748,7 @@ int pinn_residual_at(pinn_ctx* c, const double* X, int64_t n, double* f) {
   if (int rc = eval_points(c, X, n, &n_pad)) return rc;
   const int chunk = n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS;
   if (int rc = forward_taylor(c, c->xe, c->te, n_pad, chunk, c->Oe)) return rc;
-  if ((size_t)n * NO > c->cap_f) {
-    if (dev_alloc(&c->f_out, (size_t)n * NO * 8)) return PINN_EHIP;
-    c->cap_f = (size_t)n * NO;
-  }
+  HIPCHK(c->f_out.reserve((size_t)n * NO));
   // (a context with a source: s is not known at foreign points, launch_residual leaves it out)
   if (int rc = launch_residual(c, AT_FOREIGN, c->Oe, 0, (int)n, n_pad, c->f_out)) return rc;
   HIPCHK(hipMemcpyAsync(f, c->f_out, (size_t)n * NO * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2866,7 +2791,7 @@ int pinn_comm_xgmi_export(pinn_ctx* c, int n_ranks, int rank, char* handle64) {
   hipError_t e = hipExtMallocWithFlags(&c->xg.box, bytes, hipDeviceMallocUncached);
   if (e != hipSuccess) { c->xg.box = nullptr; return fail(PINN_EHIP, "mailbox allocation: %s", hipGetErrorString(e)); }
   HIPCHK(hipMemset(c->xg.box, 0, bytes));
-  if (dev_alloc(&c->xg.err, sizeof(int))) return PINN_EHIP;
+  HIPCHK(c->xg.err.reserve(1));
   HIPCHK(hipMemset(c->xg.err, 0, sizeof(int)));
   HIPCHK(hipDeviceSynchronize());
   c->xg.peers = XgPeers{};
@@ -2925,8 +2850,9 @@ int pinn_comm_benchmark(pinn_ctx* c, int mode, int iters, double* us_per_iter) {
   if (mode == 2) REQUIRE(c->xg.attached, "mailboxes are not attached");
   HIPCHK(hipSetDevice(c->device));
   const int R = c->R;
-  double *vec = nullptr, *out = nullptr;
-  if (dev_alloc(&vec, (size_t)R * 8) || dev_alloc(&out, (size_t)R * 8)) return PINN_EHIP;
+  DevBuf<double> vec, out;                       // the call's own: freed on every return
+  HIPCHK(vec.reserve(R));
+  HIPCHK(out.reserve(R));
   HIPCHK(hipMemsetAsync(vec, 0, (size_t)R * 8, c->stream));
   const dim3 grid((R + RED_COLS - 1) / RED_COLS), block(RED_THREADS);
   auto once = [&]() -> int {
@@ -2950,7 +2876,6 @@ int pinn_comm_benchmark(pinn_ctx* c, int mode, int iters, double* us_per_iter) {
   HIPCHK(hipStreamSynchronize(c->stream));
   *us_per_iter = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() / iters;
   HIPCHK(hipGetLastError());
-  (void)hipFree(vec); (void)hipFree(out);
   if (mode == 2) {
     int e = 0;
     HIPCHK(hipMemcpy(&e, c->xg.err, sizeof(int), hipMemcpyDeviceToHost));
@@ -3058,14 +2983,15 @@ int pinn_debug_stamps(pinn_ctx* c, long long* out, int64_t cap, int64_t* n_waves
   const int n_wgs = split_plan(c) == 1 ? fused20d_split_grid(c->sd.n_pad / 64) : path_rows(c);
   const size_t n = (size_t)n_wgs * 4 * 32;
   REQUIRE((size_t)cap >= n, "stamp buffer too small: need %zu", n);
-  if (dev_alloc(&c->stamps, n * 8)) return PINN_EHIP;
+  c->stamps.reset();
+  HIPCHK(c->stamps.reserve(n));
   HIPCHK(hipMemsetAsync(c->stamps, 0, n * 8, c->stream));
   rc = eval_loss_grad(c);
+  hipError_t he = rc ? hipSuccess : hipMemcpyAsync(out, c->stamps, n * 8, hipMemcpyDeviceToHost, c->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+  c->stamps.reset();                             // on every exit: the evaluations that follow take no stamps
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->stamps, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  (void)hipFree(c->stamps);
-  c->stamps = nullptr;
+  HIPCHK(he);
   *n_waves = (int64_t)(n / 32);
   return 0;
 #else
@@ -3107,6 +3033,12 @@ int pinn_debug_t16f_stamps(long long* out512) {
   (void)out512;
   return fail(PINN_EUNSUPPORTED, "built without -DPINN_STAMPS (profiling build only)");
 #endif
+}
+
+int pinn_debug_live_buffers(int64_t* n, int64_t* bytes) {
+  if (n) *n = devbuf::live_blocks.load();
+  if (bytes) *bytes = devbuf::live_bytes.load();
+  return 0;
 }
 
 int pinn_get_kernel_path(pinn_ctx* c, int* path) {
@@ -3276,12 +3208,11 @@ struct pinn_ens {
   pinn_ctx* base = nullptr;
   int K = 0, P = 0, sw = 0;                    // members, parameters, weight-mirror stride (fused20d_weight_doubles(P))
   std::vector<pinn_ctx*> mem;
-  double *theta = nullptr, *theta_r = nullptr, *gl = nullptr, *m = nullptr, *v = nullptr;   // [K][P] / [K][sw] / [K][R]
-  unsigned long long* nonfinite = nullptr;     // [K]
-  double* part = nullptr;                      // [K][n_wg][R]
-  size_t cap_part = 0;
-  double* loss_hist = nullptr;                 // Adam: [steps][K][3]
-  size_t cap_loss = 0;
+  // the blocks the members' buffers are views of (ens_build); ens_free keeps the order members -> blocks -> base
+  DevBuf<double> theta, theta_r, gl, m, v;     // [K][P] / [K][sw] / [K][R]
+  DevBuf<unsigned long long> nonfinite;        // [K]
+  DevBuf<double> part;                         // [K][n_wg][R]
+  DevBuf<double> loss_hist;                    // Adam: [steps][K][3]
   // per-member point sets and viscosities (pinn_ensk_*).  Off (shared mode) until the first per-member call; then the
   // members' sets live here, member-major, while the base keeps member 0's, so that ensure_sets(base) still gives the
   // SetDesc and the launch plan (every member has the same counts).  The shared setters broadcast in this mode.
@@ -3289,30 +3220,24 @@ struct pinn_ens {
   std::vector<double> kXf, kXu, kU;            // [K][n_f][2], [K][n_u][2], [K][n_u], as handed over
   std::vector<uint64_t> k_seeds;               // [K] device LHS seeds (the design geometry is the base's lhs)
   std::vector<double> k_nu;                    // [K]
-  double *k_xs = nullptr, *k_ts = nullptr, *k_tgt = nullptr, *k_nud = nullptr;   // [K][n_pad] x 3, [K]
-  size_t k_cap = 0;
+  DevBuf<double> k_xs, k_ts, k_tgt, k_nud;     // [K][n_pad] x 3, [K]
   // an ensemble of the adr kind (pinn_adr_ens_create): every member has its own six coefficients in BOTH modes -- the host
   // rows [K][6] and the device table [K][ADR_ENS_ROW] k_fused20d<PDE_ADR_ENS> reads, there from creation and re-uploaded when dirty --
   // and, in per-member mode, its own periodic pairs (one common n)
   bool adr = false, coef_dirty = true;
   std::vector<double> coef;                    // [K][6]
-  double* coef_d = nullptr;                    // [K][ADR_ENS_ROW]
+  DevBuf<double> coef_d;                       // [K][ADR_ENS_ROW]
   std::vector<double> kXlo, kXhi;              // [K][n_b][2]
 };
 
+// The order is the point: the members first (their views of the blocks die with them), then the blocks (`delete e`, on the
+// base's device with its stream idle), then the base, whose stream everything above ran on
 static void ens_free(pinn_ens* e) {
-  for (pinn_ctx* c : e->mem) {
-    if (!c) continue;
-    c->theta = nullptr; c->theta_r = nullptr; c->gl = nullptr; c->adam_m = nullptr; c->adam_v = nullptr;
-    c->d_nonfinite = nullptr;                  // slices of the blocks below
-    (void)pinn_destroy(c);
-  }
-  if (e->base) { (void)hipSetDevice(e->base->device); (void)hipStreamSynchronize(e->base->stream); }
-  void* ptrs[] = {e->theta, e->theta_r, e->gl, e->m, e->v, e->nonfinite, e->part, e->loss_hist, e->k_xs, e->k_ts,
-                  e->k_tgt, e->k_nud, e->coef_d};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (e->base) (void)pinn_destroy(e->base);
+  for (pinn_ctx* c : e->mem) (void)pinn_destroy(c);
+  pinn_ctx* const base = e->base;
+  if (base) { (void)hipSetDevice(base->device); (void)hipStreamSynchronize(base->stream); }
   delete e;
+  (void)pinn_destroy(base);
 }
 
 // shared -> per-member mode: every member starts from the shared sets and viscosity
@@ -3369,7 +3294,7 @@ static int ens_ensure_sets(pinn_ens* e) {
   if (!e->k_mode) return 0;
   if (!e->adr) {
     if (!e->k_nud) {
-      if (dev_alloc(&e->k_nud, K * 8)) return PINN_EHIP;
+      HIPCHK(e->k_nud.reserve(K));
       e->k_nu_dirty = true;
     }
     if (e->k_nu_dirty) {
@@ -3399,11 +3324,9 @@ static int ens_ensure_sets(pinn_ens* e) {
       for (size_t i = 0; i < n_f; ++i, ++g) { x[g] = xf[2 * i]; t[g] = xf[2 * i + 1]; }
     for (; g < n_pad; ++g) { x[g] = b->lb[0]; t[g] = b->lb[1]; }  // inert padding; LHS slots filled below
   }
-  if (K * n_pad > e->k_cap) {
-    if (dev_alloc(&e->k_xs, K * n_pad * 8) || dev_alloc(&e->k_ts, K * n_pad * 8) || dev_alloc(&e->k_tgt, K * n_pad * 8))
-      return PINN_EHIP;
-    e->k_cap = K * n_pad;
-  }
+  HIPCHK(e->k_xs.reserve(K * n_pad));
+  HIPCHK(e->k_ts.reserve(K * n_pad));
+  HIPCHK(e->k_tgt.reserve(K * n_pad));
   if (upload_real(b, e->k_xs, hx.data(), K * n_pad) || upload_real(b, e->k_ts, ht.data(), K * n_pad) ||
       upload_real(b, e->k_tgt, htg.data(), K * n_pad)) return PINN_EHIP;
   if (b->lhs.on) { if (int rc = ens_lhs_fill(e)) return rc; }
@@ -3419,7 +3342,7 @@ static int ens_eval(pinn_ens* e, const bool* active, const double* alpha, double
   if (int rc = ens_ensure_sets(e)) return rc;
   const int n_rows = path_rows(b);
   const size_t need = (size_t)e->K * n_rows * b->R;
-  if (need > e->cap_part) { if (dev_alloc(&e->part, need * 8)) return PINN_EHIP; e->cap_part = need; }
+  HIPCHK(e->part.reserve(need));
   F20dLaunch a = fused20d_args(b, nullptr);
   a.th = e->theta_r; a.part = e->part; a.n_members = e->K;
   if (e->k_mode) { a.xs = e->k_xs; a.ts = e->k_ts; a.tgt = e->k_tgt; }
@@ -3464,46 +3387,54 @@ static int ens_check_shape(const int* layers, int n_layers) {
   return 0;
 }
 
-// the base, the blocks and the members of an ensemble of float64 contexts of pde_kind (the arguments are checked)
-static int ens_build(pinn_ens** out, const int* layers, int n_layers, const double* lb, const double* ub, int pde_kind,
-                     int device, int n_members) {
+// the base, the blocks and the members of an ensemble of float64 contexts of pde_kind (the arguments are checked), into a
+// fresh e.  ens_build frees whatever stands on any failure, so every return here is plain
+static int ens_build_into(pinn_ens* e, const int* layers, int n_layers, const double* lb, const double* ub, int pde_kind,
+                          int device) {
   const int dtype = PINN_F64;
-  *out = nullptr;
-  pinn_ens* e = new pinn_ens();
-  e->K = n_members;
-  if (int rc = pinn_create(&e->base, layers, n_layers, lb, ub, pde_kind, dtype, device)) { delete e; return rc; }
+  if (int rc = pinn_create(&e->base, layers, n_layers, lb, ub, pde_kind, dtype, device)) return rc;
   pinn_ctx* b = e->base;
-  if (b->path != KP_FUSED20D) { ens_free(e); return fail(PINN_EUNSUPPORTED, "ensembles need kernel path 7 (got %d)", (int)b->path); }
+  if (b->path != KP_FUSED20D) return fail(PINN_EUNSUPPORTED, "ensembles need kernel path 7 (got %d)", (int)b->path);
   e->P = b->nd.n_theta;
   e->sw = (int)fused20d_weight_doubles(e->P);
   const size_t K = e->K, P = e->P;
   if (pde_kind == PINN_PDE_ADR) {              // every row starts as a new adr context's coefficients
     e->adr = true;
     for (size_t k = 0; k < K; ++k) e->coef.insert(e->coef.end(), b->adr, b->adr + 6);
-    if (dev_alloc(&e->coef_d, K * ADR_ENS_ROW * 8)) { ens_free(e); return PINN_EHIP; }
+    HIPCHK(e->coef_d.reserve(K * ADR_ENS_ROW));
     e->coef_dirty = true;
   }
-  if (dev_alloc(&e->theta, K * P * 8) || dev_alloc(&e->m, K * P * 8) || dev_alloc(&e->v, K * P * 8) ||
-      dev_alloc(&e->theta_r, K * e->sw * 8 + 1024) || dev_alloc(&e->gl, K * b->R * 8) ||
-      dev_alloc(&e->nonfinite, K * 8)) { ens_free(e); return PINN_EHIP; }
+  HIPCHK(e->theta.reserve(K * P));
+  HIPCHK(e->m.reserve(K * P));
+  HIPCHK(e->v.reserve(K * P));
+  HIPCHK(e->theta_r.reserve_bytes(K * e->sw * 8 + 1024));
+  HIPCHK(e->gl.reserve(K * b->R));
+  HIPCHK(e->nonfinite.reserve(K));
   HIPCHK(hipMemsetAsync(e->theta, 0, K * P * 8, b->stream));
   HIPCHK(hipMemsetAsync(e->theta_r, 0, K * e->sw * 8 + 1024, b->stream));
   HIPCHK(hipMemsetAsync(e->gl, 0, K * b->R * 8, b->stream));
   HIPCHK(hipMemsetAsync(e->nonfinite, 0, K * 8, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
-  e->mem.assign(K, nullptr);
   for (size_t k = 0; k < K; ++k) {
     pinn_ctx* c = nullptr;
-    if (int rc = pinn_create(&c, layers, n_layers, lb, ub, pde_kind, dtype, device)) { ens_free(e); return rc; }
-    e->mem[k] = c;
-    void* own[] = {c->theta, c->theta_r, c->gl, c->adam_m, c->adam_v, c->d_nonfinite};
-    for (void* p : own) (void)hipFree(p);
-    c->theta = e->theta + k * P; c->adam_m = e->m + k * P; c->adam_v = e->v + k * P;
-    c->theta_r = e->theta_r + k * e->sw; c->gl = e->gl + k * b->R; c->d_nonfinite = e->nonfinite + k;
+    if (int rc = pinn_create(&c, layers, n_layers, lb, ub, pde_kind, dtype, device)) return rc;
+    e->mem.push_back(c);
+    // the member's own six buffers are freed, in this order, and become views of its slices of the blocks
+    c->theta.borrow(e->theta + k * P); c->theta_r.borrow(e->theta_r + k * e->sw); c->gl.borrow(e->gl + k * b->R);
+    c->adam_m.borrow(e->m + k * P); c->adam_v.borrow(e->v + k * P); c->d_nonfinite.borrow(e->nonfinite + k);
     (void)hipStreamDestroy(c->stream);
     c->stream = b->stream;
     c->own_stream = false;
   }
+  return 0;
+}
+
+static int ens_build(pinn_ens** out, const int* layers, int n_layers, const double* lb, const double* ub, int pde_kind,
+                     int device, int n_members) {
+  *out = nullptr;
+  pinn_ens* e = new pinn_ens();
+  e->K = n_members;
+  if (int rc = ens_build_into(e, layers, n_layers, lb, ub, pde_kind, device)) { ens_free(e); return rc; }
   *out = e;
   return 0;
 }
@@ -3741,10 +3672,7 @@ int pinn_ens_adam_run(pinn_ens* e, int n_steps, double* losses) {
   HIPCHK(hipSetDevice(b->device));
   if (n_steps == 0) return 0;
   const size_t K = e->K;
-  if ((size_t)n_steps * K * 3 > e->cap_loss) {
-    if (dev_alloc(&e->loss_hist, (size_t)n_steps * K * 3 * 8)) return PINN_EHIP;
-    e->cap_loss = (size_t)n_steps * K * 3;
-  }
+  HIPCHK(e->loss_hist.reserve((size_t)n_steps * K * 3));
   std::vector<char> all(K, 1);
   std::vector<double> alpha(K);
   for (int s = 0; s < n_steps; ++s) {

@@ -17,7 +17,7 @@ _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _REPO = os.path.dirname(os.path.dirname(_HERE))
 LIB_PATH = os.environ.get("PINN_HIP_LIB") or os.path.join(_HERE, "libpinn_hip.so")
 SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_fused20d_kernel.h", "kernels_fused20d_reverse.h", "kernels_wide.h", "kernels_predict20.h",
-           "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h"]
+           "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h", "devbuf.h"]
 HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
 PDE_KINDS = {"burgers": 0, "burgers_ide": 1, "schrodinger": 2, "burgers_disc": 3, "burgers_disc_ide": 4, "adr": 5, "adr_ide": 6}
@@ -248,6 +248,7 @@ _SIGNATURES = {
     "pinn_debug_coef_stamps": (ctypes.c_int, [ctypes.POINTER(ctypes.c_longlong)]),
     "pinn_debug_t16f_stamps": (ctypes.c_int, [ctypes.POINTER(ctypes.c_longlong)]),
     "pinn_debug_t16_deal": (ctypes.c_int, [ctypes.c_int, _c_int_p]),
+    "pinn_debug_live_buffers": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "pinn_debug_stamps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong),
                                          ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     # ensembles (include/pinn_hip.h: pinn_ens_*)
@@ -435,6 +436,13 @@ def device_count():
     if lib.pinn_device_count(ctypes.byref(n)) != 0:
         return 0
     return n.value
+
+
+def live_buffers():
+    """(blocks, bytes) of device and pinned host memory the engine owns in this process right now (pinn_debug_live_buffers)"""
+    n, b = ctypes.c_int64(0), ctypes.c_int64(0)
+    load().pinn_debug_live_buffers(ctypes.byref(n), ctypes.byref(b))
+    return n.value, b.value
 
 
 def device_info(device=0):

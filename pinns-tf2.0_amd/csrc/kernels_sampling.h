@@ -73,9 +73,15 @@ __global__ __launch_bounds__(256) void k_lhs_fill(real* __restrict__ xs, real* _
   const uint64_t p0 = lhs_permute(i, n, half_bits, seed_lo ^ 0x243F6A88u, seed_hi ^ 0x85A308D3u);
   const uint64_t p1 = lhs_permute(i, n, half_bits, seed_lo ^ 0x13198A2Eu, seed_hi ^ 0x03707344u);
   const double dn = (double)n;
-  // explicit roundings: no fused multiply-add, so that the numpy restatement is bit-identical
-  const double x = __dadd_rn(lbx, __dmul_rn(rx, __ddiv_rn(__dadd_rn((double)p0, u0), dn)));
-  const double tt = __dadd_rn(lbt, __dmul_rn(rt, __ddiv_rn(__dadd_rn((double)p1, u1), dn)));
+  // every operation rounded on its own, so that the numpy restatement is bit-identical.  (__dadd_rn / __dmul_rn do not say
+  // that: they are inline + and * that hipcc contracts into one fma after inlining, which shows wherever lb != 0 and
+  // r * v is inexact, i.e. on any box but x in [-1, 1], t from 0.  The pragma covers the operators written in its block.)
+  double x, tt;
+  {
+#pragma clang fp contract(off)
+    x = lbx + rx * (((double)p0 + u0) / dn);
+    tt = lbt + rt * (((double)p1 + u1) / dn);
+  }
   xs[t] = (real)x;
   ts[t] = (real)tt;
 }
@@ -105,8 +111,12 @@ __global__ __launch_bounds__(256) void k_lhs_fill_ens(double* __restrict__ xs, d
   const uint64_t p0 = lhs_permute(i, n, half_bits, seed_lo ^ 0x243F6A88u, seed_hi ^ 0x85A308D3u);
   const uint64_t p1 = lhs_permute(i, n, half_bits, seed_lo ^ 0x13198A2Eu, seed_hi ^ 0x03707344u);
   const double dn = (double)n;
-  const double x = __dadd_rn(lbx, __dmul_rn(rx, __ddiv_rn(__dadd_rn((double)p0, u0), dn)));
-  const double tt = __dadd_rn(lbt, __dmul_rn(rt, __ddiv_rn(__dadd_rn((double)p1, u1), dn)));
+  double x, tt;
+  {
+#pragma clang fp contract(off)
+    x = lbx + rx * (((double)p0 + u0) / dn);
+    tt = lbt + rt * (((double)p1 + u1) / dn);
+  }
   xs[(size_t)m * stride + t] = x;
   ts[(size_t)m * stride + t] = tt;
 }

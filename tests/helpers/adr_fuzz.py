@@ -122,13 +122,14 @@ def restate_adr(layers, w, coeffs, X_f, X_u=None, u=None, X_lo=None, X_hi=None, 
             "f": f, "A_f": A_f, "r": rr, "A_r": A_r}
 
 
-def _ide_scale(layers, theta, X_f, dtype):
+def _ide_scale(layers, theta, X_f, dtype, lb=LB, ub=UB):
     """A_f of the adr_ide kind at its current coefficients (adr_ide_ref.restate returns f only)"""
     dt = np.dtype(dtype).type
     nn = adr_ide_ref.n_net(layers)
     params = ge._unpack(np.asarray(theta[:nn], dtype=np.float64), layers, dt)
-    sc = (2 / (UB - LB)).astype(dt)
-    (h, p, q, r), _ = ge._forward(params, np.asarray(X_f, dtype=np.float64).astype(dt), LB.astype(dt), sc, False)
+    lb, ub = np.asarray(lb, dtype=np.float64), np.asarray(ub, dtype=np.float64)
+    sc = (2 / (ub - lb)).astype(dt)
+    (h, p, q, r), _ = ge._forward(params, np.asarray(X_f, dtype=np.float64).astype(dt), lb.astype(dt), sc, False)
     a0, a1, lnu, r1, r2, r3 = (dt(v) for v in theta[nn:])
     nu = np.exp(lnu)
     return (ge._abs64(q) + ge._abs64(a0 * p) + ge._abs64(a1 * h * p) + ge._abs64(nu * r) + ge._abs64(r1 * h)

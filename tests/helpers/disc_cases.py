@@ -88,15 +88,16 @@ def random_cases(n=12, seed=20261016):
     return out
 
 
-def build(model, layers, q, n0, n1, seed):
+def build(model, layers, q, n0, n1, seed, lb=-1.0, ub=1.0):
     """-> (sets, w, nu): stage sets as disc_set_stage takes them (x [n,1], target [n,1], M or None), the flat weights
-    (with [lambda_1, lambda_2] appended for identification) and the viscosity (None for identification)."""
+    (with [lambda_1, lambda_2] appended for identification) and the viscosity (None for identification).  lb, ub: the x
+    range the points are drawn from (tests/helpers/boxes.py)."""
     from oracle import disc
     rs = np.random.RandomState(seed)
     W, n_out = layers[1], layers[-1]
     A, b, _ = disc.gauss_legendre_butcher(q)
     dt = rs.uniform(0.1, 0.8)
-    x0, x1 = rs.uniform(-1, 1, (n0, 1)), rs.uniform(-1, 1, (n1, 1))
+    x0, x1 = rs.uniform(lb, ub, (n0, 1)), rs.uniform(lb, ub, (n1, 1))
     u0 = -np.sin(np.pi * x0) + 0.1 * rs.standard_normal((n0, 1))
     u1 = -np.sin(np.pi * x1) + 0.1 * rs.standard_normal((n1, 1))
     n_net = sum(a * c + c for a, c in zip(layers[:-1], layers[1:]))

@@ -193,7 +193,7 @@ def _backward(params, cache, hb, pb, qb, rb, G, A):
             hb, pb, qb, rb = zb @ W.T, zpb @ W.T, zqb @ W.T, zrb @ W.T
 
 
-def restate(kind, w, layers, lb, ub, sets, dtype, tanh_formula=False):
+def restate(kind, w, layers, lb, ub, sets, dtype, tanh_formula=False, uxx_scale=None):
     """Loss, flat gradient and entrywise scale A of `kind` in {burgers, burgers_ide, schrodinger} with all arithmetic in
     `dtype` (np.float32, np.float64, np.longdouble); points, targets and weights are cast first, as the engine does.
 
@@ -204,8 +204,11 @@ def restate(kind, w, layers, lb, ub, sets, dtype, tanh_formula=False):
           of rows handed over (a set with points dropped keeps the full set's denominator, as a kernel that loses a
           point does)
     tanh_formula: True or "r5": tanh as 1 - 2 / (1 + e^{2z}) (the float32 kernels' tanh_r5); "bf": as
-                  sign(z) (1 - t) / (1 + t), t = e^{-2|z|} (k_fused20's tanh_bf)"""
+                  sign(z) (1 - t) / (1 + t), t = e^{-2|z|} (k_fused20's tanh_bf)
+    uxx_scale: None, or a factor on every u_xx of the residual and of its adjoint: 1 / sx is a kernel whose second
+               derivative carries sx once instead of twice (a mutant of tests/test_boxes_host.py)"""
     dt = np.dtype(dtype).type
+    xx = None if uxx_scale is None else dt(uxx_scale)
     wide = np.longdouble if dt is np.longdouble else np.float64
     lbd = np.asarray(lb, dtype=wide)
     s = (2 / (np.asarray(ub, dtype=wide) - lbd)).astype(dt)        # the engine: 2 / (ub - lb) in float64, then cast
@@ -221,6 +224,7 @@ def restate(kind, w, layers, lb, ub, sets, dtype, tanh_formula=False):
 
     if kind == "burgers":
         X_f, X_u, u, nu = cast(sets["X_f"]), cast(sets["X_u"]), cast(sets["u"]), dt(sets["nu"])
+        nu = nu if xx is None else nu * xx
         n_f, n_u = dt(sets.get("n_f", X_f.shape[0])), dt(sets.get("n_u", u.size))
         (h, p, q, r), cache = _forward(params, X_f, lbd, s, tanh_formula)
         f = q + h * p - nu * r
@@ -234,7 +238,7 @@ def restate(kind, w, layers, lb, ub, sets, dtype, tanh_formula=False):
         X_u, u = cast(sets["X_u"]), cast(sets["u"])
         n = dt(sets.get("n_u", X_u.shape[0]))
         l1, l2 = dt(w[-2]), dt(w[-1])
-        c2 = np.exp(l2)
+        c2 = np.exp(l2) if xx is None else np.exp(l2) * xx
         (h, p, q, r), cache = _forward(params, X_u, lbd, s, tanh_formula)
         f = q + l1 * h * p - c2 * r
         d = h - u
@@ -251,13 +255,14 @@ def restate(kind, w, layers, lb, ub, sets, dtype, tanh_formula=False):
         (h, p, q, r), cache = _forward(params, X_f, lbd, s, tanh_formula)
         u, v = h[:, 0:1], h[:, 1:2]
         h2 = u * u + v * v
-        f_u = q[:, 0:1] + dt(0.5) * r[:, 1:2] + h2 * v
-        f_v = q[:, 1:2] - dt(0.5) * r[:, 0:1] - h2 * u
+        half = dt(0.5) if xx is None else dt(0.5) * xx
+        f_u = q[:, 0:1] + half * r[:, 1:2] + h2 * v
+        f_v = q[:, 1:2] - half * r[:, 0:1] - h2 * u
         gu, gv = dt(2) * f_u / n_f, dt(2) * f_v / n_f
         hb = np.concatenate([gu * dt(2) * u * v - gv * (dt(3) * u * u + v * v),
                              gu * (u * u + dt(3) * v * v) - gv * dt(2) * u * v], axis=1)
         _backward(params, cache, hb, zero(hb), np.concatenate([gu, gv], axis=1),
-                  np.concatenate([dt(-0.5) * gv, dt(0.5) * gu], axis=1), G, A)
+                  np.concatenate([-half * gv, half * gu], axis=1), G, A)
         loss = (np.sum(f_u * f_u) + np.sum(f_v * f_v)) / n_f
         (h0, _, _, _), cache = _forward(params, X0, lbd, s, tanh_formula)
         d0 = h0 - uv0

@@ -68,10 +68,10 @@ _POOLS = {}
 
 
 def _pool(name, n_pool, seed):
-    """P: the n_pool-point design pinn_lhs_collocation(n_pool, seed) draws on a context of this case.  Burgers: equal to
-    oracle.lhs.lhs_points (rounded to float32 for float32 contexts).  hipcc contracts k_lhs_fill's lb + span * v into one
-    fused multiply-add, which the numpy oracle does not restate: it shows where span * v is inexact AND lb != 0 (the
-    Schrodinger x range), so the pool is read back from the device, which is what P is."""
+    """P: the n_pool-point design pinn_lhs_collocation(n_pool, seed) draws on a context of this case, read back from the
+    device and equal to oracle.lhs.lhs_points (rounded to float32 for float32 contexts) on both boxes.  (On the Schrodinger
+    x range it was not until k_lhs_fill stopped contracting lb + span * v into one fused multiply-add: that shows where
+    span * v is inexact and lb != 0; tests/test_gpu_boxes.py.)"""
     import pinn_native
     layers, pde, dtype = CASES[name]
     lb, ub = _bounds(pde)
@@ -81,8 +81,7 @@ def _pool(name, n_pool, seed):
     probe = _POOLS[key]
     probe.lhs_collocation(n_pool, seed)
     P = probe.get_collocation()
-    if pde == "burgers":
-        assert np.array_equal(P, rad_ref.pool_points(n_pool, seed, lb, ub, dtype))
+    assert np.array_equal(P, rad_ref.pool_points(n_pool, seed, lb, ub, dtype))
     return P
 
 

@@ -146,7 +146,7 @@ struct pinn_ctx {
   int adr_mask = 0;                  // PINN_PDE_ADR_IDE: bit k set = coefficient k is trained (pinn_set_pde_trainable)
 
   // host copies of the point sets (float64, as handed over)
-  std::vector<double> Xf, Xu, U, Xlo, Xhi;
+  PointSets sets;
   int64_t nf_total = 0, nu_total = 0, nb_total = 0;
   bool sets_dirty = true;
   SetDesc sd{};
@@ -232,14 +232,17 @@ struct pinn_ctx {
   unsigned int t16_bcount = 0;
   DevBuf<double> t16_gscr;             // k_t16_fused: tile-major weight-gradient scratch, one block per workgroup
 
-  // collocation set generated on the device (pinn_lhs_collocation) instead of handed over
-  struct { bool on = false; int64_t n_design = 0, first = 0, count = 0; uint64_t seed = 0; } lhs;
-  // collocation set drawn by residual-based adaptive sampling (pinn_rad_collocation, kernels_rad.h): the drawn points as a
-  // float64 device copy (cx, ct: ensure_sets re-places them after a re-assembly) and the call's own buffers -- pool points,
-  // their Taylor outputs and residuals, integer weights, block sums, totals -- so that no evaluation cache is disturbed
+  // Where the collocation block comes from: handed over (sets.Xf), generated on the device (pinn_lhs_collocation) or drawn
+  // by residual-based adaptive sampling (pinn_rad_collocation).  The two device origins take points first .. first + count - 1
+  // of an n_design-point design
+  enum ColFrom { COL_HANDED, COL_LHS, COL_RAD };
+  struct ColOrigin { ColFrom from = COL_HANDED; int64_t n_design = 0, first = 0, count = 0; } col;
+  struct { uint64_t seed = 0; } lhs;   // the device LHS's seed (kept when the origin changes: ens_to_k starts from it)
+  // the adaptive draw (kernels_rad.h): the drawn points as a float64 device copy (cx, ct: ensure_sets re-places them after a
+  // re-assembly) and the call's own buffers -- pool points, their Taylor outputs and residuals, integer weights, block sums,
+  // totals -- so that no evaluation cache is disturbed
   struct {
-    bool on = false, filled = false;
-    int64_t n_design = 0, first = 0, count = 0;
+    bool filled = false;
     DevBuf<double> cx, ct;
     DevBuf<void> px, pt, O;
     DevBuf<double> f;
@@ -431,9 +434,9 @@ static int src_fresh(const pinn_ctx* c, const char* who) {
                 "old points -- call pinn_set_source with values at the new points (pinn_get_collocation), or with n = 0", who);
   return 0;
 }
-// local collocation count as the next assembly will see it
+// local collocation count as the next assembly will see it: the one place that turns the origin into a count
 static int64_t n_colloc(const pinn_ctx* c) {
-  return c->lhs.on ? c->lhs.count : c->rad.on ? c->rad.count : (int64_t)(c->Xf.size() / 2);
+  return c->col.from == pinn_ctx::COL_HANDED ? (int64_t)(c->sets.Xf.size() / 2) : c->col.count;
 }
 
 // the fused kernel serves width-20 Burgers nets whose staged weights fit the 160 KiB LDS
@@ -566,17 +569,17 @@ static int upload_real(pinn_ctx* c, void* dst, const double* src, size_t n) {
 
 // device-side Latin hypercube: (re)writes the collocation slots of xs/ts in place (kernels_sampling.h)
 static int lhs_fill(pinn_ctx* c) {
-  const int64_t cnt = c->lhs.count;
+  const int64_t cnt = c->col.count;
   if (cnt <= 0) return 0;
-  const size_t off = (size_t)(2 * c->sd.n_b + c->sd.n_u);
-  const uint64_t n = (uint64_t)c->lhs.n_design;
+  const size_t off = (size_t)colloc_first(c->sd);
+  const uint64_t n = (uint64_t)c->col.n_design;
   const uint32_t lo = (uint32_t)c->lhs.seed, hi = (uint32_t)(c->lhs.seed >> 32);
+  const InMap<double> m(c->lb, c->ub);
   const dim3 grid((unsigned)((cnt + 255) / 256)), block(256);
   by_real(c, [&](auto r) {
     using real = decltype(r);
     hipLaunchKernelGGL((k_lhs_fill<real>), grid, block, 0, c->stream, c->xs.as<real>() + off, c->ts.as<real>() + off, cnt,
-                       (uint64_t)c->lhs.first, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
-                       c->ub[1] - c->lb[1]);
+                       (uint64_t)c->col.first, n, lhs_half_bits(n), lo, hi, m.lbx, m.lbt, m.ex, m.et);
   });
   HIPCHK(hipGetLastError());
   return 0;
@@ -585,63 +588,43 @@ static int lhs_fill(pinn_ctx* c) {
 // ------------------------------------------------------------------------------------------
 // training-set assembly: [boundary-lo | boundary-hi | data | collocation | pad]; the adr kind's Robin points, if any, are a
 // block of their own between the collocation block and the padding.  SetDesc does not count them (sd.n_all ends the
-// collocation block, as every kernel's point classes expect); sd.n_pad covers them
+// collocation block, as every kernel's point classes expect); sd.n_pad covers them.  pointsets.h builds the SetDesc and
+// assembles the set; the extras of this context are laid on top here
 // ------------------------------------------------------------------------------------------
 static int ensure_sets(pinn_ctx* c) {
   if (!c->sets_dirty) return 0;
-  const int n_b = (int)(c->Xlo.size() / 2), n_u = (int)(c->Xu.size() / 2),
-            n_f = c->lhs.on ? (int)c->lhs.count : c->rad.on ? (int)c->rad.count : (int)(c->Xf.size() / 2);
+  const PointSets& ps = c->sets;
+  const int n_b = (int)(ps.Xlo.size() / 2), n_u = (int)(ps.Xu.size() / 2), n_f = (int)n_colloc(c);
   const int NO = c->nd.n_out;
   if (c->pde == PINN_PDE_BURGERS_IDE)
     REQUIRE(n_f == 0, "identification evaluates the residual at the data points; no collocation set");
   if (c->pde != PINN_PDE_SCHRODINGER && !adr_family(c)) REQUIRE(n_b == 0, "boundary pairs are Schrodinger-only");
-  const int n_all = 2 * n_b + n_u + n_f;
-  REQUIRE(n_all > 0, "no training points set");
   const int n_w = is_adr(c) ? (int)(c->robin.X.size() / 2) : 0;
-  const int n_pad = (n_all + n_w + 63) / 64 * 64;
+  const SetDesc sd = make_set_desc(n_b, n_u, n_f, c->nb_total, c->nu_total, c->nf_total, n_w);
+  const int n_all = sd.n_all, n_pad = sd.n_pad;
+  REQUIRE(n_all > 0, "no training points set");
   REQUIRE(2 * n_b <= CHUNK_POINTS / 2, "too many boundary pairs for one chunk (%d)", n_b);
-  SetDesc sd{};
-  sd.n_b = n_b; sd.n_u = n_u; sd.n_f = n_f; sd.n_all = n_all; sd.n_pad = n_pad;
-  sd.inv_nb = c->nb_total > 0 ? 1.0 / (double)c->nb_total : 0.0;
-  sd.inv_nu = c->nu_total > 0 ? 1.0 / (double)c->nu_total : 0.0;
-  sd.inv_nf = c->nf_total > 0 ? 1.0 / (double)c->nf_total : 0.0;
   c->sd = sd;
 
-  std::vector<double> hx(n_pad), ht(n_pad), htg((size_t)NO * n_pad, 0.0);
-  int g = 0;
-  if (adr_family(c)) {      // pair-interleaved [lo_0, hi_0, lo_1, hi_1, ...] on every kernel path: the partner of point g is g ^ 1
-    for (int i = 0; i < n_b; ++i, g += 2) {
-      hx[g] = c->Xlo[2 * i]; ht[g] = c->Xlo[2 * i + 1];
-      hx[g + 1] = c->Xhi[2 * i]; ht[g + 1] = c->Xhi[2 * i + 1];
-    }
-  } else {
-    for (int i = 0; i < n_b; ++i, ++g) { hx[g] = c->Xlo[2 * i]; ht[g] = c->Xlo[2 * i + 1]; }
-    for (int i = 0; i < n_b; ++i, ++g) { hx[g] = c->Xhi[2 * i]; ht[g] = c->Xhi[2 * i + 1]; }
-  }
-  for (int i = 0; i < n_u; ++i, ++g) {
-    hx[g] = c->Xu[2 * i]; ht[g] = c->Xu[2 * i + 1];
-    for (int o = 0; o < NO; ++o) htg[(size_t)o * n_pad + g] = c->U[(size_t)i * NO + o];
-  }
-  if (!c->lhs.on && !c->rad.on)
-    for (int i = 0; i < n_f; ++i, ++g) { hx[g] = c->Xf[2 * i]; ht[g] = c->Xf[2 * i + 1]; }
-  if (c->lhs.on || c->rad.on)                                      // filled on the device, below
-    for (int i = 0; i < n_f; ++i, ++g) { hx[g] = c->lb[0]; ht[g] = c->lb[1]; }
+  // the adr family's pairs stand interleaved on every kernel path; a device origin's slots are filled below
+  const bool on_device = c->col.from != pinn_ctx::COL_HANDED;
+  std::vector<double> hx(n_pad), ht(n_pad), htg((size_t)NO * n_pad);
+  assemble_set(ps, sd, NO, adr_family(c), on_device, c->lb, hx.data(), ht.data(), htg.data());
+  const size_t off = (size_t)colloc_first(sd);
   if (is_adr(c) && c->src.on && !c->src.stale) {                   // s_i rides in tgt at the collocation point's own index
     REQUIRE((int)c->src.s.size() == n_f, "the source term holds %lld values, the collocation set %d points",
             (long long)c->src.s.size(), n_f);
-    for (int i = 0; i < n_f; ++i) htg[(size_t)(2 * n_b + n_u) + i] = c->src.s[i];
+    for (int i = 0; i < n_f; ++i) htg[off + i] = c->src.s[i];
   }
   if (is_adr(c) && c->kf.on && !c->kf.stale)
     REQUIRE((int)(c->kf.K.size() / 6) == n_f, "the coefficient fields hold %lld rows, the collocation set %d points",
             (long long)(c->kf.K.size() / 6), n_f);
-  c->robin.first = n_all; c->robin.n = n_w;
-  for (int j = 0; j < n_w; ++j, ++g) {                             // g_j rides in tgt at the point's own index
+  c->robin.first = robin_first(sd); c->robin.n = n_w;
+  for (int j = 0, g = robin_first(sd); j < n_w; ++j, ++g) {        // g_j rides in tgt at the point's own index
     hx[g] = c->robin.X[2 * j]; ht[g] = c->robin.X[2 * j + 1];
     htg[g] = c->robin.g[j];
   }
-  for (; g < n_pad; ++g) { hx[g] = c->lb[0]; ht[g] = c->lb[1]; }   // inert padding (zero seeds); LHS slots filled below
-  if (c->rad.on && c->rad.filled && n_f > 0) {                     // the last adaptive draw, kept through re-assemblies
-    const size_t off = (size_t)(2 * n_b + n_u);
+  if (c->col.from == pinn_ctx::COL_RAD && c->rad.filled && n_f > 0) {   // the last adaptive draw, kept through re-assemblies
     HIPCHK(hipMemcpyAsync(hx.data() + off, c->rad.cx, (size_t)n_f * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(ht.data() + off, c->rad.ct, (size_t)n_f * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -665,7 +648,7 @@ static int ensure_sets(pinn_ctx* c) {
     HIPCHK(c->kf.dev.reserve_bytes(c->kf.K.size() * rs));
     if (upload_real(c, c->kf.dev, c->kf.K.data(), c->kf.K.size())) return PINN_EHIP;
   }
-  if (c->lhs.on) { if (int rc = lhs_fill(c)) return rc; }
+  if (c->col.from == pinn_ctx::COL_LHS) { if (int rc = lhs_fill(c)) return rc; }
 
   c->chunk = n_pad < CHUNK_POINTS ? n_pad : CHUNK_POINTS;
   c->n_rows = c->chunk / 64;
@@ -871,13 +854,12 @@ static int t16_fwd(pinn_ctx* c, const void* xs, const void* ts, int n_pad, int c
 // plain forward sweep of one chunk for pinn_predict / pinn_residual: the MFMA sweep for nets wide enough to profit
 template <typename real>
 static int forward_chunk(pinn_ctx* c, const void* xs, const void* ts, int n_pad, int chunk, void* O, int base, int pts) {
-  const real lbx = (real)c->lb[0], lbt = (real)c->lb[1];
-  const real sx = (real)(2.0 / (c->ub[0] - c->lb[0])), st = (real)(2.0 / (c->ub[1] - c->lb[1]));
+  const InMap<real> m(c->lb, c->ub);
   if (tile16_ok(c) && c->nd.width >= 24)
-    return t16_fwd<real>(c, xs, ts, n_pad, chunk, O, base, pts, lbx, lbt, sx, st);
+    return t16_fwd<real>(c, xs, ts, n_pad, chunk, O, base, pts, m.lbx, m.lbt, m.sx, m.st);
   constexpr int JT = sizeof(real) == 4 ? 20 : 10;
   hipLaunchKernelGGL((k_forward<real, JT>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, c->theta_r.as<real>(),
-                     (const real*)xs, (const real*)ts, base, n_pad, chunk, lbx, lbt, sx, st, c->S.as<vec4<real>>(),
+                     (const real*)xs, (const real*)ts, base, n_pad, chunk, m.lbx, m.lbt, m.sx, m.st, c->S.as<vec4<real>>(),
                      (vec4<real>*)O);
   return 0;
 }
@@ -907,18 +889,10 @@ static int t16_fused_launch(pinn_ctx* c, const SetDesc& sd, int base, int pts, i
   return 0;
 }
 
-// the affine map of the inputs to [-1, 1] in the compute type
-template <typename real>
-struct InMap {
-  real lbx, lbt, sx, st;
-  explicit InMap(const pinn_ctx* c)
-      : lbx((real)c->lb[0]), lbt((real)c->lb[1]), sx((real)(2.0 / (c->ub[0] - c->lb[0]))), st((real)(2.0 / (c->ub[1] - c->lb[1]))) {}
-};
-
 // what every k_fused20d launch of context c takes (fused20d_api.h): the solo plan on c's set and weights.  An ensemble
 // overrides the weights, the rows, the member count and, with per-member sets, the points.
 static F20dLaunch fused20d_args(const pinn_ctx* c, hipEvent_t* ev4) {
-  const InMap<double> m(c);
+  const InMap<double> m(c->lb, c->ub);
   return F20dLaunch{c->nd, c->sd, c->theta_r.as<double>(), c->xs.as<double>(), c->ts.as<double>(),
                     c->tgt.as<double>(), m.lbx, m.lbt, m.sx, m.st, c->part.as<double>(), c->R, c->n_wg, 1, c->row_index,
                     c->stream, c->stamps, ev4 ? ev4[0] : nullptr, ev4 ? ev4[1] : nullptr};
@@ -969,7 +943,7 @@ template <typename real, int PDE>
 static int launch_fused20m(pinn_ctx* c, hipEvent_t* ev4) {
   int rc = hipErrorInvalidValue;
   if constexpr (sizeof(real) == 4 && PDE != 2 && !pde_is_adr(PDE)) {
-    const InMap<float> m(c);
+    const InMap<float> m(c->lb, c->ub);
     hipEvent_t const e0 = ev4 ? ev4[0] : nullptr, e1 = ev4 ? ev4[1] : nullptr;
     if (c->nd.n_hidden == 8)
       rc = fused20m_launch<PDE, 8>(c->nd, c->sd, c->theta_r.as<float>(), c->img, c->xs.as<float>(),
@@ -989,7 +963,7 @@ template <typename real, int PDE>
 static int launch_fused20(pinn_ctx* c, hipEvent_t* ev4) {
   int rc = hipErrorInvalidValue;
   if constexpr (!pde_is_adr(PDE)) {
-    const InMap<real> m(c);
+    const InMap<real> m(c->lb, c->ub);
     rc = fused20_launch<real, PDE>(c->nd, c->sd, c->theta_r.as<real>(), c->xs.as<real>(), c->ts.as<real>(),
                                    c->tgt.as<real>(), m.lbx, m.lbt, m.sx, m.st, (real)c->nu, c->S.as<vec4<real>>(),
                                    c->part.as<real>(), c->R, c->stream, c->stamps, ev4 ? ev4[0] : nullptr,
@@ -1097,7 +1071,7 @@ static int chunk_bwd(pinn_ctx* c, const InMap<real>& m, int base, int pts, int a
 // the chunked paths: chunk after chunk on the stream, the first chunk's rows written, the later ones' added
 template <typename real, int PDE>
 static int launch_chunks(pinn_ctx* c, hipEvent_t* ev4) {
-  const InMap<real> m(c);
+  const InMap<real> m(c->lb, c->ub);
   const int n_pad = c->sd.n_pad;
   for (int base = 0, ci = 0; base < n_pad; base += c->chunk, ++ci) {
     const int pts = (n_pad - base < c->chunk) ? n_pad - base : c->chunk;
@@ -1239,14 +1213,14 @@ static int disc_set_lds() {
 template <typename real, int NT>
 static int disc_eval(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   const DiscDesc dd = c->dd;
-  const real lbx = (real)c->lb[0], sx = (real)(2.0 / (c->ub[0] - c->lb[0]));
+  const InMap<real> m(c->lb, c->ub);
   const real c1 = real(1), c2 = (real)c->nu;
   if (int rc = disc_set_lds<real, NT>()) return rc;
   const dim3 grid(dd.n_groups, dd.n_chunks), block(256);
   const real* th = c->theta_r.as<real>();
   if (ev4) HIPCHK(hipEventRecord(ev4[0], c->stream));
   hipLaunchKernelGGL((k_disc_fwd<real, NT>), grid, block, disc_fwd_lds<NT>(sizeof(real)), c->stream, c->nd, dd, th,
-                     c->xs.as<real>(), lbx, sx, c1, c2, c->d_Ast.as<real>(), c->d_A3.as<real>(), c->d_U3.as<real>(),
+                     c->xs.as<real>(), m.lbx, m.sx, c1, c2, c->d_Ast.as<real>(), c->d_A3.as<real>(), c->d_U3.as<real>(),
                      c->d_Nn.as<real>(), 1);
   hipLaunchKernelGGL((k_disc_irk<real>), grid, block, 0, c->stream, dd, c->nd.n_out, c->d_ginfo,
                      c->d_MT[0].as<real>(), c->d_MT[1].as<real>(), c->d_Nn.as<real>(),
@@ -1257,7 +1231,7 @@ static int disc_eval(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
                      c->d_U3.as<real>(), c->d_A3.as<real>(), c1, c2, c->part.as<real>(), c->R, c->d_dAp.as<real>(),
                      c->d_lamp.as<real>());
   hipLaunchKernelGGL((k_disc_bwd_hidden<real, NT>), dim3(dd.n_groups), block, disc_hid_lds<NT>(sizeof(real)),
-                     c->stream, c->nd, dd, th, c->d_ginfo, c->xs.as<real>(), lbx, sx, c->d_Ast.as<real>(),
+                     c->stream, c->nd, dd, th, c->d_ginfo, c->xs.as<real>(), m.lbx, m.sx, c->d_Ast.as<real>(),
                      c->d_dAp.as<real>(), c->d_lossp.as<real>(), c->d_lamp.as<real>(), c->part.as<real>(), c->R);
   if (ev4) HIPCHK(hipEventRecord(ev4[2], c->stream));
   HIPCHK(hipGetLastError());
@@ -1308,12 +1282,12 @@ static int disc_predict_impl(pinn_ctx* c, int mode, int set, const double* x, in
   if (disc_alloc_scratch(c, dd, nullptr, nullptr, U3, Nn, Rb)) return PINN_EHIP;
   if (upload_real(c, xe, hx.data(), dd.n_pad)) return PINN_EHIP;
   if (hipMemcpy(ge, gi.data(), G * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return PINN_EHIP;
-  const real lbx = (real)c->lb[0], sx = (real)(2.0 / (c->ub[0] - c->lb[0]));
+  const InMap<real> m(c->lb, c->ub);
   const size_t lds_f = disc_fwd_lds<NT>(rs);
   if (int rc = disc_set_lds<real, NT>()) return rc;
   const dim3 grid(dd.n_groups, dd.n_chunks), block(256);
   hipLaunchKernelGGL((k_disc_fwd<real, NT>), grid, block, lds_f, c->stream, c->nd, dd, c->theta_r.as<real>(),
-                     xe.as<real>(), lbx, sx, real(1), (real)c->nu, (real*)nullptr, (real*)nullptr, U3.as<real>(),
+                     xe.as<real>(), m.lbx, m.sx, real(1), (real)c->nu, (real*)nullptr, (real*)nullptr, U3.as<real>(),
                      Nn.as<real>(), 0);
   if (mode == 1)
     hipLaunchKernelGGL((k_disc_irk<real>), grid, block, 0, c->stream, dd, NO, ge.get(), c->d_MT[0].as<real>(),
@@ -1460,19 +1434,20 @@ static int eval_points(pinn_ctx* c, const double* X, int64_t n, int* n_pad_out) 
 template <int NCH>
 static int predict20_launch(pinn_ctx* c, const void* xs, const void* ts, int n_pad, void* O4, double* out1) {
   const int n_tiles = n_pad / 64;
-  const double sx = 2.0 / (c->ub[0] - c->lb[0]), st = 2.0 / (c->ub[1] - c->lb[1]);
   if (c->dtype == PINN_F64) {
+    const InMap<double> m(c->lb, c->ub);
     const size_t lds = predict20_lds_bytes(c->nd, 8);
     const int wg = n_tiles < 4 * c->n_cu ? n_tiles : 4 * c->n_cu;
     hipLaunchKernelGGL((k_fwd20d<NCH>), dim3(wg), dim3(256), lds, c->stream, c->nd, c->theta_r.as<double>(),
-                       (const double*)xs, (const double*)ts, n_tiles, c->lb[0], c->lb[1], sx, st,
+                       (const double*)xs, (const double*)ts, n_tiles, m.lbx, m.lbt, m.sx, m.st,
                        (vec4<double>*)O4, out1);
   } else {
+    const InMap<float> m(c->lb, c->ub);                 // sx, st: (float) of the float64 quotient
     const size_t lds = predict20_lds_bytes(c->nd, 4);
     const int wg = n_tiles < 8 * c->n_cu ? n_tiles : 8 * c->n_cu;
     hipLaunchKernelGGL((k_fwd20f<NCH>), dim3(wg), dim3(64), lds, c->stream, c->nd, c->theta_r.as<float>(),
-                       (const float*)xs, (const float*)ts, n_tiles, (float)c->lb[0], (float)c->lb[1], (float)sx,
-                       (float)st, (vec4<float>*)O4, out1);
+                       (const float*)xs, (const float*)ts, n_tiles, m.lbx, m.lbt, m.sx, m.st,
+                       (vec4<float>*)O4, out1);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1559,12 +1534,13 @@ static int rad_alloc(pinn_ctx* c, int64_t count, int64_t M) {
   return 0;
 }
 
-// pool -> residuals -> integer weights -> CDF -> the rad.count samples from rad.first, into the collocation slots and the
+// pool -> residuals -> integer weights -> CDF -> the col.count samples from col.first, into the collocation slots and the
 // float64 copy.  Enqueues only.
 static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) {
-  const int64_t cnt = c->rad.count;
+  const int64_t cnt = c->col.count;
   if (cnt <= 0) return 0;
   const int NO = c->nd.n_out;
+  const InMap<double> m(c->lb, c->ub);
   const int n_pad = (int)((M + 63) / 64 * 64);
   const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
   const uint64_t n = (uint64_t)M;
@@ -1573,8 +1549,7 @@ static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) 
   by_real(c, [&](auto r) {
     using real = decltype(r);
     hipLaunchKernelGGL((k_lhs_fill<real>), grid_m, block, 0, c->stream, c->rad.px.as<real>(), c->rad.pt.as<real>(), M,
-                       (uint64_t)0, n, lhs_half_bits(n), lo, hi, c->lb[0], c->lb[1], c->ub[0] - c->lb[0],
-                       c->ub[1] - c->lb[1]);
+                       (uint64_t)0, n, lhs_half_bits(n), lo, hi, m.lbx, m.lbt, m.ex, m.et);
   });
   HIPCHK(hipGetLastError());
   // 2. residuals at the current weights: pinn_residual_at's forward sweep and k_residual
@@ -1588,13 +1563,13 @@ static int rad_draw(pinn_ctx* c, int64_t M, uint64_t seed, int k, double c_add) 
   hipLaunchKernelGGL(k_rad_scan, dim3(1), dim3(RAD_SCAN), 0, c->stream, c->rad.bsum, (int)grid_m.x, M, c_add, c->rad.tot);
   HIPCHK(hipGetLastError());
   // 5. the draw
-  const size_t off = (size_t)(2 * c->sd.n_b + c->sd.n_u);
+  const size_t off = (size_t)colloc_first(c->sd);
   const dim3 grid_s((unsigned)((cnt + 255) / 256)), block_s(256);
   by_real(c, [&](auto r) {
     using real = decltype(r);
     hipLaunchKernelGGL((k_rad_select<real>), grid_s, block_s, 0, c->stream, c->rad.px.as<real>(),
                        c->rad.pt.as<real>(), (const unsigned long long*)c->rad.w,
-                       (const unsigned long long*)c->rad.bsum, (const RadTotals*)c->rad.tot, M, (uint64_t)c->rad.first,
+                       (const unsigned long long*)c->rad.bsum, (const RadTotals*)c->rad.tot, M, (uint64_t)c->col.first,
                        cnt, lo, hi, c->xs.as<real>() + off, c->ts.as<real>() + off, c->rad.cx, c->rad.ct);
   });
   HIPCHK(hipGetLastError());
@@ -1679,6 +1654,23 @@ static void colloc_replaced(pinn_ctx* c) {
   if (c->src.on) c->src.stale = true;
   if (c->kf.on) c->kf.stale = true;
   c->sa.arr.reset[LAM_COL] = c->pw.arr.reset[LAM_COL] = true;
+}
+
+// what the three calls that take points first .. first + count - 1 of an n_design-point design ask of those numbers
+static int design_check(int64_t n_design, int64_t first, int64_t count) {
+  REQUIRE(n_design >= 1 && first >= 0 && count >= 0 && first + count <= n_design && count <= (1 << 30),
+          "bad design geometry (n_design %lld, first %lld, count %lld)", (long long)n_design, (long long)first,
+          (long long)count);
+  return 0;
+}
+
+// the collocation block now comes from a design on the device: no host points, the design's size as the global total
+static void colloc_from_design(pinn_ctx* c, pinn_ctx::ColFrom from, int64_t n_design, int64_t first, int64_t count) {
+  c->col = pinn_ctx::ColOrigin{from, n_design, first, count};
+  c->sets.Xf.clear();
+  c->nf_total = n_design;
+  c->sd.inv_nf = 1.0 / (double)n_design;
+  colloc_replaced(c);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1873,10 +1865,9 @@ int pinn_num_params(pinn_ctx* c, int64_t* n) {
 int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_total) {
   if (c && is_disc(c)) return fail(PINN_EINVAL, "pinn_set_collocation: discrete-time models take stage sets (pinn_disc_set_stage)");
   REQUIRE(c && (X_f || n == 0) && n >= 0 && n_total >= n, "bad collocation arguments");
-  c->Xf.assign(X_f, X_f + 2 * n);
+  c->sets.Xf.assign(X_f, X_f + 2 * n);
   c->nf_total = n_total;
-  c->lhs.on = false;
-  c->rad.on = false;
+  c->col = pinn_ctx::ColOrigin{};
   colloc_replaced(c);
   c->sets_dirty = true;
   return 0;
@@ -1885,17 +1876,11 @@ int pinn_set_collocation(pinn_ctx* c, const double* X_f, int64_t n, int64_t n_to
 int pinn_lhs_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t count, uint64_t seed) {
   REQUIRE(c, "null");
   REQUIRE(!is_disc(c) && c->pde != PINN_PDE_BURGERS_IDE, "pinn_lhs_collocation: this model has no collocation set");
-  REQUIRE(n_design >= 1 && first >= 0 && count >= 0 && first + count <= n_design && count <= (1 << 30),
-          "bad design geometry (n_design %lld, first %lld, count %lld)", (long long)n_design, (long long)first,
-          (long long)count);
+  if (int rc = design_check(n_design, first, count)) return rc;
   HIPCHK(hipSetDevice(c->device));
-  const bool same_shape = c->lhs.on && !c->sets_dirty && c->lhs.count == count;
-  colloc_replaced(c);                            // the fill writes xs and ts only
-  c->lhs.on = true; c->lhs.n_design = n_design; c->lhs.first = first; c->lhs.count = count; c->lhs.seed = seed;
-  c->rad.on = false;
-  c->Xf.clear();
-  c->nf_total = n_design;
-  c->sd.inv_nf = 1.0 / (double)n_design;
+  const bool same_shape = c->col.from == pinn_ctx::COL_LHS && !c->sets_dirty && c->col.count == count;
+  colloc_from_design(c, pinn_ctx::COL_LHS, n_design, first, count);   // (the fill writes xs and ts only)
+  c->lhs.seed = seed;
   if (same_shape) return lhs_fill(c);            // re-draw in place: one launch, nothing reallocated
   c->sets_dirty = true;
   return 0;
@@ -1906,9 +1891,7 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   REQUIRE(c, "null");
   if (is_disc(c) || c->pde == PINN_PDE_BURGERS_IDE)
     return fail(PINN_EUNSUPPORTED, "pinn_rad_collocation: this model has no collocation set");
-  REQUIRE(n_design >= 1 && first >= 0 && count >= 0 && first + count <= n_design && count <= (1 << 30),
-          "bad design geometry (n_design %lld, first %lld, count %lld)", (long long)n_design, (long long)first,
-          (long long)count);
+  if (int rc = design_check(n_design, first, count)) return rc;
   REQUIRE(n_pool >= 1 && n_pool <= RAD_POOL_MAX, "pinn_rad_collocation: n_pool %lld is outside 1..2^24", (long long)n_pool);
   if (c->src.on)                                  // refused first: the source is not made stale, the context stays usable
     return fail(PINN_EUNSUPPORTED, "pinn_rad_collocation: the adaptive draw is not combined with a source term -- the pool's "
@@ -1921,13 +1904,8 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   HIPCHK(hipSetDevice(c->device));
   // the slots stay where they are (same count, set assembled): the draw only enqueues, as an in-place LHS redraw does
   const bool in_place = !c->sets_dirty && c->sd.n_f == count;
-  if (int rc = rad_alloc(c, count, n_pool)) return rc;
-  c->lhs.on = false;
-  c->rad.on = true; c->rad.n_design = n_design; c->rad.first = first; c->rad.count = count;
-  colloc_replaced(c);                             // (no source and no fields here: refused above)
-  c->Xf.clear();
-  c->nf_total = n_design;
-  c->sd.inv_nf = 1.0 / (double)n_design;
+  if (int rc = rad_alloc(c, count, n_pool)) return rc;          // may fail before anything changes
+  colloc_from_design(c, pinn_ctx::COL_RAD, n_design, first, count);   // (no source and no fields here: refused above)
   if (!in_place) {
     c->rad.filled = false;
     c->sets_dirty = true;
@@ -1946,7 +1924,7 @@ int pinn_get_collocation(pinn_ctx* c, double* X, int64_t n) {
   if (rc) return rc;
   REQUIRE(n == c->sd.n_f, "buffer holds %lld points, the collocation set has %d", (long long)n, c->sd.n_f);
   if (n == 0) return 0;
-  const size_t off = (size_t)(2 * c->sd.n_b + c->sd.n_u), rs = real_size(c);
+  const size_t off = (size_t)colloc_first(c->sd), rs = real_size(c);
   std::vector<char> hx((size_t)n * rs), ht((size_t)n * rs);
   HIPCHK(hipMemcpyAsync(hx.data(), c->xs.as<char>() + off * rs, hx.size(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(ht.data(), c->ts.as<char>() + off * rs, ht.size(), hipMemcpyDeviceToHost, c->stream));
@@ -1961,8 +1939,8 @@ int pinn_get_collocation(pinn_ctx* c, double* X, int64_t n) {
 int pinn_set_data(pinn_ctx* c, const double* X_u, const double* u, int64_t n, int64_t n_total) {
   if (c && is_disc(c)) return fail(PINN_EINVAL, "pinn_set_data: discrete-time models take stage sets (pinn_disc_set_stage)");
   REQUIRE(c && ((X_u && u) || n == 0) && n >= 0 && n_total >= n, "bad data arguments");
-  c->Xu.assign(X_u, X_u + 2 * n);
-  c->U.assign(u, u + (size_t)c->nd.n_out * n);
+  c->sets.Xu.assign(X_u, X_u + 2 * n);
+  c->sets.U.assign(u, u + (size_t)c->nd.n_out * n);
   c->nu_total = n_total;
   c->sa.arr.reset[LAM_DATA] = c->pw.arr.reset[LAM_DATA] = true;
   c->sets_dirty = true;
@@ -1973,8 +1951,8 @@ int pinn_set_boundary(pinn_ctx* c, const double* X_lb, const double* X_ub, int64
   if (c && is_disc(c)) return fail(PINN_EINVAL, "pinn_set_boundary: discrete-time models take stage sets (pinn_disc_set_stage)");
   REQUIRE(c && ((X_lb && X_ub) || n == 0) && n >= 0 && n_total >= n, "bad boundary arguments");
   REQUIRE(c->pde == PINN_PDE_SCHRODINGER || adr_family(c) || n == 0, "boundary pairs are Schrodinger-only");
-  c->Xlo.assign(X_lb, X_lb + 2 * n);
-  c->Xhi.assign(X_ub, X_ub + 2 * n);
+  c->sets.Xlo.assign(X_lb, X_lb + 2 * n);
+  c->sets.Xhi.assign(X_ub, X_ub + 2 * n);
   c->nb_total = n_total;
   c->pw.arr.reset[LAM_PAIRS] = true;
   c->sets_dirty = true;
@@ -2047,7 +2025,7 @@ int pinn_set_source(pinn_ctx* c, const double* s, int64_t n) {
   // re-assembly; an in-place LHS redraw leaves the set in this state too
   const bool in_place = !c->sets_dirty && c->tgt && (n == 0 || c->sd.n_f == n);
   if (in_place && c->sd.n_f > 0) {
-    const size_t off = (size_t)(2 * c->sd.n_b + c->sd.n_u), rs = real_size(c);
+    const size_t off = (size_t)colloc_first(c->sd), rs = real_size(c);
     if (n == 0) {
       HIPCHK(hipMemsetAsync(c->tgt.as<char>() + off * rs, 0, (size_t)c->sd.n_f * rs, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
@@ -2722,7 +2700,7 @@ int pinn_residual(pinn_ctx* c, double* f, int64_t n) {
   if (rc) return rc;
   const SetDesc sd = c->sd;
   const bool ide = c->pde == PINN_PDE_BURGERS_IDE;
-  const int first = ide ? 2 * sd.n_b : 2 * sd.n_b + sd.n_u;
+  const int first = ide ? data_first(sd) : colloc_first(sd);
   const int cnt = ide ? sd.n_u : sd.n_f;
   REQUIRE(n == cnt, "residual buffer holds %lld points, the set has %d", (long long)n, cnt);
   if (cnt == 0) return 0;
@@ -3064,8 +3042,8 @@ int pinn_get_f64_split(pinn_ctx* c, int* split) {
 // ------------------------------------------------------------------------------------------
 // the local set sizes as ensure_sets will assemble them
 static void sa_counts(const pinn_ctx* c, int64_t* n_u, int64_t* n_f) {
-  *n_u = (int64_t)(c->Xu.size() / 2);
-  *n_f = c->lhs.on ? c->lhs.count : c->rad.on ? c->rad.count : (int64_t)(c->Xf.size() / 2);
+  *n_u = (int64_t)(c->sets.Xu.size() / 2);
+  *n_f = n_colloc(c);
 }
 
 int pinn_sa_set_weights(pinn_ctx* c, const double* lam_u, int64_t n_u, const double* lam_f, int64_t n_f) {
@@ -3129,7 +3107,7 @@ int pinn_sa_disable(pinn_ctx* c) {
 static int pw_check_counts(const pinn_ctx* c, const char* who, int64_t n_u, int64_t n_f, int64_t n_b) {
   int64_t cu, cf;
   sa_counts(c, &cu, &cf);
-  const int64_t cb = (int64_t)(c->Xlo.size() / 2);
+  const int64_t cb = (int64_t)(c->sets.Xlo.size() / 2);
   REQUIRE(n_u == cu && n_f == cf && n_b == cb,
           "%s: %lld / %lld / %lld weights for %lld data points, %lld collocation points and %lld boundary pairs", who,
           (long long)n_u, (long long)n_f, (long long)n_b, (long long)cu, (long long)cf, (long long)cb);
@@ -3213,21 +3191,21 @@ struct pinn_ens {
   DevBuf<unsigned long long> nonfinite;        // [K]
   DevBuf<double> part;                         // [K][n_wg][R]
   DevBuf<double> loss_hist;                    // Adam: [steps][K][3]
-  // per-member point sets and viscosities (pinn_ensk_*).  Off (shared mode) until the first per-member call; then the
-  // members' sets live here, member-major, while the base keeps member 0's, so that ensure_sets(base) still gives the
-  // SetDesc and the launch plan (every member has the same counts).  The shared setters broadcast in this mode.
+  // per-member point sets and viscosities (pinn_ensk_*).  Off (shared mode) until the first per-member call; then `sets`
+  // holds every member's sets as handed over (the adr kind: its periodic pairs too, one common n) WHILE THE BASE KEEPS
+  // MEMBER 0'S, so that ensure_sets(base) still gives the SetDesc and the launch plan (every member has the same counts).
+  // Hence every setter of this mode goes through the base's setter first -- a shared one with its argument, which it then
+  // broadcasts; a per-member one with its [K][n][..] argument, whose head is member 0's, which it then slices.
   bool k_mode = false, k_dirty = true, k_nu_dirty = true;
-  std::vector<double> kXf, kXu, kU;            // [K][n_f][2], [K][n_u][2], [K][n_u], as handed over
-  std::vector<uint64_t> k_seeds;               // [K] device LHS seeds (the design geometry is the base's lhs)
+  std::vector<PointSets> sets;                 // [K]
+  std::vector<uint64_t> k_seeds;               // [K] device LHS seeds (the design geometry is the base's col)
   std::vector<double> k_nu;                    // [K]
   DevBuf<double> k_xs, k_ts, k_tgt, k_nud;     // [K][n_pad] x 3, [K]
   // an ensemble of the adr kind (pinn_adr_ens_create): every member has its own six coefficients in BOTH modes -- the host
-  // rows [K][6] and the device table [K][ADR_ENS_ROW] k_fused20d<PDE_ADR_ENS> reads, there from creation and re-uploaded when dirty --
-  // and, in per-member mode, its own periodic pairs (one common n)
+  // rows [K][6] and the device table [K][ADR_ENS_ROW] k_fused20d<PDE_ADR_ENS> reads, there from creation and re-uploaded when dirty
   bool adr = false, coef_dirty = true;
   std::vector<double> coef;                    // [K][6]
   DevBuf<double> coef_d;                       // [K][ADR_ENS_ROW]
-  std::vector<double> kXlo, kXhi;              // [K][n_b][2]
 };
 
 // The order is the point: the members first (their views of the blocks die with them), then the blocks (`delete e`, on the
@@ -3245,14 +3223,7 @@ static void ens_to_k(pinn_ens* e) {
   if (e->k_mode) return;
   pinn_ctx* b = e->base;
   const size_t K = e->K;
-  e->kXf.clear(); e->kXu.clear(); e->kU.clear(); e->kXlo.clear(); e->kXhi.clear();
-  for (size_t k = 0; k < K; ++k) {
-    e->kXf.insert(e->kXf.end(), b->Xf.begin(), b->Xf.end());
-    e->kXu.insert(e->kXu.end(), b->Xu.begin(), b->Xu.end());
-    e->kU.insert(e->kU.end(), b->U.begin(), b->U.end());
-    e->kXlo.insert(e->kXlo.end(), b->Xlo.begin(), b->Xlo.end());      // (the adr kind's pairs; empty for Burgers)
-    e->kXhi.insert(e->kXhi.end(), b->Xhi.begin(), b->Xhi.end());
-  }
+  e->sets.assign(K, b->sets);
   e->k_seeds.assign(K, b->lhs.seed);
   e->k_nu.assign(K, b->nu);
   e->k_mode = true; e->k_dirty = true; e->k_nu_dirty = true;
@@ -3262,23 +3233,22 @@ static void ens_to_k(pinn_ens* e) {
 // design with seed k_seeds[k], each bit-identical to lhs_fill of a solo context with that seed
 static int ens_lhs_fill(pinn_ens* e) {
   pinn_ctx* b = e->base;
-  const int64_t cnt = b->lhs.count;
+  const int64_t cnt = b->col.count;
   if (cnt <= 0) return 0;
-  const size_t off = (size_t)(2 * b->sd.n_b + b->sd.n_u);      // off + cnt <= n_pad: inside member k's slice
-  const uint64_t n = (uint64_t)b->lhs.n_design;
+  const size_t off = (size_t)colloc_first(b->sd);             // off + cnt <= n_pad: inside member k's slice
+  const uint64_t n = (uint64_t)b->col.n_design;
+  const InMap<double> m(b->lb, b->ub);
   LhsSeeds sd{};
   for (int k = 0; k < e->K; ++k) { sd.lo[k] = (uint32_t)e->k_seeds[k]; sd.hi[k] = (uint32_t)(e->k_seeds[k] >> 32); }
   const dim3 grid((unsigned)((cnt + 255) / 256), (unsigned)e->K), block(256);
   hipLaunchKernelGGL(k_lhs_fill_ens, grid, block, 0, b->stream, e->k_xs + off, e->k_ts + off, (int64_t)b->sd.n_pad, cnt,
-                     (uint64_t)b->lhs.first, n, lhs_half_bits(n), sd, b->lb[0], b->lb[1], b->ub[0] - b->lb[0],
-                     b->ub[1] - b->lb[1]);
+                     (uint64_t)b->col.first, n, lhs_half_bits(n), sd, m.lbx, m.lbt, m.ex, m.et);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-// ensure_sets for the ensemble: the base's SetDesc and plan, then (per-member mode) the [K][n_pad] sets, assembled as
-// ensure_sets assembles one: [lo_0, hi_0, lo_1, hi_1, ... (the adr kind) | data | collocation | pad]; the adr kind's
-// coefficient table in both modes
+// ensure_sets for the ensemble: the base's SetDesc and plan, then (per-member mode) the [K][n_pad] sets, each member's slice
+// by the assembler that ensure_sets calls (one output: ens_check_shape); the adr kind's coefficient table in both modes
 static int ens_ensure_sets(pinn_ens* e) {
   pinn_ctx* b = e->base;
   if (b->sets_dirty) e->k_dirty = true;
@@ -3304,32 +3274,22 @@ static int ens_ensure_sets(pinn_ens* e) {
   }
   if (!e->k_dirty) return 0;
   const SetDesc& sd = b->sd;
-  const size_t n_pad = sd.n_pad, n_b = sd.n_b, n_u = sd.n_u, n_f = sd.n_f;
-  REQUIRE(e->kXlo.size() == K * 2 * n_b && e->kXhi.size() == K * 2 * n_b && e->kXu.size() == K * 2 * n_u &&
-          e->kU.size() == K * n_u && (b->lhs.on || e->kXf.size() == K * 2 * n_f),
-          "the members' point sets do not have the base's counts (%d pairs, %d data, %d collocation points)", sd.n_b, sd.n_u,
-          sd.n_f);
-  std::vector<double> hx(K * n_pad), ht(K * n_pad), htg(K * n_pad, 0.0);
+  const size_t n_pad = sd.n_pad;
+  const bool lhs = b->col.from == pinn_ctx::COL_LHS;            // the members' slots are filled below
+  std::vector<double> hx(K * n_pad), ht(K * n_pad), htg(K * n_pad);
   for (size_t k = 0; k < K; ++k) {
-    double *x = hx.data() + k * n_pad, *t = ht.data() + k * n_pad, *tg = htg.data() + k * n_pad;
-    const double *xu = e->kXu.data() + k * 2 * n_u, *u = e->kU.data() + k * n_u, *xf = e->kXf.data() + k * 2 * n_f;
-    const double *xlo = e->kXlo.data() + k * 2 * n_b, *xhi = e->kXhi.data() + k * 2 * n_b;
-    size_t g = 0;
-    for (size_t i = 0; i < n_b; ++i, g += 2) {   // the adr kind's pairs, interleaved as ensure_sets places them (Burgers: none)
-      x[g] = xlo[2 * i]; t[g] = xlo[2 * i + 1];
-      x[g + 1] = xhi[2 * i]; t[g + 1] = xhi[2 * i + 1];
-    }
-    for (size_t i = 0; i < n_u; ++i, ++g) { x[g] = xu[2 * i]; t[g] = xu[2 * i + 1]; tg[g] = u[i]; }
-    if (!b->lhs.on)
-      for (size_t i = 0; i < n_f; ++i, ++g) { x[g] = xf[2 * i]; t[g] = xf[2 * i + 1]; }
-    for (; g < n_pad; ++g) { x[g] = b->lb[0]; t[g] = b->lb[1]; }  // inert padding; LHS slots filled below
+    REQUIRE(has_counts(e->sets[k], sd, 1, lhs),
+            "the members' point sets do not have the base's counts (%d pairs, %d data, %d collocation points)", sd.n_b, sd.n_u,
+            sd.n_f);
+    assemble_set(e->sets[k], sd, 1, adr_family(b), lhs, b->lb, hx.data() + k * n_pad, ht.data() + k * n_pad,
+                 htg.data() + k * n_pad);
   }
   HIPCHK(e->k_xs.reserve(K * n_pad));
   HIPCHK(e->k_ts.reserve(K * n_pad));
   HIPCHK(e->k_tgt.reserve(K * n_pad));
   if (upload_real(b, e->k_xs, hx.data(), K * n_pad) || upload_real(b, e->k_ts, ht.data(), K * n_pad) ||
       upload_real(b, e->k_tgt, htg.data(), K * n_pad)) return PINN_EHIP;
-  if (b->lhs.on) { if (int rc = ens_lhs_fill(e)) return rc; }
+  if (lhs) { if (int rc = ens_lhs_fill(e)) return rc; }
   e->k_dirty = false;
   return 0;
 }
@@ -3477,11 +3437,7 @@ int pinn_ens_size(pinn_ens* e, int* n_members, int64_t* n_params) {
 int pinn_ens_set_collocation(pinn_ens* e, const double* X_f, int64_t n, int64_t n_total) {
   REQUIRE(e, "null");
   if (int rc = pinn_set_collocation(e->base, X_f, n, n_total)) return rc;
-  if (e->k_mode) {
-    e->kXf.clear();
-    for (int k = 0; k < e->K; ++k) e->kXf.insert(e->kXf.end(), X_f, X_f + 2 * n);
-    e->k_dirty = true;
-  }
+  if (e->k_mode) { broadcast_field(e->sets, &PointSets::Xf, X_f, 2 * n); e->k_dirty = true; }
   return 0;
 }
 
@@ -3489,8 +3445,8 @@ int pinn_ens_set_data(pinn_ens* e, const double* X_u, const double* u, int64_t n
   REQUIRE(e, "null");
   if (int rc = pinn_set_data(e->base, X_u, u, n, n_total)) return rc;
   if (e->k_mode) {
-    e->kXu.clear(); e->kU.clear();
-    for (int k = 0; k < e->K; ++k) { e->kXu.insert(e->kXu.end(), X_u, X_u + 2 * n); e->kU.insert(e->kU.end(), u, u + n); }
+    broadcast_field(e->sets, &PointSets::Xu, X_u, 2 * n);
+    broadcast_field(e->sets, &PointSets::U, u, n);
     e->k_dirty = true;
   }
   return 0;
@@ -3535,11 +3491,8 @@ int pinn_adr_ens_set_boundary(pinn_ens* e, const double* X_lb, const double* X_u
   if (!e->adr) return fail(PINN_EUNSUPPORTED, "pinn_adr_ens_set_boundary: boundary pairs are for ensembles of the adr kind (pinn_adr_ens_create)");
   if (int rc = pinn_set_boundary(e->base, X_lb, X_ub, n, n_total)) return rc;
   if (e->k_mode) {
-    e->kXlo.clear(); e->kXhi.clear();
-    for (int k = 0; k < e->K; ++k) {
-      e->kXlo.insert(e->kXlo.end(), X_lb, X_lb + 2 * n);
-      e->kXhi.insert(e->kXhi.end(), X_ub, X_ub + 2 * n);
-    }
+    broadcast_field(e->sets, &PointSets::Xlo, X_lb, 2 * n);
+    broadcast_field(e->sets, &PointSets::Xhi, X_ub, 2 * n);
     e->k_dirty = true;
   }
   return 0;
@@ -3555,8 +3508,8 @@ int pinn_ensk_set_collocation(pinn_ens* e, const double* X_f, int64_t n, int64_t
   REQUIRE(e->base->pde != PINN_PDE_BURGERS_IDE || n == 0,
           "identification evaluates the residual at the data points; no collocation set");
   ens_to_k(e);
-  if (int rc = pinn_set_collocation(e->base, X_f, n, n_total)) return rc;     // member 0's: the SetDesc and the plan
-  e->kXf.assign(X_f, X_f + (size_t)e->K * 2 * n);
+  if (int rc = pinn_set_collocation(e->base, X_f, n, n_total)) return rc;
+  slice_field(e->sets, &PointSets::Xf, X_f, 2 * n);
   e->k_dirty = true;
   return 0;
 }
@@ -3567,8 +3520,8 @@ int pinn_ensk_set_data(pinn_ens* e, const double* X_u, const double* u, int64_t 
           (long long)n_total);
   ens_to_k(e);
   if (int rc = pinn_set_data(e->base, X_u, u, n, n_total)) return rc;
-  e->kXu.assign(X_u, X_u + (size_t)e->K * 2 * n);
-  e->kU.assign(u, u + (size_t)e->K * n);
+  slice_field(e->sets, &PointSets::Xu, X_u, 2 * n);
+  slice_field(e->sets, &PointSets::U, u, n);
   e->k_dirty = true;
   return 0;
 }
@@ -3580,9 +3533,9 @@ int pinn_adr_ensk_set_boundary(pinn_ens* e, const double* X_lb, const double* X_
   REQUIRE(n >= 0 && 2 * n <= CHUNK_POINTS / 2 && n_total >= n, "bad boundary arguments (n %lld, n_total %lld)", (long long)n,
           (long long)n_total);
   ens_to_k(e);
-  if (int rc = pinn_set_boundary(e->base, X_lb, X_ub, n, n_total)) return rc;     // member 0's: the SetDesc and the plan
-  e->kXlo.assign(X_lb, X_lb + (size_t)e->K * 2 * n);
-  e->kXhi.assign(X_ub, X_ub + (size_t)e->K * 2 * n);
+  if (int rc = pinn_set_boundary(e->base, X_lb, X_ub, n, n_total)) return rc;
+  slice_field(e->sets, &PointSets::Xlo, X_lb, 2 * n);
+  slice_field(e->sets, &PointSets::Xhi, X_ub, 2 * n);
   e->k_dirty = true;
   return 0;
 }
@@ -3603,16 +3556,15 @@ int pinn_ensk_lhs_collocation(pinn_ens* e, int64_t n_design, int64_t first, int6
   REQUIRE(e && seeds, "null argument");
   pinn_ctx* b = e->base;
   REQUIRE(b->pde != PINN_PDE_BURGERS_IDE, "pinn_ensk_lhs_collocation: this model has no collocation set");
-  REQUIRE(n_design >= 1 && first >= 0 && count >= 0 && first + count <= n_design && count <= (1 << 30),
-          "bad design geometry (n_design %lld, first %lld, count %lld)", (long long)n_design, (long long)first,
-          (long long)count);
+  if (int rc = design_check(n_design, first, count)) return rc;
   HIPCHK(hipSetDevice(b->device));
   // re-draw in place (one launch, nothing rebuilt) when only the seeds change, as pinn_lhs_collocation does
-  const bool in_place = e->k_mode && !e->k_dirty && !b->sets_dirty && b->lhs.on && b->lhs.count == count;
+  const bool in_place = e->k_mode && !e->k_dirty && !b->sets_dirty && b->col.from == pinn_ctx::COL_LHS &&
+                        b->col.count == count;
   ens_to_k(e);
   if (int rc = pinn_lhs_collocation(b, n_design, first, count, seeds[0])) return rc;
   e->k_seeds.assign(seeds, seeds + e->K);
-  e->kXf.clear();
+  for (PointSets& ps : e->sets) ps.Xf.clear();
   if (in_place && !b->sets_dirty) return ens_lhs_fill(e);
   e->k_dirty = true;
   return 0;

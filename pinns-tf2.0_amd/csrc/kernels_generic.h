@@ -9,6 +9,7 @@
 // (1d-burgers/inf_cont_burgers.py:65-90, utils/neuralnetwork.py:55-59).
 #pragma once
 #include <type_traits>
+#include "pointsets.h"
 #include "wave.h"
 
 namespace pinn {
@@ -27,15 +28,7 @@ struct NetDesc {
   int img_kind;              // packed weight image kept by the optimiser kernels: 0 none, 1 k_fused20m, 2 wide
 };
 
-// Training-set geometry for one evaluation.  Points are stored in class order
-// [boundary-lo | boundary-hi | data | collocation | pad].  (PDE_ADR_ROBIN: a Robin block stands between the collocation block
-// and the padding; it is not counted here -- n_all ends the collocation block, n_pad covers the Robin block -- see AdrRobinArg.)
-struct SetDesc {
-  int n_b, n_u, n_f;         // local counts
-  int n_all;                 // 2*n_b + n_u + n_f
-  int n_pad;                 // rounded up to a multiple of 64
-  double inv_nb, inv_nu, inv_nf;   // 1 / GLOBAL set sizes (mean() denominators)
-};
+// (SetDesc, the training-set geometry every kernel takes, stands in pointsets.h)
 
 // Template number of the advection-diffusion-reaction kind (PINN_PDE_ADR = 5 of the C interface; the enum's 3 and 4 are the
 // discrete-time models of kernels_disc.h, which are no template values of the continuous kernels):

@@ -167,7 +167,11 @@ int pinn_adam_run_terms(pinn_ctx* c, int n_steps, double* terms3);
  *   n_logged: how many pairs were written;  done: 0 running, 1 maxIter reached, >1 break reason
  * The last-iteration quirk is reproduced: the model weights end at the last *evaluated* x.
  * pinn_lbfgs_begin only enqueues (it returns before the initial evaluation has run, except with the
- * mailbox exchange attached); pinn_lbfgs_run synchronises once, at its end, to read state and log. */
+ * mailbox exchange attached); pinn_lbfgs_run synchronises once, at its end, to read state and log.
+ * iters / losses hold n_iters entries, and that is tight: the call runs with nothing in flight, so every entry of earlier
+ * chunks has been handed out; the initial evaluation logs nothing; each of the call's iterations but the max_iter-th is
+ * followed by one evaluation, which logs one entry or ends the run (n_logged <= min(n_iters, iterations left), one less
+ * when the call issues the max_iter-th; a run that breaks nowhere logs exactly that). */
 int pinn_lbfgs_begin(pinn_ctx* c, int max_iter, double lr, int n_corr, double tol_fun,
                      double tol_x, double max_eval);
 int pinn_lbfgs_run(pinn_ctx* c, int n_iters, int* iters, double* losses, int* n_logged,
@@ -331,7 +335,8 @@ int pinn_ens_lbfgs_begin(pinn_ens* e, int n_corr, double tol_fun, double tol_x, 
                          const double* lr_k, int max_iter, const int* max_iter_k);
 /* up to n_iters iterations of every member that has not issued its max_iter yet (as pinn_lbfgs_run does per member; a
  * member whose run ended on the device stops moving while the others go on).  iters / losses [K][n_iters + 1] (may be
- * NULL): member k's log entries in row k, n_logged [K] of them; done [K] as pinn_lbfgs_run's done. */
+ * NULL): member k's log entries in row k, n_logged [K] <= n_iters of them (pinn_lbfgs_run's bound; the rows keep their
+ * length); done [K] as pinn_lbfgs_run's done. */
 int pinn_ens_lbfgs_run(pinn_ens* e, int n_iters, int* iters, double* losses, int* n_logged, int* done);
 /* out [K][n] (one output); err [K] = pinn_error_l2 kind 0 per member */
 int pinn_ens_predict(pinn_ens* e, const double* X, int64_t n, double* out);

@@ -19,6 +19,7 @@
 
 #include "../../include/pinn_hip.h"
 #include "devbuf.h"
+#include "optim_host.h"
 #include "kernels_fused20.h"
 #include "kernels_fused20m.h"
 #include "fused20d_api.h"
@@ -179,11 +180,13 @@ struct pinn_ctx {
   unsigned long long n_evals = 0;
 
   // Adam
-  double lr = 1e-3, b1 = 0.9, b2 = 0.999, eps = 1e-7;
-  int64_t adam_t = 0;
-  bool adam_ready = false, adam_want_terms = false;
-  DevBuf<double> loss_hist;          // N_PENDING regions of hist_stride steps x 3 loss parts (one per chunk in flight)
-  size_t hist_stride = 0;            // layout, not a guard: where a ticket's region starts; follows the ring when it is replaced
+  struct {
+    double lr = 1e-3, b1 = 0.9, b2 = 0.999, eps = 1e-7;
+    int64_t t = 0;
+    bool ready = false, want_terms = false;
+    DevBuf<double> loss_hist;        // N_PENDING regions of hist_stride steps x 3 loss parts (one per chunk in flight)
+    size_t hist_stride = 0;          // layout, not a guard: where a ticket's region starts; follows the ring when it is replaced
+  } adam;
 
   // Chunks of optimiser steps whose results the host has not collected yet (pinn_adam_enqueue / pinn_lbfgs_enqueue ->
   // ..._collect): the kernels of chunk k+1 are already in the stream while the host reads and logs chunk k, so a logging
@@ -202,27 +205,27 @@ struct pinn_ctx {
   static constexpr int N_SNAP = 4;     // pinn_weights_snapshot / _restore slots
   DevBuf<double> snap;
   unsigned snap_valid = 0;
-  static constexpr int N_PENDING = 4;
-  Pending pend[N_PENDING];
-  unsigned long long tickets_issued = 0, tickets_collected = 0;
-  int lb_issued_at_read = 0;           // lb_iters_issued when lb_logged_read was last brought up to date
+  struct : Tickets { Pending pend[N_PENDING]; } tk;   // the counters (optim_host.h) and the slots they index
 
   // L-BFGS
-  DevBuf<LbfgsState> lb_state;       // two copies (double buffered, see k_lbc_coef_apply); lb_flip = current
-  int lb_flip = 0;
-  DevBuf<double> lb_x, lb_d, lb_gold, lb_S, lb_Y, lb_ro, lb_al, lb_q, lb_log_loss;
-  DevBuf<int> lb_log_iter;
-  // (the host mirrors read back by pinn_lbfgs_run -- state + the log entries a chunk may have produced, three asynchronous
-  //  copies behind ONE wait; two blocking hipMemcpy more cost ~25 us per call -- are the Pending buffers above)
-  int lb_max_iter = 0, lb_ncorr = 0, lb_logged_read = 0;
-  double lb_lr = 1.0, lb_tol_fun = 0, lb_tol_x = 0, lb_max_eval = 0;
-  int lb_iters_issued = 0;
-  bool lb_post_pending = false;      // an evaluation whose break tests / log entry are still due
-  bool lb_ready = false;
-  // compact (Gram-matrix) mode
-  int lb_mode = 1, lb_mode_active = 0, lb_M1 = 0;
-  DevBuf<double> lb_SY, lb_YY, lb_dots, lb_cs, lb_cy;
-  DevBuf<LbcExtra> lb_ex;
+  struct {
+    int issued_at_read = 0;          // iters_issued when logged_read was last brought up to date
+    DevBuf<LbfgsState> state;        // two copies (double buffered, see k_lbc_coef_apply); flip = current
+    int flip = 0;
+    DevBuf<double> x, d, gold, S, Y, ro, al, q, log_loss;
+    DevBuf<int> log_iter;
+    // (the host mirrors read back by pinn_lbfgs_run -- state + the log entries a chunk may have produced, three asynchronous
+    //  copies behind ONE wait; two blocking hipMemcpy more cost ~25 us per call -- are the Pending buffers above)
+    int max_iter = 0, ncorr = 0, logged_read = 0;
+    double lr = 1.0, tol_fun = 0, tol_x = 0, max_eval = 0;
+    int iters_issued = 0;
+    bool post_pending = false;       // an evaluation whose break tests / log entry are still due
+    bool ready = false;
+    // compact (Gram-matrix) mode
+    int mode = 1, mode_active = 0, M1 = 0;
+    DevBuf<double> SY, YY, dots, cs, cy;
+    DevBuf<LbcExtra> ex;
+  } lbfgs;
   double t16_cost_full = T16_COST_FULL, t16_cost_strip = T16_COST_STRIP;   // k_t16_fused: weights of the gradient-tile dealing (t16_deal; PINN_T16_COSTS)
   long long t16_handover_ticks = 50000000ll;   // bound of that hand-over's wait, 100 MHz ticks (PINN_T16_HANDOVER_TICKS)
   bool t16_prepass_pinned = false;     // PINN_T16_PREPASS was given: the data-parallel default below does not apply
@@ -693,12 +696,12 @@ struct LamLayout {
 };
 // self-adaptive weights: Adam's constants; data and collocation points
 static LamLayout sa_layout(const pinn_ctx* c) {
-  return LamLayout{SA_CONST, {c->b1, c->b2, c->eps}, {0, c->sd.n_u, c->sd.n_f}};
+  return LamLayout{SA_CONST, {c->adam.b1, c->adam.b2, c->adam.eps}, {0, c->sd.n_u, c->sd.n_f}};
 }
 // adr point weights: the constants, then the ascent rate at 3 + point class (fused20d_api.h).  The pairs are stored
 // pair-interleaved, one entry per POINT: a pair counts twice
 static LamLayout pw_layout(const pinn_ctx* c) {
-  LamLayout L{PW_CONST, {c->b1, c->b2, c->eps}, {2 * c->sd.n_b, c->sd.n_u, c->sd.n_f}};
+  LamLayout L{PW_CONST, {c->adam.b1, c->adam.b2, c->adam.eps}, {2 * c->sd.n_b, c->sd.n_u, c->sd.n_f}};
   L.hdr[3 + CLS_BLO] = c->pw.rate[2]; L.hdr[3 + CLS_DATA] = c->pw.rate[0]; L.hdr[3 + CLS_COL] = c->pw.rate[1];
   return L;
 }
@@ -785,7 +788,7 @@ static int launch_reduce(pinn_ctx* c, int n_rows, const AdamFuse* af) {
     if (af)
       hipLaunchKernelGGL((k_reduce_xgmi<real, true>), xgrid, dim3(RED_THREADS), 0, c->stream, c->part.as<real>(),
                          n_rows, c->R, c->gl, c->xg.peers, seq, XG_TIMEOUT_TICKS, c->xg.err, c->nd.n_theta, c->theta,
-                         c->theta_r.as<real>(), c->adam_m, c->adam_v, af->alpha, c->b1, c->b2, c->eps, af->loss3, c->nd,
+                         c->theta_r.as<real>(), c->adam_m, c->adam_v, af->alpha, c->adam.b1, c->adam.b2, c->adam.eps, af->loss3, c->nd,
                          c->img, ts);
     else
       hipLaunchKernelGGL((k_reduce_xgmi<real, false>), xgrid, dim3(RED_THREADS), 0, c->stream, c->part.as<real>(),
@@ -798,7 +801,7 @@ static int launch_reduce(pinn_ctx* c, int n_rows, const AdamFuse* af) {
   if (af)
     hipLaunchKernelGGL((k_reduce_adam<real>), rgrid, dim3(RED_THREADS), 0, c->stream, c->part.as<real>(),
                        n_rows, c->R, c->gl, c->nd.n_theta, c->theta, c->theta_r.as<real>(), c->adam_m,
-                       c->adam_v, af->alpha, c->b1, c->b2, c->eps, af->loss3, c->nd, c->img, c->n_evals,
+                       c->adam_v, af->alpha, c->adam.b1, c->adam.b2, c->adam.eps, af->loss3, c->nd, c->img, c->n_evals,
                        c->d_nonfinite, ts);
   else
     hipLaunchKernelGGL((k_reduce_rows<real>), rgrid, dim3(RED_THREADS), 0, c->stream, c->part.as<real>(),
@@ -1849,7 +1852,7 @@ int pinn_destroy(pinn_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   if (c->comm) ncclCommDestroy(c->comm);
   xg_release(c);
-  for (auto& p : c->pend) if (p.ev) (void)hipEventDestroy(p.ev);
+  for (auto& p : c->tk.pend) if (p.ev) (void)hipEventDestroy(p.ev);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -2182,29 +2185,18 @@ int pinn_adam_init(pinn_ctx* c, double lr, double beta1, double beta2, double ep
   REQUIRE(c, "null");
   REQUIRE(lr > 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0, "bad Adam hyper-parameters");
   HIPCHK(hipSetDevice(c->device));
-  c->lr = lr; c->b1 = beta1; c->b2 = beta2; c->eps = eps; c->adam_t = 0;
+  c->adam.lr = lr; c->adam.b1 = beta1; c->adam.b2 = beta2; c->adam.eps = eps; c->adam.t = 0;
   HIPCHK(hipMemsetAsync(c->adam_m, 0, (size_t)c->nd.n_theta * 8, c->stream));
   HIPCHK(hipMemsetAsync(c->adam_v, 0, (size_t)c->nd.n_theta * 8, c->stream));
-  c->adam_ready = true;
+  c->adam.ready = true;
   return 0;
 }
 
 // ---- chunks in flight (see pinn_ctx::Pending) ----------------------------------------------------------------------
-static int pend_outstanding(const pinn_ctx* c) { return (int)(c->tickets_issued - c->tickets_collected); }
-
-// every chunk in flight is waited for and forgotten (its results are dropped): before anything that restarts an optimiser
-static int pend_drain(pinn_ctx* c) {
-  if (pend_outstanding(c) == 0) return 0;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->tickets_collected = c->tickets_issued;
-  return 0;
-}
-
 // the slot of the next ticket, with pinned room for n_loss doubles / n_iter ints (+ an L-BFGS state when asked)
 static int pend_reserve(pinn_ctx* c, int kind, size_t n_loss, size_t n_iter, bool want_state, pinn_ctx::Pending** out) {
-  REQUIRE(pend_outstanding(c) < pinn_ctx::N_PENDING, "%d chunks are in flight already: collect the oldest ticket first",
-          pinn_ctx::N_PENDING);
-  pinn_ctx::Pending& p = c->pend[c->tickets_issued % pinn_ctx::N_PENDING];
+  REQUIRE(c->tk.room(), "%d chunks are in flight already: collect the oldest ticket first", N_PENDING);
+  pinn_ctx::Pending& p = c->tk.pend[c->tk.next_slot()];
   if (!p.ev) HIPCHK(hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
   if (n_loss > 0) HIPCHK(p.h_loss.reserve(n_loss < 64 ? 64 : n_loss));      // at least 64 entries; nothing for none
   if (n_iter > 0) HIPCHK(p.h_iter.reserve(n_iter < 64 ? 64 : n_iter));
@@ -2214,73 +2206,88 @@ static int pend_reserve(pinn_ctx* c, int kind, size_t n_loss, size_t n_iter, boo
   return 0;
 }
 
+// the chunk in slot p is complete in the stream: its event, its number, the counter
+static int ticket_issue(pinn_ctx* c, pinn_ctx::Pending* p, int* ticket) {
+  HIPCHK(hipEventRecord(p->ev, c->stream));
+  if (ticket) *ticket = c->tk.next_number();
+  c->tk.issued += 1;
+  return 0;
+}
+
+// *pp = the chunk of `ticket`, which must be the oldest in flight and of `kind`, waited for and counted as collected
+static int ticket_oldest(pinn_ctx* c, int ticket, int kind, pinn_ctx::Pending** pp) {
+  REQUIRE(c, "null");
+  REQUIRE(c->tk.is_oldest(ticket),
+          "ticket %d is not the oldest chunk in flight (tickets are collected in the order they were issued)", ticket);
+  pinn_ctx::Pending& p = c->tk.pend[c->tk.oldest_slot()];
+  REQUIRE(p.kind == kind, kind == 1 ? "ticket %d belongs to an L-BFGS chunk" : "ticket %d belongs to an Adam chunk", ticket);
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipEventSynchronize(p.ev));
+  c->tk.collected += 1;
+  *pp = &p;
+  return 0;
+}
+
+// the next Adam step of c: its counter, and the bias correction every step size of that step is formed from
+static AdamFactors adam_step_factors(pinn_ctx* c) {
+  c->adam.t += 1;
+  return AdamFactors(c->adam.b1, c->adam.b2, (double)c->adam.t);
+}
+
 // n_steps Adam iterations into the stream.  record = false: nothing is kept (pinn_adam_run with losses == NULL).
 static int adam_issue(pinn_ctx* c, int n_steps, bool record, int* ticket) {
   REQUIRE(c && n_steps >= 0, "bad arguments");
   if (int rc0 = src_fresh(c, "pinn_adam_run / pinn_adam_enqueue")) return rc0;
-  REQUIRE(c->adam_ready, "pinn_adam_init has not been called");
+  REQUIRE(c->adam.ready, "pinn_adam_init has not been called");
   HIPCHK(hipSetDevice(c->device));
   const Range rg("pinn_adam_run");
   pinn_ctx::Pending* p = nullptr;
   double* region = nullptr;
   if (record) {
     if (int rc = pend_reserve(c, 1, (size_t)3 * (n_steps > 0 ? n_steps : 1), 0, false, &p)) return rc;
-    const size_t steps = n_steps < 16 ? 16 : n_steps;                  // at least 16 steps per region
-    if (steps * pinn_ctx::N_PENDING * 3 * 8 > c->loss_hist.capacity_bytes()) {
+    const size_t steps = ring_steps(n_steps);
+    if (ring_must_grow(steps, c->adam.loss_hist.capacity_bytes())) {
       // a larger ring: the chunks in flight finish first (their copies into the pinned buffers are then complete and the
       // tickets stay collectable), only then is the device ring replaced
-      if (pend_outstanding(c) > 0) HIPCHK(hipStreamSynchronize(c->stream));
-      HIPCHK(c->loss_hist.reserve(steps * pinn_ctx::N_PENDING * 3));
-      c->hist_stride = steps;
+      if (c->tk.outstanding() > 0) HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(c->adam.loss_hist.reserve(ring_doubles(steps)));
+      c->adam.hist_stride = steps;
     }
-    region = c->loss_hist + (size_t)(c->tickets_issued % pinn_ctx::N_PENDING) * c->hist_stride * 3;
-    p->n = n_steps;
-    p->want_terms = c->adam_want_terms;
+    region = c->adam.loss_hist + ring_region(c->tk, c->adam.hist_stride);
+    p->n = n_steps; p->want_terms = c->adam.want_terms;
   }
   const int n = c->nd.n_theta;
   for (int s = 0; s < n_steps; ++s) {
-    c->adam_t += 1;
-    const double t = (double)c->adam_t;
-    const double alpha = c->lr * std::sqrt(1.0 - std::pow(c->b2, t)) / (1.0 - std::pow(c->b1, t));
+    const AdamFactors bc = adam_step_factors(c);
+    const double alpha = bc.alpha(c->adam.lr);
     double* slot = region ? region + (size_t)3 * s : nullptr;
     if (!c->comm || c->xg.on) {                   // reduction (+ mailbox all-reduce) + update in one kernel
       AdamFuse af{alpha, slot};
       if (c->sa.on && c->sa.lr > 0.0)             // self-adaptive weights: the ascent, same counter, same form
-        af.alpha_sa = c->sa.lr * std::sqrt(1.0 - std::pow(c->b2, t)) / (1.0 - std::pow(c->b1, t));
+        af.alpha_sa = bc.alpha(c->sa.lr);
       if (c->pw.on && (c->pw.rate[0] > 0.0 || c->pw.rate[1] > 0.0 || c->pw.rate[2] > 0.0))   // adr point weights, likewise
-        af.bc_pw = std::sqrt(1.0 - std::pow(c->b2, t)) / (1.0 - std::pow(c->b1, t));
-      int rc = eval_loss_grad(c, &af);
-      if (rc) return rc;
+        af.bc_pw = bc.bc_pw();
+      if (int rc = eval_loss_grad(c, &af)) return rc;
       continue;
     }
-    int rc = eval_loss_grad(c);                   // reduce -> RCCL all-reduce -> update
-    if (rc) return rc;
+    if (int rc = eval_loss_grad(c)) return rc;    // reduce -> RCCL all-reduce -> update
     by_real(c, [&](auto r) {
       using real = decltype(r);
       hipLaunchKernelGGL((k_adam<real>), dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->gl, c->theta,
-                         c->theta_r.as<real>(), c->adam_m, c->adam_v, alpha, c->b1, c->b2, c->eps, slot, n, c->nd, c->img);
+                         c->theta_r.as<real>(), c->adam_m, c->adam_v, alpha, c->adam.b1, c->adam.b2, c->adam.eps, slot, n, c->nd,
+                         c->img);
     });
   }
   HIPCHK(hipGetLastError());
-  if (record) {
-    if (n_steps > 0)
-      HIPCHK(hipMemcpyAsync(p->h_loss, region, (size_t)3 * n_steps * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipEventRecord(p->ev, c->stream));
-    if (ticket) *ticket = (int)(c->tickets_issued & 0x7fffffff);
-    c->tickets_issued += 1;
-  }
-  return 0;
+  if (!record) return 0;
+  if (n_steps > 0) HIPCHK(hipMemcpyAsync(p->h_loss, region, (size_t)3 * n_steps * 8, hipMemcpyDeviceToHost, c->stream));
+  return ticket_issue(c, p, ticket);
 }
 
-static int adam_collect(pinn_ctx* c, int ticket, double* losses) {
-  REQUIRE(c, "null");
-  REQUIRE(pend_outstanding(c) > 0 && ticket == (int)(c->tickets_collected & 0x7fffffff),
-          "ticket %d is not the oldest chunk in flight (tickets are collected in the order they were issued)", ticket);
-  pinn_ctx::Pending& p = c->pend[c->tickets_collected % pinn_ctx::N_PENDING];
-  REQUIRE(p.kind == 1, "ticket %d belongs to an L-BFGS chunk", ticket);
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipEventSynchronize(p.ev));
-  c->tickets_collected += 1;
+int pinn_adam_collect(pinn_ctx* c, int ticket, double* losses) {
+  pinn_ctx::Pending* pp = nullptr;
+  if (int rc = ticket_oldest(c, ticket, 1, &pp)) return rc;
+  const pinn_ctx::Pending& p = *pp;
   if (int rc = xg_check(c)) return rc;          // a lost mailbox peer: the steps after it were not applied
   if (losses) {
     if (p.want_terms) memcpy(losses, p.h_loss, (size_t)3 * p.n * 8);
@@ -2293,10 +2300,10 @@ int pinn_adam_run(pinn_ctx* c, int n_steps, double* losses) {
   REQUIRE(c && n_steps >= 0, "bad arguments");
   if (n_steps == 0) return 0;
   if (!losses) return adam_issue(c, n_steps, false, nullptr);
-  REQUIRE(pend_outstanding(c) == 0, "pinn_adam_run: %d chunk(s) are in flight; collect them first", pend_outstanding(c));
+  REQUIRE(c->tk.outstanding() == 0, "pinn_adam_run: %d chunk(s) are in flight; collect them first", c->tk.outstanding());
   int ticket = 0;
   if (int rc = adam_issue(c, n_steps, true, &ticket)) return rc;
-  return adam_collect(c, ticket, losses);
+  return pinn_adam_collect(c, ticket, losses);
 }
 
 int pinn_adam_enqueue(pinn_ctx* c, int n_steps, int* ticket) {
@@ -2307,19 +2314,17 @@ int pinn_adam_enqueue(pinn_ctx* c, int n_steps, int* ticket) {
 // the chunk of pinn_adam_run_terms: pinn_adam_collect hands back 3 n values, (residual, data, boundary) before every update
 int pinn_adam_enqueue_terms(pinn_ctx* c, int n_steps, int* ticket) {
   REQUIRE(c && ticket && n_steps >= 1, "bad arguments");
-  c->adam_want_terms = true;
+  c->adam.want_terms = true;
   const int rc = adam_issue(c, n_steps, true, ticket);
-  c->adam_want_terms = false;
+  c->adam.want_terms = false;
   return rc;
 }
 
-int pinn_adam_collect(pinn_ctx* c, int ticket, double* losses) { return adam_collect(c, ticket, losses); }
-
 int pinn_adam_run_terms(pinn_ctx* c, int n_steps, double* terms3) {
   REQUIRE(c && terms3, "null");
-  c->adam_want_terms = true;
+  c->adam.want_terms = true;
   const int rc = pinn_adam_run(c, n_steps, terms3);
-  c->adam_want_terms = false;
+  c->adam.want_terms = false;
   return rc;
 }
 
@@ -2331,71 +2336,71 @@ static int lbfgs_begin_setup(pinn_ctx* c, int max_iter, double lr, int n_corr, d
   if (int rc0 = src_fresh(c, "pinn_lbfgs_begin")) return rc0;
   HIPCHK(hipSetDevice(c->device));
   const size_t n = c->nd.n_theta;
-  c->lb_max_iter = max_iter; c->lb_lr = lr; c->lb_ncorr = n_corr;
-  c->lb_tol_fun = tol_fun; c->lb_tol_x = tol_x;
-  c->lb_max_eval = max_eval > 0 ? max_eval : 1.25 * max_iter;     // custom_lbfgs.py:50
-  if (int rc = pend_drain(c)) return rc;                            // a restart: chunks still in flight are dropped
-  c->lb_iters_issued = 0; c->lb_logged_read = 0; c->lb_issued_at_read = 0; c->lb_post_pending = false;
-  c->lb_ready = false;
-  if (max_iter == 0) { c->lb_ready = true; return 0; }           // custom_lbfgs.py:43-44
-  HIPCHK(c->lb_state.reserve(2));                                   // (sizes of a context's lifetime: allocated once)
-  HIPCHK(c->lb_x.reserve(n));
-  HIPCHK(c->lb_d.reserve(n));
-  HIPCHK(c->lb_gold.reserve(n));
-  HIPCHK(c->lb_q.reserve(n));
-  const int M1 = n_corr + 1;                                       // ring slots (compact mode)
-  c->lb_M1 = M1;
+  auto& lb = c->lbfgs;
+  lb.max_iter = max_iter; lb.lr = lr; lb.ncorr = n_corr; lb.tol_fun = tol_fun; lb.tol_x = tol_x;
+  lb.max_eval = max_eval > 0 ? max_eval : 1.25 * max_iter;        // custom_lbfgs.py:50
+  if (c->tk.outstanding() > 0) {                                   // a restart: chunks still in flight are waited for and
+    HIPCHK(hipStreamSynchronize(c->stream));                       // forgotten (their results are dropped)
+    c->tk.drop_all();
+  }
+  lb.iters_issued = 0; lb.logged_read = 0; lb.issued_at_read = 0; lb.post_pending = false; lb.ready = false;
+  if (max_iter == 0) { lb.ready = true; return 0; }                // custom_lbfgs.py:43-44
+  const int M1 = lb.M1 = n_corr + 1;                               // ring slots (compact mode)
   // compact mode needs the two padded Gram matrices in LDS (<= 64 KiB) and one lane per slot
-  c->lb_mode_active = (c->lb_mode == 1 && M1 <= LBC_MAXSLOTS) ? 1 : 0;
-  if (c->lb_mode_active && lbc_coef_apply_lds_bytes(M1) > 64 * 1024) {
+  lb.mode_active = (lb.mode == 1 && M1 <= LBC_MAXSLOTS) ? 1 : 0;
+  if (lb.mode_active && lbc_coef_apply_lds_bytes(M1) > 64 * 1024) {
     const int lds = (int)lbc_coef_apply_lds_bytes(M1);
     HIPCHK(hipFuncSetAttribute((const void*)k_lbc_coef_apply<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     HIPCHK(hipFuncSetAttribute((const void*)k_lbc_coef_apply<double>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
-  HIPCHK(c->lb_S.reserve((size_t)M1 * ring_ld((int)n)));
-  HIPCHK(c->lb_Y.reserve((size_t)M1 * ring_ld((int)n)));
-  HIPCHK(c->lb_ro.reserve((size_t)2 * M1));
-  HIPCHK(c->lb_al.reserve((size_t)M1));
-  HIPCHK(c->lb_SY.reserve((size_t)2 * M1 * M1));
-  HIPCHK(c->lb_YY.reserve((size_t)2 * M1 * M1));
-  HIPCHK(c->lb_dots.reserve((size_t)2 * (5 * M1 + LBC_NSCAL)));
-  HIPCHK(c->lb_cs.reserve((size_t)M1));
-  HIPCHK(c->lb_cy.reserve((size_t)M1));
-  HIPCHK(c->lb_ex.reserve(1));
-  {  // unused ring slots must read as finite; Gram matrices, coefficients, dots and the extra record start at zero
-    static_assert(sizeof(LbcExtra) % 8 == 0, "LbcExtra is cleared as doubles");
-    ZeroList zl{};
-    auto add = [&](void* p, size_t doubles) { zl.p[zl.count] = (double*)p; zl.n[zl.count] = doubles; zl.count++; };
-    add(c->lb_S, (size_t)M1 * ring_ld((int)n)); add(c->lb_Y, (size_t)M1 * ring_ld((int)n)); add(c->lb_cs, M1); add(c->lb_cy, M1);
-    add(c->lb_SY, (size_t)2 * M1 * M1); add(c->lb_YY, (size_t)2 * M1 * M1); add(c->lb_ro, (size_t)2 * M1);
-    add(c->lb_dots, (size_t)2 * (5 * M1 + LBC_NSCAL)); add(c->lb_ex, sizeof(LbcExtra) / 8);
-    // the optimiser state starts as {0..., Hdiag = 1}: written by the same launch (no host buffer in flight)
-    static_assert(sizeof(LbfgsState) % 8 == 0 && offsetof(LbfgsState, Hdiag) % 8 == 0, "LbfgsState is initialised as doubles");
-    zl.state = (double*)c->lb_state.get(); zl.state_doubles = (int)(sizeof(LbfgsState) / 8);
-    zl.hdiag_index = (int)(offsetof(LbfgsState, Hdiag) / 8);
-    hipLaunchKernelGGL(k_zero_list, dim3(256), dim3(256), 0, c->stream, zl);
-    HIPCHK(hipGetLastError());
+  // (sizes of a context's lifetime: allocated once.)  zero: unused ring slots must read as finite; Gram matrices,
+  // coefficients, dots and the extra record start at zero
+  const size_t m1 = M1, ring = m1 * ring_ld((int)n), gram = 2 * m1 * m1, dots = 2 * (5 * m1 + LBC_NSCAL);
+  const struct { DevBuf<double>* buf; size_t count; bool zero; } bufs[] = {
+      {&lb.x, n, false},    {&lb.d, n, false},    {&lb.gold, n, false},  {&lb.q, n, false},     {&lb.al, m1, false},
+      {&lb.S, ring, true},  {&lb.Y, ring, true},  {&lb.cs, m1, true},    {&lb.cy, m1, true},    {&lb.SY, gram, true},
+      {&lb.YY, gram, true}, {&lb.ro, 2 * m1, true}, {&lb.dots, dots, true}};
+  static_assert(sizeof(LbcExtra) % 8 == 0, "LbcExtra is cleared as doubles");
+  ZeroList zl{};
+  auto add = [&](void* p, size_t doubles) { zl.p[zl.count] = (double*)p; zl.n[zl.count] = doubles; zl.count++; };
+  for (const auto& b : bufs) {
+    HIPCHK(b.buf->reserve(b.count));
+    if (b.zero) add(b.buf->get(), b.count);
   }
-  c->lb_flip = 0;
-  HIPCHK(c->lb_log_loss.reserve((size_t)max_iter + 1));
-  HIPCHK(c->lb_log_iter.reserve((size_t)max_iter + 1));
-  HIPCHK(hipMemcpyAsync(c->lb_x, c->theta, n * 8, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(lb.state.reserve(2));
+  HIPCHK(lb.ex.reserve(1));
+  add(lb.ex, sizeof(LbcExtra) / 8);
+  // the optimiser state starts as {0..., Hdiag = 1}: written by the same launch (no host buffer in flight)
+  static_assert(sizeof(LbfgsState) % 8 == 0 && offsetof(LbfgsState, Hdiag) % 8 == 0, "LbfgsState is initialised as doubles");
+  zl.state = (double*)lb.state.get(); zl.state_doubles = (int)(sizeof(LbfgsState) / 8);
+  zl.hdiag_index = (int)(offsetof(LbfgsState, Hdiag) / 8);
+  hipLaunchKernelGGL(k_zero_list, dim3(256), dim3(256), 0, c->stream, zl);
+  HIPCHK(hipGetLastError());
+  lb.flip = 0;
+  HIPCHK(lb.log_loss.reserve((size_t)max_iter + 1));
+  HIPCHK(lb.log_iter.reserve((size_t)max_iter + 1));
+  HIPCHK(hipMemcpyAsync(lb.x, c->theta, n * 8, hipMemcpyDeviceToDevice, c->stream));
   *eval = true;
   return 0;
 }
 
+// what follows an evaluation: its bookkeeping, break tests and log entry (initial = 1: pinn_lbfgs_begin's, :65-76)
+static void lbfgs_post(pinn_ctx* c, int initial) {
+  const auto& lb = c->lbfgs;
+  const int n = c->nd.n_theta;
+  hipLaunchKernelGGL(k_lbfgs_post, dim3(1), dim3(LB_THREADS), 0, c->stream, n, n, lb.max_iter, lb.max_eval, lb.tol_fun,
+                     lb.tol_x, lb.state + lb.flip, c->gl, lb.d, lb.log_iter, lb.log_loss, initial);
+}
+
 // pinn_lbfgs_begin behind the initial evaluation
 static int lbfgs_begin_post(pinn_ctx* c) {
-  const int n = c->nd.n_theta;
-  hipLaunchKernelGGL(k_lbfgs_post, dim3(1), dim3(LB_THREADS), 0, c->stream, n, n,
-                     c->lb_max_iter, c->lb_max_eval, c->lb_tol_fun, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_d,
-                     c->lb_log_iter, c->lb_log_loss, 1);
+  lbfgs_post(c, 1);
   HIPCHK(hipGetLastError());
   if (c->xg.on) {                                 // a lost mailbox peer in the first evaluation surfaces here
     HIPCHK(hipStreamSynchronize(c->stream));
     if (int rc2 = xg_check(c)) return rc2;
   }                                               // otherwise nothing is read back: pinn_lbfgs_run synchronises
-  c->lb_ready = true;
+  c->lbfgs.ready = true;
   return 0;
 }
 
@@ -2408,172 +2413,155 @@ int pinn_lbfgs_begin(pinn_ctx* c, int max_iter, double lr, int n_corr, double to
   return lbfgs_begin_post(c);
 }
 
-// up to n_iters iterations into the stream, then the state and the window of log entries they can have added on their way
-// to the chunk's pinned buffers
-//   lbfgs_open     the chunk's pending slot (*pp = nullptr: max_iter == 0, the ticket is issued already)
-//   lbfgs_iter     one iteration's step kernels; *eval: an evaluation follows (not behind the last iteration)
-//   lbfgs_behind   what follows that evaluation
-//   lbfgs_close    the state and log window to the chunk's pinned buffers, the ticket
-// (pieces, so that pinn_ens_lbfgs_run can put one evaluation of all its members between them)
-static int lbfgs_open(pinn_ctx* c, int n_iters, int* ticket, pinn_ctx::Pending** pp, int* window_out) {
-  *pp = nullptr;
+// ---- one chunk of L-BFGS iterations (pinn_lbfgs_run / _enqueue, pinn_ens_lbfgs_run) ----------------------------------------
+// a context's share of a chunk: its pending slot (nullptr: max_iter == 0, the ticket is issued already), its log window
+struct LbfgsMember { pinn_ctx* c; pinn_ctx::Pending* p; int window, ticket; };
+
+// the chunk's pending slot, with pinned room for the window of log entries the chunk can have added
+static int lbfgs_open(LbfgsMember& m, int n_iters) {
+  pinn_ctx* c = m.c;
   REQUIRE(c && n_iters >= 0, "bad arguments");
   if (int rc0 = src_fresh(c, "pinn_lbfgs_run / pinn_lbfgs_enqueue")) return rc0;
-  REQUIRE(c->lb_ready, "pinn_lbfgs_begin has not been called");
+  const auto& lb = c->lbfgs;
+  REQUIRE(lb.ready, "pinn_lbfgs_begin has not been called");
   HIPCHK(hipSetDevice(c->device));
   pinn_ctx::Pending* p = nullptr;
-  // one log entry per evaluation settled since the host last looked: the iterations issued since then, this chunk's, + 1
-  int window = (c->lb_iters_issued - c->lb_issued_at_read) + n_iters + 1;
-  const int log_room = (int)(c->lb_log_iter.capacity_bytes() / sizeof(int));   // entries the two log arrays hold
-  if (window > log_room - c->lb_logged_read) window = log_room - c->lb_logged_read;
-  if (window < 0 || c->lb_max_iter == 0) window = 0;
+  const int log_room = (int)(lb.log_iter.capacity_bytes() / sizeof(int));   // entries the two log arrays hold
+  const int window = lbfgs_window(lb.iters_issued, lb.issued_at_read, n_iters, log_room, lb.logged_read, lb.max_iter);
   if (int rc = pend_reserve(c, 2, (size_t)window + 1, (size_t)window + 1, true, &p)) return rc;
-  if (c->lb_max_iter == 0) {                                       // custom_lbfgs.py:43-44: nothing to do, done at once
-    p->n = -1;
-    HIPCHK(hipEventRecord(p->ev, c->stream));
-    if (ticket) *ticket = (int)(c->tickets_issued & 0x7fffffff);
-    c->tickets_issued += 1;
-    return 0;
-  }
-  *pp = p;
-  *window_out = window;
+  if (lb.max_iter == 0) { p->n = -1; return ticket_issue(c, p, &m.ticket); }   // custom_lbfgs.py:43-44: done at once
+  m.p = p; m.window = window;
   return 0;
 }
 
-static int lbfgs_iter(pinn_ctx* c, bool* eval) {
+// one iteration's step kernels; -> an evaluation follows (not behind the last iteration)
+static bool lbfgs_iter(pinn_ctx* c) {
+  auto& lb = c->lbfgs;
   const int n = c->nd.n_theta;
-  {
-    c->lb_iters_issued += 1;
-    if (c->lb_mode_active) {
-      const int M1 = c->lb_M1;
-      const size_t lsh = lbc_coef_apply_lds_bytes(M1);
-      LbfgsState* st_in = c->lb_state + c->lb_flip;
-      LbfgsState* st_out = c->lb_state + (c->lb_flip ^ 1);
-      const size_t mm = (size_t)M1 * M1;
-      // dot products of this iteration: already formed behind the evaluation's reduction (one partial set per
-      // 64-column tile; opt-in), or by k_lbc_dots (two half sets, one when n > 4096) -- also N > 1 ranks, the first
-      // iteration after pinn_lbfgs_begin, an evaluation issued by somebody else in between
-      int n_part;
-      if (n <= 2 * 2 * LBD_THREADS) {                 // two workgroups per ring slot, one pair stride each
-        hipLaunchKernelGGL(k_lbc_dots<2>, dim3(M1, 2), dim3(LBD_THREADS), 0, c->stream, n, M1, st_in,
-                           c->gl, c->lb_gold, c->lb_d, c->lb_S, c->lb_Y, c->lb_dots);
-        n_part = 2;
-      } else {
-        hipLaunchKernelGGL(k_lbc_dots<1>, dim3(M1), dim3(LBD_THREADS), 0, c->stream, n, M1, st_in,
-                           c->gl, c->lb_gold, c->lb_d, c->lb_S, c->lb_Y, c->lb_dots);
-        n_part = 1;
-      }
-      const double* pd = c->lb_dots;
-      const dim3 agrid((n + 63) / 64);
-      by_real(c, [&](auto r) {
-        using real = decltype(r);
-        hipLaunchKernelGGL((k_lbc_coef_apply<real>), agrid, dim3(LBC_THREADS), lsh, c->stream, n, M1,
-                           c->lb_ncorr, c->lb_max_iter, c->lb_lr, c->lb_tol_x, c->lb_tol_fun,
-                           c->lb_max_eval, c->lb_post_pending ? 1 : 0, n, st_in, st_out, c->gl,
-                           pd, n_part, c->lb_SY + c->lb_flip * mm, c->lb_YY + c->lb_flip * mm,
-                           c->lb_ro + c->lb_flip * M1, c->lb_SY + (c->lb_flip ^ 1) * mm,
-                           c->lb_YY + (c->lb_flip ^ 1) * mm, c->lb_ro + (c->lb_flip ^ 1) * M1,
-                           c->lb_log_iter, c->lb_log_loss, c->lb_S, c->lb_Y, c->lb_d, c->lb_gold,
-                           c->lb_x, c->theta, c->theta_r.as<real>(), c->nd, c->img);
-      });
-      c->lb_post_pending = false;
-      c->lb_flip ^= 1;
-    } else
-      by_real(c, [&](auto r) {
-        using real = decltype(r);
-        hipLaunchKernelGGL((k_lbfgs_step<real>), dim3(1), dim3(LB_THREADS), 0, c->stream, n, c->lb_max_iter, c->lb_ncorr,
-                           c->lb_lr, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_x, c->theta, c->theta_r.as<real>(),
-                           c->lb_d, c->lb_gold, c->lb_S, c->lb_Y, c->lb_ro, c->lb_al, c->lb_q, c->nd, c->img);
-      });
-    *eval = c->lb_iters_issued != c->lb_max_iter;                  // last iteration: no re-evaluation
-  }
-  return 0;
+  lb.iters_issued += 1;
+  if (lb.mode_active) {
+    const int M1 = lb.M1;
+    const size_t lsh = lbc_coef_apply_lds_bytes(M1), mm = (size_t)M1 * M1;
+    LbfgsState *st_in = lb.state + lb.flip, *st_out = lb.state + (lb.flip ^ 1);
+    // dot products of this iteration: already formed behind the evaluation's reduction (one partial set per
+    // 64-column tile; opt-in), or by k_lbc_dots (two half sets, one when n > 4096) -- also N > 1 ranks, the first
+    // iteration after pinn_lbfgs_begin, an evaluation issued by somebody else in between
+    const int n_part = n <= 2 * 2 * LBD_THREADS ? 2 : 1;   // two workgroups per ring slot, one pair stride each
+    if (n_part == 2)
+      hipLaunchKernelGGL(k_lbc_dots<2>, dim3(M1, 2), dim3(LBD_THREADS), 0, c->stream, n, M1, st_in, c->gl, lb.gold, lb.d,
+                         lb.S, lb.Y, lb.dots);
+    else
+      hipLaunchKernelGGL(k_lbc_dots<1>, dim3(M1), dim3(LBD_THREADS), 0, c->stream, n, M1, st_in, c->gl, lb.gold, lb.d,
+                         lb.S, lb.Y, lb.dots);
+    const double* pd = lb.dots;
+    const dim3 agrid((n + 63) / 64);
+    by_real(c, [&](auto r) {
+      using real = decltype(r);
+      hipLaunchKernelGGL((k_lbc_coef_apply<real>), agrid, dim3(LBC_THREADS), lsh, c->stream, n, M1, lb.ncorr, lb.max_iter,
+                         lb.lr, lb.tol_x, lb.tol_fun, lb.max_eval, lb.post_pending ? 1 : 0, n, st_in, st_out, c->gl, pd,
+                         n_part, lb.SY + lb.flip * mm, lb.YY + lb.flip * mm, lb.ro + lb.flip * M1,
+                         lb.SY + (lb.flip ^ 1) * mm, lb.YY + (lb.flip ^ 1) * mm, lb.ro + (lb.flip ^ 1) * M1, lb.log_iter,
+                         lb.log_loss, lb.S, lb.Y, lb.d, lb.gold, lb.x, c->theta, c->theta_r.as<real>(), c->nd, c->img);
+    });
+    lb.post_pending = false;
+    lb.flip ^= 1;
+  } else
+    by_real(c, [&](auto r) {
+      using real = decltype(r);
+      hipLaunchKernelGGL((k_lbfgs_step<real>), dim3(1), dim3(LB_THREADS), 0, c->stream, n, lb.max_iter, lb.ncorr,
+                         lb.lr, lb.tol_x, lb.state + lb.flip, c->gl, lb.x, c->theta, c->theta_r.as<real>(),
+                         lb.d, lb.gold, lb.S, lb.Y, lb.ro, lb.al, lb.q, c->nd, c->img);
+    });
+  return lb.iters_issued != lb.max_iter;                           // last iteration: no re-evaluation
 }
 
-static void lbfgs_behind(pinn_ctx* c) {
-  const int n = c->nd.n_theta;
-  if (c->lb_mode_active) { c->lb_post_pending = true; return; }   // folded into the next k_lbc_coef
-  hipLaunchKernelGGL(k_lbfgs_post, dim3(1), dim3(LB_THREADS), 0, c->stream, n, n, c->lb_max_iter,
-                     c->lb_max_eval, c->lb_tol_fun, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_d,
-                     c->lb_log_iter, c->lb_log_loss, 0);
-}
-
-static int lbfgs_close(pinn_ctx* c, pinn_ctx::Pending* p, int window, int* ticket) {
-  const int n = c->nd.n_theta;
-  if (c->lb_post_pending) {                       // the host is about to read the state: settle it
-    hipLaunchKernelGGL(k_lbfgs_post, dim3(1), dim3(LB_THREADS), 0, c->stream, n, n, c->lb_max_iter,
-                       c->lb_max_eval, c->lb_tol_fun, c->lb_tol_x, c->lb_state + c->lb_flip, c->gl, c->lb_d,
-                       c->lb_log_iter, c->lb_log_loss, 0);
-    c->lb_post_pending = false;
-  }
+// the state and the log window to the chunk's pinned buffers, the ticket
+static int lbfgs_close(LbfgsMember& m) {
+  pinn_ctx* c = m.c;
+  auto& lb = c->lbfgs;
+  pinn_ctx::Pending* p = m.p;
+  if (lb.post_pending) { lbfgs_post(c, 0); lb.post_pending = false; }   // the host is about to read the state: settle it
   HIPCHK(hipGetLastError());
-  p->n = window; p->base = c->lb_logged_read; p->issued_upto = c->lb_iters_issued;
-  HIPCHK(hipMemcpyAsync(p->h_state, c->lb_state + c->lb_flip, sizeof(LbfgsState), hipMemcpyDeviceToHost, c->stream));
-  if (window > 0) {
-    HIPCHK(hipMemcpyAsync(p->h_iter, c->lb_log_iter + p->base, (size_t)window * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(p->h_loss, c->lb_log_loss + p->base, (size_t)window * 8, hipMemcpyDeviceToHost, c->stream));
+  p->n = m.window; p->base = lb.logged_read; p->issued_upto = lb.iters_issued;
+  HIPCHK(hipMemcpyAsync(p->h_state, lb.state + lb.flip, sizeof(LbfgsState), hipMemcpyDeviceToHost, c->stream));
+  if (m.window > 0) {
+    HIPCHK(hipMemcpyAsync(p->h_iter, lb.log_iter + p->base, (size_t)m.window * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(p->h_loss, lb.log_loss + p->base, (size_t)m.window * 8, hipMemcpyDeviceToHost, c->stream));
   }
-  HIPCHK(hipEventRecord(p->ev, c->stream));
-  if (ticket) *ticket = (int)(c->tickets_issued & 0x7fffffff);
-  c->tickets_issued += 1;
+  return ticket_issue(c, p, &m.ticket);
+}
+
+// Up to n_iters iterations of K >= 1 contexts into the stream -- a context that has issued its max_iter stops moving while
+// the others go on -- then each one's state and log window on their way to its chunk's pinned buffers, and its ticket.
+// eval(act) evaluates loss and gradient of the contexts with act[k] set (K = 1: eval_loss_grad; an ensemble: one launch for
+// all its members).  Nothing is allocated here: m and act are the caller's.
+extern "C++" {
+template <typename Eval>
+static int lbfgs_chunk(LbfgsMember* m, char* act, int K, int n_iters, Eval&& eval) {
+  for (int k = 0; k < K; ++k)
+    if (int rc = lbfgs_open(m[k], n_iters)) return rc;
+  for (int s = 0; s < n_iters; ++s) {
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+      pinn_ctx* c = m[k].c;
+      act[k] = m[k].p && c->lbfgs.iters_issued < c->lbfgs.max_iter && lbfgs_iter(c);
+      any = any || act[k];
+    }
+    if (!any) break;
+    if (int rc = eval(act)) return rc;
+    for (int k = 0; k < K; ++k) {
+      if (!act[k]) continue;
+      if (m[k].c->lbfgs.mode_active) m[k].c->lbfgs.post_pending = true;   // folded into the next k_lbc_coef_apply
+      else lbfgs_post(m[k].c, 0);
+    }
+  }
+  for (int k = 0; k < K; ++k)
+    if (m[k].p) { if (int rc = lbfgs_close(m[k])) return rc; }
   return 0;
 }
+}  // extern "C++" (a template inside the API's extern "C" block)
 
 static int lbfgs_issue(pinn_ctx* c, int n_iters, int* ticket) {
   const Range rg("pinn_lbfgs_run");
-  pinn_ctx::Pending* p = nullptr;
-  int window = 0;
-  if (int rc = lbfgs_open(c, n_iters, ticket, &p, &window)) return rc;
-  if (!p) return 0;
-  for (int s = 0; s < n_iters && c->lb_iters_issued < c->lb_max_iter; ++s) {
-    bool eval = false;
-    if (int rc = lbfgs_iter(c, &eval)) return rc;
-    if (!eval) break;
-    if (int rc = eval_loss_grad(c)) return rc;
-    lbfgs_behind(c);
-  }
-  return lbfgs_close(c, p, window, ticket);
+  LbfgsMember m{c, nullptr, 0, 0};
+  char act = 0;
+  if (int rc = lbfgs_chunk(&m, &act, 1, n_iters, [c](const char*) { return eval_loss_grad(c); })) return rc;
+  *ticket = m.ticket;
+  return 0;
 }
 
-static int lbfgs_collect(pinn_ctx* c, int ticket, int cap, int* iters, double* losses, int* n_logged, int* done) {
-  REQUIRE(c, "null");
-  REQUIRE(pend_outstanding(c) > 0 && ticket == (int)(c->tickets_collected & 0x7fffffff),
-          "ticket %d is not the oldest chunk in flight (tickets are collected in the order they were issued)", ticket);
-  pinn_ctx::Pending& p = c->pend[c->tickets_collected % pinn_ctx::N_PENDING];
-  REQUIRE(p.kind == 2, "ticket %d belongs to an Adam chunk", ticket);
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipEventSynchronize(p.ev));
-  c->tickets_collected += 1;
+int pinn_lbfgs_collect(pinn_ctx* c, int ticket, int cap, int* iters, double* losses, int* n_logged, int* done) {
+  REQUIRE(cap >= 0, "bad arguments");
+  pinn_ctx::Pending* pp = nullptr;
+  if (int rc = ticket_oldest(c, ticket, 2, &pp)) return rc;
+  const pinn_ctx::Pending& p = *pp;
+  auto& lb = c->lbfgs;
   if (n_logged) *n_logged = 0;
   if (p.n < 0) { if (done) *done = 1; return 0; }
   if (int rc2 = xg_check(c)) return rc2;
   const LbfgsState hs = *p.h_state;
-  int fresh = hs.n_logged - c->lb_logged_read;
-  if (fresh < 0) fresh = 0;
-  REQUIRE(!(iters && losses) || fresh <= cap, "pinn_lbfgs_collect: %d log entries are due, the arrays hold %d", fresh, cap);
-  if (fresh > 0 && iters && losses) {
-    const int off = c->lb_logged_read - p.base;       // entries an earlier ticket has handed out already
-    if (off >= 0 && off + fresh <= p.n) {
-      memcpy(iters, p.h_iter + off, (size_t)fresh * 4);
-      memcpy(losses, p.h_loss + off, (size_t)fresh * 8);
-    } else {                                          // (cannot happen: kept as the general path)
-      HIPCHK(hipMemcpy(iters, c->lb_log_iter + c->lb_logged_read, (size_t)fresh * 4, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(losses, c->lb_log_loss + c->lb_logged_read, (size_t)fresh * 8, hipMemcpyDeviceToHost));
-    }
+  const LbfgsHandout h = lbfgs_handout(hs.n_logged, lb.logged_read, p.base, p.n);
+  REQUIRE(!(iters && losses) || h.fresh <= cap, "pinn_lbfgs_collect: %d log entries are due, the arrays hold %d", h.fresh, cap);
+  if (h.fresh > 0 && iters && losses) {
+    if (!h.inside)    // (never, over every chunking: tests/host/optim_host_check.cpp -- an invariant, so no device call here)
+      return fail(PINN_ESTATE, "pinn_lbfgs_collect: log entries from %d on lie outside the chunk's window of %d", h.off, p.n);
+    memcpy(iters, p.h_iter + h.off, (size_t)h.fresh * 4);
+    memcpy(losses, p.h_loss + h.off, (size_t)h.fresh * 8);
   }
-  c->lb_logged_read = hs.n_logged;
-  c->lb_issued_at_read = p.issued_upto;
-  if (n_logged) *n_logged = (iters && losses) ? fresh : 0;
+  lb.logged_read = hs.n_logged;
+  lb.issued_at_read = p.issued_upto;
+  if (n_logged) *n_logged = (iters && losses) ? h.fresh : 0;
   if (done) *done = hs.done;
   return 0;
 }
 
+// (the arrays hold n_iters entries: the tight bound with nothing in flight, include/pinn_hip.h)
 int pinn_lbfgs_run(pinn_ctx* c, int n_iters, int* iters, double* losses, int* n_logged, int* done) {
   REQUIRE(c && n_iters >= 0, "bad arguments");
-  REQUIRE(pend_outstanding(c) == 0, "pinn_lbfgs_run: %d chunk(s) are in flight; collect them first", pend_outstanding(c));
+  REQUIRE(c->tk.outstanding() == 0, "pinn_lbfgs_run: %d chunk(s) are in flight; collect them first", c->tk.outstanding());
   int ticket = 0;
   if (int rc = lbfgs_issue(c, n_iters, &ticket)) return rc;
-  return lbfgs_collect(c, ticket, n_iters + 1, iters, losses, n_logged, done);
+  return pinn_lbfgs_collect(c, ticket, n_iters, iters, losses, n_logged, done);
 }
 
 int pinn_lbfgs_enqueue(pinn_ctx* c, int n_iters, int* ticket) {
@@ -2581,24 +2569,19 @@ int pinn_lbfgs_enqueue(pinn_ctx* c, int n_iters, int* ticket) {
   return lbfgs_issue(c, n_iters, ticket);
 }
 
-int pinn_lbfgs_collect(pinn_ctx* c, int ticket, int cap, int* iters, double* losses, int* n_logged, int* done) {
-  REQUIRE(cap >= 0, "bad arguments");
-  return lbfgs_collect(c, ticket, cap, iters, losses, n_logged, done);
-}
-
 int pinn_lbfgs_set_mode(pinn_ctx* c, int mode) {
   REQUIRE(c && (mode == 0 || mode == 1), "mode must be 0 (reference operation order) or 1 (compact)");
-  c->lb_mode = mode;
+  c->lbfgs.mode = mode;
   return 0;
 }
 
 int pinn_lbfgs_get_x(pinn_ctx* c, double* x, int64_t n) {
   REQUIRE(c && x && n == c->nd.n_theta, "bad arguments");
-  REQUIRE(c->lb_x, "no L-BFGS run yet");
+  REQUIRE(c->lbfgs.x, "no L-BFGS run yet");
   HIPCHK(hipSetDevice(c->device));
   // in stream order, as pinn_get_weights: the context's stream is non-blocking, so a copy on the null stream would not wait
-  // for what pinn_lbfgs_begin or an enqueued chunk has still in flight (the copy of the start into lb_x, a step kernel)
-  HIPCHK(hipMemcpyAsync(x, c->lb_x, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  // for what pinn_lbfgs_begin or an enqueued chunk has still in flight (the copy of the start into lbfgs.x, a step kernel)
+  HIPCHK(hipMemcpyAsync(x, c->lbfgs.x, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -3322,7 +3305,7 @@ static int ens_eval(pinn_ens* e, const bool* active, const double* alpha, double
   pinn_ctx* c0 = e->mem[0];
   if (alpha)
     hipLaunchKernelGGL(k_reduce_adam_ens, grid, dim3(RED_THREADS), 0, b->stream, (const double*)e->part, n_rows, b->R,
-                       e->gl, e->P, e->sw, e->theta, e->theta_r, e->m, e->v, c0->b1, c0->b2, c0->eps, loss3, e->nonfinite,
+                       e->gl, e->P, e->sw, e->theta, e->theta_r, e->m, e->v, c0->adam.b1, c0->adam.b2, c0->adam.eps, loss3, e->nonfinite,
                        es);
   else
     hipLaunchKernelGGL(k_reduce_rows_ens, grid, dim3(RED_THREADS), 0, b->stream, (const double*)e->part, n_rows, b->R,
@@ -3619,7 +3602,7 @@ int pinn_ens_adam_init(pinn_ens* e, double lr, double beta1, double beta2, doubl
 
 int pinn_ens_adam_run(pinn_ens* e, int n_steps, double* losses) {
   REQUIRE(e && n_steps >= 0, "bad arguments");
-  for (pinn_ctx* c : e->mem) REQUIRE(c->adam_ready, "pinn_ens_adam_init has not been called");
+  for (pinn_ctx* c : e->mem) REQUIRE(c->adam.ready, "pinn_ens_adam_init has not been called");
   pinn_ctx* b = e->base;
   HIPCHK(hipSetDevice(b->device));
   if (n_steps == 0) return 0;
@@ -3628,12 +3611,8 @@ int pinn_ens_adam_run(pinn_ens* e, int n_steps, double* losses) {
   std::vector<char> all(K, 1);
   std::vector<double> alpha(K);
   for (int s = 0; s < n_steps; ++s) {
-    for (size_t k = 0; k < K; ++k) {             // the step size exactly as adam_issue forms it
-      pinn_ctx* c = e->mem[k];
-      c->adam_t += 1;
-      const double t = (double)c->adam_t;
-      alpha[k] = c->lr * std::sqrt(1.0 - std::pow(c->b2, t)) / (1.0 - std::pow(c->b1, t));
-    }
+    for (size_t k = 0; k < K; ++k)               // the step size from where adam_issue takes it
+      alpha[k] = adam_step_factors(e->mem[k]).alpha(e->mem[k]->adam.lr);
     if (int rc = ens_eval(e, (const bool*)all.data(), alpha.data(), e->loss_hist + (size_t)s * K * 3)) return rc;
   }
   std::vector<double> h((size_t)n_steps * K * 3);
@@ -3672,39 +3651,22 @@ int pinn_ens_lbfgs_begin(pinn_ens* e, int n_corr, double tol_fun, double tol_x, 
 int pinn_ens_lbfgs_run(pinn_ens* e, int n_iters, int* iters, double* losses, int* n_logged, int* done) {
   REQUIRE(e && n_iters >= 0, "bad arguments");
   for (pinn_ctx* c : e->mem) {
-    REQUIRE(c->lb_ready, "pinn_ens_lbfgs_begin has not been called");
-    REQUIRE(pend_outstanding(c) == 0, "chunks in flight");
+    REQUIRE(c->lbfgs.ready, "pinn_ens_lbfgs_begin has not been called");
+    REQUIRE(c->tk.outstanding() == 0, "chunks in flight");
   }
   HIPCHK(hipSetDevice(e->base->device));
   const Range rg("pinn_ens_lbfgs_run");
   const int K = e->K;
-  std::vector<pinn_ctx::Pending*> pend(K, nullptr);
-  std::vector<int> window(K, 0), ticket(K, 0);
-  for (int k = 0; k < K; ++k)
-    if (int rc = lbfgs_open(e->mem[k], n_iters, &ticket[k], &pend[k], &window[k])) return rc;
+  std::vector<LbfgsMember> m(K);
+  for (int k = 0; k < K; ++k) m[k].c = e->mem[k];
   std::vector<char> act(K, 0);
-  for (int s = 0; s < n_iters; ++s) {          // pinn_lbfgs_run's loop, member by member, one evaluation for all
-    bool any = false;
-    for (int k = 0; k < K; ++k) {
-      pinn_ctx* c = e->mem[k];
-      act[k] = 0;
-      if (!pend[k] || c->lb_iters_issued >= c->lb_max_iter) continue;
-      bool eval = false;
-      if (int rc = lbfgs_iter(c, &eval)) return rc;
-      act[k] = eval;
-      any = any || eval;
-    }
-    if (!any) break;
-    if (int rc = ens_eval(e, (const bool*)act.data(), nullptr, nullptr)) return rc;
-    for (int k = 0; k < K; ++k) if (act[k]) lbfgs_behind(e->mem[k]);
-  }
-  const int cap = n_iters + 1;
+  if (int rc = lbfgs_chunk(m.data(), act.data(), K, n_iters,       // pinn_lbfgs_run's chunk, one evaluation for all members
+                           [e](const char* a) { return ens_eval(e, (const bool*)a, nullptr, nullptr); })) return rc;
+  const int ld = n_iters + 1;                  // the rows of iters / losses (the ABI's); n_iters entries suffice, as solo
   for (int k = 0; k < K; ++k) {
-    pinn_ctx* c = e->mem[k];
-    if (pend[k]) { if (int rc = lbfgs_close(c, pend[k], window[k], &ticket[k])) return rc; }
     int nl = 0, dn = 0;
-    if (int rc = lbfgs_collect(c, ticket[k], cap, iters ? iters + (size_t)k * cap : nullptr,
-                               losses ? losses + (size_t)k * cap : nullptr, &nl, &dn)) return rc;
+    if (int rc = pinn_lbfgs_collect(m[k].c, m[k].ticket, n_iters, iters ? iters + (size_t)k * ld : nullptr,
+                               losses ? losses + (size_t)k * ld : nullptr, &nl, &dn)) return rc;
     if (n_logged) n_logged[k] = nl;
     if (done) done[k] = dn;
   }

@@ -17,7 +17,7 @@ _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _REPO = os.path.dirname(os.path.dirname(_HERE))
 LIB_PATH = os.environ.get("PINN_HIP_LIB") or os.path.join(_HERE, "libpinn_hip.so")
 SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_fused20d_kernel.h", "kernels_fused20d_reverse.h", "kernels_wide.h", "kernels_predict20.h",
-           "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h", "devbuf.h", "pointsets.h"]
+           "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h", "devbuf.h", "pointsets.h", "optim_host.h"]
 HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
 PDE_KINDS = {"burgers": 0, "burgers_ide": 1, "schrodinger": 2, "burgers_disc": 3, "burgers_disc_ide": 4, "adr": 5, "adr_ide": 6}
@@ -478,6 +478,8 @@ class Engine(object):
         self.n_f = self.n_u = self.n_b = self.n_w = 0
         self._has_source = False
         self._has_coef_fields = False
+        self._tickets = {}                # ticket -> its chunk's size (adam_enqueue / lbfgs_enqueue; negative: a terms chunk)
+        self._lb_uncollected = 0          # L-BFGS iterations enqueued and not collected yet
 
     def _check(self, rc):
         if rc != 0:
@@ -795,7 +797,6 @@ class Engine(object):
         t = ctypes.c_int(0)
         fn = self._lib.pinn_adam_enqueue_terms if terms else self._lib.pinn_adam_enqueue
         self._check(fn(self._h, int(n_steps), ctypes.byref(t)))
-        self._tickets = getattr(self, "_tickets", {})
         self._tickets[t.value] = -int(n_steps) if terms else int(n_steps)      # (negative: a terms chunk)
         return t.value
 
@@ -810,8 +811,7 @@ class Engine(object):
     def lbfgs_enqueue(self, n_iters):
         t = ctypes.c_int(0)
         self._check(self._lib.pinn_lbfgs_enqueue(self._h, int(n_iters), ctypes.byref(t)))
-        self._tickets = getattr(self, "_tickets", {})
-        self._lb_uncollected = getattr(self, "_lb_uncollected", 0) + int(n_iters)
+        self._lb_uncollected += int(n_iters)
         self._tickets[t.value] = int(n_iters)
         return t.value
 
@@ -847,7 +847,7 @@ class Engine(object):
         self._check(self._lib.pinn_lbfgs_set_mode(self._h, int(mode)))
 
     def lbfgs_run(self, n_iters):
-        cap = max(int(n_iters), 1)
+        cap = max(int(n_iters), 1)                # n_iters entries: the tight bound of the synchronous call (include/pinn_hip.h)
         iters = np.zeros(cap, dtype=np.int32)
         losses = np.zeros(cap, dtype=np.float64)
         n_logged, done = ctypes.c_int(0), ctypes.c_int(0)
@@ -1087,7 +1087,7 @@ class Ensemble(object):
 
     def lbfgs_run(self, n_iters):
         """-> (iters, losses, done): lists of K arrays of the log entries each member produced, done [K]"""
-        K, cap = self.n_members, int(n_iters) + 1
+        K, cap = self.n_members, int(n_iters) + 1     # the rows' length in the C API; at most n_iters entries come back, as solo
         iters = np.zeros((K, cap), dtype=np.int32)
         losses = np.zeros((K, cap), dtype=np.float64)
         n_logged, done = np.zeros(K, dtype=np.int32), np.zeros(K, dtype=np.int32)

@@ -54,7 +54,15 @@ enum {
    * data points over as collocation points for the usual identification loss).  Kernel paths 0 and 7 as PINN_PDE_ADR;
    * PINN_EUNSUPPORTED for the other paths, self-adaptive weights, ensembles and communicators.
    * (Additive: one enum value, two entry points; the ABI version stays 6.) */
-  PINN_PDE_ADR_IDE = 6
+  PINN_PDE_ADR_IDE = 6,
+  /* the discrete-time model of the adr operator: everything PINN_PDE_BURGERS_DISC is (layers[0] == 1, stage sets 0 and 1
+   * through pinn_disc_set_stage, a SUM of squares, pinn_predict / pinn_disc_predict, both optimisers), with
+   *     N(U) = (a0 + a1 U) U_x - nu U_xx + r1 U + r2 U^2 + r3 U^3
+   * on the first q outputs.  The six coefficients are those of PINN_PDE_ADR, set and read the same way
+   * (pinn_set_pde_params with n = 6; a new context holds Burgers', [0, 1, 0.01 / pi, 0, 0, 0]); they are fixed, not
+   * trained.  The one kind with periodic pairs, pinn_disc_set_periodic.  Every call that refuses the discrete-time kinds
+   * 3 and 4 refuses this one with the same code.  (Additive: one enum value, one entry point; the ABI version stays 6.) */
+  PINN_PDE_ADR_DISC = 7
 };
 enum { PINN_F32 = 0, PINN_F64 = 1 };
 enum {
@@ -114,7 +122,7 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
                          int k, double c_add);
 int pinn_set_boundary(pinn_ctx* c, const double* X_lb, const double* X_ub, int64_t n,
                       int64_t n_total);
-/* Discrete-time models (pde_kind 3, 4; layers[0] == 1, lb/ub hold one value each).  A stage set contributes
+/* Discrete-time models (pde_kind 3, 4, 7; layers[0] == 1, lb/ub hold one value each).  A stage set contributes
  *     sum_{p,j} ( U[p][j] + sum_k N(U)[p][k] M[j][k] - target[p] )^2        (a SUM, inf_disc_burgers.py:92-95)
  * to the loss, N acting on the first q outputs.  M is [n_out][q] row-major and already carries the step size
  * (dt * IRK_weights for U_0_model, inf_disc_burgers.py:89; dt * IRK_alpha and -dt * (IRK_beta - IRK_alpha) for
@@ -126,14 +134,22 @@ int pinn_disc_set_stage(pinn_ctx* c, int set, const double* x, const double* tar
 /* U_0_model / U_1_model at arbitrary points with the table of `set` (ide_disc_burgers.py:188-193):
  * out [n][n_out] = U + N(U) M^T.  pinn_predict returns the plain network outputs U [n][n_out]. */
 int pinn_disc_predict(pinn_ctx* c, int set, const double* x, int64_t n, double* out);
+/* Periodic pairs of PINN_PDE_ADR_DISC: n pairs, x_lb[i] with x_ub[i] (each [n]).  They add
+ *     sum_{i<n} sum_{j<n_out} (U_j(x_lb[i]) - U_j(x_ub[i]))^2   [+ (U_x,j(x_lb[i]) - U_x,j(x_ub[i]))^2 when order == 1]
+ * to the loss -- over ALL outputs, the stages and the solution at t_1 -- reported in terms[2] (terms[0] and terms[1] stay the
+ * two stage sets).  A third slot beside stage sets 0 and 1: any subset of the three may be present, at least one must be at
+ * the next evaluation.  n == 0 removes the pairs.  Refusals, the context unchanged: PINN_EUNSUPPORTED for any kind but
+ * PINN_PDE_ADR_DISC; PINN_EINVAL for order outside {0, 1}, a non-finite point, n outside 0..2^24.  (Additive: the ABI
+ * version stays 6.) */
+int pinn_disc_set_periodic(pinn_ctx* c, const double* x_lb, const double* x_ub, int64_t n, int order);
 
 /* get_params (inf_cont_burgers.py:92): p[0] = nu for PINN_PDE_BURGERS and PINN_PDE_BURGERS_DISC.
  * PINN_PDE_ADR: n must be 6, p = [a0, a1, nu, r1, r2, r3], all finite; otherwise PINN_EINVAL and the context keeps the
- * coefficients it had (a new context holds Burgers', [0, 1, 0.01 / pi, 0, 0, 0]).
+ * coefficients it had (a new context holds Burgers', [0, 1, 0.01 / pi, 0, 0, 0]).  PINN_PDE_ADR_DISC: the same.
  * PINN_PDE_ADR_IDE: n must be 6, RAW p = [a0, a1, nu, r1, r2, r3], all finite and nu > 0 (otherwise PINN_EINVAL, nothing
  * changed): written to the tail of the weight vector, log nu in the nu slot. */
 int pinn_set_pde_params(pinn_ctx* c, const double* p, int n);
-/* the current values: n = 6 raw coefficients for PINN_PDE_ADR and PINN_PDE_ADR_IDE (nu as exp of the stored log nu: what
+/* the current values: n = 6 raw coefficients for PINN_PDE_ADR, PINN_PDE_ADR_DISC and PINN_PDE_ADR_IDE (nu as exp of the stored log nu: what
  * training has made of them), n = 1 (nu) for every other kind */
 int pinn_get_pde_params(pinn_ctx* c, double* p, int n);
 /* PINN_PDE_ADR_IDE: bit k of mask set = coefficient k of (a0, a1, nu, r1, r2, r3) is trained; a new context trains none

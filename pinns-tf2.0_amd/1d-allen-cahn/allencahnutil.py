@@ -125,3 +125,35 @@ def plot_inf_cont_results(X_star, u_pred, X_u_train, Exact_u, x, t, save_path=No
     fig.colorbar(im)
     if save_path is not None and save_hp is not None:
         saveResultDir(save_path, save_hp, weights=weights)
+
+
+def plot_inf_disc_results(x_star, idx_t_0, idx_t_1, x_0, u_0, u_1_pred, Exact_u, x, t, save_path=None, save_hp=None,
+                          weights=None):
+    """Headless figure of the discrete-time script: the split-step field with the two time slices marked, the t_0 snapshot
+    with its data points, and the t_1 snapshot with the predicted last output column"""
+    import matplotlib
+    matplotlib.use("Agg")
+    fig, _ = newfig(1.0, 1.1)
+    fig.clf()
+    ax = fig.add_subplot(2, 1, 1)
+    im = ax.imshow(Exact_u.T, interpolation="nearest", cmap="rainbow", origin="lower", aspect="auto",
+                   extent=[t.min(), t.max(), x.min(), x.max()], vmin=-1.0, vmax=1.0)
+    fig.colorbar(im)
+    for idx in (idx_t_0, idx_t_1):
+        ax.axvline(float(t[idx, 0]), color="w", linewidth=1)
+    ax.set_xlabel("t")
+    ax.set_ylabel("x")
+    ax.set_title("u(t,x) split-step")
+    ax = fig.add_subplot(2, 2, 3)
+    ax.plot(x, Exact_u[idx_t_0, :], "b-", linewidth=2, label="Exact")
+    ax.plot(x_0, u_0, "rx", markersize=3, label="Data")
+    ax.set_title("t = %.2f" % float(t[idx_t_0, 0]))
+    ax.set_xlabel("x")
+    ax = fig.add_subplot(2, 2, 4)
+    ax.plot(x, Exact_u[idx_t_1, :], "b-", linewidth=2, label="Exact")
+    ax.plot(x_star, u_1_pred, "r--", linewidth=2, label="Prediction")
+    ax.set_title("t = %.2f" % float(t[idx_t_1, 0]))
+    ax.set_xlabel("x")
+    ax.legend(frameon=False, loc="best")
+    if save_path is not None and save_hp is not None:
+        saveResultDir(save_path, save_hp, weights=weights)

@@ -297,9 +297,12 @@ struct pinn_ctx {
     DevBuf<void> dev;
   } kf;
 
-  // discrete-time models (pde 3, 4): stage sets as handed over, device copies, scratch
+  // discrete-time models (pde 3, 4, 7): stage sets as handed over, device copies, scratch
   struct DiscSet { std::vector<double> x, t, M; int q = 0; bool has_M = false; };
   DiscSet dset[2];
+  // periodic pairs of the adr_disc kind (pinn_disc_set_periodic): row i of lb with row i of ub; a third slot beside the two
+  // stage sets, assembled by disc_ensure into groups of 8 pairs behind theirs
+  struct { std::vector<double> lb, ub; int order = 0; } dper;
   DiscDesc dd{};
   DevBuf<int> d_ginfo;
   DevBuf<void> d_M[2], d_MT[2];        // empty: that stage set has no table
@@ -340,7 +343,11 @@ __attribute__((always_inline)) static inline auto by_real(const pinn_ctx* c, F&&
   if (c->dtype == PINN_F64) return f(double());
   return f(float());
 }
-static bool is_disc(const pinn_ctx* c) { return c->pde == PINN_PDE_BURGERS_DISC || c->pde == PINN_PDE_BURGERS_DISC_IDE; }
+static bool disc_kind(int pde) { return pde == PINN_PDE_BURGERS_DISC || pde == PINN_PDE_BURGERS_DISC_IDE || pde == PINN_PDE_ADR_DISC; }
+static bool is_disc(const pinn_ctx* c) { return disc_kind(c->pde); }
+// the discrete-time model of the adr operator: template value DISC_ADR of the kernels of kernels_disc.h, six coefficients in
+// c->adr as for the adr kind, and the one kind with periodic pairs (pinn_disc_set_periodic)
+static bool is_adr_disc(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR_DISC; }
 static bool has_lambdas(int pde) { return pde == PINN_PDE_BURGERS_IDE || pde == PINN_PDE_BURGERS_DISC_IDE; }
 // advection-diffusion-reaction with run-time coefficients: template value PDE_ADR of the continuous kernels
 // (kernels_generic.h); it runs on the generic path 0 and, float64 width 20, on k_fused20d (path 7)
@@ -1156,19 +1163,21 @@ static int disc_alloc_scratch(pinn_ctx* c, const DiscDesc& dd, DevBuf<void>* Ast
 static int disc_ensure(pinn_ctx* c) {
   if (!c->sets_dirty) return 0;
   const int n0 = (int)c->dset[0].x.size(), n1 = (int)c->dset[1].x.size();
-  REQUIRE(n0 + n1 > 0, "no stage set given (pinn_disc_set_stage)");
+  const int np = is_adr_disc(c) ? (int)c->dper.lb.size() : 0;     // periodic pairs: any subset of the three slots may be present
+  REQUIRE(n0 + n1 + np > 0, "no stage set given (pinn_disc_set_stage)");
   int q = 0;
   for (int s = 0; s < 2; ++s)
     if (!c->dset[s].x.empty() && c->dset[s].has_M) {
       REQUIRE(q == 0 || q == c->dset[s].q, "the two stage sets use different q (%d vs %d)", q, c->dset[s].q);
       q = c->dset[s].q;
     }
-  const int G0 = (n0 + 15) / 16, G1 = (n1 + 15) / 16, G = G0 + G1;
+  const int G0 = (n0 + 15) / 16, G1 = (n1 + 15) / 16, Gp = (np + 7) / 8, G = G0 + G1 + Gp;
   DiscDesc dd{};
   disc_layout(c, dd, G, q);
   std::vector<double> hx(dd.n_pad, c->lb[0]), ht(dd.n_pad, 0.0);
   std::vector<int> gi(G);
-  for (int s = 0, g = 0; s < 2; ++s) {
+  int g = 0;
+  for (int s = 0; s < 2; ++s) {
     const std::vector<double>& x = c->dset[s].x;
     const int n = (int)x.size();
     for (int b = 0; b < n; b += 16, ++g) {
@@ -1176,6 +1185,14 @@ static int disc_ensure(pinn_ctx* c) {
       gi[g] = disc_ginfo(s, nv);
       for (int i = 0; i < nv; ++i) { hx[16 * g + i] = x[b + i]; ht[16 * g + i] = c->dset[s].t[b + i]; }
     }
+  }
+  // periodic groups behind the stage sets': rows 0..7 the lb points of up to 8 pairs, rows 8..15 their ub partners; the rows
+  // of a pair that is not there sit at the first lb point (inside the domain) and are masked by the pair count
+  for (int b = 0; b < np; b += 8, ++g) {
+    const int nv = np - b < 8 ? np - b : 8;
+    gi[g] = disc_ginfo_periodic(nv, c->dper.order);
+    for (int i = 0; i < 16; ++i) hx[16 * g + i] = c->dper.lb[0];
+    for (int i = 0; i < nv; ++i) { hx[16 * g + i] = c->dper.lb[b + i]; hx[16 * g + 8 + i] = c->dper.ub[b + i]; }
   }
   const size_t rs = real_size(c);
   HIPCHK(c->xs.reserve_bytes(dd.n_pad * rs));
@@ -1200,40 +1217,53 @@ static int disc_ensure(pinn_ctx* c) {
   return 0;
 }
 
-template <typename real, int NT>
+// the operator kind of a discrete-time context (template value DK of kernels_disc.h) and its coefficient block, by value:
+// (1, nu) for the Burgers kinds (identification reads its own from the weight vector), the six of c->adr for adr_disc with
+// the rows the periodic groups' slope differences travel in (the context's Nn, or none for a prediction)
+static int disc_dk(const pinn_ctx* c) { return is_adr_disc(c) ? DISC_ADR : DISC_BURGERS; }
+template <typename real, int DK>
+static disc_coef_t<real, DK> disc_coef(const pinn_ctx* c, const real* pair_dx) {
+  if constexpr (DK == DISC_ADR)
+    return DiscAdrArg<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5],
+                            pair_dx};
+  else
+    return DiscC12<real>{real(1), (real)c->nu};
+}
+
+template <typename real, int NT, int DK>
 static int disc_set_lds() {
   static unsigned long long done = 0;
   if (!first_call_on_device(done)) return 0;
-  HIPCHK(hipFuncSetAttribute((const void*)k_disc_fwd<real, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  HIPCHK(hipFuncSetAttribute((const void*)k_disc_fwd<real, NT, DK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)disc_fwd_lds<NT>(sizeof(real))));
-  HIPCHK(hipFuncSetAttribute((const void*)k_disc_bwd_out<real, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  HIPCHK(hipFuncSetAttribute((const void*)k_disc_bwd_out<real, NT, DK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)disc_out_lds<NT>(sizeof(real))));
-  HIPCHK(hipFuncSetAttribute((const void*)k_disc_bwd_hidden<real, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  HIPCHK(hipFuncSetAttribute((const void*)k_disc_bwd_hidden<real, NT, DK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)disc_hid_lds<NT>(sizeof(real))));
   return 0;
 }
 
-template <typename real, int NT>
+template <typename real, int NT, int DK>
 static int disc_eval(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   const DiscDesc dd = c->dd;
   const InMap<real> m(c->lb, c->ub);
-  const real c1 = real(1), c2 = (real)c->nu;
-  if (int rc = disc_set_lds<real, NT>()) return rc;
+  const disc_coef_t<real, DK> cf = disc_coef<real, DK>(c, c->d_Nn.as<real>());
+  if (int rc = disc_set_lds<real, NT, DK>()) return rc;
   const dim3 grid(dd.n_groups, dd.n_chunks), block(256);
   const real* th = c->theta_r.as<real>();
   if (ev4) HIPCHK(hipEventRecord(ev4[0], c->stream));
-  hipLaunchKernelGGL((k_disc_fwd<real, NT>), grid, block, disc_fwd_lds<NT>(sizeof(real)), c->stream, c->nd, dd, th,
-                     c->xs.as<real>(), m.lbx, m.sx, c1, c2, c->d_Ast.as<real>(), c->d_A3.as<real>(), c->d_U3.as<real>(),
+  hipLaunchKernelGGL((k_disc_fwd<real, NT, DK>), grid, block, disc_fwd_lds<NT>(sizeof(real)), c->stream, c->nd, dd, th,
+                     c->xs.as<real>(), m.lbx, m.sx, cf, c->d_Ast.as<real>(), c->d_A3.as<real>(), c->d_U3.as<real>(),
                      c->d_Nn.as<real>(), 1);
-  hipLaunchKernelGGL((k_disc_irk<real>), grid, block, 0, c->stream, dd, c->nd.n_out, c->d_ginfo,
+  hipLaunchKernelGGL((k_disc_irk<real, DK>), grid, block, 0, c->stream, dd, c->nd.n_out, c->d_ginfo,
                      c->d_MT[0].as<real>(), c->d_MT[1].as<real>(), c->d_Nn.as<real>(),
                      c->d_U3.as<real>(), c->tgt.as<real>(), c->d_R.as<real>(), c->d_lossp.as<real>(), 0);
   if (ev4) HIPCHK(hipEventRecord(ev4[1], c->stream));
-  hipLaunchKernelGGL((k_disc_bwd_out<real, NT>), grid, block, disc_out_lds<NT>(sizeof(real)), c->stream, c->nd, dd,
+  hipLaunchKernelGGL((k_disc_bwd_out<real, NT, DK>), grid, block, disc_out_lds<NT>(sizeof(real)), c->stream, c->nd, dd,
                      th, c->d_ginfo, c->d_M[0].as<real>(), c->d_M[1].as<real>(), c->d_R.as<real>(),
-                     c->d_U3.as<real>(), c->d_A3.as<real>(), c1, c2, c->part.as<real>(), c->R, c->d_dAp.as<real>(),
+                     c->d_U3.as<real>(), c->d_A3.as<real>(), cf, c->part.as<real>(), c->R, c->d_dAp.as<real>(),
                      c->d_lamp.as<real>());
-  hipLaunchKernelGGL((k_disc_bwd_hidden<real, NT>), dim3(dd.n_groups), block, disc_hid_lds<NT>(sizeof(real)),
+  hipLaunchKernelGGL((k_disc_bwd_hidden<real, NT, DK>), dim3(dd.n_groups), block, disc_hid_lds<NT>(sizeof(real)),
                      c->stream, c->nd, dd, th, c->d_ginfo, c->xs.as<real>(), m.lbx, m.sx, c->d_Ast.as<real>(),
                      c->d_dAp.as<real>(), c->d_lossp.as<real>(), c->d_lamp.as<real>(), c->part.as<real>(), c->R);
   if (ev4) HIPCHK(hipEventRecord(ev4[2], c->stream));
@@ -1241,9 +1271,13 @@ static int disc_eval(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   return launch_reduce<real>(c, dd.n_groups, af);
 }
 
+template <int DK>
+static int disc_eval_kind(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
+  if (c->dtype == PINN_F64) return disc_eval<double, 4, DK>(c, ev4, af);
+  return c->dd.wp == 64 ? disc_eval<float, 4, DK>(c, ev4, af) : disc_eval<float, 8, DK>(c, ev4, af);
+}
 static int disc_eval_any(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
-  if (c->dtype == PINN_F64) return disc_eval<double, 4>(c, ev4, af);
-  return c->dd.wp == 64 ? disc_eval<float, 4>(c, ev4, af) : disc_eval<float, 8>(c, ev4, af);
+  return disc_dk(c) == DISC_ADR ? disc_eval_kind<DISC_ADR>(c, ev4, af) : disc_eval_kind<DISC_BURGERS>(c, ev4, af);
 }
 
 static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
@@ -1268,7 +1302,7 @@ static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
 }
 
 // discrete-time models: network outputs (mode 0) or U + N(U) M^T with the table of `set` (mode 1) at n points
-template <typename real, int NT>
+template <typename real, int NT, int DK>
 static int disc_predict_impl(pinn_ctx* c, int mode, int set, const double* x, int64_t n, double* out) {
   const int NO = c->nd.n_out;
   const int G = (int)((n + 15) / 16);
@@ -1287,13 +1321,13 @@ static int disc_predict_impl(pinn_ctx* c, int mode, int set, const double* x, in
   if (hipMemcpy(ge, gi.data(), G * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return PINN_EHIP;
   const InMap<real> m(c->lb, c->ub);
   const size_t lds_f = disc_fwd_lds<NT>(rs);
-  if (int rc = disc_set_lds<real, NT>()) return rc;
+  if (int rc = disc_set_lds<real, NT, DK>()) return rc;
   const dim3 grid(dd.n_groups, dd.n_chunks), block(256);
-  hipLaunchKernelGGL((k_disc_fwd<real, NT>), grid, block, lds_f, c->stream, c->nd, dd, c->theta_r.as<real>(),
-                     xe.as<real>(), m.lbx, m.sx, real(1), (real)c->nu, (real*)nullptr, (real*)nullptr, U3.as<real>(),
-                     Nn.as<real>(), 0);
+  hipLaunchKernelGGL((k_disc_fwd<real, NT, DK>), grid, block, lds_f, c->stream, c->nd, dd, c->theta_r.as<real>(),
+                     xe.as<real>(), m.lbx, m.sx, disc_coef<real, DK>(c, nullptr), (real*)nullptr, (real*)nullptr,
+                     U3.as<real>(), Nn.as<real>(), 0);
   if (mode == 1)
-    hipLaunchKernelGGL((k_disc_irk<real>), grid, block, 0, c->stream, dd, NO, ge.get(), c->d_MT[0].as<real>(),
+    hipLaunchKernelGGL((k_disc_irk<real, DK>), grid, block, 0, c->stream, dd, NO, ge.get(), c->d_MT[0].as<real>(),
                        c->d_MT[1].as<real>(), Nn.as<real>(), U3.as<real>(), (const real*)nullptr, Rb.as<real>(),
                        (real*)nullptr, 1);
   std::vector<real> ho((size_t)dd.n_pad * dd.ldo);
@@ -1305,10 +1339,15 @@ static int disc_predict_impl(pinn_ctx* c, int mode, int set, const double* x, in
   return 0;
 }
 
+template <int DK>
+static int disc_predict_kind(pinn_ctx* c, int mode, int set, const double* x, int64_t n, double* out) {
+  if (c->dtype == PINN_F64) return disc_predict_impl<double, 4, DK>(c, mode, set, x, n, out);
+  return c->nd.width <= 64 ? disc_predict_impl<float, 4, DK>(c, mode, set, x, n, out)
+                           : disc_predict_impl<float, 8, DK>(c, mode, set, x, n, out);
+}
 static int disc_predict_any(pinn_ctx* c, int mode, int set, const double* x, int64_t n, double* out) {
-  if (c->dtype == PINN_F64) return disc_predict_impl<double, 4>(c, mode, set, x, n, out);
-  return c->nd.width <= 64 ? disc_predict_impl<float, 4>(c, mode, set, x, n, out)
-                           : disc_predict_impl<float, 8>(c, mode, set, x, n, out);
+  return disc_dk(c) == DISC_ADR ? disc_predict_kind<DISC_ADR>(c, mode, set, x, n, out)
+                                : disc_predict_kind<DISC_BURGERS>(c, mode, set, x, n, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1802,8 +1841,8 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   REQUIRE(out && layers && lb && ub, "null argument");
   REQUIRE(n_layers >= 3 && n_layers <= MAX_DENSE + 1, "need 3..%d layer sizes, got %d", MAX_DENSE + 1, n_layers);
   REQUIRE(dtype == PINN_F32 || dtype == PINN_F64, "dtype must be PINN_F32 or PINN_F64");
-  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADR_IDE, "unknown pde kind %d", pde_kind);
-  const bool disc = pde_kind == PINN_PDE_BURGERS_DISC || pde_kind == PINN_PDE_BURGERS_DISC_IDE;
+  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADR_DISC, "unknown pde kind %d", pde_kind);
+  const bool disc = disc_kind(pde_kind);
   if (disc) REQUIRE(layers[0] == 1, "discrete-time models take one input (x), got %d", layers[0]);
   else REQUIRE(layers[0] == 2, "input dimension must be 2 (x, t), got %d", layers[0]);
   const int W = layers[1], NO = layers[n_layers - 1];
@@ -1829,7 +1868,7 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   c->lb[0] = lb[0]; c->ub[0] = ub[0];
   if (disc) { c->lb[1] = 0.0; c->ub[1] = 1.0; } else { c->lb[1] = lb[1]; c->ub[1] = ub[1]; }
   c->nu = 0.01 / M_PI;
-  c->adr[1] = 1.0; c->adr[2] = c->nu;              // PINN_PDE_ADR starts as Burgers: [0, 1, nu, 0, 0, 0]
+  c->adr[1] = 1.0; c->adr[2] = c->nu;              // PINN_PDE_ADR and PINN_PDE_ADR_DISC start as Burgers: [0, 1, nu, 0, 0, 0]
   NetDesc& nd = c->nd;
   nd.n_hidden = n_layers - 2; nd.width = W; nd.n_out = NO;
   int off = 0;
@@ -2073,7 +2112,7 @@ int pinn_set_coef_fields(pinn_ctx* c, const double* K, int64_t n) {
 
 int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
   REQUIRE(c && p && n >= 1, "bad pde params");
-  if (is_adr(c)) {      // a0, a1, nu, r1, r2, r3; nothing changes on a refusal
+  if (is_adr(c) || is_adr_disc(c)) {      // a0, a1, nu, r1, r2, r3; nothing changes on a refusal
     REQUIRE(n == 6, "pinn_set_pde_params: the adr kind takes 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
     for (int i = 0; i < 6; ++i) REQUIRE(std::isfinite(p[i]), "pinn_set_pde_params: coefficient %d is not finite", i);
     for (int i = 0; i < 6; ++i) c->adr[i] = p[i];
@@ -2092,14 +2131,14 @@ int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
 
 int pinn_get_pde_params(pinn_ctx* c, double* p, int n) {
   REQUIRE(c && p, "null");
-  if (is_adr(c) || is_adr_ide(c)) REQUIRE(n == 6, "pinn_get_pde_params: this kind has 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
+  if (is_adr(c) || is_adr_ide(c) || is_adr_disc(c)) REQUIRE(n == 6, "pinn_get_pde_params: this kind has 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
   else REQUIRE(n == 1, "pinn_get_pde_params: this kind has 1 parameter (nu), got %d", n);
   if (is_adr_ide(c)) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(p, c->theta + c->nd.n_net, 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     p[2] = std::exp(p[2]);
-  } else if (is_adr(c)) {
+  } else if (is_adr(c) || is_adr_disc(c)) {
     for (int i = 0; i < 6; ++i) p[i] = c->adr[i];
   } else {
     p[0] = c->nu;
@@ -2659,6 +2698,22 @@ int pinn_disc_set_stage(pinn_ctx* c, int set, const double* x, const double* tar
   ds.has_M = M != nullptr && n > 0;
   ds.q = ds.has_M ? q : 0;
   if (ds.has_M) ds.M.assign(M, M + (size_t)c->nd.n_out * q); else ds.M.clear();
+  c->sets_dirty = true;
+  return 0;
+}
+
+int pinn_disc_set_periodic(pinn_ctx* c, const double* x_lb, const double* x_ub, int64_t n, int order) {
+  REQUIRE(c, "null");
+  if (!is_adr_disc(c))
+    return fail(PINN_EUNSUPPORTED, "pinn_disc_set_periodic: periodic pairs are for the adr_disc kind (pde 7) only");
+  REQUIRE(order == 0 || order == 1, "pinn_disc_set_periodic: order %d outside 0..1 (0: values, 1: values and slopes)", order);
+  REQUIRE(n >= 0 && n <= (1 << 24), "pinn_disc_set_periodic: bad pair count");
+  REQUIRE(n == 0 || (x_lb && x_ub), "pinn_disc_set_periodic: null argument");
+  for (int64_t i = 0; i < n; ++i)
+    REQUIRE(std::isfinite(x_lb[i]) && std::isfinite(x_ub[i]), "pinn_disc_set_periodic: pair %lld is not finite", (long long)i);
+  c->dper.lb.assign(x_lb, x_lb + n);
+  c->dper.ub.assign(x_ub, x_ub + n);
+  c->dper.order = order;
   c->sets_dirty = true;
   return 0;
 }

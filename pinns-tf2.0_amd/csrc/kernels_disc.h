@@ -1,6 +1,15 @@
-// kernels_disc.h -- discrete-time (implicit Runge-Kutta) Burgers models: 1-input tanh MLP with q(+1) outputs,
-// loss = sum over stage sets of || U + N(U) M^T - target ||^2 with N = c1 U U_x - c2 U_xx on the first q outputs
-// (reference: 1d-burgers/inf_disc_burgers.py:57-95, 1d-burgers/ide_disc_burgers.py:81-115).
+// kernels_disc.h -- discrete-time (implicit Runge-Kutta) models: 1-input tanh MLP with q(+1) outputs,
+// loss = sum over stage sets of || U + N(U) M^T - target ||^2, N acting on the first q outputs.  The operator is a
+// compile-time kind (DK) of every kernel here:
+//   DISC_BURGERS  N = c1 U U_x - c2 U_xx  (pde 3 and, with c1, c2 read from the weight vector, pde 4; reference:
+//                 1d-burgers/inf_disc_burgers.py:57-95, 1d-burgers/ide_disc_burgers.py:81-115)
+//   DISC_ADR      N = (a0 + a1 U) U_x - nu U_xx + r1 U + r2 U^2 + r3 U^3  (pde 7), six run-time coefficients by value, and
+//                 a third kind of group beside the two stage sets: periodic pairs (set id DISC_SET_PERIODIC), which add
+//                 sum_j (U_j(lb) - U_j(ub))^2 [+ (U_x,j(lb) - U_x,j(ub))^2] over ALL outputs to loss slot 2.  Rows 0..7 of
+//                 such a group are the lb points of up to 8 pairs, rows 8..15 their ub partners (row p pairs with p ^ 8),
+//                 n_valid counts the pairs; k_disc_irk skips the contraction there and stores the value differences in R
+//                 and the slope differences in the group's rows of Nn (+d on the lb row, -d on the ub row), k_disc_bwd_out
+//                 seeds g_U = 2 R, g_Ux = 2 Nn, g_Uxx = 0 without a table.  The DISC_BURGERS instantiations know none of it.
 //
 // Unlike the continuous models this path is GEMM shaped (hidden 50, 501 outputs, a 500 x 501 IRK table) over a
 // few hundred points, so every contraction runs on v_mfma_{f32,f64}_16x16x4 and the evaluation is four launches
@@ -39,6 +48,24 @@ struct DiscDesc {
 
 // group descriptor: stage set in bits 0..7, valid points (1..16) above
 __host__ __device__ inline int disc_ginfo(int set, int n_valid) { return set | (n_valid << 8); }
+
+// operator kinds (template value DK of the kernels) and what each takes by value as its coefficients
+enum { DISC_BURGERS = 0, DISC_ADR = 1 };
+template <typename real> struct DiscC12 { real c1, c2; };
+// the six coefficients, and [n_pad][ldo] rows that hold the slope differences of the periodic groups between k_disc_irk and
+// k_disc_bwd_out (the engine hands Nn: nothing else reads those rows of a group without a table).  Here and not a kernel
+// argument of its own, so that the DISC_BURGERS kernels keep their argument lists
+template <typename real> struct DiscAdrArg { real a0, a1, nu, r1, r2, r3; const real* pair_dx; };
+template <typename real, int DK> struct DiscCoefT { using type = DiscC12<real>; };
+template <typename real> struct DiscCoefT<real, DISC_ADR> { using type = DiscAdrArg<real>; };
+template <typename real, int DK> using disc_coef_t = typename DiscCoefT<real, DK>::type;
+
+// DISC_ADR: a group of periodic pairs.  Pair count (1..8) in bits 8..15 of the descriptor, order (0: values, 1: values and
+// slopes) in bit 16
+constexpr int DISC_SET_PERIODIC = 2;
+__host__ __device__ inline int disc_ginfo_periodic(int n_pairs, int order) {
+  return DISC_SET_PERIODIC | (n_pairs << 8) | (order << 16);
+}
 
 template <typename real> __device__ __forceinline__ real exp_r(real z);
 template <> __device__ __forceinline__ float exp_r<float>(float z) { return expf(z); }
@@ -144,13 +171,14 @@ __host__ __device__ inline int disc_kblocks(int K) { return ((K + 15) / 16 + 3) 
 //   Ast [H][3][n_pad][wp]   per hidden layer (a, z_x, z_xx): tanh output and the derivative channels of the
 //                           pre-activation -- what the reverse sweep needs (written by chunk 0 only)
 //   A3  [3][n_pad][wp]      output channels (a, a_x, a_xx) of the last hidden layer
-//   U3  [3][n_pad][ldo]     (U, U_x, U_xx) of the output layer;  Nn [n_pad][ldo] = c1 U U_x - c2 U_xx (0 beyond q)
+//   U3  [3][n_pad][ldo]     (U, U_x, U_xx) of the output layer;  Nn [n_pad][ldo] = N(U) of the kind DK (0 beyond q)
 // ---------------------------------------------------------------------------------------------------------
-template <typename real, int NT>
+template <typename real, int NT, int DK>
 __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const real* __restrict__ th,
-                                                  const real* __restrict__ xs, real lbx, real sx, real c1_in,
-                                                  real c2_in, real* __restrict__ Ast, real* __restrict__ A3,
-                                                  real* __restrict__ U3, real* __restrict__ Nn, int write_stash) {
+                                                  const real* __restrict__ xs, real lbx, real sx,
+                                                  disc_coef_t<real, DK> cf, real* __restrict__ Ast,
+                                                  real* __restrict__ A3, real* __restrict__ U3,
+                                                  real* __restrict__ Nn, int write_stash) {
   using TR = FusedTraits<real>;
   using acc_t = typename TR::acc_t;
   using GEO = DiscGeo<NT>;
@@ -163,8 +191,8 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
   const int n_pad = dd.n_pad, ldo = dd.ldo;
   const int m = lane & 15, g = lane >> 4;
   const bool stash = write_stash && ch == 0;
-  real c1, c2;
-  disc_coefs(nd, dd, th, c1_in, c2_in, c1, c2);
+  real c1 = 0, c2 = 0;
+  if constexpr (DK == DISC_BURGERS) disc_coefs(nd, dd, th, cf.c1, cf.c2, c1, c2);
 
   real pre[GEO::NPRE];                                     // next layer's weights, in flight
   if (H > 1) wt_load<real, NT, WP>(pre, th + nd.off_w[1], W, W, W, tid);
@@ -267,7 +295,10 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
       U3[((size_t)0 * n_pad + gp) * ldo + j] = U;
       U3[((size_t)1 * n_pad + gp) * ldo + j] = Ux;
       U3[((size_t)2 * n_pad + gp) * ldo + j] = Uxx;
-      Nn[gp * ldo + j] = j < dd.q ? c1 * U * Ux - c2 * Uxx : real(0);
+      if constexpr (DK == DISC_ADR)
+        Nn[gp * ldo + j] = j < dd.q ? (cf.a0 + cf.a1 * U) * Ux - cf.nu * Uxx + U * (cf.r1 + U * (cf.r2 + cf.r3 * U)) : real(0);
+      else
+        Nn[gp * ldo + j] = j < dd.q ? c1 * U * Ux - c2 * Uxx : real(0);
     }
   }
 }
@@ -275,11 +306,14 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
 // ---------------------------------------------------------------------------------------------------------
 // IRK stage:  R[p][j] = U[p][j] + sum_k Nn[p][k] MT[k][j] - target[p]   (MT = (dt-scaled table)^T, [ldo][ldo]
 // zero padded; MT == nullptr: no table, R = U - target).  mode 1: prediction only (no target, no mask, no loss).
+// DISC_ADR, a group of periodic pairs (mode 0 only): no contraction; R[p][j] = U[p][j] - U[p ^ 8][j] and, into the group's
+// rows of Nn (nothing reads them for a group without a table), U_x[p][j] - U_x[p ^ 8][j] (0 at order 0); the loss counts
+// each pair once, on its lb row.
 // ---------------------------------------------------------------------------------------------------------
-template <typename real>
+template <typename real, int DK>
 __global__ __launch_bounds__(256) void k_disc_irk(DiscDesc dd, int n_out, const int* __restrict__ ginfo,
                                                   const real* __restrict__ MT0, const real* __restrict__ MT1,
-                                                  const real* __restrict__ Nn, const real* __restrict__ U,
+                                                  real* __restrict__ Nn, const real* __restrict__ U,
                                                   const real* __restrict__ tgt, real* __restrict__ R,
                                                   real* __restrict__ lossp, int mode) {
   using TR = FusedTraits<real>;
@@ -287,9 +321,33 @@ __global__ __launch_bounds__(256) void k_disc_irk(DiscDesc dd, int n_out, const 
   __shared__ real wsum[4];
   const int G = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = lane & 15, g = lane >> 4, ldo = dd.ldo;
-  const int gi = ginfo[G], set = gi & 0xff, n_valid = gi >> 8;
-  const real* __restrict__ MT = set == 0 ? MT0 : MT1;
+  const int gi = ginfo[G], set = gi & 0xff;
   const int j = 64 * ch + 16 * wave + m;
+  if constexpr (DK == DISC_ADR) {
+    if (set == DISC_SET_PERIODIC) {     // (uniform over the workgroup; mode 0: predictions name set 0 or 1)
+      const int n_pairs = (gi >> 8) & 0xff, order = gi >> 16;
+      const real* __restrict__ Ux = U + (size_t)dd.n_pad * ldo;
+      real l = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int p = TR::out_row(lane, r);
+        const size_t o = (size_t)(16 * G + p) * ldo + j, oq = (size_t)(16 * G + (p ^ 8)) * ldo + j;
+        const bool on = (p & 7) < n_pairs && j < n_out;
+        const real d = on ? U[o] - U[oq] : real(0);
+        const real dx = on && order ? Ux[o] - Ux[oq] : real(0);
+        R[o] = d;
+        Nn[o] = dx;
+        if (p < 8) l += d * d + dx * dx;
+      }
+      l = wave_sum(l);
+      if (lane == 0) wsum[wave] = l;
+      __syncthreads();
+      if (tid == 0) lossp[G * dd.n_chunks + ch] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+      return;
+    }
+  }
+  const int n_valid = gi >> 8;
+  const real* __restrict__ MT = set == 0 ? MT0 : MT1;
   real uo[4], tg[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {                            // epilogue operands, in flight under the contraction
@@ -324,12 +382,12 @@ __global__ __launch_bounds__(256) void k_disc_irk(DiscDesc dd, int n_out, const 
 // reverse, output side.  part = per-group gradient rows [n_groups][R_cols]; dAp [n_chunks][3][n_pad][wp];
 // lamp [n_groups * n_chunks][2] partial sums for the identification parameters.
 // ---------------------------------------------------------------------------------------------------------
-template <typename real, int NT>
+template <typename real, int NT, int DK>
 __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, const real* __restrict__ th,
                                                       const int* __restrict__ ginfo,
                                                       const real* __restrict__ M0, const real* __restrict__ M1,
                                                       const real* __restrict__ R, const real* __restrict__ U3,
-                                                      const real* __restrict__ A3, real c1_in, real c2_in,
+                                                      const real* __restrict__ A3, disc_coef_t<real, DK> cf,
                                                       real* __restrict__ part, int R_cols,
                                                       real* __restrict__ dAp, real* __restrict__ lamp) {
   using TR = FusedTraits<real>;
@@ -346,8 +404,13 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
   const int m = lane & 15, g = lane >> 4;
   const int set = ginfo[G] & 0xff;
   const real* __restrict__ M = set == 0 ? M0 : M1;
-  real c1, c2;
-  disc_coefs(nd, dd, th, c1_in, c2_in, c1, c2);
+  bool periodic = false;
+  if constexpr (DK == DISC_ADR) {       // a group of pairs has no table: its set id never selects one
+    periodic = set == DISC_SET_PERIODIC;
+    if (periodic) M = nullptr;
+  }
+  real c1 = 0, c2 = 0;
+  if constexpr (DK == DISC_BURGERS) disc_coefs(nd, dd, th, cf.c1, cf.c2, c1, c2);
   const int jl = 16 * wave + m, j = 64 * ch + jl;
 
   // operands of the later phases: issued now, parked in registers during the contraction
@@ -364,6 +427,8 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
     const size_t o = (size_t)(16 * G + TR::out_row(lane, r)) * ldo + j;
     Rv[r] = R[o]; Uv[r] = U3[o]; Uxv[r] = U3[(size_t)n_pad * ldo + o];
     Uxxv[r] = dd.identify ? U3[(size_t)2 * n_pad * ldo + o] : real(0);
+    if constexpr (DK == DISC_ADR)
+      if (periodic) Uxv[r] = cf.pair_dx[o];     // the slope differences k_disc_irk left there
   }
 
   {  // dN tile = 2 R M  (K = n_out), then the three output-channel adjoints
@@ -376,13 +441,27 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
     for (int r = 0; r < 4; ++r) {
       const int p = TR::out_row(lane, r);
       const real dN = real(2) * acc[r];
-      const real g0 = real(2) * Rv[r] + dN * c1 * Uxv[r];
-      Gs[(0 * 16 + p) * GL + jl] = g0;
-      Gs[(1 * 16 + p) * GL + jl] = dN * c1 * Uv[r];
-      Gs[(2 * 16 + p) * GL + jl] = -c2 * dN;
-      bsum += g0;
-      l1p += dN * Uv[r] * Uxv[r];
-      l2p -= c2 * dN * Uxxv[r];
+      if constexpr (DK == DISC_ADR) {
+        const real U = Uv[r];
+        real g0 = real(2) * Rv[r], g1 = real(2) * Uxv[r], g2 = real(0);      // a group of pairs: 2 R, 2 Rx, nothing on U_xx
+        if (!periodic) {
+          g0 += dN * (cf.a1 * Uxv[r] + cf.r1 + U * (real(2) * cf.r2 + real(3) * cf.r3 * U));
+          g1 = dN * (cf.a0 + cf.a1 * U);
+          g2 = -cf.nu * dN;
+        }
+        Gs[(0 * 16 + p) * GL + jl] = g0;
+        Gs[(1 * 16 + p) * GL + jl] = g1;
+        Gs[(2 * 16 + p) * GL + jl] = g2;
+        bsum += g0;
+      } else {
+        const real g0 = real(2) * Rv[r] + dN * c1 * Uxv[r];
+        Gs[(0 * 16 + p) * GL + jl] = g0;
+        Gs[(1 * 16 + p) * GL + jl] = dN * c1 * Uv[r];
+        Gs[(2 * 16 + p) * GL + jl] = -c2 * dN;
+        bsum += g0;
+        l1p += dN * Uv[r] * Uxv[r];
+        l2p -= c2 * dN * Uxxv[r];
+      }
     }
     // db_out[j] = sum over the 16 points: 4 registers here, the other 12 in the lanes m + 16, 32, 48
     bsum += __shfl_xor(bsum, 16);
@@ -454,7 +533,7 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
 // reverse, hidden layers (one workgroup per 16-point group).  Adjoint algebra: SURVEY.md Appendix A.3 with the
 // t channel dropped (oracle/mlp.py taylor_backward).
 // ---------------------------------------------------------------------------------------------------------
-template <typename real, int NT>
+template <typename real, int NT, int DK>
 __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd, const real* __restrict__ th,
                                                          const int* __restrict__ ginfo,
                                                          const real* __restrict__ xs, real lbx, real sx,
@@ -533,7 +612,8 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
     real s = 0;
     for (int ch = 0; ch < dd.n_chunks; ++ch) s += lossp[G * dd.n_chunks + ch];
     const int set = ginfo[G] & 0xff;
-    for (int k = 0; k < 4; ++k) row[nd.n_theta + k] = (k == (set == 0 ? 0 : 1)) ? s : real(0);
+    // (DISC_ADR: the periodic pairs, set id 2, report in slot 2)
+    for (int k = 0; k < 4; ++k) row[nd.n_theta + k] = (k == (DK == DISC_ADR ? set : set == 0 ? 0 : 1)) ? s : real(0);
     if (dd.identify)
       for (int k = 0; k < 2; ++k) {
         real t = 0;

@@ -21,13 +21,17 @@ SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.h
 HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
 PDE_KINDS = {"burgers": 0, "burgers_ide": 1, "schrodinger": 2, "burgers_disc": 3, "burgers_disc_ide": 4, "adr": 5, "adr_ide": 6}
+# kinds added after the table above was pinned entry for entry (tests/test_adr_host.py): the discrete-time adr kind
+DISC_PDE_KINDS = {"adr_disc": 7}
 
 
 def pde_kind(name):
-    """name -> enum value of include/pinn_hip.h (PDE_KINDS); ValueError with the table otherwise"""
-    if name not in PDE_KINDS:
-        raise ValueError("pde must be one of %s" % sorted(PDE_KINDS))
-    return PDE_KINDS[name]
+    """name -> enum value of include/pinn_hip.h (PDE_KINDS, DISC_PDE_KINDS); ValueError with the tables otherwise"""
+    if name in PDE_KINDS:
+        return PDE_KINDS[name]
+    if name in DISC_PDE_KINDS:
+        return DISC_PDE_KINDS[name]
+    raise ValueError("pde must be one of %s" % sorted(list(PDE_KINDS) + list(DISC_PDE_KINDS)))
 
 
 DTYPES = {"f32": 0, "f64": 1, "float32": 0, "float64": 1}
@@ -236,6 +240,7 @@ _SIGNATURES = {
                                            ctypes.c_int64, _c_double_p, ctypes.c_int]),
     "pinn_disc_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_double_p, ctypes.c_int64,
                                          _c_double_p]),
+    "pinn_disc_set_periodic": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int]),
     "pinn_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "pinn_comm_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int,
                                       ctypes.c_int]),
@@ -674,9 +679,9 @@ class Engine(object):
         self._check(self._lib.pinn_set_pde_params(self._h, _dp(p), p.size))
 
     def get_pde_params(self):
-        """the current raw equation parameters: six coefficients (a0, a1, nu, r1, r2, r3) for "adr" and "adr_ide" (the
-        trained values, nu = exp of the stored log nu), [nu] otherwise"""
-        p = np.empty(6 if self.pde in ("adr", "adr_ide") else 1, dtype=np.float64)
+        """the current raw equation parameters: six coefficients (a0, a1, nu, r1, r2, r3) for "adr", "adr_disc" and "adr_ide"
+        (the trained values, nu = exp of the stored log nu), [nu] otherwise"""
+        p = np.empty(6 if self.pde in ("adr", "adr_ide", "adr_disc") else 1, dtype=np.float64)
         self._check(self._lib.pinn_get_pde_params(self._h, _dp(p), p.size))
         return p
 
@@ -704,7 +709,7 @@ class Engine(object):
                                              _dp(grad) if want_grad else None, _dp(terms)))
         return loss.value, grad, terms
 
-    # ---- discrete-time models (pde "burgers_disc", "burgers_disc_ide") -------------------------
+    # ---- discrete-time models (pde "burgers_disc", "burgers_disc_ide", "adr_disc") -------------
     def disc_set_stage(self, stage, x, target, M=None):
         """Stage set `stage` (0/1): points x [n], targets [n] (broadcast over the outputs), M [n_out, q] =
         step-scaled IRK table or None (no IRK term).  See include/pinn_hip.h."""
@@ -719,6 +724,15 @@ class Engine(object):
             q = M.shape[1]
         self._check(self._lib.pinn_disc_set_stage(self._h, int(stage), _dp(x), _dp(target), x.size,
                                                   _dp(M) if M is not None else None, q))
+
+    def disc_set_periodic(self, x_lb, x_ub, order=1):
+        """Periodic pairs of pde "adr_disc": x_lb[i] with x_ub[i]; every output's value (order 0) or value and slope
+        (order 1) difference, squared and summed, is added to the loss and reported in terms[2].  Empty arrays remove the
+        pairs.  See include/pinn_hip.h."""
+        x_lb, x_ub = _f64(x_lb).ravel(), _f64(x_ub).ravel()
+        if x_lb.size != x_ub.size:
+            raise ValueError("x_lb and x_ub must pair up")
+        self._check(self._lib.pinn_disc_set_periodic(self._h, _dp(x_lb), _dp(x_ub), x_lb.size, int(order)))
 
     def disc_predict(self, stage, x):
         x = _f64(x).ravel()

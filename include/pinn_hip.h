@@ -62,7 +62,17 @@ enum {
    * (pinn_set_pde_params with n = 6; a new context holds Burgers', [0, 1, 0.01 / pi, 0, 0, 0]); they are fixed, not
    * trained.  The one kind with periodic pairs, pinn_disc_set_periodic.  Every call that refuses the discrete-time kinds
    * 3 and 4 refuses this one with the same code.  (Additive: one enum value, one entry point; the ABI version stays 6.) */
-  PINN_PDE_ADR_DISC = 7
+  PINN_PDE_ADR_DISC = 7,
+  /* PINN_PDE_ADR_DISC with the six coefficients trained alongside the net (two snapshots joined by one Runge-Kutta step,
+   * the discrete-time identification of 1d-burgers/ide_disc_burgers.py for the whole family): the weight vector is
+   *     [net weights | a0, a1, log nu, r1, r2, r3]        n_theta = n_net + 6, nu = exp(log nu)
+   * with PINN_PDE_ADR_IDE's semantics: pinn_set_pde_trainable chooses the trained subset (a new context trains none and
+   * holds Burgers'), a frozen coefficient's gradient entry is exactly 0.0 and its value survives both optimisers bit for
+   * bit; pinn_set_pde_params (n = 6, raw, nu > 0) writes the tail, pinn_get_pde_params reads it.  Either stage set may carry
+   * a table, periodic pairs are allowed (pinn_disc_set_periodic); pairs and sets without a table add nothing to the six
+   * gradient entries.  Every call that refuses kinds 3, 4 and 7 refuses this one with the same code.  (Additive: one enum
+   * value, no entry point; the ABI version stays 6.) */
+  PINN_PDE_ADR_DISC_IDE = 8
 };
 enum { PINN_F32 = 0, PINN_F64 = 1 };
 enum {
@@ -134,12 +144,12 @@ int pinn_disc_set_stage(pinn_ctx* c, int set, const double* x, const double* tar
 /* U_0_model / U_1_model at arbitrary points with the table of `set` (ide_disc_burgers.py:188-193):
  * out [n][n_out] = U + N(U) M^T.  pinn_predict returns the plain network outputs U [n][n_out]. */
 int pinn_disc_predict(pinn_ctx* c, int set, const double* x, int64_t n, double* out);
-/* Periodic pairs of PINN_PDE_ADR_DISC: n pairs, x_lb[i] with x_ub[i] (each [n]).  They add
+/* Periodic pairs of PINN_PDE_ADR_DISC and PINN_PDE_ADR_DISC_IDE: n pairs, x_lb[i] with x_ub[i] (each [n]).  They add
  *     sum_{i<n} sum_{j<n_out} (U_j(x_lb[i]) - U_j(x_ub[i]))^2   [+ (U_x,j(x_lb[i]) - U_x,j(x_ub[i]))^2 when order == 1]
  * to the loss -- over ALL outputs, the stages and the solution at t_1 -- reported in terms[2] (terms[0] and terms[1] stay the
  * two stage sets).  A third slot beside stage sets 0 and 1: any subset of the three may be present, at least one must be at
  * the next evaluation.  n == 0 removes the pairs.  Refusals, the context unchanged: PINN_EUNSUPPORTED for any kind but
- * PINN_PDE_ADR_DISC; PINN_EINVAL for order outside {0, 1}, a non-finite point, n outside 0..2^24.  (Additive: the ABI
+ * those two; PINN_EINVAL for order outside {0, 1}, a non-finite point, n outside 0..2^24.  (Additive: the ABI
  * version stays 6.) */
 int pinn_disc_set_periodic(pinn_ctx* c, const double* x_lb, const double* x_ub, int64_t n, int order);
 
@@ -147,12 +157,12 @@ int pinn_disc_set_periodic(pinn_ctx* c, const double* x_lb, const double* x_ub, 
  * PINN_PDE_ADR: n must be 6, p = [a0, a1, nu, r1, r2, r3], all finite; otherwise PINN_EINVAL and the context keeps the
  * coefficients it had (a new context holds Burgers', [0, 1, 0.01 / pi, 0, 0, 0]).  PINN_PDE_ADR_DISC: the same.
  * PINN_PDE_ADR_IDE: n must be 6, RAW p = [a0, a1, nu, r1, r2, r3], all finite and nu > 0 (otherwise PINN_EINVAL, nothing
- * changed): written to the tail of the weight vector, log nu in the nu slot. */
+ * changed): written to the tail of the weight vector, log nu in the nu slot.  PINN_PDE_ADR_DISC_IDE: the same. */
 int pinn_set_pde_params(pinn_ctx* c, const double* p, int n);
-/* the current values: n = 6 raw coefficients for PINN_PDE_ADR, PINN_PDE_ADR_DISC and PINN_PDE_ADR_IDE (nu as exp of the stored log nu: what
- * training has made of them), n = 1 (nu) for every other kind */
+/* the current values: n = 6 raw coefficients for PINN_PDE_ADR, PINN_PDE_ADR_DISC, PINN_PDE_ADR_IDE and
+ * PINN_PDE_ADR_DISC_IDE (the last two: nu as exp of the stored log nu, what training has made of them), n = 1 (nu) for every other kind */
 int pinn_get_pde_params(pinn_ctx* c, double* p, int n);
-/* PINN_PDE_ADR_IDE: bit k of mask set = coefficient k of (a0, a1, nu, r1, r2, r3) is trained; a new context trains none
+/* PINN_PDE_ADR_IDE and PINN_PDE_ADR_DISC_IDE: bit k of mask set = coefficient k of (a0, a1, nu, r1, r2, r3) is trained; a new context trains none
  * (mask 0).  PINN_EINVAL for a mask outside 0..63, PINN_EUNSUPPORTED for every other kind; the context is unchanged then.
  * Takes effect at the next evaluation; a running Adam / L-BFGS state is not reset.  (Additive: the ABI version stays 6.) */
 int pinn_set_pde_trainable(pinn_ctx* c, int mask);

@@ -144,7 +144,7 @@ struct pinn_ctx {
   int n_layers = 0;
   double lb[2]{}, ub[2]{}, nu = 0.0;
   double adr[6]{};                   // PINN_PDE_ADR: a0, a1, nu, r1, r2, r3 (pinn_set_pde_params)
-  int adr_mask = 0;                  // PINN_PDE_ADR_IDE: bit k set = coefficient k is trained (pinn_set_pde_trainable)
+  int adr_mask = 0;                  // PINN_PDE_ADR_IDE, PINN_PDE_ADR_DISC_IDE: bit k set = coefficient k is trained (pinn_set_pde_trainable)
 
   // host copies of the point sets (float64, as handed over)
   PointSets sets;
@@ -343,11 +343,18 @@ __attribute__((always_inline)) static inline auto by_real(const pinn_ctx* c, F&&
   if (c->dtype == PINN_F64) return f(double());
   return f(float());
 }
-static bool disc_kind(int pde) { return pde == PINN_PDE_BURGERS_DISC || pde == PINN_PDE_BURGERS_DISC_IDE || pde == PINN_PDE_ADR_DISC; }
+static bool disc_kind(int pde) {
+  return pde == PINN_PDE_BURGERS_DISC || pde == PINN_PDE_BURGERS_DISC_IDE || pde == PINN_PDE_ADR_DISC ||
+         pde == PINN_PDE_ADR_DISC_IDE;
+}
 static bool is_disc(const pinn_ctx* c) { return disc_kind(c->pde); }
 // the discrete-time model of the adr operator: template value DISC_ADR of the kernels of kernels_disc.h, six coefficients in
 // c->adr as for the adr kind, and the one kind with periodic pairs (pinn_disc_set_periodic)
 static bool is_adr_disc(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR_DISC; }
+// the same model with trainable coefficients: template value DISC_ADR_IDE, the six are the tail of theta as for adr_ide
+// (adr_ide_write_tail, c->adr_mask), periodic pairs allowed
+static bool is_adr_disc_ide(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR_DISC_IDE; }
+static bool has_pairs(const pinn_ctx* c) { return is_adr_disc(c) || is_adr_disc_ide(c); }
 static bool has_lambdas(int pde) { return pde == PINN_PDE_BURGERS_IDE || pde == PINN_PDE_BURGERS_DISC_IDE; }
 // advection-diffusion-reaction with run-time coefficients: template value PDE_ADR of the continuous kernels
 // (kernels_generic.h); it runs on the generic path 0 and, float64 width 20, on k_fused20d (path 7)
@@ -355,9 +362,11 @@ static bool is_adr(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR; }
 // the same equation with trainable coefficients: template value PDE_ADR_IDE, the six coefficients are the tail of theta
 // ([a0, a1, log nu, r1, r2, r3]); the same two paths
 static bool is_adr_ide(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR_IDE; }
+// the kinds whose tail is [a0, a1, log nu, r1, r2, r3] with a mask of the trained ones
+static bool has_adr_tail(const pinn_ctx* c) { return is_adr_ide(c) || is_adr_disc_ide(c); }
 static bool adr_family(const pinn_ctx* c) { return is_adr(c) || is_adr_ide(c); }
 // trailing equation parameters of the flat weight vector
-static int tail_len(int pde) { return has_lambdas(pde) ? 2 : pde == PINN_PDE_ADR_IDE ? 6 : 0; }
+static int tail_len(int pde) { return has_lambdas(pde) ? 2 : pde == PINN_PDE_ADR_IDE || pde == PINN_PDE_ADR_DISC_IDE ? 6 : 0; }
 // what a kernel of kind PDE takes in the place of the scalar nu
 template <typename real, int PDE>
 static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
@@ -1163,7 +1172,7 @@ static int disc_alloc_scratch(pinn_ctx* c, const DiscDesc& dd, DevBuf<void>* Ast
 static int disc_ensure(pinn_ctx* c) {
   if (!c->sets_dirty) return 0;
   const int n0 = (int)c->dset[0].x.size(), n1 = (int)c->dset[1].x.size();
-  const int np = is_adr_disc(c) ? (int)c->dper.lb.size() : 0;     // periodic pairs: any subset of the three slots may be present
+  const int np = has_pairs(c) ? (int)c->dper.lb.size() : 0;     // periodic pairs: any subset of the three slots may be present
   REQUIRE(n0 + n1 + np > 0, "no stage set given (pinn_disc_set_stage)");
   int q = 0;
   for (int s = 0; s < 2; ++s)
@@ -1204,10 +1213,11 @@ static int disc_ensure(pinn_ctx* c) {
   if (disc_alloc_scratch(c, dd, &c->d_Ast, &c->d_A3, c->d_U3, c->d_Nn, c->d_R)) return PINN_EHIP;
   HIPCHK(c->d_dAp.reserve_bytes((size_t)dd.n_chunks * 3 * dd.n_pad * dd.wp * rs));
   HIPCHK(c->d_lossp.reserve_bytes((size_t)G * dd.n_chunks * rs));
-  HIPCHK(c->d_lamp.reserve_bytes((size_t)G * dd.n_chunks * 2 * rs));
+  const size_t n_lam = (size_t)G * dd.n_chunks * (is_adr_disc_ide(c) ? 6 : 2);     // [group * chunk][2], [...][6] for adr_disc_ide
+  HIPCHK(c->d_lamp.reserve_bytes(n_lam * rs));
   // cleared in stream order: the context's stream is non-blocking, so a hipMemset on the null stream (asynchronous to the
   // host for device memory) is not ordered before the first evaluation's kernels and can wipe rows they have written
-  HIPCHK(hipMemsetAsync(c->d_lamp, 0, (size_t)G * dd.n_chunks * 2 * rs, c->stream));
+  HIPCHK(hipMemsetAsync(c->d_lamp, 0, n_lam * rs, c->stream));
   const size_t need_part = (size_t)G * c->R * rs;
   HIPCHK(c->part.reserve_bytes(need_part));
   HIPCHK(hipMemsetAsync(c->part, 0, need_part, c->stream));
@@ -1219,11 +1229,14 @@ static int disc_ensure(pinn_ctx* c) {
 
 // the operator kind of a discrete-time context (template value DK of kernels_disc.h) and its coefficient block, by value:
 // (1, nu) for the Burgers kinds (identification reads its own from the weight vector), the six of c->adr for adr_disc with
-// the rows the periodic groups' slope differences travel in (the context's Nn, or none for a prediction)
-static int disc_dk(const pinn_ctx* c) { return is_adr_disc(c) ? DISC_ADR : DISC_BURGERS; }
+// the rows the periodic groups' slope differences travel in (the context's Nn, or none for a prediction), the mask and those
+// rows for adr_disc_ide
+static int disc_dk(const pinn_ctx* c) { return is_adr_disc_ide(c) ? DISC_ADR_IDE : is_adr_disc(c) ? DISC_ADR : DISC_BURGERS; }
 template <typename real, int DK>
 static disc_coef_t<real, DK> disc_coef(const pinn_ctx* c, const real* pair_dx) {
-  if constexpr (DK == DISC_ADR)
+  if constexpr (DK == DISC_ADR_IDE)      // the coefficients are the tail of the weight vector; by value, which of them train
+    return DiscAdrIdeArg<real>{c->adr_mask, pair_dx};
+  else if constexpr (DK == DISC_ADR)
     return DiscAdrArg<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5],
                             pair_dx};
   else
@@ -1237,7 +1250,7 @@ static int disc_set_lds() {
   HIPCHK(hipFuncSetAttribute((const void*)k_disc_fwd<real, NT, DK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)disc_fwd_lds<NT>(sizeof(real))));
   HIPCHK(hipFuncSetAttribute((const void*)k_disc_bwd_out<real, NT, DK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)disc_out_lds<NT>(sizeof(real))));
+                             (int)disc_out_lds<NT, DK>(sizeof(real))));
   HIPCHK(hipFuncSetAttribute((const void*)k_disc_bwd_hidden<real, NT, DK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)disc_hid_lds<NT>(sizeof(real))));
   return 0;
@@ -1259,7 +1272,7 @@ static int disc_eval(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
                      c->d_MT[0].as<real>(), c->d_MT[1].as<real>(), c->d_Nn.as<real>(),
                      c->d_U3.as<real>(), c->tgt.as<real>(), c->d_R.as<real>(), c->d_lossp.as<real>(), 0);
   if (ev4) HIPCHK(hipEventRecord(ev4[1], c->stream));
-  hipLaunchKernelGGL((k_disc_bwd_out<real, NT, DK>), grid, block, disc_out_lds<NT>(sizeof(real)), c->stream, c->nd, dd,
+  hipLaunchKernelGGL((k_disc_bwd_out<real, NT, DK>), grid, block, (disc_out_lds<NT, DK>(sizeof(real))), c->stream, c->nd, dd,
                      th, c->d_ginfo, c->d_M[0].as<real>(), c->d_M[1].as<real>(), c->d_R.as<real>(),
                      c->d_U3.as<real>(), c->d_A3.as<real>(), cf, c->part.as<real>(), c->R, c->d_dAp.as<real>(),
                      c->d_lamp.as<real>());
@@ -1277,7 +1290,11 @@ static int disc_eval_kind(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   return c->dd.wp == 64 ? disc_eval<float, 4, DK>(c, ev4, af) : disc_eval<float, 8, DK>(c, ev4, af);
 }
 static int disc_eval_any(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
-  return disc_dk(c) == DISC_ADR ? disc_eval_kind<DISC_ADR>(c, ev4, af) : disc_eval_kind<DISC_BURGERS>(c, ev4, af);
+  switch (disc_dk(c)) {
+    case DISC_ADR_IDE: return disc_eval_kind<DISC_ADR_IDE>(c, ev4, af);
+    case DISC_ADR: return disc_eval_kind<DISC_ADR>(c, ev4, af);
+    default: return disc_eval_kind<DISC_BURGERS>(c, ev4, af);
+  }
 }
 
 static int eval_loss_grad(pinn_ctx* c, const AdamFuse* af = nullptr) {
@@ -1346,8 +1363,11 @@ static int disc_predict_kind(pinn_ctx* c, int mode, int set, const double* x, in
                            : disc_predict_impl<float, 8, DK>(c, mode, set, x, n, out);
 }
 static int disc_predict_any(pinn_ctx* c, int mode, int set, const double* x, int64_t n, double* out) {
-  return disc_dk(c) == DISC_ADR ? disc_predict_kind<DISC_ADR>(c, mode, set, x, n, out)
-                                : disc_predict_kind<DISC_BURGERS>(c, mode, set, x, n, out);
+  switch (disc_dk(c)) {
+    case DISC_ADR_IDE: return disc_predict_kind<DISC_ADR_IDE>(c, mode, set, x, n, out);
+    case DISC_ADR: return disc_predict_kind<DISC_ADR>(c, mode, set, x, n, out);
+    default: return disc_predict_kind<DISC_BURGERS>(c, mode, set, x, n, out);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1750,7 +1770,7 @@ int pinn_device_info(int device, char* name, int cap, int* n_cu, int64_t* hbm_by
   return 0;
 }
 
-// PINN_PDE_ADR_IDE: raw [a0, a1, nu, r1, r2, r3] -> the tail of theta (log nu in the nu slot) and its compute-dtype mirror
+// PINN_PDE_ADR_IDE, PINN_PDE_ADR_DISC_IDE: raw [a0, a1, nu, r1, r2, r3] -> the tail of theta (log nu in the nu slot) and its compute-dtype mirror
 static int adr_ide_write_tail(pinn_ctx* c, const double* p) {
   double tail[6];
   for (int i = 0; i < 6; ++i) tail[i] = i == 2 ? std::log(p[i]) : p[i];
@@ -1832,7 +1852,7 @@ static int ctx_device_init(pinn_ctx* c) {
   }
   for (KernelPath p : PATH_PREFERENCE)      // (KP_GENERIC, the last, takes every net)
     if (path_ok(c, p)) { c->path = p; break; }
-  if (is_adr_ide(c)) return adr_ide_write_tail(c, c->adr);      // starts as Burgers too, every coefficient frozen
+  if (has_adr_tail(c)) return adr_ide_write_tail(c, c->adr);    // starts as Burgers too, every coefficient frozen
   return 0;
 }
 
@@ -1841,7 +1861,7 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   REQUIRE(out && layers && lb && ub, "null argument");
   REQUIRE(n_layers >= 3 && n_layers <= MAX_DENSE + 1, "need 3..%d layer sizes, got %d", MAX_DENSE + 1, n_layers);
   REQUIRE(dtype == PINN_F32 || dtype == PINN_F64, "dtype must be PINN_F32 or PINN_F64");
-  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADR_DISC, "unknown pde kind %d", pde_kind);
+  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADR_DISC_IDE, "unknown pde kind %d", pde_kind);
   const bool disc = disc_kind(pde_kind);
   if (disc) REQUIRE(layers[0] == 1, "discrete-time models take one input (x), got %d", layers[0]);
   else REQUIRE(layers[0] == 2, "input dimension must be 2 (x, t), got %d", layers[0]);
@@ -2119,10 +2139,11 @@ int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
     c->nu = p[2];
     return 0;
   }
-  if (is_adr_ide(c)) {  // raw a0, a1, nu, r1, r2, r3 -> the tail of theta; nothing changes on a refusal
-    REQUIRE(n == 6, "pinn_set_pde_params: the adr_ide kind takes 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
+  if (has_adr_tail(c)) {  // raw a0, a1, nu, r1, r2, r3 -> the tail of theta; nothing changes on a refusal
+    const char* kind = is_adr_ide(c) ? "adr_ide" : "adr_disc_ide";
+    REQUIRE(n == 6, "pinn_set_pde_params: the %s kind takes 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", kind, n);
     for (int i = 0; i < 6; ++i) REQUIRE(std::isfinite(p[i]), "pinn_set_pde_params: coefficient %d is not finite", i);
-    REQUIRE(p[2] > 0.0, "pinn_set_pde_params: the adr_ide kind stores log nu, so nu must be positive (got %g)", p[2]);
+    REQUIRE(p[2] > 0.0, "pinn_set_pde_params: the %s kind stores log nu, so nu must be positive (got %g)", kind, p[2]);
     return adr_ide_write_tail(c, p);
   }
   c->nu = p[0];
@@ -2131,9 +2152,9 @@ int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
 
 int pinn_get_pde_params(pinn_ctx* c, double* p, int n) {
   REQUIRE(c && p, "null");
-  if (is_adr(c) || is_adr_ide(c) || is_adr_disc(c)) REQUIRE(n == 6, "pinn_get_pde_params: this kind has 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
+  if (is_adr(c) || has_adr_tail(c) || is_adr_disc(c)) REQUIRE(n == 6, "pinn_get_pde_params: this kind has 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
   else REQUIRE(n == 1, "pinn_get_pde_params: this kind has 1 parameter (nu), got %d", n);
-  if (is_adr_ide(c)) {
+  if (has_adr_tail(c)) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(p, c->theta + c->nd.n_net, 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2148,8 +2169,9 @@ int pinn_get_pde_params(pinn_ctx* c, double* p, int n) {
 
 int pinn_set_pde_trainable(pinn_ctx* c, int mask) {
   REQUIRE(c, "null");
-  if (!is_adr_ide(c))
-    return fail(PINN_EUNSUPPORTED, "pinn_set_pde_trainable: only the adr_ide kind (pde 6) has trainable coefficients to choose from");
+  if (!has_adr_tail(c))
+    return fail(PINN_EUNSUPPORTED, "pinn_set_pde_trainable: only the adr_ide kind (pde 6) and its discrete-time form, the "
+                "adr_disc_ide kind (pde 8), have trainable coefficients to choose from");
   REQUIRE(mask >= 0 && mask <= 63, "pinn_set_pde_trainable: mask %d is outside 0..63 (bit k = coefficient k of a0, a1, nu, r1, r2, r3)", mask);
   c->adr_mask = mask;
   return 0;
@@ -2704,8 +2726,9 @@ int pinn_disc_set_stage(pinn_ctx* c, int set, const double* x, const double* tar
 
 int pinn_disc_set_periodic(pinn_ctx* c, const double* x_lb, const double* x_ub, int64_t n, int order) {
   REQUIRE(c, "null");
-  if (!is_adr_disc(c))
-    return fail(PINN_EUNSUPPORTED, "pinn_disc_set_periodic: periodic pairs are for the adr_disc kind (pde 7) only");
+  if (!has_pairs(c))
+    return fail(PINN_EUNSUPPORTED, "pinn_disc_set_periodic: periodic pairs are for the adr_disc kind (pde 7) and the "
+                "adr_disc_ide kind (pde 8) only");
   REQUIRE(order == 0 || order == 1, "pinn_disc_set_periodic: order %d outside 0..1 (0: values, 1: values and slopes)", order);
   REQUIRE(n >= 0 && n <= (1 << 24), "pinn_disc_set_periodic: bad pair count");
   REQUIRE(n == 0 || (x_lb && x_ub), "pinn_disc_set_periodic: null argument");

@@ -10,6 +10,10 @@
 //                 n_valid counts the pairs; k_disc_irk skips the contraction there and stores the value differences in R
 //                 and the slope differences in the group's rows of Nn (+d on the lb row, -d on the ub row), k_disc_bwd_out
 //                 seeds g_U = 2 R, g_Ux = 2 Nn, g_Uxx = 0 without a table.  The DISC_BURGERS instantiations know none of it.
+//   DISC_ADR_IDE  DISC_ADR with the six coefficients read from the tail of the weight vector, th[n_net + k] =
+//                 [a0, a1, log nu, r1, r2, r3] (pde 8), as pde 4 reads its two; by value go the mask of the trained ones and
+//                 the pairs' rows.  k_disc_bwd_out forms the six sums of dN dN/dp_k beside db_out and leaves them, masked,
+//                 in lamp [group * chunk][6]; k_disc_bwd_hidden adds the chunks in a fixed order.  No atomics anywhere.
 //
 // Unlike the continuous models this path is GEMM shaped (hidden 50, 501 outputs, a 500 x 501 IRK table) over a
 // few hundred points, so every contraction runs on v_mfma_{f32,f64}_16x16x4 and the evaluation is four launches
@@ -50,14 +54,18 @@ struct DiscDesc {
 __host__ __device__ inline int disc_ginfo(int set, int n_valid) { return set | (n_valid << 8); }
 
 // operator kinds (template value DK of the kernels) and what each takes by value as its coefficients
-enum { DISC_BURGERS = 0, DISC_ADR = 1 };
+enum { DISC_BURGERS = 0, DISC_ADR = 1, DISC_ADR_IDE = 2 };
+constexpr bool disc_adr_like(int DK) { return DK == DISC_ADR || DK == DISC_ADR_IDE; }
 template <typename real> struct DiscC12 { real c1, c2; };
 // the six coefficients, and [n_pad][ldo] rows that hold the slope differences of the periodic groups between k_disc_irk and
 // k_disc_bwd_out (the engine hands Nn: nothing else reads those rows of a group without a table).  Here and not a kernel
 // argument of its own, so that the DISC_BURGERS kernels keep their argument lists
 template <typename real> struct DiscAdrArg { real a0, a1, nu, r1, r2, r3; const real* pair_dx; };
+// DISC_ADR_IDE: bit k of mask set = coefficient k is trained (a frozen one's gradient entry is written as 0.0)
+template <typename real> struct DiscAdrIdeArg { int mask; const real* pair_dx; };
 template <typename real, int DK> struct DiscCoefT { using type = DiscC12<real>; };
 template <typename real> struct DiscCoefT<real, DISC_ADR> { using type = DiscAdrArg<real>; };
+template <typename real> struct DiscCoefT<real, DISC_ADR_IDE> { using type = DiscAdrIdeArg<real>; };
 template <typename real, int DK> using disc_coef_t = typename DiscCoefT<real, DK>::type;
 
 // DISC_ADR: a group of periodic pairs.  Pair count (1..8) in bits 8..15 of the descriptor, order (0: values, 1: values and
@@ -78,6 +86,24 @@ __device__ __forceinline__ void disc_coefs(const NetDesc& nd, const DiscDesc& dd
   if (dd.identify) { c1 = th[nd.n_net]; c2 = exp_r(th[nd.n_net + 1]); }
 }
 
+// the six coefficients an adr-like kernel computes with: the by-value block's, or the tail of the weight vector.  The tail's
+// address is wave-uniform, so the loads are scalar; nu = exp(log nu) is formed once per wave and read back into scalar
+// registers, where it costs no vector register per thread (call it with every lane active)
+__device__ __forceinline__ float first_lane(float v) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+__device__ __forceinline__ double first_lane(double v) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+template <typename real, int DK>
+__device__ __forceinline__ AdrCoef<real> disc_adr_coefs(const disc_coef_t<real, DK>& cf, const real* __restrict__ tail) {
+  if constexpr (DK == DISC_ADR_IDE)
+    return AdrCoef<real>{tail[0], tail[1], first_lane(exp_r(tail[2])), tail[3], tail[4], tail[5]};
+  else
+    return AdrCoef<real>{cf.a0, cf.a1, cf.nu, cf.r1, cf.r2, cf.r3};
+}
+
 // LDS geometry shared by host and device
 template <int NT> struct DiscGeo {
   static constexpr int WP = 16 * NT;
@@ -91,8 +117,9 @@ template <int NT> struct DiscGeo {
 template <int NT> inline size_t disc_fwd_lds(size_t rs) {
   return (size_t)(2 * 3 * DiscGeo<NT>::CS + DiscGeo<NT>::WP * DiscGeo<NT>::WLD) * rs;
 }
-template <int NT> inline size_t disc_out_lds(size_t rs) {
-  return (size_t)(3 * 16 * 68 + 3 * DiscGeo<NT>::CS + DiscGeo<NT>::WP * 68 + 8) * rs;
+// (the last term is wsum: [4 waves][2] for pde 4, [4 waves][6] for DISC_ADR_IDE; the other kinds launch with what they had)
+template <int NT, int DK = DISC_BURGERS> inline size_t disc_out_lds(size_t rs) {
+  return (size_t)(3 * 16 * 68 + 3 * DiscGeo<NT>::CS + DiscGeo<NT>::WP * 68 + (DK == DISC_ADR_IDE ? 24 : 8)) * rs;
 }
 template <int NT> inline size_t disc_hid_lds(size_t rs) {
   return (size_t)(3 * 3 * DiscGeo<NT>::CS + DiscGeo<NT>::WP * DiscGeo<NT>::TLD + 16) * rs;
@@ -197,6 +224,8 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
   real pre[GEO::NPRE];                                     // next layer's weights, in flight
   if (H > 1) wt_load<real, NT, WP>(pre, th + nd.off_w[1], W, W, W, tid);
   else wt_load<real, NT, WP>(pre, th + nd.off_w[H] + 64 * ch, NO, W, min(64, NO - 64 * ch), tid);
+  [[maybe_unused]] AdrCoef<real> k6{};                     // DISC_ADR_IDE: the tail's, behind the first weight loads
+  if constexpr (DK == DISC_ADR_IDE) k6 = disc_adr_coefs<real, DK>(cf, th + nd.n_net);
 
   // dense 0 (fan_in 1): h = sx (x - lb) - 1, h_x = sx, h_xx = 0
   for (int i = tid; i < 16 * WP; i += 256) {
@@ -297,6 +326,8 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
       U3[((size_t)2 * n_pad + gp) * ldo + j] = Uxx;
       if constexpr (DK == DISC_ADR)
         Nn[gp * ldo + j] = j < dd.q ? (cf.a0 + cf.a1 * U) * Ux - cf.nu * Uxx + U * (cf.r1 + U * (cf.r2 + cf.r3 * U)) : real(0);
+      else if constexpr (DK == DISC_ADR_IDE)
+        Nn[gp * ldo + j] = j < dd.q ? (k6.a0 + k6.a1 * U) * Ux - k6.nu * Uxx + U * (k6.r1 + U * (k6.r2 + k6.r3 * U)) : real(0);
       else
         Nn[gp * ldo + j] = j < dd.q ? c1 * U * Ux - c2 * Uxx : real(0);
     }
@@ -306,7 +337,7 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
 // ---------------------------------------------------------------------------------------------------------
 // IRK stage:  R[p][j] = U[p][j] + sum_k Nn[p][k] MT[k][j] - target[p]   (MT = (dt-scaled table)^T, [ldo][ldo]
 // zero padded; MT == nullptr: no table, R = U - target).  mode 1: prediction only (no target, no mask, no loss).
-// DISC_ADR, a group of periodic pairs (mode 0 only): no contraction; R[p][j] = U[p][j] - U[p ^ 8][j] and, into the group's
+// DISC_ADR and DISC_ADR_IDE, a group of periodic pairs (mode 0 only): no contraction; R[p][j] = U[p][j] - U[p ^ 8][j] and, into the group's
 // rows of Nn (nothing reads them for a group without a table), U_x[p][j] - U_x[p ^ 8][j] (0 at order 0); the loss counts
 // each pair once, on its lb row.
 // ---------------------------------------------------------------------------------------------------------
@@ -323,7 +354,7 @@ __global__ __launch_bounds__(256) void k_disc_irk(DiscDesc dd, int n_out, const 
   const int m = lane & 15, g = lane >> 4, ldo = dd.ldo;
   const int gi = ginfo[G], set = gi & 0xff;
   const int j = 64 * ch + 16 * wave + m;
-  if constexpr (DK == DISC_ADR) {
+  if constexpr (disc_adr_like(DK)) {
     if (set == DISC_SET_PERIODIC) {     // (uniform over the workgroup; mode 0: predictions name set 0 or 1)
       const int n_pairs = (gi >> 8) & 0xff, order = gi >> 16;
       const real* __restrict__ Ux = U + (size_t)dd.n_pad * ldo;
@@ -380,7 +411,10 @@ __global__ __launch_bounds__(256) void k_disc_irk(DiscDesc dd, int n_out, const 
 
 // ---------------------------------------------------------------------------------------------------------
 // reverse, output side.  part = per-group gradient rows [n_groups][R_cols]; dAp [n_chunks][3][n_pad][wp];
-// lamp [n_groups * n_chunks][2] partial sums for the identification parameters.
+// lamp [n_groups * n_chunks][2] partial sums for the identification parameters ([...][6] for DISC_ADR_IDE: the sums over
+// this tile of dN U_x, dN U U_x, -nu dN U_xx, dN U, dN U^2, dN U^3, a frozen coefficient's stored as 0.0 -- the mask is applied
+// here, where the coefficient block is: k_disc_bwd_hidden takes none, and its sum of zeros is 0.0).  dN is 0 on padded rows
+// (R is), beyond column q (M is), and where the set has no table, so the sums need no mask of their own.
 // ---------------------------------------------------------------------------------------------------------
 template <typename real, int NT, int DK>
 __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, const real* __restrict__ th,
@@ -398,19 +432,21 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
   real* Gs = reinterpret_cast<real*>(disc_smem);           // [3][16][GL] output-channel adjoints of this chunk
   real* a3s = Gs + 3 * 16 * GL;                            // [3][16][LD] last hidden layer's output channels
   real* wos = a3s + 3 * CS;                                // [WP][OL] output-layer weights of this chunk
-  real* wsum = wos + WP * OL;                              // [4][2]
+  real* wsum = wos + WP * OL;                              // [4][2]  (DISC_ADR_IDE: [4][6])
   const int G = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int W = nd.width, H = nd.n_hidden, NO = nd.n_out, ldo = dd.ldo, n_pad = dd.n_pad;
   const int m = lane & 15, g = lane >> 4;
   const int set = ginfo[G] & 0xff;
   const real* __restrict__ M = set == 0 ? M0 : M1;
   bool periodic = false;
-  if constexpr (DK == DISC_ADR) {       // a group of pairs has no table: its set id never selects one
+  if constexpr (disc_adr_like(DK)) {    // a group of pairs has no table: its set id never selects one
     periodic = set == DISC_SET_PERIODIC;
     if (periodic) M = nullptr;
   }
   real c1 = 0, c2 = 0;
   if constexpr (DK == DISC_BURGERS) disc_coefs(nd, dd, th, cf.c1, cf.c2, c1, c2);
+  [[maybe_unused]] AdrCoef<real> k6{};
+  if constexpr (DK == DISC_ADR_IDE) k6 = disc_adr_coefs<real, DK>(cf, th + nd.n_net);
   const int jl = 16 * wave + m, j = 64 * ch + jl;
 
   // operands of the later phases: issued now, parked in registers during the contraction
@@ -426,8 +462,9 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
   for (int r = 0; r < 4; ++r) {
     const size_t o = (size_t)(16 * G + TR::out_row(lane, r)) * ldo + j;
     Rv[r] = R[o]; Uv[r] = U3[o]; Uxv[r] = U3[(size_t)n_pad * ldo + o];
-    Uxxv[r] = dd.identify ? U3[(size_t)2 * n_pad * ldo + o] : real(0);
-    if constexpr (DK == DISC_ADR)
+    if constexpr (DK == DISC_ADR_IDE) Uxxv[r] = U3[(size_t)2 * n_pad * ldo + o];      // always: d/d log nu needs the plane
+    else Uxxv[r] = dd.identify ? U3[(size_t)2 * n_pad * ldo + o] : real(0);
+    if constexpr (disc_adr_like(DK))
       if (periodic) Uxv[r] = cf.pair_dx[o];     // the slope differences k_disc_irk left there
   }
 
@@ -437,11 +474,28 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
       acc = disc_gemm_k<real>(R + (size_t)(16 * G + m) * ldo + 4 * g, M + (size_t)(4 * g) * ldo + j, ldo,
                               disc_kblocks(NO));
     real l1p = 0, l2p = 0, bsum = 0;
+    [[maybe_unused]] real t6[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int p = TR::out_row(lane, r);
       const real dN = real(2) * acc[r];
-      if constexpr (DK == DISC_ADR) {
+      if constexpr (DK == DISC_ADR_IDE) {
+        // DISC_ADR's seeds from the products the six sums are made of: dN U_x, dN U, dN U^2 (t6[2] takes -nu behind wave_sum)
+        const real U = Uv[r];
+        real g0 = real(2) * Rv[r], g1 = real(2) * Uxv[r], g2 = real(0);
+        if (!periodic) {
+          const real dUx = dN * Uxv[r], dU = dN * U, dU2 = dU * U;
+          g0 += k6.a1 * dUx + k6.r1 * dN + real(2) * k6.r2 * dU + real(3) * k6.r3 * dU2;
+          g1 = k6.a0 * dN + k6.a1 * dU;
+          g2 = -k6.nu * dN;
+          t6[0] += dUx; t6[1] += dUx * U; t6[2] += dN * Uxxv[r];
+          t6[3] += dU;  t6[4] += dU2;     t6[5] += dU2 * U;
+        }
+        Gs[(0 * 16 + p) * GL + jl] = g0;
+        Gs[(1 * 16 + p) * GL + jl] = g1;
+        Gs[(2 * 16 + p) * GL + jl] = g2;
+        bsum += g0;
+      } else if constexpr (DK == DISC_ADR) {
         const real U = Uv[r];
         real g0 = real(2) * Rv[r], g1 = real(2) * Uxv[r], g2 = real(0);      // a group of pairs: 2 R, 2 Rx, nothing on U_xx
         if (!periodic) {
@@ -472,6 +526,15 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
       l2p = wave_sum(l2p);
       if (lane == 0) { wsum[wave * 2 + 0] = l1p; wsum[wave * 2 + 1] = l2p; }
     }
+    if constexpr (DK == DISC_ADR_IDE) {   // the wave's tile first, then the four waves through LDS: a fixed order
+#pragma unroll
+      for (int k = 0; k < 6; ++k) t6[k] = wave_sum(t6[k]);
+      t6[2] *= -k6.nu;
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) wsum[wave * 6 + k] = t6[k];
+      }
+    }
   }
 #pragma unroll
   for (int n = 0; n < 3 * 16 * WP / 256; ++n) {
@@ -482,6 +545,10 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
   __syncthreads();
   if (dd.identify && tid < 2)
     lamp[(size_t)(G * dd.n_chunks + ch) * 2 + tid] = (wsum[tid] + wsum[2 + tid]) + (wsum[4 + tid] + wsum[6 + tid]);
+  if constexpr (DK == DISC_ADR_IDE)
+    if (tid < 6)
+      lamp[(size_t)(G * dd.n_chunks + ch) * 6 + tid] =
+          ((cf.mask >> tid) & 1) ? (wsum[tid] + wsum[6 + tid]) + (wsum[12 + tid] + wsum[18 + tid]) : real(0);
 
   {  // dW_out[k][j] partial of this group: sum over 3 channels x 16 points of A3_c[p][k] G_c[p][j]
     acc_t acc[NT];
@@ -558,6 +625,26 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
   real* hs = wt + WP * TLD;                         // [16] normalised inputs of the group's points
   real* __restrict__ row = part + (size_t)G * R_cols;
 
+  if constexpr (DK == DISC_ADR_IDE) {
+    // the six tail entries: one column per thread of wave 1 (wave 0 walks the loss partials), four chunks in flight per round,
+    // summed in a fixed order.  Ahead of the big loads: here the sum holds no register across them (behind them,
+    // <float, 8> gained 8 bytes of scratch over its DISC_ADR sibling).  k_disc_bwd_out stored a frozen coefficient's
+    // partials as 0.0; a group of pairs has no tail gradient and reads nothing
+    if (tid >= 64 && tid < 70) {
+      const int k = tid - 64, nch = dd.n_chunks;
+      real t = 0;
+      if ((ginfo[G] & 0xff) != DISC_SET_PERIODIC)
+        for (int c0 = 0; c0 < nch; c0 += 4) {
+          const real* src = lamp + (size_t)(G * nch + c0) * 6 + k;
+          real v[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) v[u] = c0 + u < nch ? src[6 * u] : real(0);
+          t += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+      row[nd.n_net + k] = t;
+    }
+  }
+
   // in flight from the start: weights of the last hidden layer, its stash and the stash below it
   real pre[GEO::NPRE];
   if (H > 1) wt_load<real, NT, WP>(pre, th + nd.off_w[H - 1], W, W, W, tid);
@@ -613,7 +700,7 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
     for (int ch = 0; ch < dd.n_chunks; ++ch) s += lossp[G * dd.n_chunks + ch];
     const int set = ginfo[G] & 0xff;
     // (DISC_ADR: the periodic pairs, set id 2, report in slot 2)
-    for (int k = 0; k < 4; ++k) row[nd.n_theta + k] = (k == (DK == DISC_ADR ? set : set == 0 ? 0 : 1)) ? s : real(0);
+    for (int k = 0; k < 4; ++k) row[nd.n_theta + k] = (k == (disc_adr_like(DK) ? set : set == 0 ? 0 : 1)) ? s : real(0);
     if (dd.identify)
       for (int k = 0; k < 2; ++k) {
         real t = 0;

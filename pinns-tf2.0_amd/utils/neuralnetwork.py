@@ -10,8 +10,10 @@ return shapes (numpy arrays where the reference returns eager tensors).
 
 What changes: there is no TensorFlow, so a subclass cannot spell its PDE with GradientTapes.
 It names one of the engine's residual kinds instead (`pde="burgers" | "burgers_ide" |
-"schrodinger" | "burgers_disc" | "burgers_disc_ide" | "adr" | "adr_ide" | "adr_disc"`; "adr_disc" is the discrete-time
-(q-stage Runge-Kutta, 1-input) model of the adr operator with periodic pairs, see 1d-allen-cahn/inf_disc_allen_cahn.py; "adr" is u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 = 0
+"schrodinger" | "burgers_disc" | "burgers_disc_ide" | "adr" | "adr_ide" | "adr_disc" | "adr_disc_ide"`; "adr_disc" is the discrete-time
+(q-stage Runge-Kutta, 1-input) model of the adr operator with periodic pairs, see 1d-allen-cahn/inf_disc_allen_cahn.py, and
+"adr_disc_ide" the same model with the coefficients named in hp["adr_trainable"] learned from two snapshots, see
+1d-allen-cahn/ide_disc_allen_cahn.py; "adr" is u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 = 0
 with fixed coefficients the subclass hands to `self._engine.set_pde_params(a0, a1, nu, r1, r2, r3)`, "adr_ide" the same
 equation with the coefficients named in hp["adr_trainable"] learned from the data, see _adr_ide_options) and the engine evaluates forward, u_t/u_x/u_xx, residual, loss and the flat
 gradient on the GPU (csrc/).  Extra, optional hp keys: "dtype" ("f64" default = the reference's
@@ -253,7 +255,7 @@ class NeuralNetwork(object):
         self._resample, self._rad_k, self._rad_c, self._rad_pool = _resample_options(hp, self.pde)
         self._sa = _sa_options(hp, self.pde)
         self._pw = _pw_options(hp, self.pde)
-        self._adr_ide = _adr_ide_options(hp) if self.pde == "adr_ide" else None
+        self._adr_ide = _adr_ide_options(hp) if self.pde in ("adr_ide", "adr_disc_ide") else None
 
         # L-BFGS configuration, same fields as the reference (neuralnetwork.py:13-17)
         self.nt_config = Struct()
@@ -276,7 +278,7 @@ class NeuralNetwork(object):
         if self.pde in ("adr", "adr_ide") and parallel.env_world()[0] > 1 and bool(hp.get("data_parallel", True)):
             raise ValueError('pde "%s": a data-parallel launch (world > 1) is not supported for this kind; run one process, '
                              'or set hp["data_parallel"] = false for independent replicas' % self.pde)
-        self._dp = None if self.pde.startswith("burgers_disc") or self.pde == "adr_disc" else parallel.from_env(bool(hp.get("data_parallel", True)))
+        self._dp = None if self.pde.startswith("burgers_disc") or self.pde in ("adr_disc", "adr_disc_ide") else parallel.from_env(bool(hp.get("data_parallel", True)))
         self.is_root = parallel.is_root()
         world, _, local_rank = parallel.env_world()
         device = hp.get("device", os.environ.get("PINN_DEVICE", local_rank if world > 1 else 0))

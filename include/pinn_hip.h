@@ -72,7 +72,23 @@ enum {
    * a table, periodic pairs are allowed (pinn_disc_set_periodic); pairs and sets without a table add nothing to the six
    * gradient entries.  Every call that refuses kinds 3, 4 and 7 refuses this one with the same code.  (Additive: one enum
    * value, no entry point; the ABI version stays 6.) */
-  PINN_PDE_ADR_DISC_IDE = 8
+  PINN_PDE_ADR_DISC_IDE = 8,
+  /* PINN_PDE_ADR_DISC_IDE with a dispersion term (Korteweg-de Vries u_t + a1 u u_x + d3 u_xxx = 0, the linear dispersive
+   * equation, KdV-Burgers):
+   *     N(U) = (a0 + a1 U) U_x - nu U_xx + d3 U_xxx + r1 U + r2 U^2 + r3 U^3
+   * on the first q outputs; the weight vector is
+   *     [net weights | a0, a1, log nu, r1, r2, r3, d3]    n_theta = n_net + 7, d3 raw (its sign is free)
+   * Everything kind 8 has: either stage set may carry a table, periodic pairs at order 0 or 1, pinn_predict /
+   * pinn_disc_predict, both optimisers, pinn_set_pde_trainable (mask 0..127, bit 6 = d3; a new context trains none and
+   * holds [0, 1, 0.01 / pi, 0, 0, 0, 0]), a frozen coefficient frozen bit for bit -- so the inference model is this kind
+   * with nothing trained.  pinn_set_pde_params / pinn_get_pde_params carry 7 raw values, and nu = 0 is allowed: the
+   * kernels then compute without the diffusion term, the nu slot of the tail holds 0.0, is not read and has gradient
+   * entry exactly 0.0, and the nu bit cannot be trained (PINN_EINVAL from whichever of the two calls comes second, nothing
+   * changed) until pinn_set_pde_params gives nu > 0 again.  pinn_set_weights never touches that flag: to restore a
+   * checkpoint, set the params first, then the weights.  Hidden width above 64 is PINN_EUNSUPPORTED at create in both
+   * dtypes (four Taylor channels fill the LDS).  Every call that refuses kinds 3, 4, 7 and 8 refuses this one with the
+   * same code.  (Additive: one enum value, no entry point; the ABI version stays 6.) */
+  PINN_PDE_ADRD_DISC = 9
 };
 enum { PINN_F32 = 0, PINN_F64 = 1 };
 enum {
@@ -144,7 +160,7 @@ int pinn_disc_set_stage(pinn_ctx* c, int set, const double* x, const double* tar
 /* U_0_model / U_1_model at arbitrary points with the table of `set` (ide_disc_burgers.py:188-193):
  * out [n][n_out] = U + N(U) M^T.  pinn_predict returns the plain network outputs U [n][n_out]. */
 int pinn_disc_predict(pinn_ctx* c, int set, const double* x, int64_t n, double* out);
-/* Periodic pairs of PINN_PDE_ADR_DISC and PINN_PDE_ADR_DISC_IDE: n pairs, x_lb[i] with x_ub[i] (each [n]).  They add
+/* Periodic pairs of PINN_PDE_ADR_DISC, PINN_PDE_ADR_DISC_IDE and PINN_PDE_ADRD_DISC: n pairs, x_lb[i] with x_ub[i] (each [n]).  They add
  *     sum_{i<n} sum_{j<n_out} (U_j(x_lb[i]) - U_j(x_ub[i]))^2   [+ (U_x,j(x_lb[i]) - U_x,j(x_ub[i]))^2 when order == 1]
  * to the loss -- over ALL outputs, the stages and the solution at t_1 -- reported in terms[2] (terms[0] and terms[1] stay the
  * two stage sets).  A third slot beside stage sets 0 and 1: any subset of the three may be present, at least one must be at
@@ -157,13 +173,17 @@ int pinn_disc_set_periodic(pinn_ctx* c, const double* x_lb, const double* x_ub, 
  * PINN_PDE_ADR: n must be 6, p = [a0, a1, nu, r1, r2, r3], all finite; otherwise PINN_EINVAL and the context keeps the
  * coefficients it had (a new context holds Burgers', [0, 1, 0.01 / pi, 0, 0, 0]).  PINN_PDE_ADR_DISC: the same.
  * PINN_PDE_ADR_IDE: n must be 6, RAW p = [a0, a1, nu, r1, r2, r3], all finite and nu > 0 (otherwise PINN_EINVAL, nothing
- * changed): written to the tail of the weight vector, log nu in the nu slot.  PINN_PDE_ADR_DISC_IDE: the same. */
+ * changed): written to the tail of the weight vector, log nu in the nu slot.  PINN_PDE_ADR_DISC_IDE: the same.
+ * PINN_PDE_ADRD_DISC: n must be 7, RAW p = [a0, a1, nu, r1, r2, r3, d3], all finite and nu >= 0 (nu == 0: see the kind);
+ * PINN_EINVAL for nu == 0 while the nu bit is trainable. */
 int pinn_set_pde_params(pinn_ctx* c, const double* p, int n);
 /* the current values: n = 6 raw coefficients for PINN_PDE_ADR, PINN_PDE_ADR_DISC, PINN_PDE_ADR_IDE and
- * PINN_PDE_ADR_DISC_IDE (the last two: nu as exp of the stored log nu, what training has made of them), n = 1 (nu) for every other kind */
+ * PINN_PDE_ADR_DISC_IDE (the last two: nu as exp of the stored log nu, what training has made of them), n = 7 for
+ * PINN_PDE_ADRD_DISC (nu = 0 while its flag is up), n = 1 (nu) for every other kind */
 int pinn_get_pde_params(pinn_ctx* c, double* p, int n);
 /* PINN_PDE_ADR_IDE and PINN_PDE_ADR_DISC_IDE: bit k of mask set = coefficient k of (a0, a1, nu, r1, r2, r3) is trained; a new context trains none
  * (mask 0).  PINN_EINVAL for a mask outside 0..63, PINN_EUNSUPPORTED for every other kind; the context is unchanged then.
+ * PINN_PDE_ADRD_DISC: seven names (.., d3), mask 0..127; PINN_EINVAL for the nu bit while nu == 0.
  * Takes effect at the next evaluation; a running Adam / L-BFGS state is not reset.  (Additive: the ABI version stays 6.) */
 int pinn_set_pde_trainable(pinn_ctx* c, int mask);
 

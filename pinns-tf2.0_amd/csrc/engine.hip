@@ -143,8 +143,9 @@ struct pinn_ctx {
   int layers[MAX_DENSE + 1]{};
   int n_layers = 0;
   double lb[2]{}, ub[2]{}, nu = 0.0;
-  double adr[6]{};                   // PINN_PDE_ADR: a0, a1, nu, r1, r2, r3 (pinn_set_pde_params)
-  int adr_mask = 0;                  // PINN_PDE_ADR_IDE, PINN_PDE_ADR_DISC_IDE: bit k set = coefficient k is trained (pinn_set_pde_trainable)
+  double adr[7]{};                   // PINN_PDE_ADR: a0, a1, nu, r1, r2, r3 (pinn_set_pde_params); [6]: d3 of PINN_PDE_ADRD_DISC at create
+  int adr_mask = 0;                  // PINN_PDE_ADR_IDE, PINN_PDE_ADR_DISC_IDE, PINN_PDE_ADRD_DISC: bit k set = coefficient k is trained (pinn_set_pde_trainable)
+  bool nu_off = false;               // PINN_PDE_ADRD_DISC: nu == 0 (pinn_set_pde_params); the kernels get it by value, the nu slot holds 0.0
 
   // host copies of the point sets (float64, as handed over)
   PointSets sets;
@@ -345,7 +346,7 @@ __attribute__((always_inline)) static inline auto by_real(const pinn_ctx* c, F&&
 }
 static bool disc_kind(int pde) {
   return pde == PINN_PDE_BURGERS_DISC || pde == PINN_PDE_BURGERS_DISC_IDE || pde == PINN_PDE_ADR_DISC ||
-         pde == PINN_PDE_ADR_DISC_IDE;
+         pde == PINN_PDE_ADR_DISC_IDE || pde == PINN_PDE_ADRD_DISC;
 }
 static bool is_disc(const pinn_ctx* c) { return disc_kind(c->pde); }
 // the discrete-time model of the adr operator: template value DISC_ADR of the kernels of kernels_disc.h, six coefficients in
@@ -354,7 +355,10 @@ static bool is_adr_disc(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR_DISC;
 // the same model with trainable coefficients: template value DISC_ADR_IDE, the six are the tail of theta as for adr_ide
 // (adr_ide_write_tail, c->adr_mask), periodic pairs allowed
 static bool is_adr_disc_ide(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR_DISC_IDE; }
-static bool has_pairs(const pinn_ctx* c) { return is_adr_disc(c) || is_adr_disc_ide(c); }
+// adr_disc_ide with a dispersion term d3 U_xxx: template value DISC_ADRD (four Taylor channels), a tail of seven
+// ([.., d3], raw) and a flag for nu == 0 (c->nu_off)
+static bool is_adrd_disc(const pinn_ctx* c) { return c->pde == PINN_PDE_ADRD_DISC; }
+static bool has_pairs(const pinn_ctx* c) { return is_adr_disc(c) || is_adr_disc_ide(c) || is_adrd_disc(c); }
 static bool has_lambdas(int pde) { return pde == PINN_PDE_BURGERS_IDE || pde == PINN_PDE_BURGERS_DISC_IDE; }
 // advection-diffusion-reaction with run-time coefficients: template value PDE_ADR of the continuous kernels
 // (kernels_generic.h); it runs on the generic path 0 and, float64 width 20, on k_fused20d (path 7)
@@ -362,11 +366,13 @@ static bool is_adr(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR; }
 // the same equation with trainable coefficients: template value PDE_ADR_IDE, the six coefficients are the tail of theta
 // ([a0, a1, log nu, r1, r2, r3]); the same two paths
 static bool is_adr_ide(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR_IDE; }
-// the kinds whose tail is [a0, a1, log nu, r1, r2, r3] with a mask of the trained ones
-static bool has_adr_tail(const pinn_ctx* c) { return is_adr_ide(c) || is_adr_disc_ide(c); }
+// the kinds whose tail is [a0, a1, log nu, r1, r2, r3] (adrd_disc: and d3) with a mask of the trained ones
+static bool has_adr_tail(const pinn_ctx* c) { return is_adr_ide(c) || is_adr_disc_ide(c) || is_adrd_disc(c); }
 static bool adr_family(const pinn_ctx* c) { return is_adr(c) || is_adr_ide(c); }
 // trailing equation parameters of the flat weight vector
-static int tail_len(int pde) { return has_lambdas(pde) ? 2 : pde == PINN_PDE_ADR_IDE || pde == PINN_PDE_ADR_DISC_IDE ? 6 : 0; }
+static int tail_len(int pde) {
+  return has_lambdas(pde) ? 2 : pde == PINN_PDE_ADR_IDE || pde == PINN_PDE_ADR_DISC_IDE ? 6 : pde == PINN_PDE_ADRD_DISC ? 7 : 0;
+}
 // what a kernel of kind PDE takes in the place of the scalar nu
 template <typename real, int PDE>
 static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
@@ -1158,12 +1164,13 @@ static int disc_upload_tables(pinn_ctx* c, int ldo) {
   return 0;
 }
 
+static int disc_dk(const pinn_ctx* c);
 static int disc_alloc_scratch(pinn_ctx* c, const DiscDesc& dd, DevBuf<void>* Ast, DevBuf<void>* A3, DevBuf<void>& U3,
                               DevBuf<void>& Nn, DevBuf<void>& Rb) {
-  const size_t rs = real_size(c), H = c->nd.n_hidden;
-  if (Ast) HIPCHK(Ast->reserve_bytes(H * 3 * (size_t)dd.n_pad * dd.wp * rs));
-  if (A3) HIPCHK(A3->reserve_bytes(3 * (size_t)dd.n_pad * dd.wp * rs));
-  HIPCHK(U3.reserve_bytes(3 * (size_t)dd.n_pad * dd.ldo * rs));
+  const size_t rs = real_size(c), H = c->nd.n_hidden, NC = disc_nc(disc_dk(c));     // Taylor channels of the kind
+  if (Ast) HIPCHK(Ast->reserve_bytes(H * NC * (size_t)dd.n_pad * dd.wp * rs));
+  if (A3) HIPCHK(A3->reserve_bytes(NC * (size_t)dd.n_pad * dd.wp * rs));
+  HIPCHK(U3.reserve_bytes(NC * (size_t)dd.n_pad * dd.ldo * rs));
   HIPCHK(Nn.reserve_bytes((size_t)dd.n_pad * dd.ldo * rs));
   HIPCHK(Rb.reserve_bytes((size_t)dd.n_pad * dd.ldo * rs));
   return 0;
@@ -1211,9 +1218,10 @@ static int disc_ensure(pinn_ctx* c) {
   HIPCHK(hipMemcpy(c->d_ginfo, gi.data(), G * sizeof(int), hipMemcpyHostToDevice));
   if (disc_upload_tables(c, dd.ldo)) return PINN_EHIP;
   if (disc_alloc_scratch(c, dd, &c->d_Ast, &c->d_A3, c->d_U3, c->d_Nn, c->d_R)) return PINN_EHIP;
-  HIPCHK(c->d_dAp.reserve_bytes((size_t)dd.n_chunks * 3 * dd.n_pad * dd.wp * rs));
+  HIPCHK(c->d_dAp.reserve_bytes((size_t)dd.n_chunks * disc_nc(disc_dk(c)) * dd.n_pad * dd.wp * rs));
   HIPCHK(c->d_lossp.reserve_bytes((size_t)G * dd.n_chunks * rs));
-  const size_t n_lam = (size_t)G * dd.n_chunks * (is_adr_disc_ide(c) ? 6 : 2);     // [group * chunk][2], [...][6] for adr_disc_ide
+  // [group * chunk][2], [...][6] for adr_disc_ide, [...][7] for adrd_disc
+  const size_t n_lam = (size_t)G * dd.n_chunks * (has_adr_tail(c) ? tail_len(c->pde) : 2);
   HIPCHK(c->d_lamp.reserve_bytes(n_lam * rs));
   // cleared in stream order: the context's stream is non-blocking, so a hipMemset on the null stream (asynchronous to the
   // host for device memory) is not ordered before the first evaluation's kernels and can wipe rows they have written
@@ -1230,11 +1238,15 @@ static int disc_ensure(pinn_ctx* c) {
 // the operator kind of a discrete-time context (template value DK of kernels_disc.h) and its coefficient block, by value:
 // (1, nu) for the Burgers kinds (identification reads its own from the weight vector), the six of c->adr for adr_disc with
 // the rows the periodic groups' slope differences travel in (the context's Nn, or none for a prediction), the mask and those
-// rows for adr_disc_ide
-static int disc_dk(const pinn_ctx* c) { return is_adr_disc_ide(c) ? DISC_ADR_IDE : is_adr_disc(c) ? DISC_ADR : DISC_BURGERS; }
+// rows for adr_disc_ide, and with them the nu == 0 flag for adrd_disc
+static int disc_dk(const pinn_ctx* c) {
+  return is_adrd_disc(c) ? DISC_ADRD : is_adr_disc_ide(c) ? DISC_ADR_IDE : is_adr_disc(c) ? DISC_ADR : DISC_BURGERS;
+}
 template <typename real, int DK>
 static disc_coef_t<real, DK> disc_coef(const pinn_ctx* c, const real* pair_dx) {
-  if constexpr (DK == DISC_ADR_IDE)      // the coefficients are the tail of the weight vector; by value, which of them train
+  if constexpr (DK == DISC_ADRD)
+    return DiscAdrdArg<real>{c->adr_mask, c->nu_off ? 1 : 0, pair_dx};
+  else if constexpr (DK == DISC_ADR_IDE)      // the coefficients are the tail of the weight vector; by value, which of them train
     return DiscAdrIdeArg<real>{c->adr_mask, pair_dx};
   else if constexpr (DK == DISC_ADR)
     return DiscAdrArg<real>{(real)c->adr[0], (real)c->adr[1], (real)c->adr[2], (real)c->adr[3], (real)c->adr[4], (real)c->adr[5],
@@ -1248,11 +1260,11 @@ static int disc_set_lds() {
   static unsigned long long done = 0;
   if (!first_call_on_device(done)) return 0;
   HIPCHK(hipFuncSetAttribute((const void*)k_disc_fwd<real, NT, DK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)disc_fwd_lds<NT>(sizeof(real))));
+                             (int)disc_fwd_lds<NT, DK>(sizeof(real))));
   HIPCHK(hipFuncSetAttribute((const void*)k_disc_bwd_out<real, NT, DK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)disc_out_lds<NT, DK>(sizeof(real))));
   HIPCHK(hipFuncSetAttribute((const void*)k_disc_bwd_hidden<real, NT, DK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)disc_hid_lds<NT>(sizeof(real))));
+                             (int)disc_hid_lds<NT, DK>(sizeof(real))));
   return 0;
 }
 
@@ -1265,7 +1277,7 @@ static int disc_eval(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   const dim3 grid(dd.n_groups, dd.n_chunks), block(256);
   const real* th = c->theta_r.as<real>();
   if (ev4) HIPCHK(hipEventRecord(ev4[0], c->stream));
-  hipLaunchKernelGGL((k_disc_fwd<real, NT, DK>), grid, block, disc_fwd_lds<NT>(sizeof(real)), c->stream, c->nd, dd, th,
+  hipLaunchKernelGGL((k_disc_fwd<real, NT, DK>), grid, block, (disc_fwd_lds<NT, DK>(sizeof(real))), c->stream, c->nd, dd, th,
                      c->xs.as<real>(), m.lbx, m.sx, cf, c->d_Ast.as<real>(), c->d_A3.as<real>(), c->d_U3.as<real>(),
                      c->d_Nn.as<real>(), 1);
   hipLaunchKernelGGL((k_disc_irk<real, DK>), grid, block, 0, c->stream, dd, c->nd.n_out, c->d_ginfo,
@@ -1276,7 +1288,7 @@ static int disc_eval(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
                      th, c->d_ginfo, c->d_M[0].as<real>(), c->d_M[1].as<real>(), c->d_R.as<real>(),
                      c->d_U3.as<real>(), c->d_A3.as<real>(), cf, c->part.as<real>(), c->R, c->d_dAp.as<real>(),
                      c->d_lamp.as<real>());
-  hipLaunchKernelGGL((k_disc_bwd_hidden<real, NT, DK>), dim3(dd.n_groups), block, disc_hid_lds<NT>(sizeof(real)),
+  hipLaunchKernelGGL((k_disc_bwd_hidden<real, NT, DK>), dim3(dd.n_groups), block, (disc_hid_lds<NT, DK>(sizeof(real))),
                      c->stream, c->nd, dd, th, c->d_ginfo, c->xs.as<real>(), m.lbx, m.sx, c->d_Ast.as<real>(),
                      c->d_dAp.as<real>(), c->d_lossp.as<real>(), c->d_lamp.as<real>(), c->part.as<real>(), c->R);
   if (ev4) HIPCHK(hipEventRecord(ev4[2], c->stream));
@@ -1287,10 +1299,12 @@ static int disc_eval(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
 template <int DK>
 static int disc_eval_kind(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   if (c->dtype == PINN_F64) return disc_eval<double, 4, DK>(c, ev4, af);
-  return c->dd.wp == 64 ? disc_eval<float, 4, DK>(c, ev4, af) : disc_eval<float, 8, DK>(c, ev4, af);
+  if constexpr (DK == DISC_ADRD) return disc_eval<float, 4, DK>(c, ev4, af);     // widths above 64 are refused at create
+  else return c->dd.wp == 64 ? disc_eval<float, 4, DK>(c, ev4, af) : disc_eval<float, 8, DK>(c, ev4, af);
 }
 static int disc_eval_any(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   switch (disc_dk(c)) {
+    case DISC_ADRD: return disc_eval_kind<DISC_ADRD>(c, ev4, af);
     case DISC_ADR_IDE: return disc_eval_kind<DISC_ADR_IDE>(c, ev4, af);
     case DISC_ADR: return disc_eval_kind<DISC_ADR>(c, ev4, af);
     default: return disc_eval_kind<DISC_BURGERS>(c, ev4, af);
@@ -1337,7 +1351,7 @@ static int disc_predict_impl(pinn_ctx* c, int mode, int set, const double* x, in
   if (upload_real(c, xe, hx.data(), dd.n_pad)) return PINN_EHIP;
   if (hipMemcpy(ge, gi.data(), G * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return PINN_EHIP;
   const InMap<real> m(c->lb, c->ub);
-  const size_t lds_f = disc_fwd_lds<NT>(rs);
+  const size_t lds_f = disc_fwd_lds<NT, DK>(rs);
   if (int rc = disc_set_lds<real, NT, DK>()) return rc;
   const dim3 grid(dd.n_groups, dd.n_chunks), block(256);
   hipLaunchKernelGGL((k_disc_fwd<real, NT, DK>), grid, block, lds_f, c->stream, c->nd, dd, c->theta_r.as<real>(),
@@ -1359,11 +1373,13 @@ static int disc_predict_impl(pinn_ctx* c, int mode, int set, const double* x, in
 template <int DK>
 static int disc_predict_kind(pinn_ctx* c, int mode, int set, const double* x, int64_t n, double* out) {
   if (c->dtype == PINN_F64) return disc_predict_impl<double, 4, DK>(c, mode, set, x, n, out);
-  return c->nd.width <= 64 ? disc_predict_impl<float, 4, DK>(c, mode, set, x, n, out)
+  if constexpr (DK == DISC_ADRD) return disc_predict_impl<float, 4, DK>(c, mode, set, x, n, out);
+  else return c->nd.width <= 64 ? disc_predict_impl<float, 4, DK>(c, mode, set, x, n, out)
                            : disc_predict_impl<float, 8, DK>(c, mode, set, x, n, out);
 }
 static int disc_predict_any(pinn_ctx* c, int mode, int set, const double* x, int64_t n, double* out) {
   switch (disc_dk(c)) {
+    case DISC_ADRD: return disc_predict_kind<DISC_ADRD>(c, mode, set, x, n, out);
     case DISC_ADR_IDE: return disc_predict_kind<DISC_ADR_IDE>(c, mode, set, x, n, out);
     case DISC_ADR: return disc_predict_kind<DISC_ADR>(c, mode, set, x, n, out);
     default: return disc_predict_kind<DISC_BURGERS>(c, mode, set, x, n, out);
@@ -1770,12 +1786,18 @@ int pinn_device_info(int device, char* name, int cap, int* n_cu, int64_t* hbm_by
   return 0;
 }
 
-// PINN_PDE_ADR_IDE, PINN_PDE_ADR_DISC_IDE: raw [a0, a1, nu, r1, r2, r3] -> the tail of theta (log nu in the nu slot) and its compute-dtype mirror
+// PINN_PDE_ADR_IDE, PINN_PDE_ADR_DISC_IDE: raw [a0, a1, nu, r1, r2, r3] -> the tail of theta (log nu in the nu slot) and its compute-dtype mirror.
+// PINN_PDE_ADRD_DISC: seven, d3 raw behind them; nu == 0 raises c->nu_off and leaves 0.0 in the nu slot, nu > 0 lowers it
 static int adr_ide_write_tail(pinn_ctx* c, const double* p) {
-  double tail[6];
-  for (int i = 0; i < 6; ++i) tail[i] = i == 2 ? std::log(p[i]) : p[i];
+  const int nt = tail_len(c->pde);
+  double tail[7];
+  for (int i = 0; i < nt; ++i) tail[i] = i == 2 ? std::log(p[i]) : p[i];
+  if (is_adrd_disc(c)) {
+    c->nu_off = p[2] == 0.0;
+    if (c->nu_off) tail[2] = 0.0;
+  }
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(c->theta + c->nd.n_net, tail, sizeof(tail), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->theta + c->nd.n_net, tail, (size_t)nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));       // tail lives on this stack
   if (int rc = cast_weights(c)) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1861,7 +1883,7 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   REQUIRE(out && layers && lb && ub, "null argument");
   REQUIRE(n_layers >= 3 && n_layers <= MAX_DENSE + 1, "need 3..%d layer sizes, got %d", MAX_DENSE + 1, n_layers);
   REQUIRE(dtype == PINN_F32 || dtype == PINN_F64, "dtype must be PINN_F32 or PINN_F64");
-  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADR_DISC_IDE, "unknown pde kind %d", pde_kind);
+  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADRD_DISC, "unknown pde kind %d", pde_kind);
   const bool disc = disc_kind(pde_kind);
   if (disc) REQUIRE(layers[0] == 1, "discrete-time models take one input (x), got %d", layers[0]);
   else REQUIRE(layers[0] == 2, "input dimension must be 2 (x, t), got %d", layers[0]);
@@ -1872,6 +1894,10 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   REQUIRE(W >= 1 && W <= MAX_WIDTH, "hidden width %d outside 1..%d", W, MAX_WIDTH);
   if (disc) {
     REQUIRE(NO >= 1 && NO <= 65536, "output size %d outside 1..65536", NO);
+    // four Taylor channels: k_disc_bwd_hidden at NT = 8 would need 169 024 B of LDS, a CU has 163 840 B
+    if (pde_kind == PINN_PDE_ADRD_DISC && W > 64)
+      return fail(PINN_EUNSUPPORTED, "the adrd_disc kind: hidden width %d exceeds 64, what the four-channel kernels hold in LDS "
+                  "(float32 too)", W);
     REQUIRE(W <= (dtype == PINN_F64 ? 64 : 128), "discrete-time models: hidden width %d exceeds what the LDS-resident "
             "kernels hold (64 in float64, 128 in float32)", W);
   }
@@ -2139,6 +2165,14 @@ int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
     c->nu = p[2];
     return 0;
   }
+  if (is_adrd_disc(c)) {  // raw a0, a1, nu, r1, r2, r3, d3 -> the tail of theta; nu == 0 is allowed (the flag); nothing changes on a refusal
+    REQUIRE(n == 7, "pinn_set_pde_params: the adrd_disc kind takes 7 coefficients (a0, a1, nu, r1, r2, r3, d3), got %d", n);
+    for (int i = 0; i < 7; ++i) REQUIRE(std::isfinite(p[i]), "pinn_set_pde_params: coefficient %d is not finite", i);
+    REQUIRE(p[2] >= 0.0, "pinn_set_pde_params: the adrd_disc kind stores log nu, so nu must be positive or exactly 0 (got %g)", p[2]);
+    REQUIRE(p[2] > 0.0 || !(c->adr_mask & 4), "pinn_set_pde_params: nu must be positive to be trained (the nu bit of the "
+            "trainable mask is set)");
+    return adr_ide_write_tail(c, p);
+  }
   if (has_adr_tail(c)) {  // raw a0, a1, nu, r1, r2, r3 -> the tail of theta; nothing changes on a refusal
     const char* kind = is_adr_ide(c) ? "adr_ide" : "adr_disc_ide";
     REQUIRE(n == 6, "pinn_set_pde_params: the %s kind takes 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", kind, n);
@@ -2152,13 +2186,14 @@ int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
 
 int pinn_get_pde_params(pinn_ctx* c, double* p, int n) {
   REQUIRE(c && p, "null");
-  if (is_adr(c) || has_adr_tail(c) || is_adr_disc(c)) REQUIRE(n == 6, "pinn_get_pde_params: this kind has 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
+  if (is_adrd_disc(c)) REQUIRE(n == 7, "pinn_get_pde_params: this kind has 7 coefficients (a0, a1, nu, r1, r2, r3, d3), got %d", n);
+  else if (is_adr(c) || has_adr_tail(c) || is_adr_disc(c)) REQUIRE(n == 6, "pinn_get_pde_params: this kind has 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
   else REQUIRE(n == 1, "pinn_get_pde_params: this kind has 1 parameter (nu), got %d", n);
   if (has_adr_tail(c)) {
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(p, c->theta + c->nd.n_net, 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(p, c->theta + c->nd.n_net, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    p[2] = std::exp(p[2]);
+    p[2] = c->nu_off ? 0.0 : std::exp(p[2]);
   } else if (is_adr(c) || is_adr_disc(c)) {
     for (int i = 0; i < 6; ++i) p[i] = c->adr[i];
   } else {
@@ -2172,6 +2207,12 @@ int pinn_set_pde_trainable(pinn_ctx* c, int mask) {
   if (!has_adr_tail(c))
     return fail(PINN_EUNSUPPORTED, "pinn_set_pde_trainable: only the adr_ide kind (pde 6) and its discrete-time form, the "
                 "adr_disc_ide kind (pde 8), have trainable coefficients to choose from");
+  if (is_adrd_disc(c)) {
+    REQUIRE(mask >= 0 && mask <= 127, "pinn_set_pde_trainable: mask %d is outside 0..127 (bit k = coefficient k of a0, a1, nu, r1, r2, r3, d3)", mask);
+    REQUIRE(!(mask & 4) || !c->nu_off, "pinn_set_pde_trainable: nu must be positive to be trained (it is 0: pinn_set_pde_params)");
+    c->adr_mask = mask;
+    return 0;
+  }
   REQUIRE(mask >= 0 && mask <= 63, "pinn_set_pde_trainable: mask %d is outside 0..63 (bit k = coefficient k of a0, a1, nu, r1, r2, r3)", mask);
   c->adr_mask = mask;
   return 0;
@@ -2728,7 +2769,7 @@ int pinn_disc_set_periodic(pinn_ctx* c, const double* x_lb, const double* x_ub, 
   REQUIRE(c, "null");
   if (!has_pairs(c))
     return fail(PINN_EUNSUPPORTED, "pinn_disc_set_periodic: periodic pairs are for the adr_disc kind (pde 7) and the "
-                "adr_disc_ide kind (pde 8) only");
+                "adr_disc_ide kind (pde 8) only");      // (and adrd_disc, pde 9; the wording is pinned by the earlier kinds' tests)
   REQUIRE(order == 0 || order == 1, "pinn_disc_set_periodic: order %d outside 0..1 (0: values, 1: values and slopes)", order);
   REQUIRE(n >= 0 && n <= (1 << 24), "pinn_disc_set_periodic: bad pair count");
   REQUIRE(n == 0 || (x_lb && x_ub), "pinn_disc_set_periodic: null argument");

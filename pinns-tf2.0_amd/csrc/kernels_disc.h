@@ -14,12 +14,16 @@
 //                 [a0, a1, log nu, r1, r2, r3] (pde 8), as pde 4 reads its two; by value go the mask of the trained ones and
 //                 the pairs' rows.  k_disc_bwd_out forms the six sums of dN dN/dp_k beside db_out and leaves them, masked,
 //                 in lamp [group * chunk][6]; k_disc_bwd_hidden adds the chunks in a fixed order.  No atomics anywhere.
+//   DISC_ADRD     DISC_ADR_IDE with a dispersion term, N = ... + d3 U_xxx (pde 9: KdV, KdV-Burgers): FOUR Taylor channels
+//                 (value, d/dx, d2/dx2, d3/dx3) through both sweeps -- disc_nc(DK) planes wherever the others carry three --
+//                 and a seventh tail entry, th[n_net + 6] = d3 (raw), with a seventh sum dN U_xxx in lamp [...][7].  nu = 0
+//                 is a flag by value (nu_off): the nu slot is then not read and the kernels compute with nu = 0.
 //
 // Unlike the continuous models this path is GEMM shaped (hidden 50, 501 outputs, a 500 x 501 IRK table) over a
 // few hundred points, so every contraction runs on v_mfma_{f32,f64}_16x16x4 and the evaluation is four launches
 // whose grids are (16-point groups) x (64-column chunks of the output dimension):
 //
-//   k_disc_fwd         hidden layers (3 Taylor channels value / d/dx / d2/dx2, recomputed per chunk, LDS resident),
+//   k_disc_fwd         hidden layers (3 Taylor channels value / d/dx / d2/dx2 -- 4 for DISC_ADRD --, recomputed per chunk, LDS resident),
 //                      output-layer chunk, N chunk                              -> U3, Nn (+ stash for the reverse)
 //   k_disc_irk         R = U + Nn M^T - target (K = q), sum R^2                 -> R, loss partials
 //   k_disc_bwd_out     dN = 2 R M (K = n_out), output-channel adjoints G_c, dW_out / db_out partial rows,
@@ -54,8 +58,13 @@ struct DiscDesc {
 __host__ __device__ inline int disc_ginfo(int set, int n_valid) { return set | (n_valid << 8); }
 
 // operator kinds (template value DK of the kernels) and what each takes by value as its coefficients
-enum { DISC_BURGERS = 0, DISC_ADR = 1, DISC_ADR_IDE = 2 };
-constexpr bool disc_adr_like(int DK) { return DK == DISC_ADR || DK == DISC_ADR_IDE; }
+enum { DISC_BURGERS = 0, DISC_ADR = 1, DISC_ADR_IDE = 2, DISC_ADRD = 3 };
+constexpr bool disc_adr_like(int DK) { return DK == DISC_ADR || DK == DISC_ADR_IDE || DK == DISC_ADRD; }
+// Taylor channels carried through the forward and reverse sweeps, and the kinds whose coefficients are the tail of the weight
+// vector with the length of that tail
+constexpr int disc_nc(int DK) { return DK == DISC_ADRD ? 4 : 3; }
+constexpr bool disc_adr_tail(int DK) { return DK == DISC_ADR_IDE || DK == DISC_ADRD; }
+constexpr int disc_ntail(int DK) { return DK == DISC_ADRD ? 7 : 6; }
 template <typename real> struct DiscC12 { real c1, c2; };
 // the six coefficients, and [n_pad][ldo] rows that hold the slope differences of the periodic groups between k_disc_irk and
 // k_disc_bwd_out (the engine hands Nn: nothing else reads those rows of a group without a table).  Here and not a kernel
@@ -63,9 +72,12 @@ template <typename real> struct DiscC12 { real c1, c2; };
 template <typename real> struct DiscAdrArg { real a0, a1, nu, r1, r2, r3; const real* pair_dx; };
 // DISC_ADR_IDE: bit k of mask set = coefficient k is trained (a frozen one's gradient entry is written as 0.0)
 template <typename real> struct DiscAdrIdeArg { int mask; const real* pair_dx; };
+// DISC_ADRD: the mask over seven (bit 6 = d3), and nu_off = 1 where nu is 0 (the tail's log nu slot is then not read)
+template <typename real> struct DiscAdrdArg { int mask; int nu_off; const real* pair_dx; };
 template <typename real, int DK> struct DiscCoefT { using type = DiscC12<real>; };
 template <typename real> struct DiscCoefT<real, DISC_ADR> { using type = DiscAdrArg<real>; };
 template <typename real> struct DiscCoefT<real, DISC_ADR_IDE> { using type = DiscAdrIdeArg<real>; };
+template <typename real> struct DiscCoefT<real, DISC_ADRD> { using type = DiscAdrdArg<real>; };
 template <typename real, int DK> using disc_coef_t = typename DiscCoefT<real, DK>::type;
 
 // DISC_ADR: a group of periodic pairs.  Pair count (1..8) in bits 8..15 of the descriptor, order (0: values, 1: values and
@@ -100,6 +112,8 @@ template <typename real, int DK>
 __device__ __forceinline__ AdrCoef<real> disc_adr_coefs(const disc_coef_t<real, DK>& cf, const real* __restrict__ tail) {
   if constexpr (DK == DISC_ADR_IDE)
     return AdrCoef<real>{tail[0], tail[1], first_lane(exp_r(tail[2])), tail[3], tail[4], tail[5]};
+  else if constexpr (DK == DISC_ADRD)      // (d3 = tail[6] is read beside this block, where it is used)
+    return AdrCoef<real>{tail[0], tail[1], cf.nu_off ? real(0) : first_lane(exp_r(tail[2])), tail[3], tail[4], tail[5]};
   else
     return AdrCoef<real>{cf.a0, cf.a1, cf.nu, cf.r1, cf.r2, cf.r3};
 }
@@ -114,15 +128,17 @@ template <int NT> struct DiscGeo {
   static constexpr int NPRE = WP * WP / 256;   // register-staged weight values per thread
   static constexpr int NPRE_O = WP * 64 / 256; // ... for a [WP][64] output-layer chunk
 };
-template <int NT> inline size_t disc_fwd_lds(size_t rs) {
-  return (size_t)(2 * 3 * DiscGeo<NT>::CS + DiscGeo<NT>::WP * DiscGeo<NT>::WLD) * rs;
+template <int NT, int DK = DISC_BURGERS> inline size_t disc_fwd_lds(size_t rs) {
+  return (size_t)(2 * disc_nc(DK) * DiscGeo<NT>::CS + DiscGeo<NT>::WP * DiscGeo<NT>::WLD) * rs;
 }
-// (the last term is wsum: [4 waves][2] for pde 4, [4 waves][6] for DISC_ADR_IDE; the other kinds launch with what they had)
+// (the last term is wsum: [4 waves][2] for pde 4, [4 waves][6] for DISC_ADR_IDE, [4 waves][7] for DISC_ADRD; the other kinds
+// launch with what they had)
 template <int NT, int DK = DISC_BURGERS> inline size_t disc_out_lds(size_t rs) {
-  return (size_t)(3 * 16 * 68 + 3 * DiscGeo<NT>::CS + DiscGeo<NT>::WP * 68 + (DK == DISC_ADR_IDE ? 24 : 8)) * rs;
+  return (size_t)(disc_nc(DK) * 16 * 68 + disc_nc(DK) * DiscGeo<NT>::CS + DiscGeo<NT>::WP * 68 +
+                  (disc_adr_tail(DK) ? 4 * disc_ntail(DK) : 8)) * rs;
 }
-template <int NT> inline size_t disc_hid_lds(size_t rs) {
-  return (size_t)(3 * 3 * DiscGeo<NT>::CS + DiscGeo<NT>::WP * DiscGeo<NT>::TLD + 16) * rs;
+template <int NT, int DK = DISC_BURGERS> inline size_t disc_hid_lds(size_t rs) {
+  return (size_t)(3 * disc_nc(DK) * DiscGeo<NT>::CS + DiscGeo<NT>::WP * DiscGeo<NT>::TLD + 16) * rs;
 }
 
 // register staging of a [rows <= WP][cols] weight tile: thread t holds elements t, t + 256, ... of the padded
@@ -199,6 +215,7 @@ __host__ __device__ inline int disc_kblocks(int K) { return ((K + 15) / 16 + 3) 
 //                           pre-activation -- what the reverse sweep needs (written by chunk 0 only)
 //   A3  [3][n_pad][wp]      output channels (a, a_x, a_xx) of the last hidden layer
 //   U3  [3][n_pad][ldo]     (U, U_x, U_xx) of the output layer;  Nn [n_pad][ldo] = N(U) of the kind DK (0 beyond q)
+//   DISC_ADRD: a fourth plane everywhere (z_xxx, a_xxx, U_xxx), [H][4], [4] and [4]
 // ---------------------------------------------------------------------------------------------------------
 template <typename real, int NT, int DK>
 __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const real* __restrict__ th,
@@ -209,10 +226,10 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
   using TR = FusedTraits<real>;
   using acc_t = typename TR::acc_t;
   using GEO = DiscGeo<NT>;
-  constexpr int WP = GEO::WP, LD = GEO::LD, CS = GEO::CS, WLD = GEO::WLD;
+  constexpr int WP = GEO::WP, LD = GEO::LD, CS = GEO::CS, WLD = GEO::WLD, NC = disc_nc(DK);
   extern __shared__ __attribute__((aligned(16))) char disc_smem[];
-  real* act = reinterpret_cast<real*>(disc_smem);          // [2][3][16][LD]
-  real* wb = act + 2 * 3 * CS;                             // [WP][WLD] weights of the layer being applied
+  real* act = reinterpret_cast<real*>(disc_smem);          // [2][NC][16][LD]
+  real* wb = act + 2 * NC * CS;                            // [WP][WLD] weights of the layer being applied
   const int G = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int W = nd.width, H = nd.n_hidden, NO = nd.n_out;
   const int n_pad = dd.n_pad, ldo = dd.ldo;
@@ -225,12 +242,15 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
   if (H > 1) wt_load<real, NT, WP>(pre, th + nd.off_w[1], W, W, W, tid);
   else wt_load<real, NT, WP>(pre, th + nd.off_w[H] + 64 * ch, NO, W, min(64, NO - 64 * ch), tid);
   [[maybe_unused]] AdrCoef<real> k6{};                     // DISC_ADR_IDE: the tail's, behind the first weight loads
-  if constexpr (DK == DISC_ADR_IDE) k6 = disc_adr_coefs<real, DK>(cf, th + nd.n_net);
+  if constexpr (disc_adr_tail(DK)) k6 = disc_adr_coefs<real, DK>(cf, th + nd.n_net);
+  [[maybe_unused]] real kd3 = 0;                           // DISC_ADRD: the seventh
+  if constexpr (DK == DISC_ADRD) kd3 = th[nd.n_net + 6];
 
-  // dense 0 (fan_in 1): h = sx (x - lb) - 1, h_x = sx, h_xx = 0
+  // dense 0 (fan_in 1): h = sx (x - lb) - 1, h_x = sx, h_xx = h_xxx = 0
   for (int i = tid; i < 16 * WP; i += 256) {
     const int p = i / WP, j = i % WP;
     real a = 0, zp = 0, ax = 0, axx = 0;
+    [[maybe_unused]] real axxx = 0;
     if (j < W) {
       const real w0 = th[nd.off_w[0] + j], b0 = th[nd.off_b[0] + j];
       const real h = sx * (xs[16 * G + p] - lbx) - real(1);
@@ -239,15 +259,18 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
       const real d1 = real(1) - a * a, d2 = real(-2) * a * d1;
       ax = d1 * zp;
       axx = d2 * zp * zp;
+      if constexpr (NC == 4) axxx = real(-2) * d1 * (real(1) - real(3) * a * a) * zp * zp * zp;
     }
     act[0 * CS + p * LD + j] = a;
     act[1 * CS + p * LD + j] = ax;
     act[2 * CS + p * LD + j] = axx;
+    if constexpr (NC == 4) act[3 * CS + p * LD + j] = axxx;
     if (stash) {
       const size_t o = (size_t)(16 * G + p) * WP + j;
       Ast[(size_t)0 * n_pad * WP + o] = a;
       Ast[(size_t)1 * n_pad * WP + o] = zp;
       Ast[(size_t)2 * n_pad * WP + o] = 0;
+      if constexpr (NC == 4) Ast[(size_t)3 * n_pad * WP + o] = 0;
     }
   }
 
@@ -260,12 +283,13 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
     if (l + 1 < H) wt_load<real, NT, WP>(pre, th + nd.off_w[l + 1], W, W, W, tid);
     else wt_load<real, NT, WP>(pre, th + nd.off_w[H] + 64 * ch, NO, W, min(64, NO - 64 * ch), tid);
     const real* __restrict__ bl = th + nd.off_b[l];
-    const real* in = act + cur * 3 * CS;
-    real* out = act + (cur ^ 1) * 3 * CS;
+    const real* in = act + cur * NC * CS;
+    real* out = act + (cur ^ 1) * NC * CS;
     for (int ct = wave; ct < NT; ct += 4) {
       const int j = 16 * ct + m;
       const real bj = j < W ? bl[j] : real(0);
       acc_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0};
+      [[maybe_unused]] acc_t acc3 = {0, 0, 0, 0};
 #pragma unroll 4
       for (int ks = 0; ks < ksteps; ++ks) {
         const int k = 4 * ks + g;
@@ -274,6 +298,7 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
         acc0 = TR::mfma(ap[0], b, acc0);
         acc1 = TR::mfma(ap[CS], b, acc1);
         acc2 = TR::mfma(ap[2 * CS], b, acc2);
+        if constexpr (NC == 4) acc3 = TR::mfma(ap[3 * CS], b, acc3);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -284,11 +309,16 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
         out[0 * CS + p * LD + j] = a;
         out[1 * CS + p * LD + j] = d1 * zp;
         out[2 * CS + p * LD + j] = d2 * zp * zp + d1 * zr;
+        if constexpr (NC == 4) {   // a''' = d3t z'^3 + 3 d2 z' z'' + d1 z'''
+          const real d3t = real(-2) * d1 * (real(1) - real(3) * a * a);
+          out[3 * CS + p * LD + j] = d3t * zp * zp * zp + real(3) * d2 * zp * zr + d1 * acc3[r];
+        }
         if (stash) {
           const size_t o = (size_t)(16 * G + p) * WP + j;
-          Ast[((size_t)l * 3 + 0) * n_pad * WP + o] = a;
-          Ast[((size_t)l * 3 + 1) * n_pad * WP + o] = zp;
-          Ast[((size_t)l * 3 + 2) * n_pad * WP + o] = zr;
+          Ast[((size_t)l * NC + 0) * n_pad * WP + o] = a;
+          Ast[((size_t)l * NC + 1) * n_pad * WP + o] = zp;
+          Ast[((size_t)l * NC + 2) * n_pad * WP + o] = zr;
+          if constexpr (NC == 4) Ast[((size_t)l * NC + 3) * n_pad * WP + o] = acc3[r];
         }
       }
     }
@@ -297,9 +327,9 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
   __syncthreads();
   wt_store<real, NT, WP>(pre, wb, WLD, tid);               // output-layer chunk [W][64] (zero padded to [WP][WP])
   __syncthreads();
-  const real* in = act + cur * 3 * CS;
+  const real* in = act + cur * NC * CS;
   if (stash)
-    for (int i = tid; i < 3 * 16 * WP; i += 256) {
+    for (int i = tid; i < NC * 16 * WP; i += 256) {
       const int c = i / (16 * WP), rem = i % (16 * WP), p = rem / WP, j = rem % WP;
       A3[((size_t)c * n_pad + 16 * G + p) * WP + j] = in[c * CS + p * LD + j];
     }
@@ -308,6 +338,7 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
     const int jl = 16 * wave + m, j = 64 * ch + jl;
     const real bj = j < NO ? th[nd.off_b[H] + j] : real(0);
     acc_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0};
+    [[maybe_unused]] acc_t acc3 = {0, 0, 0, 0};
 #pragma unroll 4
     for (int ks = 0; ks < ksteps; ++ks) {
       const int k = 4 * ks + g;
@@ -316,6 +347,7 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
       acc0 = TR::mfma(ap[0], b, acc0);
       acc1 = TR::mfma(ap[CS], b, acc1);
       acc2 = TR::mfma(ap[2 * CS], b, acc2);
+      if constexpr (NC == 4) acc3 = TR::mfma(ap[3 * CS], b, acc3);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -324,7 +356,11 @@ __global__ __launch_bounds__(256) void k_disc_fwd(NetDesc nd, DiscDesc dd, const
       U3[((size_t)0 * n_pad + gp) * ldo + j] = U;
       U3[((size_t)1 * n_pad + gp) * ldo + j] = Ux;
       U3[((size_t)2 * n_pad + gp) * ldo + j] = Uxx;
-      if constexpr (DK == DISC_ADR)
+      if constexpr (NC == 4) U3[((size_t)3 * n_pad + gp) * ldo + j] = acc3[r];
+      if constexpr (DK == DISC_ADRD)
+        Nn[gp * ldo + j] = j < dd.q ? (k6.a0 + k6.a1 * U) * Ux - k6.nu * Uxx + kd3 * acc3[r] + U * (k6.r1 + U * (k6.r2 + k6.r3 * U))
+                                    : real(0);
+      else if constexpr (DK == DISC_ADR)
         Nn[gp * ldo + j] = j < dd.q ? (cf.a0 + cf.a1 * U) * Ux - cf.nu * Uxx + U * (cf.r1 + U * (cf.r2 + cf.r3 * U)) : real(0);
       else if constexpr (DK == DISC_ADR_IDE)
         Nn[gp * ldo + j] = j < dd.q ? (k6.a0 + k6.a1 * U) * Ux - k6.nu * Uxx + U * (k6.r1 + U * (k6.r2 + k6.r3 * U)) : real(0);
@@ -427,12 +463,12 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
   using TR = FusedTraits<real>;
   using acc_t = typename TR::acc_t;
   using GEO = DiscGeo<NT>;
-  constexpr int WP = GEO::WP, LD = GEO::LD, CS = GEO::CS, GL = 68, OL = 68;
+  constexpr int WP = GEO::WP, LD = GEO::LD, CS = GEO::CS, GL = 68, OL = 68, NC = disc_nc(DK), NTL = disc_ntail(DK);
   extern __shared__ __attribute__((aligned(16))) char disc_smem[];
-  real* Gs = reinterpret_cast<real*>(disc_smem);           // [3][16][GL] output-channel adjoints of this chunk
-  real* a3s = Gs + 3 * 16 * GL;                            // [3][16][LD] last hidden layer's output channels
-  real* wos = a3s + 3 * CS;                                // [WP][OL] output-layer weights of this chunk
-  real* wsum = wos + WP * OL;                              // [4][2]  (DISC_ADR_IDE: [4][6])
+  real* Gs = reinterpret_cast<real*>(disc_smem);           // [NC][16][GL] output-channel adjoints of this chunk
+  real* a3s = Gs + NC * 16 * GL;                           // [NC][16][LD] last hidden layer's output channels
+  real* wos = a3s + NC * CS;                               // [WP][OL] output-layer weights of this chunk
+  real* wsum = wos + WP * OL;                              // [4][2]  (DISC_ADR_IDE: [4][6], DISC_ADRD: [4][7])
   const int G = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int W = nd.width, H = nd.n_hidden, NO = nd.n_out, ldo = dd.ldo, n_pad = dd.n_pad;
   const int m = lane & 15, g = lane >> 4;
@@ -446,23 +482,27 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
   real c1 = 0, c2 = 0;
   if constexpr (DK == DISC_BURGERS) disc_coefs(nd, dd, th, cf.c1, cf.c2, c1, c2);
   [[maybe_unused]] AdrCoef<real> k6{};
-  if constexpr (DK == DISC_ADR_IDE) k6 = disc_adr_coefs<real, DK>(cf, th + nd.n_net);
+  if constexpr (disc_adr_tail(DK)) k6 = disc_adr_coefs<real, DK>(cf, th + nd.n_net);
+  [[maybe_unused]] real kd3 = 0;
+  if constexpr (DK == DISC_ADRD) kd3 = th[nd.n_net + 6];
   const int jl = 16 * wave + m, j = 64 * ch + jl;
 
   // operands of the later phases: issued now, parked in registers during the contraction
-  real pa[3 * 16 * WP / 256], pw[GEO::NPRE_O];
+  real pa[NC * 16 * WP / 256], pw[GEO::NPRE_O];
 #pragma unroll
-  for (int n = 0; n < 3 * 16 * WP / 256; ++n) {
+  for (int n = 0; n < NC * 16 * WP / 256; ++n) {
     const int i = tid + 256 * n, c = i / (16 * WP), rem = i % (16 * WP);
     pa[n] = A3[((size_t)c * n_pad + 16 * G + rem / WP) * WP + rem % WP];
   }
   wt_load<real, NT, 64>(pw, th + nd.off_w[H] + 64 * ch, NO, W, min(64, NO - 64 * ch), tid);
   real Rv[4], Uv[4], Uxv[4], Uxxv[4];
+  [[maybe_unused]] real Uxxxv[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const size_t o = (size_t)(16 * G + TR::out_row(lane, r)) * ldo + j;
     Rv[r] = R[o]; Uv[r] = U3[o]; Uxv[r] = U3[(size_t)n_pad * ldo + o];
-    if constexpr (DK == DISC_ADR_IDE) Uxxv[r] = U3[(size_t)2 * n_pad * ldo + o];      // always: d/d log nu needs the plane
+    if constexpr (DK == DISC_ADRD) Uxxxv[r] = U3[(size_t)3 * n_pad * ldo + o];        // d/d d3 needs the plane
+    if constexpr (disc_adr_tail(DK)) Uxxv[r] = U3[(size_t)2 * n_pad * ldo + o];       // always: d/d log nu needs the plane
     else Uxxv[r] = dd.identify ? U3[(size_t)2 * n_pad * ldo + o] : real(0);
     if constexpr (disc_adr_like(DK))
       if (periodic) Uxv[r] = cf.pair_dx[o];     // the slope differences k_disc_irk left there
@@ -474,12 +514,12 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
       acc = disc_gemm_k<real>(R + (size_t)(16 * G + m) * ldo + 4 * g, M + (size_t)(4 * g) * ldo + j, ldo,
                               disc_kblocks(NO));
     real l1p = 0, l2p = 0, bsum = 0;
-    [[maybe_unused]] real t6[6] = {0, 0, 0, 0, 0, 0};
+    [[maybe_unused]] real t6[NTL] = {};
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int p = TR::out_row(lane, r);
       const real dN = real(2) * acc[r];
-      if constexpr (DK == DISC_ADR_IDE) {
+      if constexpr (disc_adr_tail(DK)) {
         // DISC_ADR's seeds from the products the six sums are made of: dN U_x, dN U, dN U^2 (t6[2] takes -nu behind wave_sum)
         const real U = Uv[r];
         real g0 = real(2) * Rv[r], g1 = real(2) * Uxv[r], g2 = real(0);
@@ -490,10 +530,12 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
           g2 = -k6.nu * dN;
           t6[0] += dUx; t6[1] += dUx * U; t6[2] += dN * Uxxv[r];
           t6[3] += dU;  t6[4] += dU2;     t6[5] += dU2 * U;
+          if constexpr (DK == DISC_ADRD) t6[6] += dN * Uxxxv[r];
         }
         Gs[(0 * 16 + p) * GL + jl] = g0;
         Gs[(1 * 16 + p) * GL + jl] = g1;
         Gs[(2 * 16 + p) * GL + jl] = g2;
+        if constexpr (DK == DISC_ADRD) Gs[(3 * 16 + p) * GL + jl] = periodic ? real(0) : kd3 * dN;   // g3: nothing from the pairs
         bsum += g0;
       } else if constexpr (DK == DISC_ADR) {
         const real U = Uv[r];
@@ -526,18 +568,18 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
       l2p = wave_sum(l2p);
       if (lane == 0) { wsum[wave * 2 + 0] = l1p; wsum[wave * 2 + 1] = l2p; }
     }
-    if constexpr (DK == DISC_ADR_IDE) {   // the wave's tile first, then the four waves through LDS: a fixed order
+    if constexpr (disc_adr_tail(DK)) {    // the wave's tile first, then the four waves through LDS: a fixed order
 #pragma unroll
-      for (int k = 0; k < 6; ++k) t6[k] = wave_sum(t6[k]);
+      for (int k = 0; k < NTL; ++k) t6[k] = wave_sum(t6[k]);
       t6[2] *= -k6.nu;
       if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) wsum[wave * 6 + k] = t6[k];
+        for (int k = 0; k < NTL; ++k) wsum[wave * NTL + k] = t6[k];
       }
     }
   }
 #pragma unroll
-  for (int n = 0; n < 3 * 16 * WP / 256; ++n) {
+  for (int n = 0; n < NC * 16 * WP / 256; ++n) {
     const int i = tid + 256 * n, c = i / (16 * WP), rem = i % (16 * WP);
     a3s[c * CS + (rem / WP) * LD + rem % WP] = pa[n];
   }
@@ -545,17 +587,17 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
   __syncthreads();
   if (dd.identify && tid < 2)
     lamp[(size_t)(G * dd.n_chunks + ch) * 2 + tid] = (wsum[tid] + wsum[2 + tid]) + (wsum[4 + tid] + wsum[6 + tid]);
-  if constexpr (DK == DISC_ADR_IDE)
-    if (tid < 6)
-      lamp[(size_t)(G * dd.n_chunks + ch) * 6 + tid] =
-          ((cf.mask >> tid) & 1) ? (wsum[tid] + wsum[6 + tid]) + (wsum[12 + tid] + wsum[18 + tid]) : real(0);
+  if constexpr (disc_adr_tail(DK))
+    if (tid < NTL)
+      lamp[(size_t)(G * dd.n_chunks + ch) * NTL + tid] =
+          ((cf.mask >> tid) & 1) ? (wsum[tid] + wsum[NTL + tid]) + (wsum[2 * NTL + tid] + wsum[3 * NTL + tid]) : real(0);
 
-  {  // dW_out[k][j] partial of this group: sum over 3 channels x 16 points of A3_c[p][k] G_c[p][j]
+  {  // dW_out[k][j] partial of this group: sum over the channels x 16 points of A3_c[p][k] G_c[p][j]
     acc_t acc[NT];
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt) acc[rt] = acc_t{0, 0, 0, 0};
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
+    for (int c = 0; c < NC; ++c)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         const int p = 4 * ks + g;
@@ -578,6 +620,7 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
   for (int kt = wave; kt < NT; kt += 4) {
     const int k = 16 * kt + m;
     acc_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0};
+    [[maybe_unused]] acc_t acc3 = {0, 0, 0, 0};
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
       const int jj = 4 * ks + g;
@@ -585,20 +628,26 @@ __global__ __launch_bounds__(256) void k_disc_bwd_out(NetDesc nd, DiscDesc dd, c
       acc0 = TR::mfma(Gs[(0 * 16 + m) * GL + jj], b, acc0);
       acc1 = TR::mfma(Gs[(1 * 16 + m) * GL + jj], b, acc1);
       acc2 = TR::mfma(Gs[(2 * 16 + m) * GL + jj], b, acc2);
+      if constexpr (NC == 4) acc3 = TR::mfma(Gs[(3 * 16 + m) * GL + jj], b, acc3);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const size_t gp = 16 * G + TR::out_row(lane, r);
-      dAp[(((size_t)ch * 3 + 0) * n_pad + gp) * WP + k] = acc0[r];
-      dAp[(((size_t)ch * 3 + 1) * n_pad + gp) * WP + k] = acc1[r];
-      dAp[(((size_t)ch * 3 + 2) * n_pad + gp) * WP + k] = acc2[r];
+      dAp[(((size_t)ch * NC + 0) * n_pad + gp) * WP + k] = acc0[r];
+      dAp[(((size_t)ch * NC + 1) * n_pad + gp) * WP + k] = acc1[r];
+      dAp[(((size_t)ch * NC + 2) * n_pad + gp) * WP + k] = acc2[r];
+      if constexpr (NC == 4) dAp[(((size_t)ch * NC + 3) * n_pad + gp) * WP + k] = acc3[r];
     }
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // reverse, hidden layers (one workgroup per 16-point group).  Adjoint algebra: SURVEY.md Appendix A.3 with the
-// t channel dropped (oracle/mlp.py taylor_backward).
+// t channel dropped (oracle/mlp.py taylor_backward).  DISC_ADRD carries a fourth channel: with a = tanh z, d1 = 1 - a^2,
+// d2 = -2 a d1, d3 = -2 d1 (1 - 3 a^2), d4 = 8 a d1 (2 - 3 a^2) and (hb, pb, rb, sb) the adjoints of (a, a', a'', a'''),
+//   gz0 = d1 hb + d2 z' pb + (d3 z'^2 + d2 z'') rb + (d4 z'^3 + 3 d3 z' z'' + d2 z''') sb
+//   gz1 = d1 pb + 2 d2 z' rb + 3 (d3 z'^2 + d2 z'') sb,   gz2 = d1 rb + 3 d2 z' sb,   gz3 = d1 sb
+// (sb = 0: the three-channel algebra).
 // ---------------------------------------------------------------------------------------------------------
 template <typename real, int NT, int DK>
 __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd, const real* __restrict__ th,
@@ -612,33 +661,33 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
   using TR = FusedTraits<real>;
   using acc_t = typename TR::acc_t;
   using GEO = DiscGeo<NT>;
-  constexpr int WP = GEO::WP, LD = GEO::LD, CS = GEO::CS, TLD = GEO::TLD;
+  constexpr int WP = GEO::WP, LD = GEO::LD, CS = GEO::CS, TLD = GEO::TLD, NC = disc_nc(DK), NTL = disc_ntail(DK);
   constexpr int EPT = 16 * WP / 256;                       // (point, feature) elements per thread
   extern __shared__ __attribute__((aligned(16))) char disc_smem[];
   const int G = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int W = nd.width, H = nd.n_hidden, n_pad = dd.n_pad;
   const int m = lane & 15, g = lane >> 4;
-  real* adj = reinterpret_cast<real*>(disc_smem);   // [3][16][LD] adjoint of the layer's output channels
-  real* gz = adj + 3 * CS;                          // adjoint of the pre-activation channels
-  real* inp = gz + 3 * CS;                          // the layer's input channels
-  real* wt = inp + 3 * CS;                          // [WP][TLD] weights of the layer being reversed
+  real* adj = reinterpret_cast<real*>(disc_smem);   // [NC][16][LD] adjoint of the layer's output channels
+  real* gz = adj + NC * CS;                         // adjoint of the pre-activation channels
+  real* inp = gz + NC * CS;                         // the layer's input channels
+  real* wt = inp + NC * CS;                         // [WP][TLD] weights of the layer being reversed
   real* hs = wt + WP * TLD;                         // [16] normalised inputs of the group's points
   real* __restrict__ row = part + (size_t)G * R_cols;
 
-  if constexpr (DK == DISC_ADR_IDE) {
-    // the six tail entries: one column per thread of wave 1 (wave 0 walks the loss partials), four chunks in flight per round,
+  if constexpr (disc_adr_tail(DK)) {
+    // the six (DISC_ADRD: seven) tail entries: one column per thread of wave 1 (wave 0 walks the loss partials), four chunks in flight per round,
     // summed in a fixed order.  Ahead of the big loads: here the sum holds no register across them (behind them,
     // <float, 8> gained 8 bytes of scratch over its DISC_ADR sibling).  k_disc_bwd_out stored a frozen coefficient's
     // partials as 0.0; a group of pairs has no tail gradient and reads nothing
-    if (tid >= 64 && tid < 70) {
+    if (tid >= 64 && tid < 64 + NTL) {
       const int k = tid - 64, nch = dd.n_chunks;
       real t = 0;
       if ((ginfo[G] & 0xff) != DISC_SET_PERIODIC)
         for (int c0 = 0; c0 < nch; c0 += 4) {
-          const real* src = lamp + (size_t)(G * nch + c0) * 6 + k;
+          const real* src = lamp + (size_t)(G * nch + c0) * NTL + k;
           real v[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) v[u] = c0 + u < nch ? src[6 * u] : real(0);
+          for (int u = 0; u < 4; ++u) v[u] = c0 + u < nch ? src[NTL * u] : real(0);
           t += (v[0] + v[1]) + (v[2] + v[3]);
         }
       row[nd.n_net + k] = t;
@@ -648,46 +697,50 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
   // in flight from the start: weights of the last hidden layer, its stash and the stash below it
   real pre[GEO::NPRE];
   if (H > 1) wt_load<real, NT, WP>(pre, th + nd.off_w[H - 1], W, W, W, tid);
-  real sc[3][EPT], sp[3][EPT];                             // stash of layer l / layer l - 1
-  auto load_stash = [&](real (&dst)[3][EPT], int l) {
+  real sc[NC][EPT], sp[NC][EPT];                           // stash of layer l / layer l - 1
+  auto load_stash = [&](real (&dst)[NC][EPT], int l) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
+    for (int c = 0; c < NC; ++c)
 #pragma unroll
       for (int e = 0; e < EPT; ++e) {
         const int i = tid + 256 * e;
-        dst[c][e] = Ast[(((size_t)l * 3 + c) * n_pad + 16 * G + i / WP) * WP + i % WP];
+        dst[c][e] = Ast[(((size_t)l * NC + c) * n_pad + 16 * G + i / WP) * WP + i % WP];
       }
   };
   load_stash(sc, H - 1);
   if (H > 1) load_stash(sp, H - 2);
 
   {  // adjoint of the last hidden layer = sum of the chunk partials (fixed order), 4 chunks x all of this
-     // thread's elements in flight per round
+     // thread's elements in flight per round (four channels: 2 chunks per round, v would be 128 VGPRs in float64 otherwise)
+    constexpr int CPR = NC == 4 ? 2 : 4;
     const int nch = dd.n_chunks;
-    const size_t cstride = (size_t)3 * n_pad * WP;
-    real s[3][EPT];
+    const size_t cstride = (size_t)NC * n_pad * WP;
+    real s[NC][EPT];
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
+    for (int c = 0; c < NC; ++c)
 #pragma unroll
       for (int e = 0; e < EPT; ++e) s[c][e] = 0;
-    for (int c0 = 0; c0 < nch; c0 += 4) {
-      real v[3][EPT][4];
+    for (int c0 = 0; c0 < nch; c0 += CPR) {
+      real v[NC][EPT][CPR];
 #pragma unroll
-      for (int c = 0; c < 3; ++c)
+      for (int c = 0; c < NC; ++c)
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
           const int i = tid + 256 * e;
           const real* src = dAp + ((size_t)c * n_pad + 16 * G + i / WP) * WP + i % WP + (size_t)c0 * cstride;
 #pragma unroll
-          for (int u = 0; u < 4; ++u) v[c][e][u] = c0 + u < nch ? src[(size_t)u * cstride] : real(0);
+          for (int u = 0; u < CPR; ++u) v[c][e][u] = c0 + u < nch ? src[(size_t)u * cstride] : real(0);
         }
 #pragma unroll
-      for (int c = 0; c < 3; ++c)
+      for (int c = 0; c < NC; ++c)
 #pragma unroll
-        for (int e = 0; e < EPT; ++e) s[c][e] += (v[c][e][0] + v[c][e][1]) + (v[c][e][2] + v[c][e][3]);
+        for (int e = 0; e < EPT; ++e) {
+          if constexpr (CPR == 4) s[c][e] += (v[c][e][0] + v[c][e][1]) + (v[c][e][2] + v[c][e][3]);
+          else s[c][e] += v[c][e][0] + v[c][e][1];
+        }
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
+    for (int c = 0; c < NC; ++c)
 #pragma unroll
       for (int e = 0; e < EPT; ++e) {
         const int i = tid + 256 * e;
@@ -718,15 +771,28 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
       const real a = sc[0][e], zp = sc[1][e], zr = sc[2][e];
       const real hb = adj[0 * CS + p * LD + j], pb = adj[1 * CS + p * LD + j], rb = adj[2 * CS + p * LD + j];
       const real d1 = real(1) - a * a, d2 = real(-2) * a * d1, d3 = real(-2) * d1 * (real(1) - real(3) * a * a);
-      gz[0 * CS + p * LD + j] = d1 * hb + d2 * (zp * pb + zr * rb) + d3 * zp * zp * rb;
-      gz[1 * CS + p * LD + j] = d1 * pb + real(2) * d2 * zp * rb;
-      gz[2 * CS + p * LD + j] = d1 * rb;
+      if constexpr (NC == 4) {
+        const real zt = sc[3][e], sb = adj[3 * CS + p * LD + j];
+        const real d4 = real(8) * a * d1 * (real(2) - real(3) * a * a);
+        const real c2 = d3 * zp * zp + d2 * zr;              // d a'' / d z
+        gz[0 * CS + p * LD + j] = d1 * hb + d2 * zp * pb + c2 * rb + (d4 * zp * zp * zp + real(3) * d3 * zp * zr + d2 * zt) * sb;
+        gz[1 * CS + p * LD + j] = d1 * pb + real(2) * d2 * zp * rb + real(3) * c2 * sb;
+        gz[2 * CS + p * LD + j] = d1 * rb + real(3) * d2 * zp * sb;
+        gz[3 * CS + p * LD + j] = d1 * sb;
+      } else {
+        gz[0 * CS + p * LD + j] = d1 * hb + d2 * (zp * pb + zr * rb) + d3 * zp * zp * rb;
+        gz[1 * CS + p * LD + j] = d1 * pb + real(2) * d2 * zp * rb;
+        gz[2 * CS + p * LD + j] = d1 * rb;
+      }
       if (l >= 1) {
         const real a0 = sp[0][e], zp0 = sp[1][e], zr0 = sp[2][e];
         const real e1 = real(1) - a0 * a0, e2 = real(-2) * a0 * e1;
         inp[0 * CS + p * LD + j] = a0;
         inp[1 * CS + p * LD + j] = e1 * zp0;
         inp[2 * CS + p * LD + j] = e2 * zp0 * zp0 + e1 * zr0;
+        if constexpr (NC == 4)
+          inp[3 * CS + p * LD + j] = real(-2) * e1 * (real(1) - real(3) * a0 * a0) * zp0 * zp0 * zp0 + real(3) * e2 * zp0 * zr0 +
+                                     e1 * sp[3][e];
       }
     }
     if (l >= 1) wt_store<real, NT, WP>(pre, wt, TLD, tid);
@@ -734,7 +800,7 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
     // next iteration's operands
     if (l >= 1) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c)
+      for (int c = 0; c < NC; ++c)
 #pragma unroll
         for (int e = 0; e < EPT; ++e) sc[c][e] = sp[c][e];
       if (l >= 2) {
@@ -742,7 +808,7 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
         wt_load<real, NT, WP>(pre, th + nd.off_w[l - 1], W, W, W, tid);
       }
     }
-    if (tid < W) {   // bias gradient; dense 0 has one input row (h, h_x = sx, h_xx = 0)
+    if (tid < W) {   // bias gradient; dense 0 has one input row (h, h_x = sx, h_xx = h_xxx = 0)
       real sb = 0, sw = 0;
       for (int p = 0; p < 16; ++p) {
         const real zb = gz[0 * CS + p * LD + tid];
@@ -759,7 +825,7 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
 #pragma unroll
         for (int rt = 0; rt < NT; ++rt) acc[rt] = acc_t{0, 0, 0, 0};
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
+        for (int c = 0; c < NC; ++c)
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) {
             const int p = 4 * ks + g;
@@ -779,6 +845,7 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
       for (int kt = wave; kt < NT; kt += 4) {   // adjoint of the input channels: gz_c W_l^T
         const int k = 16 * kt + m;
         acc_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0};
+        [[maybe_unused]] acc_t acc3 = {0, 0, 0, 0};
 #pragma unroll 4
         for (int ks = 0; ks < ksteps; ++ks) {
           const int jj = 4 * ks + g;
@@ -787,6 +854,7 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
           acc0 = TR::mfma(ap[0], b, acc0);
           acc1 = TR::mfma(ap[CS], b, acc1);
           acc2 = TR::mfma(ap[2 * CS], b, acc2);
+          if constexpr (NC == 4) acc3 = TR::mfma(ap[3 * CS], b, acc3);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -794,6 +862,7 @@ __global__ __launch_bounds__(256) void k_disc_bwd_hidden(NetDesc nd, DiscDesc dd
           adj[0 * CS + p * LD + k] = acc0[r];
           adj[1 * CS + p * LD + k] = acc1[r];
           adj[2 * CS + p * LD + k] = acc2[r];
+          if constexpr (NC == 4) adj[3 * CS + p * LD + k] = acc3[r];
         }
       }
     }

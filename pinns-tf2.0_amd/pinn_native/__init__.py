@@ -22,7 +22,7 @@ HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
 PDE_KINDS = {"burgers": 0, "burgers_ide": 1, "schrodinger": 2, "burgers_disc": 3, "burgers_disc_ide": 4, "adr": 5, "adr_ide": 6}
 # kinds added after the table above was pinned entry for entry (tests/test_adr_host.py): the discrete-time adr kind
-DISC_PDE_KINDS = {"adr_disc": 7, "adr_disc_ide": 8}
+DISC_PDE_KINDS = {"adr_disc": 7, "adr_disc_ide": 8, "adrd_disc": 9}
 
 
 def pde_kind(name):
@@ -39,17 +39,21 @@ DTYPES = {"f32": 0, "f64": 1, "float32": 0, "float64": 1}
 ADR_COEFF_NAMES = ("a0", "a1", "nu", "r1", "r2", "r3")     # order of the coefficients, and of the tail of "adr_ide" weights
 
 
-def adr_trainable_mask(names_or_mask):
-    """names from ADR_COEFF_NAMES (or an int mask, passed through) -> bit mask of pinn_set_pde_trainable"""
+ADRD_COEFF_NAMES = ADR_COEFF_NAMES + ("d3",)               # "adrd_disc": the dispersion coefficient behind the six
+
+
+def adr_trainable_mask(names_or_mask, names=ADR_COEFF_NAMES):
+    """names from ADR_COEFF_NAMES (ADRD_COEFF_NAMES for "adrd_disc": pass it as `names`), or an int mask, passed through
+    -> bit mask of pinn_set_pde_trainable"""
     if isinstance(names_or_mask, (int, np.integer)):
         return int(names_or_mask)
     if isinstance(names_or_mask, str):
         names_or_mask = [names_or_mask]
     mask = 0
     for name in names_or_mask:
-        if name not in ADR_COEFF_NAMES:
-            raise ValueError("unknown adr coefficient %r: choose from %s" % (name, ", ".join(ADR_COEFF_NAMES)))
-        mask |= 1 << ADR_COEFF_NAMES.index(name)
+        if name not in names:
+            raise ValueError("unknown adr coefficient %r: choose from %s" % (name, ", ".join(names)))
+        mask |= 1 << names.index(name)
     return mask
 
 
@@ -680,15 +684,18 @@ class Engine(object):
 
     def get_pde_params(self):
         """the current raw equation parameters: six coefficients (a0, a1, nu, r1, r2, r3) for "adr", "adr_disc", "adr_ide"
-        and "adr_disc_ide" (the last two: the trained values, nu = exp of the stored log nu), [nu] otherwise"""
-        p = np.empty(6 if self.pde in ("adr", "adr_ide", "adr_disc", "adr_disc_ide") else 1, dtype=np.float64)
+        and "adr_disc_ide" (the last two: the trained values, nu = exp of the stored log nu), seven (.., d3) for "adrd_disc"
+        (nu = 0 where it was set to 0), [nu] otherwise"""
+        p = np.empty(7 if self.pde == "adrd_disc" else 6 if self.pde in ("adr", "adr_ide", "adr_disc", "adr_disc_ide") else 1,
+                     dtype=np.float64)
         self._check(self._lib.pinn_get_pde_params(self._h, _dp(p), p.size))
         return p
 
     def set_pde_trainable(self, names_or_mask):
         """pde "adr_ide" and "adr_disc_ide": which coefficients are trained -- names from ADR_COEFF_NAMES or a bit mask (bit k = name k); the
-        others stay frozen at their values, bit for bit"""
-        self._check(self._lib.pinn_set_pde_trainable(self._h, adr_trainable_mask(names_or_mask)))
+        others stay frozen at their values, bit for bit.  pde "adrd_disc": names from ADRD_COEFF_NAMES (bit 6 = d3)"""
+        names = ADRD_COEFF_NAMES if self.pde == "adrd_disc" else ADR_COEFF_NAMES
+        self._check(self._lib.pinn_set_pde_trainable(self._h, adr_trainable_mask(names_or_mask, names)))
 
     # ---- weights ---------------------------------------------------------------------------
     def set_weights(self, w):
@@ -709,7 +716,7 @@ class Engine(object):
                                              _dp(grad) if want_grad else None, _dp(terms)))
         return loss.value, grad, terms
 
-    # ---- discrete-time models (pde "burgers_disc", "burgers_disc_ide", "adr_disc", "adr_disc_ide") -------------
+    # ---- discrete-time models (pde "burgers_disc", "burgers_disc_ide", "adr_disc", "adr_disc_ide", "adrd_disc") -------------
     def disc_set_stage(self, stage, x, target, M=None):
         """Stage set `stage` (0/1): points x [n], targets [n] (broadcast over the outputs), M [n_out, q] =
         step-scaled IRK table or None (no IRK term).  See include/pinn_hip.h."""
@@ -726,7 +733,7 @@ class Engine(object):
                                                   _dp(M) if M is not None else None, q))
 
     def disc_set_periodic(self, x_lb, x_ub, order=1):
-        """Periodic pairs of pde "adr_disc" and "adr_disc_ide": x_lb[i] with x_ub[i]; every output's value (order 0) or value and slope
+        """Periodic pairs of pde "adr_disc", "adr_disc_ide" and "adrd_disc": x_lb[i] with x_ub[i]; every output's value (order 0) or value and slope
         (order 1) difference, squared and summed, is added to the loss and reported in terms[2].  Empty arrays remove the
         pairs.  See include/pinn_hip.h."""
         x_lb, x_ub = _f64(x_lb).ravel(), _f64(x_ub).ravel()

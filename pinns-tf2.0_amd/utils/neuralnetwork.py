@@ -12,7 +12,7 @@ What changes: there is no TensorFlow, so a subclass cannot spell its PDE with Gr
 It names one of the engine's residual kinds instead (`pde="burgers" | "burgers_ide" |
 "schrodinger" | "burgers_disc" | "burgers_disc_ide" | "adr" | "adr_ide" | "adr_disc" | "adr_disc_ide"`; "adr_disc" is the discrete-time
 (q-stage Runge-Kutta, 1-input) model of the adr operator with periodic pairs, see 1d-allen-cahn/inf_disc_allen_cahn.py, and
-"adr_disc_ide" the same model with the coefficients named in hp["adr_trainable"] learned from two snapshots, see
+"adrd_disc" the same family with a dispersion term d3 U_xxx (seven coefficients; KdV), "adr_disc_ide" the same model with the coefficients named in hp["adr_trainable"] learned from two snapshots, see
 1d-allen-cahn/ide_disc_allen_cahn.py; "adr" is u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 = 0
 with fixed coefficients the subclass hands to `self._engine.set_pde_params(a0, a1, nu, r1, r2, r3)`, "adr_ide" the same
 equation with the coefficients named in hp["adr_trainable"] learned from the data, see _adr_ide_options) and the engine evaluates forward, u_t/u_x/u_xx, residual, loss and the flat
@@ -194,6 +194,34 @@ def _adr_ide_options(hp):
     return tuple(n for n in ADR_NAMES if n in names), tuple(init)
 
 
+ADRD_NAMES = ADR_NAMES + ("d3",)
+
+
+def _adrd_options(hp):
+    """pde "adrd_disc" (the discrete-time adr family with a d3 U_xxx term): hp["adr_trainable"] = names from a0, a1, nu, r1, r2,
+    r3, d3 (default: none), hp["adr_init"] = the seven raw start values (default Burgers' and d3 = 0).  nu = 0 is allowed (KdV
+    has no diffusion) but cannot be trained then.  Refused here, before any device work, with the offending key named.
+    -> (names in the order of ADRD_NAMES, seven floats)"""
+    names = hp.get("adr_trainable", [])
+    if isinstance(names, str) or not isinstance(names, (list, tuple)):
+        raise ValueError('hp["adr_trainable"] must be a list of names from %s (got %r)' % (", ".join(ADRD_NAMES), names))
+    for n in names:
+        if n not in ADRD_NAMES:
+            raise ValueError('hp["adr_trainable"]: unknown coefficient %r; choose from %s' % (n, ", ".join(ADRD_NAMES)))
+    init = hp.get("adr_init", [0.0, 1.0, 0.01 / np.pi, 0.0, 0.0, 0.0, 0.0])
+    try:
+        init = [float(v) for v in init]
+    except (TypeError, ValueError):
+        raise ValueError('hp["adr_init"] must be seven numbers [a0, a1, nu, r1, r2, r3, d3] (got %r)' % (init,))
+    if len(init) != 7 or not all(np.isfinite(v) for v in init):
+        raise ValueError('hp["adr_init"] must be seven finite numbers [a0, a1, nu, r1, r2, r3, d3] (got %r)' % (init,))
+    if init[2] < 0.0:
+        raise ValueError('hp["adr_init"]: nu (entry 2) must be >= 0 (got %r)' % (init[2],))
+    if init[2] == 0.0 and "nu" in names:
+        raise ValueError('hp["adr_trainable"]: nu must be positive to be trained, hp["adr_init"] has nu = 0')
+    return tuple(n for n in ADRD_NAMES if n in names), tuple(init)
+
+
 class _AdamConfig(object):
     """Holds what tf.keras.optimizers.Adam held (neuralnetwork.py:19-22)."""
 
@@ -255,7 +283,8 @@ class NeuralNetwork(object):
         self._resample, self._rad_k, self._rad_c, self._rad_pool = _resample_options(hp, self.pde)
         self._sa = _sa_options(hp, self.pde)
         self._pw = _pw_options(hp, self.pde)
-        self._adr_ide = _adr_ide_options(hp) if self.pde in ("adr_ide", "adr_disc_ide") else None
+        self._adr_ide = (_adrd_options(hp) if self.pde == "adrd_disc" else
+                         _adr_ide_options(hp) if self.pde in ("adr_ide", "adr_disc_ide") else None)
 
         # L-BFGS configuration, same fields as the reference (neuralnetwork.py:13-17)
         self.nt_config = Struct()
@@ -278,7 +307,7 @@ class NeuralNetwork(object):
         if self.pde in ("adr", "adr_ide") and parallel.env_world()[0] > 1 and bool(hp.get("data_parallel", True)):
             raise ValueError('pde "%s": a data-parallel launch (world > 1) is not supported for this kind; run one process, '
                              'or set hp["data_parallel"] = false for independent replicas' % self.pde)
-        self._dp = None if self.pde.startswith("burgers_disc") or self.pde in ("adr_disc", "adr_disc_ide") else parallel.from_env(bool(hp.get("data_parallel", True)))
+        self._dp = None if self.pde.startswith("burgers_disc") or self.pde in ("adr_disc", "adr_disc_ide", "adrd_disc") else parallel.from_env(bool(hp.get("data_parallel", True)))
         self.is_root = parallel.is_root()
         world, _, local_rank = parallel.env_world()
         device = hp.get("device", os.environ.get("PINN_DEVICE", local_rank if world > 1 else 0))
@@ -299,6 +328,8 @@ class NeuralNetwork(object):
                 self.sizes_w.append(int(width * self.layers[1]))
                 self.sizes_b.append(int(width if i != 0 else self.layers[1]))
 
+        if self.pde == "adrd_disc":                  # the params first (nu = 0 is a flag of the context), then the weights
+            self._engine.set_pde_params(*self._adr_ide[1])
         self._engine.set_weights(self._initial_weights(hp))
         if self._adr_ide:
             self._engine.set_pde_trainable(list(self._adr_ide[0]))
@@ -469,7 +500,7 @@ class NeuralNetwork(object):
         log nu in the nu slot)."""
         if self._adr_ide:
             tail = np.array(self._adr_ide[1], dtype=np.float64)
-            tail[2] = np.log(tail[2])
+            tail[2] = np.log(tail[2]) if tail[2] > 0.0 else 0.0      # ("adrd_disc" with nu = 0: the slot holds 0.0, unread)
             return tail
         return np.zeros(0)
 
@@ -551,7 +582,7 @@ class NeuralNetwork(object):
         trainable coefficients)."""
         if self._adr_ide and self._adr_ide[0]:
             p = self._engine.get_pde_params()
-            return "  " + "  ".join("%s = %.5e" % (n, p[ADR_NAMES.index(n)]) for n in self._adr_ide[0])
+            return "  " + "  ".join("%s = %.5e" % (n, p[ADRD_NAMES.index(n)]) for n in self._adr_ide[0])
         return ""
 
     def get_weights(self, convert_to_tensor=True):

@@ -88,7 +88,24 @@ enum {
    * checkpoint, set the params first, then the weights.  Hidden width above 64 is PINN_EUNSUPPORTED at create in both
    * dtypes (four Taylor channels fill the LDS).  Every call that refuses kinds 3, 4, 7 and 8 refuses this one with the
    * same code.  (Additive: one enum value, no entry point; the ABI version stays 6.) */
-  PINN_PDE_ADRD_DISC = 9
+  PINN_PDE_ADRD_DISC = 9,
+  /* the adr equation with a coefficient on u_t and a second time derivative, eight run-time coefficients
+   * p = [a0, a1, nu, r1, r2, r3, b, kappa] (pinn_set_pde_params / pinn_get_pde_params with n = 8, all finite, any sign):
+   *     f = b u_t + (a0 + a1 u) u_x - nu (u_xx + kappa u_tt) + r1 u + r2 u^2 + r3 u^3 - s(x, t)
+   * u_xx + kappa u_tt travels through the net as ONE Taylor channel (L a = d1 L z + d2 (z_x^2 + kappa z_t^2) through a tanh),
+   * so the sweeps carry four channels as PINN_PDE_ADR's do.  b = 1, kappa = 0 is PINN_PDE_ADR (the same bits); b = 0,
+   * nu = c^2, kappa = -1 / c^2 the wave equation u_tt = c^2 u_xx (b: a telegraph damping; r1..r3: Klein-Gordon); with the
+   * second input read as y, b = 0, nu = 1, kappa = 1 is Poisson's -Laplace u = s and r1 = -k^2 Helmholtz'.  A new context
+   * holds [0, 1, 0.01 / pi, 0, 0, 0, 1, 0], which is Burgers.  Point classes: collocation points with an optional source
+   * (pinn_set_source), data points, periodic pairs on u and u_x (pinn_set_boundary), and three-term wall points
+   * (pinn_set_robin3; pinn_set_robin means gamma = 0).  Loss, terms and gradient row as PINN_PDE_ADR with Robin points.
+   * Kernel path 7 for float64 2-20-...-20-1 nets with 4, 6 or 8 hidden layers (k_adr2_20d), path 0 otherwise, in float32 and
+   * float64 (every other path: PINN_EUNSUPPORTED from pinn_set_kernel_path).  pinn_residual,
+   * pinn_residual_at (N[u] without s), pinn_robin_residual, LHS redraws, both optimisers, tickets, snapshots, pinn_predict
+   * and pinn_error_l2 as for PINN_PDE_ADR.  PINN_EUNSUPPORTED, before any device work and the context unchanged: point
+   * weights, pinn_set_pde_trainable, pinn_set_coef_fields, pinn_rad_collocation, ensembles, communicators.
+   * (Additive: one enum value and pinn_set_robin3; the ABI version stays 6.) */
+  PINN_PDE_ADR2 = 10
 };
 enum { PINN_F32 = 0, PINN_F64 = 1 };
 enum {
@@ -511,6 +528,13 @@ int pinn_pw_disable(pinn_ctx* c);
 int pinn_set_robin(pinn_ctx* c, const double* X_w /*[n][2]*/, const double* alpha, const double* beta, const double* g,
                    int64_t n, int64_t n_total);
 int pinn_robin_residual(pinn_ctx* c, double* out /*[n]*/, int64_t n);
+/* Three-term wall points of PINN_PDE_ADR2: r_j = alpha_j u + beta_j u_x + gamma_j u_t - g_j, everything else as pinn_set_robin
+ * (storage, N_w = n_total, the wall part added to terms[2], n = 0 removes the class; pinn_robin_residual returns r_j).
+ * (0, 0, 1, v0) is the initial velocity of a wave or a Neumann wall y = const of a 2-D problem, (0, c, 1, 0) the Sommerfeld
+ * wall u_t + c u_x = 0.  PINN_EINVAL for a point with alpha = beta = gamma = 0 and for what pinn_set_robin refuses so;
+ * PINN_EUNSUPPORTED for every kind but PINN_PDE_ADR2.  (Additive: the ABI version stays 6.) */
+int pinn_set_robin3(pinn_ctx* c, const double* X_w /*[n][2]*/, const double* alpha, const double* beta, const double* gamma,
+                    const double* g, int64_t n, int64_t n_total);
 
 /* Source term of the adr kind (PINN_PDE_ADR): a right-hand side s(x, t), given as one value per LOCAL collocation point.  The
  * residual of collocation point i and the loss are

@@ -143,7 +143,8 @@ struct pinn_ctx {
   int layers[MAX_DENSE + 1]{};
   int n_layers = 0;
   double lb[2]{}, ub[2]{}, nu = 0.0;
-  double adr[7]{};                   // PINN_PDE_ADR: a0, a1, nu, r1, r2, r3 (pinn_set_pde_params); [6]: d3 of PINN_PDE_ADRD_DISC at create
+  double adr[8]{};                   // PINN_PDE_ADR: a0, a1, nu, r1, r2, r3 (pinn_set_pde_params); [6]: d3 of PINN_PDE_ADRD_DISC at create;
+                                     // PINN_PDE_ADR2: [6] = b, [7] = kappa
   int adr_mask = 0;                  // PINN_PDE_ADR_IDE, PINN_PDE_ADR_DISC_IDE, PINN_PDE_ADRD_DISC: bit k set = coefficient k is trained (pinn_set_pde_trainable)
   bool nu_off = false;               // PINN_PDE_ADRD_DISC: nu == 0 (pinn_set_pde_params); the kernels get it by value, the nu slot holds 0.0
 
@@ -273,6 +274,7 @@ struct pinn_ctx {
   // set: points first .. first + n - 1 (ensure_sets)
   struct {
     std::vector<double> X, alpha, beta, g;
+    std::vector<double> gamma;         // PINN_PDE_ADR2 (pinn_set_robin3; zeros from pinn_set_robin): rows (alpha, beta, gamma, 0) in ab
     int64_t n_total = 0;
     DevBuf<void> ab;
     int first = 0, n = 0;
@@ -368,7 +370,14 @@ static bool is_adr(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR; }
 static bool is_adr_ide(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR_IDE; }
 // the kinds whose tail is [a0, a1, log nu, r1, r2, r3] (adrd_disc: and d3) with a mask of the trained ones
 static bool has_adr_tail(const pinn_ctx* c) { return is_adr_ide(c) || is_adr_disc_ide(c) || is_adrd_disc(c); }
-static bool adr_family(const pinn_ctx* c) { return is_adr(c) || is_adr_ide(c); }
+// the adr equation with b u_t and u_xx + kappa u_tt as one Taylor channel: template value PDE_ADR2, eight coefficients in
+// c->adr, the point classes of the adr kind with three-term wall points and a source; the generic path 0 and, float64
+// width 20, k_adr2_20d (path 7)
+static bool is_adr2(const pinn_ctx* c) { return c->pde == PINN_PDE_ADR2; }
+// the kinds whose sets are the adr kind's: interleaved periodic pairs, no fused kernel of the Burgers kinds
+static bool adr_family(const pinn_ctx* c) { return is_adr(c) || is_adr_ide(c) || is_adr2(c); }
+// the kinds that take wall points (pinn_set_robin) and a source (pinn_set_source)
+static bool has_walls(const pinn_ctx* c) { return is_adr(c) || is_adr2(c); }
 // trailing equation parameters of the flat weight vector
 static int tail_len(int pde) {
   return has_lambdas(pde) ? 2 : pde == PINN_PDE_ADR_IDE || pde == PINN_PDE_ADR_DISC_IDE ? 6 : pde == PINN_PDE_ADRD_DISC ? 7 : 0;
@@ -388,6 +397,9 @@ static pde_coef_t<real, PDE> pde_coef(const pinn_ctx* c) {
     return AdrVarArg<real>{pde_coef<real, PDE_ADR_SRC>(c), c->kf.dev.as<real>()};
   else if constexpr (PDE == PDE_ADR_IDE)
     return AdrIdeArg{c->adr_mask};
+  else if constexpr (PDE == PDE_ADR2)      // src: the set's tgt, zero in the collocation block without a source
+    return Adr2Arg<real>{pde_coef<real, PDE_ADR>(c), (real)c->adr[6], (real)c->adr[7], c->robin.ab.as<real>(), c->robin.first,
+                         c->robin.n, (real)(c->robin.n_total > 0 ? 1.0 / (double)c->robin.n_total : 0.0), c->tgt.as<real>()};
   else
     return (real)c->nu;
 }
@@ -419,6 +431,7 @@ static int pde_kind(const pinn_ctx* c, Where w) {
     case PINN_PDE_BURGERS_IDE: return 1;
     case PINN_PDE_ADR: return adr_kind(c, w);
     case PINN_PDE_ADR_IDE: return PDE_ADR_IDE;
+    case PINN_PDE_ADR2: return PDE_ADR2;       // one kind: the wall count may be 0, tgt is zero without a source
     default: return 2;                     // Schrodinger
   }
 }
@@ -437,6 +450,7 @@ __attribute__((always_inline)) static inline int by_kind(const pinn_ctx* c, int 
       case PDE_ADR_ROBIN: return f(r, Kind<PDE_ADR_ROBIN>());
       case PDE_ADR_SRC: return f(r, Kind<PDE_ADR_SRC>());
       case PDE_ADR_VAR: return f(r, Kind<PDE_ADR_VAR>());
+      case PDE_ADR2: return f(r, Kind<PDE_ADR2>());
     }
     return fail(PINN_EINVAL, "no kernel of kind %d", kind);
   });
@@ -530,7 +544,9 @@ static const PathInfo PATHS[KP_COUNT] = {
 static const KernelPath PATH_PREFERENCE[] = {KP_FUSED20M, KP_FUSED20D, KP_FUSED20, KP_WIDE, KP_T16_FUSED, KP_T16, KP_GENERIC};
 // the adr kind's two implementations
 static bool adr_has_path(KernelPath p) { return p == KP_GENERIC || p == KP_FUSED20D; }
-static bool path_ok(const pinn_ctx* c, KernelPath p) { return PATHS[p].ok(c) && (!adr_family(c) || adr_has_path(p)); }
+static bool path_ok(const pinn_ctx* c, KernelPath p) {
+  return PATHS[p].ok(c) && (!adr_family(c) || adr_has_path(p));
+}
 
 static bool t16_fwd_on(const pinn_ctx* c) { return c->path == KP_T16 || c->path == KP_T16_FWD; }
 static bool t16_bwd_on(const pinn_ctx* c) { return c->path == KP_T16 || c->path == KP_T16_BWD || c->path == KP_T16_FUSED; }
@@ -624,7 +640,7 @@ static int ensure_sets(pinn_ctx* c) {
   if (c->pde == PINN_PDE_BURGERS_IDE)
     REQUIRE(n_f == 0, "identification evaluates the residual at the data points; no collocation set");
   if (c->pde != PINN_PDE_SCHRODINGER && !adr_family(c)) REQUIRE(n_b == 0, "boundary pairs are Schrodinger-only");
-  const int n_w = is_adr(c) ? (int)(c->robin.X.size() / 2) : 0;
+  const int n_w = has_walls(c) ? (int)(c->robin.X.size() / 2) : 0;
   const SetDesc sd = make_set_desc(n_b, n_u, n_f, c->nb_total, c->nu_total, c->nf_total, n_w);
   const int n_all = sd.n_all, n_pad = sd.n_pad;
   REQUIRE(n_all > 0, "no training points set");
@@ -636,7 +652,7 @@ static int ensure_sets(pinn_ctx* c) {
   std::vector<double> hx(n_pad), ht(n_pad), htg((size_t)NO * n_pad);
   assemble_set(ps, sd, NO, adr_family(c), on_device, c->lb, hx.data(), ht.data(), htg.data());
   const size_t off = (size_t)colloc_first(sd);
-  if (is_adr(c) && c->src.on && !c->src.stale) {                   // s_i rides in tgt at the collocation point's own index
+  if (has_walls(c) && c->src.on && !c->src.stale) {                // s_i rides in tgt at the collocation point's own index
     REQUIRE((int)c->src.s.size() == n_f, "the source term holds %lld values, the collocation set %d points",
             (long long)c->src.s.size(), n_f);
     for (int i = 0; i < n_f; ++i) htg[off + i] = c->src.s[i];
@@ -664,8 +680,12 @@ static int ensure_sets(pinn_ctx* c) {
   if (upload_real(c, c->ts, ht.data(), n_pad)) return PINN_EHIP;
   if (upload_real(c, c->tgt, htg.data(), (size_t)NO * n_pad)) return PINN_EHIP;
   if (n_w > 0) {
-    std::vector<double> hab((size_t)2 * n_w);
-    for (int j = 0; j < n_w; ++j) { hab[2 * j] = c->robin.alpha[j]; hab[2 * j + 1] = c->robin.beta[j]; }
+    const int rw = is_adr2(c) ? 4 : 2;             // PDE_ADR2: rows (alpha, beta, gamma, 0), one 16- or 32-byte load each
+    std::vector<double> hab((size_t)rw * n_w, 0.0);
+    for (int j = 0; j < n_w; ++j) {
+      hab[rw * j] = c->robin.alpha[j]; hab[rw * j + 1] = c->robin.beta[j];
+      if (rw == 4) hab[rw * j + 2] = c->robin.gamma[j];
+    }
     HIPCHK(c->robin.ab.reserve_bytes(hab.size() * rs));
     if (upload_real(c, c->robin.ab, hab.data(), hab.size())) return PINN_EHIP;
   }
@@ -880,6 +900,13 @@ static int t16_fwd(pinn_ctx* c, const void* xs, const void* ts, int n_pad, int c
 template <typename real>
 static int forward_chunk(pinn_ctx* c, const void* xs, const void* ts, int n_pad, int chunk, void* O, int base, int pts) {
   const InMap<real> m(c->lb, c->ub);
+  constexpr int JT2 = sizeof(real) == 4 ? 20 : 10;
+  if (is_adr2(c)) {                              // the fourth channel carries kappa: this kind's own sweep, whatever the width
+    hipLaunchKernelGGL((k_forward_adr2<real, JT2>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, c->theta_r.as<real>(),
+                       (const real*)xs, (const real*)ts, base, n_pad, chunk, m.lbx, m.lbt, m.sx, m.st, c->S.as<vec4<real>>(),
+                       (vec4<real>*)O, (real)c->adr[7]);
+    return 0;
+  }
   if (tile16_ok(c) && c->nd.width >= 24)
     return t16_fwd<real>(c, xs, ts, n_pad, chunk, O, base, pts, m.lbx, m.lbt, m.sx, m.st);
   constexpr int JT = sizeof(real) == 4 ? 20 : 10;
@@ -1112,6 +1139,32 @@ static int launch_chunks(pinn_ctx* c, hipEvent_t* ev4) {
   return 0;
 }
 
+// PDE_ADR2: one launch of k_adr2_20d on path 7 (float64); on path 0 chunk after chunk, k_forward_adr2 and
+// k_backward<real, PDE_ADR2>
+template <typename real>
+static int launch_adr2(pinn_ctx* c, hipEvent_t* ev4) {
+  if (c->path == KP_FUSED20D) {
+    int rc = hipErrorInvalidValue;
+    if constexpr (sizeof(real) == 8) rc = adr2_20d_launch_any(fused20d_args(c, ev4), pde_coef<double, PDE_ADR2>(c));
+    if (rc) return fail(PINN_EHIP, "adr2_20d launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
+  }
+  if (c->path != KP_GENERIC) return fail(PINN_EUNSUPPORTED, "the adr2 kind (pde 10) runs on kernel paths 0 and 7 only");
+  const InMap<real> m(c->lb, c->ub);
+  const int n_pad = c->sd.n_pad;
+  constexpr int KT = sizeof(real) == 4 ? 10 : 5;
+  for (int base = 0, ci = 0; base < n_pad; base += c->chunk, ++ci) {
+    const int pts = (n_pad - base < c->chunk) ? n_pad - base : c->chunk;
+    if (int rc = forward_chunk<real>(c, c->xs, c->ts, n_pad, c->chunk, c->O, base, pts)) return rc;
+    if (ev4 && ci == 0) HIPCHK(hipEventRecord(ev4[1], c->stream));
+    hipLaunchKernelGGL((k_backward<real, PDE_ADR2, KT>), dim3(pts / 64), dim3(64), 0, c->stream, c->nd, c->sd,
+                       c->theta_r.as<real>(), c->xs.as<real>(), c->ts.as<real>(), c->tgt.as<real>(), base, n_pad, c->chunk,
+                       m.lbx, m.lbt, m.sx, m.st, pde_coef<real, PDE_ADR2>(c), c->S.as<vec4<real>>(), c->O.as<vec4<real>>(),
+                       c->ZA.as<vec4<real>>(), c->ZB.as<vec4<real>>(), c->part.as<real>(), c->R, ci > 0 ? 1 : 0);
+  }
+  return 0;
+}
+
 // events of a sampled evaluation: [0] start, [1] forward done, [2] sweeps done; the one-launch paths attach [0] and [1] to
 // their kernel (its own begin and end).  Out of line: each (dtype, kind) is a function of its own behind eval_loss_grad's
 // switch, so a step walks the code of its own kind and not one body that holds all sixteen
@@ -1119,7 +1172,8 @@ template <typename real, int PDE>
 __attribute__((noinline)) static int launch_sweeps(pinn_ctx* c, hipEvent_t* ev4, const AdamFuse* af) {
   if (ev4 && !PATHS[c->path].one_launch) HIPCHK(hipEventRecord(ev4[0], c->stream));
   int rc;
-  switch (c->path) {
+  if constexpr (PDE == PDE_ADR2) rc = launch_adr2<real>(c, ev4);
+  else switch (c->path) {
     case KP_FUSED20D: rc = launch_fused20d<real, PDE>(c, ev4, af); break;
     case KP_FUSED20M: rc = launch_fused20m<real, PDE>(c, ev4); break;
     case KP_FUSED20: rc = launch_fused20<real, PDE>(c, ev4); break;
@@ -1533,7 +1587,7 @@ static int predict20_launch(pinn_ctx* c, const void* xs, const void* ts, int n_p
 
 // Taylor-channel forward sweep of the points in xs/ts -> O ([n_out][n_pad] vec4 (u, u_x, u_t, u_xx))
 static int forward_taylor(pinn_ctx* c, const void* xs, const void* ts, int n_pad, int chunk, void* O) {
-  if (predict20_ok(c->nd) && !is_disc(c)) return predict20_launch<4>(c, xs, ts, n_pad, O, nullptr);
+  if (predict20_ok(c->nd) && !is_disc(c) && !is_adr2(c)) return predict20_launch<4>(c, xs, ts, n_pad, O, nullptr);
   const size_t need_S = (size_t)c->nd.n_hidden * c->nd.width * (size_t)chunk * 4 * real_size(c);
   HIPCHK(c->S.reserve_bytes(need_S));
   for (int base = 0; base < n_pad; base += chunk) {
@@ -1573,7 +1627,7 @@ static int launch_residual(pinn_ctx* c, Where w, const void* O, int first, int c
       return fail(PINN_EINVAL, "a residual has no Robin form");
     } else {
       pde_coef_t<real, PDE> coef = pde_coef<real, PDE>(c);
-      if constexpr (PDE == PDE_ADR_SRC) {           // s is not known at foreign points: the null form, N[u] alone
+      if constexpr (PDE == PDE_ADR_SRC || PDE == PDE_ADR2) {   // s is not known at foreign points: the null form, N[u] alone
         if (w == AT_FOREIGN) coef.src = nullptr;
       }
       hipLaunchKernelGGL((k_residual<real, PDE>), grid, block, 0, c->stream, first, count, n_pad, (const vec4<real>*)O,
@@ -1694,6 +1748,8 @@ static int single_device_only(const pinn_ctx* c, const char* who) {
     if (x.present(c)) return fail(PINN_EUNSUPPORTED, "%s: %s single-device (%s first)", who, x.is, x.remove);
   if (is_adr_ide(c))
     return fail(PINN_EUNSUPPORTED, "%s: the adr_ide kind (pde 6) is single-device; it has no data-parallel launch", who);
+  if (is_adr2(c))
+    return fail(PINN_EUNSUPPORTED, "%s: the adr2 kind (pde 10) is single-device; it has no data-parallel launch", who);
   return 0;
 }
 
@@ -1715,7 +1771,9 @@ static int adr_extra_gate(const pinn_ctx* c, const Extra& x, const char* who) {
   if (c->pde == PINN_PDE_ADR_IDE)
     return fail(PINN_EUNSUPPORTED, "%s: %s for %s only; the adr_ide kind (pde 6) has no variant for %s", who, x.is, x.home,
                 x.pron);
-  if (c->pde != x.home_pde) return fail(PINN_EUNSUPPORTED, "%s: %s for %s only", who, x.is, x.home);
+  // the adr2 kind (pde 10) takes wall points and a source as the adr kind does, and neither fields nor point weights
+  const bool adr2_has = is_adr2(c) && (&x == &EXTRAS[X_ROBIN] || &x == &EXTRAS[X_SRC]);
+  if (c->pde != x.home_pde && !adr2_has) return fail(PINN_EUNSUPPORTED, "%s: %s for %s only", who, x.is, x.home);
   if (EXTRAS[X_PW].present(c))
     return fail(PINN_EUNSUPPORTED, "%s: %s (%s first)", who, x.pw_clash, EXTRAS[X_PW].remove);
   if (!adr_has_path(c->path))
@@ -1883,7 +1941,7 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   REQUIRE(out && layers && lb && ub, "null argument");
   REQUIRE(n_layers >= 3 && n_layers <= MAX_DENSE + 1, "need 3..%d layer sizes, got %d", MAX_DENSE + 1, n_layers);
   REQUIRE(dtype == PINN_F32 || dtype == PINN_F64, "dtype must be PINN_F32 or PINN_F64");
-  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADRD_DISC, "unknown pde kind %d", pde_kind);
+  REQUIRE(pde_kind >= 0 && pde_kind <= PINN_PDE_ADR2, "unknown pde kind %d", pde_kind);
   const bool disc = disc_kind(pde_kind);
   if (disc) REQUIRE(layers[0] == 1, "discrete-time models take one input (x), got %d", layers[0]);
   else REQUIRE(layers[0] == 2, "input dimension must be 2 (x, t), got %d", layers[0]);
@@ -1915,6 +1973,7 @@ int pinn_create(pinn_ctx** out, const int* layers, int n_layers, const double* l
   if (disc) { c->lb[1] = 0.0; c->ub[1] = 1.0; } else { c->lb[1] = lb[1]; c->ub[1] = ub[1]; }
   c->nu = 0.01 / M_PI;
   c->adr[1] = 1.0; c->adr[2] = c->nu;              // PINN_PDE_ADR and PINN_PDE_ADR_DISC start as Burgers: [0, 1, nu, 0, 0, 0]
+  if (pde_kind == PINN_PDE_ADR2) c->adr[6] = 1.0;  // ... and PINN_PDE_ADR2 with b = 1, kappa = 0
   NetDesc& nd = c->nd;
   nd.n_hidden = n_layers - 2; nd.width = W; nd.n_out = NO;
   int off = 0;
@@ -1979,6 +2038,8 @@ int pinn_rad_collocation(pinn_ctx* c, int64_t n_design, int64_t first, int64_t c
   REQUIRE(c, "null");
   if (is_disc(c) || c->pde == PINN_PDE_BURGERS_IDE)
     return fail(PINN_EUNSUPPORTED, "pinn_rad_collocation: this model has no collocation set");
+  if (is_adr2(c))
+    return fail(PINN_EUNSUPPORTED, "pinn_rad_collocation: the adr2 kind (pde 10) has no adaptive draw");
   if (int rc = design_check(n_design, first, count)) return rc;
   REQUIRE(n_pool >= 1 && n_pool <= RAD_POOL_MAX, "pinn_rad_collocation: n_pool %lld is outside 1..2^24", (long long)n_pool);
   if (c->src.on)                                  // refused first: the source is not made stale, the context stays usable
@@ -2066,6 +2127,37 @@ int pinn_set_robin(pinn_ctx* c, const double* X_w, const double* alpha, const do
   c->robin.X.assign(X_w, X_w + 2 * n);
   c->robin.alpha.assign(alpha, alpha + n);
   c->robin.beta.assign(beta, beta + n);
+  c->robin.gamma.assign((size_t)n, 0.0);           // (read by the adr2 kind alone: there this call means gamma = 0)
+  c->robin.g.assign(g, g + n);
+  c->robin.n_total = n_total;
+  if (n == 0) c->robin.n = 0;
+  c->sets_dirty = true;
+  return 0;
+}
+
+// Three-term wall points of the adr2 kind: alpha u + beta u_x + gamma u_t = g at (x_j, t_j).  pinn_set_robin's order of
+// refusals (the arrays first, then the context; nothing touched on a refusal) and its storage; n = 0 removes the class.
+int pinn_set_robin3(pinn_ctx* c, const double* X_w, const double* alpha, const double* beta, const double* gamma,
+                    const double* g, int64_t n, int64_t n_total) {
+  REQUIRE(n >= 0 && n_total >= n, "pinn_set_robin3: bad counts (n %lld, n_total %lld)", (long long)n, (long long)n_total);
+  REQUIRE(n <= (1 << 30), "pinn_set_robin3: too many points (%lld)", (long long)n);
+  REQUIRE(n == 0 || (X_w && alpha && beta && gamma && g), "pinn_set_robin3: null array");
+  for (int64_t j = 0; j < n; ++j) {
+    REQUIRE(std::isfinite(X_w[2 * j]) && std::isfinite(X_w[2 * j + 1]), "pinn_set_robin3: point %lld is not finite",
+            (long long)j);
+    REQUIRE(std::isfinite(alpha[j]) && std::isfinite(beta[j]) && std::isfinite(gamma[j]) && std::isfinite(g[j]),
+            "pinn_set_robin3: alpha, beta, gamma or g of point %lld is not finite", (long long)j);
+    REQUIRE(alpha[j] != 0.0 || beta[j] != 0.0 || gamma[j] != 0.0,
+            "pinn_set_robin3: point %lld has alpha = beta = gamma = 0: it constrains nothing", (long long)j);
+  }
+  REQUIRE(c, "pinn_set_robin3: null context");
+  if (!is_adr2(c))
+    return fail(PINN_EUNSUPPORTED, "pinn_set_robin3: three-term wall points are for the adr2 kind (pde 10) only");
+  if (int rc = adr_extra_gate(c, EXTRAS[X_ROBIN], "pinn_set_robin3")) return rc;
+  c->robin.X.assign(X_w, X_w + 2 * n);
+  c->robin.alpha.assign(alpha, alpha + n);
+  c->robin.beta.assign(beta, beta + n);
+  c->robin.gamma.assign(gamma, gamma + n);
   c->robin.g.assign(g, g + n);
   c->robin.n_total = n_total;
   if (n == 0) c->robin.n = 0;
@@ -2076,7 +2168,8 @@ int pinn_set_robin(pinn_ctx* c, const double* X_w, const double* alpha, const do
 // r_j = alpha_j u + beta_j u_x - g_j at the current weights: the generic forward sweep over the set, then k_robin_residual
 int pinn_robin_residual(pinn_ctx* c, double* out, int64_t n) {
   REQUIRE(c, "null");
-  if (!is_adr(c)) return fail(PINN_EUNSUPPORTED, "pinn_robin_residual: Robin points are for the adr kind (pde 5) only");
+  if (!has_walls(c))
+    return fail(PINN_EUNSUPPORTED, "pinn_robin_residual: Robin points are for the adr kind (pde 5) and the adr2 kind (pde 10) only");
   REQUIRE(n == (int64_t)(c->robin.X.size() / 2),
           "pinn_robin_residual: buffer holds %lld values, the context has %lld Robin points", (long long)n,
           (long long)(c->robin.X.size() / 2));
@@ -2089,8 +2182,12 @@ int pinn_robin_residual(pinn_ctx* c, double* out, int64_t n) {
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   by_real(c, [&](auto r) {
     using real = decltype(r);
-    hipLaunchKernelGGL((k_robin_residual<real>), grid, block, 0, c->stream, pde_coef<real, PDE_ADR_ROBIN>(c),
-                       c->O.as<vec4<real>>(), c->tgt.as<real>(), c->robin.out);
+    if (is_adr2(c))                            // + gamma_j u_t
+      hipLaunchKernelGGL((k_robin3_residual<real>), grid, block, 0, c->stream, pde_coef<real, PDE_ADR2>(c),
+                         c->O.as<vec4<real>>(), c->tgt.as<real>(), c->robin.out);
+    else
+      hipLaunchKernelGGL((k_robin_residual<real>), grid, block, 0, c->stream, pde_coef<real, PDE_ADR_ROBIN>(c),
+                         c->O.as<vec4<real>>(), c->tgt.as<real>(), c->robin.out);
   });
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, c->robin.out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2158,6 +2255,13 @@ int pinn_set_coef_fields(pinn_ctx* c, const double* K, int64_t n) {
 
 int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
   REQUIRE(c && p && n >= 1, "bad pde params");
+  if (is_adr2(c)) {                       // a0, a1, nu, r1, r2, r3, b, kappa: any sign; nothing changes on a refusal
+    REQUIRE(n == 8, "pinn_set_pde_params: the adr2 kind takes 8 coefficients (a0, a1, nu, r1, r2, r3, b, kappa), got %d", n);
+    for (int i = 0; i < 8; ++i) REQUIRE(std::isfinite(p[i]), "pinn_set_pde_params: coefficient %d is not finite", i);
+    for (int i = 0; i < 8; ++i) c->adr[i] = p[i];
+    c->nu = p[2];
+    return 0;
+  }
   if (is_adr(c) || is_adr_disc(c)) {      // a0, a1, nu, r1, r2, r3; nothing changes on a refusal
     REQUIRE(n == 6, "pinn_set_pde_params: the adr kind takes 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
     for (int i = 0; i < 6; ++i) REQUIRE(std::isfinite(p[i]), "pinn_set_pde_params: coefficient %d is not finite", i);
@@ -2186,6 +2290,11 @@ int pinn_set_pde_params(pinn_ctx* c, const double* p, int n) {
 
 int pinn_get_pde_params(pinn_ctx* c, double* p, int n) {
   REQUIRE(c && p, "null");
+  if (is_adr2(c)) {
+    REQUIRE(n == 8, "pinn_get_pde_params: this kind has 8 coefficients (a0, a1, nu, r1, r2, r3, b, kappa), got %d", n);
+    for (int i = 0; i < 8; ++i) p[i] = c->adr[i];
+    return 0;
+  }
   if (is_adrd_disc(c)) REQUIRE(n == 7, "pinn_get_pde_params: this kind has 7 coefficients (a0, a1, nu, r1, r2, r3, d3), got %d", n);
   else if (is_adr(c) || has_adr_tail(c) || is_adr_disc(c)) REQUIRE(n == 6, "pinn_get_pde_params: this kind has 6 coefficients (a0, a1, nu, r1, r2, r3), got %d", n);
   else REQUIRE(n == 1, "pinn_get_pde_params: this kind has 1 parameter (nu), got %d", n);
@@ -3042,6 +3151,9 @@ int pinn_set_kernel_path(pinn_ctx* c, int path) {
                   EXTRAS[k].remove);
   if (is_adr(c) && !adr_has_path(p))
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: the adr kind (pde 5) runs on kernel paths 0 and 7 only; path %d "
+                "(%s) has no variant for it", path, PATHS[p].name);
+  if (is_adr2(c) && !adr_has_path(p))
+    return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: the adr2 kind (pde 10) runs on kernel paths 0 and 7 only; path %d "
                 "(%s) has no variant for it", path, PATHS[p].name);
   if (is_adr_ide(c) && !adr_has_path(p))
     return fail(PINN_EUNSUPPORTED, "pinn_set_kernel_path: the adr_ide kind (pde 6) runs on kernel paths 0 and 7 only; path %d "

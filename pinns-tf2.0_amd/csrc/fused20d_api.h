@@ -155,6 +155,10 @@ int fused20d_launch_any(const F20dLaunch& a, const AdrSrcArg<double>& k);
 // 2 n_b + n_u + i; the collocation slots of a.tgt hold s_i or zeros; the Robin part of k is as above, k.n may be 0; k.k and
 // k.src are not read by this kernel.  Launch only while fields are present.
 int fused20d_launch_any(const F20dLaunch& a, const AdrVarArg<double>& k);
+// one evaluation of the adr2 kind (k_adr2_20d<PDE_ADR2, H, .>, adr2_20d_unit.hip: the kernel text under a name and in a code
+// object of its own; kernels_generic.h Adr2Arg): PDE_ADR_SRC's set -- the wall block's rows are (alpha, beta, gamma, 0), both
+// counts may be 0 -- and launch plan
+int adr2_20d_launch_any(const F20dLaunch& a, const Adr2Arg<double>& k);
 
 // one evaluation of a.n_members members of the adr kind (k_fused20d<PDE_ADR_ENS, H, ., true, sets>, kernels_generic.h
 // AdrEnsArg): k.coef is a device table of a.n_members rows of ADR_ENS_ROW doubles (a0, a1, nu, r1, r2, r3, two pads), member

@@ -199,6 +199,41 @@ __device__ __forceinline__ void preact_adjoint_d(const double a, const double zp
   br = d1 * orr;
 }
 
+// The two functions above as traits of PDE, called from the forward sweep, the rotated-input macro, first_nat and dense 0: every
+// kind gets them as they are; PDE_ADR2 (u_xx + kappa u_tt as the fourth channel, kernels_generic.h) adds its kappa terms as fmas
+// whose multiplicand holds kappa, so kappa = 0 adds exact zeros and the values are PDE_ADR_SRC's
+template <int PDE>
+__device__ __forceinline__ void channels_pde_d(const double a, const double zp, const double zq, const double zr, const double kap,
+                                               double& h, double& p, double& q, double& r) {
+  if constexpr (PDE == PDE_ADR2) {
+    const double d1 = __builtin_fma(-a, a, 1.0);
+    const double t = (-2.0 * a) * zp, tq = (-2.0 * a) * zq;
+    h = a; p = d1 * zp; q = d1 * zq; r = d1 * __builtin_fma(kap * tq, zq, __builtin_fma(t, zp, zr));
+  } else {
+    (void)kap;
+    channels_d(a, zp, zq, zr, h, p, q, r);
+  }
+}
+template <int PDE>
+__device__ __forceinline__ void preact_adjoint_pde_d(const double a, const double zp, const double zq, const double zr,
+                                                     const double kap, const double oh, const double op, const double oq,
+                                                     const double orr, double& bh, double& bp, double& bq, double& br) {
+  preact_adjoint_d(a, zp, zq, zr, oh, op, oq, orr, bh, bp, bq, br);
+  if constexpr (PDE == PDE_ADR2) {
+    const double a2 = a * a, d1 = 1.0 - a2;
+    const double d2 = (-2.0 * a) * d1;
+    const double d3 = (-2.0 * d1) * __builtin_fma(-3.0, a2, 1.0);
+    const double zqw = zq * orr;
+    bh = __builtin_fma((kap * d3) * zq, zqw, bh);
+    bq = __builtin_fma(kap * (d2 + d2), zqw, bq);
+  } else {
+    (void)kap;
+  }
+}
+// kappa of the kind's slot: PDE_ADR2's, 0 (and unused) everywhere else
+template <typename Slot> __device__ __forceinline__ double f20d_kappa(const Slot&) { return 0.0; }
+__device__ __forceinline__ double f20d_kappa(const Adr2Arg<double>& a) { return a.kappa; }
+
 // ONE_TILE: the launch has at least as many workgroups as tiles: every gradient block is produced exactly once, so
 // it is stored, not accumulated (no LDS read-modify-write), and there is no loop-carried coordinate prefetch.
 // ENS: ensemble launch, grid (n_wg, members) over a shared point set: member m = blockIdx.y reads its weights at
@@ -272,6 +307,7 @@ __device__ __forceinline__ double f20d_nu(const double* nu) { return nu[blockIdx
 __device__ __forceinline__ double f20d_nu(const SaArgs& a) { return a.nu; }
 __device__ __forceinline__ double f20d_nu(const AdrPwArgs& a) { return a.k.nu; }
 __device__ __forceinline__ double f20d_nu(const AdrRobinArg<double>& a) { return a.k.nu; }
+__device__ __forceinline__ double f20d_nu(const Adr2Arg<double>& a) { return a.k.nu; }
 __device__ __forceinline__ double f20d_nu(const AdrEnsArg&) { return 0.0; }               // (read from the member's row)
 // what a kernel holds of its member's row: the six coefficients (PDE_ADR_ENS), nothing at all (every other kind)
 template <int PDE> struct F20dEnsCoef { struct type {}; };

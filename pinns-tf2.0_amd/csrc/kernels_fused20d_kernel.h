@@ -26,6 +26,8 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
                 "Robin points: the fixed-coefficient adr kind only, solo launch, no point weights");
   static_assert(PDE != PDE_ADR_SRC || (!ENS && !SETS && !SAW),
                 "source term: the fixed-coefficient adr kind only, solo launch, no point weights");
+  static_assert(PDE != PDE_ADR2 || (!ENS && !SETS && !SAW && !PINN_F20D_SPLIT),
+                "adr2 (u_xx + kappa u_tt as one channel): solo launch, no point weights");
   static_assert(PDE != PDE_ADR_VAR || (!ENS && !SETS && !SAW),
                 "coefficient fields: the adr kind only, solo launch, no point weights (no SAW)");
   // weight offsets: compile-time constants in the one-tile variant (immediate operands; Adam step 41.9 -> 40.8 us with
@@ -116,6 +118,9 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
 
   double c1 = 1.0, c2 = f20d_nu(nu);
   if (PDE == 1) { c1 = wl[nd.n_net]; c2 = exp(wl[nd.n_net + 1]); }
+  // PDE_ADR2: kappa is read inside every layer of both sweeps (channels_pde_d, preact_adjoint_pde_d): a scalar pair
+  const double kap = f20d_kappa(nu);
+  (void)kap;
   // SAW, tile loop: the weight array and the ascent step size are held in vector registers (an opaque move): the tile-loop
   // variants use 96 of the 106 scalar registers already, and with these four more they spilled 2-4 of them
   double* sa_lam_p = nullptr;
@@ -158,6 +163,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
         adr_park[0] = nu.k.a0; adr_park[1] = nu.k.a1; adr_park[2] = nu.k.nu; adr_park[3] = nu.k.r1; adr_park[4] = nu.k.r2;
         adr_park[5] = nu.k.r3; adr_park[6] = sd.inv_nb; adr_park[7] = (double)nu.first; adr_park[8] = (double)nu.n;
         adr_park[9] = nu.inv_nw;
+        if constexpr (PDE == PDE_ADR2) adr_park[10] = nu.b;     // b beside the other ten (kappa: above)
       }
     }
   }
@@ -437,7 +443,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       const double w0x = wl[nd.off_w[0] + f], w0t = wl[nd.off_w[0] + FW + f], b0 = wl[nd.off_b[0] + f];
       const double a = tanh_d(__builtin_fma(hx, w0x, __builtin_fma(ht, w0t, b0)));
       a0[n] = a;
-      channels_d(a, sx * w0x, st * w0t, 0.0, in[0][n], in[1][n], in[2][n], in[3][n]);
+      channels_pde_d<PDE>(a, sx * w0x, st * w0t, 0.0, kap, in[0][n], in[1][n], in[2][n], in[3][n]);
     }
 #pragma unroll
     for (int d = 1; d < H; ++d) {
@@ -475,7 +481,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
 #pragma unroll
       for (int n = 0; n < 5; ++n) {
         const double a = tanh_d(acc[0][n]);
-        channels_d(a, acc[1][n], acc[2][n], acc[3][n], in[0][n], in[1][n], in[2][n], in[3][n]);
+        channels_pde_d<PDE>(a, acc[1][n], acc[2][n], acc[3][n], kap, in[0][n], in[1][n], in[2][n], in[3][n]);
         if (d < H - 1) {       // a is a VALU result; z_x, z_t, z_xx are raw matrix results (see agd_put_after)
           stash[d][n][0] = agd_put(a); stash[d][n][1] = agd_put_after(acc[1][n], in[1][n]);
           stash[d][n][2] = agd_put_after(acc[2][n], in[2][n]); stash[d][n][3] = agd_put_after(acc[3][n], in[3][n]);
@@ -553,7 +559,9 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
       double inv_nb;
       int rb_j = -1, rb_n = 0;               // PDE_ADR_ROBIN, _SRC, _VAR: this point's place in the Robin block, the block's length
       double inv_nw = 0.0;
+      double adr2_b = 1.0;                   // PDE_ADR2: the coefficient of u_t
       if constexpr (ONE_TILE) {
+        if constexpr (PDE == PDE_ADR2) adr2_b = nu.b;
         if constexpr (pde_adr_robin(PDE)) { kc = nu.k; rb_j = pt - nu.first; rb_n = nu.n; inv_nw = nu.inv_nw; }
         else if constexpr (PDE == PDE_ADR_ENS) kc = ens_k;
         else kc = nu;
@@ -564,8 +572,9 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
         kc = AdrCoef<double>{kp[0], kp[1], kp[2], kp[3], kp[4], kp[5]};
         inv_nb = kp[6];
         if constexpr (pde_adr_robin(PDE)) { rb_j = pt - (int)kp[7]; rb_n = (int)kp[8]; inv_nw = kp[9]; }
+        if constexpr (PDE == PDE_ADR2) adr2_b = kp[10];
       }
-      (void)rb_j; (void)rb_n; (void)inv_nw;
+      (void)rb_j; (void)rb_n; (void)inv_nw; (void)adr2_b;
       const int cls = point_class_adr(sd, pt);
       if (cls == CLS_COL) {
         if constexpr (PDE == PDE_ADR_VAR) {
@@ -578,7 +587,12 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
           kc = AdrCoef<double>{k01.x, k01.y, k23.x, k23.y, k45.x, k45.y};
         }
         const double u = o[0], adv = kc.a0 + kc.a1 * u;
-        double f = o[2] + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
+        double ut = o[2];
+        if constexpr (PDE == PDE_ADR2) {     // b u_t, a product of its own: b = 1 gives u_t
+#pragma clang fp contract(off)
+          ut = adr2_b * o[2];
+        }
+        double f = ut + adv * o[1] - kc.nu * o[3] + u * (kc.r1 + u * (kc.r2 + kc.r3 * u));
         if constexpr (pde_adr_src(PDE)) {
           // minus the source s_i = tgt[pt], loaded here (the one-tile adr variants have no vector registers to hold it across
           // the forward sweep) and subtracted as an operation of its own: a zero source gives PDE_ADR's bits
@@ -589,6 +603,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
         if (s == 0) lacc[0] += f * f * inv_nf;
         sb[0] = fbar * (kc.a1 * o[1] + kc.r1 + u * (2.0 * kc.r2 + 3.0 * kc.r3 * u));
         sb[1] = fbar * adv; sb[2] = fbar; sb[3] = -kc.nu * fbar;
+        if constexpr (PDE == PDE_ADR2) sb[2] = fbar * adr2_b;
       } else if (cls == CLS_DATA) {
         const double dd = o[0] - tgt[pt];
         if (s == 0) lacc[64] += dd * dd * inv_nu;
@@ -601,10 +616,18 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
         // the Robin block stands behind the collocation block (CLS_PAD by sd's counts): r = alpha u + beta u_x - g
         if ((unsigned)rb_j < (unsigned)rb_n) {
           typedef double d2 __attribute__((ext_vector_type(2)));
-          const d2 ab = *reinterpret_cast<const d2*>(rb_ab + 2 * rb_j);
-          const double r = ab.x * o[0] + ab.y * o[1] - tgt[pt];
-          if (s == 0) lacc[128] += r * r * inv_nw;
-          sb[0] = 2.0 * r * ab.x * inv_nw; sb[1] = 2.0 * r * ab.y * inv_nw;
+          if constexpr (PDE == PDE_ADR2) {   // rows (alpha, beta, gamma, 0): two 16-byte loads; + gamma u_t by an fma (gamma = 0: an exact zero)
+            const d2* const row = reinterpret_cast<const d2*>(rb_ab + 4 * rb_j);
+            const d2 ab = row[0], gz = row[1];
+            const double r = __builtin_fma(gz.x, o[2], ab.x * o[0] + ab.y * o[1]) - tgt[pt];
+            if (s == 0) lacc[128] += r * r * inv_nw;
+            sb[0] = 2.0 * r * ab.x * inv_nw; sb[1] = 2.0 * r * ab.y * inv_nw; sb[2] = 2.0 * r * gz.x * inv_nw;
+          } else {
+            const d2 ab = *reinterpret_cast<const d2*>(rb_ab + 2 * rb_j);
+            const double r = ab.x * o[0] + ab.y * o[1] - tgt[pt];
+            if (s == 0) lacc[128] += r * r * inv_nw;
+            sb[0] = 2.0 * r * ab.x * inv_nw; sb[1] = 2.0 * r * ab.y * inv_nw;
+          }
         }
       }
     } else if constexpr (PDE == PDE_ADR_IDE) {
@@ -722,7 +745,7 @@ __global__ __launch_bounds__(256) void PINN_F20D_KERNEL(const double* __restrict
     // PDE_ADR_IDE: quarters 0 and 1 hold four sums each, one per DPP row (= slot): [loss_f, a0, a1, log nu], [data, r1, r2, r3]
     const double t0 = PDE == PDE_ADR_IDE ? row16_sum(lacc[0]) : wave_sum(lacc[0]);
     const double t1 = PDE == PDE_ADR_IDE ? row16_sum(lacc[64]) : wave_sum(lacc[64]);
-    const double t2 = (PDE == 1 || pde_is_adr(PDE)) ? wave_sum(lacc[128]) : 0.0, t3 = PDE == 1 ? wave_sum(lacc[192]) : 0.0;
+    const double t2 = (PDE == 1 || pde_is_adr(PDE) || PDE == PDE_ADR2) ? wave_sum(lacc[128]) : 0.0, t3 = PDE == 1 ? wave_sum(lacc[192]) : 0.0;
     double ide_mask = 0.0;
     if constexpr (PDE == PDE_ADR_IDE) ide_mask = lacc_all[wave * 256 + 192 + 7];      // this wave's own parked copy
     __syncthreads();                                   // every wave's accumulators are final

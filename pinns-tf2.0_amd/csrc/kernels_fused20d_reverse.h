@@ -58,7 +58,7 @@
         double a, zp, zq, zr;
         if (d == H - 1) { a = top[n][0]; zp = top[n][1]; zq = top[n][2]; zr = top[n][3]; }
         else { a = agd_get(stash[d][n][0]); zp = agd_get(stash[d][n][1]); zq = agd_get(stash[d][n][2]); zr = agd_get(stash[d][n][3]); }
-        preact_adjoint_d(a, zp, zq, zr, ob[0][n], ob[1][n], ob[2][n], ob[3][n], zb[0][n], zb[1][n], zb[2][n], zb[3][n]);
+        preact_adjoint_pde_d<PDE>(a, zp, zq, zr, kap, ob[0][n], ob[1][n], ob[2][n], ob[3][n], zb[0][n], zb[1][n], zb[2][n], zb[3][n]);
       }
       STAMP2(d == 4, 20);
       // One tile: the phase before this one is summed HERE, not where its last block was parked -- the stash entries of
@@ -85,7 +85,7 @@
           a_ = agd_get(stash[d - 1][0][0]); zp_ = agd_get(stash[d - 1][0][1]);
           zq_ = agd_get(stash[d - 1][0][2]); zr_ = agd_get(stash[d - 1][0][3]);
         }
-        channels_d(a_, zp_, zq_, zr_, first_nat[0], first_nat[1], first_nat[2], first_nat[3]);
+        channels_pde_d<PDE>(a_, zp_, zq_, zr_, kap, first_nat[0], first_nat[1], first_nat[2], first_nat[3]);
       }
       // adjoint of the layer-(d-1) outputs: in_bar[4m + i] = sum_j z_bar_j W_d[4m + i][j]
       const double* __restrict__ wd = wl + nd.off_w[d] + pr;
@@ -133,7 +133,7 @@
       zq_ = agd_get(stash[d - 1][M][2]); zr_ = agd_get(stash[d - 1][M][3]);                                 \
     }                                                                                                       \
     double h_, p_, q_, r_;                                                                                  \
-    channels_d(a_, zp_, zq_, zr_, h_, p_, q_, r_);                                                          \
+    channels_pde_d<PDE>(a_, zp_, zq_, zr_, kap, h_, p_, q_, r_);                                                      \
     O4[0] = PINN_TO_POINTS(h_); O4[1] = PINN_TO_POINTS(p_);                                             \
     O4[2] = PINN_TO_POINTS(q_); O4[3] = PINN_TO_POINTS(r_);                                             \
   } while (0)
@@ -183,7 +183,7 @@
       for (int n = 0; n < 5; ++n) {
         const int f = 4 * n + s;
         double bh, bp, bq, br;
-        preact_adjoint_d(a0[n], sx * wl[nd.off_w[0] + f], st * wl[nd.off_w[0] + FW + f], 0.0, ob[0][n], ob[1][n],
+        preact_adjoint_pde_d<PDE>(a0[n], sx * wl[nd.off_w[0] + f], st * wl[nd.off_w[0] + FW + f], 0.0, kap, ob[0][n], ob[1][n],
                          ob[2][n], ob[3][n], bh, bp, bq, br);
         bT[0][n] = PINN_TO_POINTS(bh); bT[1][n] = PINN_TO_POINTS(bp); bT[2][n] = PINN_TO_POINTS(bq);
       }

@@ -79,6 +79,18 @@ constexpr int PDE_ADR_VAR = 7;
 // coefficients.  No generic-path kernel is instantiated with it.
 constexpr int PDE_ADR_ENS = 8;
 constexpr int ADR_ENS_ROW = 8;           // doubles per row of the table
+// Template number of PINN_PDE_ADR2 = 10 of the C interface: the adr equation with a time-derivative coefficient b and
+// u_xx + kappa u_tt carried as ONE Taylor channel,
+//   f = b u_t + (a0 + a1 u) u_x - nu (u_xx + kappa u_tt) + r1 u + r2 u^2 + r3 u^3 - s.
+// L = d_xx + kappa d_tt passes a tanh layer as L a = d1 L z + d2 (z_x^2 + kappa z_t^2) and a linear layer as z_xx does, so the
+// fourth entry of every stash and output vec4 is w = u_xx + kappa u_tt and kappa is read inside every layer of both sweeps
+// (channels_of, preact_adjoint).  The point classes are PDE_ADR_SRC's -- pair-interleaved periodic pairs, data, collocation
+// points with s in tgt (zero without a source), a wall block behind the collocation block (its count may be 0) -- with
+// THREE-term wall points, r_j = alpha_j u + beta_j u_x + gamma_j u_t - g_j.  Every new term is an fma whose multiplicand
+// holds the new coefficient, and b u_t is a product of its own: kappa = 0, b = 1, gamma = 0 adds exact zeros and multiplies by
+// one, which gives PDE_ADR_SRC's bits.  Not a member of pde_is_adr: no k_fused20d, tile16 or wide kernel has a variant of it; its
+// float64 width-20 kernel is the text of k_fused20d under the name k_adr2_20d, in adr2_20d_unit.hip.
+constexpr int PDE_ADR2 = 9;
 constexpr bool pde_is_adr(int PDE) {
   return PDE == PDE_ADR || PDE == PDE_ADR_IDE || PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR ||
          PDE == PDE_ADR_ENS;
@@ -89,11 +101,11 @@ constexpr bool pde_adr_fixed(int PDE) { return PDE == PDE_ADR || PDE == PDE_ADR_
 // the kinds that share k_fused20d's seed block and loss-row layout of PDE_ADR: the fixed ones and PDE_ADR_VAR, whose block
 // differs in where a collocation point's six coefficients come from and in nothing else
 // (and PDE_ADR_ENS, whose six come from its member's row of a table)
-constexpr bool pde_adr_seed_block(int PDE) { return pde_adr_fixed(PDE) || PDE == PDE_ADR_VAR || PDE == PDE_ADR_ENS; }
+constexpr bool pde_adr_seed_block(int PDE) { return pde_adr_fixed(PDE) || PDE == PDE_ADR_VAR || PDE == PDE_ADR_ENS || PDE == PDE_ADR2; }
 // the kinds that carry a Robin block behind the collocation block
-constexpr bool pde_adr_robin(int PDE) { return PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR; }
+constexpr bool pde_adr_robin(int PDE) { return PDE == PDE_ADR_ROBIN || PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR || PDE == PDE_ADR2; }
 // the kinds that subtract s_i = tgt[point] at a collocation point
-constexpr bool pde_adr_src(int PDE) { return PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR; }
+constexpr bool pde_adr_src(int PDE) { return PDE == PDE_ADR_SRC || PDE == PDE_ADR_VAR || PDE == PDE_ADR2; }
 // trailing equation parameters of the weight vector: 2 lambdas (PDE 1), six coefficients (PDE_ADR_IDE)
 constexpr int pde_n_tail(int PDE) { return PDE == 1 ? 2 : PDE == PDE_ADR_IDE ? 6 : 0; }
 template <typename real> struct AdrCoef { real a0, a1, nu, r1, r2, r3; };
@@ -119,6 +131,16 @@ template <typename real> struct AdrVarArg : AdrSrcArg<real> {
 struct AdrEnsArg {
   const double* coef;
 };
+// PDE_ADR2: the eight coefficients, the wall rows ab[4 j ..] = (alpha_j, beta_j, gamma_j, 0) of wall point first + j, the
+// block's first point and length, 1 / GLOBAL wall count, and the source by SET index for k_residual (nullptr: N[u] alone)
+template <typename real> struct Adr2Arg {
+  AdrCoef<real> k;
+  real b, kappa;
+  const real* ab;
+  int first, n;
+  real inv_nw;
+  const real* src;
+};
 // row i of the table (every load inside the caller's collocation branch)
 template <typename real> __device__ __forceinline__ AdrCoef<real> adr_row(const real* __restrict__ kf, int i) {
   const real* __restrict__ r = kf + (size_t)6 * i;
@@ -134,11 +156,13 @@ template <typename real> struct PdeCoef<real, PDE_ADR_ROBIN> { using type = AdrR
 template <typename real> struct PdeCoef<real, PDE_ADR_SRC> { using type = AdrSrcArg<real>; };
 template <typename real> struct PdeCoef<real, PDE_ADR_VAR> { using type = AdrVarArg<real>; };
 template <typename real> struct PdeCoef<real, PDE_ADR_ENS> { using type = AdrEnsArg; };
+template <typename real> struct PdeCoef<real, PDE_ADR2> { using type = Adr2Arg<real>; };
 template <typename real, int PDE> using pde_coef_t = typename PdeCoef<real, PDE>::type;
 template <typename real> __device__ __forceinline__ real coef_nu(real nu) { return nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrCoef<real>& k) { return k.nu; }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrIdeArg&) { return real(0); }
 template <typename real> __device__ __forceinline__ real coef_nu(const AdrRobinArg<real>& a) { return a.k.nu; }
+template <typename real> __device__ __forceinline__ real coef_nu(const Adr2Arg<real>& a) { return a.k.nu; }
 template <typename real> __device__ __forceinline__ AdrCoef<real> coef_adr(real) { return AdrCoef<real>{0, 0, 0, 0, 0, 0}; }
 template <typename real> __device__ __forceinline__ AdrCoef<real> coef_adr(const AdrCoef<real>& k) { return k; }
 // the current coefficients of PDE_ADR_IDE from the tail of the weight vector
@@ -161,6 +185,7 @@ template <> __device__ __forceinline__ double tanh_r<double>(double z) { return 
 //   S[(d*W + k)*n_pad + pt] = (a, zp, zq, zr) of dense layer d, feature k      (d < H)
 //   O[o*n_pad + pt]         = (u_o, d/dx, d/dt, d2/dx2) of output o
 // ---------------------------------------------------------------------------------------------
+// (k_forward_adr2 below is this text with one more term in the fourth channel: a change here belongs there too)
 template <typename real, int JT>
 __global__ __launch_bounds__(64) void k_forward(NetDesc nd, const real* __restrict__ th,
                                                 const real* __restrict__ xs,
@@ -223,6 +248,84 @@ __global__ __launch_bounds__(64) void k_forward(NetDesc nd, const real* __restri
       const vec4<real> s = Sin[(size_t)k * s_pad];
       const real a = s.x, d1 = real(1) - a * a, d2 = real(-2) * a * d1;
       const real p = d1 * s.y, q = d1 * s.z, r = d2 * s.y * s.y + d1 * s.w;
+#pragma unroll
+      for (int o = 0; o < 2; ++o) {
+        if (o < nd.n_out) {
+          const real w = WL[k * nd.n_out + o];
+          oz[o] += a * w; op[o] += p * w; oq[o] += q * w; orr[o] += r * w;
+        }
+      }
+    }
+    for (int o = 0; o < nd.n_out; ++o)
+      O[(size_t)o * n_pad + pt] = vec4<real>{oz[o], op[o], oq[o], orr[o]};
+  }
+}
+
+// PDE_ADR2's forward sweep, O[pt] = (u, u_x, u_t, u_xx + kap u_tt): k_forward with the kappa term of every layer's fourth
+// channel added by an fma on top of k_forward's own expression (kap = 0: an exact zero, k_forward's bits).  A kernel text of
+// its own and not a shared body: k_forward through a shared inline function compiles to other instructions than it had.
+template <typename real, int JT>
+__global__ __launch_bounds__(64) void k_forward_adr2(NetDesc nd, const real* __restrict__ th,
+                                                const real* __restrict__ xs,
+                                                const real* __restrict__ ts, int base, int n_pad,
+                                                int s_pad, real lbx, real lbt, real sx, real st,
+                                                vec4<real>* __restrict__ S,
+                                                vec4<real>* __restrict__ O, real kap) {
+  const int lp = blockIdx.x * 64 + threadIdx.x;   // point index inside the chunk (stash index)
+  const int pt = base + lp;                        // index into the point arrays
+  const int W = nd.width, H = nd.n_hidden;
+  const real x = xs[pt], t = ts[pt];
+  const real hx = sx * (x - lbx) - real(1), ht = st * (t - lbt) - real(1);
+
+  {  // dense 0: inputs are (hx, ht); p0 = (sx, 0), q0 = (0, st), r0 = 0
+    const real* __restrict__ W0 = th + nd.off_w[0];
+    const real* __restrict__ b0 = th + nd.off_b[0];
+    for (int j = 0; j < W; ++j) {
+      const real w0 = W0[j], w1 = W0[W + j];
+      const real z = hx * w0 + ht * w1 + b0[j];
+      S[(size_t)j * s_pad + lp] = vec4<real>{tanh_r(z), sx * w0, st * w1, real(0)};
+    }
+  }
+  for (int d = 1; d < H; ++d) {
+    const real* __restrict__ Wd = th + nd.off_w[d];
+    const real* __restrict__ bd = th + nd.off_b[d];
+    const vec4<real>* __restrict__ Sin = S + (size_t)(d - 1) * W * s_pad + lp;
+    vec4<real>* __restrict__ Sout = S + (size_t)d * W * s_pad + lp;
+    for (int j0 = 0; j0 < W; j0 += JT) {
+      real az[JT], ap[JT], aq[JT], ar[JT];
+#pragma unroll
+      for (int jj = 0; jj < JT; ++jj) {
+        az[jj] = (j0 + jj < W) ? bd[j0 + jj] : real(0);
+        ap[jj] = aq[jj] = ar[jj] = real(0);
+      }
+      for (int k = 0; k < W; ++k) {
+        const vec4<real> s = Sin[(size_t)k * s_pad];
+        const real a = s.x, d1 = real(1) - a * a, d2 = real(-2) * a * d1;
+        const real p = d1 * s.y, q = d1 * s.z, r = fma(kap * d2 * s.z, s.z, d2 * s.y * s.y + d1 * s.w);
+#pragma unroll
+        for (int jj = 0; jj < JT; ++jj) {
+          if (j0 + jj < W) {
+            const real w = Wd[k * W + j0 + jj];
+            az[jj] += a * w; ap[jj] += p * w; aq[jj] += q * w; ar[jj] += r * w;
+          }
+        }
+      }
+#pragma unroll
+      for (int jj = 0; jj < JT; ++jj)
+        if (j0 + jj < W)
+          Sout[(size_t)(j0 + jj) * s_pad] = vec4<real>{tanh_r(az[jj]), ap[jj], aq[jj], ar[jj]};
+    }
+  }
+  {  // linear output layer (dense H)
+    const real* __restrict__ WL = th + nd.off_w[H];
+    const real* __restrict__ bL = th + nd.off_b[H];
+    const vec4<real>* __restrict__ Sin = S + (size_t)(H - 1) * W * s_pad + lp;
+    real oz[2] = {bL[0], nd.n_out > 1 ? bL[1] : real(0)};
+    real op[2] = {0, 0}, oq[2] = {0, 0}, orr[2] = {0, 0};
+    for (int k = 0; k < W; ++k) {
+      const vec4<real> s = Sin[(size_t)k * s_pad];
+      const real a = s.x, d1 = real(1) - a * a, d2 = real(-2) * a * d1;
+      const real p = d1 * s.y, q = d1 * s.z, r = fma(kap * d2 * s.z, s.z, d2 * s.y * s.y + d1 * s.w);
 #pragma unroll
       for (int o = 0; o < 2; ++o) {
         if (o < nd.n_out) {
@@ -372,6 +475,56 @@ __device__ __forceinline__ void point_seeds_own(const SetDesc& sd, int g, int n_
   }
 }
 
+// PDE_ADR2: loss parts and output adjoints of point g from its own outputs o = (u, u_x, u_t, w), w = u_xx + kappa u_tt; O
+// is read for the partner of a periodic pair only.  PDE_ADR_SRC's expressions with b u_t in the place of u_t (a product of its
+// own, never contracted: b = 1 gives u_t) and gamma u_t added to a wall residual by an fma (gamma = 0 adds an exact zero)
+template <typename real>
+__device__ __forceinline__ void adr2_point_seeds(const SetDesc& sd, int g, const vec4<real>* __restrict__ O,
+                                                 const real* __restrict__ tgt, const Adr2Arg<real>& a, vec4<real>& sb,
+                                                 real lt[3]) {
+  const vec4<real> o = O[g];
+  sb = vec4<real>{0, 0, 0, 0};
+  lt[0] = lt[1] = lt[2] = real(0);
+  const int j = g - a.first;
+  if ((unsigned)j < (unsigned)a.n) {        // the wall block stands behind the collocation block
+    const vec4<real> w = *reinterpret_cast<const vec4<real>*>(a.ab + 4 * (size_t)j);
+    const real r = fma(w.z, o.z, w.x * o.x + w.y * o.y) - tgt[g];
+    lt[2] = r * r * a.inv_nw;
+    sb.x = real(2) * r * w.x * a.inv_nw; sb.y = real(2) * r * w.y * a.inv_nw; sb.z = real(2) * r * w.z * a.inv_nw;
+    return;
+  }
+  const int cls = point_class_adr(sd, g);
+  if (cls == CLS_PAD) return;
+  const real inv_nf = (real)sd.inv_nf, inv_nu = (real)sd.inv_nu, inv_nb = (real)sd.inv_nb;
+  if (cls == CLS_COL) {
+    const AdrCoef<real>& k = a.k;
+    const real u = o.x, adv = k.a0 + k.a1 * u;
+    real bz, f;
+    {
+#pragma clang fp contract(off)
+      bz = a.b * o.z;
+    }
+    f = adr_residual(k, vec4<real>{o.x, o.y, bz, o.w});
+    {
+#pragma clang fp contract(off)
+      f = f - tgt[g];
+    }
+    const real fb = real(2) * f * inv_nf;
+    lt[0] = f * f * inv_nf;
+    sb.x = fb * (k.a1 * o.y + k.r1 + u * (real(2) * k.r2 + real(3) * k.r3 * u));
+    sb.y = fb * adv; sb.z = fb * a.b; sb.w = -k.nu * fb;
+  } else if (cls == CLS_DATA) {
+    const real dd = o.x - tgt[g];
+    lt[1] = dd * dd * inv_nu;
+    sb.x = real(2) * dd * inv_nu;
+  } else {                          // own minus partner, as PDE_ADR
+    const vec4<real> pr = O[g ^ 1];
+    const real du = o.x - pr.x, dp = o.y - pr.y;
+    if (cls == CLS_BLO) lt[2] = (du * du + dp * dp) * inv_nb;
+    sb.x = real(2) * du * inv_nb; sb.y = real(2) * dp * inv_nb;
+  }
+}
+
 template <typename real>
 __device__ __forceinline__ real dot4(const vec4<real>& a, const vec4<real>& b) {
   return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
@@ -398,6 +551,28 @@ __device__ __forceinline__ vec4<real> preact_adjoint(const vec4<real>& s, const 
   zb.w = d1 * ob.w;
   return zb;
 }
+
+// The two functions above as a trait of PDE: every existing kind gets them as they are; PDE_ADR2 adds its kappa terms by an
+// fma on top of each (kappa = 0: an exact zero)
+template <int PDE, typename real>
+__device__ __forceinline__ vec4<real> channels_pde(const vec4<real>& s, real& d1, real& d2, real kap) {
+  vec4<real> in = channels_of(s, d1, d2);
+  if constexpr (PDE == PDE_ADR2) in.w = fma(kap * d2 * s.z, s.z, in.w);
+  return in;
+}
+template <int PDE, typename real>
+__device__ __forceinline__ vec4<real> preact_adjoint_pde(const vec4<real>& s, const vec4<real>& ob, real kap) {
+  vec4<real> zb = preact_adjoint(s, ob);
+  if constexpr (PDE == PDE_ADR2) {
+    const real a = s.x, d1 = real(1) - a * a, d2 = real(-2) * a * d1;
+    const real d3 = real(-2) * d1 * (real(1) - real(3) * a * a);
+    zb.x = fma(kap * d3 * s.z * s.z, ob.w, zb.x);
+    zb.z = fma(real(2) * d2 * kap * s.z, ob.w, zb.z);
+  }
+  return zb;
+}
+template <typename real, typename Coef> __device__ __forceinline__ real coef_kappa(const Coef&) { return real(0); }
+template <typename real> __device__ __forceinline__ real coef_kappa(const Adr2Arg<real>& a) { return a.kappa; }
 
 // ---------------------------------------------------------------------------------------------
 // Reverse sweep for one wave of 64 points.  Emits one partial-gradient row per wave:
@@ -426,9 +601,11 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
   real c1 = real(1), c2 = coef_nu<real>(nu);
   if (PDE == 1) { c1 = th[nd.n_net]; c2 = exp(th[nd.n_net + 1]); }
 
+  const real kap = coef_kappa<real>(nu);
   vec4<real> sb[2];
   real lt[3], dl[PDE == PDE_ADR_IDE ? 6 : 2];
-  if constexpr (PDE == PDE_ADR) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr<real>(nu));
+  if constexpr (PDE == PDE_ADR2) { sb[1] = vec4<real>{0, 0, 0, 0}; adr2_point_seeds<real>(sd, pt, O, tgt, nu, sb[0], lt); }
+  else if constexpr (PDE == PDE_ADR) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr<real>(nu));
   else if constexpr (PDE == PDE_ADR_VAR) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, nu.k, &nu, nu.kf);
   else if constexpr (pde_adr_robin(PDE)) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, nu.k, &nu);
   else if constexpr (PDE == PDE_ADR_IDE) point_seeds<real, PDE>(sd, pt, n_pad, O, tgt, c1, c2, sb, lt, dl, coef_adr_tail<real>(th + nd.n_net));
@@ -463,7 +640,7 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
     for (int k = 0; k < W; ++k) {
       const vec4<real> s = Sin[(size_t)k * s_pad];
       real d1, d2;
-      const vec4<real> in = channels_of(s, d1, d2);
+      const vec4<real> in = channels_pde<PDE>(s, d1, d2, kap);
       vec4<real> ob{0, 0, 0, 0};
 #pragma unroll
       for (int o = 0; o < 2; ++o) {
@@ -476,7 +653,7 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
           ob.x += sb[o].x * w; ob.y += sb[o].y * w; ob.z += sb[o].z * w; ob.w += sb[o].w * w;
         }
       }
-      Zcur[(size_t)k * s_pad + lp] = preact_adjoint(s, ob);
+      Zcur[(size_t)k * s_pad + lp] = preact_adjoint_pde<PDE>(s, ob, kap);
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) if (q * 64 + lane < W * NO) put(nd.off_w[H] + q * 64 + lane, keep[q]);
@@ -497,7 +674,7 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
         const int k = (k0 + kk < W) ? k0 + kk : W - 1;
         sk[kk] = Sin[(size_t)k * s_pad];
         real d1, d2;
-        in[kk] = channels_of(sk[kk], d1, d2);
+        in[kk] = channels_pde<PDE>(sk[kk], d1, d2, kap);
         acc[kk] = vec4<real>{0, 0, 0, 0};
         keep0[kk] = keep1[kk] = real(0);
       }
@@ -524,7 +701,7 @@ __global__ __launch_bounds__(64) void k_backward(NetDesc nd, SetDesc sd,
           const int o = nd.off_w[d] + (k0 + kk) * W;
           if (lane < W) put(o + lane, keep0[kk]);
           if (lane + 64 < W) put(o + lane + 64, keep1[kk]);
-          Znxt[(size_t)(k0 + kk) * s_pad + lp] = preact_adjoint(sk[kk], acc[kk]);
+          Znxt[(size_t)(k0 + kk) * s_pad + lp] = preact_adjoint_pde<PDE>(sk[kk], acc[kk], kap);
         }
       }
       if (k0 == 0) {
@@ -577,6 +754,19 @@ __global__ void k_residual(int first, int n, int n_pad, const vec4<real>* __rest
       r = r - nu.src[g];
     }
     f[i] = (double)r;
+  } else if constexpr (PDE == PDE_ADR2) {      // O's fourth entry is u_xx + kappa u_tt (k_forward_adr2)
+    const vec4<real> o = O[g];
+    real bz, r;
+    {
+#pragma clang fp contract(off)
+      bz = nu.b * o.z;
+    }
+    r = adr_residual(nu.k, vec4<real>{o.x, o.y, bz, o.w});
+    if (nu.src) {
+#pragma clang fp contract(off)
+      r = r - nu.src[g];
+    }
+    f[i] = (double)r;
   } else if constexpr (PDE == PDE_ADR_IDE) {
     f[i] = (double)adr_residual(coef_adr_tail<real>(th + n_net), O[g]);
   } else if (PDE == 2) {
@@ -601,6 +791,17 @@ __global__ void k_robin_residual(AdrRobinArg<real> rb, const vec4<real>* __restr
   if (j >= rb.n) return;
   const vec4<real> o = O[rb.first + j];
   out[j] = (double)(rb.ab[2 * j] * o.x + rb.ab[2 * j + 1] * o.y - tgt[rb.first + j]);
+}
+
+// the three-term wall residuals of PDE_ADR2, r_j = alpha_j u + beta_j u_x + gamma_j u_t - g_j
+template <typename real>
+__global__ void k_robin3_residual(Adr2Arg<real> rb, const vec4<real>* __restrict__ O, const real* __restrict__ tgt,
+                                 double* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= rb.n) return;
+  const vec4<real> o = O[rb.first + j];
+  const vec4<real> w = *reinterpret_cast<const vec4<real>*>(rb.ab + 4 * (size_t)j);
+  out[j] = (double)(fma(w.z, o.z, w.x * o.x + w.y * o.y) - tgt[rb.first + j]);
 }
 
 }  // namespace pinn

@@ -16,22 +16,24 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _REPO = os.path.dirname(os.path.dirname(_HERE))
 LIB_PATH = os.environ.get("PINN_HIP_LIB") or os.path.join(_HERE, "libpinn_hip.so")
-SOURCES = ["engine.hip", "fused20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_fused20d_kernel.h", "kernels_fused20d_reverse.h", "kernels_wide.h", "kernels_predict20.h",
+SOURCES = ["engine.hip", "fused20d_unit.hip", "adr2_20d_unit.hip", "fused20d_api.h", "fused20m_unit.hip", "fused20m_api.h", "kernels_generic.h", "kernels_fused20.h", "kernels_fused20m.h", "kernels_fused20d.h", "kernels_fused20d_kernel.h", "kernels_fused20d_reverse.h", "kernels_wide.h", "kernels_predict20.h",
            "kernels_disc.h", "kernels_sampling.h", "kernels_rad.h", "kernels_tile16.h", "kernels_tile16f.h", "kernels_xgmi.h", "kernels_optim.h", "wave.h", "devbuf.h", "pointsets.h", "optim_host.h"]
 HEADER = os.path.join(_REPO, "include", "pinn_hip.h")
 
 PDE_KINDS = {"burgers": 0, "burgers_ide": 1, "schrodinger": 2, "burgers_disc": 3, "burgers_disc_ide": 4, "adr": 5, "adr_ide": 6}
 # kinds added after the table above was pinned entry for entry (tests/test_adr_host.py): the discrete-time adr kind
 DISC_PDE_KINDS = {"adr_disc": 7, "adr_disc_ide": 8, "adrd_disc": 9}
+# ... and the adr equation with b u_t and u_xx + kappa u_tt as one Taylor channel (wave, telegraph, Klein-Gordon, Helmholtz)
+ADR2_PDE_KINDS = {"adr2": 10}
 
 
 def pde_kind(name):
-    """name -> enum value of include/pinn_hip.h (PDE_KINDS, DISC_PDE_KINDS); ValueError with the tables otherwise"""
-    if name in PDE_KINDS:
-        return PDE_KINDS[name]
-    if name in DISC_PDE_KINDS:
-        return DISC_PDE_KINDS[name]
-    raise ValueError("pde must be one of %s" % sorted(list(PDE_KINDS) + list(DISC_PDE_KINDS)))
+    """name -> enum value of include/pinn_hip.h (PDE_KINDS, DISC_PDE_KINDS, ADR2_PDE_KINDS); ValueError with the tables
+    otherwise"""
+    for table in (PDE_KINDS, DISC_PDE_KINDS, ADR2_PDE_KINDS):
+        if name in table:
+            return table[name]
+    raise ValueError("pde must be one of %s" % sorted(list(PDE_KINDS) + list(DISC_PDE_KINDS) + list(ADR2_PDE_KINDS)))
 
 
 DTYPES = {"f32": 0, "f64": 1, "float32": 0, "float64": 1}
@@ -40,6 +42,7 @@ ADR_COEFF_NAMES = ("a0", "a1", "nu", "r1", "r2", "r3")     # order of the coeffi
 
 
 ADRD_COEFF_NAMES = ADR_COEFF_NAMES + ("d3",)               # "adrd_disc": the dispersion coefficient behind the six
+ADR2_COEFF_NAMES = ADR_COEFF_NAMES + ("b", "kappa")        # "adr2": b u_t and -nu (u_xx + kappa u_tt)
 
 
 def adr_trainable_mask(names_or_mask, names=ADR_COEFF_NAMES):
@@ -67,7 +70,8 @@ class PinnNativeError(RuntimeError):
 
 COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC",
                 "-mllvm", "-amdgpu-kernarg-preload-count=16"]   # leading argument dwords arrive in SGPRs (no s_load round trip)
-UNITS = [("engine.hip", []), ("fused20d_unit.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("fused20m_unit.hip", [])]
+UNITS = [("engine.hip", []), ("fused20d_unit.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("fused20m_unit.hip", []),
+         ("adr2_20d_unit.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"])]      # k_adr2_20d: the text of k_fused20d, its flags
 
 
 def _build_tag():
@@ -303,6 +307,9 @@ _SIGNATURES = {
     "pinn_set_robin": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64,
                                       ctypes.c_int64]),
     "pinn_robin_residual": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
+    # three-term wall points of the adr2 kind
+    "pinn_set_robin3": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                       ctypes.c_int64, ctypes.c_int64]),
     # source term of the adr kind (include/pinn_hip.h: pinn_set_source)
     "pinn_set_source": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
     # coefficient fields of the adr kind (include/pinn_hip.h: pinn_set_coef_fields)
@@ -597,13 +604,24 @@ class Engine(object):
         """Robin points of the adr kind: alpha u + beta u_x = g at the rows (x, t) of X_w; alpha, beta and g are arrays of one
         value per point or scalars (broadcast).  (1, 0, g) is a Dirichlet value, (0, 1, g) a flux, (h, 1, g) a Robin wall.
         An empty X_w removes the class.  Their part of the loss is added to terms[2] of loss_grad."""
+        X_w, cols, n = self._robin_columns(X_w, (("alpha", alpha), ("beta", beta), ("g", g)), n_total)
+        if np.any((cols[0] == 0.0) & (cols[1] == 0.0)):
+            raise ValueError("a Robin point with alpha = beta = 0 constrains nothing")
+        self._check(self._lib.pinn_set_robin(self._h, _dp(X_w), _dp(cols[0]), _dp(cols[1]), _dp(cols[2]), n,
+                                             n if n_total is None else int(n_total)))
+        self.n_w = n
+
+    @staticmethod
+    def _robin_columns(X_w, named, n_total):
+        """set_robin's and set_robin3's view of their arguments: X_w as [n, 2], every named column broadcast to [n], all
+        finite -> (X_w, columns, n)"""
         X_w = _f64(X_w)
         if X_w.size % 2 or (X_w.ndim > 1 and X_w.shape[-1] != 2):
             raise ValueError("X_w must be [n, 2] rows (x, t), got shape %s" % (X_w.shape,))
         X_w = np.ascontiguousarray(X_w.reshape(-1, 2))
         n = X_w.shape[0]
         cols = []
-        for name, v in (("alpha", alpha), ("beta", beta), ("g", g)):
+        for name, v in named:
             v = _f64(v)
             if v.size != 1 and v.size != n:
                 raise ValueError("%s must be a scalar or hold one value per Robin point (%d), got %d" % (name, n, v.size))
@@ -613,12 +631,19 @@ class Engine(object):
             cols.append(v)
         if not np.all(np.isfinite(X_w)):
             raise ValueError("X_w must be finite")
-        if np.any((cols[0] == 0.0) & (cols[1] == 0.0)):
-            raise ValueError("a Robin point with alpha = beta = 0 constrains nothing")
         if n_total is not None and int(n_total) < n:
             raise ValueError("n_total (%d) is smaller than the local count (%d)" % (int(n_total), n))
-        self._check(self._lib.pinn_set_robin(self._h, _dp(X_w), _dp(cols[0]), _dp(cols[1]), _dp(cols[2]), n,
-                                             n if n_total is None else int(n_total)))
+        return X_w, cols, n
+
+    def set_robin3(self, X_w, alpha, beta, gamma, g, n_total=None):
+        """Three-term wall points of the adr2 kind: alpha u + beta u_x + gamma u_t = g at the rows (x, t) of X_w, the arguments
+        as set_robin's.  (0, 0, 1, v0) is an initial velocity (or a Neumann wall y = const of a 2-D problem), (0, c, 1, 0)
+        the absorbing wall u_t + c u_x = 0.  An empty X_w removes the class."""
+        X_w, cols, n = self._robin_columns(X_w, (("alpha", alpha), ("beta", beta), ("gamma", gamma), ("g", g)), n_total)
+        if np.any((cols[0] == 0.0) & (cols[1] == 0.0) & (cols[2] == 0.0)):
+            raise ValueError("a wall point with alpha = beta = gamma = 0 constrains nothing")
+        self._check(self._lib.pinn_set_robin3(self._h, _dp(X_w), _dp(cols[0]), _dp(cols[1]), _dp(cols[2]), _dp(cols[3]), n,
+                                              n if n_total is None else int(n_total)))
         self.n_w = n
 
     def set_source(self, s):
@@ -685,8 +710,8 @@ class Engine(object):
     def get_pde_params(self):
         """the current raw equation parameters: six coefficients (a0, a1, nu, r1, r2, r3) for "adr", "adr_disc", "adr_ide"
         and "adr_disc_ide" (the last two: the trained values, nu = exp of the stored log nu), seven (.., d3) for "adrd_disc"
-        (nu = 0 where it was set to 0), [nu] otherwise"""
-        p = np.empty(7 if self.pde == "adrd_disc" else 6 if self.pde in ("adr", "adr_ide", "adr_disc", "adr_disc_ide") else 1,
+        (nu = 0 where it was set to 0), eight (.., b, kappa) for "adr2", [nu] otherwise"""
+        p = np.empty(8 if self.pde == "adr2" else 7 if self.pde == "adrd_disc" else 6 if self.pde in ("adr", "adr_ide", "adr_disc", "adr_disc_ide") else 1,
                      dtype=np.float64)
         self._check(self._lib.pinn_get_pde_params(self._h, _dp(p), p.size))
         return p

@@ -15,7 +15,9 @@ It names one of the engine's residual kinds instead (`pde="burgers" | "burgers_i
 "adrd_disc" the same family with a dispersion term d3 U_xxx (seven coefficients; KdV), "adr_disc_ide" the same model with the coefficients named in hp["adr_trainable"] learned from two snapshots, see
 1d-allen-cahn/ide_disc_allen_cahn.py; "adr" is u_t + (a0 + a1 u) u_x - nu u_xx + r1 u + r2 u^2 + r3 u^3 = 0
 with fixed coefficients the subclass hands to `self._engine.set_pde_params(a0, a1, nu, r1, r2, r3)`, "adr_ide" the same
-equation with the coefficients named in hp["adr_trainable"] learned from the data, see _adr_ide_options) and the engine evaluates forward, u_t/u_x/u_xx, residual, loss and the flat
+equation with the coefficients named in hp["adr_trainable"] learned from the data, see _adr_ide_options; "adr2" is
+b u_t + (a0 + a1 u) u_x - nu (u_xx + kappa u_tt) + r1 u + r2 u^2 + r3 u^3 = s with the eight coefficients of hp["adr2"] -- wave,
+telegraph, Klein-Gordon, and Poisson / Helmholtz with t read as y -- see _adr2_options, _set_robin3) and the engine evaluates forward, u_t/u_x/u_xx, residual, loss and the flat
 gradient on the GPU (csrc/).  Extra, optional hp keys: "dtype" ("f64" default = the reference's
 arithmetic, neuralnetwork.py:24-26 | "f32" = the throughput mode north_star sanctions) for the
 kernel arithmetic, "device" (HIP ordinal), "nt_guard" (see nt_optimization), "resample_every" / "resample" / "rad_*"
@@ -197,6 +199,32 @@ def _adr_ide_options(hp):
 ADRD_NAMES = ADR_NAMES + ("d3",)
 
 
+ADR2_NAMES = ADR_NAMES + ("b", "kappa")
+
+
+def _adr2_options(hp):
+    """pde "adr2" (b u_t + (a0 + a1 u) u_x - nu (u_xx + kappa u_tt) + r1 u + r2 u^2 + r3 u^3 = s): hp["adr2"] = the eight
+    coefficients, as a list [a0, a1, nu, r1, r2, r3, b, kappa] or as a dict of names (those not named keep a new context's
+    value: Burgers', b = 1, kappa = 0).  All finite, any sign.  -> the eight values."""
+    base = [0.0, 1.0, 0.01 / np.pi, 0.0, 0.0, 0.0, 1.0, 0.0]
+    given = hp.get("adr2", {})
+    try:
+        if isinstance(given, dict):
+            for n in given:
+                if n not in ADR2_NAMES:
+                    raise ValueError('hp["adr2"]: unknown coefficient %r; choose from %s' % (n, ", ".join(ADR2_NAMES)))
+            vals = [float(given.get(n, base[i])) for i, n in enumerate(ADR2_NAMES)]
+        else:
+            vals = [float(v) for v in given]
+    except TypeError:
+        raise ValueError('hp["adr2"] must be a dict of names from %s or eight numbers (got %r)' % (", ".join(ADR2_NAMES), given))
+    if len(vals) != 8:
+        raise ValueError('hp["adr2"] must be eight numbers [a0, a1, nu, r1, r2, r3, b, kappa] (got %r)' % (given,))
+    if not all(np.isfinite(v) for v in vals):
+        raise ValueError('hp["adr2"] must be eight finite numbers [a0, a1, nu, r1, r2, r3, b, kappa] (got %r)' % (given,))
+    return tuple(vals)
+
+
 def _adrd_options(hp):
     """pde "adrd_disc" (the discrete-time adr family with a d3 U_xxx term): hp["adr_trainable"] = names from a0, a1, nu, r1, r2,
     r3, d3 (default: none), hp["adr_init"] = the seven raw start values (default Burgers' and d3 = 0).  nu = 0 is allowed (KdV
@@ -285,6 +313,7 @@ class NeuralNetwork(object):
         self._pw = _pw_options(hp, self.pde)
         self._adr_ide = (_adrd_options(hp) if self.pde == "adrd_disc" else
                          _adr_ide_options(hp) if self.pde in ("adr_ide", "adr_disc_ide") else None)
+        self._adr2 = _adr2_options(hp) if self.pde == "adr2" else None
 
         # L-BFGS configuration, same fields as the reference (neuralnetwork.py:13-17)
         self.nt_config = Struct()
@@ -304,10 +333,10 @@ class NeuralNetwork(object):
 
         # one rank of a torchrun launch = one shard of the point sets on GPU LOCAL_RANK (module docstring); the
         # discrete-time models hold <= 256 points and stay replicated
-        if self.pde in ("adr", "adr_ide") and parallel.env_world()[0] > 1 and bool(hp.get("data_parallel", True)):
+        if self.pde in ("adr", "adr_ide", "adr2") and parallel.env_world()[0] > 1 and bool(hp.get("data_parallel", True)):
             raise ValueError('pde "%s": a data-parallel launch (world > 1) is not supported for this kind; run one process, '
                              'or set hp["data_parallel"] = false for independent replicas' % self.pde)
-        self._dp = None if self.pde.startswith("burgers_disc") or self.pde in ("adr_disc", "adr_disc_ide", "adrd_disc") else parallel.from_env(bool(hp.get("data_parallel", True)))
+        self._dp = None if self.pde.startswith("burgers_disc") or self.pde in ("adr_disc", "adr_disc_ide", "adrd_disc", "adr2") else parallel.from_env(bool(hp.get("data_parallel", True)))
         self.is_root = parallel.is_root()
         world, _, local_rank = parallel.env_world()
         device = hp.get("device", os.environ.get("PINN_DEVICE", local_rank if world > 1 else 0))
@@ -330,6 +359,8 @@ class NeuralNetwork(object):
 
         if self.pde == "adrd_disc":                  # the params first (nu = 0 is a flag of the context), then the weights
             self._engine.set_pde_params(*self._adr_ide[1])
+        if self._adr2:
+            self._engine.set_pde_params(*self._adr2)
         self._engine.set_weights(self._initial_weights(hp))
         if self._adr_ide:
             self._engine.set_pde_trainable(list(self._adr_ide[0]))
@@ -378,7 +409,7 @@ class NeuralNetwork(object):
         broadcast): Dirichlet (1, 0, g), Neumann (0, 1, g), Robin (h, 1, g).  Their mean square is added to the boundary
         part of the loss.  One device; not combined with hp["point_weights"].  Redraws of the collocation set
         (hp["resample"]) leave them in place."""
-        if self.pde != "adr":
+        if self.pde not in ("adr", "adr2"):
             raise ValueError('_set_robin: Robin points are for the "adr" kind; the %s model is not supported' % self.pde)
         if self._pw:
             raise ValueError('_set_robin: Robin points are not combined with hp["point_weights"] (the weights cover data, '
@@ -387,13 +418,21 @@ class NeuralNetwork(object):
             raise ValueError('_set_robin: Robin points run on one device; a data-parallel launch is not supported')
         self._engine.set_robin(X_w, alpha, beta, g)
 
+    def _set_robin3(self, X_w, alpha, beta, gamma, g):
+        """Three-term wall points of the "adr2" kind, alpha u + beta u_x + gamma u_t = g at the rows (x, t) of X_w
+        (Engine.set_robin3; scalars broadcast): an initial velocity (0, 0, 1, v0), a Neumann wall y = const of a 2-D problem,
+        the absorbing wall (0, c, 1, 0).  Their mean square is added to the boundary part of the loss.  One device."""
+        if self.pde != "adr2":
+            raise ValueError('_set_robin3: three-term wall points are for the "adr2" kind; the %s model is not supported' % self.pde)
+        self._engine.set_robin3(X_w, alpha, beta, gamma, g)
+
     def _set_source(self, s):
         """Source term of the "adr" kind (Engine.set_source): f = N[u] - s at the collocation points.  s is an array of one
         value per collocation point (call _set_collocation first), or a callable taking X [n, 2] = (x, t) and returning [n]
         -- then every device redraw of the collocation set (hp["resample_every"] > 0, Latin hypercube) is followed by
         get_collocation() and set_source(s(X)).  An array cannot follow a redraw.  None removes the source.  One device; not
         combined with hp["resample"] = "rad" (the pool's residuals would lack s) or hp["point_weights"]."""
-        if self.pde != "adr":
+        if self.pde not in ("adr", "adr2"):
             raise ValueError('_set_source: a source term is for the "adr" kind; the %s model is not supported' % self.pde)
         if self._resample == "rad":
             raise ValueError('_set_source: a source term is not combined with hp["resample"] = "rad" (the adaptive draw\'s '
